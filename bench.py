@@ -451,6 +451,29 @@ def mesh_distance(v, rv, extent):
             "vertices": [int(len(v)), int(len(rv))]}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, vertices, faces):
+    """What the timed path returned in its last step, as .npy files under `path`: vertices (float32, as computed) and faces
+    (float64: every index exact).  A mesh over DUMP_BYTES is written as a fixed, seeded sample of rows of each array (the same rows
+    for the same shapes), with the row indices beside it; mesh_shape.npy holds the full row counts either way."""
+    os.makedirs(path, exist_ok=True)
+    v = vertices.detach().cpu().numpy().astype(np.float32)
+    f = faces.detach().cpu().numpy().astype(np.float64)
+    np.save(os.path.join(path, "mesh_shape.npy"), np.array([v.shape[0], f.shape[0]], np.float64))
+    if v.nbytes + f.nbytes <= DUMP_BYTES - (1 << 20):
+        np.save(os.path.join(path, "vertices.npy"), v)
+        np.save(os.path.join(path, "faces.npy"), f)
+        return
+    rng = np.random.default_rng(0)
+    rows = (DUMP_BYTES // 2) // (v.itemsize * 3 + 8 + f.itemsize * 3 + 8)   # the same row count for both arrays
+    for name, a in (("vertices", v), ("faces", f)):
+        idx = np.sort(rng.choice(a.shape[0], min(rows, a.shape[0]), replace=False))
+        np.save(os.path.join(path, name + ".npy"), a[idx])
+        np.save(os.path.join(path, name + "_rows.npy"), idx.astype(np.float64))
+
+
 def _median_time(fn, warm=1, n=3):
     for _ in range(warm):
         fn()
@@ -723,7 +746,11 @@ def main():
                          "check alone)")
     ap.add_argument("--no-decoder-filter", action="store_true",
                     help="every lattice point through the six-product kernel (TSR(decoder_filter=False), round 4's path) as the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the mesh of the last one (vertices, faces) to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     global DECODER_PRECISION
     DECODER_PRECISION = args.decoder_precision
 
@@ -789,6 +816,8 @@ def main():
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
     elapsed = parallel.max_over_ranks(elapsed, device if backend == "nccl" else "cpu")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, v, f)
 
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     if rank == 0:

@@ -10,6 +10,9 @@ Run in the build container with the interpreter that has scikit-image installed:
 tests/golden/mc_skimage.npz holding input volumes AND skimage.measure.marching_cubes(vol, 0.0)
 outputs (verts float32, faces int32), plus the reference's own post-processing of them
 (MarchingCubeHelper.forward: faces[:, [1,0,2]], verts / (R-1)).
+
+It also writes tests/golden/mc_skimage_fuzz.npz: seeded random volumes and single cells with
+skimage's output for each (verts float32, faces int32), or the name of the exception it raised.
 """
 import os
 import warnings
@@ -50,6 +53,31 @@ def volumes():
     return vols
 
 
+def fuzz_volumes():
+    rng = np.random.default_rng(20261015)
+    vols = {}
+    for i in range(12):
+        vols["r%d" % i] = rng.standard_normal(tuple(rng.integers(2, 10, 3))).astype(np.float32)
+    for i in range(600):
+        vols["c%d" % i] = rng.standard_normal((2, 2, 2)).astype(np.float32)
+    for i in range(200):
+        vols["i%d" % i] = rng.integers(-3, 4, (2, 2, 2)).astype(np.float32)
+    return vols
+
+
+def fuzz():
+    out = {"skimage_version": np.array(skimage.__version__)}
+    for k, v in fuzz_volumes().items():
+        out[k + "_vol"] = v
+        try:
+            verts, faces, _, _ = measure.marching_cubes(v, 0.0)
+            out[k + "_verts"] = verts.astype(np.float32)
+            out[k + "_faces"] = faces.astype(np.int32)
+        except Exception as e:
+            out[k + "_error"] = np.array(type(e).__name__)
+    np.savez_compressed(os.path.join(HERE, "mc_skimage_fuzz.npz"), **out)
+
+
 def main():
     out = {"skimage_version": np.array(skimage.__version__)}
     for k, v in volumes().items():
@@ -66,6 +94,7 @@ def main():
             print(name, "no error")
         except Exception as e:
             print(name, type(e).__name__, e)
+    fuzz()
 
 
 if __name__ == "__main__":
