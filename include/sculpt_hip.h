@@ -218,14 +218,19 @@ int sculpt_grid_decode(const void *mlp_packed, int n_hidden_64, int R, int x_beg
 #define SCULPT_ERR_MC_LEVEL 11
 #define SCULPT_ERR_MC_EMPTY 12
 #define SCULPT_ERR_MC_NAN 13 /* the volume contains NaN (e.g. a 16-bit split density mode left its range) */
-#define SCULPT_ERR_MC_WORKSPACE 14 /* more active cells than the workspace's record pool holds: repeat with a larger one (below) */
+#define SCULPT_ERR_MC_WORKSPACE 14 /* more active cells than the workspace's pool is named for: repeat once with that many (below) */
 
-/* Workspace: per-row arrays + 8 bytes per ACTIVE cell (a cell whose corner signs differ) in a record pool.
- * sculpt_mc_workspace_bytes sizes the pool for one active cell per 8 cells (a closed surface at 256^3 has ~1 per 17): 23 MB at
- * 256^3, 181 MB at 512^3; sculpt_mc_workspace_bytes_for for max_active_cells of them (<= 0: the default).  A count phase that runs
- * out of pool still returns the right totals, with SCULPT_ERR_MC_WORKSPACE and -- through sculpt_mc_count_read_ex -- the number
- * of active cells; the caller allocates sculpt_mc_workspace_bytes_for(.., that many) and repeats the count with
- * sculpt_mc_count_launch_for(.., max_active_cells = that many, ..).  (The emit phase after an overflow writes nothing.) */
+/* Workspace: per-row arrays + a record pool of 8 bytes per ACTIVE cell (a cell whose corner signs differ).
+ * A pool is NAMED for a capacity of c records: max_active_cells of sculpt_mc_workspace_bytes_for / sculpt_mc_count_launch_for
+ * (<= 0: the default, one active cell per 8 cells, at least 65 536; a closed surface at 256^3 has ~1 per 17), clamped to the
+ * number of cells.  It occupies at most 2c records (up to 64 unevenly loaded parts of c records in all + a spill run of c).
+ * sculpt_mc_workspace_bytes is the default: 39 MB at 256^3, 315 MB at 512^3.
+ * Guarantee: a count phase with at most c active cells never runs out of pool -- in every count form (any level, classic
+ * tables, sign planes, slab flags) and whatever the surface's spread.  A count phase with more active cells than that may run
+ * out; it still returns the right totals, with SCULPT_ERR_MC_WORKSPACE and -- through sculpt_mc_count_read_ex -- the number of
+ * active cells n.  The caller allocates sculpt_mc_workspace_bytes_for(.., n) and repeats the count ONCE with
+ * sculpt_mc_count_launch_for(.., max_active_cells = n, ..): that count succeeds.  The error text names n and c (as
+ * "rec_capacity" of the workspace).  (The emit phase after an overflow writes nothing.) */
 size_t sculpt_mc_workspace_bytes(int n0, int n1, int n2);
 size_t sculpt_mc_workspace_bytes_for(int n0, int n1, int n2, int64_t max_active_cells);
 int sculpt_mc_count(const float *vol, int n0, int n1, int n2, double level, unsigned flags,

@@ -21,9 +21,10 @@
 //           rank of e among the owner's vertices, read from the owner's record (a neighbour cell at offset {0,-1}^3, found
 //           through the rows' chunk tables, in LDS): no lattice-wide edge -> id map (round 6; it was int32 [R^3][4], 268 MB at 256^3)
 // Workspace: per-row arrays (counts, offsets, 256-bit active masks) + 8 bytes per ACTIVE cell in a pool whose capacity the caller
-// chooses (sculpt_mc_workspace_bytes_for); a count pass that runs out of pool reports SCULPT_ERR_MC_WORKSPACE and the number of
-// active cells, and the caller repeats it with a larger workspace.  23 MB at 256^3 and 181 MB at 512^3 with the default pool
-// (one active cell per 8 cells), where the dense records + map of round 5 took 403 MB and 3.2 GB.
+// chooses (sculpt_mc_workspace_bytes_for; parts + a spill run, see CellRec): a count pass with at most that many active cells
+// never runs out of pool; one with more reports SCULPT_ERR_MC_WORKSPACE and the number of active cells, and the caller repeats
+// it once with a workspace for that many.  39 MB at 256^3 and 315 MB at 512^3 with the default pool (one active cell per 8
+// cells), where the dense records + map of round 5 took 403 MB and 3.2 GB.
 #include <float.h>
 #include <math.h>
 #include <string.h>
@@ -548,13 +549,18 @@ static_assert(sizeof(McHeader) == 64, "header is 64 bytes");
 // are consecutive, in cell order, in the pool; the brick that classified the row took the space with one atomic add.  The pool is
 // split into up to MC_SUBPOOLS equal parts with a counter each (a brick takes from the part its hashed index names): 13 000 bricks
 // adding to ONE counter serialise in the L2 (classify pass 71 -> 116 us with two such counters), 200 per counter on 64 different
-// lines do not.  A pool that holds every cell of the grid is never split (it cannot overflow, whatever the spread).
+// lines do not.  The parts are uneven (a brick takes its whole run, up to 4096 records, from one of them): a brick that does not
+// fit its part takes one contiguous range of a SPILL run of as many records as the parts hold together, with a counter of its own.
+// Only bricks with active cells add to that counter, so it never passes the number of active cells: a pool named for c records
+// (c parts + c spill) cannot overflow with at most c active cells, whatever the spread.  A pool that holds every cell of the grid
+// -- or a grid of too few bricks to split -- is one part and needs no spill run.
 //   w0 = x_local | len << 8 | classic << 15 | ofs << 16      (the chosen tiling: no re-classification later)
 //   w1 = exclusive prefix inside the block of ntri (bits 0-11) and of the owned vertices (bits 16-27), and -- for a cell with
 //        x, y, z > 0 on the Lewiner tables -- the ranks of the vertices on edges 5 / 6 / 10 among the cell's own (bits 12-13 /
 //        14-15 / 28-29; see LUT_ROWRANK); bit 30 = the classic flag again: w1 alone names an interior owner's vertices
 struct CellRec { unsigned w0, w1; };
 static constexpr int MC_SUBPOOLS = 64, MC_CTR_STRIDE = 16;   // one counter per 64-byte line
+static constexpr int MC_SPILL_CTR = MC_SUBPOOLS * MC_CTR_STRIDE, MC_NCTR = MC_SPILL_CTR + MC_CTR_STRIDE;   // + the spill counter
 __device__ __forceinline__ unsigned rec_tri(const CellRec &r) { return r.w1 & 0xfffu; }
 __device__ __forceinline__ unsigned rec_vert(const CellRec &r) { return (r.w1 >> 16) & 0xfffu; }
 __device__ __forceinline__ unsigned rank_bits_to_w1(unsigned rk) { return ((rk & 15u) << 12) | (((rk >> 4) & 3u) << 28); }
@@ -581,6 +587,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_classify_brick_kernel(const float
                                                                      CellRec *__restrict__ recs,
                                                                      RowChunk *__restrict__ chunks,
                                                                      unsigned *__restrict__ pool_ctr, int nsub, unsigned sub_cap,
+                                                                     unsigned spill_cap,
                                                                      int *__restrict__ block_counts,
                                                                      int *__restrict__ block_nact,
                                                                      float2 *__restrict__ block_minmax,
@@ -715,7 +722,12 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_classify_brick_kernel(const float
         if (tid == 0) {       // this brick's piece of the record pool
             const unsigned sub = (((unsigned)brick * 2654435761u) >> 12) % (unsigned)nsub;
             unsigned at = atomicAdd(&pool_ctr[sub * MC_CTR_STRIDE], (unsigned)total_active);
-            if (at + (unsigned)total_active > sub_cap) { hdr->pool_overflow = 1u; at = ~0u; } else at += sub * sub_cap;
+            if (at + (unsigned)total_active <= sub_cap) {
+                at += sub * sub_cap;
+            } else {   // the part is full: a range of the spill run after the parts
+                at = atomicAdd(&pool_ctr[MC_SPILL_CTR], (unsigned)total_active);
+                if (at + (unsigned)total_active > spill_cap) { hdr->pool_overflow = 1u; at = ~0u; } else at += (unsigned)nsub * sub_cap;
+            }
             s_pool = at;
         }
         if (use_planes) {     // this brick needs its values after all
@@ -1259,8 +1271,9 @@ struct WsLayout {
     size_t off_counts, off_nact, off_minmax, off_tri, off_vert, off_gtot, off_gmm, off_recs, off_chunks, off_ctr, off_aofs, off_gact, total;
     int ngroups;
     int nblocks;
-    long rec_capacity, nbricks;
+    long rec_capacity, nbricks;   // rec_capacity: the records the pool is named for (what it holds whatever the spread)
     int nsub;                 // parts of the record pool (one counter each)
+    long sub_cap, spill_cap;  // records of one part, of the spill run after the nsub parts (0 for a pool of one part)
 };
 // records of the default pool: one active cell per 8 cells (a closed surface at 256^3 has ~1 per 17), at least 65 536
 static long default_rec_capacity(const Grid &g) { return std::min(g.ncells, std::max(g.ncells / 8, 65536L)); }
@@ -1282,10 +1295,13 @@ static WsLayout ws_layout(const Grid &g, long rec_capacity) {
     w.nbricks = (long)cdiv(g.c2, MC_BLOCK) * cdiv(g.c1, MC_TY) * cdiv(g.c0, MC_TZ);
     w.off_aofs = o;   o = al(o + sizeof(unsigned) * w.nblocks);
     w.off_gact = o;   o = al(o + sizeof(unsigned) * w.ngroups);
-    w.rec_capacity = std::max(1L, std::min(rec_capacity, g.ncells));
+    // (parts + spill run: at most 2 * rec_capacity records, addressed with 32-bit indices)
+    w.rec_capacity = std::max(1L, std::min(std::min(rec_capacity, g.ncells), 0x7fffffffL));
     w.nsub = w.rec_capacity >= g.ncells ? 1 : (int)std::max(1L, std::min<long>(MC_SUBPOOLS, w.nbricks / 16));
-    w.off_ctr = o;    o = al(o + sizeof(unsigned) * MC_SUBPOOLS * MC_CTR_STRIDE);
-    w.off_recs = o;   o = al(o + sizeof(CellRec) * (size_t)w.rec_capacity);
+    w.sub_cap = w.rec_capacity / w.nsub;
+    w.spill_cap = w.nsub > 1 ? w.rec_capacity : 0;
+    w.off_ctr = o;    o = al(o + sizeof(unsigned) * MC_NCTR);
+    w.off_recs = o;   o = al(o + sizeof(CellRec) * (size_t)(w.nsub * w.sub_cap + w.spill_cap));
     w.total = o;
     return w;
 }
@@ -1324,7 +1340,7 @@ static int mc_count_launch(const float *vol, const unsigned *signbits, int sign_
     init.min_ord = 0xffffffffu;
     init.max_ord = 0u;
     init.rec_capacity = (unsigned)std::min<long>(w.rec_capacity, 0xffffffffL);
-    SC_HIP(hipMemsetAsync(ws + w.off_ctr, 0, sizeof(unsigned) * MC_SUBPOOLS * MC_CTR_STRIDE, st));
+    SC_HIP(hipMemsetAsync(ws + w.off_ctr, 0, sizeof(unsigned) * MC_NCTR, st));
     SC_HIP(hipMemcpyAsync(hdr, &init, sizeof(init), hipMemcpyHostToDevice, st));
     const int classic = (flags & SCULPT_MC_USE_CLASSIC) ? 1 : 0;
     // float f > double level  <=>  f > (largest float <= level): the sign pass needs no fp64
@@ -1334,7 +1350,7 @@ static int mc_count_launch(const float *vol, const unsigned *signbits, int sign_
         const int bpr = cdiv(g.c2, MC_BLOCK), nby = cdiv(g.c1, MC_TY), nbz = cdiv(g.c0, MC_TZ);
         hipLaunchKernelGGL(mc_classify_brick_kernel, dim3(bpr * nby * nbz), dim3(MC_BLOCK), 0, st, vol, g, levelf, level, classic,
                            nby, bpr, reinterpret_cast<CellRec *>(ws + w.off_recs), reinterpret_cast<RowChunk *>(ws + w.off_chunks),
-                           reinterpret_cast<unsigned *>(ws + w.off_ctr), w.nsub, (unsigned)(w.rec_capacity / w.nsub),
+                           reinterpret_cast<unsigned *>(ws + w.off_ctr), w.nsub, (unsigned)w.sub_cap, (unsigned)w.spill_cap,
                            reinterpret_cast<int *>(ws + w.off_counts),
                            reinterpret_cast<int *>(ws + w.off_nact), reinterpret_cast<float2 *>(ws + w.off_minmax), hdr, signbits, sign_ld);
     }

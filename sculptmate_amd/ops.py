@@ -303,7 +303,7 @@ def marching_cubes(vol, level=0.0, reference_order=False, vert_div=1.0, vert_mul
     assert vol.dim() == 3
     n0, n1, n2 = vol.shape
     # The workspace holds 8 bytes per ACTIVE cell in a record pool (default: one active cell per 8 cells).  A shape whose count
-    # phase ran out of pool once (SCULPT_ERR_MC_WORKSPACE: a noisy volume) keeps the larger capacity.
+    # phase ran out of pool once (SCULPT_ERR_MC_WORKSPACE: a noisy volume) keeps a larger capacity.
     rec_cap = _MC_REC_CAPACITY.get((vol.device, n0, n1, n2), 0)
     ws = _workspace(("mc", vol.device), lib.sculpt_mc_workspace_bytes_for(n0, n1, n2, rec_cap), vol.device)
     flags = 0
@@ -349,12 +349,13 @@ def marching_cubes(vol, level=0.0, reference_order=False, vert_div=1.0, vert_mul
     nact = ctypes.c_int64()
     rc = lib.sculpt_mc_count_read_ex(n0, n1, n2, float(level), rflags, _ptr(ws), ctypes.byref(nv), ctypes.byref(nf),
                                      ctypes.cast(mm, ctypes.c_void_p), ctypes.byref(nact), _stream())
-    while rc == _lib.ERR_MC_WORKSPACE:
-        # more active cells than the pool holds (the speculative emit above wrote nothing): a larger workspace, the count again.
-        # (The pool is handed out in up to 64 parts: half as much again covers their uneven loads; a pool that holds every cell
-        # of the grid cannot overflow, so the loop ends.)
-        rec_cap = max(2 * rec_cap, int(nact.value + nact.value // 2 + 4096))
-        _MC_REC_CAPACITY[(vol.device, n0, n1, n2)] = rec_cap
+    if rc == _lib.ERR_MC_WORKSPACE:
+        # more active cells than the pool holds (the speculative emit above wrote nothing).  A pool named for at least that many
+        # cannot overflow (sculpt_hip.h), so the count runs once more in such a workspace; a second overflow raises (check below).
+        # Later calls of the shape start with that capacity and some headroom (the cache only grows).
+        rec_cap = max(int(nact.value), rec_cap)
+        key_rc = (vol.device, n0, n1, n2)
+        _MC_REC_CAPACITY[key_rc] = max(_MC_REC_CAPACITY.get(key_rc, 0), rec_cap + rec_cap // 4)
         ws = _workspace(("mc", vol.device), lib.sculpt_mc_workspace_bytes_for(n0, n1, n2, rec_cap), vol.device)
         cap = None
         launch_count()

@@ -307,6 +307,206 @@ def test_workspace_is_a_record_pool_and_overflow_is_reported_then_retried(cuda):
         ops._MC_REC_CAPACITY.pop(key, None)
 
 
+
+# ------------------------------------------------------------------------------------------------- the record-pool protocol
+# sculpt_hip.h: a count phase with more active cells than its pool is named for returns the right totals, SCULPT_ERR_MC_WORKSPACE
+# and the number n of active cells; a count into sculpt_mc_workspace_bytes_for(.., n) with max_active_cells = n then succeeds --
+# whatever the spread of the active cells over the pool's parts (one brick of 4 x 4 x 256 cells takes up to 4096 records at once).
+def _lin(n):
+    return np.linspace(-1.0, 1.0, n, dtype=np.float32)
+
+
+def _sphere(n, r=0.6):
+    z, y, x = np.meshgrid(_lin(n), _lin(n), _lin(n), indexing="ij")
+    return (r - np.sqrt(x * x + y * y + z * z)).astype(np.float32)
+
+
+def _pool_volume(name):
+    """Deterministic volumes: dense noise, sparse closed surfaces (few bricks hold all the records), ragged multi-segment rows."""
+    if name.startswith("noise"):
+        shape, seed = {"noise24": ((24, 25, 26), 11), "noise64": ((64, 64, 64), 4), "noise9x10x300": ((9, 10, 300), 5),
+                       "noise40x3x520": ((40, 3, 520), 23), "noise66x37x700": ((66, 37, 700), 6)}[name]
+        return np.random.default_rng(seed).standard_normal(shape).astype(np.float32)
+    if name == "sphere128":
+        return _sphere(128)
+    if name == "noisy_sphere128":
+        return (_sphere(128) + np.float32(0.2) * np.random.default_rng(5).standard_normal((128,) * 3).astype(np.float32)).astype(np.float32)
+    if name == "sphere256":
+        return _sphere(256)
+    if name == "cylinder":   # axis along the fastest axis: the surface crosses few bricks, each of them densely
+        z, y = np.meshgrid(_lin(256), _lin(256), indexing="ij")
+        return np.broadcast_to((0.6 - np.sqrt(z * z + y * y))[:, :, None], (256, 256, 64)).astype(np.float32)
+    if name == "sphere9x10x300":
+        z, y, x = np.meshgrid(_lin(9), _lin(10), _lin(300), indexing="ij")
+        return (0.8 - np.sqrt(x * x + y * y + z * z)).astype(np.float32)
+    raise KeyError(name)
+
+
+class _Pool:
+    """The count phase through the C ABI into a workspace named for a given number of records."""
+
+    def __init__(self, cuda, vol_np):
+        import ctypes
+
+        from sculptmate_amd import _lib
+
+        self.ct, self.L, self.lib = ctypes, _lib, _lib.lib
+        self.cuda, self.shape = cuda, vol_np.shape
+        self.vol = torch.from_numpy(np.ascontiguousarray(vol_np)).to(cuda)
+        self.st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def count(self, cap, level=0.0, flags=0, planes=None):
+        ct = self.ct
+        ws = torch.empty(self.lib.sculpt_mc_workspace_bytes_for(*self.shape, cap), dtype=torch.uint8, device=self.cuda)
+        sp, wpr = (ct.c_void_p(planes.data_ptr()), planes.stride(0)) if planes is not None else (None, 0)
+        rflags = flags | (self.L.MC_SIGNED if planes is not None else 0)
+        self.L.check(self.lib.sculpt_mc_count_launch_for(ct.c_void_p(self.vol.data_ptr()), sp, wpr, *self.shape, float(level), rflags,
+                                                         cap, ct.c_void_p(ws.data_ptr()), self.st))
+        nv, nf, na = ct.c_int64(), ct.c_int64(), ct.c_int64()
+        rc = self.lib.sculpt_mc_count_read_ex(*self.shape, float(level), rflags, ct.c_void_p(ws.data_ptr()), ct.byref(nv), ct.byref(nf),
+                                              None, ct.byref(na), self.st)
+        return rc, (nv.value, nf.value, na.value), ws
+
+    def emit(self, ws, counts, level=0.0, flags=0):
+        ct = self.ct
+        verts = torch.full((counts[0], 3), -7.0, dtype=torch.float32, device=self.cuda)
+        faces = torch.full((counts[1], 3), -7, dtype=torch.int32, device=self.cuda)
+        top = torch.full((2, self.shape[1], self.shape[2]), -7, dtype=torch.int32, device=self.cuda) if flags & self.L.MC_SLAB else None
+        self.L.check(self.lib.sculpt_mc_emit(ct.c_void_p(self.vol.data_ptr()), *self.shape, float(level), flags, ct.c_void_p(ws.data_ptr()),
+                                             1.0, 1.0, 0.0, 0, ct.c_void_p(verts.data_ptr()), ct.c_void_p(faces.data_ptr()),
+                                             ct.c_void_p(top.data_ptr()) if top is not None else None, self.st))
+        torch.cuda.synchronize()
+        return verts, faces, top
+
+    def protocol(self, first_cap, level=0.0, flags=0, planes=None):
+        """The header's protocol: an overflowing count, then ONE count with max_active_cells = the active cells it reported, which
+        must succeed with the same totals; then the emit.  Returns the totals of the first count, the mesh (and the top-plane map)."""
+        rc, counts, _ = self.count(first_cap, level, flags, planes)
+        assert rc == self.L.ERR_MC_WORKSPACE, (rc, counts, first_cap)
+        assert "record pool" in self.L.last_error()
+        n_active = counts[2]
+        assert n_active > first_cap > 0 or first_cap == 0
+        rc, again, ws = self.count(n_active, level, flags, planes)
+        assert rc == 0, (rc, self.L.last_error(), n_active)
+        assert again == counts, (again, counts)
+        return counts, self.emit(ws, counts, level, flags)
+
+
+POOL_VOLUMES = ["noise24", "noise64", "sphere128", "noisy_sphere128", "cylinder", "sphere256", "noise9x10x300", "noise40x3x520",
+                "noise66x37x700", "sphere9x10x300"]
+
+
+@pytest.mark.parametrize("name", POOL_VOLUMES)
+def test_pool_protocol_of_the_header_through_the_c_abi(cuda, name):
+    """Count with a small pool (SCULPT_ERR_MC_WORKSPACE, the oracle's totals, the active cells), count again into a workspace for
+    exactly that many active cells (must succeed: the parts of the pool are loaded unevenly, so equal parts alone do not hold them),
+    emit: the oracle's mesh bit for bit."""
+    vol = _pool_volume(name)
+    rv, rf = capi.marching_cubes(vol, 0.0)
+    P = _Pool(cuda, vol)
+    (nv, nf, na), (v, f, _) = P.protocol(256)
+    assert (nv, nf) == (rv.shape[0], rf.shape[0])
+    assert na <= np.prod(np.array(vol.shape) - 1)
+    _same(v, f, rv, rf)
+
+
+FORM_VOLUMES = ["noise24", "sphere128", "cylinder", "noise66x37x700"]
+
+
+@pytest.mark.parametrize("name", FORM_VOLUMES)
+@pytest.mark.parametrize("form", ["level", "classic", "sign_planes", "slab_halo_low"])
+def test_pool_protocol_in_every_count_form(cuda, name, form):
+    """The same protocol in every form of the count phase that fills the pool: a nonzero level and the classic tables against the
+    oracle, the sign-plane count against the oracle (SCULPT_MC_SIGNED on the read), the slab flags against the same count into a
+    pool for every cell of the grid (one part: it cannot overflow) -- vertices, faces and the top-plane map."""
+    vol = _pool_volume(name)
+    P = _Pool(cuda, vol)
+    if form == "level":
+        level = 0.1
+        rv, rf = capi.marching_cubes(vol, level)
+        (nv, nf, _), (v, f, _) = P.protocol(256, level=level)
+    elif form == "classic":
+        rv, rf = capi.marching_cubes(vol, 0.0, use_classic=True)
+        flags = P.L.MC_USE_CLASSIC
+        (nv, nf, _), (v, f, _) = P.protocol(256, flags=flags)
+    elif form == "sign_planes":
+        rv, rf = capi.marching_cubes(vol, 0.0)
+        (nv, nf, _), (v, f, _) = P.protocol(256, planes=_planes_of(vol).to(cuda))
+    else:
+        flags = P.L.MC_SLAB | P.L.MC_SLAB_HALO_LOW
+        ncells = int(np.prod(np.array(vol.shape) - 1))
+        rc, want_counts, ws = P.count(ncells, flags=flags)
+        assert rc == 0, P.L.last_error()
+        wv, wf, wtop = P.emit(ws, want_counts, flags=flags)
+        counts, (v, f, top) = P.protocol(256, flags=flags)
+        assert counts == want_counts
+        assert torch.equal(v, wv) and torch.equal(f, wf) and torch.equal(top, wtop)
+        if name.startswith("noise"):          # a surface through plane 0: faces reference the previous slab's vertices
+            assert bool((f < 0).any())
+        return
+    assert (nv, nf) == (rv.shape[0], rf.shape[0])
+    _same(v, f, rv, rf)
+
+
+def test_dense_field_overflows_the_default_pool_then_one_retry(cuda):
+    """Noise at 64^3: nearly every cell is active, more than the default pool (max(ncells / 8, 65 536) records).  A count with
+    max_active_cells = 0 (the default) overflows; the first retry with the reported number succeeds with the oracle's mesh."""
+    shape = (64, 64, 64)
+    vol = _pool_volume("noise64")
+    rv, rf = capi.marching_cubes(vol, 0.0)
+    P = _Pool(cuda, vol)
+    assert P.lib.sculpt_mc_workspace_bytes_for(*shape, 0) == P.lib.sculpt_mc_workspace_bytes(*shape)
+    (nv, nf, na), (v, f, _) = P.protocol(0)
+    ncells = 63 ** 3
+    assert na > max(ncells // 8, 65536)
+    assert (nv, nf) == (rv.shape[0], rf.shape[0])
+    _same(v, f, rv, rf)
+
+
+class _CountingLib:
+    """ops.lib with the calls of sculpt_mc_count_launch_for counted."""
+
+    def __init__(self, lib):
+        self._lib, self.count_launches = lib, 0
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name != "sculpt_mc_count_launch_for":
+            return fn
+
+        def counted(*args):
+            self.count_launches += 1
+            return fn(*args)
+
+        return counted
+
+
+@pytest.mark.parametrize("name", ["cylinder", "noisy_sphere128"])
+@pytest.mark.parametrize("slab", [False, True])
+def test_ops_marching_cubes_retries_exactly_once(cuda, monkeypatch, name, slab):
+    """ops.marching_cubes with a remembered capacity far too small for the shape: one overflowing count, ONE retry, the oracle's
+    mesh; the capacity it remembers holds the active cells (and is no smaller than the one that overflowed), so the next call of
+    the shape counts once."""
+    from sculptmate_amd import ops
+
+    vol_np = _pool_volume(name)
+    rv, rf = capi.marching_cubes(vol_np, 0.0)
+    vol = torch.from_numpy(vol_np).to(cuda)
+    n_active = _Pool(cuda, vol_np).count(int(np.prod(np.array(vol_np.shape) - 1)))[1][2]
+    proxy = _CountingLib(ops.lib)
+    monkeypatch.setattr(ops, "lib", proxy)
+    key = (vol.device,) + tuple(vol_np.shape)
+    small = 1000
+    monkeypatch.setattr(ops, "_MC_REC_CAPACITY", {key: small})
+    kw = dict(slab=dict(axis0_offset=0, halo_low=False)) if slab else {}
+    for launches in (2, 1):
+        proxy.count_launches = 0
+        out = ops.marching_cubes(vol, 0.0, **kw)
+        assert proxy.count_launches == launches
+        _same(out[0], out[1], rv, rf)
+        assert ops._MC_REC_CAPACITY[key] >= max(n_active, small)
+
+
 def test_workspace_footprint(cuda):
     """VERDICT r5 #5: <= 100 MB at 256^3 and <= 0.8 GB at 512^3 (the dense records + lattice-edge map took 403 MB / 3.2 GB)."""
     from sculptmate_amd import _lib
