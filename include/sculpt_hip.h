@@ -500,7 +500,8 @@ int sculpt_pixel_shuffle(const float *g, int ldg, float *planes, int n_planes, i
                          sculpt_stream_t stream);
 
 /* F.normalize(x, dim=-1, p=2, eps) on n rows of 3 (the "normalize_channel_last" head activation, network.py:129-130;
- * may run in place) */
+ * may run in place).  A finite row whose squared norm overflows fp32 (|x| >= 2^64) is still normalised to unit length, as the
+ * operation defines it (an fp32 evaluation of the formula would divide by inf and return 0). */
 int sculpt_normalize_rows3(const float *x, int64_t n, float eps, float *y, sculpt_stream_t stream);
 
 /* Texture bake, material composition per texel (StableFast/sf3d/system.py:375-440): all inputs are [res*res][3]
@@ -571,7 +572,8 @@ int sculpt_fuse_sigmoid(const float *maps, int n_maps, int64_t n, const float *w
  *     global_estimator/multi_head_estimator.py:90-94): out [So*So][9*n_groups*C], k = (ky*3+kx)*n_groups*C + g*C + c,
  *     So = (S-3)/s + 1; elements of 2 (bf16) or 4 (f32) bytes, C*elem_bytes a multiple of 16;
  *   sculpt_col_reduce_f32: out[c] = max (mean = 0) or mean (mean != 0) over the rows of x [rows][ld]
- *     (x.amax / x.mean over the pixels, multi_head_estimator.py:96-101). */
+ *     (x.amax / x.mean over the pixels, multi_head_estimator.py:96-101); as amax, a column holding a NaN gives NaN and an
+ *     all -inf column gives -inf; rows >= 1 (an empty reduction is refused). */
 int sculpt_resize_bilinear_hwc(const float *in_hwc, const float *mul_hw /* may be NULL */, int Hin, int Win, int C, float *out_hwc,
                                int Hout, int Wout, sculpt_stream_t stream);
 int sculpt_im2col3x3_strided(const void *in, int n_groups, int S, int C, int elem_bytes, int stride, void *out, sculpt_stream_t stream);

@@ -71,24 +71,27 @@ __global__ __launch_bounds__(256) void im2col3x3_strided_kernel(const uint4 *__r
     }
 }
 
+// the max of x.amax: a NaN wins (fmaxf would drop it), so a column holding a NaN reduces to that NaN
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+
 // out[c] = max (MEAN = false) or mean (MEAN = true) over rows of x [rows][ld]; one wave per 64 columns, rows strided
 template <bool MEAN>
 __global__ __launch_bounds__(256) void col_reduce_kernel(const float *__restrict__ x, int ld, int rows, int cols, float *__restrict__ out) {
     __shared__ float part[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + lane;
-    float acc = MEAN ? 0.f : -FLT_MAX;
+    float acc = MEAN ? 0.f : -INFINITY;   // an all -inf column is -inf, as x.amax gives (rows >= 1: checked by the launcher)
     if (c < cols)
         for (int r = wave; r < rows; r += 4) {
             const float v = x[(long)r * ld + c];
-            acc = MEAN ? acc + v : fmaxf(acc, v);
+            acc = MEAN ? acc + v : nan_max(acc, v);
         }
     part[wave][lane] = acc;
     __syncthreads();
     if (wave == 0 && c < cols) {
         float a = part[0][lane];
 #pragma unroll
-        for (int w = 1; w < 4; ++w) a = MEAN ? a + part[w][lane] : fmaxf(a, part[w][lane]);
+        for (int w = 1; w < 4; ++w) a = MEAN ? a + part[w][lane] : nan_max(a, part[w][lane]);
         out[c] = MEAN ? a / (float)rows : a;
     }
 }

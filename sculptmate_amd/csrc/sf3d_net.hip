@@ -60,11 +60,19 @@ __global__ __launch_bounds__(256) void pixel_shuffle_kernel(const float *__restr
     }
 }
 
-// F.normalize(x, dim=-1, p=2, eps) on rows of 3  (sf3d/models/utils.py:69-72; network.py:129-130)
+// F.normalize(x, dim=-1, p=2, eps) on rows of 3  (sf3d/models/utils.py:69-72; network.py:129-130).
+// A finite row whose squared norm overflows fp32 (|x| >= 2^64) is normalised scaled by 2^-100 (exact): it comes out a unit
+// vector, where the plain formula divides by inf and gives 0.  Every other row takes the plain formula.
 __global__ __launch_bounds__(256) void normalize3_kernel(const float *__restrict__ x, long n, float eps, float *__restrict__ y) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float a = x[3 * i], b = x[3 * i + 1], c = x[3 * i + 2];
-        const float d = fmaxf(sqrtf(a * a + b * b + c * c), eps);
+        float a = x[3 * i], b = x[3 * i + 1], c = x[3 * i + 2];
+        float d = fmaxf(sqrtf(a * a + b * b + c * c), eps);
+        if (isinf(d) && isfinite(a) && isfinite(b) && isfinite(c)) {
+            a *= 0x1p-100f;
+            b *= 0x1p-100f;
+            c *= 0x1p-100f;
+            d = sqrtf(a * a + b * b + c * c);   // >= 2^-36: no underflow, and no eps (the norm is >= 2^64 before scaling)
+        }
         y[3 * i] = a / d;
         y[3 * i + 1] = b / d;
         y[3 * i + 2] = c / d;

@@ -672,6 +672,7 @@ def im2col3x3_strided(act, n_groups, S, stride, out):
 def col_reduce(x, rows, out, mean=False):
     """out[c] = max (or mean) over the first `rows` rows of fp32 x [*, cols] (sculpt_col_reduce_f32)."""
     assert x.dtype == torch.float32 and out.dtype == torch.float32 and x.stride(1) == 1
+    assert out.is_contiguous() and out.numel() >= x.shape[1], "col_reduce: out holds fewer than x.shape[1] columns"
     check(lib.sculpt_col_reduce_f32(_ptr(x), x.stride(0), rows, x.shape[1], 1 if mean else 0, _ptr(out), _stream()))
     return out
 
@@ -682,10 +683,11 @@ def pixel_shuffle(g, planes, n_planes, S, Co, r):
     check(lib.sculpt_pixel_shuffle(_ptr(g), g.stride(0), _ptr(planes), n_planes, S, Co, r, _stream()))
 
 
-def normalize_rows3(x, eps=1e-7):
-    """F.normalize(x, dim=-1, eps=eps) for [N,3] fp32."""
+def normalize_rows3(x, eps=1e-7, out=None):
+    """F.normalize(x, dim=-1, eps=eps) for [N,3] fp32; out may be x itself (in place)."""
     x = _req(x.contiguous(), torch.float32, "x")
-    y = torch.empty_like(x)
+    y = torch.empty_like(x) if out is None else _req(out, torch.float32, "out")
+    assert y.shape == x.shape
     check(lib.sculpt_normalize_rows3(_ptr(x), x.shape[0], float(eps), _ptr(y), _stream()))
     return y
 

@@ -465,22 +465,49 @@ def test_attention_forced_rescale_branch(cuda):
     assert _rel(o, ref)[1] < 0.06
 
 
+def _layernorm_fp64_bound(x, w, b, eps):
+    """fp64 LayerNorm of x and a per-element bound on the kernel's fp32 error: the mean is a sum of depth <= 16 (a lane's chain of
+    cols/256 float4 steps, 3 adds in a step, a 6-level wave tree), off by dm <= 16 u mean|x|, which moves y by |w| dm rstd; the
+    variance (a sum of the same depth over deviations from the fp32 mean: (16 + 4) u, + (dm rstd)^2 <= 2 dm rstd) and rsqrtf
+    (2 u) move rstd relatively, hence y by |w xhat| times that; the epilogue rounds 4 times."""
+    u = 2.0 ** -24
+    x64 = x.double()
+    mean, var = x64.mean(1, keepdim=True), x64.var(1, unbiased=False, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xhat = (x64 - mean) * rstd
+    ref = xhat * w.double() + b.double()
+    dm = 16 * u * x64.abs().mean(1, keepdim=True)
+    rel = 20 * u + 2 * dm * rstd + 2 * u
+    return ref, w.double().abs() * (dm * rstd + xhat.abs() * (rel + 4 * u)) + b.double().abs() * 2 * u
+
+
+@pytest.mark.parametrize("rows", [1025, 1, 77, 3073])
+@pytest.mark.parametrize("offset", [0.0, 300.0])   # 300 = 100 sigma: a one-pass variance would lose it
 @pytest.mark.parametrize("cols,eps", [(768, 1e-12), (1024, 1e-5), (256, 1e-5)])
-def test_layernorm(cuda, cols, eps):
+def test_layernorm(cuda, cols, eps, rows, offset):
     from sculptmate_amd import ops
 
-    g = torch.Generator().manual_seed(cols)
-    x = torch.randn(1025, cols, generator=g) * 3 + 0.5
+    g = torch.Generator().manual_seed(cols if (rows, offset) == (1025, 0.0) else cols * 10007 + rows + int(offset))
+    x = torch.randn(rows, cols, generator=g) * 3 + 0.5
+    if offset:
+        x += offset * torch.sign(torch.randn(rows, 1, generator=g))
     w, b = torch.randn(cols, generator=g), torch.randn(cols, generator=g)
     ref = torch.nn.functional.layer_norm(x, (cols,), w, b, eps)
-    y = torch.empty(1025, cols, dtype=BF, device=cuda)
-    y32 = torch.empty(1025, cols, device=cuda)
-    ops.layernorm(x.to(cuda), w.to(cuda), b.to(cuda), eps, y=y, y_f32=y32)
-    assert _rel(y32, ref)[1] < 2e-5
+    y = torch.empty(rows, cols, dtype=BF, device=cuda)
+    y32 = torch.full((rows + 2, cols), float("nan"), device=cuda)   # rows past `rows` must stay unwritten
+    ops.layernorm(x.to(cuda), w.to(cuda), b.to(cuda), eps, y=y, y_f32=y32[:rows])
+    if offset == 0.0:
+        assert _rel(y32[:rows], ref)[1] < 2e-5
     assert _rel(y, ref)[0] < 4e-3
-    yb = torch.empty(1025, cols, dtype=BF, device=cuda)
+    ref64, tol = _layernorm_fp64_bound(x, w, b, eps)
+    err = (y32[:rows].cpu().double() - ref64).abs()
+    assert (err <= tol).all(), float((err / tol).max())
+    assert torch.isnan(y32[rows:]).all()
+    yb = torch.empty(rows, cols, dtype=BF, device=cuda)
     ops.layernorm(x.to(BF).to(cuda), w.to(cuda), b.to(cuda), eps, y=yb)
     assert _rel(yb, torch.nn.functional.layer_norm(x.to(BF).float(), (cols,), w, b, eps))[0] < 4e-3
+    ref64b, tolb = _layernorm_fp64_bound(x.to(BF).float(), w, b, eps)
+    assert ((yb.cpu().double() - ref64b).abs() <= tolb + 2.0 ** -8 * ref64b.abs()).all()   # + half a bf16 ulp of the result
 
 
 def test_groupnorm_tokens_and_transpose_add(cuda):
