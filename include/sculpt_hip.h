@@ -652,6 +652,84 @@ size_t sculpt_mesh_num_faces(const sculpt_host_mesh_t *m);
 int sculpt_mesh_read(const sculpt_host_mesh_t *m, double *V, int32_t *F);
 void sculpt_mesh_free(sculpt_host_mesh_t *m);
 
+/* Triangle remeshing ON THE DEVICE (csrc/remesh_device.hip; driven by sculptmate_amd/sf3d/remesh_device.py, which does the
+ * sorts and prefix sums): the same three operations as sculpt_mesh_* above, with the mesh in HBM.  Positions fp32 [nv][3], faces
+ * int32 [nf][3]; DEVICE pointers except where a name ends in _host; every call is asynchronous on `stream`.
+ * Every pass rebuilds its topology from the faces:
+ *   sculpt_rmd_halfedge_keys   keys[3 f + k] = (min << 32 | max) of half-edge F[f][k] -> F[f][(k + 1) % 3]
+ *   (caller: stable sort of the keys -> skeys, sperm)
+ *   sculpt_rmd_edge_heads      head[i] = 1 where a run of equal sorted keys starts      (caller: inclusive prefix sum -> eid_incl)
+ *   sculpt_rmd_edge_fill       she[i] = sperm[i], fe[half-edge] = edge, es[edge] = first sorted index (es[ne] = 3 nf)
+ *   (caller: stable sort of the corners by vertex -> vfc, vfs = CSR offsets [nv + 1])
+ *   sculpt_rmd_boundary        bnd[u] = 1 (caller zeroes it) where an edge at u does not have exactly two faces
+ * Local operations claim their footprint with a 64-bit atomicMin of (priority << 32 | edge id) on claim[nv] (caller fills it
+ * with ~0); a candidate applies only when it holds every vertex of its footprint, so a round is deterministic.
+ *   sculpt_rmd_collapse_*      mode 0 = decimate (any edge, midpoint, link condition), 1 = Botsch-Kobbelt (edges < low, boundary
+ *                              vertices stay, no new edge > high, no face turns over); footprint: every vertex of every face around
+ *                              both ends; priority: edge length.  select: win[e] = faces removed (0: lost); apply: dead faces get
+ *                              face_alive = 0 (caller fills 1), F and P change in place.
+ *   sculpt_rmd_flip_*          valence flips (target 6, 4 on the boundary) with the crease (cos >= 0.5) and fold guards; footprint
+ *                              {u, v, a, b}; win[e] = 1 for an applied flip.
+ *   sculpt_rmd_split_*         mark edges longer than `high` (one or two faces), count the children of every face (1..4), then emit
+ *                              the new vertices at P[nv + mark_incl[e] - 1] and the children at Fo[off_incl[f] - count ..]; nothing
+ *                              is written at or beyond vcap vertices / fcap faces: the caller compares the totals with the
+ *                              capacities and emits again into larger buffers if they did not fit.
+ *   sculpt_rmd_grid_*          uniform grid over the projection surface GP / GF: params_host = {lo x, y, z, cell, nx, ny, nz};
+ *                              count the cells of every face, then write (cell, face) pairs (caller: stable sort by cell, CSR)
+ *   sculpt_rmd_relax           tangential relaxation (Jacobi) + projection onto the grid's surface in fp64, then the moves that
+ *                              turned a face over are taken back; Q [nv][3] out, undo [nv] scratch
+ *   sculpt_rmd_compact_faces, _mark_used, _compact_vertices: keep live faces / referenced vertices in index order
+ *   sculpt_rmd_first_halfedge, _subdivide: midpoint subdivision, new vertices in order of first appearance (like the host's)
+ *   sculpt_rmd_validate        status bit 0: face index out of range, 1: repeated index in a face, 2: non-finite position
+ *   sculpt_rmd_halfedge_lengths per face: the sum of its three side lengths (fp64) */
+typedef struct sculpt_rmd_topo {
+    const int32_t *F;      /* [nf][3] */
+    const int64_t *skeys;  /* [3 nf] half-edge keys, sorted */
+    const int32_t *she;    /* [3 nf] half-edge ids in sorted order */
+    const int32_t *es;     /* [ne + 1] first sorted index of every edge */
+    const int32_t *fe;     /* [3 nf] edge of every half-edge */
+    const int32_t *vfs;    /* [nv + 1] vertex -> corner offsets */
+    const int32_t *vfc;    /* [3 nf] corners (3 f + k) by vertex, in corner order */
+    const uint8_t *bnd;    /* [nv] */
+    int64_t nf, nv, ne;
+} sculpt_rmd_topo_t;
+int sculpt_rmd_halfedge_keys(const int32_t *F, int64_t nf, int64_t *keys, sculpt_stream_t stream);
+int sculpt_rmd_edge_heads(const int64_t *skeys, int64_t nh, int32_t *head, sculpt_stream_t stream);
+int sculpt_rmd_edge_fill(const int64_t *sperm, const int32_t *eid_incl, int64_t nh, int32_t *she, int32_t *fe, int32_t *es,
+                         sculpt_stream_t stream);
+int sculpt_rmd_boundary(const sculpt_rmd_topo_t *topo, uint8_t *bnd, sculpt_stream_t stream);
+int sculpt_rmd_collapse_propose(const sculpt_rmd_topo_t *topo, const float *P, int mode, double low, double high,
+                                unsigned long long *claim, unsigned long long *cand, sculpt_stream_t stream);
+int sculpt_rmd_collapse_select(const sculpt_rmd_topo_t *topo, const float *P, int mode, const unsigned long long *claim,
+                               const unsigned long long *cand, int32_t *win, sculpt_stream_t stream);
+int sculpt_rmd_collapse_apply(const sculpt_rmd_topo_t *topo, float *P, int32_t *F, int mode, const int32_t *win, uint8_t *face_alive,
+                              sculpt_stream_t stream);
+int sculpt_rmd_flip_propose(const sculpt_rmd_topo_t *topo, const float *P, unsigned long long *claim, unsigned long long *cand,
+                            sculpt_stream_t stream);
+int sculpt_rmd_flip_apply(const sculpt_rmd_topo_t *topo, const float *P, const unsigned long long *claim,
+                          const unsigned long long *cand, int32_t *F, int32_t *win, sculpt_stream_t stream);
+int sculpt_rmd_split_mark(const sculpt_rmd_topo_t *topo, const float *P, double high, int32_t *mark, sculpt_stream_t stream);
+int sculpt_rmd_split_count(const sculpt_rmd_topo_t *topo, const int32_t *mark, int32_t *cnt, sculpt_stream_t stream);
+int sculpt_rmd_split_emit(const sculpt_rmd_topo_t *topo, float *P, int64_t vcap, const int32_t *mark, const int32_t *mark_incl,
+                          const int32_t *off_incl, int64_t fcap, int32_t *Fo, sculpt_stream_t stream);
+int sculpt_rmd_grid_count(const float *GP, const int32_t *GF, int64_t gnf, const double *params_host, int32_t *cnt,
+                          sculpt_stream_t stream);
+int sculpt_rmd_grid_fill(const float *GP, const int32_t *GF, int64_t gnf, const double *params_host, const int32_t *off_incl,
+                         int32_t *cell, int32_t *face, sculpt_stream_t stream);
+int sculpt_rmd_relax(const sculpt_rmd_topo_t *topo, const float *P, const float *GP, const int32_t *GF, int64_t gnf,
+                     const int32_t *items, const int32_t *start, const double *params_host, int project, float *Q, uint8_t *undo,
+                     sculpt_stream_t stream);
+int sculpt_rmd_compact_faces(const int32_t *F, const uint8_t *alive, const int32_t *incl, int64_t nf, int32_t *Fo,
+                             sculpt_stream_t stream);
+int sculpt_rmd_mark_used(const int32_t *F, int64_t nf, int32_t *used, sculpt_stream_t stream);
+int sculpt_rmd_compact_vertices(const float *P, const int32_t *used, const int32_t *incl, int64_t nv, float *Po, int32_t *F, int64_t nf,
+                                sculpt_stream_t stream);
+int sculpt_rmd_first_halfedge(const sculpt_rmd_topo_t *topo, int32_t *first, sculpt_stream_t stream);
+int sculpt_rmd_subdivide(const sculpt_rmd_topo_t *topo, const float *P, const int32_t *rank_incl, float *Po, int32_t *Fo,
+                         sculpt_stream_t stream);
+int sculpt_rmd_validate(const float *P, int64_t nv, const int32_t *F, int64_t nf, int32_t *status, sculpt_stream_t stream);
+int sculpt_rmd_halfedge_lengths(const float *P, const int32_t *F, int64_t nf, double *len, sculpt_stream_t stream);
+
 /* Mesh hand-off, HOST side (no GPU work): the face block of a binary little-endian PLY file -- per face `uchar 3` followed by
  * three int32 -- from the int64 faces TSR.run returns (the reference's `t_pos_idx.cpu().numpy()`, TripoSR/tsr/system.py:200).
  * faces_host int64 [n][3] -> records_host uint8 [n][13].  Thread-safe; callers split n over threads (sculptmate_amd/meshio.py). */

@@ -162,6 +162,28 @@ SIGNATURES = {
     "sculpt_mesh_read": (_i, [_vp, _vp, _vp]),
     "sculpt_mesh_free": (None, [_vp]),
     "sculpt_ply_face_records": (_i, [_vp, _sz, _vp]),
+    "sculpt_rmd_halfedge_keys": (_i, [_vp, _i64, _vp, _vp]),
+    "sculpt_rmd_edge_heads": (_i, [_vp, _i64, _vp, _vp]),
+    "sculpt_rmd_edge_fill": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "sculpt_rmd_boundary": (_i, [_vp, _vp, _vp]),
+    "sculpt_rmd_collapse_propose": (_i, [_vp, _vp, _i, _d, _d, _vp, _vp, _vp]),
+    "sculpt_rmd_collapse_select": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "sculpt_rmd_collapse_apply": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "sculpt_rmd_flip_propose": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "sculpt_rmd_flip_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_rmd_split_mark": (_i, [_vp, _vp, _d, _vp, _vp]),
+    "sculpt_rmd_split_count": (_i, [_vp, _vp, _vp, _vp]),
+    "sculpt_rmd_split_emit": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "sculpt_rmd_grid_count": (_i, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "sculpt_rmd_grid_fill": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_rmd_relax": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "sculpt_rmd_compact_faces": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "sculpt_rmd_mark_used": (_i, [_vp, _i64, _vp, _vp]),
+    "sculpt_rmd_compact_vertices": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "sculpt_rmd_first_halfedge": (_i, [_vp, _vp, _vp]),
+    "sculpt_rmd_subdivide": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_rmd_validate": (_i, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    "sculpt_rmd_halfedge_lengths": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "rasterize_cpu": (None, [_vp, _sz, _vp, _sz, ctypes.c_longlong, _vp]),
     "interpolate_cpu": (None, [_vp, _sz, _vp, _sz, _vp, ctypes.c_longlong, _vp]),
 }
@@ -170,6 +192,12 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = the .so does not export what the header declares
     _fn.restype = _res
     _fn.argtypes = _args
+
+class RmdTopo(ctypes.Structure):
+    """sculpt_rmd_topo_t (include/sculpt_hip.h)."""
+    _fields_ = [("F", _vp), ("skeys", _vp), ("she", _vp), ("es", _vp), ("fe", _vp), ("vfs", _vp), ("vfc", _vp), ("bnd", _vp),
+                ("nf", _i64), ("nv", _i64), ("ne", _i64)]
+
 
 class LnFold(ctypes.Structure):
     """sculpt_ln_fold_t (include/sculpt_hip.h)."""

@@ -126,3 +126,7 @@ def gpytoolbox_remesher(mesh, mode, vertex_count, remesh_steps: int = 10, gpytoo
 
 def default_remesher():
     return native_remesher
+
+
+# the same operations with the mesh in HBM (HIP kernels, opt-in: `SF3D.remesher = device_remesher`)
+from .remesh_device import decimate_device, device_remesher, remesh_botsch_device, subdivide_device  # noqa: E402,F401
