@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- meshes/sec of the TripoSR generation hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" = one image -> mesh through the reference's own entry points (TripoSR/generate.py:32-43 ->
@@ -9,8 +9,13 @@ tsr/system.py:82-115,171-200): TSR.forward (ViT-B/16 + 16-block triplane transfo
 + TSR.extract_meshes at 256^3 (fused triplane sample + NeRF-MLP: fp32 arithmetic on the bf16 matrix pipe through an exact
 three-limb split of both operands, fp32 accumulate; Lewiner marching cubes).
 `value` times those two calls with the image resident in HBM and the mesh left in HBM (the contract's
-definition); the extra key "boundary" times TSR.run_async(host image) -> host mesh (H2D of the image,
-pinned D2H of vertices / faces on a copy stream under the next image's kernels).
+definition).
+A plain run does only what `value` needs: set-up (weights, images, density-bias calibration, the two-pass grid's identity
+check), warm-up, the timed steps, --dump-outputs, one JSON line.  --full adds everything else the line can carry, all of it
+measured after the timed region: the stage split, the pass times of the identity check, the siblings (exact-fp32 kernel,
+full evaluation, kernel parity), the extras ("boundary" times TSR.run(host images) -> host meshes: H2D of the image, pinned
+D2H of vertices / faces on a copy stream under the next image's kernels; "batched", "slab512", "sf3d", "parity_mode") and
+the CPU baseline with its mesh comparison.
 Workload = BASELINE.json configs[1] "TripoSR single image, mc_resolution=256, bf16 on 1xMI355X";
 with N GPUs each rank runs the same per-GPU workload on its own images (configs[2]: one image per
 GPU, no collectives on the data path) -> "scaling": "weak".
@@ -731,19 +736,22 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure the stage split, the identity check's pass times, the siblings, "
+                         "the extras and the CPU baseline (a plain run measures the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-optional-modes", action="store_true",
                     help="accepted for old command lines: the two-limb decoder modes it used to skip were removed in round 6")
     ap.add_argument("--no-siblings", action="store_true",
-                    help="skip the exact-fp32 kernel's sibling measurement and the kernel-parity pass (profiling runs)")
+                    help="with --full: skip the exact-fp32 kernel's sibling measurement and the kernel-parity pass")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra keys measured after the timed region (boundary, slab512, sf3d)")
+                    help="with --full: skip the extra keys measured after the timed region (boundary, slab512, sf3d)")
     ap.add_argument("--decoder-precision", choices=("bf16l3", "fp32"), default="bf16l3",
                     help="bf16l3 (default = TSR's default: fp32-equivalent three-limb bf16 split), fp32 (exact-fp32 MFMA kernel), "
                          "or a two-limb experiment mode")
-    ap.add_argument("--check-rounds", type=int, default=5,
-                    help="timing rounds of the three passes inside the identity check of the two-pass grid (0: profiling runs, the "
-                         "check alone)")
+    ap.add_argument("--check-rounds", type=int, default=None,
+                    help="timing rounds of the three passes inside the identity check of the two-pass grid (default 5 with --full, "
+                         "else 0: the check alone)")
     ap.add_argument("--no-decoder-filter", action="store_true",
                     help="every lattice point through the six-product kernel (TSR(decoder_filter=False), round 4's path) as the headline")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -751,6 +759,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.check_rounds is None:
+        args.check_rounds = 5 if args.full else 0
+    siblings = args.full and not args.no_siblings
+    extras = args.full and not args.no_extras
     global DECODER_PRECISION
     DECODER_PRECISION = args.decoder_precision
 
@@ -866,7 +878,7 @@ def main():
             "data": "synthetic 512x512 RGBA composited on grey; random-init weights (seeded), calibrated density bias",
             "config": {"workload": "TripoSR single image -> mesh, mc_resolution=256, 1 image per GPU per step",
                        "entry_points_timed": "TSR.forward([image resident in HBM]) + TSR.extract_meshes(codes, resolution=256): mesh "
-                                             "left in HBM; the host-boundary rate is the extra key 'boundary'",
+                                             "left in HBM; the host-boundary rate is the extra key 'boundary' (--full)",
                        "mc_resolution": MC_RES, "threshold": THRESHOLD, "images_per_gpu_per_step": 1,
                        "decoder_precision": mode, "decoder_filter": use_filter,
                        # test plumbing made visible (tests/test_gpu_bench_ranks.py): ranks sharing one device are NOT a multi-GPU figure
@@ -897,28 +909,29 @@ def main():
             "latency_ms_per_image": elapsed / args.steps * 1e3,  # steps run back to back, one image in flight: step time = latency
         }
         with torch.no_grad():
-            st = stage_split(model, imgs[0])  # outside the timed region
-            out["stages_ms"] = st
-            out["transformer_ms"] = round(st["image_tokenizer"] + st["backbone"], 3)
-            # bf16 MFMA fraction of the transformer stack: 2.96 TFLOP / image over the two stage times
-            out["transformer_roofline"] = {"bound": "mfma", "achieved": 2.96 / (out["transformer_ms"] * 1e-3), "peak": PEAK_BF16_MFMA_TFLOPS,
-                                           "unit": "TFLOP/s", "frac": 2.96 / (out["transformer_ms"] * 1e-3) / PEAK_BF16_MFMA_TFLOPS}
+            if args.full:
+                st = stage_split(model, imgs[0])  # outside the timed region
+                out["stages_ms"] = st
+                out["transformer_ms"] = round(st["image_tokenizer"] + st["backbone"], 3)
+                # bf16 MFMA fraction of the transformer stack: 2.96 TFLOP / image over the two stage times
+                out["transformer_roofline"] = {"bound": "mfma", "achieved": 2.96 / (out["transformer_ms"] * 1e-3), "peak": PEAK_BF16_MFMA_TFLOPS,
+                                               "unit": "TFLOP/s", "frac": 2.96 / (out["transformer_ms"] * 1e-3) / PEAK_BF16_MFMA_TFLOPS}
             single = args.gpus == 1 and DECODER_PRECISION == "bf16l3"
             if filt is not None:
                 out["density"] = {"filtered": filt,
                                   "guard": {k: model.filter_info[k] for k in ("filtered", "fallbacks", "calibrations")}}
-                if use_filter and single and not args.no_siblings:
+                if use_filter and single and siblings:
                     out["density"]["full"] = full_density_sibling(model, imgs, args.steps)
-            if single and not args.no_siblings:
+            if single and siblings:
                 out["fp32_exact"] = fp32_exact_sibling(model, imgs, args.steps)
                 out["parity"] = {"kernel_vs_fp32_kernel": kernel_parity(model, imgs[0])}
-            if single and not args.no_extras:
+            if single and extras:
                 out["boundary"] = boundary_rate(model, imgs_np, args.steps)
                 try:
                     out["batched"] = batched_rates(model, imgs, args.steps)
                 except Exception as e:  # an extra must never take the headline line down
                     out["batched"] = {"error": "%s: %s" % (type(e).__name__, e)}
-            if single and not args.no_extras:
+            if single and extras:
                 for key, fn in (("slab512", lambda: slab512_extra(model, imgs[0])), ("sf3d", lambda: sf3d_extra(device))):
                     t0 = time.perf_counter()
                     try:
@@ -927,7 +940,7 @@ def main():
                     except Exception as e:  # an extra must never take the headline line down
                         out[key] = {"error": "%s: %s" % (type(e).__name__, e)}
                     torch.cuda.empty_cache()
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], cpu_verts = cpu_baseline(sd, imgs_np[0])
             # the headline mode's mesh (bf16 transformer, default decoder mode) against the oracle's fp32 CPU mesh of the same
             # image at BASELINE config 1's resolution: two-sided nearest-vertex distances over the 1.74 extent
@@ -938,7 +951,7 @@ def main():
                          "two-sided nearest-vertex distance / 1.74; bounds asserted in tests/test_gpu_transformer.py: mean < 4e-4, "
                          "p99 < 2e-3, p99.9 < 5e-2, max < 1e-1" % DECODER_PRECISION)
             out.setdefault("parity", {})["bf16_mesh_vs_fp32_cpu"] = d
-            if DECODER_PRECISION == "bf16l3" and not args.no_extras:
+            if DECODER_PRECISION == "bf16l3" and extras:
                 try:
                     with torch.no_grad():
                         out["parity_mode"] = parity_mode_extra(sd, model, imgs, imgs_np, cpu_verts, args.steps, "fp16l2")
