@@ -661,7 +661,16 @@ void sculpt_mesh_free(sculpt_host_mesh_t *m);
  *   sculpt_rmd_edge_heads      head[i] = 1 where a run of equal sorted keys starts      (caller: inclusive prefix sum -> eid_incl)
  *   sculpt_rmd_edge_fill       she[i] = sperm[i], fe[half-edge] = edge, es[edge] = first sorted index (es[ne] = 3 nf)
  *   (caller: stable sort of the corners by vertex -> vfc, vfs = CSR offsets [nv + 1])
- *   sculpt_rmd_boundary        bnd[u] = 1 (caller zeroes it) where an edge at u does not have exactly two faces
+ *   sculpt_rmd_high_valence    flags[u] = 1 (caller zeroes it) where u has more than 64 distinct neighbours
+ *   sculpt_rmd_boundary        bnd[u] = 1 where an edge at u does not have exactly two faces; the caller fills bnd beforehand with
+ *                              the flags it carries: for the first pass over an input, its high-valence flags; after that, the
+ *                              previous pass's bnd (0 for vertices a split added), with bnd[kept] |= bnd[removed] after a
+ *                              decimation collapse.  High-valence rule, the host's (remesh_host.h: Mesh::build scans once, the
+ *                              operations keep the flags): a vertex with more than 64 distinct neighbours in the INPUT is a
+ *                              feature like a boundary vertex for the whole call, whatever its valence becomes -- the
+ *                              Botsch-Kobbelt pass never moves or removes it (an interior neighbour may collapse into it), the
+ *                              link condition treats it as a boundary vertex, and its flip valence is faces + 1 with target 4.
+ *                              No operation is refused for the size of a fan.
  * Local operations claim their footprint with a 64-bit atomicMin of (priority << 32 | edge id) on claim[nv] (caller fills it
  * with ~0); a candidate applies only when it holds every vertex of its footprint, so a round is deterministic.
  *   sculpt_rmd_collapse_*      mode 0 = decimate (any edge, midpoint, link condition), 1 = Botsch-Kobbelt (edges < low, boundary
@@ -676,8 +685,10 @@ void sculpt_mesh_free(sculpt_host_mesh_t *m);
  *                              capacities and emits again into larger buffers if they did not fit.
  *   sculpt_rmd_grid_*          uniform grid over the projection surface GP / GF: params_host = {lo x, y, z, cell, nx, ny, nz};
  *                              count the cells of every face, then write (cell, face) pairs (caller: stable sort by cell, CSR)
- *   sculpt_rmd_relax           tangential relaxation (Jacobi) + projection onto the grid's surface in fp64, then the moves that
- *                              turned a face over are taken back; Q [nv][3] out, undo [nv] scratch
+ *   sculpt_rmd_relax           tangential relaxation (Jacobi) + projection onto the grid's surface in fp64, the centroid over the
+ *                              distinct neighbours; then every vertex of a face that turned over takes its move back, repeated
+ *                              until no face is turned over (one readback per pass: this call synchronizes `stream`);
+ *                              Q [nv][3] out, undo: 4-byte aligned scratch of SCULPT_RMD_UNDO_BYTES(nv) bytes
  *   sculpt_rmd_compact_faces, _mark_used, _compact_vertices: keep live faces / referenced vertices in index order
  *   sculpt_rmd_first_halfedge, _subdivide: midpoint subdivision, new vertices in order of first appearance (like the host's)
  *   sculpt_rmd_validate        status bit 0: face index out of range, 1: repeated index in a face, 2: non-finite position
@@ -697,7 +708,9 @@ int sculpt_rmd_halfedge_keys(const int32_t *F, int64_t nf, int64_t *keys, sculpt
 int sculpt_rmd_edge_heads(const int64_t *skeys, int64_t nh, int32_t *head, sculpt_stream_t stream);
 int sculpt_rmd_edge_fill(const int64_t *sperm, const int32_t *eid_incl, int64_t nh, int32_t *she, int32_t *fe, int32_t *es,
                          sculpt_stream_t stream);
+int sculpt_rmd_high_valence(const sculpt_rmd_topo_t *topo, uint8_t *flags, sculpt_stream_t stream);
 int sculpt_rmd_boundary(const sculpt_rmd_topo_t *topo, uint8_t *bnd, sculpt_stream_t stream);
+#define SCULPT_RMD_UNDO_BYTES(nv) ((((int64_t)(nv) + 3) & ~(int64_t)3) + 4) /* a flag per vertex, then the pass's int32 "grew" */
 int sculpt_rmd_collapse_propose(const sculpt_rmd_topo_t *topo, const float *P, int mode, double low, double high,
                                 unsigned long long *claim, unsigned long long *cand, sculpt_stream_t stream);
 int sculpt_rmd_collapse_select(const sculpt_rmd_topo_t *topo, const float *P, int mode, const unsigned long long *claim,

@@ -165,6 +165,7 @@ SIGNATURES = {
     "sculpt_rmd_halfedge_keys": (_i, [_vp, _i64, _vp, _vp]),
     "sculpt_rmd_edge_heads": (_i, [_vp, _i64, _vp, _vp]),
     "sculpt_rmd_edge_fill": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "sculpt_rmd_high_valence": (_i, [_vp, _vp, _vp]),
     "sculpt_rmd_boundary": (_i, [_vp, _vp, _vp]),
     "sculpt_rmd_collapse_propose": (_i, [_vp, _vp, _i, _d, _d, _vp, _vp, _vp]),
     "sculpt_rmd_collapse_select": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
@@ -192,6 +193,11 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)  # AttributeError here = the .so does not export what the header declares
     _fn.restype = _res
     _fn.argtypes = _args
+
+def rmd_undo_bytes(nv):
+    """SCULPT_RMD_UNDO_BYTES (include/sculpt_hip.h): the scratch sculpt_rmd_relax takes."""
+    return ((nv + 3) & ~3) + 4
+
 
 class RmdTopo(ctypes.Structure):
     """sculpt_rmd_topo_t (include/sculpt_hip.h)."""

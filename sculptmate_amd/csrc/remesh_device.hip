@@ -8,7 +8,8 @@
 //   the keys sorted (stable): edge e owns the sorted range [es[e], es[e + 1]); she[] are the half-edge ids in that order, fe[h]
 //     the edge of half-edge h
 //   vertex -> corner CSR (stable sort of the corners by vertex): corners vfc[vfs[u] .. vfs[u + 1]) of vertex u, face = corner / 3
-//   bnd[u]: some edge at u does not have exactly two faces
+//   bnd[u]: some edge at u does not have exactly two faces, or a flag the caller carries from earlier passes: a vertex with more
+//     than 64 distinct neighbours in the input stays a feature for the whole call (remesh_host.h Mesh::build scans once)
 // Local operations (collapse, flip) run as propose / select / apply: every valid candidate claims every vertex of its footprint
 // with a 64-bit atomicMin of (priority << 32 | edge id); only a candidate that holds its whole footprint applies.  Two winners
 // never share a footprint vertex, so neither reads or writes anything the other changes and a round is the same as applying
@@ -25,7 +26,7 @@ using namespace sculpt;
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxFan = 64;  // a collapse or flip at a vertex with more faces than this is not proposed (the host treats it alike)
+constexpr int kMaxNeighbours = 64;  // a vertex with more distinct neighbours is a feature: boundary (remesh_host.h scan_boundary_vertex)
 constexpr unsigned long long kNoClaim = ~0ull;
 
 struct D3 {
@@ -161,6 +162,30 @@ __global__ void boundary_kernel(Topo T, uint8_t *__restrict__ bnd) {
     }
 }
 
+// a vertex with more than kMaxNeighbours distinct neighbours is flagged like a boundary vertex (the host's "absurd valence:
+// treat as a feature", scanned once per input; the caller carries the flag through the passes); a fan of f faces has at most 2 f neighbours, so only fans above kMaxNeighbours / 2 are scanned, and
+// the scan stops at the first neighbour past the limit: O(fan x kMaxNeighbours)
+__global__ void high_valence_kernel(Topo T, uint8_t *__restrict__ flags) {
+    const long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= T.nv || fan(T, (int)u) <= kMaxNeighbours / 2) return;
+    int nb[kMaxNeighbours], n = 0;
+    for (int j = T.vfs[u]; j < T.vfs[u + 1]; ++j) {
+        const int f = fan_face(T, j);
+        for (int k = 0; k < 3; ++k) {
+            const int w = T.F[3 * f + k];
+            if (w == (int)u) continue;
+            int i = 0;
+            while (i < n && nb[i] != w) ++i;
+            if (i < n) continue;
+            if (n == kMaxNeighbours) {
+                flags[u] = 1;
+                return;
+            }
+            nb[n++] = w;
+        }
+    }
+}
+
 // ---- collapse (shared by decimate and the Botsch-Kobbelt pass) -----------------------------------------------------------
 // mode 0 = decimate: any edge, remove min(u, v), keep max at the midpoint, link condition only (remesh_host.h decimate()).
 // mode 1 = Botsch: edges shorter than `low`, never both ends on the boundary, the interior end goes, a boundary end stays put,
@@ -198,7 +223,6 @@ __global__ void collapse_propose_kernel(Topo T, const float *__restrict__ P, int
         if (mode == 1 && !(norm(ld(P, a) - ld(P, b)) < low)) return;
     }
     if (!collapse_target(T, P, mode, (int)e, u, v, pf)) return;
-    if (fan(T, u) > kMaxFan || fan(T, v) > kMaxFan) return;
     if (!link_ok(T, u, v, (int)e)) return;
     const D3 p = {(double)pf[0], (double)pf[1], (double)pf[2]};
     if (mode == 1) {
@@ -289,7 +313,7 @@ __device__ bool flip_target(const Topo &T, const float *P, int e, int &u, int &v
     a = third(T.F, f1, u, v);
     b = third(T.F, f2, u, v);
     if (a == b) return false;
-    if (fan(T, a) > kMaxFan || faces_with(T, a, b) != 0) return false;  // the new edge exists already
+    if (faces_with(T, a, b) != 0) return false;  // the new edge exists already
     auto val = [&](int x) { return fan(T, x) + (T.bnd[x] ? 1 : 0); };
     auto tgt = [&](int x) { return T.bnd[x] ? 4 : 6; };
     auto sq = [](int x) { return x * x; };
@@ -548,13 +572,24 @@ __global__ void relax_kernel(Topo T, const float *__restrict__ P, Grid G, int pr
     const long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= T.nv) return;
     for (int k = 0; k < 3; ++k) Q[3 * u + k] = P[3 * u + k];
-    const int deg = fan(T, (int)u);
-    if (deg == 0 || T.bnd[u]) return;
+    if (fan(T, (int)u) == 0 || T.bnd[u]) return;
     D3 N = {0, 0, 0}, c = {0, 0, 0};
+    int deg = 0;
     for (int j = T.vfs[u]; j < T.vfs[u + 1]; ++j) {
-        const int f = fan_face(T, j), k = T.vfc[j] - 3 * f;
-        N = N + face_normal(P, T.F, f);        // length = 2 area: area-weighted vertex normal
-        c = c + ld(P, T.F[3 * f + (k + 1) % 3]);  // an interior vertex meets every neighbour once as the next corner
+        const int f = fan_face(T, j);
+        N = N + face_normal(P, T.F, f);  // length = 2 area: area-weighted vertex normal
+        // the centroid of the distinct neighbours, each at its first face around u (remesh_host.h Mesh::neighbours): the "next
+        // corner" of every face is the same set only where the fan is consistently oriented.  An interior vertex has at most
+        // kMaxNeighbours neighbours, so this is O(fan^2) with a small fan.
+        for (int k = 0; k < 3; ++k) {
+            const int w = T.F[3 * f + k];
+            if (w == (int)u) continue;
+            bool seen = false;
+            for (int j2 = T.vfs[u]; j2 < j && !seen; ++j2) seen = has(T.F, fan_face(T, j2), w);
+            if (seen) continue;
+            c = c + ld(P, w);
+            ++deg;
+        }
     }
     c = (1.0 / deg) * c;
     const double ln = norm(N);
@@ -572,13 +607,19 @@ __global__ void relax_kernel(Topo T, const float *__restrict__ P, Grid G, int pr
     Q[3 * u] = (float)p.x, Q[3 * u + 1] = (float)p.y, Q[3 * u + 2] = (float)p.z;
 }
 
-// second pass: every vertex of a face that turned over (old positions vs new) takes its move back
+// second pass: every vertex of a face that turned over (old positions vs new) takes its move back.  Taking back one vertex can
+// turn over another face whose other corners moved, so the pass repeats until it marks no new vertex (*grew = 0); the marks only
+// grow, so this ends.
 __global__ void undo_mark_kernel(const int32_t *__restrict__ F, long nf, const float *__restrict__ P, const float *__restrict__ Q,
-                                 uint8_t *__restrict__ undo) {
+                                 uint8_t *__restrict__ undo, int32_t *__restrict__ grew) {
     const long f = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= nf) return;
     if (dot(face_normal(P, F, (int)f), face_normal(Q, F, (int)f)) <= 0)
-        for (int k = 0; k < 3; ++k) undo[F[3 * f + k]] = 1;  // every writer stores the same value
+        for (int k = 0; k < 3; ++k)
+            if (!undo[F[3 * f + k]]) {
+                undo[F[3 * f + k]] = 1;  // every writer stores the same value
+                *grew = 1;
+            }
 }
 
 __global__ void undo_apply_kernel(const float *__restrict__ P, const uint8_t *__restrict__ undo, long nv, float *__restrict__ Q) {
@@ -724,6 +765,12 @@ int sculpt_rmd_boundary(const sculpt_rmd_topo_t *topo, uint8_t *bnd, sculpt_stre
     return 0;
 }
 
+int sculpt_rmd_high_valence(const sculpt_rmd_topo_t *topo, uint8_t *flags, sculpt_stream_t stream) {
+    if (int rc = check_topo(topo, "rmd_high_valence")) return rc;
+    RMD_LAUNCH(high_valence_kernel, topo->nv, topo_of(topo), flags);
+    return 0;
+}
+
 int sculpt_rmd_collapse_propose(const sculpt_rmd_topo_t *topo, const float *P, int mode, double low, double high,
                                 unsigned long long *claim, unsigned long long *cand, sculpt_stream_t stream) {
     if (int rc = check_topo(topo, "rmd_collapse_propose")) return rc;
@@ -804,10 +851,20 @@ int sculpt_rmd_relax(const sculpt_rmd_topo_t *topo, const float *P, const float 
     if (int rc = check_topo(topo, "rmd_relax")) return rc;
     SC_REQUIRE(!project || (params_host && (gnf == 0 || (GP && GF && items && start))), "rmd_relax: projection without a grid");
     const Grid G = grid_of(GP, GF, project ? (long)gnf : 0, items, start, project ? params_host : nullptr);
+    SC_REQUIRE(((uintptr_t)undo & 3) == 0, "rmd_relax: undo scratch must be 4-byte aligned");
     RMD_LAUNCH(relax_kernel, topo->nv, topo_of(topo), P, G, project, Q);
-    SC_HIP(hipMemsetAsync(undo, 0, (size_t)topo->nv, as_stream(stream)));
-    RMD_LAUNCH(undo_mark_kernel, topo->nf, topo->F, (long)topo->nf, P, Q, undo);
-    RMD_LAUNCH(undo_apply_kernel, topo->nv, P, undo, (long)topo->nv, Q);
+    if (topo->nf == 0 || topo->nv == 0) return 0;
+    hipStream_t st = as_stream(stream);
+    SC_HIP(hipMemsetAsync(undo, 0, (size_t)topo->nv, st));
+    int32_t *grew = reinterpret_cast<int32_t *>(undo + (SCULPT_RMD_UNDO_BYTES(topo->nv) - 4));
+    for (int32_t h = 1; h;) {  // the undo pass to a fixed point: one readback per pass, usually one or two
+        h = 0;
+        SC_HIP(hipMemsetAsync(grew, 0, sizeof(int32_t), st));
+        RMD_LAUNCH(undo_mark_kernel, topo->nf, topo->F, (long)topo->nf, P, Q, undo, grew);
+        RMD_LAUNCH(undo_apply_kernel, topo->nv, P, undo, (long)topo->nv, Q);
+        SC_HIP(hipMemcpyAsync(&h, grew, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        SC_HIP(hipStreamSynchronize(st));
+    }
     return 0;
 }
 

@@ -86,9 +86,11 @@ def _inputs(v, f, who, check_faces=True):
 
 
 class _Topo:
-    """Edge table, vertex -> corner CSR and boundary flags of the faces F (see csrc/remesh_device.hip)."""
+    """Edge table, vertex -> corner CSR and boundary flags of the faces F (see csrc/remesh_device.hip).  `carry`: the previous
+    pass's bnd (None: the first pass over an input, whose vertices with more than 64 neighbours become features).  Like the
+    host's Mesh, a flag once set stays for the whole call: a high-valence vertex is a feature even after its valence drops."""
 
-    def __init__(self, ctx, F, nv):
+    def __init__(self, ctx, F, nv, carry=None):
         ctx.stats["passes"] += 1
         dev = F.device
         s = ctx.stream
@@ -103,16 +105,21 @@ class _Topo:
         eid = torch.cumsum(head, 0, dtype=torch.int32)
         self.she = torch.empty(nh, dtype=torch.int32, device=dev)
         self.fe = torch.empty(nh, dtype=torch.int32, device=dev)
-        self.es = torch.empty(nh + 1, dtype=torch.int32, device=dev)
+        self.es = torch.empty(nh + 1, dtype=torch.int32, device=dev) if nh else torch.zeros(1, dtype=torch.int32, device=dev)  # es[ne] = 3 nf
         check(lib.sculpt_rmd_edge_fill(_p(sperm), _p(eid), nh, _p(self.she), _p(self.fe), _p(self.es), s))
         self.ne = ctx.read(eid[-1:]) if nh else 0
         sv, vperm = torch.sort(F.reshape(-1), stable=True)
         self.vfc = vperm.to(torch.int32)
         self.vfs = torch.searchsorted(sv, torch.arange(nv + 1, dtype=torch.int32, device=dev), out_int32=True)
         self.bnd = torch.zeros(max(nv, 1), dtype=torch.uint8, device=dev)
+        if carry is not None:
+            n = min(nv, carry.shape[0])
+            self.bnd[:n] = carry[:n]  # vertices a split added start at 0
         self.c = _lib.RmdTopo(F.data_ptr() if nf else 0, self.skeys.data_ptr() if nh else 0, self.she.data_ptr() if nh else 0,
                               self.es.data_ptr(), self.fe.data_ptr() if nh else 0, self.vfs.data_ptr(),
                               self.vfc.data_ptr() if nh else 0, self.bnd.data_ptr(), nf, nv, self.ne)
+        if carry is None:
+            check(lib.sculpt_rmd_high_valence(self.ref(), _p(self.bnd), s))
         check(lib.sculpt_rmd_boundary(self.ref(), _p(self.bnd), s))
 
     def ref(self):
@@ -165,6 +172,12 @@ def _collapse_round(ctx, T, P, mode, low=0.0, high=0.0, target=None):
     alive = torch.ones(T.nf, dtype=torch.uint8, device=dev)
     F = T.F
     check(lib.sculpt_rmd_collapse_apply(T.ref(), _p(P), _p(F), mode, _p(win), _p(alive), ctx.stream))
+    if mode == 0:
+        # the kept end (the larger index) inherits the removed end's flag, as in Mesh::collapse; in mode 1 the removed end is
+        # never flagged
+        key = T.skeys[T.es[:T.ne][win > 0].long()]
+        lo, hi = key >> 32, key & 0xFFFFFFFF
+        T.bnd[hi] |= T.bnd[lo]
     ctx.stats["collapses"] += n
     return _compact_faces(ctx, F, alive, T.nf - removed), n
 
@@ -268,7 +281,7 @@ class _Grid:
 
 def _relax(ctx, T, V, grid, project):
     Q = torch.empty_like(V.buf)
-    undo = torch.empty(max(T.nv, 1), dtype=torch.uint8, device=V.buf.device)
+    undo = torch.empty(_lib.rmd_undo_bytes(T.nv), dtype=torch.uint8, device=V.buf.device)
     g = grid if project else None
     check(lib.sculpt_rmd_relax(T.ref(), _p(V.P), _p(g.GP) if g else None, _p(g.GF) if g else None, g.GF.shape[0] if g else 0,
                                _p(g.items) if g else None, _p(g.start) if g else None, g.params if g else None, 1 if project else 0,
@@ -311,8 +324,9 @@ def subdivide_device(v, f, iters=1):
 
 def _decimate(ctx, P, F, target):
     V = P
+    T = None
     while F.shape[0] > target:
-        T = _Topo(ctx, F, V.shape[0])
+        T = _Topo(ctx, F, V.shape[0], carry=T.bnd if T is not None else None)
         ctx.stats["rounds"] += 1
         F, n = _collapse_round(ctx, T, V, 0, target=target)
         if n == 0:
@@ -357,16 +371,16 @@ def remesh_botsch_device(v, f, i=10, h=None, project=True):
                 Fn, n = _split_sweep(ctx, T, V, high)
                 if n == 0:
                     break
-                T = _Topo(ctx, Fn, V.nv)
+                T = _Topo(ctx, Fn, V.nv, carry=T.bnd)
             for _ in range(COLLAPSE_ROUNDS):
                 Fn, n = _collapse_round(ctx, T, V.P, 1, low, high)
                 if n == 0:
                     break
-                T = _Topo(ctx, Fn, V.nv)
+                T = _Topo(ctx, Fn, V.nv, carry=T.bnd)
             for _ in range(FLIP_ROUNDS):
                 if _flip_round(ctx, T, V.P) == 0:
                     break
-                T = _Topo(ctx, T.F, V.nv)  # the faces were rewritten in place
+                T = _Topo(ctx, T.F, V.nv, carry=T.bnd)  # the faces were rewritten in place
             _relax(ctx, T, V, grid, project)
         P, F = V.P[:V.nv], T.F
     P = _compact_vertices(ctx, P.contiguous(), P.shape[0], F)
