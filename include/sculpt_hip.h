@@ -585,12 +585,15 @@ int sculpt_col_reduce_f32(const float *x, int ld, int rows, int cols, int mean, 
  * same mesh.  faces: int32 or int64 [nf][3] (faces_i64).
  *   sculpt_uv_moments         sums9 (device doubles) = sum of x, y, z, xx, xy, xz, yy, yz, zz over the vertices: the statistics
  *                             behind _align_mesh_with_main_axis (:546-623; exact principal axes instead of the reference's
- *                             randomised torch.pca_lowrank)
+ *                             randomised torch.pca_lowrank); workspace: sculpt_uv_moments_workspace_bytes() device bytes,
+ *                             the sums are added in a fixed order (reproducible to the bit)
  *   sculpt_uv_box_project     rot_pos / rot_nrm = rot (row-major 3x3, host) applied to every vertex; face_uv [nf][3][2] and
  *                             chart [nf] in 0..5 = _box_assign_vertex_to_cube_face (:16-122)
- *   sculpt_uv_chart_tangents  vertex_tangents4 [nv][4] (xyz = _calculate_tangents, :239-305); sums42 (device doubles) [6][7] =
- *                             per chart the sum over its corners of the vertex tangent (3), of the expected tangent (3; with
- *                             the reference's F.normalize(x, -1) scaling, :326-341) and the corner count
+ *   sculpt_uv_chart_tangents  vertex_tangents4 [nv][4] (xyz = _calculate_tangents, :239-305, w = corner count); sums42 (device
+ *                             doubles) [6][7] = per chart the sum over its corners of the vertex tangent (3), of the expected
+ *                             tangent (3; with the reference's F.normalize(x, -1) scaling, :326-341) and the corner count;
+ *                             workspace: sculpt_uv_chart_tangents_workspace_bytes(nv) device bytes.  Reproducible to the bit:
+ *                             fixed-point vertex sums, chart sums added in a fixed order
  *   sculpt_uv_rotate_charts   face_uv rotated per chart by the angle (cos, sin given per chart) about the chart centre and
  *                             stretched to [0, 1] by the chart's joint min / max (:357-381), in place
  *   sculpt_uv_assign_atlas    assigned [nf]: chart c stays c, moves to the overlap slice c + 6, or to 12 ("remaining") -- the
@@ -598,12 +601,15 @@ int sculpt_col_reduce_f32(const float *x, int ld, int rows, int cols, int mean, 
  *                             (UV-space z-buffer of res x res pixels per chart, zbuf = 6*res*res uint64 scratch)
  *   sculpt_uv_place           out_uv [nf][3][2] atlas coordinates (:177-237, 383-527); block_scratch: ceil(nf/256) ints */
 size_t sculpt_uv_stats_words(void);
-int sculpt_uv_moments(const float *v_pos, size_t nv, double *sums9, sculpt_stream_t stream);
+size_t sculpt_uv_moments_workspace_bytes(void);
+int sculpt_uv_moments(const float *v_pos, size_t nv, double *sums9, void *workspace, sculpt_stream_t stream);
 int sculpt_uv_box_project(const float *v_pos, const float *v_nrm, size_t nv, const void *faces, int faces_i64, size_t nf,
                           const float *rot9_host, float *rot_pos, float *rot_nrm, float *face_uv, int *chart, unsigned *stats,
                           sculpt_stream_t stream);
+size_t sculpt_uv_chart_tangents_workspace_bytes(size_t nv);
 int sculpt_uv_chart_tangents(const float *rot_pos, const float *rot_nrm, size_t nv, const void *faces, int faces_i64, size_t nf,
-                             const float *face_uv, const int *chart, float *vertex_tangents4, double *sums42, sculpt_stream_t stream);
+                             const float *face_uv, const int *chart, float *vertex_tangents4, double *sums42, void *workspace,
+                             sculpt_stream_t stream);
 int sculpt_uv_rotate_charts(float *face_uv, const int *chart, size_t nf, const float *cos6_host, const float *sin6_host, unsigned *stats,
                             sculpt_stream_t stream);
 int sculpt_uv_assign_atlas(const float *rot_pos, const void *faces, int faces_i64, size_t nf, const float *face_uv, const int *chart,
@@ -619,13 +625,15 @@ void assign_faces_uv_to_atlas_index(const float *vertices, size_t nv, const long
 /* StableFast geometry tail:
  *   dilate_fill (sf3d/models/utils.py:96-133): img f32 [3][H][W], mask f32 [H][W]; scratch 8*H*W floats
  *   vertex normals / tangents (sf3d/models/mesh.py:66-139): area-weighted face normal / UV tangent splat
- *   (float atomics: the sum order is not reproducible to the last bit), normalise, Gram-Schmidt. */
+ *   as order-independent fixed-point sums (reproducible to the bit), normalise, Gram-Schmidt; workspace:
+ *   sculpt_vertex_accumulate_workspace_bytes(nv) device bytes. */
 int sculpt_dilate_fill(const float *img, const float *mask, int H, int W, int iterations, float *scratch, float *out,
                        sculpt_stream_t stream);
-int sculpt_vertex_normals(const float *v_pos, size_t nv, const void *faces, int faces_i64, size_t nf, float *out,
+size_t sculpt_vertex_accumulate_workspace_bytes(size_t nv);
+int sculpt_vertex_normals(const float *v_pos, size_t nv, const void *faces, int faces_i64, size_t nf, void *workspace, float *out,
                           sculpt_stream_t stream);
 int sculpt_vertex_tangents(const float *v_pos, const float *v_tex, const float *v_nrm, size_t nv, const void *faces,
-                           int faces_i64, size_t nf, float *count_scratch, float *out, sculpt_stream_t stream);
+                           int faces_i64, size_t nf, void *workspace, float *out, sculpt_stream_t stream);
 
 /* fp32 -> bf16 (round to nearest even), n elements */
 int sculpt_cast_bf16(const float *x, uint16_t *y, int64_t n, sculpt_stream_t stream);

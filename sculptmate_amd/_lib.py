@@ -128,7 +128,8 @@ SIGNATURES = {
     "sculpt_upsample_scatter": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp]),
     "sculpt_cast_bf16": (_i, [_vp, _vp, _i64, _vp]),
     "sculpt_dilate_fill": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "sculpt_vertex_normals": (_i, [_vp, _sz, _vp, _i, _sz, _vp, _vp]),
+    "sculpt_vertex_accumulate_workspace_bytes": (_sz, [_sz]),
+    "sculpt_vertex_normals": (_i, [_vp, _sz, _vp, _i, _sz, _vp, _vp, _vp]),
     "sculpt_vertex_tangents": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _sz, _vp, _vp, _vp]),
     "sculpt_resize_aa_bilinear": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "sculpt_bake_workspace_bytes": (_sz, [_i]),
@@ -137,9 +138,11 @@ SIGNATURES = {
     "sculpt_im2col3x3": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "sculpt_pixel_shuffle": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "sculpt_uv_stats_words": (_sz, []),
-    "sculpt_uv_moments": (_i, [_vp, _sz, _vp, _vp]),
+    "sculpt_uv_moments_workspace_bytes": (_sz, []),
+    "sculpt_uv_moments": (_i, [_vp, _sz, _vp, _vp, _vp]),
     "sculpt_uv_box_project": (_i, [_vp, _vp, _sz, _vp, _i, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "sculpt_uv_chart_tangents": (_i, [_vp, _vp, _sz, _vp, _i, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_uv_chart_tangents_workspace_bytes": (_sz, [_sz]),
+    "sculpt_uv_chart_tangents": (_i, [_vp, _vp, _sz, _vp, _i, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_uv_rotate_charts": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "sculpt_uv_assign_atlas": (_i, [_vp, _vp, _i, _sz, _vp, _vp, _i, _vp, _vp, _vp]),
     "assign_faces_uv_to_atlas_index": (None, [_vp, _sz, _vp, _sz, _vp, _vp, _vp]),

@@ -4,6 +4,7 @@
 //   sculpt_vertex_normals     Mesh._compute_vertex_normal   StableFast/sf3d/models/mesh.py:66-92
 //   sculpt_vertex_tangents    Mesh._compute_vertex_tangent  StableFast/sf3d/models/mesh.py:94-139
 #include "common.h"
+#include "fixsum.h"
 
 namespace sculpt {
 
@@ -60,33 +61,42 @@ __global__ __launch_bounds__(256) void dilate_b_kernel(const float *__restrict__
 }
 
 // ---- vertex normals / tangents ---------------------------------------------------------------------------
-template <typename IdxT>
+// The face values are scattered onto the corners as order-independent fixed-point sums (fixsum.h): PASS 0 notes the
+// largest |term| of every sum (and, for the tangents, counts the corners), PASS 1 adds.  Workspace (both entries):
+// int64 [nv][3] sums | u32 [nv][3] largest |term| | int [nv] corner counts.
+inline size_t vertex_accumulate_workspace_bytes(size_t nv) { return nv * (24 + 12 + 4); }
+
+template <typename IdxT, int PASS>
 __global__ __launch_bounds__(256) void face_normal_splat_kernel(const float *__restrict__ v, const IdxT *__restrict__ f,
-                                                                long nf, float *__restrict__ acc) {
+                                                                long nf, long long *__restrict__ acc, unsigned *__restrict__ mag) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= nf) return;
     const long i0 = f[3 * t], i1 = f[3 * t + 1], i2 = f[3 * t + 2];
     const float ax = v[3 * i1] - v[3 * i0], ay = v[3 * i1 + 1] - v[3 * i0 + 1], az = v[3 * i1 + 2] - v[3 * i0 + 2];
     const float bx = v[3 * i2] - v[3 * i0], by = v[3 * i2 + 1] - v[3 * i0 + 1], bz = v[3 * i2 + 2] - v[3 * i0 + 2];
-    const float nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+    const float nrm[3] = {ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx};
     const long ids[3] = {i0, i1, i2};
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        atomicAdd(&acc[3 * ids[k]], nx); atomicAdd(&acc[3 * ids[k] + 1], ny); atomicAdd(&acc[3 * ids[k] + 2], nz);
-    }
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            if (PASS == 0) fx_note(&mag[3 * ids[k] + r], nrm[r]);
+            else fx_add(&acc[3 * ids[k] + r], mag[3 * ids[k] + r], nrm[r]);
+        }
 }
-__global__ __launch_bounds__(256) void normal_finish_kernel(float *__restrict__ n, long nv) {
+__global__ __launch_bounds__(256) void normal_finish_kernel(const long long *__restrict__ acc, const unsigned *__restrict__ mag,
+                                                            float *__restrict__ n, long nv) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= nv) return;
-    float x = n[3 * i], y = n[3 * i + 1], z = n[3 * i + 2];
+    float x = fx_value(acc[3 * i], mag[3 * i]), y = fx_value(acc[3 * i + 1], mag[3 * i + 1]), z = fx_value(acc[3 * i + 2], mag[3 * i + 2]);
     if (!(x * x + y * y + z * z > 1e-20f)) { x = 0.f; y = 0.f; z = 1.f; }
     const float l = fmaxf(sqrtf(x * x + y * y + z * z), 1e-12f);  // F.normalize eps
     n[3 * i] = x / l; n[3 * i + 1] = y / l; n[3 * i + 2] = z / l;
 }
-template <typename IdxT>
+template <typename IdxT, int PASS>
 __global__ __launch_bounds__(256) void face_tangent_splat_kernel(const float *__restrict__ v, const float *__restrict__ uv,
-                                                                 const IdxT *__restrict__ f, long nf,
-                                                                 float *__restrict__ tan, float *__restrict__ cnt) {
+                                                                 const IdxT *__restrict__ f, long nf, long long *__restrict__ acc,
+                                                                 unsigned *__restrict__ mag, int *__restrict__ cnt) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= nf) return;
     const long i0 = f[3 * t], i1 = f[3 * t + 1], i2 = f[3 * t + 2];
@@ -103,16 +113,22 @@ __global__ __launch_bounds__(256) void face_tangent_splat_kernel(const float *__
     const long ids[3] = {i0, i1, i2};
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        atomicAdd(&tan[3 * ids[k]], tg[0]); atomicAdd(&tan[3 * ids[k] + 1], tg[1]); atomicAdd(&tan[3 * ids[k] + 2], tg[2]);
-        atomicAdd(&cnt[ids[k]], 1.0f);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            if (PASS == 0) fx_note(&mag[3 * ids[k] + r], tg[r]);
+            else fx_add(&acc[3 * ids[k] + r], mag[3 * ids[k] + r], tg[r]);
+        }
+        if (PASS == 0) atomicAdd(&cnt[ids[k]], 1);
     }
 }
-__global__ __launch_bounds__(256) void tangent_finish_kernel(float *__restrict__ tan, const float *__restrict__ cnt,
-                                                             const float *__restrict__ nrm, long nv) {
+__global__ __launch_bounds__(256) void tangent_finish_kernel(const long long *__restrict__ acc, const unsigned *__restrict__ mag,
+                                                             const int *__restrict__ cnt, const float *__restrict__ nrm,
+                                                             float *__restrict__ tan, long nv) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= nv) return;
-    const float c = cnt[i];
-    float x = tan[3 * i] / c, y = tan[3 * i + 1] / c, z = tan[3 * i + 2] / c;  // tangents / tansum
+    const float c = (float)cnt[i];
+    // tangents / tansum
+    float x = fx_value(acc[3 * i], mag[3 * i]) / c, y = fx_value(acc[3 * i + 1], mag[3 * i + 1]) / c, z = fx_value(acc[3 * i + 2], mag[3 * i + 2]) / c;
     float l = fmaxf(sqrtf(x * x + y * y + z * z), 1e-12f);
     x /= l; y /= l; z /= l;
     const float nx = nrm[3 * i], ny = nrm[3 * i + 1], nz = nrm[3 * i + 2];
@@ -120,6 +136,25 @@ __global__ __launch_bounds__(256) void tangent_finish_kernel(float *__restrict__
     x -= d * nx; y -= d * ny; z -= d * nz;
     l = fmaxf(sqrtf(x * x + y * y + z * z), 1e-12f);
     tan[3 * i] = x / l; tan[3 * i + 1] = y / l; tan[3 * i + 2] = z / l;
+}
+
+template <typename IdxT>
+void vertex_normals_launch(const float *v_pos, long nv, const IdxT *F, long nf, long long *acc, unsigned *mag, float *out, hipStream_t st) {
+    if (nf) {
+        hipLaunchKernelGGL((face_normal_splat_kernel<IdxT, 0>), dim3(cdiv(nf, 256)), dim3(256), 0, st, v_pos, F, nf, acc, mag);
+        hipLaunchKernelGGL((face_normal_splat_kernel<IdxT, 1>), dim3(cdiv(nf, 256)), dim3(256), 0, st, v_pos, F, nf, acc, mag);
+    }
+    if (nv) hipLaunchKernelGGL(normal_finish_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, st, acc, mag, out, nv);
+}
+
+template <typename IdxT>
+void vertex_tangents_launch(const float *v_pos, const float *v_tex, const float *v_nrm, long nv, const IdxT *F, long nf, long long *acc,
+                            unsigned *mag, int *cnt, float *out, hipStream_t st) {
+    if (nf) {
+        hipLaunchKernelGGL((face_tangent_splat_kernel<IdxT, 0>), dim3(cdiv(nf, 256)), dim3(256), 0, st, v_pos, v_tex, F, nf, acc, mag, cnt);
+        hipLaunchKernelGGL((face_tangent_splat_kernel<IdxT, 1>), dim3(cdiv(nf, 256)), dim3(256), 0, st, v_pos, v_tex, F, nf, acc, mag, cnt);
+    }
+    if (nv) hipLaunchKernelGGL(tangent_finish_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, st, acc, mag, cnt, v_nrm, out, nv);
 }
 
 }  // namespace sculpt
@@ -150,41 +185,35 @@ int sculpt_dilate_fill(const float *img, const float *mask, int H, int W, int it
     return 0;
 }
 
-int sculpt_vertex_normals(const float *v_pos, size_t nv, const void *faces, int faces_i64, size_t nf, float *out,
+size_t sculpt_vertex_accumulate_workspace_bytes(size_t nv) { return vertex_accumulate_workspace_bytes(nv); }
+
+int sculpt_vertex_normals(const float *v_pos, size_t nv, const void *faces, int faces_i64, size_t nf, void *workspace, float *out,
                           sculpt_stream_t stream) {
-    SC_REQUIRE(v_pos && faces && out, "vertex_normals: null argument");
+    SC_REQUIRE(v_pos && faces && out && (workspace || !nv), "vertex_normals: null argument");
     hipStream_t st = as_stream(stream);
-    SC_HIP(hipMemsetAsync(out, 0, 3 * nv * sizeof(float), st));
-    if (nf) {
-        if (faces_i64)
-            hipLaunchKernelGGL(face_normal_splat_kernel<long long>, dim3(cdiv((long)nf, 256)), dim3(256), 0, st, v_pos,
-                               reinterpret_cast<const long long *>(faces), (long)nf, out);
-        else
-            hipLaunchKernelGGL(face_normal_splat_kernel<int>, dim3(cdiv((long)nf, 256)), dim3(256), 0, st, v_pos,
-                               reinterpret_cast<const int *>(faces), (long)nf, out);
-        SC_LAUNCH_CHECK();
-    }
-    if (nv) hipLaunchKernelGGL(normal_finish_kernel, dim3(cdiv((long)nv, 256)), dim3(256), 0, st, out, (long)nv);
+    long long *acc = static_cast<long long *>(workspace);
+    unsigned *mag = reinterpret_cast<unsigned *>(acc + 3 * nv);
+    if (nv) SC_HIP(hipMemsetAsync(workspace, 0, vertex_accumulate_workspace_bytes(nv), st));
+    if (faces_i64)
+        vertex_normals_launch(v_pos, (long)nv, reinterpret_cast<const long long *>(faces), (long)nf, acc, mag, out, st);
+    else
+        vertex_normals_launch(v_pos, (long)nv, reinterpret_cast<const int *>(faces), (long)nf, acc, mag, out, st);
     SC_LAUNCH_CHECK();
     return 0;
 }
 
 int sculpt_vertex_tangents(const float *v_pos, const float *v_tex, const float *v_nrm, size_t nv, const void *faces,
-                           int faces_i64, size_t nf, float *count_scratch, float *out, sculpt_stream_t stream) {
-    SC_REQUIRE(v_pos && v_tex && v_nrm && faces && out && count_scratch, "vertex_tangents: null argument");
+                           int faces_i64, size_t nf, void *workspace, float *out, sculpt_stream_t stream) {
+    SC_REQUIRE(v_pos && v_tex && v_nrm && faces && out && (workspace || !nv), "vertex_tangents: null argument");
     hipStream_t st = as_stream(stream);
-    SC_HIP(hipMemsetAsync(out, 0, 3 * nv * sizeof(float), st));
-    SC_HIP(hipMemsetAsync(count_scratch, 0, nv * sizeof(float), st));
-    if (nf) {
-        if (faces_i64)
-            hipLaunchKernelGGL(face_tangent_splat_kernel<long long>, dim3(cdiv((long)nf, 256)), dim3(256), 0, st, v_pos, v_tex,
-                               reinterpret_cast<const long long *>(faces), (long)nf, out, count_scratch);
-        else
-            hipLaunchKernelGGL(face_tangent_splat_kernel<int>, dim3(cdiv((long)nf, 256)), dim3(256), 0, st, v_pos, v_tex,
-                               reinterpret_cast<const int *>(faces), (long)nf, out, count_scratch);
-        SC_LAUNCH_CHECK();
-    }
-    if (nv) hipLaunchKernelGGL(tangent_finish_kernel, dim3(cdiv((long)nv, 256)), dim3(256), 0, st, out, count_scratch, v_nrm, (long)nv);
+    long long *acc = static_cast<long long *>(workspace);
+    unsigned *mag = reinterpret_cast<unsigned *>(acc + 3 * nv);
+    int *cnt = reinterpret_cast<int *>(mag + 3 * nv);
+    if (nv) SC_HIP(hipMemsetAsync(workspace, 0, vertex_accumulate_workspace_bytes(nv), st));
+    if (faces_i64)
+        vertex_tangents_launch(v_pos, v_tex, v_nrm, (long)nv, reinterpret_cast<const long long *>(faces), (long)nf, acc, mag, cnt, out, st);
+    else
+        vertex_tangents_launch(v_pos, v_tex, v_nrm, (long)nv, reinterpret_cast<const int *>(faces), (long)nf, acc, mag, cnt, out, st);
     SC_LAUNCH_CHECK();
     return 0;
 }

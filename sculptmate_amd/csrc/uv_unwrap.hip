@@ -18,17 +18,35 @@
 //                              _distribute_individual_uvs_in_atlas (:177-237, 383-527)
 //
 // All of it is HBM-bound gather / scatter work: one thread per face or vertex, 32-bit atomics on ordered-float keys for
-// the min / max reductions (order independent, exact), double atomics for the few sums, ballot + popcount for ranks.
+// the min / max reductions (order independent, exact), ballot + popcount for ranks.  Every stage is reproducible to the
+// bit: the per-vertex tangents are fixed-point sums (fixsum.h), the moments and the chart sums are per-block partials added
+// in block order by one wave.  The file is compiled without FMA contraction (pragma below), so the float32 arithmetic that
+// tests/_uvref.py restates bit for bit rounds where it is written.
 #include <float.h>
 #include <math.h>
 
 #include <vector>
 
 #include "common.h"
+#include "fixsum.h"
+
+// HIP's __fadd_rn / __fsub_rn / __fmul_rn are plain operators defined in a header that hipcc compiles with FMA contraction
+// on, so a __fadd_rn of a __fmul_rn may still become one fused multiply-add.  What keeps the arithmetic of this file from
+// fusing is this pragma: every operator written below it rounds on its own.  rn_add / rn_sub / rn_mul add nothing to it;
+// they mark the arithmetic that tests/_uvref.py restates bit for bit.
+#pragma clang fp contract(off)
 
 namespace sculpt {
 
 namespace {
+
+__device__ __forceinline__ float rn_add(float a, float b) { return a + b; }
+__device__ __forceinline__ float rn_sub(float a, float b) { return a - b; }
+__device__ __forceinline__ float rn_mul(float a, float b) { return a * b; }
+// __fsqrt_rn compiles to the native v_sqrt_f32, which is not correctly rounded; sqrtf is, but only as long as hipcc's
+// default -fhip-fp32-correctly-rounded-divide-sqrt holds.  The fp64 square root of a float, rounded to float, is correctly
+// rounded whatever that flag says (53 >= 2 * 24 + 2 bits).
+__device__ __forceinline__ float rn_sqrt(float x) { return (float)sqrt((double)x); }
 
 constexpr int UVB = 256;
 
@@ -86,8 +104,20 @@ __device__ __forceinline__ double block_sum(double v, double *sh) {
     return t;
 }
 
+// sums[i] = the blocks' partials [nb][nvals], added in block order (one wave: the result does not depend on scheduling)
+__global__ __launch_bounds__(64) void uv_partials_reduce_kernel(const double *__restrict__ partial, int nb, int nvals, double *__restrict__ sums) {
+    const int i = threadIdx.x;
+    if (i >= nvals) return;
+    double t = 0.0;
+    for (int b = 0; b < nb; ++b) t += partial[(size_t)b * nvals + i];
+    sums[i] = t;
+}
+
 // ---------------------------------------------------------------------------------------------- moments
-__global__ __launch_bounds__(UVB) void uv_moments_kernel(const float *__restrict__ v, long nv, double *__restrict__ out) {
+// workspace of sculpt_uv_moments: partials [MOM_MAX_BLOCKS][9] doubles
+constexpr int MOM_MAX_BLOCKS = 1024;
+
+__global__ __launch_bounds__(UVB) void uv_moments_kernel(const float *__restrict__ v, long nv, double *__restrict__ partial) {
     __shared__ double sh[UVB / 64];
     double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // x y z xx xy xz yy yz zz
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
@@ -98,7 +128,7 @@ __global__ __launch_bounds__(UVB) void uv_moments_kernel(const float *__restrict
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
         const double t = block_sum(s[k], sh);
-        if (threadIdx.x == 0) atomicAdd(&out[k], t);
+        if (threadIdx.x == 0) partial[(size_t)blockIdx.x * 9 + k] = t;
     }
 }
 
@@ -113,8 +143,8 @@ __global__ __launch_bounds__(UVB) void uv_rotate_mesh_kernel(const float *__rest
         const float n[3] = {nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]};
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
-            const float a = __fadd_rn(__fadd_rn(__fmul_rn(R.m[3 * r], p[0]), __fmul_rn(R.m[3 * r + 1], p[1])), __fmul_rn(R.m[3 * r + 2], p[2]));
-            const float b = __fadd_rn(__fadd_rn(__fmul_rn(R.m[3 * r], n[0]), __fmul_rn(R.m[3 * r + 1], n[1])), __fmul_rn(R.m[3 * r + 2], n[2]));
+            const float a = rn_add(rn_add(rn_mul(R.m[3 * r], p[0]), rn_mul(R.m[3 * r + 1], p[1])), rn_mul(R.m[3 * r + 2], p[2]));
+            const float b = rn_add(rn_add(rn_mul(R.m[3 * r], n[0]), rn_mul(R.m[3 * r + 1], n[1])), rn_mul(R.m[3 * r + 2], n[2]));
             rpos[3 * i + r] = a;
             rnrm[3 * i + r] = b;
             mn[r] = fminf(mn[r], a);
@@ -139,7 +169,7 @@ __global__ __launch_bounds__(UVB) void uv_rotate_mesh_kernel(const float *__rest
 
 // ---------------------------------------------------------------------------------------------- box projection
 __device__ __forceinline__ float unit_coord(float p, float lo, float hi) {
-    return __fsub_rn(__fmul_rn(2.0f, __fdiv_rn(__fsub_rn(p, lo), __fsub_rn(hi, lo))), 1.0f);
+    return rn_sub(rn_mul(2.0f, __fdiv_rn(rn_sub(p, lo), rn_sub(hi, lo))), 1.0f);
 }
 
 template <typename IdxT>
@@ -160,8 +190,8 @@ __global__ __launch_bounds__(UVB) void uv_box_project_kernel(const float *__rest
             for (int r = 0; r < 3; ++r) tri[k][r] = unit_coord(rpos[3 * (long)vi[k] + r], lo[r], hi[r]);
         }
 #pragma unroll
-        for (int r = 0; r < 3; ++r) ns[r] = __fadd_rn(__fadd_rn(rnrm[3 * (long)vi[0] + r], rnrm[3 * (long)vi[1] + r]), rnrm[3 * (long)vi[2] + r]);
-        const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(ns[0], ns[0]), __fmul_rn(ns[1], ns[1])), __fmul_rn(ns[2], ns[2])));
+        for (int r = 0; r < 3; ++r) ns[r] = rn_add(rn_add(rnrm[3 * (long)vi[0] + r], rnrm[3 * (long)vi[1] + r]), rnrm[3 * (long)vi[2] + r]);
+        const float len = rn_sqrt(rn_add(rn_add(rn_mul(ns[0], ns[0]), rn_mul(ns[1], ns[1])), rn_mul(ns[2], ns[2])));
         const float inv = fmaxf(len, 1e-6f);
         const float fn[3] = {__fdiv_rn(ns[0], inv), __fdiv_rn(ns[1], inv), __fdiv_rn(ns[2], inv)};
         // argmax over (+x, -x, +y, -y, +z, -z) of the component along that direction; first maximum wins
@@ -195,70 +225,91 @@ __global__ __launch_bounds__(UVB) void uv_box_finish_kernel(float *__restrict__ 
     const float div[3] = {uv_ord2f(st[ST_DIV]), uv_ord2f(st[ST_DIV + 1]), uv_ord2f(st[ST_DIV + 2])};
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nf * 6; i += (long)gridDim.x * blockDim.x) {
         const int k = (int)((i % 6) >> 1);
-        const float x = __fmul_rn(__fadd_rn(__fdiv_rn(face_uv[i], div[k]), 1.0f), 0.5f);
+        const float x = rn_mul(rn_add(__fdiv_rn(face_uv[i], div[k]), 1.0f), 0.5f);
         face_uv[i] = fminf(fmaxf(x, 0.f), 1.f);
     }
 }
 
 // ---------------------------------------------------------------------------------------------- tangents
-template <typename IdxT>
+// workspace of sculpt_uv_chart_tangents: chart-sum partials [CS_MAX_BLOCKS][42] doubles, then per vertex the fixed-point tangent
+// sums int64 [nv][3], the largest |term| of each u32 [nv][3] and the corner count int [nv]
+constexpr int CS_MAX_BLOCKS = 1024;
+
+inline size_t uv_tangent_workspace_bytes(size_t nv) { return (size_t)CS_MAX_BLOCKS * 42 * sizeof(double) + nv * (24 + 12 + 4); }
+
+// PASS 0: the largest |term| of every sum and the corner counts; PASS 1: the fixed-point sums
+template <typename IdxT, int PASS>
 __global__ __launch_bounds__(UVB) void uv_face_tangent_kernel(const float *__restrict__ rpos, const IdxT *__restrict__ faces, long nf,
-                                                              const float *__restrict__ face_uv, float *__restrict__ acc /* [nv][4] */) {
+                                                              const float *__restrict__ face_uv, long long *__restrict__ acc,
+                                                              unsigned *__restrict__ mag, int *__restrict__ cnt) {
     for (long f = (long)blockIdx.x * blockDim.x + threadIdx.x; f < nf; f += (long)gridDim.x * blockDim.x) {
         int vi[3];
         load_face(faces, f, vi[0], vi[1], vi[2]);
         const float *t = face_uv + 6 * f;
-        const float du1 = t[2] - t[0], dv1 = t[3] - t[1], du2 = t[4] - t[0], dv2 = t[5] - t[1];
-        const float den = fmaxf(__fsub_rn(__fmul_rn(du1, dv2), __fmul_rn(dv1, du2)), 1e-6f);  // clip(1e-6): negatives too
+        const float du1 = rn_sub(t[2], t[0]), dv1 = rn_sub(t[3], t[1]), du2 = rn_sub(t[4], t[0]), dv2 = rn_sub(t[5], t[1]);
+        const float den = fmaxf(rn_sub(rn_mul(du1, dv2), rn_mul(dv1, du2)), 1e-6f);  // clip(1e-6): negatives too
         float tg[3];
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             const float p0 = rpos[3 * (long)vi[0] + r];
-            const float d1 = rpos[3 * (long)vi[1] + r] - p0, d2 = rpos[3 * (long)vi[2] + r] - p0;
-            tg[r] = __fdiv_rn(__fsub_rn(__fmul_rn(d1, dv2), __fmul_rn(d2, dv1)), den);
+            const float d1 = rn_sub(rpos[3 * (long)vi[1] + r], p0), d2 = rn_sub(rpos[3 * (long)vi[2] + r], p0);
+            tg[r] = __fdiv_rn(rn_sub(rn_mul(d1, dv2), rn_mul(d2, dv1)), den);
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            float *a = acc + 4 * (long)vi[k];
-            atomicAdd(a, tg[0]);
-            atomicAdd(a + 1, tg[1]);
-            atomicAdd(a + 2, tg[2]);
-            atomicAdd(a + 3, 1.0f);
+            const long v = vi[k];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                if (PASS == 0) fx_note(&mag[3 * v + r], tg[r]);
+                else fx_add(&acc[3 * v + r], mag[3 * v + r], tg[r]);
+            }
+            if (PASS == 0) atomicAdd(&cnt[v], 1);
         }
     }
 }
 
-// acc [nv][4] (sum, count) -> (tangent perpendicular to the normal, unused)
-__global__ __launch_bounds__(UVB) void uv_vertex_tangent_kernel(float *__restrict__ acc, const float *__restrict__ rnrm, long nv) {
+// (sum, count) -> vt [nv][4] = (tangent perpendicular to the normal, corner count)
+__global__ __launch_bounds__(UVB) void uv_vertex_tangent_kernel(const long long *__restrict__ acc, const unsigned *__restrict__ mag,
+                                                                const int *__restrict__ cnt_i, const float *__restrict__ rnrm, long nv,
+                                                                float *__restrict__ vt) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
-        float *a = acc + 4 * i;
-        const float cnt = a[3];
-        float t[3] = {a[0] / cnt, a[1] / cnt, a[2] / cnt};
-        float len = fmaxf(sqrtf(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]), 1e-12f);
-        t[0] /= len; t[1] /= len; t[2] /= len;
+        const float cnt = (float)cnt_i[i];
+        float t[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) t[r] = __fdiv_rn(fx_value(acc[3 * i + r], mag[3 * i + r]), cnt);
+        float len = fmaxf(rn_sqrt(rn_add(rn_add(rn_mul(t[0], t[0]), rn_mul(t[1], t[1])), rn_mul(t[2], t[2]))), 1e-12f);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) t[r] = __fdiv_rn(t[r], len);
         const float n[3] = {rnrm[3 * i], rnrm[3 * i + 1], rnrm[3 * i + 2]};
-        const float d = t[0] * n[0] + t[1] * n[1] + t[2] * n[2];
-        t[0] -= d * n[0]; t[1] -= d * n[1]; t[2] -= d * n[2];
-        len = fmaxf(sqrtf(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]), 1e-12f);
-        a[0] = t[0] / len; a[1] = t[1] / len; a[2] = t[2] / len;
+        const float d = rn_add(rn_add(rn_mul(t[0], n[0]), rn_mul(t[1], n[1])), rn_mul(t[2], n[2]));
+#pragma unroll
+        for (int r = 0; r < 3; ++r) t[r] = rn_sub(t[r], rn_mul(d, n[r]));
+        len = fmaxf(rn_sqrt(rn_add(rn_add(rn_mul(t[0], t[0]), rn_mul(t[1], t[1])), rn_mul(t[2], t[2]))), 1e-12f);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) vt[4 * i + r] = __fdiv_rn(t[r], len);
+        vt[4 * i + 3] = cnt;
     }
 }
 
+__device__ __forceinline__ float uv_cross_term(float a, float b, float c, float d) { return rn_sub(rn_mul(a, b), rn_mul(c, d)); }
+
 __device__ __forceinline__ void expected_tangent(const float *p, const float *n, float *e) {
     const float s[3] = {-p[1], p[0], 0.f};
-    const float c1[3] = {s[1] * n[2] - s[2] * n[1], s[2] * n[0] - s[0] * n[2], s[0] * n[1] - s[1] * n[0]};       // side x n
-    const float c2[3] = {n[1] * c1[2] - n[2] * c1[1], n[2] * c1[0] - n[0] * c1[2], n[0] * c1[1] - n[1] * c1[0]};  // n x (side x n)
+    const float c1[3] = {uv_cross_term(s[1], n[2], s[2], n[1]), uv_cross_term(s[2], n[0], s[0], n[2]),
+                         uv_cross_term(s[0], n[1], s[1], n[0])};  // side x n
+    const float c2[3] = {uv_cross_term(n[1], c1[2], n[2], c1[1]), uv_cross_term(n[2], c1[0], n[0], c1[2]),
+                         uv_cross_term(n[0], c1[1], n[1], c1[0])};  // n x (side x n)
     // F.normalize(x, -1): p = -1 "norm" = 1 / (1/|x| + 1/|y| + 1/|z|), clamped at 1e-12
-    const float inv = 1.0f / fabsf(c2[0]) + 1.0f / fabsf(c2[1]) + 1.0f / fabsf(c2[2]);
-    const float nm = fmaxf(1.0f / inv, 1e-12f);
-    e[0] = c2[0] / nm; e[1] = c2[1] / nm; e[2] = c2[2] / nm;
+    const float inv = rn_add(rn_add(__fdiv_rn(1.0f, fabsf(c2[0])), __fdiv_rn(1.0f, fabsf(c2[1]))), __fdiv_rn(1.0f, fabsf(c2[2])));
+    const float nm = fmaxf(__fdiv_rn(1.0f, inv), 1e-12f);
+    e[0] = __fdiv_rn(c2[0], nm); e[1] = __fdiv_rn(c2[1], nm); e[2] = __fdiv_rn(c2[2], nm);
 }
 
 // sums [6][7] doubles: sum of the corner tangents (3), of the expected tangents (3), number of corners
 template <typename IdxT>
 __global__ __launch_bounds__(UVB) void uv_chart_sums_kernel(const float *__restrict__ rpos, const float *__restrict__ rnrm,
                                                             const IdxT *__restrict__ faces, long nf, const int *__restrict__ chart,
-                                                            const float *__restrict__ vt /* [nv][4] */, double *__restrict__ sums) {
+                                                            const float *__restrict__ vt /* [nv][4] */, double *__restrict__ partial) {
     __shared__ double sh[UVB / 64];
     double loc[6][7];
 #pragma unroll
@@ -290,9 +341,10 @@ __global__ __launch_bounds__(UVB) void uv_chart_sums_kernel(const float *__restr
 #pragma unroll
         for (int k = 0; k < 7; ++k) {
             const double t = block_sum(loc[c][k], sh);
-            if (threadIdx.x == 0 && t != 0.0) atomicAdd(&sums[c * 7 + k], t);
+            if (threadIdx.x == 0) partial[(size_t)blockIdx.x * 42 + c * 7 + k] = t;
         }
 }
+
 
 // ---------------------------------------------------------------------------------------------- chart rotation
 struct Rot2x6 { float c[6], s[6]; };
@@ -311,10 +363,10 @@ __global__ __launch_bounds__(UVB) void uv_rotate_chart_kernel(float *__restrict_
         float lo = FLT_MAX, hi = -FLT_MAX;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const float x = __fsub_rn(__fmul_rn(face_uv[6 * f + 2 * k], 2.0f), 1.0f);
-            const float y = __fsub_rn(__fmul_rn(face_uv[6 * f + 2 * k + 1], 2.0f), 1.0f);
-            const float u = __fadd_rn(__fmul_rn(co, x), __fmul_rn(-si, y));
-            const float v = __fadd_rn(__fmul_rn(si, x), __fmul_rn(co, y));
+            const float x = rn_sub(rn_mul(face_uv[6 * f + 2 * k], 2.0f), 1.0f);
+            const float y = rn_sub(rn_mul(face_uv[6 * f + 2 * k + 1], 2.0f), 1.0f);
+            const float u = rn_add(rn_mul(co, x), rn_mul(-si, y));
+            const float v = rn_add(rn_mul(si, x), rn_mul(co, y));
             face_uv[6 * f + 2 * k] = u;
             face_uv[6 * f + 2 * k + 1] = v;
             lo = fminf(lo, fminf(u, v));
@@ -345,9 +397,9 @@ __global__ __launch_bounds__(UVB) void uv_rescale_chart_kernel(float *__restrict
     for (long f = (long)blockIdx.x * blockDim.x + threadIdx.x; f < nf; f += (long)gridDim.x * blockDim.x) {
         const int c = chart[f] % 6;
         const float lo = uv_ord2f(st[ST_CH_MIN + c]), hi = uv_ord2f(st[ST_CH_MAX + c]);
-        const float span = __fsub_rn(hi, lo);
+        const float span = rn_sub(hi, lo);
 #pragma unroll
-        for (int k = 0; k < 6; ++k) face_uv[6 * f + k] = __fdiv_rn(__fsub_rn(face_uv[6 * f + k], lo), span);
+        for (int k = 0; k < 6; ++k) face_uv[6 * f + k] = __fdiv_rn(rn_sub(face_uv[6 * f + k], lo), span);
     }
 }
 
@@ -366,24 +418,26 @@ struct TriRaster {
 __device__ __forceinline__ TriRaster make_raster(const float *t, int res) {
     TriRaster r;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { r.x[k] = t[2 * k] * res; r.y[k] = t[2 * k + 1] * res; }
-    const float area = (r.x[1] - r.x[0]) * (r.y[2] - r.y[0]) - (r.x[2] - r.x[0]) * (r.y[1] - r.y[0]);
+    for (int k = 0; k < 3; ++k) { r.x[k] = rn_mul(t[2 * k], (float)res); r.y[k] = rn_mul(t[2 * k + 1], (float)res); }
+    const float area = rn_sub(rn_mul(rn_sub(r.x[1], r.x[0]), rn_sub(r.y[2], r.y[0])),
+                                 rn_mul(rn_sub(r.x[2], r.x[0]), rn_sub(r.y[1], r.y[0])));
     r.degenerate = fabsf(area) < 1e-12f;
-    r.inv_area = r.degenerate ? 0.f : 1.0f / area;
+    r.inv_area = r.degenerate ? 0.f : __fdiv_rn(1.0f, area);
     const float xmin = fminf(r.x[0], fminf(r.x[1], r.x[2])), xmax = fmaxf(r.x[0], fmaxf(r.x[1], r.x[2]));
     const float ymin = fminf(r.y[0], fminf(r.y[1], r.y[2])), ymax = fmaxf(r.y[0], fmaxf(r.y[1], r.y[2]));
-    r.x0 = max(0, (int)floorf(xmin - 0.5f));
-    r.x1 = min(res - 1, (int)ceilf(xmax - 0.5f));
-    r.y0 = max(0, (int)floorf(ymin - 0.5f));
-    r.y1 = min(res - 1, (int)ceilf(ymax - 0.5f));
+    r.x0 = max(0, (int)floorf(rn_sub(xmin, 0.5f)));
+    r.x1 = min(res - 1, (int)ceilf(rn_sub(xmax, 0.5f)));
+    r.y0 = max(0, (int)floorf(rn_sub(ymin, 0.5f)));
+    r.y1 = min(res - 1, (int)ceilf(rn_sub(ymax, 0.5f)));
     return r;
 }
 
 __device__ __forceinline__ bool inside_strict(const TriRaster &r, float px, float py) {
     if (r.degenerate) return false;
-    const float l1 = ((px - r.x[0]) * (r.y[2] - r.y[0]) - (r.x[2] - r.x[0]) * (py - r.y[0])) * r.inv_area;
-    const float l2 = ((r.x[1] - r.x[0]) * (py - r.y[0]) - (px - r.x[0]) * (r.y[1] - r.y[0])) * r.inv_area;
-    return l1 > EDGE_EPS && l2 > EDGE_EPS && (1.0f - l1 - l2) > EDGE_EPS;
+    const float dx = rn_sub(px, r.x[0]), dy = rn_sub(py, r.y[0]);
+    const float l1 = rn_mul(uv_cross_term(dx, rn_sub(r.y[2], r.y[0]), rn_sub(r.x[2], r.x[0]), dy), r.inv_area);
+    const float l2 = rn_mul(uv_cross_term(rn_sub(r.x[1], r.x[0]), dy, dx, rn_sub(r.y[1], r.y[0])), r.inv_area);
+    return l1 > EDGE_EPS && l2 > EDGE_EPS && rn_sub(rn_sub(1.0f, l1), l2) > EDGE_EPS;
 }
 
 __device__ __forceinline__ unsigned long long zkey(float depth, long f) {
@@ -403,7 +457,7 @@ __global__ __launch_bounds__(UVB) void uv_zbuffer_kernel(const float *__restrict
         int vi[3];
         load_face(faces, f, vi[0], vi[1], vi[2]);
         const int ax = c >> 1;
-        const float cen = (rpos[3 * (long)vi[0] + ax] + rpos[3 * (long)vi[1] + ax] + rpos[3 * (long)vi[2] + ax]) * (1.0f / 3.0f);
+        const float cen = rn_mul(rn_add(rn_add(rpos[3 * (long)vi[0] + ax], rpos[3 * (long)vi[1] + ax]), rpos[3 * (long)vi[2] + ax]), 1.0f / 3.0f);
         const unsigned long long key = zkey((c & 1) ? -cen : cen, f);   // in front = further out along the chart's direction
         const TriRaster r = make_raster(face_uv + 6 * f, res);
         unsigned long long *zb = zbuf + (size_t)c * res * res;
@@ -419,11 +473,12 @@ __global__ __launch_bounds__(UVB) void uv_zbuffer_kernel(const float *__restrict
         if (PASS == 1 && nsamples == 0) {
             // smaller than a pixel: it drew nothing; it is hidden if its centroid lies inside the triangle that owns the
             // pixel and that triangle is in front of it
-            const float cx = (r.x[0] + r.x[1] + r.x[2]) * (1.0f / 3.0f), cy = (r.y[0] + r.y[1] + r.y[2]) * (1.0f / 3.0f);
+            const float cx = rn_mul(rn_add(rn_add(r.x[0], r.x[1]), r.x[2]), 1.0f / 3.0f);
+            const float cy = rn_mul(rn_add(rn_add(r.y[0], r.y[1]), r.y[2]), 1.0f / 3.0f);
             const int px = min(res - 1, max(0, (int)cx)), py = min(res - 1, max(0, (int)cy));
             const unsigned long long w = zb[(size_t)py * res + px];
-            if (w > key) {
-                const long wf = (long)(0xffffffffu - (unsigned)(w & 0xffffffffull));
+            const long wf = (long)(0xffffffffu - (unsigned)(w & 0xffffffffull));
+            if (w > key && wf < nf) {  // a key this kernel wrote always names a face; never read past face_uv
                 const TriRaster rw = make_raster(face_uv + 6 * wf, res);
                 lost = inside_strict(rw, cx, cy);
             }
@@ -542,15 +597,15 @@ __global__ __launch_bounds__(UVB) void uv_place_kernel(const float *__restrict__
     if (a >= 6 && a < 12) {  // _handle_slice_uvs: fill the patch, at most 2x magnified
         const float ulo = uv_ord2f(st[ST_SL_UMIN + a - 6]), uhi = uv_ord2f(st[ST_SL_UMAX + a - 6]);
         const float vlo = uv_ord2f(st[ST_SL_VMIN + a - 6]), vhi = uv_ord2f(st[ST_SL_VMAX + a - 6]);
-        const float us = fmaxf(__fsub_rn(uhi, ulo), 0.5f), vs = fmaxf(__fsub_rn(vhi, vlo), 0.5f);
+        const float us = fmaxf(rn_sub(uhi, ulo), 0.5f), vs = fmaxf(rn_sub(vhi, vlo), 0.5f);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { uc[k] = __fdiv_rn(__fsub_rn(uc[k], ulo), us); vc[k] = __fdiv_rn(__fsub_rn(vc[k], vlo), vs); }
+        for (int k = 0; k < 3; ++k) { uc[k] = __fdiv_rn(rn_sub(uc[k], ulo), us); vc[k] = __fdiv_rn(rn_sub(vc[k], vlo), vs); }
     }
     const float m1 = (float)(1.0 - 2.0 * pad), a1 = (float)pad;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        uc[k] = clamp01(__fadd_rn(__fmul_rn(uc[k], m1), a1));
-        vc[k] = clamp01(__fadd_rn(__fmul_rn(vc[k], m1), a1));
+        uc[k] = clamp01(rn_add(rn_mul(uc[k], m1), a1));
+        vc[k] = clamp01(rn_add(rn_mul(vc[k], m1), a1));
     }
     if (rem) {  // _handle_remaining_uvs: every triangle in its own cell of an nw x nh grid
         const double left = (double)st[ST_REMAINING];
@@ -560,20 +615,20 @@ __global__ __launch_bounds__(UVB) void uv_place_kernel(const float *__restrict__
         const float lim = (float)(fmin(w, h) * 1.5);
         const float ulo = fminf(uc[0], fminf(uc[1], uc[2])), uhi = fmaxf(uc[0], fmaxf(uc[1], uc[2]));
         const float vlo = fminf(vc[0], fminf(vc[1], vc[2])), vhi = fmaxf(vc[0], fmaxf(vc[1], vc[2]));
-        const float us = fmaxf(__fsub_rn(uhi, ulo), lim), vs = fmaxf(__fsub_rn(vhi, vlo), lim);
+        const float us = fmaxf(rn_sub(uhi, ulo), lim), vs = fmaxf(rn_sub(vhi, vlo), lim);
         const float mu = (float)(1.0 - pad * nw * 0.5), au = (float)(pad * nw * 0.25);
         const float mv = (float)(1.0 - pad * nh * 0.5), av = (float)(pad * nh * 0.25);
         const float wf = (float)w, hf = (float)h;
-        const float xo = __fmul_rn((float)(rank % nw), wf), yo = __fmul_rn((float)(rank / nw), hf);
+        const float xo = rn_mul((float)(rank % nw), wf), yo = rn_mul((float)(rank / nw), hf);
         const float m2 = (float)(1.0 - 2.0 * pad * 0.5), a2 = (float)(pad * 0.5);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            float u = clamp01(__fadd_rn(__fmul_rn(__fdiv_rn(__fsub_rn(uc[k], ulo), us), mu), au));
-            float v = clamp01(__fadd_rn(__fmul_rn(__fdiv_rn(__fsub_rn(vc[k], vlo), vs), mv), av));
-            u = __fadd_rn(__fmul_rn(u, wf), xo);
-            v = __fadd_rn(__fmul_rn(v, hf), yo);
-            uc[k] = clamp01(__fadd_rn(__fmul_rn(u, m2), a2));
-            vc[k] = clamp01(__fadd_rn(__fmul_rn(v, m2), a2));
+            float u = clamp01(rn_add(rn_mul(__fdiv_rn(rn_sub(uc[k], ulo), us), mu), au));
+            float v = clamp01(rn_add(rn_mul(__fdiv_rn(rn_sub(vc[k], vlo), vs), mv), av));
+            u = rn_add(rn_mul(u, wf), xo);
+            v = rn_add(rn_mul(v, hf), yo);
+            uc[k] = clamp01(rn_add(rn_mul(u, m2), a2));
+            vc[k] = clamp01(rn_add(rn_mul(v, m2), a2));
         }
     }
     // _find_slice_offset_and_scale
@@ -592,12 +647,24 @@ __global__ __launch_bounds__(UVB) void uv_place_kernel(const float *__restrict__
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        out[6 * f + 2 * k] = __fadd_rn(__fdiv_rn(uc[k], dx), ox);
-        out[6 * f + 2 * k + 1] = __fadd_rn(__fdiv_rn(vc[k], dy), oy);
+        out[6 * f + 2 * k] = rn_add(__fdiv_rn(uc[k], dx), ox);
+        out[6 * f + 2 * k + 1] = rn_add(__fdiv_rn(vc[k], dy), oy);
     }
 }
 
 inline int uv_grid(long n) { return (int)std::max<long>(1, std::min<long>((n + UVB - 1) / UVB, (long)num_cus() * 32)); }
+
+template <typename IdxT>
+void uv_chart_tangents_launch(const float *rot_pos, const float *rot_nrm, long nv, const IdxT *F, long nf, const float *face_uv,
+                                     const int *chart, float *vt, double *sums42, double *partial, long long *acc, unsigned *mag,
+                                     int *cnt, hipStream_t st) {
+    const int nb = std::min(uv_grid(nf), CS_MAX_BLOCKS);
+    hipLaunchKernelGGL((uv_face_tangent_kernel<IdxT, 0>), dim3(uv_grid(nf)), dim3(UVB), 0, st, rot_pos, F, nf, face_uv, acc, mag, cnt);
+    hipLaunchKernelGGL((uv_face_tangent_kernel<IdxT, 1>), dim3(uv_grid(nf)), dim3(UVB), 0, st, rot_pos, F, nf, face_uv, acc, mag, cnt);
+    hipLaunchKernelGGL(uv_vertex_tangent_kernel, dim3(uv_grid(nv)), dim3(UVB), 0, st, acc, mag, cnt, rot_nrm, nv, vt);
+    hipLaunchKernelGGL(uv_chart_sums_kernel<IdxT>, dim3(nb), dim3(UVB), 0, st, rot_pos, rot_nrm, F, nf, chart, vt, partial);
+    hipLaunchKernelGGL(uv_partials_reduce_kernel, dim3(1), dim3(64), 0, st, partial, nb, 42, sums42);
+}
 
 }  // namespace
 
@@ -609,11 +676,15 @@ extern "C" {
 
 size_t sculpt_uv_stats_words(void) { return (size_t)ST_WORDS; }
 
-int sculpt_uv_moments(const float *v_pos, size_t nv, double *sums9, sculpt_stream_t stream) {
-    SC_REQUIRE(v_pos && sums9 && nv >= 1, "uv_moments: bad argument");
+size_t sculpt_uv_moments_workspace_bytes(void) { return (size_t)MOM_MAX_BLOCKS * 9 * sizeof(double); }
+
+int sculpt_uv_moments(const float *v_pos, size_t nv, double *sums9, void *workspace, sculpt_stream_t stream) {
+    SC_REQUIRE(v_pos && sums9 && workspace && nv >= 1, "uv_moments: bad argument");
     hipStream_t st = as_stream(stream);
-    SC_HIP(hipMemsetAsync(sums9, 0, 9 * sizeof(double), st));
-    hipLaunchKernelGGL(uv_moments_kernel, dim3(uv_grid((long)nv)), dim3(UVB), 0, st, v_pos, (long)nv, sums9);
+    double *partial = static_cast<double *>(workspace);
+    const int nb = std::min(uv_grid((long)nv), MOM_MAX_BLOCKS);
+    hipLaunchKernelGGL(uv_moments_kernel, dim3(nb), dim3(UVB), 0, st, v_pos, (long)nv, partial);
+    hipLaunchKernelGGL(uv_partials_reduce_kernel, dim3(1), dim3(64), 0, st, partial, nb, 9, sums9);
     SC_LAUNCH_CHECK();
     return 0;
 }
@@ -639,25 +710,25 @@ int sculpt_uv_box_project(const float *v_pos, const float *v_nrm, size_t nv, con
     return 0;
 }
 
+size_t sculpt_uv_chart_tangents_workspace_bytes(size_t nv) { return uv_tangent_workspace_bytes(nv); }
+
 int sculpt_uv_chart_tangents(const float *rot_pos, const float *rot_nrm, size_t nv, const void *faces, int faces_i64, size_t nf,
-                             const float *face_uv, const int *chart, float *vertex_tangents4, double *sums42, sculpt_stream_t stream) {
-    SC_REQUIRE(rot_pos && rot_nrm && faces && face_uv && chart && vertex_tangents4 && sums42, "uv_chart_tangents: null argument");
+                             const float *face_uv, const int *chart, float *vertex_tangents4, double *sums42, void *workspace,
+                             sculpt_stream_t stream) {
+    SC_REQUIRE(rot_pos && rot_nrm && faces && face_uv && chart && vertex_tangents4 && sums42 && workspace, "uv_chart_tangents: null argument");
+    SC_REQUIRE(nv >= 1 && nf >= 1, "uv_chart_tangents: empty mesh");
     hipStream_t st = as_stream(stream);
-    SC_HIP(hipMemsetAsync(vertex_tangents4, 0, nv * 4 * sizeof(float), st));
-    SC_HIP(hipMemsetAsync(sums42, 0, 42 * sizeof(double), st));
-    if (faces_i64) {
-        const long long *F = reinterpret_cast<const long long *>(faces);
-        hipLaunchKernelGGL(uv_face_tangent_kernel<long long>, dim3(uv_grid((long)nf)), dim3(UVB), 0, st, rot_pos, F, (long)nf, face_uv, vertex_tangents4);
-        hipLaunchKernelGGL(uv_vertex_tangent_kernel, dim3(uv_grid((long)nv)), dim3(UVB), 0, st, vertex_tangents4, rot_nrm, (long)nv);
-        hipLaunchKernelGGL(uv_chart_sums_kernel<long long>, dim3(std::min(uv_grid((long)nf), 1024)), dim3(UVB), 0, st, rot_pos, rot_nrm, F, (long)nf,
-                           chart, vertex_tangents4, sums42);
-    } else {
-        const int *F = reinterpret_cast<const int *>(faces);
-        hipLaunchKernelGGL(uv_face_tangent_kernel<int>, dim3(uv_grid((long)nf)), dim3(UVB), 0, st, rot_pos, F, (long)nf, face_uv, vertex_tangents4);
-        hipLaunchKernelGGL(uv_vertex_tangent_kernel, dim3(uv_grid((long)nv)), dim3(UVB), 0, st, vertex_tangents4, rot_nrm, (long)nv);
-        hipLaunchKernelGGL(uv_chart_sums_kernel<int>, dim3(std::min(uv_grid((long)nf), 1024)), dim3(UVB), 0, st, rot_pos, rot_nrm, F, (long)nf, chart,
-                           vertex_tangents4, sums42);
-    }
+    double *partial = static_cast<double *>(workspace);
+    long long *acc = reinterpret_cast<long long *>(partial + (size_t)CS_MAX_BLOCKS * 42);
+    unsigned *mag = reinterpret_cast<unsigned *>(acc + 3 * nv);
+    int *cnt = reinterpret_cast<int *>(mag + 3 * nv);
+    SC_HIP(hipMemsetAsync(acc, 0, nv * (24 + 12 + 4), st));
+    if (faces_i64)
+        uv_chart_tangents_launch(rot_pos, rot_nrm, (long)nv, reinterpret_cast<const long long *>(faces), (long)nf, face_uv, chart,
+                                 vertex_tangents4, sums42, partial, acc, mag, cnt, st);
+    else
+        uv_chart_tangents_launch(rot_pos, rot_nrm, (long)nv, reinterpret_cast<const int *>(faces), (long)nf, face_uv, chart,
+                                 vertex_tangents4, sums42, partial, acc, mag, cnt, st);
     SC_LAUNCH_CHECK();
     return 0;
 }

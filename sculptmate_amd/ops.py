@@ -607,8 +607,9 @@ def vertex_normals(v_pos, faces):
     """Mesh._compute_vertex_normal (sf3d/models/mesh.py:66-92)."""
     v = _req(v_pos.contiguous(), torch.float32, "v_pos")
     f = faces.contiguous()
+    ws = torch.empty(max(1, int(lib.sculpt_vertex_accumulate_workspace_bytes(v.shape[0]))), dtype=torch.uint8, device=v.device)
     out = torch.empty_like(v)
-    check(lib.sculpt_vertex_normals(_ptr(v), v.shape[0], _ptr(f), int(f.dtype == torch.int64), f.shape[0], _ptr(out), _stream()))
+    check(lib.sculpt_vertex_normals(_ptr(v), v.shape[0], _ptr(f), int(f.dtype == torch.int64), f.shape[0], _ptr(ws), _ptr(out), _stream()))
     return out
 
 
@@ -618,10 +619,10 @@ def vertex_tangents(v_pos, v_tex, v_nrm, faces):
     t = _req(v_tex.contiguous(), torch.float32, "v_tex")
     n = _req(v_nrm.contiguous(), torch.float32, "v_nrm")
     f = faces.contiguous()
-    cnt = torch.empty(v.shape[0], dtype=torch.float32, device=v.device)
+    ws = torch.empty(max(1, int(lib.sculpt_vertex_accumulate_workspace_bytes(v.shape[0]))), dtype=torch.uint8, device=v.device)
     out = torch.empty_like(v)
     check(lib.sculpt_vertex_tangents(_ptr(v), _ptr(t), _ptr(n), v.shape[0], _ptr(f), int(f.dtype == torch.int64), f.shape[0],
-                                     _ptr(cnt), _ptr(out), _stream()))
+                                     _ptr(ws), _ptr(out), _stream()))
     return out
 
 

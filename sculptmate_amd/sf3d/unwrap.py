@@ -87,7 +87,8 @@ class BoxProjectionUnwrapper:
     # ---- stages -------------------------------------------------------------------------------------------------
     def rotation(self, v_pos):
         sums = self._b("sums9", (9,), torch.float64, v_pos.device)
-        check(lib.sculpt_uv_moments(_ptr(v_pos), v_pos.shape[0], _ptr(sums), _stream()))
+        ws = self._b("moments_ws", (int(lib.sculpt_uv_moments_workspace_bytes()),), torch.uint8, v_pos.device)
+        check(lib.sculpt_uv_moments(_ptr(v_pos), v_pos.shape[0], _ptr(sums), _ptr(ws), _stream()))
         main, second = principal_axes(sums.cpu().numpy(), v_pos.shape[0])
         return axis_rotation(main, second)
 
@@ -107,8 +108,9 @@ class BoxProjectionUnwrapper:
         dev, nv, nf = rp.device, rp.shape[0], faces.shape[0]
         vt = self._b("vtan", (nv, 4), torch.float32, dev)
         sums = self._b("sums42", (6, 7), torch.float64, dev)
+        ws = self._b("tangent_ws", (int(lib.sculpt_uv_chart_tangents_workspace_bytes(nv)),), torch.uint8, dev)
         check(lib.sculpt_uv_chart_tangents(_ptr(rp), _ptr(rn), nv, _ptr(faces), int(faces.dtype == torch.int64), nf, _ptr(uv), _ptr(chart),
-                                           _ptr(vt), _ptr(sums), _stream()))
+                                           _ptr(vt), _ptr(sums), _ptr(ws), _stream()))
         s = sums.cpu().numpy()
         angles = np.zeros(6, np.float32)
         for c in range(6):
