@@ -60,6 +60,13 @@ def test_conv_blocks_vs_torch(cuda):
     ops.upsample_bilinear(xin, ops.Act(ub, 0, ci, 31, 20))
     ru = F.interpolate(x, size=(31, 20), mode="bilinear", align_corners=False)[0]
     assert _rel(ub[:, :ci].float().cpu().reshape(31, 20, ci).permute(2, 0, 1), ru)[1] < 3e-2  # bf16 output rounding
+    # ... and per element the bound derived from the kernel's expression (_cnnref.upsample_coef): one rounding to bf16 of an
+    # fp32 value within c u max|source| of the fp64 interpolation -- a few hundred times tighter wherever |ref| is small
+    import _cnnref
+
+    xa = x[0].permute(1, 2, 0).reshape(H * W, ci).to(torch.bfloat16)
+    ref64, amax = _cnnref.upsample_ref(xa, H, W, 31, 20)
+    assert ((ub[:, :ci].cpu().double() - ref64).abs() <= _cnnref.upsample_bound(ref64, amax, H, W, 31, 20)).all()
     ab = torch.zeros(H * W, 64, dtype=torch.bfloat16, device=cuda)
     ops.add_bf16(xin, xin, ops.Act(ab, 0, ci, H, W))
     assert torch.equal(ab[:, :ci].float().cpu(), (2 * x[0]).permute(1, 2, 0).reshape(H * W, ci).to(torch.bfloat16).float())
