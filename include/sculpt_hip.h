@@ -194,7 +194,7 @@ int sculpt_grid_decode(const void *mlp_packed, int n_hidden_64, int R, int x_beg
 /* ------------------------------------------------------------------------------------------
  * Marching cubes (Lewiner), output identical to skimage.measure.marching_cubes(vol, level)
  * with default arguments, including vertex and face ORDER.
- *   vol f32 [n0][n1][n2] C order.  Two phases: count (synchronises the stream, returns sizes),
+ *   vol f32 [n0][n1][n2] C order.  Two phases: count (waits for the counts, returns sizes),
  *   then emit into caller-allocated buffers.
  *   flags: SCULPT_MC_REFERENCE_ORDER  faces columns reordered [1,0,2] and stored as int64,
  *          verts multiplied by vert_scale (isosurface.py:52-53) then mapped v*a + b
@@ -219,6 +219,7 @@ int sculpt_grid_decode(const void *mlp_packed, int n_hidden_64, int R, int x_beg
 #define SCULPT_ERR_MC_EMPTY 12
 #define SCULPT_ERR_MC_NAN 13 /* the volume contains NaN (e.g. a 16-bit split density mode left its range) */
 #define SCULPT_ERR_MC_WORKSPACE 14 /* more active cells than the workspace's pool is named for: repeat once with that many (below) */
+#define SCULPT_ERR_MC_NO_COUNT 15 /* sculpt_mc_count_read: no count launch is pending for this workspace (see there) */
 
 /* Workspace: per-row arrays + a record pool of 8 bytes per ACTIVE cell (a cell whose corner signs differ).
  * A pool is NAMED for a capacity of c records: max_active_cells of sculpt_mc_workspace_bytes_for / sculpt_mc_count_launch_for
@@ -246,9 +247,25 @@ int sculpt_mc_emit(const float *vol, int n0, int n1, int n2, double level, unsig
  *   sculpt_mc_emit_capped   the emit phase into buffers of cap_verts vertices / cap_faces faces sized by the CALLER'S ESTIMATE
  *                           (e.g. the previous mesh + 25 %); the kernels read the totals on the device and write NOTHING when the
  *                           mesh does not fit either buffer;
- *   sculpt_mc_count_read    synchronises the stream and returns the totals with sculpt_mc_count's error semantics: when they exceed
+ *   sculpt_mc_count_read    waits for the COUNTS and returns the totals with sculpt_mc_count's error semantics: when they exceed
  *                           the capacities the caller allocates exactly and calls sculpt_mc_emit.
- * sculpt_mc_count == launch + read; sculpt_mc_emit == emit_capped with unbounded capacities. */
+ * sculpt_mc_count == launch + read + a stream synchronise; sculpt_mc_emit == emit_capped with unbounded capacities.
+ * How the counts reach the host.  Every count launch (all sculpt_mc_count_launch* forms) queues, behind its last kernel, a copy of
+ * the 64-byte header into a pinned host slot of the library and records an event; sculpt_mc_count_read / _read_ex wait for that
+ * event (not for the stream) and read the slot.  The contract:
+ *   - after sculpt_mc_count_read returns, the counts are final, and so is everything queued on the stream BEFORE the count launch
+ *     (e.g. an asynchronous copy of sculpt_density_grid_filtered's statistics);
+ *   - work queued on the stream AFTER the count launch -- sculpt_mc_emit_capped included -- may still be running: the caller's
+ *     vertex and face buffers are ordered by the stream, as after any asynchronous launch;
+ *   - a slot belongs to the (device, workspace pointer) of its launch until it is read: one read per launch.  A read without a
+ *     pending launch for that workspace (never launched, read already) fails at once with SCULPT_ERR_MC_NO_COUNT; it never blocks;
+ *   - a second count launch on the same workspace before the read REPLACES the pending one (the read returns the second's counts);
+ *   - at most 8 count launches may be pending per device; a ninth takes the slot of the oldest, whose read then fails as above;
+ *   - launch and read are made with the same current device; the `stream` argument of the read functions is unused (kept for
+ *     the ABI);
+ *   - the count launches are not graph-capturable (they record an event for the host).
+ * The slots and events are created on first use and reused (no allocation on the warm path); calls may come from several host
+ * threads (one mutex, never held across the wait). */
 int sculpt_mc_count_launch(const float *vol, int n0, int n1, int n2, double level, unsigned flags, void *workspace,
                            sculpt_stream_t stream);
 /* The count phase when the caller already holds the planes "vol > level" of the whole lattice -- sign_planes[(i0 * n1 + i1) *

@@ -225,6 +225,7 @@ ERR_MC_LEVEL = 11
 ERR_MC_EMPTY = 12
 ERR_MC_NAN = 13
 ERR_MC_WORKSPACE = 14
+ERR_MC_NO_COUNT = 15
 EPI_NONE, EPI_GELU, EPI_GEGLU, EPI_RELU = 0, 1, 2, 3
 QUERY_ALIGN_CORNERS = 1
 QUERY_CHANNEL_LAST = 2

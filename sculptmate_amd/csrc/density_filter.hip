@@ -42,6 +42,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 
 #include "common.h"
 #include "triplane_mlp.h"
@@ -105,6 +106,26 @@ static size_t filter_layout(int R, int nx, void *base, FilterView *v) {
         v->list = reinterpret_cast<uint32_t *>(list);
     }
     return o;
+}
+
+// The header of a call, cleared by a one-wave launch in front of pass A (whose workgroups add to it): sculpt_plane_features
+// comes through another entry and is skipped by callers that keep their tables, so no earlier kernel of this call can do it.
+__global__ __launch_bounds__(64) void filter_header_clear_kernel(FilterHeader *__restrict__ hdr) {
+    static_assert(sizeof(FilterHeader) == 16 * sizeof(int32_t), "one word per lane");
+    if (threadIdx.x < 16) reinterpret_cast<int32_t *>(hdr)[threadIdx.x] = 0;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize once per kernel (slot), device and size instead of on every call: the attribute
+// stays with the loaded kernel.  (Two threads racing through the first call both set it: harmless.)
+static int ensure_dynamic_lds(const void *kern, int slot, size_t bytes) {
+    static std::atomic<int> have[3][64];   // bytes the attribute was last raised to
+    int dev = 0;
+    SC_HIP(hipGetDevice(&dev));
+    const bool tracked = dev >= 0 && dev < 64;
+    if (tracked && have[slot][dev].load(std::memory_order_acquire) >= (int)bytes) return 0;
+    SC_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (tracked) have[slot][dev].store((int)bytes, std::memory_order_release);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -614,9 +635,10 @@ int sculpt_density_grid_filtered(const void *mlp_packed, int n_hidden_64, int R,
     const float *blob = reinterpret_cast<const float *>(mlp_packed);
     const long ntiles = (long)nx * ((R + 31) / 32) * R;
     if (passes & SCULPT_FILTER_PASS_A) {
-        SC_HIP(hipMemsetAsync(v.hd, 0, sizeof(FilterHeader), st));
+        hipLaunchKernelGGL(filter_header_clear_kernel, dim3(1), dim3(64), 0, st, v.hd);
+        SC_LAUNCH_CHECK();
         auto kern = (flags & SCULPT_FILTER_COARSE_FP16) ? density_coarse_kernel<tf16x8> : density_coarse_kernel<tbf16x8>;
-        SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c));
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), (flags & SCULPT_FILTER_COARSE_FP16) ? 0 : 1, lds_c)) return rc;
         int threads = 1024;
         size_t lds_launch = lds_c;
 #ifdef SCULPT_EXPERIMENTS
@@ -639,7 +661,7 @@ int sculpt_density_grid_filtered(const void *mlp_packed, int n_hidden_64, int R,
     }
     auto list_pass = [&](int stage) -> int {
         auto kern = density_list_l3k_kernel<1024>;
-        SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x));
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 2, lds_x)) return rc;
         const int grid = (int)std::min<long>((ntiles + 15) / 16, num_cus());
         hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds_x, st, blob, FA, FB, FC, R, density_bias, out_add,
                            v.list, v.hd, out, stage, v.sign, v.audit, (long)nx * R * R);
@@ -653,6 +675,9 @@ int sculpt_density_grid_filtered(const void *mlp_packed, int n_hidden_64, int R,
         if (int rc = list_pass(0)) return rc;
     }
     if (passes & SCULPT_FILTER_PASS_C) {   // the values marching cubes reads
+        // Two launches: a point's word needs the cell words of its own and three neighbouring rows (x - 1, y - 1), which other
+        // workgroups write; one launch would need a grid-wide barrier between the two halves, or every thread classifying the
+        // cells of all four rows itself (4 x the bit arithmetic of filter_cells_kernel for one launch boundary of 2-3 us).
         hipLaunchKernelGGL(filter_cells_kernel, dim3(cdiv(words, 1024)), dim3(1024), 0, st, v.sign, R, nx, v.cell, v.hd);
         hipLaunchKernelGGL(filter_points_kernel<1>, dim3(cdiv(words, 1024)), dim3(1024), 0, st, v.cell, v.sign, v.mark, R, nx, v.list, v.hd);
         SC_LAUNCH_CHECK();

@@ -31,6 +31,8 @@
 
 #include <stdlib.h>
 
+#include <mutex>
+
 #include "common.h"
 #include "mc_luts.h"
 
@@ -827,6 +829,13 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_classify_brick_kernel(const float
     }
 }
 
+// Header and pool counters of a count phase, from the host's values passed BY VALUE (no upload from host memory, no fill): a
+// launch of its own in front of the classify pass, whose workgroups add to the counters and store into the header.
+__global__ __launch_bounds__(256) void mc_init_kernel(McHeader *__restrict__ hdr, McHeader init, unsigned *__restrict__ pool_ctr) {
+    if (threadIdx.x == 0) *hdr = init;
+    for (int i = threadIdx.x; i < MC_NCTR; i += blockDim.x) pool_ctr[i] = 0u;
+}
+
 // two-level exclusive scan of the packed per-workgroup counts (tri low 16 | vert high 16 of an int):
 // level 1: every workgroup scans 1024 entries and publishes its 64-bit total (tri | vert << 32)
 __global__ __launch_bounds__(1024) void mc_scan1_kernel(const int *__restrict__ block_counts,
@@ -1306,6 +1315,101 @@ static WsLayout ws_layout(const Grid &g, long rec_capacity) {
     return w;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The counts' way to the host.  mc_count_launch queues, right behind mc_scan2_kernel, a copy of the header into a pinned host
+// slot and records an event; sculpt_mc_count_read waits for THAT EVENT, not for the stream: work queued behind the count phase
+// (the speculative emit) goes on while the host reads the counts, allocates and queues what comes next.
+// A small ring of slots per device, created on first use and reused; a slot belongs to the workspace pointer it was launched
+// with until its read; the library has no teardown, so the slots (64 pinned bytes and an event each) live as long as the
+// process.  One mutex guards every ring: it is held while a slot is chosen and its copy + event are queued, and
+// while a read looks its slot up and copies the 64 bytes out -- never across the wait for the event.
+// ---------------------------------------------------------------------------------------------
+static constexpr int MC_RING = 8, MC_RING_DEVICES = 64;
+struct CountSlot {
+    const void *ws;              // the workspace of the pending count (key; meaningful while `pending`)
+    McHeader *host;              // pinned, 64 bytes; null: the slot has not been created yet
+    hipEvent_t ev;               // recorded behind the copy into `host`
+    bool pending;                // launched and not read yet
+    unsigned long long seq;      // launch number: the oldest pending slot gives way when the ring is full
+};
+static std::mutex g_ring_mu;
+static CountSlot g_ring[MC_RING_DEVICES][MC_RING];
+static unsigned long long g_ring_seq = 0;
+
+static int ring_device(int *dev) {
+    SC_HIP(hipGetDevice(dev));
+    SC_REQUIRE(*dev >= 0 && *dev < MC_RING_DEVICES, "mc_count: device %d is beyond the %d the count slots cover", *dev, MC_RING_DEVICES);
+    return 0;
+}
+
+// queue the header's copy and the event for the count phase just launched on `st` into `workspace`
+static int ring_launch(const void *workspace, const McHeader *hdr_dev, hipStream_t st) {
+    int dev = 0;
+    if (int rc = ring_device(&dev)) return rc;
+    std::lock_guard<std::mutex> lock(g_ring_mu);
+    CountSlot *ring = g_ring[dev], *slot = nullptr;
+    for (int i = 0; i < MC_RING && !slot; ++i)   // a second launch on the same workspace replaces the pending one
+        if (ring[i].host && ring[i].pending && ring[i].ws == workspace) slot = &ring[i];
+    for (int i = 0; i < MC_RING && !slot; ++i)
+        if (ring[i].host && !ring[i].pending) slot = &ring[i];
+    for (int i = 0; i < MC_RING && !slot; ++i)
+        if (!ring[i].host) slot = &ring[i];
+    if (!slot) {   // every slot pending: the oldest launch loses its slot (its read reports that no count is pending)
+        slot = &ring[0];
+        for (int i = 1; i < MC_RING; ++i)
+            if (ring[i].seq < slot->seq) slot = &ring[i];
+    }
+    if (!slot->host) {   // first use of this slot (the current device is `dev`: the event belongs to it)
+        void *p = nullptr;
+        SC_HIP(hipHostMalloc(&p, sizeof(McHeader), hipHostMallocDefault));
+        hipEvent_t ev;
+        if (hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) {
+            (void)hipHostFree(p);
+            set_error("hipEventCreateWithFlags failed: %s", hipGetErrorString(e));
+            return 1;
+        }
+        slot->host = reinterpret_cast<McHeader *>(p);
+        slot->ev = ev;
+    }
+    slot->pending = false;   // (stays so when one of the two calls below fails)
+    SC_HIP(hipMemcpyAsync(slot->host, hdr_dev, sizeof(McHeader), hipMemcpyDeviceToHost, st));
+    SC_HIP(hipEventRecord(slot->ev, st));
+    slot->ws = workspace;
+    slot->seq = ++g_ring_seq;
+    slot->pending = true;
+    return 0;
+}
+
+// wait for the pending count of `workspace` and take its header; the slot is free afterwards
+static int ring_read(const void *workspace, McHeader *out) {
+    int dev = 0;
+    if (int rc = ring_device(&dev)) return rc;
+    CountSlot *ring = g_ring[dev], *slot = nullptr;
+    hipEvent_t ev;
+    unsigned long long seq;
+    {
+        std::lock_guard<std::mutex> lock(g_ring_mu);
+        for (int i = 0; i < MC_RING && !slot; ++i)
+            if (ring[i].host && ring[i].pending && ring[i].ws == workspace) slot = &ring[i];
+        if (!slot) {
+            set_error("mc_count_read: no count launch is pending for workspace %p on device %d (read already, never launched, or "
+                      "more than %d counts pending)", workspace, dev, MC_RING);
+            return SCULPT_ERR_MC_NO_COUNT;
+        }
+        ev = slot->ev;
+        seq = slot->seq;
+    }
+    SC_HIP(hipEventSynchronize(ev));
+    std::lock_guard<std::mutex> lock(g_ring_mu);
+    if (!slot->pending || slot->seq != seq) {   // another thread launched or read on this workspace meanwhile
+        set_error("mc_count_read: the pending count of workspace %p was replaced while it was being read", workspace);
+        return SCULPT_ERR_MC_NO_COUNT;
+    }
+    *out = *slot->host;
+    slot->pending = false;
+    return 0;
+}
+
 }  // namespace sculpt
 
 using namespace sculpt;
@@ -1340,8 +1444,8 @@ static int mc_count_launch(const float *vol, const unsigned *signbits, int sign_
     init.min_ord = 0xffffffffu;
     init.max_ord = 0u;
     init.rec_capacity = (unsigned)std::min<long>(w.rec_capacity, 0xffffffffL);
-    SC_HIP(hipMemsetAsync(ws + w.off_ctr, 0, sizeof(unsigned) * MC_NCTR, st));
-    SC_HIP(hipMemcpyAsync(hdr, &init, sizeof(init), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(mc_init_kernel, dim3(1), dim3(256), 0, st, hdr, init, reinterpret_cast<unsigned *>(ws + w.off_ctr));
+    SC_LAUNCH_CHECK();
     const int classic = (flags & SCULPT_MC_USE_CLASSIC) ? 1 : 0;
     // float f > double level  <=>  f > (largest float <= level): the sign pass needs no fp64
     float levelf = (float)level;
@@ -1366,7 +1470,8 @@ static int mc_count_launch(const float *vol, const unsigned *signbits, int sign_
                        reinterpret_cast<const float2 *>(ws + w.off_gmm), w.ngroups, hdr,
                        reinterpret_cast<unsigned *>(ws + w.off_gact));
     SC_LAUNCH_CHECK();
-    return 0;
+    // the counts are final here: their copy to the host and the event sculpt_mc_count_read waits for
+    return ring_launch(workspace, hdr, st);
 }
 
 int sculpt_mc_count_launch(const float *vol, int n0, int n1, int n2, double level, unsigned flags, void *workspace,
@@ -1403,13 +1508,10 @@ int sculpt_mc_count_read(int n0, int n1, int n2, double level, unsigned flags, c
 
 int sculpt_mc_count_read_ex(int n0, int n1, int n2, double level, unsigned flags, const void *workspace, int64_t *n_verts_host,
                             int64_t *n_faces_host, float *minmax_host, int64_t *n_active_host, sculpt_stream_t stream) {
-    hipStream_t st = as_stream(stream);
-    (void)n0; (void)n1; (void)n2;
+    (void)n0; (void)n1; (void)n2; (void)stream;
     SC_REQUIRE(workspace && n_verts_host && n_faces_host, "mc_count: null argument");
-    const McHeader *hdr = reinterpret_cast<const McHeader *>(workspace);
     McHeader res;
-    SC_HIP(hipMemcpyAsync(&res, hdr, sizeof(res), hipMemcpyDeviceToHost, st));
-    SC_HIP(hipStreamSynchronize(st));
+    if (int rc = ring_read(workspace, &res)) return rc;
     *n_verts_host = (int64_t)res.total_vert;
     *n_faces_host = (int64_t)res.total_tri;
     if (n_active_host) *n_active_host = (int64_t)res.total_active;
@@ -1446,7 +1548,9 @@ int sculpt_mc_count(const float *vol, int n0, int n1, int n2, double level, unsi
                     int64_t *n_verts_host, int64_t *n_faces_host, float *minmax_host, sculpt_stream_t stream) {
     SC_REQUIRE(n_verts_host && n_faces_host, "mc_count: null argument");
     if (int rc = sculpt_mc_count_launch(vol, n0, n1, n2, level, flags, workspace, stream)) return rc;
-    return sculpt_mc_count_read(n0, n1, n2, level, flags, workspace, n_verts_host, n_faces_host, minmax_host, stream);
+    const int rc = sculpt_mc_count_read(n0, n1, n2, level, flags, workspace, n_verts_host, n_faces_host, minmax_host, stream);
+    SC_HIP(hipStreamSynchronize(as_stream(stream)));   // the synchronous form: nothing of the call is left running
+    return rc;
 }
 
 int sculpt_mc_emit_capped(const float *vol, int n0, int n1, int n2, double level, unsigned flags, void *workspace,

@@ -854,8 +854,9 @@ class TSR(KernelEngine):
         return info
 
     def _extract_filtered(self, planes, R, mc, dkw, density_events=None, x_begin=0, x_end=None):
-        """The two-pass grid of lattice planes [x_begin, x_end) + mc(volume) (marching cubes: its count read-back waits for the
-        stream, so the statistics of the grid call have landed when it returns), under the run-time guard."""
+        """The two-pass grid of lattice planes [x_begin, x_end) + mc(volume) (marching cubes: its count read-back waits for an
+        event recorded behind the count phase, and the grid call's statistics copy is queued BEFORE that phase on the same stream,
+        so the statistics have landed when it returns), under the run-time guard."""
         info = self.filter_info
         dkw = dict(dkw, x_begin=x_begin, x_end=x_end)
         if info["margin"] is None:
@@ -874,7 +875,9 @@ class TSR(KernelEngine):
         if x_begin == 0 and (x_end is None or x_end == R) and getattr(mc, "takes_sign_planes", False) and _MC_SIGN_PLANES:
             signs = ops.filter_sign_planes(R, planes.device)
         try:
-            # waits for the stream (sculpt_mc_count reads its counts back): the statistics have landed with it
+            # waits for the counts (sculpt_mc_count_read: an event behind the count phase, not the whole stream -- the emit may still
+            # be running).  density_grid_filtered queued the copy into `host` before the count launch, on the same stream, so the
+            # event covers it: the statistics have landed with the counts.  Keep that order.
             mesh = mc(vol) if signs is None else mc(vol, signs)
         except Exception as e:  # an empty / out-of-range surface raises in both evaluations; checked below before it is believed
             mesh, err = None, e
