@@ -21,36 +21,17 @@
 #include <stdlib.h>
 
 #include "gemm_f32.h"
+#include "limbs.h"
 
 namespace sculpt {
 
 typedef __bf16 lbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 lbf16x2 __attribute__((ext_vector_type(2)));
-typedef float lf32x2 __attribute__((ext_vector_type(2)));
+typedef Limb<LT_BF16X3> L3;   // limbs.h: the split (x = x1 + x2 + x3 exactly) and its packed pairs
 
 static constexpr int L3_BK = 32;
 static constexpr int L3_CS = 128 * 16 + 32;   // bytes from one k-chunk plane (128 rows x 16 B) to the next
 static constexpr int L3_LT = 4 * L3_CS;       // one limb of one operand tile
 static constexpr int L3_OP = 3 * L3_LT;       // one operand tile, three limbs
-
-__device__ __forceinline__ unsigned l3_cvt_pk(float lo, float hi) {
-    const lf32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, lbf16x2));
-}
-
-// four consecutive-k fp32 values -> the 8-byte piece of each limb plane
-__device__ __forceinline__ void l3_split4(const float4 &x, uint2 &p1, uint2 &p2, uint2 &p3) {
-#pragma clang fp contract(off)
-    const unsigned a1 = l3_cvt_pk(x.x, x.y), b1 = l3_cvt_pk(x.z, x.w);
-    const float r0 = x.x - __uint_as_float(a1 << 16), r1 = x.y - __uint_as_float(a1 & 0xffff0000u);   // exact
-    const float r2 = x.z - __uint_as_float(b1 << 16), r3 = x.w - __uint_as_float(b1 & 0xffff0000u);
-    const unsigned a2 = l3_cvt_pk(r0, r1), b2 = l3_cvt_pk(r2, r3);
-    const float s0 = r0 - __uint_as_float(a2 << 16), s1 = r1 - __uint_as_float(a2 & 0xffff0000u);     // exact, <= 8 bits
-    const float s2 = r2 - __uint_as_float(b2 << 16), s3 = r3 - __uint_as_float(b2 & 0xffff0000u);
-    p1 = make_uint2(a1, b1);
-    p2 = make_uint2(a2, b2);
-    p3 = make_uint2(l3_cvt_pk(s0, s1), l3_cvt_pk(s2, s3));
-}
 
 // PIPE = false: the plain form -- per K-step {barrier; split + write; barrier; load next; 48 MFMAs}.  The split is ~180 vector
 // instructions per wave and K-step, and on a SIMD the vector phase of one wave does not slide under the matrix phase of
@@ -111,8 +92,8 @@ __global__ __launch_bounds__(256, 2) void gemm_l3_kernel(GemmF32Args g_in) {
     auto split_all = [&]() {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            l3_split4(rw[i], pw[i][0], pw[i][1], pw[i][2]);
-            if (i < AI) l3_split4(ra[i], pa[i][0], pa[i][1], pa[i][2]);
+            L3::split4(rw[i].x, rw[i].y, rw[i].z, rw[i].w, pw[i]);
+            if (i < AI) L3::split4(ra[i].x, ra[i].y, ra[i].z, ra[i].w, pa[i]);
         }
     };
     auto write_all = [&]() {
@@ -186,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void gemm_l3_kernel(GemmF32Args g_in) {
                     // the first fence or sunk to its only use behind the last one -- IR-level motion the fences do not see)
                     asm volatile("" : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));
                     L3_MF(wf[0], af[2]);   // smallest terms first
-                    a1 = l3_cvt_pk(x0, x1); b1 = l3_cvt_pk(x2, x3);
+                    a1 = L3::cvt_pk(x0, x1); b1 = L3::cvt_pk(x2, x3);
                     t0 = __uint_as_float(a1 << 16); t1 = __uint_as_float(a1 & 0xffff0000u);
                     t2 = __uint_as_float(b1 << 16); t3 = __uint_as_float(b1 & 0xffff0000u);
                     asm volatile("" : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3));
@@ -198,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void gemm_l3_kernel(GemmF32Args g_in) {
                     if (gi < 4) { L3_RD(af1[gi >> 1][(gi & 1) * 2], afo, (gi & 1) * 2, 1, gi >> 1); }
                     L3_FENCE;
                     L3_MF(wf[1], af[1]);
-                    a2 = l3_cvt_pk(r0, r1); b2 = l3_cvt_pk(r2, r3);
+                    a2 = L3::cvt_pk(r0, r1); b2 = L3::cvt_pk(r2, r3);
                     t0 = __uint_as_float(a2 << 16); t1 = __uint_as_float(a2 & 0xffff0000u);
                     t2 = __uint_as_float(b2 << 16); t3 = __uint_as_float(b2 & 0xffff0000u);
                     asm volatile("" : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3));
@@ -210,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void gemm_l3_kernel(GemmF32Args g_in) {
                     asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));
                     L3_FENCE;
                     L3_MF(wf[1], af[0]);
-                    a3 = l3_cvt_pk(r0, r1); b3 = l3_cvt_pk(r2, r3);
+                    a3 = L3::cvt_pk(r0, r1); b3 = L3::cvt_pk(r2, r3);
                     asm volatile("" : "+v"(a3), "+v"(b3));
                     L3_FENCE;
                     L3_MF(wf[0], af[0]);

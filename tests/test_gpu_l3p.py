@@ -352,6 +352,62 @@ def test_two_fp16_limb_attention_vs_fp64(Tq, Tk, heads, gain, monkeypatch):
         assert float((got[Tq:].flip(0).double() - ref).norm() / ref.norm()) < 2e-6
 
 
+@pytest.mark.parametrize("Tq,Tk", [(1, 1), (33, 63), (128, 64), (129, 65), (256, 128), (257, 129), (31, 193)])
+def test_limb_attention_shared_parts_at_tile_edges(Tq, Tk, monkeypatch):
+    """What the kernels of csrc/attention_l3.hip share -- the batch / lane prologue, the ragged-tile mask with the row maximum, the
+    output epilogue --, and attention_l2.hip's copy of them, in every form (4 waves x three limbs, 8 waves x three limbs, 8 waves x two fp16 limbs) at the smallest
+    shapes where they can go wrong: one to four key tiles (the loads of tile 1 and of tile t + 2 taken and not taken), a last key
+    tile of 1 and of 63 keys, a query block edge at 128 and at 256 with a last block of one row; Q and K are column slices of wider
+    tensors.  Against an fp64 softmax of the same fp32 operands with the bounds of test_fused_three_limb_attention_vs_fp64 /
+    test_two_fp16_limb_attention_vs_fp64; no write outside the Tq rows; the limb output is the split of the fp32 output bit for
+    bit; a batch of two in one launch equals the two launches bit for bit."""
+    from sculptmate_amd import ops
+
+    heads, D, scale = 2, 128, 0.125
+    g = torch.Generator().manual_seed(1000 * Tq + Tk)
+    Ts, ldv = ((Tk + 7) // 8) * 8, ((Tk + 63) // 64) * 64
+    Q2 = _rand((2 * Tq, D + 64), g)[:, 32:32 + D]            # two batch entries: rows stacked; row stride D + 64
+    K2 = _rand((2 * Ts, D + 32), g)[:, 32:32 + D]
+    V = _rand((2, D, Tk), g)
+    Vt2 = torch.full((D, Ts + ldv), 7.0, device=_dev())      # V^T side by side; padding columns finite, multiplied by exact zeros
+    Vt2[:, :Tk], Vt2[:, Ts:Ts + Tk] = V[0], V[1]
+    ent = [(Q2[b * Tq:], K2[b * Ts:], Vt2[:, b * Ts:]) for b in range(2)]
+    qh = Q2[:Tq].double().view(Tq, heads, 64).transpose(0, 1); kh = K2[:Tk].double().view(Tk, heads, 64).transpose(0, 1)
+    vh = V[0].t().double().view(Tk, heads, 64).transpose(0, 1)
+    ref = (torch.softmax(qh @ kh.transpose(1, 2) * scale, -1) @ vh).transpose(0, 1).reshape(Tq, D)
+    R = Tq + 5                                               # limb rows from one batch entry to the next
+    e3 = None
+    for form, two in (("nol3pipe", False), ("l3pipe", False), ("l3pipe", True)):
+        monkeypatch.setenv("SCULPT_ATTN_FORM", form)
+        fmt = "f16x2" if two else "bf16x3"
+        outs = []
+        for Q, K, Vt in ent:
+            o = torch.full((Tq + 40, D), float("nan"), device=_dev())
+            ops.attention_f32(Q, K, Vt, o, Tq, Tk, heads, scale, None, l3=True, two_fp16_limbs=two)
+            assert torch.isfinite(o[:Tq]).all() and torch.isnan(o[Tq:]).all(), form
+            outs.append(o[:Tq])
+        rel, mx = float((outs[0].double() - ref).norm() / ref.norm()), float((outs[0].double() - ref).abs().max())
+        print("Tq %d Tk %d %s%s: rel err vs fp64 %.2e, max abs %.2e" % (Tq, Tk, form, " two fp16 limbs" if two else "", rel, mx))
+        if two:
+            assert rel < 2e-6 and rel < 4.0 * e3 + 2e-7, (form, rel, e3)
+        else:
+            assert rel < 1e-6 and mx < 2e-5, (form, rel, mx)
+            e3 = rel
+        # the limb output at a row offset: the split of the fp32 output in the kernel's own format, zero rows before and after
+        O = ops.Limbs(32 + Tq + 8, D, _dev(), zero=True, fmt=fmt)
+        ops.attention_f32(*ent[0], O, Tq, Tk, heads, scale, None, l3=True, o_row0=32, two_fp16_limbs=two)
+        want = torch.zeros(32 + Tq + 8, D, device=_dev()); want[32:32 + Tq] = outs[0]
+        assert torch.equal(O.data, ops.Limbs.of(want, fmt=fmt).data), form
+        # both entries in one launch
+        got = torch.full((2 * Tq + 40, D), float("nan"), device=_dev())
+        ops.attention_f32_l3_batched(Q2, K2, Vt2, got, Tq, Tk, heads, scale, 2, Tq * Q2.stride(0), Ts * K2.stride(0), Ts, Tq * D, two_fp16_limbs=two)
+        assert torch.equal(got[:2 * Tq], torch.cat(outs)) and torch.isnan(got[2 * Tq:]).all(), form
+        O = ops.Limbs(2 * R, D, _dev(), zero=True, fmt=fmt)
+        ops.attention_f32_l3_batched(Q2, K2, Vt2, O, Tq, Tk, heads, scale, 2, Tq * Q2.stride(0), Ts * K2.stride(0), Ts, R * D, two_fp16_limbs=two)
+        want = torch.zeros(2 * R, D, device=_dev()); want[:Tq], want[R:R + Tq] = outs[0], outs[1]
+        assert torch.equal(O.data, ops.Limbs.of(want, fmt=fmt).data), form
+
+
 def test_fp16l2_range_fallback():
     """An activation beyond the fp16 range (here: a LayerNorm gain of 3e5 in one block) makes the two-limb result non-finite;
     forward() answers with the three-limb twin's scene code -- bit for bit what TSR(precision="bf16l3") gives -- and counts it."""
