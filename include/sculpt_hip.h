@@ -472,6 +472,54 @@ int sculpt_transpose_add(const float *x_tc, const float *residual_ct, float *out
 int sculpt_resize_aa_bilinear(const float *in_hwc, int Hin, int Win, int C, float *tmp, float *out_hwc, int Hout,
                               int Wout, sculpt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The image front end on the device (preprocessing.preprocess_image_device; the host path it restates: preprocessing.py:73-127,
+ * rembg/bg.py:149-238, rembg/sessions/base.py:44-69, rembg/sessions/u2net.py:34-44).  Images are tightly packed uint8 [H][W][C]
+ * with sides in [1, 32768].  EXACTNESS: every entry point below is integer arithmetic or IEEE operations rounded one by one (the
+ * file is compiled without floating-point contraction), and gives the bytes / floats the host library gives -- Pillow's
+ * Image.resize(LANCZOS) and Image.composite, numpy's float64 / float32 expressions -- bit for bit.  Added without a version
+ * change (new symbols only).
+ *
+ * Pillow's 8-bit LANCZOS resample is separable.  The tables of one axis, inSize -> outSize, are computed on the HOST (double
+ * arithmetic and libm's sin, the very function the host library calls; no device memory is touched, no GPU is needed):
+ *   sculpt_resample_lanczos_ksize   taps per output index, (int)ceil(3 max(inSize / outSize, 1)) * 2 + 1; 0 for sizes out of range
+ *   sculpt_resample_lanczos_coeffs  bounds_host int32 [outSize][2] = (first input index, taps used), kk_host int32 [outSize][ksize]
+ *                                   = the weights in 2^-22 units, rounded half away from zero, zero past the taps used
+ * sculpt_resample_u8 takes them as DEVICE arrays: the horizontal pass first (into tmp, uint8 [Hin][Wout][C]), then the vertical
+ * one; each is acc = 2^21 + sum pixel * k in int32, out = clamp(acc >> 22, 0, 255).  A pass whose size does not change is skipped
+ * and its tables may be NULL (tmp is needed only when both run); C is 1, 3 or 4 and every channel is treated alike (no alpha
+ * premultiplication: what Pillow does for L and RGB, not for RGBA). */
+int sculpt_resample_lanczos_ksize(int in_size, int out_size);
+int sculpt_resample_lanczos_coeffs(int in_size, int out_size, int ksize, int32_t *bounds_host, int32_t *kk_host);
+int sculpt_resample_u8(const uint8_t *in_hwc, int Hin, int Win, int C, const int32_t *bounds_x, const int32_t *kk_x, int ksize_x,
+                       const int32_t *bounds_y, const int32_t *kk_y, int ksize_y, uint8_t *tmp, uint8_t *out_hwc, int Hout, int Wout,
+                       sculpt_stream_t stream);
+/* U^2-Net's input from the resized picture (C = 3 or 4; a fourth channel is ignored): out_chw fp32 [3][H][W] =
+ * (float)(((double)v / max - mean[c]) / std[c]) with max the maximum over the three channels of the whole image, taken on the device;
+ * three fp64 operations and one rounding to fp32, as numpy evaluates normalize().  ws: 4 int32 of device scratch. */
+int sculpt_u2net_input(const uint8_t *img_hwc, int H, int W, int C, const double *mean3_host, const double *std3_host, int32_t *ws,
+                       float *out_chw, sculpt_stream_t stream);
+/* The 8-bit mask of the network's output d0 (fp32, n elements): mask = (uint8)(((d - mi) / (ma - mi)) * 255) with mi, ma the
+ * minimum and maximum of d0 taken on the device, every fp32 operation rounded on its own, truncating conversion.  ma == mi (a
+ * constant d0) gives 0 everywhere -- the host's result there is numpy's undefined cast of NaN.  ws: 4 uint32 of device scratch. */
+int sculpt_u2net_mask(const float *d0, int64_t n, uint32_t *ws, uint8_t *mask, sculpt_stream_t stream);
+/* The cut-out Image.composite(img, transparent, mask) is, per byte, md255(v, M) = (t = v * M + 128, ((t >> 8) + t) >> 8), with
+ * alpha 255 for C = 3.  sculpt_cutout_bbox: bbox_host[4] = (ymin, ymax, xmin, xmax), both ends INCLUSIVE, of the pixels whose
+ * cut-out alpha md255(A, M) is non-zero; (H, -1, W, -1) when there is none.  img_hwc may be NULL for C = 3.  This is the front
+ * end's only readback: the four integers (ws: 4 int32 of device scratch) are copied into a pinned slot of the library behind the
+ * kernel, an event is recorded behind the copy, and the call waits for that event -- not for the stream -- as
+ * sculpt_mc_count_read does.  Not graph-capturable; calls may come from several host threads. */
+int sculpt_cutout_bbox(const uint8_t *img_hwc, const uint8_t *mask, int H, int W, int C, int32_t *ws, int32_t *bbox_host,
+                       sculpt_stream_t stream);
+/* Cut-out, frame and grey composite as one gather: out [S][S][grey ? 3 : 4]; pixel (oy, ox) is the cut-out's pixel
+ * (y0 + oy - top, x0 + ox - left) where that lies in the box [y0, y0 + h) x [x0, x0 + w), transparent black elsewhere.
+ * grey = 0: RGBA.  grey != 0: x = v / 255, a = alpha / 255, rgb = x * a + (1 - a) * 0.5, out = (uint8)(rgb * 255) in fp32, every
+ * operation rounded on its own and no fused multiply-add (preprocessing.py:112-116). */
+int sculpt_cutout_frame(const uint8_t *img_hwc, const uint8_t *mask, int H, int W, int C, int y0, int x0, int h, int w, int top,
+                        int left, int S, int grey, uint8_t *out, sculpt_stream_t stream);
+/* out = (float)v / 255, a rounded fp32 division: what ImagePreprocessor's conversion gives for a uint8 image */
+int sculpt_u8_to_unit_f32(const uint8_t *in, int64_t n, float *out, sculpt_stream_t stream);
+
 /* ViT front end (tokenizers/image.py:48 + HF ViTEmbeddings; DINOv2: sf3d/models/tokenizers/image.py:86 +
  * dinov2.py:176-210): normalise (x-mean)/std and cut the [S][S][3] fp32 image into patch rows
  * [floor(S/P)^2][ld] (the stride-P patch convolution as a GEMM; trailing S - floor(S/P)*P pixels ignored like the

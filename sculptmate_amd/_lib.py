@@ -132,6 +132,14 @@ SIGNATURES = {
     "sculpt_vertex_normals": (_i, [_vp, _sz, _vp, _i, _sz, _vp, _vp, _vp]),
     "sculpt_vertex_tangents": (_i, [_vp, _vp, _vp, _sz, _vp, _i, _sz, _vp, _vp, _vp]),
     "sculpt_resize_aa_bilinear": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "sculpt_resample_lanczos_ksize": (_i, [_i, _i]),
+    "sculpt_resample_lanczos_coeffs": (_i, [_i, _i, _i, _vp, _vp]),
+    "sculpt_resample_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
+    "sculpt_u2net_input": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_u2net_mask": (_i, [_vp, _i64, _vp, _vp, _vp]),
+    "sculpt_cutout_bbox": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sculpt_cutout_frame": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sculpt_u8_to_unit_f32": (_i, [_vp, _i64, _vp, _vp]),
     "sculpt_bake_workspace_bytes": (_sz, [_i]),
     "sculpt_bake_rasterize": (_i, [_vp, _sz, _vp, _sz, _i, _vp, _vp, _vp]),
     "sculpt_bake_interpolate": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _vp, _vp]),

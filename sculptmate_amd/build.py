@@ -53,6 +53,9 @@ def source_digest(flags_text=None):
 
 
 def _flags():
+    # No fast-math flag and nothing that relaxes the correctly rounded fp32 division (-fno-hip-fp32-correctly-rounded-divide-sqrt)
+    # may be added here: csrc/image_front.hip is held bit for bit to Pillow / numpy and relies on IEEE operations (it refuses
+    # __FAST_MATH__ at compile time; the division flag has no macro, tests/test_gpu_image_front.py is what would notice).
     extra = os.environ.get("SCULPT_EXTRA_HIPCC_FLAGS", "").split()
     return ["-O3", "--offload-arch=" + ARCH, "-std=c++17", "-fPIC", "-Wno-unused-result"] + extra
 

@@ -1003,3 +1003,107 @@ def add_bf16(a: Act, b: Act, out: Act):
 
 def fuse_sigmoid(maps, w, bias, out):
     check(lib.sculpt_fuse_sigmoid(_ptr(maps), maps.shape[0], maps.shape[1], _ptr(w), float(bias), _ptr(out), _stream()))
+
+
+# ----------------------------------------------------------------------------------------------
+# image front end: uint8 HWC images resident in HBM (csrc/image_front.hip; bit for bit the host library's results)
+# ----------------------------------------------------------------------------------------------
+def lanczos_tables_host(in_size, out_size):
+    """Pillow's 8-bit LANCZOS tables of one axis (sculpt_resample_lanczos_*; host only, no GPU) ->
+    (ksize, bounds int32 [out_size, 2] = (first input index, taps used), kk int32 [out_size, ksize])."""
+    ksize = lib.sculpt_resample_lanczos_ksize(int(in_size), int(out_size))
+    if ksize <= 0:
+        raise SculptError("lanczos tables: sizes %r -> %r are out of range" % (in_size, out_size))
+    bounds = np.empty((out_size, 2), np.int32)
+    kk = np.empty((out_size, ksize), np.int32)
+    check(lib.sculpt_resample_lanczos_coeffs(int(in_size), int(out_size), ksize, bounds.ctypes.data, kk.ctypes.data))
+    return ksize, bounds, kk
+
+
+_LANCZOS_TABLES = {}   # (device, in_size, out_size) -> (ksize, bounds, kk) on the device; the oldest entry leaves past 64
+
+
+def _lanczos_tables(in_size, out_size, device):
+    key = (str(device), int(in_size), int(out_size))
+    hit = _LANCZOS_TABLES.get(key)
+    if hit is None:
+        ksize, bounds, kk = lanczos_tables_host(in_size, out_size)
+        hit = (ksize, torch.from_numpy(bounds).to(device), torch.from_numpy(kk).to(device))
+        if len(_LANCZOS_TABLES) >= 64:
+            _LANCZOS_TABLES.pop(next(iter(_LANCZOS_TABLES)))
+        _LANCZOS_TABLES[key] = hit
+    return hit
+
+
+def resample_lanczos_u8(img, out_h, out_w):
+    """Image.resize((out_w, out_h), LANCZOS) of an 8-bit image: uint8 [H, W, C] (C in 1, 3, 4; every channel alike) or [H, W]."""
+    img = _req(img, torch.uint8, "image")
+    flat = img.dim() == 2
+    H, W = img.shape[:2]
+    C = 1 if flat else img.shape[2]
+    out_h, out_w = int(out_h), int(out_w)
+    kx, bx, cx = _lanczos_tables(W, out_w, img.device) if W != out_w else (0, None, None)
+    ky, by, cy = _lanczos_tables(H, out_h, img.device) if H != out_h else (0, None, None)
+    tmp = torch.empty((H, out_w, C), dtype=torch.uint8, device=img.device) if (kx and ky) else None
+    out = torch.empty((out_h, out_w) if flat else (out_h, out_w, C), dtype=torch.uint8, device=img.device)
+    check(lib.sculpt_resample_u8(_ptr(img), H, W, C, _ptr(bx), _ptr(cx), kx, _ptr(by), _ptr(cy), ky, _ptr(tmp), _ptr(out), out_h, out_w,
+                                 _stream()))
+    return out
+
+
+def u2net_input(img, mean, std):
+    """rembg's normalize() after its resize: uint8 [H, W, 3 or 4] -> fp32 [3, H, W] = ((v / max - mean) / std in float64).astype(float32)."""
+    img = _req(img, torch.uint8, "image")
+    H, W, C = img.shape
+    ws = torch.empty(4, dtype=torch.int32, device=img.device)
+    out = torch.empty((3, H, W), dtype=torch.float32, device=img.device)
+    m, s = (ctypes.c_double * 3)(*mean), (ctypes.c_double * 3)(*std)
+    check(lib.sculpt_u2net_input(_ptr(img), H, W, C, ctypes.cast(m, ctypes.c_void_p), ctypes.cast(s, ctypes.c_void_p), _ptr(ws), _ptr(out),
+                                 _stream()))
+    return out
+
+
+def u2net_mask(d0):
+    """rembg's min-max stretch of the network output to 8 bits: fp32 [...] -> uint8 [...] (a constant d0 gives 0)."""
+    d0 = _req(d0, torch.float32, "d0")
+    ws = torch.empty(4, dtype=torch.int32, device=d0.device)
+    out = torch.empty(d0.shape, dtype=torch.uint8, device=d0.device)
+    check(lib.sculpt_u2net_mask(_ptr(d0), d0.numel(), _ptr(ws), _ptr(out), _stream()))
+    return out
+
+
+def cutout_bbox(img, mask):
+    """(ymin, ymax, xmin, xmax), both ends inclusive, of the non-zero alpha of Image.composite(img, transparent, mask); None when
+    the cut-out is empty.  img uint8 [H, W, 3 or 4], mask uint8 [H, W].  Four integers come back to the host: the call waits for
+    them (an event behind the copy), not for the stream."""
+    img, mask = _req(img, torch.uint8, "image"), _req(mask, torch.uint8, "mask")
+    H, W, C = img.shape
+    if tuple(mask.shape) != (H, W):
+        raise SculptError("cutout_bbox: mask %s for a %d x %d image" % (tuple(mask.shape), H, W))
+    ws = torch.empty(4, dtype=torch.int32, device=img.device)
+    box = (ctypes.c_int32 * 4)()
+    check(lib.sculpt_cutout_bbox(_ptr(img), _ptr(mask), H, W, C, _ptr(ws), ctypes.cast(box, ctypes.c_void_p), _stream()))
+    return None if box[1] < 0 else (box[0], box[1], box[2], box[3])
+
+
+def cutout_frame(img, mask, y0, x0, h, w, top, left, side, grey):
+    """The cut-out's box [y0, y0 + h) x [x0, x0 + w) placed at (top, left) of a transparent side x side frame: uint8 [side, side, 4],
+    or with grey=True composited on 0.5 grey as preprocess_image does: uint8 [side, side, 3]."""
+    img, mask = _req(img, torch.uint8, "image"), _req(mask, torch.uint8, "mask")
+    H, W, C = img.shape
+    if tuple(mask.shape) != (H, W):
+        raise SculptError("cutout_frame: mask %s for a %d x %d image" % (tuple(mask.shape), H, W))
+    out = torch.empty((side, side, 3 if grey else 4), dtype=torch.uint8, device=img.device)
+    if side > 0:
+        check(lib.sculpt_cutout_frame(_ptr(img), _ptr(mask), H, W, C, int(y0), int(x0), int(h), int(w), int(top), int(left), int(side),
+                                      1 if grey else 0, _ptr(out), _stream()))
+    return out
+
+
+def u8_to_unit_f32(x):
+    """uint8 -> fp32 v / 255 (ImagePreprocessor's conversion of an 8-bit image)."""
+    x = _req(x, torch.uint8, "image")
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if x.numel():
+        check(lib.sculpt_u8_to_unit_f32(_ptr(x), x.numel(), _ptr(out), _stream()))
+    return out

@@ -77,6 +77,19 @@ class U2netSession:
         d0 = self.net.forward(x).cpu().numpy()[None]
         return [prediction_to_mask(d0, img.size)]
 
+    def predict_device(self, img_u8: torch.Tensor) -> torch.Tensor:
+        """predict() for a picture that is already in HBM, with no host round trip: uint8 [H, W, 3 or 4] on this session's
+        device (a fourth channel is ignored, as convert("RGB") drops it) -> the uint8 [H, W] mask, bit for bit the one
+        predict() builds from the same network output.  LANCZOS to 320 x 320, normalize(), the network, the min-max stretch to
+        8 bits and LANCZOS back to the picture's size are all kernels of csrc/image_front.hip on the current stream."""
+        from .. import ops
+
+        if img_u8.dim() != 3 or img_u8.shape[2] not in (3, 4):
+            raise ValueError("predict_device expects a uint8 [H, W, 3 or 4] image, got %s" % (tuple(img_u8.shape),))
+        small = ops.resample_lanczos_u8(img_u8, SIZE[1], SIZE[0])
+        d0 = self.net.forward(ops.u2net_input(small, MEAN, STD))
+        return ops.resample_lanczos_u8(ops.u2net_mask(d0.contiguous()), img_u8.shape[0], img_u8.shape[1])
+
     @classmethod
     def name(cls, *args, **kwargs):
         return "u2net"
