@@ -109,6 +109,27 @@ int sculpt_triplane_query_ex(const float *planes, int C, int H, int W, const voi
                              unsigned flags, float *density, float *features, float *density_act, float *color,
                              sculpt_stream_t stream);
 
+/* Volume-render rays through a scene code (TriplaneNeRFRenderer._forward, nerf_renderer.py:93-152, with the box test of
+ * utils.py:115-149), one launch; per sample the arithmetic of sculpt_triplane_query_ex(SCULPT_QUERY_CHANNEL_LAST).
+ *   planes_cl   f32 [3][H][W][C]   (sculpt_planes_channel_last of the scene code)
+ *   rays_o/d    f32 [n_rays][3]    world origins and directions (directions as the caller has them: not normalised here)
+ *   t_vals      f32 [S + 1] device: torch.linspace(0, 1, S + 1), made on the host (its fp32 roundings are part of the contract)
+ *   comp_rgb    f32 [n_rays][3]    sum_i w_i color_i + (1 - sum_i w_i); a ray that misses the box is white
+ *   opacity     f32 [n_rays]       sum_i w_i (0 for a miss); may be NULL
+ *   z_vals      f32 [n_rays][S]    sample depths, zero for a miss; may be NULL
+ *   weights     f32 [n_rays][S]    w_i = alpha_i T_i, zero for a miss; may be NULL
+ * A ray's result depends on that ray alone (not on n_rays, its position in the array or the launch geometry). */
+int sculpt_render_rays(const float *planes_cl /* [3][H][W][C] */, int C, int H, int W,
+                       const void *mlp_packed, int n_hidden_64,
+                       const float *rays_o, const float *rays_d /* [n_rays][3] */, int64_t n_rays,
+                       float radius, float density_bias,
+                       const float *t_vals /* device, [S + 1] */, int S,
+                       float *comp_rgb /* [n_rays][3] */,
+                       float *opacity /* nullable [n_rays] */,
+                       float *z_vals  /* nullable [n_rays][S] */,
+                       float *weights /* nullable [n_rays][S] */,
+                       sculpt_stream_t stream);
+
 /* Dense density grid over the lattice slab ix in [x_begin,x_end), flat order ix*R*R + iy*R + iz
  * (isosurface.py:34-37), in two launches:
  *

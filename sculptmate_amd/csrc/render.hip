@@ -1,0 +1,175 @@
+// Volume renderer for gfx950 (MI355X): rays -> box test -> S samples -> fused triplane sample + NeRF-MLP -> alpha composite,
+// one launch, nothing per sample in memory.
+//
+// Replaces (reference file:line):
+//   rays_intersect_bbox                      TripoSR/tsr/utils.py:115-149
+//   TriplaneNeRFRenderer._forward            TripoSR/tsr/models/nerf_renderer.py:93-152
+//
+// Shape ("ray renderer"):
+//   * a wave owns 32 consecutive rays; lane p = lane & 31 is the ray, the two halves h = lane >> 5 split the layer-0 features
+//     exactly as in query_points_kernel (csrc/triplane.hip).  Taps, layer 0, hidden layers, last layer and the two output
+//     activations are the point query's own functions (triplane_mlp.h): a sample's density_act and color are the bits
+//     ops.triplane_query gives at that point from channel-last planes.
+//   * the wave walks s = 0 .. S-1 in order, one 32-point MFMA tile per depth (neighbouring rays at equal depth read neighbouring
+//     texels).  T, sum w and the three colour sums stay in registers; the composite is a plain sequential fp32 product and sum:
+//     no cross-lane operation, no atomics, and a ray's result depends on nothing but the ray -- not on the grid, not on which
+//     rays share its tile.
+//   * a tile with no valid ray is skipped; an invalid ray in a mixed tile samples the box centre and stores white.
+//   * ray geometry and composite are compiled with contraction off (every fp32 operation rounded on its own, as torch on the
+//     CPU does): z_vals and xyz equal the reference's bit for bit.
+// Three quirks of the reference are kept: |d| < 1e-6 becomes +1e-6 whatever the sign of d; delta is the step of the unit
+// interval t_vals, not a world length; T is multiplied by (1 - alpha + 1e-10).
+#include <algorithm>
+
+#include "common.h"
+#include "triplane_mlp.h"
+
+namespace sculpt {
+
+struct RayHit {
+    float t_near, t_far;
+    bool valid;
+};
+
+// utils.py:115-149 with near = 0, valid_thresh = 0.01; `box` = fp32((1 - 1e-3)) * radius
+__device__ __forceinline__ RayHit ray_box(const float o[3], const float d[3], float box) {
+#pragma clang fp contract(off)
+    float tn = 0.f, tf = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float dv = fabsf(d[k]) < 1e-6f ? 1e-6f : d[k];
+        const float i0 = (box - o[k]) / dv, i1 = (-box - o[k]) / dv;
+        const float lo = fminf(i0, i1), hi = fmaxf(i0, i1);
+        tn = k == 0 ? lo : fmaxf(tn, lo);
+        tf = k == 0 ? hi : fminf(tf, hi);
+    }
+    tn = fmaxf(tn, 0.f);
+    RayHit r;
+    r.valid = tf - tn > 0.01f;
+    r.t_near = r.valid ? tn : 0.f;
+    r.t_far = r.valid ? tf : 0.f;
+    return r;
+}
+
+template <int C>
+__global__ __launch_bounds__(512) void render_rays_kernel(
+    const float *__restrict__ planes, int H, int W, const float *__restrict__ blob, const float *__restrict__ rays_o,
+    const float *__restrict__ rays_d, long N, float radius, float span, float box, float density_bias,
+    const float *__restrict__ t_vals, int S, float *__restrict__ comp_rgb, float *__restrict__ opacity,
+    float *__restrict__ z_vals, float *__restrict__ weights, int a0_lds) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
+    const int NH = hd.NH;
+    float *a0s = smem + lds_floats_for(NH);
+    if (a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
+    load_weights_to_lds(smem, blob, hd);
+    const LdsView L = lds_view(smem, NH);
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
+    const int p = lane & 31, h = lane >> 5;
+    const long ntiles = (N + 31) / 32;
+    const float *A0g = blob + hd.off_a0;
+    const long HW = (long)H * W;
+
+    for (long tile = (long)blockIdx.x * nwave + wave; tile < ntiles; tile += (long)gridDim.x * nwave) {
+        const long n = tile * 32 + p;
+        const bool live = n < N, writer = live && h == 0;
+        const long nc = live ? n : N - 1;
+        float o[3], d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { o[k] = rays_o[3 * nc + k]; d[k] = rays_d[3 * nc + k]; }
+        const RayHit hit = ray_box(o, d, box);
+        const bool valid = live && hit.valid;
+        float T = 1.f, sw = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
+        if (__builtin_amdgcn_ballot_w64(valid) != 0) {  // wave-uniform
+            for (int s = 0; s < S; ++s) {
+                float z, x[3], delta;
+                {
+#pragma clang fp contract(off)
+                    const float ta = t_vals[s], tb = t_vals[s + 1];
+                    const float t_mid = (ta + tb) / 2.0f;
+                    z = hit.t_near * (1.0f - t_mid) + hit.t_far * t_mid;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) x[k] = valid ? o[k] + z * d[k] : 0.f;
+                    delta = tb - ta;
+                }
+                int off[3][4];
+                float wt[3][4];
+                point_taps<false>(x[0], x[1], x[2], radius, span, H, W, off, wt);
+                f32x16 acc0 = lds_bias16(L.bacc, 0, h, 0);
+                f32x16 acc1 = lds_bias16(L.bacc, 0, h, 1);
+                layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, acc0, acc1);
+                f32x16 x0 = silu16(acc0), x1 = silu16(acc1);
+                hidden_layers(L, NH, lane, h, x0, x1);
+                const float dens = density_act_f(last_dot(L, 0, h, x0, x1), density_bias);
+                const float r = color_f(last_dot(L, 1, h, x0, x1));
+                const float g = color_f(last_dot(L, 2, h, x0, x1));
+                const float b = color_f(last_dot(L, 3, h, x0, x1));
+                float w;
+                {   // nerf_renderer.py:125-140, one sample further along the ray
+#pragma clang fp contract(off)
+                    const float alpha = 1.0f - expf(-delta * dens);
+                    w = alpha * T;
+                    sw = sw + w;
+                    c0 = c0 + w * r;
+                    c1 = c1 + w * g;
+                    c2 = c2 + w * b;
+                    T = T * ((1.0f - alpha) + 1e-10f);
+                }
+                if (writer) {
+                    if (z_vals) z_vals[n * S + s] = valid ? z : 0.f;
+                    if (weights) weights[n * S + s] = valid ? w : 0.f;
+                }
+            }
+        } else if (writer) {
+            for (int s = 0; s < S; ++s) {
+                if (z_vals) z_vals[n * S + s] = 0.f;
+                if (weights) weights[n * S + s] = 0.f;
+            }
+        }
+        if (writer) {
+#pragma clang fp contract(off)
+            const float op = valid ? sw : 0.f;
+            const float bg = 1.0f - op;  // nerf_renderer.py:149: white behind what the ray did not absorb
+            comp_rgb[3 * n] = (valid ? c0 : 0.f) + bg;
+            comp_rgb[3 * n + 1] = (valid ? c1 : 0.f) + bg;
+            comp_rgb[3 * n + 2] = (valid ? c2 : 0.f) + bg;
+            if (opacity) opacity[n] = op;
+        }
+    }
+}
+
+}  // namespace sculpt
+
+using namespace sculpt;
+
+extern "C" int sculpt_render_rays(const float *planes_cl, int C, int H, int W, const void *mlp_packed, int n_hidden_64,
+                                  const float *rays_o, const float *rays_d, int64_t n_rays, float radius, float density_bias,
+                                  const float *t_vals, int S, float *comp_rgb, float *opacity, float *z_vals, float *weights,
+                                  sculpt_stream_t stream) {
+    SC_REQUIRE(C == 40, "render_rays: built for C=40 channels per plane (got %d)", C);
+    SC_REQUIRE(planes_cl && mlp_packed, "render_rays: null input");
+    SC_REQUIRE(H >= 1 && W >= 1, "render_rays: bad plane size %d x %d", H, W);
+    SC_REQUIRE(n_rays >= 0, "render_rays: negative ray count");
+    SC_REQUIRE(S >= 1, "render_rays: need at least one sample per ray (got %d)", S);
+    SC_REQUIRE(n_hidden_64 >= 0, "render_rays: bad n_hidden_64");
+    SC_REQUIRE(radius > 0.f, "render_rays: radius must be positive");
+    if (n_rays == 0) return 0;
+    SC_REQUIRE(rays_o && rays_d && t_vals && comp_rgb, "render_rays: null rays, t_vals or comp_rgb");
+    size_t lds = (size_t)lds_floats_for(n_hidden_64) * sizeof(float);
+    SC_REQUIRE(lds <= 160 * 1024, "render_rays: %d hidden layers do not fit LDS", n_hidden_64);
+    const size_t a0_bytes = (size_t)3 * C * 64 * sizeof(float);
+    const int a0_lds = lds + a0_bytes <= 160 * 1024 ? 1 : 0;
+    if (a0_lds) lds += a0_bytes;
+    auto kern = render_rays_kernel<40>;
+    SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const long ntiles = ((long)n_rays + 31) / 32;
+    const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
+    const float span = (float)((double)radius - (double)(-radius));
+    const float box = (float)(1.0 - 1.0e-3) * radius;  // utils.py:131-133, the product rounded once in fp32
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W,
+                       reinterpret_cast<const float *>(mlp_packed), rays_o, rays_d, (long)n_rays, radius, span, box, density_bias,
+                       t_vals, S, comp_rgb, opacity, z_vals, weights, a0_lds);
+    SC_LAUNCH_CHECK();
+    return 0;
+}

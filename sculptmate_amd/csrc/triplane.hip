@@ -76,19 +76,11 @@ __global__ __launch_bounds__(512) void query_points_kernel(
     float *__restrict__ density, float *__restrict__ features, float *__restrict__ density_act,
     float *__restrict__ color, int a0_lds) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int K0 = 3 * C, S0 = K0 / 2;
+    constexpr int S0 = 3 * C / 2;
     const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
     const int NH = hd.NH;
-    // layer-0 A operands in LDS as [T][s/4][lane][4] (one ds_read_b128 = four k-steps) when they fit next to the
-    // hidden layers (30 KiB; not with 8 hidden layers = 128 KiB): 30 LDS reads per tile instead of 120 global loads
     float *a0s = smem + lds_floats_for(NH);
-    if (CL && a0_lds) {
-        const float *src = blob + hd.off_a0;
-        for (int i = threadIdx.x; i < 2 * S0 * 64; i += blockDim.x) {
-            const int ln = i & 63, s = (i >> 6) % S0, T = (i >> 6) / S0;
-            a0s[((T * (S0 / 4) + (s >> 2)) * 64 + ln) * 4 + (s & 3)] = src[i];
-        }
-    }
+    if (CL && a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
     load_weights_to_lds(smem, blob, hd);
     const LdsView L = lds_view(smem, NH);
 
@@ -102,69 +94,14 @@ __global__ __launch_bounds__(512) void query_points_kernel(
         long n = tile * 32 + p;
         const bool valid = n < N;
         if (!valid) n = N - 1;
-        float q[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) q[k] = to_unit(pts[3 * n + k], radius, span);
-        // plane pl: (gx, gy) = (q[ia], q[ib]); ia = {0,0,1}, ib = {1,2,2}  (nerf_renderer.py:57-60)
         int off[3][4];
         float wt[3][4];
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-            const float gx = q[pl == 2 ? 1 : 0], gy = q[pl == 0 ? 1 : 2];
-            Tap1 tx = tap_of<AC>(gx, W), ty = tap_of<AC>(gy, H);
-            const float wx = tx.w1, ex = 1.0f - wx, wy = ty.w1, ey = 1.0f - wy;
-            const int x0 = tx.i0, x1 = x0 + 1, y0 = ty.i0, y1 = y0 + 1;
-            const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W;
-            const bool vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
-            const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x1, 0), W - 1);
-            const int cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y1, 0), H - 1);
-            off[pl][0] = cy0 * W + cx0; wt[pl][0] = (vy0 && vx0) ? ey * ex : 0.f;
-            off[pl][1] = cy0 * W + cx1; wt[pl][1] = (vy0 && vx1) ? ey * wx : 0.f;
-            off[pl][2] = cy1 * W + cx0; wt[pl][2] = (vy1 && vx0) ? wy * ex : 0.f;
-            off[pl][3] = cy1 * W + cx1; wt[pl][3] = (vy1 && vx1) ? wy * wx : 0.f;
-        }
+        point_taps<AC>(pts[3 * n], pts[3 * n + 1], pts[3 * n + 2], radius, span, H, W, off, wt);
         // layer 0 on MFMA: step s consumes feature k = h*S0 + s of point p
         f32x16 acc0 = lds_bias16(L.bacc, 0, h, 0);
         f32x16 acc1 = lds_bias16(L.bacc, 0, h, 1);
         if (CL) {
-            static_assert(C % 4 == 0 && (3 * C / 2) % 4 == 0, "channel-last path reads groups of four channels");
-            constexpr int C4 = C / 4;
-            const f32x4 *P4 = reinterpret_cast<const f32x4 *>(planes);
-#pragma unroll 5
-            for (int gq = 0; gq < S0 / 4; ++gq) {
-                const int f = h * S0 + 4 * gq;
-                const int pl = f / C, ch4 = (f - pl * C) >> 2;
-                const f32x4 *B = P4 + (long)pl * HW * C4 + ch4;
-                const int o0 = pl == 0 ? off[0][0] : (pl == 1 ? off[1][0] : off[2][0]);
-                const int o1 = pl == 0 ? off[0][1] : (pl == 1 ? off[1][1] : off[2][1]);
-                const int o2 = pl == 0 ? off[0][2] : (pl == 1 ? off[1][2] : off[2][2]);
-                const int o3 = pl == 0 ? off[0][3] : (pl == 1 ? off[1][3] : off[2][3]);
-                const float w0 = pl == 0 ? wt[0][0] : (pl == 1 ? wt[1][0] : wt[2][0]);
-                const float w1 = pl == 0 ? wt[0][1] : (pl == 1 ? wt[1][1] : wt[2][1]);
-                const float w2 = pl == 0 ? wt[0][2] : (pl == 1 ? wt[1][2] : wt[2][2]);
-                const float w3 = pl == 0 ? wt[0][3] : (pl == 1 ? wt[1][3] : wt[2][3]);
-                const f32x4 t0 = B[(long)o0 * C4], t1 = B[(long)o1 * C4], t2 = B[(long)o2 * C4], t3 = B[(long)o3 * C4];
-                f32x4 qa0, qa1;
-                if (a0_lds) {
-                    qa0 = reinterpret_cast<const f32x4 *>(a0s)[(0 * (S0 / 4) + gq) * 64 + lane];
-                    qa1 = reinterpret_cast<const f32x4 *>(a0s)[(1 * (S0 / 4) + gq) * 64 + lane];
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        qa0[j] = A0g[(0 * S0 + 4 * gq + j) * 64 + lane];
-                        qa1[j] = A0g[(1 * S0 + 4 * gq + j) * 64 + lane];
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float v = t0[j] * w0;  // same tap order as torch: nw + ne + sw + se
-                    v += t1[j] * w1;
-                    v += t2[j] * w2;
-                    v += t3[j] * w3;
-                    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa0[j], v, acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa1[j], v, acc1, 0, 0, 0);
-                }
-            }
+            layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, acc0, acc1);
         } else {
 #pragma unroll 4
         for (int s = 0; s < S0; ++s) {
@@ -198,12 +135,12 @@ __global__ __launch_bounds__(512) void query_points_kernel(
         const float f2 = last_dot(L, 3, h, x0, x1);
         if (valid && h == 0) {
             if (density) density[n] = d;
-            if (density_act) density_act[n] = exp_f(d + density_bias);
+            if (density_act) density_act[n] = density_act_f(d, density_bias);
             if (features) { features[3 * n] = f0; features[3 * n + 1] = f1; features[3 * n + 2] = f2; }
             if (color) {
-                color[3 * n] = __builtin_amdgcn_rcpf(1.0f + exp_f(-f0));
-                color[3 * n + 1] = __builtin_amdgcn_rcpf(1.0f + exp_f(-f1));
-                color[3 * n + 2] = __builtin_amdgcn_rcpf(1.0f + exp_f(-f2));
+                color[3 * n] = color_f(f0);
+                color[3 * n + 1] = color_f(f1);
+                color[3 * n + 2] = color_f(f2);
             }
         }
     }

@@ -178,6 +178,93 @@ __device__ __forceinline__ float to_unit(float p, float radius, float span) {
     return d * 2.0f + (-1.0f);
 }
 
+// The four bilinear taps of a point on each of the three planes: texel offsets (y*W + x, clamped into the plane) and weights
+// (0 for a tap outside: zeros padding).  Plane pl reads (gx, gy) = (q[ia], q[ib]), ia = {0,0,1}, ib = {1,2,2}
+// (nerf_renderer.py:57-60).  Shared by the point query and the ray renderer, so a sample on a ray gets the point query's bits.
+template <bool AC>
+__device__ __forceinline__ void point_taps(float px, float py, float pz, float radius, float span, int H, int W, int (&off)[3][4],
+                                           float (&wt)[3][4]) {
+    const float q[3] = {to_unit(px, radius, span), to_unit(py, radius, span), to_unit(pz, radius, span)};
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+        const float gx = q[pl == 2 ? 1 : 0], gy = q[pl == 0 ? 1 : 2];
+        Tap1 tx = tap_of<AC>(gx, W), ty = tap_of<AC>(gy, H);
+        const float wx = tx.w1, ex = 1.0f - wx, wy = ty.w1, ey = 1.0f - wy;
+        const int x0 = tx.i0, x1 = x0 + 1, y0 = ty.i0, y1 = y0 + 1;
+        const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W;
+        const bool vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
+        const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x1, 0), W - 1);
+        const int cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y1, 0), H - 1);
+        off[pl][0] = cy0 * W + cx0; wt[pl][0] = (vy0 && vx0) ? ey * ex : 0.f;
+        off[pl][1] = cy0 * W + cx1; wt[pl][1] = (vy0 && vx1) ? ey * wx : 0.f;
+        off[pl][2] = cy1 * W + cx0; wt[pl][2] = (vy1 && vx0) ? wy * ex : 0.f;
+        off[pl][3] = cy1 * W + cx1; wt[pl][3] = (vy1 && vx1) ? wy * wx : 0.f;
+    }
+}
+
+// layer-0 A operands in LDS as [T][s/4][lane][4] (one ds_read_b128 = four k-steps) when they fit next to the
+// hidden layers (30 KiB; not with 8 hidden layers = 128 KiB): 30 LDS reads per tile instead of 120 global loads.
+// Call before load_weights_to_lds (its barrier publishes both).
+template <int C>
+__device__ __forceinline__ void stage_a0_in_lds(float *a0s, const float *blob, const MlpPackHeader &hd) {
+    constexpr int S0 = 3 * C / 2;
+    const float *src = blob + hd.off_a0;
+    for (int i = threadIdx.x; i < 2 * S0 * 64; i += blockDim.x) {
+        const int ln = i & 63, s = (i >> 6) % S0, T = (i >> 6) / S0;
+        a0s[((T * (S0 / 4) + (s >> 2)) * 64 + ln) * 4 + (s & 3)] = src[i];
+    }
+}
+
+// Layer 0 of one tile from channel-last planes [3][H][W][C] on the matrix pipe: lane (p, h) samples features
+// k = h*S0 + s, s = 0..S0-1, of its point (four channels per 16-byte load) and step s feeds both 32-neuron tiles.
+template <int C>
+__device__ __forceinline__ void layer0_channel_last(const float *planes, long HW, const int (&off)[3][4], const float (&wt)[3][4],
+                                                    const float *a0s, const float *A0g, int a0_lds, int lane, int h,
+                                                    f32x16 &acc0, f32x16 &acc1) {
+    static_assert(C % 4 == 0 && (3 * C / 2) % 4 == 0, "channel-last path reads groups of four channels");
+    constexpr int S0 = 3 * C / 2, C4 = C / 4;
+    const f32x4 *P4 = reinterpret_cast<const f32x4 *>(planes);
+#pragma unroll 5
+    for (int gq = 0; gq < S0 / 4; ++gq) {
+        const int f = h * S0 + 4 * gq;
+        const int pl = f / C, ch4 = (f - pl * C) >> 2;
+        const f32x4 *B = P4 + (long)pl * HW * C4 + ch4;
+        const int o0 = pl == 0 ? off[0][0] : (pl == 1 ? off[1][0] : off[2][0]);
+        const int o1 = pl == 0 ? off[0][1] : (pl == 1 ? off[1][1] : off[2][1]);
+        const int o2 = pl == 0 ? off[0][2] : (pl == 1 ? off[1][2] : off[2][2]);
+        const int o3 = pl == 0 ? off[0][3] : (pl == 1 ? off[1][3] : off[2][3]);
+        const float w0 = pl == 0 ? wt[0][0] : (pl == 1 ? wt[1][0] : wt[2][0]);
+        const float w1 = pl == 0 ? wt[0][1] : (pl == 1 ? wt[1][1] : wt[2][1]);
+        const float w2 = pl == 0 ? wt[0][2] : (pl == 1 ? wt[1][2] : wt[2][2]);
+        const float w3 = pl == 0 ? wt[0][3] : (pl == 1 ? wt[1][3] : wt[2][3]);
+        const f32x4 t0 = B[(long)o0 * C4], t1 = B[(long)o1 * C4], t2 = B[(long)o2 * C4], t3 = B[(long)o3 * C4];
+        f32x4 qa0, qa1;
+        if (a0_lds) {
+            qa0 = reinterpret_cast<const f32x4 *>(a0s)[(0 * (S0 / 4) + gq) * 64 + lane];
+            qa1 = reinterpret_cast<const f32x4 *>(a0s)[(1 * (S0 / 4) + gq) * 64 + lane];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                qa0[j] = A0g[(0 * S0 + 4 * gq + j) * 64 + lane];
+                qa1[j] = A0g[(1 * S0 + 4 * gq + j) * 64 + lane];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float v = t0[j] * w0;  // same tap order as torch: nw + ne + sw + se
+            v += t1[j] * w1;
+            v += t2[j] * w2;
+            v += t3[j] * w3;
+            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa0[j], v, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(qa1[j], v, acc1, 0, 0, 0);
+        }
+    }
+}
+
+// the two output activations of nerf_renderer.py:82-87: trunc_exp(density + bias) and sigmoid(features)
+__device__ __forceinline__ float density_act_f(float d, float density_bias) { return exp_f(d + density_bias); }
+__device__ __forceinline__ float color_f(float f) { return __builtin_amdgcn_rcpf(1.0f + exp_f(-f)); }
+
 __device__ __forceinline__ void load_row32(const float *row, f32x16 &a, f32x16 &b) {
     const f32x4 *p = reinterpret_cast<const f32x4 *>(row);
 #pragma unroll

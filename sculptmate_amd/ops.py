@@ -91,6 +91,46 @@ def triplane_query(planes, mlp, points, radius=0.87, density_bias=-1.0,
     return {k: v.view(*shape, v.shape[-1]) for k, v in out.items() if v is not None}
 
 
+_t_vals_cache = {}
+
+
+def ray_t_vals(n_samples, device):
+    """torch.linspace(0, 1, S + 1) made on the host (nerf_renderer.py:109-111), uploaded once per (S, device): the fp32
+    roundings of this table are part of the parity contract, like grid_axis_coords for the lattice."""
+    key = (int(n_samples), str(device))
+    t = _t_vals_cache.get(key)
+    if t is None:
+        t = _t_vals_cache[key] = torch.linspace(0, 1, int(n_samples) + 1).to(device)
+    return t
+
+
+def render_rays(planes, mlp, rays_o, rays_d, radius=0.87, density_bias=-1.0, n_samples=128, want=()):
+    """TriplaneNeRFRenderer._forward (nerf_renderer.py:93-152) for one scene code in one launch (sculpt_render_rays).
+    planes: [3,C,H,W] (converted to channel-last here, once) or a ChannelLastPlanes; rays_o / rays_d: [..., 3] world rays.
+    Returns (comp_rgb [..., 3], extras) with extras[k] for k in want: "opacity" [...], "z_vals" [..., S], "weights" [..., S]."""
+    unknown = set(want) - {"opacity", "z_vals", "weights"}
+    if unknown:
+        raise SculptError("render_rays: unknown output %s" % sorted(unknown))
+    if tuple(rays_o.shape) != tuple(rays_d.shape) or rays_o.shape[-1] != 3:
+        raise SculptError("render_rays: rays_o %s and rays_d %s must both be [..., 3]" % (tuple(rays_o.shape), tuple(rays_d.shape)))
+    S = int(n_samples)
+    if S < 1:
+        raise SculptError("render_rays: n_samples must be at least 1")
+    if not isinstance(planes, ChannelLastPlanes):
+        planes = ChannelLastPlanes(planes)
+    shape = tuple(rays_o.shape[:-1])
+    ro = _req(rays_o.reshape(-1, 3).contiguous(), torch.float32, "rays_o")
+    rd = _req(rays_d.reshape(-1, 3).contiguous(), torch.float32, "rays_d")
+    N, dev = ro.shape[0], ro.device
+    rgb = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    out = {k: torch.empty((N,) + w, dtype=torch.float32, device=dev) if k in want else None
+           for k, w in (("opacity", ()), ("z_vals", (S,)), ("weights", (S,)))}
+    check(lib.sculpt_render_rays(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(ro), _ptr(rd),
+                                 N, float(radius), float(density_bias), _ptr(ray_t_vals(S, dev)), S, _ptr(rgb),
+                                 _ptr(out["opacity"]), _ptr(out["z_vals"]), _ptr(out["weights"]), _stream()))
+    return rgb.view(*shape, 3), {k: v.view(*shape, *v.shape[1:]) for k, v in out.items() if v is not None}
+
+
 def grid_axis_coords(resolution, radius):
     """Per-axis lattice coordinate table, computed on the host exactly as the reference does:
     torch.linspace(0, 1, R) (isosurface.py:28-32) then scale_tensor(., (0,1), (-r, r))

@@ -12,6 +12,7 @@ Pipeline per image (reference file:line):
   Transformer1D, 16 blocks                          tsr/models/transformer/transformer_1d.py:179-219
   TriplaneUpsampleNetwork -> scene code [3,40,64,64] tsr/models/network_utils.py:24-32
   extract_mesh: density grid -> marching cubes      tsr/system.py:171-200
+  render: spherical cameras -> ray kernel           tsr/utils.py:339-397, tsr/models/nerf_renderer.py:93-172
 """
 import math
 import os
@@ -23,6 +24,7 @@ import torch
 from .. import _lib, ops
 from ..engine import KernelEngine, prepare_ln_linear
 from .posemb import interpolate_pos_embedding
+from .cameras import get_spherical_cameras
 from .utils import ImagePreprocessor
 
 BF16 = torch.bfloat16
@@ -169,12 +171,16 @@ class MarchingCubeHelper:
 
 
 class TriplaneNeRFRenderer:
-    """tsr/models/nerf_renderer.py:17-91 (mesh path only; the volume renderer is never called)."""
+    """tsr/models/nerf_renderer.py:17-172: the point query of the mesh path and the volume renderer, each one fused launch
+    (sculpt_triplane_query_ex, sculpt_render_rays)."""
 
     def __init__(self, cfg):
         self.cfg = type("Cfg", (), dict(cfg))()
         assert cfg.get("feature_reduction", "concat") == "concat"
         assert cfg.get("density_activation", "exp") == "exp"
+        assert cfg.get("color_activation", "sigmoid") == "sigmoid"
+        self.num_samples_per_ray = int(cfg.get("num_samples_per_ray", 128))
+        self.randomized = bool(cfg.get("randomized", False))
         self.chunk_size = 0
 
     def set_chunk_size(self, chunk_size: int):
@@ -187,6 +193,24 @@ class TriplaneNeRFRenderer:
             triplane = ops.ChannelLastPlanes(triplane)
         return ops.triplane_query(triplane, decoder, positions, radius=self.cfg.radius,
                                   density_bias=self.cfg.density_bias)
+
+    def _forward(self, decoder, triplane, rays_o, rays_d):
+        if self.randomized:
+            raise NotImplementedError("TriplaneNeRFRenderer: randomized=True (jittered samples, a training option) is not "
+                                      "implemented; the ray kernel places samples at the interval midpoints")
+        dev = triplane.data.device if isinstance(triplane, ops.ChannelLastPlanes) else triplane.device
+        rgb, _ = ops.render_rays(triplane, decoder, rays_o.to(dev), rays_d.to(dev), radius=self.cfg.radius,
+                                 density_bias=self.cfg.density_bias, n_samples=self.num_samples_per_ray)
+        return rgb
+
+    def forward(self, decoder, triplane, rays_o, rays_d):
+        """nerf_renderer.py:154-172 -> comp_rgb with the rays' leading shape.  triplane: [3, C, H, W] (or an
+        ops.ChannelLastPlanes) with rays [..., 3] for one scene; [B, 3, C, H, W] with rays [B, ..., 3] for a stack."""
+        if isinstance(triplane, ops.ChannelLastPlanes) or triplane.ndim == 4:
+            return self._forward(decoder, triplane, rays_o, rays_d)
+        return torch.stack([self._forward(decoder, triplane[i], rays_o[i], rays_d[i]) for i in range(triplane.shape[0])], dim=0)
+
+    __call__ = forward
 
 
 def _bf(x, dev):
@@ -784,6 +808,36 @@ class TSR(KernelEngine):
         return twin.forward(image)
 
     __call__ = forward
+
+    # ------------------------------------------------------------------ previews
+    def render(self, scene_codes, n_views: int, elevation_deg: float = 0.0, camera_distance: float = 1.9, fovy_deg: float = 40.0,
+               height: int = 256, width: int = 256, return_type: str = "pt"):
+        """Upstream TripoSR's `model.render`: turntable pictures straight from the scene codes -> per scene code a list of n_views pictures.
+        return_type "pt": float32 [height, width, 3] tensors on the device (nothing is synchronised); "np": float32 arrays;
+        "pil": PIL images of (x * 255) truncated to uint8.  All views of one scene code are one launch of the ray kernel, over
+        planes converted to channel-last once."""
+        if return_type not in ("pt", "np", "pil"):
+            raise ValueError("return_type must be 'pt', 'np' or 'pil'")
+        if self.decoder is None:
+            raise _lib.SculptError("TSR.render: the model has no weights on a device yet (load_state_dict + to(device))")
+        rays_o, rays_d = get_spherical_cameras(n_views, elevation_deg, camera_distance, fovy_deg, height, width)
+        rays_o, rays_d = rays_o.to(self.device, non_blocking=True), rays_d.to(self.device, non_blocking=True)
+        images = []
+        with torch.no_grad():
+            for code in scene_codes:
+                planes = ops.ChannelLastPlanes(code.to(self.device))
+                views = self.renderer(self.decoder, planes, rays_o, rays_d)
+                if return_type == "pt":
+                    images.append(list(views.unbind(0)))
+                    continue
+                host = views.cpu().numpy()
+                if return_type == "np":
+                    images.append([host[i] for i in range(n_views)])
+                else:
+                    from PIL import Image
+
+                    images.append([Image.fromarray((host[i] * 255.0).astype(np.uint8)) for i in range(n_views)])
+        return images
 
     # ------------------------------------------------------------------ mesh extraction
     def set_marching_cubes_resolution(self, resolution: int):
