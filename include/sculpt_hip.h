@@ -130,6 +130,27 @@ int sculpt_render_rays(const float *planes_cl /* [3][H][W][C] */, int C, int H, 
                        float *weights /* nullable [n_rays][S] */,
                        sculpt_stream_t stream);
 
+/* Texture bake of a scene code: colour of every covered texel of a rasterised UV atlas (sculpt_bake_rasterize), one launch;
+ * per covered texel the position (a*u + b*v) + c*w of sculpt_bake_interpolate (gathered through faces[tri] from the indexed
+ * vertices) and the colour of sculpt_triplane_query_ex(SCULPT_QUERY_CHANNEL_LAST) at it, bit for bit; the density row of the
+ * decoder is not evaluated and nothing per texel but the result is written.
+ *   planes_cl   f32 [3][H][W][C]     (sculpt_planes_channel_last of the scene code)
+ *   v_pos       f32 [nv][3], faces i32 or i64 [nf][3] (DEVICE)
+ *   rast        f32 [res][res][4]    (u, v, w, tri) or (0, 0, 0, -1)
+ *   color       f32 [res][res][3]    exactly 0 where the texel is not covered
+ *   mask        u8  [res][res]       1 where covered; may be NULL
+ * A texel whose tri is outside [0, nf), or whose vertex indices are outside [0, nv), counts as not covered and nothing is
+ * read through such an index.  A texel's result depends on that texel alone (not on res, its place in the image or the
+ * launch geometry).  res == 0 is a no-op. */
+int sculpt_bake_scene_color(const float *planes_cl /* [3][H][W][C] */, int C, int H, int W,
+                            const void *mlp_packed, int n_hidden_64,
+                            const float *v_pos /* [nv][3] */, size_t nv,
+                            const void *faces /* [nf][3] */, int faces_i64, size_t nf,
+                            const float *rast /* [res][res][4] = (u, v, w, tri) or (0,0,0,-1) */, int res,
+                            float radius,
+                            float *color /* [res][res][3] */, uint8_t *mask /* nullable [res][res] */,
+                            sculpt_stream_t stream);
+
 /* Dense density grid over the lattice slab ix in [x_begin,x_end), flat order ix*R*R + iy*R + iz
  * (isosurface.py:34-37), in two launches:
  *

@@ -1,0 +1,133 @@
+// Texture bake of a TripoSR scene code for gfx950 (MI355X): rasterised UV atlas -> colour per covered texel, one launch,
+// no position image in memory and no decoder work on texels between the charts.
+//
+// The hot step of upstream TripoSR's --bake-texture (the colour field queried once per covered texel of the unwrapped mesh);
+// the composed route of this library is sculpt_bake_interpolate + sculpt_triplane_query_ex over every texel (what sf3d/bake.py
+// does for its 1 M texels).
+//
+// Shape ("texture bake"):
+//   * a wave owns 32 consecutive texels; lane p = lane & 31 is the texel, the two halves h = lane >> 5 split the layer-0
+//     features exactly as in query_points_kernel (csrc/triplane.hip) and render_rays_kernel (csrc/render.hip).  Taps, layer 0,
+//     hidden layers, the three colour rows of the last layer and the colour activation are the point query's own functions
+//     (triplane_mlp.h): a covered texel's colour is the bits ops.triplane_query gives at the interpolated position from
+//     channel-last planes.  The density row is not evaluated.
+//   * the position is (a*u + b*v) + c*w per component with contraction off: the bits of bake_interpolate_kernel (csrc/baker.hip),
+//     gathered through faces[t] from the indexed vertex array.
+//   * a tile with no covered texel is skipped (wave-uniform ballot) and stores zeros; an uncovered texel in a mixed tile samples
+//     the box centre and stores 0, 0, 0 and mask 0.  A texel's result depends on that texel alone.
+//   * index guard: a texel whose triangle index is outside [0, nf) or whose vertex indices are outside [0, nv) is uncovered;
+//     nothing is read through such an index.
+#include <algorithm>
+
+#include "common.h"
+#include "triplane_mlp.h"
+
+namespace sculpt {
+
+struct Texel {
+    float x[3];
+    bool covered;
+};
+
+// rast = (u, v, w, tri) or (0, 0, 0, -1) -> interpolated position, or the box centre for a texel that is not covered
+__device__ __forceinline__ Texel texel_position(const float4 r, const float *__restrict__ v_pos, long nv, const void *__restrict__ faces,
+                                                int faces_i64, long nf) {
+#pragma clang fp contract(off)
+    Texel tx;
+    tx.x[0] = tx.x[1] = tx.x[2] = 0.f;
+    tx.covered = false;
+    if (!(r.w >= 0.f && r.w < 2147483648.f)) return tx;  // also a NaN
+    const long t = (long)(int)r.w;
+    if (t >= nf) return tx;
+    long i[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        i[k] = faces_i64 ? (long)reinterpret_cast<const long long *>(faces)[3 * t + k] : (long)reinterpret_cast<const int *>(faces)[3 * t + k];
+    if (i[0] < 0 || i[0] >= nv || i[1] < 0 || i[1] >= nv || i[2] < 0 || i[2] >= nv) return tx;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tx.x[k] = v_pos[3 * i[0] + k] * r.x + v_pos[3 * i[1] + k] * r.y + v_pos[3 * i[2] + k] * r.z;
+    tx.covered = true;
+    return tx;
+}
+
+template <int C>
+__global__ __launch_bounds__(512) void bake_scene_color_kernel(
+    const float *__restrict__ planes, int H, int W, const float *__restrict__ blob, const float *__restrict__ v_pos, long nv,
+    const void *__restrict__ faces, int faces_i64, long nf, const float4 *__restrict__ rast, long N, float radius, float span,
+    float *__restrict__ color, uint8_t *__restrict__ mask, int a0_lds) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
+    const int NH = hd.NH;
+    float *a0s = smem + lds_floats_for(NH);
+    if (a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
+    load_weights_to_lds(smem, blob, hd);
+    const LdsView L = lds_view(smem, NH);
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
+    const int p = lane & 31, h = lane >> 5;
+    const long ntiles = (N + 31) / 32;
+    const float *A0g = blob + hd.off_a0;
+    const long HW = (long)H * W;
+
+    for (long tile = (long)blockIdx.x * nwave + wave; tile < ntiles; tile += (long)gridDim.x * nwave) {
+        const long n = tile * 32 + p;
+        const bool live = n < N, writer = live && h == 0;
+        const Texel tx = texel_position(rast[live ? n : N - 1], v_pos, nv, faces, faces_i64, nf);
+        const bool covered = live && tx.covered;
+        float r = 0.f, g = 0.f, b = 0.f;
+        if (__builtin_amdgcn_ballot_w64(covered) != 0) {  // wave-uniform
+            int off[3][4];
+            float wt[3][4];
+            point_taps<false>(tx.x[0], tx.x[1], tx.x[2], radius, span, H, W, off, wt);
+            f32x16 acc0 = lds_bias16(L.bacc, 0, h, 0);
+            f32x16 acc1 = lds_bias16(L.bacc, 0, h, 1);
+            layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, acc0, acc1);
+            f32x16 x0 = silu16(acc0), x1 = silu16(acc1);
+            hidden_layers(L, NH, lane, h, x0, x1);
+            r = color_f(last_dot(L, 1, h, x0, x1));
+            g = color_f(last_dot(L, 2, h, x0, x1));
+            b = color_f(last_dot(L, 3, h, x0, x1));
+        }
+        if (writer) {
+            color[3 * n] = covered ? r : 0.f;
+            color[3 * n + 1] = covered ? g : 0.f;
+            color[3 * n + 2] = covered ? b : 0.f;
+            if (mask) mask[n] = covered ? 1 : 0;
+        }
+    }
+}
+
+}  // namespace sculpt
+
+using namespace sculpt;
+
+extern "C" int sculpt_bake_scene_color(const float *planes_cl, int C, int H, int W, const void *mlp_packed, int n_hidden_64,
+                                       const float *v_pos, size_t nv, const void *faces, int faces_i64, size_t nf, const float *rast,
+                                       int res, float radius, float *color, uint8_t *mask, sculpt_stream_t stream) {
+    SC_REQUIRE(C == 40, "bake_scene_color: built for C=40 channels per plane (got %d)", C);
+    SC_REQUIRE(planes_cl && mlp_packed, "bake_scene_color: null input");
+    SC_REQUIRE(H >= 1 && W >= 1, "bake_scene_color: bad plane size %d x %d", H, W);
+    SC_REQUIRE(res >= 0, "bake_scene_color: negative resolution");
+    SC_REQUIRE(n_hidden_64 >= 0, "bake_scene_color: bad n_hidden_64");
+    SC_REQUIRE(radius > 0.f, "bake_scene_color: radius must be positive");
+    SC_REQUIRE(nv <= (size_t)1 << 40 && nf <= (size_t)1 << 40, "bake_scene_color: mesh too large");
+    if (res == 0) return 0;
+    SC_REQUIRE(rast && color, "bake_scene_color: null rast or color");
+    SC_REQUIRE(nf == 0 || (v_pos && faces && nv > 0), "bake_scene_color: null mesh");
+    size_t lds = (size_t)lds_floats_for(n_hidden_64) * sizeof(float);
+    SC_REQUIRE(lds <= 160 * 1024, "bake_scene_color: %d hidden layers do not fit LDS", n_hidden_64);
+    const size_t a0_bytes = (size_t)3 * C * 64 * sizeof(float);
+    const int a0_lds = lds + a0_bytes <= 160 * 1024 ? 1 : 0;
+    if (a0_lds) lds += a0_bytes;
+    auto kern = bake_scene_color_kernel<40>;
+    SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const long N = (long)res * res;
+    const long ntiles = (N + 31) / 32;
+    const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
+    const float span = (float)((double)radius - (double)(-radius));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W,
+                       reinterpret_cast<const float *>(mlp_packed), v_pos, (long)nv, faces, faces_i64, (long)nf,
+                       reinterpret_cast<const float4 *>(rast), N, radius, span, color, mask, a0_lds);
+    SC_LAUNCH_CHECK();
+    return 0;
+}

@@ -22,12 +22,16 @@ class TripoGenerator(GeneratorFacade):
       "bf16l3" the same tolerance with the fp32 exponent range: every matrix product with both operands split exactly into three
                bf16 limbs, fp32 accumulate (~3.6x the forward time);
       "fp32"   the exact-fp32 matrix instruction (slowest; the parity yard-stick).
-    The environment variable SCULPT_PRECISION overrides the default for an add-on that cannot be edited."""
+    The environment variable SCULPT_PRECISION overrides the default for an add-on that cannot be edited.
+    `bake_texture_resolution` (default 0): with the add-on's texture tick box set (generate_mesh(enable_texture=True)), a value
+    above 0 bakes a UV texture of that size from the scene code (TSR.bake_texture; upstream's default is 2048) instead of one
+    colour per vertex."""
 
     def __init__(self, device):
         super().__init__(device, checkpoint_dir=ROOT_DIR + "/checkpoints/", chunk_size=8192, mc_resolution=256,
                          precision=os.environ.get("SCULPT_PRECISION", "bf16"))
         self.last_meshes = None  # headless callers read the result here (inside Blender it goes to the scene)
+        self.bake_texture_resolution = 0
 
     def _construct_model(self):
         model = TSR.from_pretrained(self.checkpoint_dir, config_name="config.yaml", weight_name="model.ckpt",
@@ -42,7 +46,8 @@ class TripoGenerator(GeneratorFacade):
             with torch.no_grad():
                 codes = self.model([input_image], device=self.device)
             self.last_meshes = self.model.extract_mesh(codes, enable_texture=enable_texture, mesh_name=input_name,
-                                                       resolution=self.mc_resolution)
+                                                       resolution=self.mc_resolution,
+                                                       bake_texture=int(self.bake_texture_resolution or 0))
         except Exception as err:
             print(self.run_error_tag, err)
             return STATUS_FAILED

@@ -23,6 +23,33 @@ def write_obj(path, vertices, faces, vertex_colors=None):
         np.savetxt(fh, f, fmt="f %d %d %d")
 
 
+def write_obj_textured(path, vertices, faces, uvs, texture):
+    """A mesh with per-corner UVs and a base-colour picture: `v` lines (positions stay shared), one `vt u v` line per face
+    corner (uvs f32 [3*Nf, 2], origin bottom-left -- OBJ's own convention), `f v/vt` faces (1-based), and beside the file
+    NAME.mtl (`map_Kd NAME.png`) and NAME.png (texture uint8 [H,W,3], row 0 at the top)."""
+    import os
+
+    v = np.asarray(vertices, np.float64)
+    f = np.asarray(faces, np.int64)
+    uv = np.asarray(uvs, np.float64)
+    if uv.shape != (3 * len(f), 2):
+        raise ValueError("write_obj_textured: uvs %s must be [3*Nf, 2] = [%d, 2]" % (uv.shape, 3 * len(f)))
+    stem = os.path.splitext(str(path))[0]
+    name = os.path.basename(stem)
+    corner = np.arange(3 * len(f), dtype=np.int64).reshape(-1, 3)
+    rec = np.stack([f, corner], 2).reshape(-1, 6) + 1
+    with open(path, "w") as fh:
+        fh.write("# sculptmate_amd\nmtllib %s.mtl\n" % name)
+        np.savetxt(fh, v, fmt="v %.7g %.7g %.7g")
+        np.savetxt(fh, uv, fmt="vt %.7g %.7g")
+        fh.write("usemtl %s_material\n" % name)
+        np.savetxt(fh, rec, fmt="f %d/%d %d/%d %d/%d")
+    with open(stem + ".mtl", "w") as fh:
+        fh.write("# sculptmate_amd\nnewmtl %s_material\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd %s.png\n" % (name, name))
+    with open(stem + ".png", "wb") as fh:
+        fh.write(encode_png(texture))
+
+
 def read_obj(path):
     vs, cs, fs = [], [], []
     with open(path) as fh:

@@ -618,6 +618,35 @@ def bake_interpolate(attr, rast, face_indices):
     return out
 
 
+def bake_scene_color(planes, mlp, v_pos, faces, rast, radius=0.87):
+    """Colour of a TripoSR scene code at every covered texel of a rasterised atlas, one launch (sculpt_bake_scene_color):
+    the position bake_interpolate gives and the colour triplane_query gives there from channel-last planes, bit for bit, with
+    no position image in between and no decoder work on texels outside the charts.
+    planes: [3,C,H,W] (converted to channel-last here, once) or a ChannelLastPlanes; v_pos f32 [Nv,3]; faces i32 / i64 [Nf,3]
+    indexing v_pos; rast f32 [res,res,4] from bake_rasterize.  -> (color f32 [res,res,3], exactly 0 where not covered;
+    mask bool [res,res])."""
+    if not isinstance(planes, ChannelLastPlanes):
+        planes = ChannelLastPlanes(planes)
+    v = _req(v_pos.contiguous() if isinstance(v_pos, torch.Tensor) else v_pos, torch.float32, "v_pos")
+    if not (isinstance(faces, torch.Tensor) and faces.is_cuda):
+        raise SculptError("faces must be a CUDA/HIP tensor (no CPU fallback)")
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise SculptError("bake_scene_color: faces must be int32 or int64, got %s" % faces.dtype)
+    f = faces.contiguous()
+    r = _req(rast.contiguous() if isinstance(rast, torch.Tensor) else rast, torch.float32, "rast")
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise SculptError("bake_scene_color: v_pos %s must be [Nv, 3] and faces %s [Nf, 3]" % (tuple(v.shape), tuple(f.shape)))
+    if r.ndim != 3 or r.shape[0] != r.shape[1] or r.shape[2] != 4:
+        raise SculptError("bake_scene_color: rast %s must be [res, res, 4]" % (tuple(r.shape),))
+    res = r.shape[0]
+    color = torch.empty((res, res, 3), dtype=torch.float32, device=r.device)
+    mask = torch.empty((res, res), dtype=torch.uint8, device=r.device)
+    check(lib.sculpt_bake_scene_color(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(v), v.shape[0],
+                                      _ptr(f), int(f.dtype == torch.int64), f.shape[0], _ptr(r), res, float(radius), _ptr(color),
+                                      _ptr(mask), _stream()))
+    return color, mask.view(torch.bool)
+
+
 def resize_aa_bilinear(img_hwc, size):
     """F.interpolate(bilinear, align_corners=False, antialias=True) to (size, size) on an HWC fp32 device image
     (ImagePreprocessor.convert_and_resize, tsr/utils.py:82-88)."""

@@ -36,3 +36,44 @@ def import_obj_blender(verts, faces, vertex_colors=None, name="NewMesh"):
     bsdf.inputs["Roughness"].default_value = 1
     bsdf.inputs["IOR"].default_value = 1.00
     return new_object
+
+
+def import_textured_blender(verts, faces, uvs, texture_image, name="NewMesh"):
+    """The sink of a baked mesh (TSR.bake_texture): shared vertices, per-loop UVs (uvs f32 [3*Nf, 2] in face-corner order,
+    origin bottom-left as Blender has it) and a material whose image texture feeds the Principled BSDF's Base Color;
+    Roughness 1 and IOR 1.00 as the vertex-colour material above sets them.  Blender's UV layers are per loop, so nothing is
+    un-indexed; the loop order must be faces.ravel() for uvs to land on the right corners, which is verified, not assumed."""
+    import bpy
+
+    from ..sf3d.blender_sink import _image
+
+    faces = np.asarray(faces)
+    uvs = np.asarray(uvs, np.float32)
+    if uvs.shape != (faces.size, 2):
+        raise ValueError("import_textured_blender: uvs %s must be [3*Nf, 2] = [%d, 2]" % (uvs.shape, faces.size))
+    mesh_data = bpy.data.meshes.new(name=name)
+    mesh_data.from_pydata(np.asarray(verts).tolist(), [], faces.tolist())
+    loop_vert = np.empty(len(mesh_data.loops), np.int32)
+    mesh_data.loops.foreach_get("vertex_index", loop_vert)
+    if loop_vert.size != faces.size or not np.array_equal(loop_vert, faces.reshape(-1)):
+        raise RuntimeError("import_textured_blender: Blender's loops are not in face-corner order (%d loops for %d corners); "
+                           "the UVs would land on the wrong corners" % (loop_vert.size, faces.size))
+    new_object = bpy.data.objects.new(name=name, object_data=mesh_data)
+    bpy.context.collection.objects.link(new_object)
+    mesh_data.uv_layers.new(name="UVMap")
+    mesh_data.uv_layers.active.data.foreach_set("uv", uvs.ravel())
+    mat = bpy.data.materials.new(name="BakedTextureMaterial")
+    mesh_data.materials.append(mat)
+    mat.use_nodes = True
+    nodes, links = mat.node_tree.nodes, mat.node_tree.links
+    for node in list(nodes):
+        nodes.remove(node)
+    out_node = nodes.new(type="ShaderNodeOutputMaterial")
+    bsdf = nodes.new(type="ShaderNodeBsdfPrincipled")
+    tex = nodes.new(type="ShaderNodeTexImage")
+    tex.image = _image(bpy, "%s_BaseColor" % name, texture_image.convert("RGBA"))
+    links.new(tex.outputs["Color"], bsdf.inputs["Base Color"])
+    links.new(bsdf.outputs["BSDF"], out_node.inputs["Surface"])
+    bsdf.inputs["Roughness"].default_value = 1
+    bsdf.inputs["IOR"].default_value = 1.00
+    return new_object

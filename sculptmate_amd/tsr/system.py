@@ -36,26 +36,55 @@ from .spec import DEFAULT_CFG, IMAGE_MEAN, IMAGE_STD, param_spec  # noqa: E402,F
 class Mesh:
     """What run() returns per image: trimesh-constructible arrays."""
 
-    def __init__(self, vertices, faces, vertex_colors=None):
+    def __init__(self, vertices, faces, vertex_colors=None, uvs=None, texture=None):
+        """uvs / texture: what TSR.bake_texture adds -- uvs f32 [3*Nf, 2] per face corner (origin bottom-left, the convention of
+        sf3d and meshio.write_glb), texture f32 [res, res, 3] in [0, 1] with row 0 at the top."""
         self.vertices = vertices
         self.faces = faces
         self.vertex_colors = vertex_colors
+        self.uvs = uvs
+        self.texture = texture
 
     def to_trimesh(self):  # pragma: no cover (trimesh is optional)
         import trimesh
 
         return trimesh.Trimesh(vertices=self.vertices, faces=self.faces, vertex_colors=self.vertex_colors)
 
+    def texture_image(self):
+        """The baked texture as a uint8 RGB PIL picture: floor(256 x) clipped to 0..255, no dither (deterministic)."""
+        from PIL import Image
+
+        from ..sf3d.bake import float32_to_uint8_np
+
+        if self.texture is None:
+            raise ValueError("Mesh.texture_image: this mesh has no baked texture (TSR.bake_texture)")
+        return Image.fromarray(float32_to_uint8_np(_host(self.texture).astype(np.float32), dither=False))
+
     def export(self, path):
         """Write .obj / .ply / .glb by extension (sculptmate_amd/meshio.py), the call upstream users make on the
-        trimesh object their extract_mesh returns."""
+        trimesh object their extract_mesh returns.  A baked mesh (uvs + texture) goes out textured: .glb with TEXCOORD_0 and the
+        base-colour texture (glTF has one index per vertex, so positions are un-indexed to 3*Nf vertices there and only there),
+        .obj with `vt` lines, `f v/vt` faces and a .mtl + .png beside the file (positions stay shared)."""
         from .. import meshio
 
         ext = str(path).rsplit(".", 1)[-1].lower()
         writer = {"obj": meshio.write_obj, "ply": meshio.write_ply, "glb": meshio.write_glb}.get(ext)
         if writer is None:
             raise ValueError(f"unsupported mesh format .{ext} (obj, ply, glb)")
+        if self.uvs is not None and self.texture is not None and ext in ("glb", "obj"):
+            v, f, uv = _host(self.vertices), _host(self.faces), _host(self.uvs)
+            picture = np.asarray(self.texture_image())
+            if ext == "glb":
+                meshio.write_glb(str(path), v[f.reshape(-1)], np.arange(f.size, dtype=np.int64).reshape(-1, 3), uvs=uv,
+                                 basecolor_tex=picture)
+            else:
+                meshio.write_obj_textured(str(path), v, f, uv, picture)
+            return
         writer(str(path), self.vertices, self.faces, vertex_colors=self.vertex_colors)
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
 class _PinnedPool:
@@ -266,6 +295,8 @@ class TSR(KernelEngine):
         self.isosurface_helper = None
         self.decoder = None  # ops.PackedMLP after to(device)
         self.mesh_sink = None  # callable(verts, faces, colors, name); default: bpy if importable
+        self.textured_mesh_sink = None  # callable(verts, faces, uvs, image, name) for baked meshes; default: bpy if importable
+        self._unwrapper = None  # the cached BoxProjectionUnwrapper of bake_texture
         # forward(): images per transformer pass.  1 (default): image by image.  > 1: the reference's batched pass
         # (system.py:82-115) over stacked token rows; in the bf16 mode it gives each image the bits of its single-image pass
         # (every GEMM keeps the single-image tile form: encode_images), which is why run() batches by default there
@@ -845,11 +876,49 @@ class TSR(KernelEngine):
             return
         self.isosurface_helper = MarchingCubeHelper(resolution)
 
+    def bake_texture(self, mesh: Mesh, scene_code, texture_resolution: int = 2048, island_padding: float = 0.02, unwrapper=None) -> Mesh:
+        """Upstream TripoSR's --bake-texture: unwrap `mesh`, query the colour field of `scene_code` ([3, C, H, W]) once per
+        covered texel, pad the charts -> a Mesh with the same vertices and faces, vertex_colors None, uvs f32 [3*Nf, 2] per face
+        corner (origin bottom-left) and texture f32 [res, res, 3] (row 0 at the top), all on the device.
+        Stages: ops.vertex_normals -> unwrapper(v_pos, v_nrm, faces, island_padding) (default: one cached
+        sf3d.unwrap.BoxProjectionUnwrapper; sf3d.bake.cell_atlas_unwrapper, the hook form of ops.uv_cell_atlas, is the
+        deterministic stand-in) -> ops.bake_rasterize on the per-corner UVs -> ops.bake_scene_color (one fused launch) ->
+        ops.dilate_fill with res // 150 iterations, the padding rule of the SF3D bake.  Nothing here waits for the device (the
+        box-projection unwrapper itself reads two small sums back)."""
+        if self.decoder is None:
+            raise _lib.SculptError("TSR.bake_texture: the model has no weights on a device yet (load_state_dict + to(device))")
+        res = int(texture_resolution)
+        if res < 1:
+            raise ValueError("TSR.bake_texture: texture_resolution must be positive")
+        if scene_code.ndim == 5 and scene_code.shape[0] == 1:
+            scene_code = scene_code[0]
+        with torch.no_grad():
+            v = _f32(mesh.vertices, self.device)
+            f = torch.as_tensor(mesh.faces).to(self.device).contiguous()
+            if unwrapper is None:
+                if self._unwrapper is None:
+                    from ..sf3d.unwrap import BoxProjectionUnwrapper
+
+                    self._unwrapper = BoxProjectionUnwrapper()
+                unwrapper = self._unwrapper
+            uv, corner = unwrapper(v, ops.vertex_normals(v, f), f, island_padding)
+            uv = uv.to(torch.float32)[corner.reshape(-1).long()].contiguous()   # per corner, whatever rows the unwrapper shares
+            rast = ops.bake_rasterize(uv, torch.arange(3 * f.shape[0], device=self.device, dtype=torch.int32).view(-1, 3), res)
+            planes = scene_code if isinstance(scene_code, ops.ChannelLastPlanes) else ops.ChannelLastPlanes(scene_code.to(self.device))
+            color, mask = ops.bake_scene_color(planes, self.decoder, v, f, rast, radius=self.renderer.cfg.radius)
+            it = res // 150
+            if it > 0:
+                color = ops.dilate_fill(color.permute(2, 0, 1)[None].contiguous(), mask[None, None], iterations=it)[0].permute(1, 2, 0).contiguous()
+        return Mesh(mesh.vertices, mesh.faces, None, uvs=uv, texture=color)
+
     def extract_meshes(self, scene_codes, enable_texture=False, resolution: int = 256, threshold: float = 25.0,
-                       x_range=None, density_events=None) -> List[Mesh]:
+                       x_range=None, density_events=None, bake_texture: int = 0) -> List[Mesh]:
         """The arithmetic of system.py:171-200 without the Blender sink: returns device tensors.
         density_events: optional (start, stop) torch events recorded around the dense-grid launch (bench.py's live
-        per-launch timing of the dominant kernel, on the stream it is launched on)."""
+        per-launch timing of the dominant kernel, on the stream it is launched on).
+        bake_texture: with enable_texture, a resolution > 0 bakes a UV texture of that size (TSR.bake_texture) instead of
+        computing vertex colours; 0 (default): vertex colours as before."""
+        bake = int(bake_texture) if enable_texture else 0
         self.set_marching_cubes_resolution(resolution)
         r = self.renderer.cfg.radius
         R = resolution
@@ -865,18 +934,21 @@ class TSR(KernelEngine):
             # density_act - threshold == -(-(density_act - threshold))  (system.py:184, isosurface.py:45)
             if self._filter_applies(planes, R, threshold):
                 v_pos, t_pos_idx = self._extract_filtered(planes, R, mc, dkw, density_events)
-                color = None
-                if enable_texture:
-                    color = self.renderer.query_triplane(self.decoder, v_pos, planes)["color"]
-                out.append(Mesh(v_pos, t_pos_idx, color))
+                out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake))
                 continue
             vol = ops.density_grid(planes, self.decoder, R, precision=self.decoder_precision, events=density_events, **dkw)
             v_pos, t_pos_idx = mc(vol)   # (both decoder modes have the fp32 range: a NaN here is a NaN of the model)
-            color = None
-            if enable_texture:
-                color = self.renderer.query_triplane(self.decoder, v_pos, planes)["color"]
-            out.append(Mesh(v_pos, t_pos_idx, color))
+            out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake))
         return out
+
+    def _textured(self, v_pos, t_pos_idx, planes, enable_texture, bake):
+        """The appearance half of extract_meshes: nothing, vertex colours (system.py:189-193) or a baked texture."""
+        if enable_texture and bake > 0:
+            return self.bake_texture(Mesh(v_pos, t_pos_idx), planes, bake)
+        color = None
+        if enable_texture:
+            color = self.renderer.query_triplane(self.decoder, v_pos, planes)["color"]
+        return Mesh(v_pos, t_pos_idx, color)
 
     # -- the two-pass ("filtered") density grid: calibration, guard, fallback (csrc/density_filter.hip)
     FILTER_SAFETY = 8.0        # margin = FILTER_SAFETY x the largest coarse error of the calibration probe
@@ -981,12 +1053,20 @@ class TSR(KernelEngine):
         return Mesh(v_pos, t_pos_idx, color)
 
     def extract_mesh(self, scene_codes, enable_texture=False, mesh_name="NewMesh", resolution: int = 256,
-                     threshold: float = 25.0):
-        """system.py:171-200: same signature; pushes each mesh into the sink (Blender when `bpy` is
-        importable, exactly like the reference's import_obj_blender) and also returns the meshes."""
-        meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold)
+                     threshold: float = 25.0, bake_texture: int = 0):
+        """system.py:171-200: same signature (+ bake_texture, see extract_meshes); pushes each mesh into the sink (Blender when
+        `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
+        the textured sink (per-loop UVs + an image-texture material)."""
+        meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture)
         sink = self.mesh_sink or _default_sink()
         for m in meshes:
+            if m.texture is not None:
+                tsink = self.textured_mesh_sink or (_default_textured_sink() if self.mesh_sink is None else None)
+                if tsink is not None:
+                    tsink(_host(m.vertices), _host(m.faces), _host(m.uvs), m.texture_image(), mesh_name)
+                elif sink is not None:   # a caller's own four-argument sink: the geometry, without colours
+                    sink(_host(m.vertices), _host(m.faces), None, mesh_name)
+                continue
             if sink is not None:
                 sink(m.vertices.cpu().numpy(), m.faces.cpu().numpy(),
                      None if m.vertex_colors is None else m.vertex_colors.cpu().numpy(), mesh_name)
@@ -1113,6 +1193,16 @@ def _default_sink():
     from .blender_sink import import_obj_blender
 
     return import_obj_blender
+
+
+def _default_textured_sink():
+    try:
+        import bpy  # noqa: F401
+    except Exception:
+        return None
+    from .blender_sink import import_textured_blender
+
+    return import_textured_blender
 
 
 def load_config(yaml_path: str, vit_json_path: Optional[str] = None):
