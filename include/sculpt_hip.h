@@ -151,6 +151,24 @@ int sculpt_bake_scene_color(const float *planes_cl /* [3][H][W][C] */, int C, in
                             float *color /* [res][res][3] */, uint8_t *mask /* nullable [res][res] */,
                             sculpt_stream_t stream);
 
+/* Gradient of the raw density (the decoder's output 0, before bias and exp) with respect to the query point, in world units,
+ * and the outward unit normal of the density's iso-surface through the point: forward-mode differentiation of
+ * sculpt_triplane_query_ex(SCULPT_QUERY_CHANNEL_LAST), one launch, 8 points x {value, d/dx, d/dy, d/dz} per MFMA tile.
+ *   planes_cl   f32 [3][H][W][C]   (sculpt_planes_channel_last of the scene code)
+ *   points      f32 [N][3]
+ *   flags       0 or SCULPT_QUERY_ALIGN_CORNERS
+ *   grad        f32 [N][3]   d density / d p; floor's one-sided derivative where a pixel coordinate is an integer (torch
+ *                            autograd's); exactly 0 for a point outside all three planes
+ *   normal      f32 [N][3]   -grad / |grad| (the density grows inwards); exactly (0,0,0) where |grad| is 0 or not finite
+ *   density     f32 [N]      the `density` of sculpt_triplane_query_ex at the point, bit for bit
+ * Each output may be NULL, not all three.  A point's result depends on that point alone (not on N, its place in the array or
+ * the launch geometry).  Refused: C != 40, N < 0, unknown flags, all outputs NULL (with N > 0).  N == 0 is a no-op. */
+int sculpt_triplane_density_grad(const float *planes_cl /* [3][H][W][C] */, int C, int H, int W,
+                                 const void *mlp_packed, int n_hidden_64,
+                                 const float *points /* [N][3] */, long long N, float radius, int flags /* QUERY_ALIGN_CORNERS */,
+                                 float *grad /* [N][3] or null */, float *normal /* [N][3] or null */, float *density /* [N] or null */,
+                                 sculpt_stream_t stream);
+
 /* Dense density grid over the lattice slab ix in [x_begin,x_end), flat order ix*R*R + iy*R + iz
  * (isosurface.py:34-37), in two launches:
  *

@@ -25,13 +25,17 @@ class TripoGenerator(GeneratorFacade):
     The environment variable SCULPT_PRECISION overrides the default for an add-on that cannot be edited.
     `bake_texture_resolution` (default 0): with the add-on's texture tick box set (generate_mesh(enable_texture=True)), a value
     above 0 bakes a UV texture of that size from the scene code (TSR.bake_texture; upstream's default is 2048) instead of one
-    colour per vertex."""
+    colour per vertex.
+    `vertex_normals` (default None): "field" leaves smooth unit normals on the meshes in `last_meshes` (Mesh.vertex_normals, the
+    gradient of the density field at each vertex: TSR.field_normals), "faces" the averaged facet normals; Mesh.export writes
+    them.  The Blender sinks take none: Blender shades shared vertices smooth by itself."""
 
     def __init__(self, device):
         super().__init__(device, checkpoint_dir=ROOT_DIR + "/checkpoints/", chunk_size=8192, mc_resolution=256,
                          precision=os.environ.get("SCULPT_PRECISION", "bf16"))
         self.last_meshes = None  # headless callers read the result here (inside Blender it goes to the scene)
         self.bake_texture_resolution = 0
+        self.vertex_normals = None
 
     def _construct_model(self):
         model = TSR.from_pretrained(self.checkpoint_dir, config_name="config.yaml", weight_name="model.ckpt",
@@ -47,7 +51,8 @@ class TripoGenerator(GeneratorFacade):
                 codes = self.model([input_image], device=self.device)
             self.last_meshes = self.model.extract_mesh(codes, enable_texture=enable_texture, mesh_name=input_name,
                                                        resolution=self.mc_resolution,
-                                                       bake_texture=int(self.bake_texture_resolution or 0))
+                                                       bake_texture=int(self.bake_texture_resolution or 0),
+                                                       normals=self.vertex_normals)
         except Exception as err:
             print(self.run_error_tag, err)
             return STATUS_FAILED

@@ -8,8 +8,26 @@ users export them through trimesh, which is not a dependency here.
 import numpy as np
 
 
-def write_obj(path, vertices, faces, vertex_colors=None):
-    """`v x y z [r g b]` / `f a b c` (1-based), one numpy formatting pass per block."""
+def _normals_for(normals, nv, who):
+    n = np.asarray(normals, np.float32)
+    if n.shape != (nv, 3):
+        raise ValueError("%s: normals %s must be [Nv, 3] = [%d, 3]" % (who, n.shape, nv))
+    return n
+
+
+class MeshArrays(tuple):
+    """What read_obj / read_ply return: the tuple (vertices, faces, colours | None) they always returned, with the normals
+    of the file (f32 [Nv, 3], or None) beside it as `.normals`."""
+
+    def __new__(cls, vertices, faces, colors, normals=None):
+        self = tuple.__new__(cls, (vertices, faces, colors))
+        self.normals = normals
+        return self
+
+
+def write_obj(path, vertices, faces, vertex_colors=None, normals=None):
+    """`v x y z [r g b]` / `f a b c` (1-based), one numpy formatting pass per block.  normals f32 [Nv, 3] (one per vertex):
+    `vn x y z` lines after the vertices and `f a//a b//b c//c` faces."""
     v = np.asarray(vertices, np.float64)
     f = np.asarray(faces, np.int64) + 1
     if vertex_colors is not None:
@@ -20,13 +38,18 @@ def write_obj(path, vertices, faces, vertex_colors=None):
     with open(path, "w") as fh:
         fh.write("# sculptmate_amd\n")
         np.savetxt(fh, v, fmt=fmt)
-        np.savetxt(fh, f, fmt="f %d %d %d")
+        if normals is None:
+            np.savetxt(fh, f, fmt="f %d %d %d")
+        else:
+            np.savetxt(fh, _normals_for(normals, len(v), "write_obj").astype(np.float64), fmt="vn %.7g %.7g %.7g")
+            np.savetxt(fh, np.repeat(f, 2, axis=1), fmt="f %d//%d %d//%d %d//%d")
 
 
-def write_obj_textured(path, vertices, faces, uvs, texture):
+def write_obj_textured(path, vertices, faces, uvs, texture, normals=None):
     """A mesh with per-corner UVs and a base-colour picture: `v` lines (positions stay shared), one `vt u v` line per face
     corner (uvs f32 [3*Nf, 2], origin bottom-left -- OBJ's own convention), `f v/vt` faces (1-based), and beside the file
-    NAME.mtl (`map_Kd NAME.png`) and NAME.png (texture uint8 [H,W,3], row 0 at the top)."""
+    NAME.mtl (`map_Kd NAME.png`) and NAME.png (texture uint8 [H,W,3], row 0 at the top).  normals f32 [Nv, 3] (one per shared
+    vertex): `vn` lines after the `vt` lines and `f v/vt/vn` faces."""
     import os
 
     v = np.asarray(vertices, np.float64)
@@ -42,8 +65,13 @@ def write_obj_textured(path, vertices, faces, uvs, texture):
         fh.write("# sculptmate_amd\nmtllib %s.mtl\n" % name)
         np.savetxt(fh, v, fmt="v %.7g %.7g %.7g")
         np.savetxt(fh, uv, fmt="vt %.7g %.7g")
+        if normals is not None:
+            np.savetxt(fh, _normals_for(normals, len(v), "write_obj_textured").astype(np.float64), fmt="vn %.7g %.7g %.7g")
         fh.write("usemtl %s_material\n" % name)
-        np.savetxt(fh, rec, fmt="f %d/%d %d/%d %d/%d")
+        if normals is None:
+            np.savetxt(fh, rec, fmt="f %d/%d %d/%d %d/%d")
+        else:
+            np.savetxt(fh, np.stack([f, corner, f], 2).reshape(-1, 9) + 1, fmt="f %d/%d/%d %d/%d/%d %d/%d/%d")
     with open(stem + ".mtl", "w") as fh:
         fh.write("# sculptmate_amd\nnewmtl %s_material\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd %s.png\n" % (name, name))
     with open(stem + ".png", "wb") as fh:
@@ -51,7 +79,9 @@ def write_obj_textured(path, vertices, faces, uvs, texture):
 
 
 def read_obj(path):
-    vs, cs, fs = [], [], []
+    """-> MeshArrays (vertices f32, faces i64 of the position indices, colours f32 | None), `.normals` f32 [Nv, 3] | None: the
+    `vn` lines brought into vertex order through the faces' normal indices (the writers above give every vertex one normal)."""
+    vs, cs, fs, ns, fn = [], [], [], [], []
     with open(path) as fh:
         for line in fh:
             p = line.split()
@@ -61,9 +91,18 @@ def read_obj(path):
                 vs.append([float(x) for x in p[1:4]])
                 if len(p) >= 7:
                     cs.append([float(x) for x in p[4:7]])
+            elif p[0] == "vn":
+                ns.append([float(x) for x in p[1:4]])
             elif p[0] == "f":
                 fs.append([int(x.split("/")[0]) - 1 for x in p[1:4]])
-    return (np.array(vs, np.float32), np.array(fs, np.int64), np.array(cs, np.float32) if cs else None)
+                if ns:
+                    fn.append([int(x.split("/")[2]) - 1 for x in p[1:4]])
+    v, f = np.array(vs, np.float32), np.array(fs, np.int64)
+    normals = None
+    if ns:
+        normals = np.zeros((len(v), 3), np.float32)
+        normals[f.reshape(-1)] = np.array(ns, np.float32)[np.array(fn, np.int64).reshape(-1)]
+    return MeshArrays(v, f, np.array(cs, np.float32) if cs else None, normals)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -252,7 +291,7 @@ def read_glb(path, uv_origin="bottom_left"):
     }
 
 
-def _ply_layout(vertices, faces, vertex_colors):
+def _ply_layout(vertices, faces, vertex_colors, normals=None):
     """(header bytes, vertex block as a C-contiguous array whose bytes ARE the block, int faces [Nf,3]) of write_ply's file."""
     v = np.ascontiguousarray(vertices, np.float32)
     f = np.asarray(faces)
@@ -260,14 +299,18 @@ def _ply_layout(vertices, faces, vertex_colors):
         f = f.astype(np.int64)
     head = ["ply", "format binary_little_endian 1.0", "comment sculptmate_amd", "element vertex %d" % len(v),
             "property float x", "property float y", "property float z"]
+    if normals is not None:
+        head += ["property float nx", "property float ny", "property float nz"]
+        v = np.ascontiguousarray(np.concatenate([v, _normals_for(normals, len(v), "write_ply")], 1))   # [Nv,6]: xyz, nx ny nz
     if vertex_colors is not None:
         head += ["property uchar red", "property uchar green", "property uchar blue"]
         c8 = np.round(np.clip(np.asarray(vertex_colors, np.float64), 0, 1) * 255).astype(np.uint8)
-        vblock = np.empty((len(v), 15), np.uint8)          # float32 xyz + uchar rgb, packed
-        vblock[:, :12] = v.view(np.uint8).reshape(len(v), 12)
-        vblock[:, 12:] = c8
+        w = 4 * v.shape[1]
+        vblock = np.empty((len(v), w + 3), np.uint8)       # float32 xyz [+ normal] + uchar rgb, packed
+        vblock[:, :w] = v.view(np.uint8).reshape(len(v), w)
+        vblock[:, w:] = c8
     else:
-        vblock = v                                           # the raw [Nv,3] float32 buffer is the vertex block
+        vblock = v                                           # the raw float32 buffer is the vertex block
     head += ["element face %d" % len(f), "property list uchar int vertex_indices", "end_header"]
     return ("\n".join(head) + "\n").encode(), vblock, f
 
@@ -302,14 +345,15 @@ def _ply_face_records(f):
 PLY_CHUNK_FACES = 1 << 18   # faces converted + written per task (3.4 MB of records)
 
 
-def write_ply(path, vertices, faces, vertex_colors=None, pool=None):
-    """Binary little-endian PLY: float32 xyz, optional uchar rgb, faces as `uchar 3` + int32 triplets.
+def write_ply(path, vertices, faces, vertex_colors=None, pool=None, normals=None):
+    """Binary little-endian PLY: float32 xyz, optional float32 nx ny nz (normals f32 [Nv, 3]), optional uchar rgb, faces as
+    `uchar 3` + int32 triplets.
     The file is laid out up front (header, vertex block, 13-byte face records) and written with positioned writes, the face
     records converted chunk by chunk; with `pool` (a concurrent.futures executor) the chunks are converted and written in
     parallel -- NumPy copies and os.pwrite release the GIL -- and the same bytes land in the file either way."""
     import os
 
-    head, vblock, f = _ply_layout(vertices, faces, vertex_colors)
+    head, vblock, f = _ply_layout(vertices, faces, vertex_colors, normals)
     v_off = len(head)
     f_off = v_off + vblock.nbytes
     fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
@@ -350,7 +394,8 @@ def write_npz(path, vertices, faces, vertex_colors=None):
 
 
 def read_ply(path):
-    """Read back what write_ply wrote -> (vertices f32, faces i64, colours f32 in [0,1] | None)."""
+    """Read back what write_ply wrote -> MeshArrays (vertices f32, faces i64, colours f32 in [0,1] | None), `.normals` f32
+    [Nv, 3] | None."""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -358,13 +403,16 @@ def read_ply(path):
     nv = int([h for h in head if h.startswith("element vertex")][0].split()[-1])
     nf = int([h for h in head if h.startswith("element face")][0].split()[-1])
     coloured = any(h == "property uchar red" for h in head)
-    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if coloured else [])
+    with_normals = any(h == "property float nx" for h in head)
+    fields = ([("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if with_normals else [])
+              + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if coloured else []))
     vdt = np.dtype(fields)
     vrec = np.frombuffer(data, vdt, nv, end)
     frec = np.frombuffer(data, np.dtype([("n", "u1"), ("i", "<i4", (3,))]), nf, end + nv * vdt.itemsize)
     v = np.stack([vrec["x"], vrec["y"], vrec["z"]], 1)
     c = np.stack([vrec["red"], vrec["green"], vrec["blue"]], 1).astype(np.float32) / 255.0 if coloured else None
-    return v, frec["i"].astype(np.int64), c
+    n = np.stack([vrec["nx"], vrec["ny"], vrec["nz"]], 1) if with_normals else None
+    return MeshArrays(v, frec["i"].astype(np.int64), c, n)
 
 
 def write_sf3d_glb(path, mesh, name="mesh"):

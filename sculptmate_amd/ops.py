@@ -131,6 +131,33 @@ def render_rays(planes, mlp, rays_o, rays_d, radius=0.87, density_bias=-1.0, n_s
     return rgb.view(*shape, 3), {k: v.view(*shape, *v.shape[1:]) for k, v in out.items() if v is not None}
 
 
+def field_normals(planes, mlp, points, radius=0.87, align_corners=False, want=("normal",)):
+    """Gradient of the raw density with respect to the point, and the outward unit normal -grad / |grad| of the density's
+    iso-surface through it (sculpt_triplane_density_grad: forward mode through the point query's own sample + MLP, one launch).
+    planes: [3,C,H,W] (converted to channel-last here, once) or a ChannelLastPlanes; points: [..., 3].
+    Returns a dict with the keys of `want`: "normal" [..., 3] (exactly 0 where the gradient is 0 or not finite), "grad" [..., 3],
+    "density" [..., 1] (triplane_query's `density` from channel-last planes, bit for bit)."""
+    want = tuple(want)
+    unknown = set(want) - {"normal", "grad", "density"}
+    if unknown:
+        raise SculptError("field_normals: unknown output %s" % sorted(unknown))
+    if not want:
+        raise SculptError("field_normals: want is empty (any of normal, grad, density)")
+    if points.shape[-1] != 3:
+        raise SculptError("field_normals: points %s must be [..., 3]" % (tuple(points.shape),))
+    if not isinstance(planes, ChannelLastPlanes):
+        planes = ChannelLastPlanes(planes)
+    shape = tuple(points.shape[:-1])
+    pts = _req(points.reshape(-1, 3).contiguous(), torch.float32, "points")
+    N = pts.shape[0]
+    out = {k: torch.empty((N, w), dtype=torch.float32, device=pts.device) if k in want else None
+           for k, w in (("grad", 3), ("normal", 3), ("density", 1))}
+    check(lib.sculpt_triplane_density_grad(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(pts), N,
+                                           float(radius), _lib.QUERY_ALIGN_CORNERS if align_corners else 0, _ptr(out["grad"]),
+                                           _ptr(out["normal"]), _ptr(out["density"]), _stream()))
+    return {k: v.view(*shape, v.shape[-1]) for k, v in out.items() if v is not None}
+
+
 def grid_axis_coords(resolution, radius):
     """Per-axis lattice coordinate table, computed on the host exactly as the reference does:
     torch.linspace(0, 1, R) (isosurface.py:28-32) then scale_tensor(., (0,1), (-r, r))

@@ -36,14 +36,16 @@ from .spec import DEFAULT_CFG, IMAGE_MEAN, IMAGE_STD, param_spec  # noqa: E402,F
 class Mesh:
     """What run() returns per image: trimesh-constructible arrays."""
 
-    def __init__(self, vertices, faces, vertex_colors=None, uvs=None, texture=None):
+    def __init__(self, vertices, faces, vertex_colors=None, uvs=None, texture=None, vertex_normals=None):
         """uvs / texture: what TSR.bake_texture adds -- uvs f32 [3*Nf, 2] per face corner (origin bottom-left, the convention of
-        sf3d and meshio.write_glb), texture f32 [res, res, 3] in [0, 1] with row 0 at the top."""
+        sf3d and meshio.write_glb), texture f32 [res, res, 3] in [0, 1] with row 0 at the top.
+        vertex_normals: f32 [Nv, 3] unit normals per shared vertex (extract_meshes(normals=...)), also on a baked mesh."""
         self.vertices = vertices
         self.faces = faces
         self.vertex_colors = vertex_colors
         self.uvs = uvs
         self.texture = texture
+        self.vertex_normals = vertex_normals
 
     def to_trimesh(self):  # pragma: no cover (trimesh is optional)
         import trimesh
@@ -64,7 +66,8 @@ class Mesh:
         """Write .obj / .ply / .glb by extension (sculptmate_amd/meshio.py), the call upstream users make on the
         trimesh object their extract_mesh returns.  A baked mesh (uvs + texture) goes out textured: .glb with TEXCOORD_0 and the
         base-colour texture (glTF has one index per vertex, so positions are un-indexed to 3*Nf vertices there and only there),
-        .obj with `vt` lines, `f v/vt` faces and a .mtl + .png beside the file (positions stay shared)."""
+        .obj with `vt` lines, `f v/vt` faces and a .mtl + .png beside the file (positions stay shared).  vertex_normals, when the
+        mesh has them, go into every format (glTF NORMAL, `vn`, nx ny nz); the un-indexed .glb gets normals[faces] per corner."""
         from .. import meshio
 
         ext = str(path).rsplit(".", 1)[-1].lower()
@@ -74,13 +77,14 @@ class Mesh:
         if self.uvs is not None and self.texture is not None and ext in ("glb", "obj"):
             v, f, uv = _host(self.vertices), _host(self.faces), _host(self.uvs)
             picture = np.asarray(self.texture_image())
+            vn = None if self.vertex_normals is None else _host(self.vertex_normals)
             if ext == "glb":
                 meshio.write_glb(str(path), v[f.reshape(-1)], np.arange(f.size, dtype=np.int64).reshape(-1, 3), uvs=uv,
-                                 basecolor_tex=picture)
+                                 basecolor_tex=picture, normals=None if vn is None else vn[f.reshape(-1)])
             else:
-                meshio.write_obj_textured(str(path), v, f, uv, picture)
+                meshio.write_obj_textured(str(path), v, f, uv, picture, normals=vn)
             return
-        writer(str(path), self.vertices, self.faces, vertex_colors=self.vertex_colors)
+        writer(str(path), self.vertices, self.faces, vertex_colors=self.vertex_colors, normals=self.vertex_normals)
 
 
 def _host(x):
@@ -156,7 +160,7 @@ class PendingMesh:
             # later calls return the SAME Mesh: a second set of views would carry no lease, and the buffers could go back to
             # the pool (and be overwritten by a later run_async) while it is still alive
             self._leases, self._host = (), None
-            self._mesh = Mesh(*arrays)
+            self._mesh = Mesh(arrays[0], arrays[1], arrays[2], vertex_normals=arrays[3])
         return self._mesh
 
 
@@ -222,6 +226,14 @@ class TriplaneNeRFRenderer:
             triplane = ops.ChannelLastPlanes(triplane)
         return ops.triplane_query(triplane, decoder, positions, radius=self.cfg.radius,
                                   density_bias=self.cfg.density_bias)
+
+    def query_normals(self, decoder, positions, triplane):
+        """Outward unit normals of the density field at `positions` [..., 3]: -grad / |grad| of the raw density that
+        query_triplane returns (ops.field_normals); exactly 0 where the gradient is 0.  triplane: [3, C, H, W] or an
+        ops.ChannelLastPlanes."""
+        if not isinstance(triplane, ops.ChannelLastPlanes):
+            triplane = triplane.contiguous()
+        return ops.field_normals(triplane, decoder, positions, radius=self.cfg.radius)["normal"]
 
     def _forward(self, decoder, triplane, rays_o, rays_d):
         if self.randomized:
@@ -870,6 +882,19 @@ class TSR(KernelEngine):
                     images.append([Image.fromarray((host[i] * 255.0).astype(np.uint8)) for i in range(n_views)])
         return images
 
+    def field_normals(self, points, scene_code):
+        """Outward unit normals of the density field of `scene_code` ([3, C, H, W] or an ops.ChannelLastPlanes) at `points`
+        [..., 3] in world units: -grad / |grad| of the raw density, one launch (ops.field_normals) -> f32 [..., 3] on the
+        device, exactly 0 where the gradient is 0 (a point outside the scene's box on every axis)."""
+        if self.decoder is None:
+            raise _lib.SculptError("TSR.field_normals: the model has no weights on a device yet (load_state_dict + to(device))")
+        if not isinstance(scene_code, ops.ChannelLastPlanes):
+            if scene_code.ndim == 5 and scene_code.shape[0] == 1:
+                scene_code = scene_code[0]
+            scene_code = scene_code.to(self.device)
+        with torch.no_grad():
+            return self.renderer.query_normals(self.decoder, _f32(points, self.device), scene_code)
+
     # ------------------------------------------------------------------ mesh extraction
     def set_marching_cubes_resolution(self, resolution: int):
         if self.isosurface_helper is not None and self.isosurface_helper.resolution == resolution:
@@ -912,12 +937,17 @@ class TSR(KernelEngine):
         return Mesh(mesh.vertices, mesh.faces, None, uvs=uv, texture=color)
 
     def extract_meshes(self, scene_codes, enable_texture=False, resolution: int = 256, threshold: float = 25.0,
-                       x_range=None, density_events=None, bake_texture: int = 0) -> List[Mesh]:
+                       x_range=None, density_events=None, bake_texture: int = 0, normals=None) -> List[Mesh]:
         """The arithmetic of system.py:171-200 without the Blender sink: returns device tensors.
         density_events: optional (start, stop) torch events recorded around the dense-grid launch (bench.py's live
         per-launch timing of the dominant kernel, on the stream it is launched on).
         bake_texture: with enable_texture, a resolution > 0 bakes a UV texture of that size (TSR.bake_texture) instead of
-        computing vertex colours; 0 (default): vertex colours as before."""
+        computing vertex colours; 0 (default): vertex colours as before.
+        normals: None (default): Mesh.vertex_normals stays unset.  "field": the outward unit normals of the density field at the
+        vertices (TSR.field_normals: the gradient of the field whose iso-surface the mesh is).  "faces": area-weighted averages of
+        the facet normals (ops.vertex_normals).  Either way f32 [Nv, 3] per shared vertex, also on a baked mesh."""
+        if normals not in (None, "field", "faces"):
+            raise ValueError("normals must be None, 'field' or 'faces', got %r" % (normals,))
         bake = int(bake_texture) if enable_texture else 0
         self.set_marching_cubes_resolution(resolution)
         r = self.renderer.cfg.radius
@@ -934,21 +964,28 @@ class TSR(KernelEngine):
             # density_act - threshold == -(-(density_act - threshold))  (system.py:184, isosurface.py:45)
             if self._filter_applies(planes, R, threshold):
                 v_pos, t_pos_idx = self._extract_filtered(planes, R, mc, dkw, density_events)
-                out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake))
+                out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
                 continue
             vol = ops.density_grid(planes, self.decoder, R, precision=self.decoder_precision, events=density_events, **dkw)
             v_pos, t_pos_idx = mc(vol)   # (both decoder modes have the fp32 range: a NaN here is a NaN of the model)
-            out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake))
+            out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
         return out
 
-    def _textured(self, v_pos, t_pos_idx, planes, enable_texture, bake):
-        """The appearance half of extract_meshes: nothing, vertex colours (system.py:189-193) or a baked texture."""
+    def _textured(self, v_pos, t_pos_idx, planes, enable_texture, bake, normals=None):
+        """The appearance half of extract_meshes: nothing, vertex colours (system.py:189-193) or a baked texture; and the
+        vertex normals when asked for."""
         if enable_texture and bake > 0:
-            return self.bake_texture(Mesh(v_pos, t_pos_idx), planes, bake)
-        color = None
-        if enable_texture:
-            color = self.renderer.query_triplane(self.decoder, v_pos, planes)["color"]
-        return Mesh(v_pos, t_pos_idx, color)
+            mesh = self.bake_texture(Mesh(v_pos, t_pos_idx), planes, bake)
+        else:
+            color = None
+            if enable_texture:
+                color = self.renderer.query_triplane(self.decoder, v_pos, planes)["color"]
+            mesh = Mesh(v_pos, t_pos_idx, color)
+        if normals == "field":
+            mesh.vertex_normals = self.field_normals(v_pos, planes)
+        elif normals == "faces":
+            mesh.vertex_normals = ops.vertex_normals(v_pos, t_pos_idx)
+        return mesh
 
     # -- the two-pass ("filtered") density grid: calibration, guard, fallback (csrc/density_filter.hip)
     FILTER_SAFETY = 8.0        # margin = FILTER_SAFETY x the largest coarse error of the calibration probe
@@ -1053,11 +1090,12 @@ class TSR(KernelEngine):
         return Mesh(v_pos, t_pos_idx, color)
 
     def extract_mesh(self, scene_codes, enable_texture=False, mesh_name="NewMesh", resolution: int = 256,
-                     threshold: float = 25.0, bake_texture: int = 0):
-        """system.py:171-200: same signature (+ bake_texture, see extract_meshes); pushes each mesh into the sink (Blender when
+                     threshold: float = 25.0, bake_texture: int = 0, normals=None):
+        """system.py:171-200: same signature (+ bake_texture and normals, see extract_meshes); pushes each mesh into the sink (Blender when
         `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
-        the textured sink (per-loop UVs + an image-texture material)."""
-        meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture)
+        the textured sink (per-loop UVs + an image-texture material).  The sinks take no normals (Blender shades a mesh with
+        shared vertices smooth by itself); they stay on the returned meshes."""
+        meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture, normals=normals)
         sink = self.mesh_sink or _default_sink()
         for m in meshes:
             if m.texture is not None:
@@ -1072,7 +1110,8 @@ class TSR(KernelEngine):
                      None if m.vertex_colors is None else m.vertex_colors.cpu().numpy(), mesh_name)
         return meshes
 
-    def run_async(self, image, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, tokens=None):
+    def run_async(self, image, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, tokens=None,
+                  normals=None):
         """One host image -> PendingMesh.  The image goes host -> HBM, the forward and the mesh extraction are queued on
         the current stream, and the mesh (the reference's `.cpu().numpy()` at system.py:200) is copied device -> pinned
         host memory on a separate copy stream, so the copy of mesh i runs under the kernels of image i + 1.
@@ -1080,11 +1119,11 @@ class TSR(KernelEngine):
         `image` is not touched again): a caller with several images queues the tokens of image i + 1 before this call (run)."""
         with torch.no_grad():
             codes = self.forward([image], self.device) if tokens is None else self.forward_tokens(tokens)
-            m = self.extract_meshes(codes, enable_texture, mc_resolution, threshold)[0]
+            m = self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals)[0]
         return self._mesh_to_host_async(m)
 
     def _mesh_to_host_async(self, m) -> PendingMesh:
-        """Device mesh -> PendingMesh: vertices / faces / colours copied into pinned host buffers on the copy stream."""
+        """Device mesh -> PendingMesh: vertices / faces / colours / normals copied into pinned host buffers on the copy stream."""
         main = torch.cuda.current_stream(self.device)
         copy = getattr(self, "_copy_stream", None)
         if copy is None:
@@ -1097,7 +1136,7 @@ class TSR(KernelEngine):
         host, leases = [], []
         with torch.cuda.stream(copy):
             copy.wait_event(ready)
-            for t in (m.vertices, m.faces, m.vertex_colors):
+            for t in (m.vertices, m.faces, m.vertex_colors, m.vertex_normals):
                 if t is None:
                     host.append(None)
                     continue
@@ -1110,7 +1149,8 @@ class TSR(KernelEngine):
             done.record(copy)
         return PendingMesh(host, done, tuple(leases))
 
-    def run(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, batch=None) -> List[Mesh]:
+    def run(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, batch=None,
+            normals=None) -> List[Mesh]:
         """Headless entry point: images -> list of Mesh with host (NumPy) arrays; the device -> host copy of mesh i overlaps the
         kernels that follow it.
         batch (images per transformer pass; None = the default): in the bf16 mode a stacked pass of several images gives each
@@ -1118,17 +1158,19 @@ class TSR(KernelEngine):
         ops.single_image_tiles), so several images run RUN_BATCH = 8 per pass by default -- the reference's batched forward
         (system.py:82-115), 3.5-3.9 instead of 5.2 ms of transformer per image -- and the meshes are those of one-at-a-time calls
         (test_run_batches_by_default_and_returns_the_serial_meshes).  The limb modes default to one image per pass with the
-        tokenizer look-ahead (run_pipelined).  batch=1 forces that everywhere."""
+        tokenizer look-ahead (run_pipelined).  batch=1 forces that everywhere.
+        normals: None, "field" or "faces" (extract_meshes): Mesh.vertex_normals as float32 [Nv, 3] on the host."""
         images = _as_image_list(images)
         if batch is None:
             batch = self.RUN_BATCH if (self.precision == "bf16" and len(images) >= 2) else 1
         if batch <= 1 or len(images) < 2:
-            return [p.result() for p in self.run_pipelined(images, mc_resolution, threshold, enable_texture)]
-        return [p.result() for p in self.run_batched(images, batch, mc_resolution, threshold, enable_texture)]
+            return [p.result() for p in self.run_pipelined(images, mc_resolution, threshold, enable_texture, normals=normals)]
+        return [p.result() for p in self.run_batched(images, batch, mc_resolution, threshold, enable_texture, normals=normals)]
 
     RUN_BATCH = 8   # images per transformer pass of TSR.run in the bf16 mode (4: 139.7, 8: 143.5 meshes/s device to device)
 
-    def run_batched(self, images, batch: int = 4, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False):
+    def run_batched(self, images, batch: int = 4, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False,
+                    normals=None):
         """images (host or device) -> list of PendingMesh through batched forward passes of `batch` images each."""
         images = list(images)
         pending = []
@@ -1138,23 +1180,23 @@ class TSR(KernelEngine):
             for i in range(0, len(images), self.max_batch):
                 with torch.no_grad():
                     codes = self.forward(images[i:i + self.max_batch], self.device)
-                    for m in self.extract_meshes(codes, enable_texture, mc_resolution, threshold):
+                    for m in self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals):
                         pending.append(self._mesh_to_host_async(m))
         finally:
             self.max_batch = keep
         return pending
 
-    def run_pipelined(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False):
+    def run_pipelined(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, normals=None):
         """images (host or device) -> list of PendingMesh, with the tokenizer of image i + 1 queued beside the backbone /
         density grid / marching cubes of image i (tokens_async) and the device -> host copy of mesh i under image i + 1."""
         images = list(images)
         if len(images) < 2:
-            return [self.run_async(im, mc_resolution, threshold, enable_texture) for im in images]
+            return [self.run_async(im, mc_resolution, threshold, enable_texture, normals=normals) for im in images]
         pending, nxt = [], self.tokens_async(images[0])
         for i, im in enumerate(images):
             cur = nxt
             nxt = self.tokens_async(images[i + 1]) if i + 1 < len(images) else None
-            pending.append(self.run_async(im, mc_resolution, threshold, enable_texture, tokens=cur))
+            pending.append(self.run_async(im, mc_resolution, threshold, enable_texture, tokens=cur, normals=normals))
         return pending
 
 

@@ -1,0 +1,230 @@
+"""The density-gradient kernel (csrc/field_normal.hip: sculpt_triplane_density_grad) and the layers above it on the GPU, against
+the reference's own autograd gradient in fp64 (tests/golden/field_normal.npz, made by make_field_normal_goldens.py) and against
+the point query it differentiates.
+
+Decoder and planes are regenerated from seeds (synth.decoder_state(seed=1), synth.triplane(seed=2, scale=4.0)).  The golden's
+2043 points: (a) 1024 inside, (b) 512 in the zero-padding band, (c) 256 with one plane pair cut off, (d) 128 outside every plane,
+(e) 123 of an 8-aligned run of near-equal points; none within 1e-4 of a cell edge, where the derivative jumps.
+
+Measured on an MI355X (E_ref = 3.685e-2, the reference's own fp32 error against its fp64 gradient):
+  gradient  max_i |grad_dev_i - grad64_i| = 3.614e-2 = 0.98 E_ref (bound 4 E_ref)
+  normals   largest |n_dev - n64| = 4.03e-4, at most 0.097 of its bound; largest | |n_dev| - 1 | = 1.01e-7 (bound 1e-6)"""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN
+from sculptmate_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+RADIUS = 0.87
+
+
+def _bits(a):
+    return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a).view(np.uint32)
+
+
+@pytest.fixture(scope="module")
+def scene(cuda):
+    """Golden, decoder, planes in both layouts and ONE device result with every output on all points (shared, never modified)."""
+    from sculptmate_amd import ops
+
+    g = np.load(os.path.join(GOLDEN, "field_normal.npz"))
+    Ws, bs = synth.decoder_lists(synth.decoder_state(seed=1))
+    mlp = ops.PackedMLP(Ws, bs, cuda)
+    raw = torch.from_numpy(synth.triplane(seed=2, scale=4.0)).to(cuda)
+    planes = ops.ChannelLastPlanes(raw)
+    pts = torch.from_numpy(g["points"]).to(cuda)
+    got = ops.field_normals(planes, mlp, pts, radius=RADIUS, want=("normal", "grad", "density"))
+    return {"g": g, "mlp": mlp, "raw": raw, "planes": planes, "pts": pts, "got": got,
+            "host": {k: v.cpu().numpy() for k, v in got.items()}}
+
+
+def test_gradient_against_the_reference(scene):
+    """max_i |grad_dev_i - grad64_i| <= 4 E_ref, E_ref = the reference's own fp32 autograd error on the same graph; 4 is the
+    project's margin for another fp32 order of the same graph (test_gpu_render.py)."""
+    g, got = scene["g"], scene["host"]
+    assert got["grad"].shape == (2043, 3) and got["grad"].dtype == np.float32
+    e_ref = float(g["E_ref"])
+    err = np.linalg.norm(got["grad"].astype(np.float64) - g["grad64"], axis=1)
+    print("gradient: device vs reference fp64 %.3e, E_ref %.3e, ratio %.2f (point %d, |grad64| %.1f)" % (
+        err.max(), e_ref, err.max() / e_ref, err.argmax(), np.linalg.norm(g["grad64"][err.argmax()])))
+    assert np.isfinite(got["grad"]).all()
+    assert err.max() <= 4 * e_ref, (err.max(), e_ref)
+
+
+def test_normals_against_the_reference(scene):
+    """|n_dev - n64| <= 2 (4 E_ref) / |grad64| + 1e-6 wherever grad64 is not 0 (normalisation is 2 / |g| Lipschitz; 1e-6 for the
+    fp32 roundings of the quotient), unit length to 1e-6, and exactly 0 with an exactly 0 gradient on set (d)."""
+    g, got = scene["g"], scene["host"]
+    e_ref = float(g["E_ref"])
+    g64 = g["grad64"]
+    norm = np.linalg.norm(g64, axis=1)
+    live = norm > 0
+    n64 = -g64[live] / norm[live, None]
+    n_dev = got["normal"].astype(np.float64)
+    err = np.linalg.norm(n_dev[live] - n64, axis=1)
+    bound = 2 * (4 * e_ref) / norm[live] + 1e-6
+    length = np.abs(np.linalg.norm(n_dev[live], axis=1) - 1.0)
+    print("normals: %d live points, largest error %.3e, largest error / bound %.3f, largest | |n| - 1 | %.3e" % (
+        live.sum(), err.max(), (err / bound).max(), length.max()))
+    assert (err <= bound).all(), (err / bound).max()
+    assert length.max() <= 1e-6
+    o = g["set_offsets"]
+    d = slice(int(o[3]), int(o[4]))
+    assert not live[d].any()
+    assert not got["grad"][d].any() and not got["normal"][d].any()
+    assert not got["normal"][~live].any()
+
+
+def test_density_is_the_point_querys_bit_for_bit(scene):
+    from sculptmate_amd import ops
+
+    want = ops.triplane_query(scene["planes"], scene["mlp"], scene["pts"], radius=RADIUS, want=("density",))["density"]
+    assert scene["got"]["density"].shape == (2043, 1)
+    assert np.array_equal(_bits(scene["got"]["density"]), _bits(want))
+    err = np.abs(scene["host"]["density"][:, 0].astype(np.float64) - scene["g"]["density64"]).max()
+    print("density: device vs reference fp64 %.3e, E_ref_density %.3e" % (err, float(scene["g"]["E_ref_density"])))
+
+
+def test_a_points_result_is_its_own(scene):
+    from sculptmate_amd import ops
+
+    got, pts, planes, mlp = scene["got"], scene["pts"], scene["planes"], scene["mlp"]
+    perm = torch.from_numpy(np.random.default_rng(5).permutation(len(pts))).to(pts.device)
+    shuffled = ops.field_normals(planes, mlp, pts[perm].contiguous(), radius=RADIUS, want=("normal", "grad", "density"))
+    for k in ("normal", "grad", "density"):
+        assert np.array_equal(_bits(shuffled[k]), _bits(got[k][perm])), k
+    for n in (1, 7, 8, 9, 33):
+        head = ops.field_normals(planes, mlp, pts[:n].contiguous(), radius=RADIUS, want=("normal", "grad"))
+        for k in ("normal", "grad"):
+            assert head[k].shape == (n, 3) and np.array_equal(_bits(head[k]), _bits(got[k][:n])), (k, n)
+    # leading shape and the reference layout of the planes
+    first = ops.field_normals(scene["raw"], mlp, pts[:2040].view(8, 255, 3), radius=RADIUS, want=("normal", "grad", "density"))
+    assert first["normal"].shape == (8, 255, 3) and first["density"].shape == (8, 255, 1)
+    for k in ("normal", "grad", "density"):
+        assert np.array_equal(_bits(first[k]).reshape(2040, -1), _bits(got[k][:2040])), k
+    # a single output
+    only = ops.field_normals(planes, mlp, pts)
+    assert sorted(only) == ["normal"] and np.array_equal(_bits(only["normal"]), _bits(got["normal"]))
+
+
+def test_refusals(scene, cuda):
+    from sculptmate_amd import _lib, ops
+
+    planes, mlp, pts = scene["planes"], scene["mlp"], scene["pts"]
+    with pytest.raises(_lib.SculptError):
+        ops.field_normals(planes, mlp, pts.cpu())
+    with pytest.raises(_lib.SculptError):
+        ops.field_normals(torch.zeros((3, 32, 8, 8), device=cuda), mlp, pts[:8].contiguous())
+    with pytest.raises(_lib.SculptError):
+        ops.field_normals(planes, mlp, pts, want=("normal", "curvature"))
+    out = torch.zeros((8, 3), device=cuda)
+    with pytest.raises(_lib.SculptError):   # the C entry point itself: a negative count, no output at all
+        _lib.check(_lib.lib.sculpt_triplane_density_grad(planes.data.data_ptr(), 40, 64, 64, mlp.blob.data_ptr(), mlp.n_hidden,
+                                                         pts.data_ptr(), -1, RADIUS, 0, None, out.data_ptr(), None, None))
+    with pytest.raises(_lib.SculptError):
+        _lib.check(_lib.lib.sculpt_triplane_density_grad(planes.data.data_ptr(), 40, 64, 64, mlp.blob.data_ptr(), mlp.n_hidden,
+                                                         pts.data_ptr(), 8, RADIUS, 0, None, None, None, None))
+    empty = ops.field_normals(planes, mlp, pts[:0], want=("normal", "grad", "density"))
+    assert empty["normal"].shape == (0, 3) and empty["grad"].shape == (0, 3) and empty["density"].shape == (0, 1)
+    torch.cuda.synchronize()
+
+
+@pytest.fixture(scope="module")
+def model(cuda):
+    """A small synthetic TSR, one scene code and a density threshold its random weights reach (the grid's median)."""
+    from sculptmate_amd import ops
+    from sculptmate_amd.tsr import TSR
+    from sculptmate_amd.tsr.spec import SMALL_CFG
+
+    m = TSR(SMALL_CFG, pos_embed_mode="size")
+    m.load_state_dict(synth.tsr_state(31, SMALL_CFG))
+    m.to(cuda)
+    img = synth.composite_rgb(synth.image_rgba(seed=32, size=SMALL_CFG["cond_image_size"]))
+    codes = m([img], device=cuda)
+    threshold = float(ops.density_grid(codes[0].contiguous(), m.decoder, 32).median())
+    plain = m.extract_meshes(codes, resolution=32, threshold=threshold)[0]
+    return dict(m=m, img=img, codes=codes, threshold=threshold, plain=plain)
+
+
+def test_model_surface(model):
+    from sculptmate_amd import ops
+    from sculptmate_amd.tsr import TSR
+    from sculptmate_amd.tsr.spec import SMALL_CFG
+
+    m, plain, kw = model["m"], model["plain"], dict(resolution=32, threshold=model["threshold"])
+    assert plain.vertex_normals is None and plain.vertices.shape[0] > 0
+    field = m.extract_meshes(model["codes"], normals="field", **kw)[0]
+    assert np.array_equal(_bits(field.vertices), _bits(plain.vertices)) and torch.equal(field.faces, plain.faces)
+    want = m.field_normals(field.vertices, model["codes"][0])
+    assert want.shape == field.vertices.shape and want.dtype == torch.float32 and want.is_cuda
+    assert np.array_equal(_bits(field.vertex_normals), _bits(want))
+    length = torch.linalg.norm(want.double(), dim=1)
+    assert bool(((length - 1).abs() <= 1e-6).all())
+    faces = m.extract_meshes(model["codes"], normals="faces", **kw)[0]
+    assert np.array_equal(_bits(faces.vertex_normals), _bits(ops.vertex_normals(plain.vertices, plain.faces)))
+    agree = float(((field.vertex_normals * faces.vertex_normals).sum(1) > 0).float().mean())
+    print("field normal . facet normal > 0 on %.1f %% of %d vertices" % (100 * agree, len(want)))   # a figure, not a check
+    none = m.extract_meshes(model["codes"], normals=None, **kw)[0]
+    assert none.vertex_normals is None
+    assert np.array_equal(_bits(none.vertices), _bits(plain.vertices)) and torch.equal(none.faces, plain.faces)
+    with pytest.raises(ValueError):
+        m.extract_meshes(model["codes"], normals="x", **kw)
+    # a baked mesh keeps one normal per shared vertex; vertex colours and normals go together
+    baked = m.extract_meshes(model["codes"], enable_texture=True, bake_texture=64, normals="field", **kw)[0]
+    assert baked.texture is not None and np.array_equal(_bits(baked.vertex_normals), _bits(want))
+    coloured = m.extract_meshes(model["codes"], enable_texture=True, normals="field", **kw)[0]
+    assert coloured.vertex_colors is not None and np.array_equal(_bits(coloured.vertex_normals), _bits(want))
+    with pytest.raises(ops.SculptError, match="no weights on a device"):
+        TSR(SMALL_CFG, pos_embed_mode="size").field_normals(plain.vertices, model["codes"][0])
+
+
+def test_run_returns_host_normals(model):
+    m = model["m"]
+    meshes = m.run([model["img"], model["img"]], mc_resolution=32, threshold=model["threshold"], normals="field")
+    assert len(meshes) == 2
+    for mesh in meshes:
+        n = mesh.vertex_normals
+        assert isinstance(n, np.ndarray) and n.dtype == np.float32 and n.shape == mesh.vertices.shape and n.shape[0] > 0
+        assert np.abs(np.linalg.norm(n.astype(np.float64), axis=1) - 1).max() <= 1e-6
+    assert np.array_equal(meshes[0].vertex_normals.view(np.uint32), meshes[1].vertex_normals.view(np.uint32))
+    single = m.run([model["img"]], mc_resolution=32, threshold=model["threshold"], normals="faces")[0]
+    assert single.vertex_normals.shape == single.vertices.shape and single.vertex_normals.dtype == np.float32
+    assert m.run([model["img"]], mc_resolution=32, threshold=model["threshold"])[0].vertex_normals is None
+
+
+def test_generator_leaves_normals_on_last_meshes(cuda, tmp_path):
+    import types
+
+    from test_host_logic import _write_checkpoint
+
+    from sculptmate_amd import ops
+    from sculptmate_amd.generate import TripoGenerator
+    from sculptmate_amd.tsr.spec import SMALL_CFG
+
+    _write_checkpoint(str(tmp_path), SMALL_CFG, seed=61)
+    g = TripoGenerator(cuda)
+    assert g.vertex_normals is None
+    g.checkpoint_dir = str(tmp_path)
+    g.mc_resolution = 32
+    assert g.initiate_model() == 0
+    sunk = []
+    g.model.mesh_sink = lambda v, f, c, name: sunk.append((v, f, c, name))
+    orig = g.model.extract_mesh
+
+    def reachable(self, codes, **kw):   # random weights never reach the default threshold: take the grid's median
+        return orig(codes, **dict(kw, threshold=float(ops.density_grid(codes[0].contiguous(), self.decoder, kw["resolution"]).median())))
+
+    g.model.extract_mesh = types.MethodType(reachable, g.model)
+    img = (synth.composite_rgb(synth.image_rgba(seed=62, size=SMALL_CFG["cond_image_size"])) * 255).astype(np.uint8)
+    assert g.generate_mesh(img, "plain") == 0
+    assert g.last_meshes[0].vertex_normals is None
+    g.vertex_normals = "field"
+    assert g.generate_mesh(img, "smooth") == 0
+    mesh = g.last_meshes[0]
+    assert mesh.vertex_normals is not None and mesh.vertex_normals.shape == mesh.vertices.shape and mesh.vertices.shape[0] > 0
+    assert len(sunk) == 2 and sunk[1][3] == "smooth"
