@@ -350,6 +350,55 @@ int sculpt_mc_emit_capped(const float *vol, int n0, int n1, int n2, double level
                           int64_t cap_faces, int *top_plane_map /* or NULL */, sculpt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Connected components of an indexed triangle mesh, and the mesh without its small ones (csrc/mesh_components.hip).
+ *   faces   int32 or int64 (faces_i64 != 0) [n_faces][3], on the device, over n_vertices SHARED vertices (what sculpt_mc_emit
+ *           writes): two faces are connected when they name a common vertex.  0 <= n_vertices, n_faces < 2^31.
+ *   labels  labels[v] = the smallest vertex index of v's component: exact, and the same whatever the order of the faces or of
+ *           the threads.  A vertex no face names is a component of its own with 0 faces.  A face with repeated indices connects
+ *           less and still counts.  A face with an index outside [0, n_vertices) is never read through: the result is refused
+ *           (SCULPT_ERR_MESH_COMPONENTS).  Every loop of the kernels has a step budget that cannot run out while the
+ *           union-find's invariant (parent[x] <= x) holds; should one run out, the same error comes back instead of a spin.
+ *   rule    which components sculpt_mesh_components_compact keeps:
+ *           SCULPT_CC_KEEP_NONE       none asked for (labels and counts only: sculpt_mesh_components_report)
+ *           SCULPT_CC_KEEP_LARGEST    the one with the most faces; of several with as many, the one with the smallest root
+ *           SCULPT_CC_KEEP_MIN_FACES  those with at least min_faces (>= 1) faces
+ *           SCULPT_CC_KEEP_FRACTION   those with (double)faces >= fraction * (double)largest face count, 0 < fraction < 1
+ *           A component without faces is never kept.
+ * Two phases, like marching cubes, with the counts' way to the host of sculpt_mc_count_launch / _read (a pinned slot and an event
+ * per launch, keyed by the workspace pointer, at most 8 pending per device, not graph-capturable; the contract stated there):
+ *   sculpt_mesh_components_launch   label + count + select + the scans' totals, queued on `stream`.  Refuses n_faces == 0 or
+ *                                   n_vertices == 0: there is nothing to launch, the caller returns the empty result.
+ *   sculpt_mesh_components_read     waits for the launch's event; counts_host[5] = {components, faces of the largest, root of
+ *                                   the largest, kept vertices, kept faces} (the last two are 0 under SCULPT_CC_KEEP_NONE).
+ *   sculpt_mesh_components_compact  the kept vertex rows and faces in their input order (the input with rows deleted), the faces
+ *                                   re-indexed and in the input's integer type; vertex_index[i] / face_index[j] = the input row
+ *                                   of output row i / j.  cap_vertices / cap_faces: rows of the output buffers (the counts read
+ *                                   above); a row beyond them is not written.  vertices: f32 [n_vertices][3].
+ *   sculpt_mesh_components_report   labels (or NULL) [n_vertices]; every root ascending [n_components], with the faces and the
+ *                                   vertices of its component.
+ *   sculpt_mesh_component_labels    label only, into the caller's array, and wait for the error word (synchronous).
+ * The workspace (sculpt_mesh_components_workspace_bytes; 0 for sizes out of range) is 16 bytes per vertex + 4 bytes per 1024
+ * vertices (twice) and per 1024 faces + under 2 KB of header and alignment; launch, compact and report of one mesh take the same one, untouched in between.
+ * ------------------------------------------------------------------------------------------ */
+#define SCULPT_CC_KEEP_NONE 0
+#define SCULPT_CC_KEEP_LARGEST 1
+#define SCULPT_CC_KEEP_MIN_FACES 2
+#define SCULPT_CC_KEEP_FRACTION 3
+#define SCULPT_ERR_MESH_COMPONENTS 16 /* an index out of range, a step budget spent, or a read without a pending launch */
+size_t sculpt_mesh_components_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int sculpt_mesh_components_launch(const void *faces, int faces_i64, int64_t n_faces, int64_t n_vertices, int rule, int64_t min_faces,
+                                  double fraction, void *workspace, sculpt_stream_t stream);
+int sculpt_mesh_components_read(const void *workspace, int64_t *counts_host /* [5] */);
+int sculpt_mesh_components_compact(const float *vertices, const void *faces, int faces_i64, int64_t n_faces, int64_t n_vertices,
+                                   void *workspace, float *out_vertices, int64_t cap_vertices, void *out_faces, int64_t cap_faces,
+                                   int64_t *vertex_index, int64_t *face_index, sculpt_stream_t stream);
+int sculpt_mesh_components_report(const void *workspace, int64_t n_vertices, int64_t n_faces, int64_t n_components,
+                                  int32_t *labels /* or NULL */, int32_t *roots, int32_t *face_counts, int32_t *vertex_counts,
+                                  sculpt_stream_t stream);
+int sculpt_mesh_component_labels(const void *faces, int faces_i64, int64_t n_faces, int64_t n_vertices, int32_t *labels,
+                                 void *workspace, sculpt_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Transformer primitives (bf16 storage, fp32 accumulate).  bf16 values are uint16_t bit patterns.
  * ------------------------------------------------------------------------------------------ */
 #define SCULPT_EPI_NONE 0

@@ -63,7 +63,7 @@ class MeshWriter:
 
 
 def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture=False, out_dir=None, names=None, fmt="ply",
-                keep=True, writers=4, batch=1):
+                keep=True, writers=4, batch=1, keep_components=None):
     """images: the WHOLE batch, identical on every rank (a list of host arrays / PIL images, or callables returning one, so
     that a rank only loads the files it owns).  Returns (local, summary):
       local   {index: Mesh} of the images this rank owns (empty dict with keep=False: meshes are only written);
@@ -73,6 +73,8 @@ def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture
     submit loop (0: synchronously, inside the loop).
     batch > 1: this rank's images go through the transformer `batch` per pass (TSR.run_batched: the reference's batched forward,
     3.9 instead of 5.3 ms per image at 4); the meshes then differ from single-image calls by the bf16 transformer's rounding.
+    keep_components: None, "largest", an int or a float (TSR.extract_meshes): every mesh without its small connected components;
+    handed to the model only when set.
     A rank that fails still takes part in the one exchange, with an error marker in place of its counts: every rank then
     raises, none is left waiting in a collective the failed rank never enters."""
     import torch.distributed as dist
@@ -85,6 +87,7 @@ def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture
     if fmt not in ("ply", "npz", "obj"):
         raise ValueError("format must be 'ply', 'npz' or 'obj'")
     local, counts = {}, []
+    ckw = {} if keep_components is None else {"keep_components": keep_components}
     writer = MeshWriter(writers) if (out_dir is not None and writers) else None
     failure = None
 
@@ -116,7 +119,7 @@ def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture
             prev_group = None
             for k in range(0, len(mine), batch):
                 idx = mine[k:k + batch]
-                cur_group = (idx, model.run_batched([load(i) for i in idx], batch, mc_resolution, threshold, enable_texture))
+                cur_group = (idx, model.run_batched([load(i) for i in idx], batch, mc_resolution, threshold, enable_texture, **ckw))
                 if prev_group is not None:
                     for i, pnd in zip(*prev_group):
                         finish(i, pnd)
@@ -136,9 +139,9 @@ def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture
                 if k + 1 < len(mine):
                     im_next = load(mine[k + 1])
                     tok_next = model.tokens_async(im_next)
-                cur = (i, model.run_async(im, mc_resolution, threshold, enable_texture, tokens=tok))
+                cur = (i, model.run_async(im, mc_resolution, threshold, enable_texture, tokens=tok, **ckw))
             else:
-                cur = (i, model.run_async(load(i), mc_resolution, threshold, enable_texture))
+                cur = (i, model.run_async(load(i), mc_resolution, threshold, enable_texture, **ckw))
             if prev is not None:
                 finish(*prev)
             prev = cur

@@ -31,10 +31,10 @@
 
 #include <stdlib.h>
 
-#include <mutex>
 
 #include "common.h"
 #include "mc_luts.h"
+#include "readback_ring.h"
 
 // The CPU implementation rounds every double operation separately (x86-64, no FMA contraction);
 // keep the device arithmetic identical.
@@ -1318,97 +1318,12 @@ static WsLayout ws_layout(const Grid &g, long rec_capacity) {
 // ---------------------------------------------------------------------------------------------
 // The counts' way to the host.  mc_count_launch queues, right behind mc_scan2_kernel, a copy of the header into a pinned host
 // slot and records an event; sculpt_mc_count_read waits for THAT EVENT, not for the stream: work queued behind the count phase
-// (the speculative emit) goes on while the host reads the counts, allocates and queues what comes next.
-// A small ring of slots per device, created on first use and reused; a slot belongs to the workspace pointer it was launched
-// with until its read; the library has no teardown, so the slots (64 pinned bytes and an event each) live as long as the
-// process.  One mutex guards every ring: it is held while a slot is chosen and its copy + event are queued, and
-// while a read looks its slot up and copies the 64 bytes out -- never across the wait for the event.
+// (the speculative emit) goes on while the host reads the counts, allocates and queues what comes next.  The ring of slots is
+// readback_ring.h's (shared with mesh_components.hip, which has a ring of its own).
 // ---------------------------------------------------------------------------------------------
-static constexpr int MC_RING = 8, MC_RING_DEVICES = 64;
-struct CountSlot {
-    const void *ws;              // the workspace of the pending count (key; meaningful while `pending`)
-    McHeader *host;              // pinned, 64 bytes; null: the slot has not been created yet
-    hipEvent_t ev;               // recorded behind the copy into `host`
-    bool pending;                // launched and not read yet
-    unsigned long long seq;      // launch number: the oldest pending slot gives way when the ring is full
-};
-static std::mutex g_ring_mu;
-static CountSlot g_ring[MC_RING_DEVICES][MC_RING];
-static unsigned long long g_ring_seq = 0;
-
-static int ring_device(int *dev) {
-    SC_HIP(hipGetDevice(dev));
-    SC_REQUIRE(*dev >= 0 && *dev < MC_RING_DEVICES, "mc_count: device %d is beyond the %d the count slots cover", *dev, MC_RING_DEVICES);
-    return 0;
-}
-
-// queue the header's copy and the event for the count phase just launched on `st` into `workspace`
-static int ring_launch(const void *workspace, const McHeader *hdr_dev, hipStream_t st) {
-    int dev = 0;
-    if (int rc = ring_device(&dev)) return rc;
-    std::lock_guard<std::mutex> lock(g_ring_mu);
-    CountSlot *ring = g_ring[dev], *slot = nullptr;
-    for (int i = 0; i < MC_RING && !slot; ++i)   // a second launch on the same workspace replaces the pending one
-        if (ring[i].host && ring[i].pending && ring[i].ws == workspace) slot = &ring[i];
-    for (int i = 0; i < MC_RING && !slot; ++i)
-        if (ring[i].host && !ring[i].pending) slot = &ring[i];
-    for (int i = 0; i < MC_RING && !slot; ++i)
-        if (!ring[i].host) slot = &ring[i];
-    if (!slot) {   // every slot pending: the oldest launch loses its slot (its read reports that no count is pending)
-        slot = &ring[0];
-        for (int i = 1; i < MC_RING; ++i)
-            if (ring[i].seq < slot->seq) slot = &ring[i];
-    }
-    if (!slot->host) {   // first use of this slot (the current device is `dev`: the event belongs to it)
-        void *p = nullptr;
-        SC_HIP(hipHostMalloc(&p, sizeof(McHeader), hipHostMallocDefault));
-        hipEvent_t ev;
-        if (hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) {
-            (void)hipHostFree(p);
-            set_error("hipEventCreateWithFlags failed: %s", hipGetErrorString(e));
-            return 1;
-        }
-        slot->host = reinterpret_cast<McHeader *>(p);
-        slot->ev = ev;
-    }
-    slot->pending = false;   // (stays so when one of the two calls below fails)
-    SC_HIP(hipMemcpyAsync(slot->host, hdr_dev, sizeof(McHeader), hipMemcpyDeviceToHost, st));
-    SC_HIP(hipEventRecord(slot->ev, st));
-    slot->ws = workspace;
-    slot->seq = ++g_ring_seq;
-    slot->pending = true;
-    return 0;
-}
-
-// wait for the pending count of `workspace` and take its header; the slot is free afterwards
-static int ring_read(const void *workspace, McHeader *out) {
-    int dev = 0;
-    if (int rc = ring_device(&dev)) return rc;
-    CountSlot *ring = g_ring[dev], *slot = nullptr;
-    hipEvent_t ev;
-    unsigned long long seq;
-    {
-        std::lock_guard<std::mutex> lock(g_ring_mu);
-        for (int i = 0; i < MC_RING && !slot; ++i)
-            if (ring[i].host && ring[i].pending && ring[i].ws == workspace) slot = &ring[i];
-        if (!slot) {
-            set_error("mc_count_read: no count launch is pending for workspace %p on device %d (read already, never launched, or "
-                      "more than %d counts pending)", workspace, dev, MC_RING);
-            return SCULPT_ERR_MC_NO_COUNT;
-        }
-        ev = slot->ev;
-        seq = slot->seq;
-    }
-    SC_HIP(hipEventSynchronize(ev));
-    std::lock_guard<std::mutex> lock(g_ring_mu);
-    if (!slot->pending || slot->seq != seq) {   // another thread launched or read on this workspace meanwhile
-        set_error("mc_count_read: the pending count of workspace %p was replaced while it was being read", workspace);
-        return SCULPT_ERR_MC_NO_COUNT;
-    }
-    *out = *slot->host;
-    slot->pending = false;
-    return 0;
-}
+static ReadbackRing<McHeader> g_ring{"mc_count", SCULPT_ERR_MC_NO_COUNT};
+static int ring_launch(const void *workspace, const McHeader *hdr_dev, hipStream_t st) { return g_ring.launch(workspace, hdr_dev, st); }
+static int ring_read(const void *workspace, McHeader *out) { return g_ring.read(workspace, out); }
 
 }  // namespace sculpt
 

@@ -28,7 +28,10 @@ class TripoGenerator(GeneratorFacade):
     colour per vertex.
     `vertex_normals` (default None): "field" leaves smooth unit normals on the meshes in `last_meshes` (Mesh.vertex_normals, the
     gradient of the density field at each vertex: TSR.field_normals), "faces" the averaged facet normals; Mesh.export writes
-    them.  The Blender sinks take none: Blender shades shared vertices smooth by itself."""
+    them.  The Blender sinks take none: Blender shades shared vertices smooth by itself.
+    `keep_components` (default None): "largest", an int >= 1 (minimum faces) or a float in (0, 1) (fraction of the largest
+    component's faces) drops the other connected components of every mesh -- the floaters around the object -- on the device
+    before it is coloured, baked or handed to Blender (TSR.extract_meshes)."""
 
     def __init__(self, device):
         super().__init__(device, checkpoint_dir=ROOT_DIR + "/checkpoints/", chunk_size=8192, mc_resolution=256,
@@ -36,6 +39,7 @@ class TripoGenerator(GeneratorFacade):
         self.last_meshes = None  # headless callers read the result here (inside Blender it goes to the scene)
         self.bake_texture_resolution = 0
         self.vertex_normals = None
+        self.keep_components = None
 
     def _construct_model(self):
         model = TSR.from_pretrained(self.checkpoint_dir, config_name="config.yaml", weight_name="model.ckpt",
@@ -52,7 +56,8 @@ class TripoGenerator(GeneratorFacade):
             self.last_meshes = self.model.extract_mesh(codes, enable_texture=enable_texture, mesh_name=input_name,
                                                        resolution=self.mc_resolution,
                                                        bake_texture=int(self.bake_texture_resolution or 0),
-                                                       normals=self.vertex_normals)
+                                                       normals=self.vertex_normals,
+                                                       keep_components=self.keep_components)
         except Exception as err:
             print(self.run_error_tag, err)
             return STATUS_FAILED

@@ -461,6 +461,108 @@ _MC_SPECULATE = not _lib.form_has("SCULPT_MC_FORM", "nospeculate")   # A/B: the 
 
 
 # ----------------------------------------------------------------------------------------------
+# connected components of a mesh (csrc/mesh_components.hip)
+# ----------------------------------------------------------------------------------------------
+def keep_rule(keep):
+    """`keep` of mesh_keep_components -> (rule, min_faces, fraction) of sculpt_mesh_components_launch: "largest", an int >= 1
+    (at least that many faces) or a float in (0, 1) (at least that fraction of the largest component's faces).  Anything else,
+    bool included, is a ValueError -- raised here, before anything is launched."""
+    import numbers
+
+    if isinstance(keep, str):
+        if keep == "largest":
+            return _lib.CC_KEEP_LARGEST, 0, 0.0
+    elif isinstance(keep, (bool, np.bool_)):
+        pass
+    elif isinstance(keep, numbers.Integral):
+        if int(keep) >= 1:
+            return _lib.CC_KEEP_MIN_FACES, int(keep), 0.0
+    elif isinstance(keep, numbers.Real):
+        if 0.0 < float(keep) < 1.0:
+            return _lib.CC_KEEP_FRACTION, 0, float(keep)
+    raise ValueError("keep must be 'largest', an int >= 1 (minimum faces) or a float in (0, 1) (fraction of the largest "
+                     "component), got %r" % (keep,))
+
+
+def _cc_faces(faces, n_vertices):
+    if not (isinstance(faces, torch.Tensor) and faces.is_cuda):
+        raise SculptError("faces must be a CUDA/HIP tensor (no CPU fallback)")
+    if faces.dtype not in (torch.int32, torch.int64) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise SculptError("faces must be int32 or int64 [Nf, 3], got %s %s" % (faces.dtype, tuple(faces.shape)))
+    if not 0 <= int(n_vertices) < 2 ** 31 - 1 or faces.shape[0] >= 2 ** 31 - 1:
+        raise SculptError("mesh components: %d vertices, %d faces (each below 2^31 - 1)" % (n_vertices, faces.shape[0]))
+    return faces.contiguous()
+
+
+def _cc_launch(f, nv, rule, min_faces, fraction):
+    """Label + count + select + scan totals, and the one wait for the counts -> (workspace, [C, largest, root, Nv', Nf'])."""
+    nf = f.shape[0]
+    ws = _workspace(("cc", f.device), lib.sculpt_mesh_components_workspace_bytes(nv, nf), f.device)
+    check(lib.sculpt_mesh_components_launch(_ptr(f), int(f.dtype == torch.int64), nf, nv, rule, min_faces, fraction, _ptr(ws), _stream()))
+    counts = (ctypes.c_int64 * 5)()
+    check(lib.sculpt_mesh_components_read(_ptr(ws), counts))
+    return ws, [int(c) for c in counts]
+
+
+def mesh_component_labels(faces, n_vertices):
+    """labels i32 [Nv] alone (sculpt_mesh_component_labels): labels[v] = the smallest vertex index of v's component."""
+    f, nv = _cc_faces(faces, n_vertices), int(n_vertices)
+    if f.shape[0] == 0 or nv == 0:
+        return torch.arange(nv, dtype=torch.int32, device=f.device)
+    ws = _workspace(("cc", f.device), lib.sculpt_mesh_components_workspace_bytes(nv, f.shape[0]), f.device)
+    labels = torch.empty(nv, dtype=torch.int32, device=f.device)
+    check(lib.sculpt_mesh_component_labels(_ptr(f), int(f.dtype == torch.int64), f.shape[0], nv, _ptr(labels), _ptr(ws), _stream()))
+    return labels
+
+
+def mesh_components(faces, n_vertices):
+    """Connected components of an indexed mesh with shared vertices (what marching_cubes returns): faces int32 / int64 [Nf, 3]
+    over n_vertices vertices -> dict of int32 device tensors
+        labels         [Nv]  the smallest vertex index of the vertex's component (exact; independent of the order of the faces)
+        roots          [C]   every component's label, ascending -- a vertex no face names is a component with 0 faces
+        face_counts    [C]   in the order of roots (a face with repeated indices counts)
+        vertex_counts  [C]
+    Nf == 0: nothing is launched; labels = arange(Nv) and no component is reported (none has a face)."""
+    f, nv = _cc_faces(faces, n_vertices), int(n_vertices)
+    dev = f.device
+    if f.shape[0] == 0 or nv == 0:
+        e = torch.empty(0, dtype=torch.int32, device=dev)
+        return {"labels": torch.arange(nv, dtype=torch.int32, device=dev), "roots": e, "face_counts": e.clone(), "vertex_counts": e.clone()}
+    ws, (C, _, _, _, _) = _cc_launch(f, nv, _lib.CC_KEEP_NONE, 0, 0.0)
+    labels = torch.empty(nv, dtype=torch.int32, device=dev)
+    roots, fc, vc = (torch.empty(C, dtype=torch.int32, device=dev) for _ in range(3))
+    check(lib.sculpt_mesh_components_report(_ptr(ws), nv, f.shape[0], C, _ptr(labels), _ptr(roots), _ptr(fc), _ptr(vc), _stream()))
+    return {"labels": labels, "roots": roots, "face_counts": fc, "vertex_counts": vc}
+
+
+def mesh_keep_components(vertices, faces, keep):
+    """The mesh without its small connected components ("floaters"), on the device.
+    vertices f32 [Nv, 3], faces int32 / int64 [Nf, 3]; keep: "largest" (most faces; a tie goes to the smaller root), an int >= 1
+    (components of at least that many faces) or a float x in (0, 1) ((double)faces >= x * (double)faces of the largest).
+    -> (vertices' [Nv', 3], faces' [Nf', 3] re-indexed, in faces' dtype, vertex_index i64 [Nv'], face_index i64 [Nf']): the input
+    with rows deleted, order preserved; the index lists name the input row of every output row.  Vertices no face names are
+    dropped.  One wait for five integers between the two phases (sculpt_mesh_components_read), like marching_cubes."""
+    rule, min_faces, fraction = keep_rule(keep)
+    v = _req(vertices.contiguous() if isinstance(vertices, torch.Tensor) else vertices, torch.float32, "vertices")
+    if v.dim() != 2 or v.shape[1] != 3:
+        raise SculptError("vertices must be [Nv, 3], got %s" % (tuple(v.shape),))
+    f, nv = _cc_faces(faces, v.shape[0]), v.shape[0]
+    dev = v.device
+    if f.shape[0] == 0 or nv == 0:
+        return (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=f.dtype, device=dev),
+                torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev))
+    ws, (_, _, _, knv, knf) = _cc_launch(f, nv, rule, min_faces, fraction)
+    out_v = torch.empty((knv, 3), dtype=torch.float32, device=dev)
+    out_f = torch.empty((knf, 3), dtype=f.dtype, device=dev)
+    vi = torch.empty(knv, dtype=torch.int64, device=dev)
+    fi = torch.empty(knf, dtype=torch.int64, device=dev)
+    check(lib.sculpt_mesh_components_compact(_ptr(v), _ptr(f), int(f.dtype == torch.int64), f.shape[0], nv, _ptr(ws),
+                                             _ptr(out_v) if knv else None, knv, _ptr(out_f) if knf else None, knf,
+                                             _ptr(vi) if knv else None, _ptr(fi) if knf else None, _stream()))
+    return out_v, out_f, vi, fi
+
+
+# ----------------------------------------------------------------------------------------------
 # transformer primitives (bf16 storage as torch.bfloat16 tensors; fp32 accumulate)
 # ----------------------------------------------------------------------------------------------
 BF16 = torch.bfloat16

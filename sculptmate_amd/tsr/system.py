@@ -47,6 +47,25 @@ class Mesh:
         self.texture = texture
         self.vertex_normals = vertex_normals
 
+    def keep_components(self, keep) -> "Mesh":
+        """The mesh without its small connected components (the "floaters" a thresholded density field leaves around the
+        object): keep = "largest", an int >= 1 (components of at least that many faces) or a float in (0, 1) (at least that
+        fraction of the largest component's faces) -- ops.mesh_keep_components on this mesh's device tensors (a mesh of host
+        arrays, as TSR.run returns them, is refused there like any CPU tensor).  Rows keep their order; vertex_colors and
+        vertex_normals follow their vertices (vertex_index), the per-corner uvs of a baked mesh their faces (face_index, three
+        rows per face); the texture is untouched (the dropped charts stay in it, unused)."""
+        v, f, vi, fi = ops.mesh_keep_components(self.vertices, self.faces, keep)
+
+        def rows(x, index):
+            return None if x is None else x[index]
+
+        corner = None
+        if self.uvs is not None:
+            three = torch.arange(3, device=fi.device) if isinstance(fi, torch.Tensor) else np.arange(3)
+            corner = (fi[:, None] * 3 + three).reshape(-1)
+        return Mesh(v, f, rows(self.vertex_colors, vi), uvs=rows(self.uvs, corner), texture=self.texture,
+                    vertex_normals=rows(self.vertex_normals, vi))
+
     def to_trimesh(self):  # pragma: no cover (trimesh is optional)
         import trimesh
 
@@ -937,7 +956,8 @@ class TSR(KernelEngine):
         return Mesh(mesh.vertices, mesh.faces, None, uvs=uv, texture=color)
 
     def extract_meshes(self, scene_codes, enable_texture=False, resolution: int = 256, threshold: float = 25.0,
-                       x_range=None, density_events=None, bake_texture: int = 0, normals=None) -> List[Mesh]:
+                       x_range=None, density_events=None, bake_texture: int = 0, normals=None,
+                       keep_components=None) -> List[Mesh]:
         """The arithmetic of system.py:171-200 without the Blender sink: returns device tensors.
         density_events: optional (start, stop) torch events recorded around the dense-grid launch (bench.py's live
         per-launch timing of the dominant kernel, on the stream it is launched on).
@@ -945,9 +965,15 @@ class TSR(KernelEngine):
         computing vertex colours; 0 (default): vertex colours as before.
         normals: None (default): Mesh.vertex_normals stays unset.  "field": the outward unit normals of the density field at the
         vertices (TSR.field_normals: the gradient of the field whose iso-surface the mesh is).  "faces": area-weighted averages of
-        the facet normals (ops.vertex_normals).  Either way f32 [Nv, 3] per shared vertex, also on a baked mesh."""
+        the facet normals (ops.vertex_normals).  Either way f32 [Nv, 3] per shared vertex, also on a baked mesh.
+        keep_components: None (default): the mesh is what marching cubes returns, and nothing more is launched.  "largest", an
+        int >= 1 (minimum faces) or a float in (0, 1) (fraction of the largest component's faces): the other connected
+        components -- the floaters around the object -- are dropped on the device right after marching cubes
+        (ops.mesh_keep_components), so the colours, the baked atlas and the normals see only what is kept."""
         if normals not in (None, "field", "faces"):
             raise ValueError("normals must be None, 'field' or 'faces', got %r" % (normals,))
+        if keep_components is not None:
+            ops.keep_rule(keep_components)   # a ValueError before anything is launched
         bake = int(bake_texture) if enable_texture else 0
         self.set_marching_cubes_resolution(resolution)
         r = self.renderer.cfg.radius
@@ -964,10 +990,14 @@ class TSR(KernelEngine):
             # density_act - threshold == -(-(density_act - threshold))  (system.py:184, isosurface.py:45)
             if self._filter_applies(planes, R, threshold):
                 v_pos, t_pos_idx = self._extract_filtered(planes, R, mc, dkw, density_events)
+                if keep_components is not None:
+                    v_pos, t_pos_idx = ops.mesh_keep_components(v_pos, t_pos_idx, keep_components)[:2]
                 out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
                 continue
             vol = ops.density_grid(planes, self.decoder, R, precision=self.decoder_precision, events=density_events, **dkw)
             v_pos, t_pos_idx = mc(vol)   # (both decoder modes have the fp32 range: a NaN here is a NaN of the model)
+            if keep_components is not None:
+                v_pos, t_pos_idx = ops.mesh_keep_components(v_pos, t_pos_idx, keep_components)[:2]
             out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
         return out
 
@@ -1066,7 +1096,9 @@ class TSR(KernelEngine):
         """BASELINE config 5: the voxel grid of ONE image split into slabs along the slowest lattice axis over
         the ranks of the default process group (RCCL over xGMI), one padded all-gather of the per-slab
         triangles, identical result on every rank and identical to the single-GPU mesh
-        (sculptmate_amd/slab.py).  Without a process group the slabs run one after the other here."""
+        (sculptmate_amd/slab.py).  Without a process group the slabs run one after the other here.
+        It takes no keep_components: components cross the slabs, so the gathered mesh is filtered afterwards, with
+        Mesh.keep_components."""
         import torch.distributed as dist
 
         from .. import slab
@@ -1090,12 +1122,14 @@ class TSR(KernelEngine):
         return Mesh(v_pos, t_pos_idx, color)
 
     def extract_mesh(self, scene_codes, enable_texture=False, mesh_name="NewMesh", resolution: int = 256,
-                     threshold: float = 25.0, bake_texture: int = 0, normals=None):
-        """system.py:171-200: same signature (+ bake_texture and normals, see extract_meshes); pushes each mesh into the sink (Blender when
+                     threshold: float = 25.0, bake_texture: int = 0, normals=None, keep_components=None):
+        """system.py:171-200: same signature (+ bake_texture, normals and keep_components, see extract_meshes: the sink receives the
+        filtered mesh); pushes each mesh into the sink (Blender when
         `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
         the textured sink (per-loop UVs + an image-texture material).  The sinks take no normals (Blender shades a mesh with
         shared vertices smooth by itself); they stay on the returned meshes."""
-        meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture, normals=normals)
+        meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture, normals=normals,
+                                     keep_components=keep_components)
         sink = self.mesh_sink or _default_sink()
         for m in meshes:
             if m.texture is not None:
@@ -1111,7 +1145,7 @@ class TSR(KernelEngine):
         return meshes
 
     def run_async(self, image, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, tokens=None,
-                  normals=None):
+                  normals=None, keep_components=None):
         """One host image -> PendingMesh.  The image goes host -> HBM, the forward and the mesh extraction are queued on
         the current stream, and the mesh (the reference's `.cpu().numpy()` at system.py:200) is copied device -> pinned
         host memory on a separate copy stream, so the copy of mesh i runs under the kernels of image i + 1.
@@ -1119,7 +1153,8 @@ class TSR(KernelEngine):
         `image` is not touched again): a caller with several images queues the tokens of image i + 1 before this call (run)."""
         with torch.no_grad():
             codes = self.forward([image], self.device) if tokens is None else self.forward_tokens(tokens)
-            m = self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals)[0]
+            m = self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals,
+                                    keep_components=keep_components)[0]
         return self._mesh_to_host_async(m)
 
     def _mesh_to_host_async(self, m) -> PendingMesh:
@@ -1150,7 +1185,7 @@ class TSR(KernelEngine):
         return PendingMesh(host, done, tuple(leases))
 
     def run(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, batch=None,
-            normals=None) -> List[Mesh]:
+            normals=None, keep_components=None) -> List[Mesh]:
         """Headless entry point: images -> list of Mesh with host (NumPy) arrays; the device -> host copy of mesh i overlaps the
         kernels that follow it.
         batch (images per transformer pass; None = the default): in the bf16 mode a stacked pass of several images gives each
@@ -1159,18 +1194,21 @@ class TSR(KernelEngine):
         (system.py:82-115), 3.5-3.9 instead of 5.2 ms of transformer per image -- and the meshes are those of one-at-a-time calls
         (test_run_batches_by_default_and_returns_the_serial_meshes).  The limb modes default to one image per pass with the
         tokenizer look-ahead (run_pipelined).  batch=1 forces that everywhere.
-        normals: None, "field" or "faces" (extract_meshes): Mesh.vertex_normals as float32 [Nv, 3] on the host."""
+        normals: None, "field" or "faces" (extract_meshes): Mesh.vertex_normals as float32 [Nv, 3] on the host.
+        keep_components: None, "largest", an int or a float (extract_meshes): the meshes without their small components."""
         images = _as_image_list(images)
         if batch is None:
             batch = self.RUN_BATCH if (self.precision == "bf16" and len(images) >= 2) else 1
         if batch <= 1 or len(images) < 2:
-            return [p.result() for p in self.run_pipelined(images, mc_resolution, threshold, enable_texture, normals=normals)]
-        return [p.result() for p in self.run_batched(images, batch, mc_resolution, threshold, enable_texture, normals=normals)]
+            return [p.result() for p in self.run_pipelined(images, mc_resolution, threshold, enable_texture, normals=normals,
+                                                              keep_components=keep_components)]
+        return [p.result() for p in self.run_batched(images, batch, mc_resolution, threshold, enable_texture, normals=normals,
+                                                        keep_components=keep_components)]
 
     RUN_BATCH = 8   # images per transformer pass of TSR.run in the bf16 mode (4: 139.7, 8: 143.5 meshes/s device to device)
 
     def run_batched(self, images, batch: int = 4, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False,
-                    normals=None):
+                    normals=None, keep_components=None):
         """images (host or device) -> list of PendingMesh through batched forward passes of `batch` images each."""
         images = list(images)
         pending = []
@@ -1180,23 +1218,27 @@ class TSR(KernelEngine):
             for i in range(0, len(images), self.max_batch):
                 with torch.no_grad():
                     codes = self.forward(images[i:i + self.max_batch], self.device)
-                    for m in self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals):
+                    for m in self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals,
+                                                 keep_components=keep_components):
                         pending.append(self._mesh_to_host_async(m))
         finally:
             self.max_batch = keep
         return pending
 
-    def run_pipelined(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, normals=None):
+    def run_pipelined(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, normals=None,
+                      keep_components=None):
         """images (host or device) -> list of PendingMesh, with the tokenizer of image i + 1 queued beside the backbone /
         density grid / marching cubes of image i (tokens_async) and the device -> host copy of mesh i under image i + 1."""
         images = list(images)
         if len(images) < 2:
-            return [self.run_async(im, mc_resolution, threshold, enable_texture, normals=normals) for im in images]
+            return [self.run_async(im, mc_resolution, threshold, enable_texture, normals=normals, keep_components=keep_components)
+                    for im in images]
         pending, nxt = [], self.tokens_async(images[0])
         for i, im in enumerate(images):
             cur = nxt
             nxt = self.tokens_async(images[i + 1]) if i + 1 < len(images) else None
-            pending.append(self.run_async(im, mc_resolution, threshold, enable_texture, tokens=cur, normals=normals))
+            pending.append(self.run_async(im, mc_resolution, threshold, enable_texture, tokens=cur, normals=normals,
+                                          keep_components=keep_components))
         return pending
 
 
