@@ -874,7 +874,26 @@ void sculpt_mesh_free(sculpt_host_mesh_t *m);
  *   sculpt_rmd_compact_faces, _mark_used, _compact_vertices: keep live faces / referenced vertices in index order
  *   sculpt_rmd_first_halfedge, _subdivide: midpoint subdivision, new vertices in order of first appearance (like the host's)
  *   sculpt_rmd_validate        status bit 0: face index out of range, 1: repeated index in a face, 2: non-finite position
- *   sculpt_rmd_halfedge_lengths per face: the sum of its three side lengths (fp64) */
+ *   sculpt_rmd_halfedge_lengths per face: the sum of its three side lengths (fp64)
+ * Quadric-error simplification (csrc/mesh_simplify.hip; sf3d/remesh_device.py simplify_device, ops.mesh_simplify), on the same
+ * topology and rounds; compiled without floating-point contraction, so every value below is a fixed sequence of IEEE fp64
+ * operations (restated in tests/_qemref.py):
+ *   sculpt_rmd_qem_quadrics    Q[u][10] fp64 = {aa ab ac ad bb bc bd cc cd dd} summed, in the order of u's CSR corners, over the
+ *                              plane (unit normal n, d = -n . p0) of every face around u; a face whose cross product has zero or
+ *                              non-finite length contributes nothing.  Once per call: vertices keep their indices, apply keeps Q.
+ *   sculpt_rmd_qem_cost        per edge with one or two faces, q = Q[u] + Q[v] (u < v; u goes, v stays): no candidate when
+ *                              bnd[u] != bnd[v]; target = the minimiser of the error (the reference's three determinants) unless
+ *                              both ends are flagged, det == 0 or the point rounded to fp32 is not finite -- then whichever of
+ *                              p_u, p_v, the fp32 midpoint has the least error (ties in that order).  target[e][3] fp32 is the
+ *                              point rounded once; cost = the error AT target, clamped at 0 (a non-finite error: no candidate).
+ *                              The link condition as in mode 0;
+ *                              fold-over: for every face of the two fans that survives and has a normal now, the unit edges
+ *                              d1, d2 from the target to its other corners must exist with |d1 . d2| <= 0.999 and
+ *                              normalize(d1 x d2) . (current unit normal) >= 0.2.  cand[e] = (fp32 bits of cost) << 32 | e, or ~0
+ *                              (then target[e] = 0).  Claims nothing.
+ *   sculpt_rmd_qem_claim       candidates with cand[e] <= *cap (a DEVICE scalar: the round's k-th smallest key) claim the footprint
+ *                              of mode 0 on claim[nv]; then sculpt_rmd_collapse_select(mode 0) names the winners
+ *   sculpt_rmd_qem_apply       like sculpt_rmd_collapse_apply, with P[v] = target[e] and Q[v] += Q[u] */
 typedef struct sculpt_rmd_topo {
     const int32_t *F;      /* [nf][3] */
     const int64_t *skeys;  /* [3 nf] half-edge keys, sorted */
@@ -924,6 +943,13 @@ int sculpt_rmd_subdivide(const sculpt_rmd_topo_t *topo, const float *P, const in
                          sculpt_stream_t stream);
 int sculpt_rmd_validate(const float *P, int64_t nv, const int32_t *F, int64_t nf, int32_t *status, sculpt_stream_t stream);
 int sculpt_rmd_halfedge_lengths(const float *P, const int32_t *F, int64_t nf, double *len, sculpt_stream_t stream);
+int sculpt_rmd_qem_quadrics(const sculpt_rmd_topo_t *topo, const float *P, double *Q, sculpt_stream_t stream);
+int sculpt_rmd_qem_cost(const sculpt_rmd_topo_t *topo, const float *P, const double *Q, unsigned long long *cand, float *target,
+                        sculpt_stream_t stream);
+int sculpt_rmd_qem_claim(const sculpt_rmd_topo_t *topo, const unsigned long long *cand, const unsigned long long *cap,
+                         unsigned long long *claim, sculpt_stream_t stream);
+int sculpt_rmd_qem_apply(const sculpt_rmd_topo_t *topo, float *P, int32_t *F, double *Q, const float *target, const int32_t *win,
+                         uint8_t *face_alive, sculpt_stream_t stream);
 
 /* Mesh hand-off, HOST side (no GPU work): the face block of a binary little-endian PLY file -- per face `uchar 3` followed by
  * three int32 -- from the int64 faces TSR.run returns (the reference's `t_pos_idx.cpu().numpy()`, TripoSR/tsr/system.py:200).

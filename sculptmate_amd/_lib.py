@@ -205,6 +205,10 @@ SIGNATURES = {
     "sculpt_rmd_subdivide": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_rmd_validate": (_i, [_vp, _i64, _vp, _i64, _vp, _vp]),
     "sculpt_rmd_halfedge_lengths": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "sculpt_rmd_qem_quadrics": (_i, [_vp, _vp, _vp, _vp]),
+    "sculpt_rmd_qem_cost": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_rmd_qem_claim": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "sculpt_rmd_qem_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rasterize_cpu": (None, [_vp, _sz, _vp, _sz, ctypes.c_longlong, _vp]),
     "interpolate_cpu": (None, [_vp, _sz, _vp, _sz, _vp, ctypes.c_longlong, _vp]),
 }

@@ -31,7 +31,10 @@ class TripoGenerator(GeneratorFacade):
     them.  The Blender sinks take none: Blender shades shared vertices smooth by itself.
     `keep_components` (default None): "largest", an int >= 1 (minimum faces) or a float in (0, 1) (fraction of the largest
     component's faces) drops the other connected components of every mesh -- the floaters around the object -- on the device
-    before it is coloured, baked or handed to Blender (TSR.extract_meshes)."""
+    before it is coloured, baked or handed to Blender (TSR.extract_meshes).
+    `simplify` (default None): an int >= 1 (target faces) or a float in (0, 1) (ratio of the faces) reduces every mesh by
+    quadric-error edge collapses on the device, after keep_components and before the colours, the bake and the normals
+    (TSR.extract_meshes; ops.mesh_simplify)."""
 
     def __init__(self, device):
         super().__init__(device, checkpoint_dir=ROOT_DIR + "/checkpoints/", chunk_size=8192, mc_resolution=256,
@@ -40,6 +43,7 @@ class TripoGenerator(GeneratorFacade):
         self.bake_texture_resolution = 0
         self.vertex_normals = None
         self.keep_components = None
+        self.simplify = None
 
     def _construct_model(self):
         model = TSR.from_pretrained(self.checkpoint_dir, config_name="config.yaml", weight_name="model.ckpt",
@@ -57,7 +61,7 @@ class TripoGenerator(GeneratorFacade):
                                                        resolution=self.mc_resolution,
                                                        bake_texture=int(self.bake_texture_resolution or 0),
                                                        normals=self.vertex_normals,
-                                                       keep_components=self.keep_components)
+                                                       keep_components=self.keep_components, simplify=self.simplify)
         except Exception as err:
             print(self.run_error_tag, err)
             return STATUS_FAILED

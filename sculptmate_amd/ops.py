@@ -4,6 +4,7 @@ torch is plumbing here: it owns HBM allocations and the current HIP stream; ever
 passes raw device pointers + sizes into libsculpt_hip.so.  No function has a CPU path.
 """
 import ctypes
+import math
 import threading
 import os
 
@@ -560,6 +561,66 @@ def mesh_keep_components(vertices, faces, keep):
                                              _ptr(out_v) if knv else None, knv, _ptr(out_f) if knf else None, knf,
                                              _ptr(vi) if knv else None, _ptr(fi) if knf else None, _stream()))
     return out_v, out_f, vi, fi
+
+
+# ----------------------------------------------------------------------------------------------
+# mesh simplification: quadric-error edge collapse (csrc/mesh_simplify.hip, sf3d/remesh_device.py simplify_device)
+# ----------------------------------------------------------------------------------------------
+def simplify_rule(simplify):
+    """`simplify` of mesh_simplify -> ("faces", n) for an int n >= 1 (a target face count) or ("ratio", x) for a float x in
+    (0, 1) (the target is floor(x * Nf)).  Anything else, bool included, is a ValueError -- raised here, before anything is
+    launched."""
+    import numbers
+
+    if isinstance(simplify, (bool, np.bool_, str)):
+        pass
+    elif isinstance(simplify, numbers.Integral):
+        if int(simplify) >= 1:
+            return "faces", int(simplify)
+    elif isinstance(simplify, numbers.Real):
+        if 0.0 < float(simplify) < 1.0:
+            return "ratio", float(simplify)
+    raise ValueError("simplify must be an int >= 1 (target faces) or a float in (0, 1) (ratio of the faces), got %r" % (simplify,))
+
+
+def simplify_target(simplify, n_faces):
+    """The target face count of `simplify` (simplify_rule) on a mesh of n_faces faces."""
+    kind, x = simplify_rule(simplify)
+    return x if kind == "faces" else int(math.floor(x * int(n_faces)))
+
+
+def mesh_simplify(vertices, faces, simplify):
+    """The mesh reduced by quadric-error edge collapses (Garland & Heckbert; the rules of Fast-Quadric-Mesh-Simplification), on
+    the device.  vertices float [Nv, 3], faces int32 / int64 [Nf, 3] (device tensors; CPU tensors are refused); simplify: an
+    int >= 1 (target faces) or a float in (0, 1) (target = floor(ratio * Nf)).
+    -> (vertices' f32 [Nv', 3], faces' [Nf', 3] in faces' dtype, vertex_index i64 [Nv']).
+    Contract:
+      - at most `target` faces, unless a round collapses nothing (a closed component of 4 faces cannot go lower; border and
+        fold-over rules can hold more): the call then returns what it reached;
+      - target >= Nf: nothing is launched, the input tensors come back as they are (their dtype included) and
+        vertex_index = arange(Nv);
+      - surviving faces and vertices keep their relative order; orientation is kept;
+      - vertex_index[i] is the input vertex that output vertex i descends from: the kept end of its collapses (it has moved:
+        its position is the collapses' target point);
+      - deterministic: two calls give the same bits;
+      - per round the host reads back what a decimation round reads (the edge count, the round's result); the counts are in
+        sf3d.remesh_device.last_stats()."""
+    simplify_rule(simplify)
+    from .sf3d import remesh_device as rmd
+
+    for t, name in ((vertices, "vertices"), (faces, "faces")):   # here too: a target already met returns before simplify_device
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise SculptError("mesh_simplify: %s must be a CUDA/HIP tensor (no CPU fallback)" % name)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.dtype.is_floating_point:
+        raise SculptError("vertices must be float [Nv, 3], got %s %s" % (vertices.dtype, tuple(vertices.shape)))
+    if faces.dtype not in (torch.int32, torch.int64) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise SculptError("faces must be int32 or int64 [Nf, 3], got %s %s" % (faces.dtype, tuple(faces.shape)))
+    nf = faces.shape[0]
+    target = simplify_target(simplify, nf)
+    if target >= nf:
+        return vertices, faces, torch.arange(vertices.shape[0], dtype=torch.int64, device=vertices.device)
+    v, f, index = rmd.simplify_device(vertices, faces, target)
+    return v, f.to(faces.dtype), index
 
 
 # ----------------------------------------------------------------------------------------------

@@ -5,6 +5,7 @@ sculpt_rmd_* in include/sculpt_hip.h), with the contract of the host calls in sf
     remesh_botsch_device(v, f, i=10, h=None, project=True) -> (v, f)
     subdivide_device(v, f, iters=1) -> (v, f)
     device_remesher(mesh, mode, vertex_count, remesh_steps=10) -> Mesh      the SF3D.remesher hook, opt-in
+    simplify_device(v, f, target_faces) -> (v, f, vertex_index)             quadric-error collapse (ops.mesh_simplify)
 
 v and f are HIP tensors (v any float dtype, f any integer dtype); results are float32 [n, 3] / int32 [m, 3] HIP tensors.  CPU
 tensors are refused.  The rules are the host's (csrc/remesh_host.h); its sequential order becomes rounds of independent local
@@ -133,24 +134,51 @@ def _compact_faces(ctx, F, alive, nf_new):
     return Fo
 
 
-def _compact_vertices(ctx, P, nv, F):
-    """Referenced vertices in index order; F is renumbered in place."""
+def _compact_vertices(ctx, P, nv, F, with_index=False):
+    """Referenced vertices in index order; F is renumbered in place.  with_index: also the kept vertices' old indices (i64)."""
     used = torch.zeros(max(nv, 1), dtype=torch.int32, device=P.device)
     check(lib.sculpt_rmd_mark_used(_p(F), F.shape[0], _p(used), ctx.stream))
     incl = torch.cumsum(used, 0, dtype=torch.int32)
     n = ctx.read(incl[nv - 1:nv]) if nv else 0
     Po = torch.empty((n, 3), dtype=torch.float32, device=P.device)
     check(lib.sculpt_rmd_compact_vertices(_p(P), _p(used), _p(incl), nv, _p(Po), _p(F), F.shape[0], ctx.stream))
+    if with_index:
+        # old index of every kept vertex without another wait (n is known): row incl - 1 takes it, unused rows share a spare slot
+        dest = torch.where(used[:nv] > 0, incl[:nv] - 1, n).long()
+        index = torch.empty(n + 1, dtype=torch.int64, device=P.device)
+        index.scatter_(0, dest, torch.arange(nv, dtype=torch.int64, device=P.device))
+        return Po, index[:n]
     return Po
 
 
-def _collapse_round(ctx, T, P, mode, low=0.0, high=0.0, target=None):
-    """One round of independent collapses on T's faces; returns (new faces, collapses) -- (T.F, 0) if nothing collapsed."""
+def _qem_propose(ctx, T, P, Q, target, claim, cand):
+    """The quadric-error proposal of one round: every edge's key and target point, then the claims of the candidates under the
+    round's cap -- the k-th smallest key, k = ceil((faces - target) / 2): a collapse removes at most two faces, so the k cheapest
+    could reach the target on their own, and a dearer edge that is merely the cheapest of its neighbourhood waits.  The cap stays
+    on the device.  Returns the targets [ne, 3]."""
+    tgt = torch.empty((max(T.ne, 1), 3), dtype=torch.float32, device=P.device)
+    check(lib.sculpt_rmd_qem_cost(T.ref(), _p(P), _p(Q), _p(cand), _p(tgt), ctx.stream))
+    if T.ne == 0:
+        return tgt
+    k = max(1, min(T.ne, (T.nf - target + 1) // 2))
+    # a key holds non-negative fp32 bits, so it orders the same signed; "no candidate" (~0 = -1) goes last
+    keys = torch.where(cand[:T.ne] == -1, torch.iinfo(torch.int64).max, cand[:T.ne])
+    cap = torch.sort(keys).values[k - 1:k].contiguous()  # (a sort: kthvalue selects a 1-D tensor with a single workgroup)
+    check(lib.sculpt_rmd_qem_claim(T.ref(), _p(cand), _p(cap), _p(claim), ctx.stream))
+    return tgt
+
+
+def _collapse_round(ctx, T, P, mode, low=0.0, high=0.0, target=None, Q=None):
+    """One round of independent collapses on T's faces; returns (new faces, collapses) -- (T.F, 0) if nothing collapsed.
+    Q (quadrics fp64 [nv, 10]; mode 0, with a target): the quadric-error rule instead of the shortest edge (_qem_propose)."""
     dev = P.device
     claim = torch.full((max(T.nv, 1),), -1, dtype=torch.int64, device=dev)  # ~0: unclaimed
     cand = torch.empty(max(T.ne, 1), dtype=torch.int64, device=dev)
     win = torch.empty(max(T.ne, 1), dtype=torch.int32, device=dev)
-    check(lib.sculpt_rmd_collapse_propose(T.ref(), _p(P), mode, float(low), float(high), _p(claim), _p(cand), ctx.stream))
+    if Q is None:
+        check(lib.sculpt_rmd_collapse_propose(T.ref(), _p(P), mode, float(low), float(high), _p(claim), _p(cand), ctx.stream))
+    else:
+        tgt = _qem_propose(ctx, T, P, Q, target, claim, cand)
     check(lib.sculpt_rmd_collapse_select(T.ref(), _p(P), mode, _p(claim), _p(cand), _p(win), ctx.stream))
     win = win[:T.ne]
     removed, n = ctx.read(win.sum(), (win > 0).sum())
@@ -171,7 +199,10 @@ def _collapse_round(ctx, T, P, mode, low=0.0, high=0.0, target=None):
             return T.F, 0
     alive = torch.ones(T.nf, dtype=torch.uint8, device=dev)
     F = T.F
-    check(lib.sculpt_rmd_collapse_apply(T.ref(), _p(P), _p(F), mode, _p(win), _p(alive), ctx.stream))
+    if Q is None:
+        check(lib.sculpt_rmd_collapse_apply(T.ref(), _p(P), _p(F), mode, _p(win), _p(alive), ctx.stream))
+    else:
+        check(lib.sculpt_rmd_qem_apply(T.ref(), _p(P), _p(F), _p(Q), _p(tgt), _p(win), _p(alive), ctx.stream))
     if mode == 0:
         # the kept end (the larger index) inherits the removed end's flag, as in Mesh::collapse; in mode 1 the removed end is
         # never flagged
@@ -333,6 +364,30 @@ def _decimate(ctx, P, F, target):
             break
     V = _compact_vertices(ctx, V, V.shape[0], F)
     return V, F
+
+
+def simplify_device(v, f, target_faces):
+    """Quadric-error edge collapse (csrc/mesh_simplify.hip) down to at most `target_faces` faces, or to where a round collapses
+    nothing: the rounds of _decimate with the quadric rule of _qem_propose.  -> (v f32 [n, 3], f int32 [m, 3], vertex_index i64
+    [n]: the input vertex every output vertex descends from -- the kept end of its collapses).  The quadrics are built once, on
+    the first topology; vertices keep their indices until the final compaction."""
+    P, F = _inputs(v, f, "mesh_simplify")
+    target = max(0, int(target_faces))
+    ctx = _Ctx()
+    nv = P.shape[0]
+    T = Q = None
+    while F.shape[0] > target:
+        T = _Topo(ctx, F, nv, carry=T.bnd if T is not None else None)
+        if Q is None:
+            Q = torch.empty((max(nv, 1), 10), dtype=torch.float64, device=P.device)
+            check(lib.sculpt_rmd_qem_quadrics(T.ref(), _p(P), _p(Q), ctx.stream))
+        ctx.stats["rounds"] += 1
+        F, n = _collapse_round(ctx, T, P, 0, target=target, Q=Q)
+        if n == 0:
+            break
+    P, index = _compact_vertices(ctx, P, nv, F, with_index=True)
+    ctx.done()
+    return P, F, index
 
 
 def decimate_device(v, f, face_ratio=0.1, num_faces=None):

@@ -66,6 +66,21 @@ class Mesh:
         return Mesh(v, f, rows(self.vertex_colors, vi), uvs=rows(self.uvs, corner), texture=self.texture,
                     vertex_normals=rows(self.vertex_normals, vi))
 
+    def simplify(self, simplify) -> "Mesh":
+        """The mesh reduced to a target face count by quadric-error edge collapses on the device (ops.mesh_simplify): simplify =
+        an int >= 1 (target faces) or a float in (0, 1) (ratio of the faces).  vertex_colors and vertex_normals follow
+        vertex_index -- the values of the input vertex each output vertex descends from.  That is an approximation: the vertex
+        has moved to its collapses' target point; TSR.extract_meshes(simplify=...) evaluates colours and normals at the final
+        vertices instead.  A baked mesh (uvs / texture) is refused: its atlas belongs to the faces it was baked for, so simplify
+        before baking."""
+        ops.simplify_rule(simplify)
+        if self.uvs is not None or self.texture is not None:
+            raise ValueError("Mesh.simplify: this mesh has a baked texture; simplify before baking "
+                             "(TSR.extract_meshes(simplify=..., bake_texture=...))")
+        v, f, vi = ops.mesh_simplify(self.vertices, self.faces, simplify)
+        return Mesh(v, f, None if self.vertex_colors is None else self.vertex_colors[vi],
+                    vertex_normals=None if self.vertex_normals is None else self.vertex_normals[vi])
+
     def to_trimesh(self):  # pragma: no cover (trimesh is optional)
         import trimesh
 
@@ -957,7 +972,7 @@ class TSR(KernelEngine):
 
     def extract_meshes(self, scene_codes, enable_texture=False, resolution: int = 256, threshold: float = 25.0,
                        x_range=None, density_events=None, bake_texture: int = 0, normals=None,
-                       keep_components=None) -> List[Mesh]:
+                       keep_components=None, simplify=None) -> List[Mesh]:
         """The arithmetic of system.py:171-200 without the Blender sink: returns device tensors.
         density_events: optional (start, stop) torch events recorded around the dense-grid launch (bench.py's live
         per-launch timing of the dominant kernel, on the stream it is launched on).
@@ -969,11 +984,16 @@ class TSR(KernelEngine):
         keep_components: None (default): the mesh is what marching cubes returns, and nothing more is launched.  "largest", an
         int >= 1 (minimum faces) or a float in (0, 1) (fraction of the largest component's faces): the other connected
         components -- the floaters around the object -- are dropped on the device right after marching cubes
-        (ops.mesh_keep_components), so the colours, the baked atlas and the normals see only what is kept."""
+        (ops.mesh_keep_components), so the colours, the baked atlas and the normals see only what is kept.
+        simplify: None (default): nothing is launched, nothing changes.  An int >= 1 (target faces) or a float in (0, 1) (ratio of
+        the faces left after keep_components): quadric-error edge collapses on the device (ops.mesh_simplify) after
+        keep_components and before the colours, the bake and the normals, which are therefore evaluated at the final vertices."""
         if normals not in (None, "field", "faces"):
             raise ValueError("normals must be None, 'field' or 'faces', got %r" % (normals,))
         if keep_components is not None:
             ops.keep_rule(keep_components)   # a ValueError before anything is launched
+        if simplify is not None:
+            ops.simplify_rule(simplify)
         bake = int(bake_texture) if enable_texture else 0
         self.set_marching_cubes_resolution(resolution)
         r = self.renderer.cfg.radius
@@ -992,12 +1012,16 @@ class TSR(KernelEngine):
                 v_pos, t_pos_idx = self._extract_filtered(planes, R, mc, dkw, density_events)
                 if keep_components is not None:
                     v_pos, t_pos_idx = ops.mesh_keep_components(v_pos, t_pos_idx, keep_components)[:2]
+                if simplify is not None:
+                    v_pos, t_pos_idx = ops.mesh_simplify(v_pos, t_pos_idx, simplify)[:2]
                 out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
                 continue
             vol = ops.density_grid(planes, self.decoder, R, precision=self.decoder_precision, events=density_events, **dkw)
             v_pos, t_pos_idx = mc(vol)   # (both decoder modes have the fp32 range: a NaN here is a NaN of the model)
             if keep_components is not None:
                 v_pos, t_pos_idx = ops.mesh_keep_components(v_pos, t_pos_idx, keep_components)[:2]
+            if simplify is not None:
+                v_pos, t_pos_idx = ops.mesh_simplify(v_pos, t_pos_idx, simplify)[:2]
             out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
         return out
 
@@ -1122,14 +1146,14 @@ class TSR(KernelEngine):
         return Mesh(v_pos, t_pos_idx, color)
 
     def extract_mesh(self, scene_codes, enable_texture=False, mesh_name="NewMesh", resolution: int = 256,
-                     threshold: float = 25.0, bake_texture: int = 0, normals=None, keep_components=None):
-        """system.py:171-200: same signature (+ bake_texture, normals and keep_components, see extract_meshes: the sink receives the
-        filtered mesh); pushes each mesh into the sink (Blender when
+                     threshold: float = 25.0, bake_texture: int = 0, normals=None, keep_components=None, simplify=None):
+        """system.py:171-200: same signature (+ bake_texture, normals, keep_components and simplify, see extract_meshes: the sink
+        receives the filtered, simplified mesh); pushes each mesh into the sink (Blender when
         `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
         the textured sink (per-loop UVs + an image-texture material).  The sinks take no normals (Blender shades a mesh with
         shared vertices smooth by itself); they stay on the returned meshes."""
         meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture, normals=normals,
-                                     keep_components=keep_components)
+                                     keep_components=keep_components, simplify=simplify)
         sink = self.mesh_sink or _default_sink()
         for m in meshes:
             if m.texture is not None:
@@ -1145,7 +1169,7 @@ class TSR(KernelEngine):
         return meshes
 
     def run_async(self, image, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, tokens=None,
-                  normals=None, keep_components=None):
+                  normals=None, keep_components=None, simplify=None):
         """One host image -> PendingMesh.  The image goes host -> HBM, the forward and the mesh extraction are queued on
         the current stream, and the mesh (the reference's `.cpu().numpy()` at system.py:200) is copied device -> pinned
         host memory on a separate copy stream, so the copy of mesh i runs under the kernels of image i + 1.
@@ -1154,7 +1178,7 @@ class TSR(KernelEngine):
         with torch.no_grad():
             codes = self.forward([image], self.device) if tokens is None else self.forward_tokens(tokens)
             m = self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals,
-                                    keep_components=keep_components)[0]
+                                    keep_components=keep_components, simplify=simplify)[0]
         return self._mesh_to_host_async(m)
 
     def _mesh_to_host_async(self, m) -> PendingMesh:
@@ -1185,7 +1209,7 @@ class TSR(KernelEngine):
         return PendingMesh(host, done, tuple(leases))
 
     def run(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, batch=None,
-            normals=None, keep_components=None) -> List[Mesh]:
+            normals=None, keep_components=None, simplify=None) -> List[Mesh]:
         """Headless entry point: images -> list of Mesh with host (NumPy) arrays; the device -> host copy of mesh i overlaps the
         kernels that follow it.
         batch (images per transformer pass; None = the default): in the bf16 mode a stacked pass of several images gives each
@@ -1195,20 +1219,21 @@ class TSR(KernelEngine):
         (test_run_batches_by_default_and_returns_the_serial_meshes).  The limb modes default to one image per pass with the
         tokenizer look-ahead (run_pipelined).  batch=1 forces that everywhere.
         normals: None, "field" or "faces" (extract_meshes): Mesh.vertex_normals as float32 [Nv, 3] on the host.
-        keep_components: None, "largest", an int or a float (extract_meshes): the meshes without their small components."""
+        keep_components: None, "largest", an int or a float (extract_meshes): the meshes without their small components.
+        simplify: None, an int or a float (extract_meshes): the meshes reduced by quadric-error collapses on the device."""
         images = _as_image_list(images)
         if batch is None:
             batch = self.RUN_BATCH if (self.precision == "bf16" and len(images) >= 2) else 1
         if batch <= 1 or len(images) < 2:
             return [p.result() for p in self.run_pipelined(images, mc_resolution, threshold, enable_texture, normals=normals,
-                                                              keep_components=keep_components)]
+                                                              keep_components=keep_components, simplify=simplify)]
         return [p.result() for p in self.run_batched(images, batch, mc_resolution, threshold, enable_texture, normals=normals,
-                                                        keep_components=keep_components)]
+                                                        keep_components=keep_components, simplify=simplify)]
 
     RUN_BATCH = 8   # images per transformer pass of TSR.run in the bf16 mode (4: 139.7, 8: 143.5 meshes/s device to device)
 
     def run_batched(self, images, batch: int = 4, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False,
-                    normals=None, keep_components=None):
+                    normals=None, keep_components=None, simplify=None):
         """images (host or device) -> list of PendingMesh through batched forward passes of `batch` images each."""
         images = list(images)
         pending = []
@@ -1219,26 +1244,27 @@ class TSR(KernelEngine):
                 with torch.no_grad():
                     codes = self.forward(images[i:i + self.max_batch], self.device)
                     for m in self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals,
-                                                 keep_components=keep_components):
+                                                 keep_components=keep_components, simplify=simplify):
                         pending.append(self._mesh_to_host_async(m))
         finally:
             self.max_batch = keep
         return pending
 
     def run_pipelined(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, normals=None,
-                      keep_components=None):
+                      keep_components=None, simplify=None):
         """images (host or device) -> list of PendingMesh, with the tokenizer of image i + 1 queued beside the backbone /
         density grid / marching cubes of image i (tokens_async) and the device -> host copy of mesh i under image i + 1."""
         images = list(images)
         if len(images) < 2:
-            return [self.run_async(im, mc_resolution, threshold, enable_texture, normals=normals, keep_components=keep_components)
+            return [self.run_async(im, mc_resolution, threshold, enable_texture, normals=normals, keep_components=keep_components,
+                                   simplify=simplify)
                     for im in images]
         pending, nxt = [], self.tokens_async(images[0])
         for i, im in enumerate(images):
             cur = nxt
             nxt = self.tokens_async(images[i + 1]) if i + 1 < len(images) else None
             pending.append(self.run_async(im, mc_resolution, threshold, enable_texture, tokens=cur, normals=normals,
-                                          keep_components=keep_components))
+                                          keep_components=keep_components, simplify=simplify))
         return pending
 
 

@@ -1,0 +1,375 @@
+"""ops.mesh_simplify (csrc/mesh_simplify.hip, the rounds of sf3d/remesh_device.py) and the layers above it on the GPU: stage by
+stage against the fp64 restatement tests/_qemref.py, then properties of the whole call, then through the model.  The kernels
+run without floating-point contraction and the restatement keeps their order of operations, so the stage comparisons are of
+bits.  The properties are those tests/test_mesh_simplify_host.py shows the restatement to reach."""
+
+import numpy as np
+import pytest
+import torch
+
+import _qemref
+from sculptmate_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+NO = _qemref.NO_CLAIM
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _bits(a):
+    a = np.ascontiguousarray(_np(a) if isinstance(a, torch.Tensor) else a)
+    return a.view(np.uint64 if a.dtype.itemsize == 8 else np.uint32)
+
+
+def _u64(t):
+    return [int(x) & 0xFFFFFFFFFFFFFFFF for x in _np(t).tolist()]
+
+
+class _Stage:
+    """The device state of one round, driven kernel by kernel the way simplify_device drives it."""
+
+    def __init__(self, cuda, P, F):
+        from sculptmate_amd._lib import check, lib
+        from sculptmate_amd.sf3d import remesh_device as rd
+
+        self.rd, self.lib, self.check = rd, lib, check
+        self.ctx = rd._Ctx()
+        self.P = torch.from_numpy(np.ascontiguousarray(P, np.float32)).to(cuda)
+        self.F = torch.from_numpy(np.ascontiguousarray(F, np.int32)).to(cuda)
+        self.T = rd._Topo(self.ctx, self.F, self.P.shape[0])
+        self.Q = torch.full((max(self.P.shape[0], 1), 10), float("nan"), dtype=torch.float64, device=cuda)
+        check(lib.sculpt_rmd_qem_quadrics(self.T.ref(), rd._p(self.P), rd._p(self.Q), self.ctx.stream))
+
+    def cost(self):
+        rd, T = self.rd, self.T
+        cand = torch.full((max(T.ne, 1),), 5, dtype=torch.int64, device=self.P.device)
+        tgt = torch.full((max(T.ne, 1), 3), float("nan"), dtype=torch.float32, device=self.P.device)
+        self.check(self.lib.sculpt_rmd_qem_cost(T.ref(), rd._p(self.P), rd._p(self.Q), rd._p(cand), rd._p(tgt), self.ctx.stream))
+        return _u64(cand[:T.ne]), _np(tgt[:T.ne])
+
+    def winners(self, target):
+        rd, T = self.rd, self.T
+        dev = self.P.device
+        claim = torch.full((max(T.nv, 1),), -1, dtype=torch.int64, device=dev)
+        self.cand = torch.empty(max(T.ne, 1), dtype=torch.int64, device=dev)
+        self.win = torch.empty(max(T.ne, 1), dtype=torch.int32, device=dev)
+        self.tgt = rd._qem_propose(self.ctx, T, self.P, self.Q, target, claim, self.cand)
+        self.check(self.lib.sculpt_rmd_collapse_select(T.ref(), rd._p(self.P), 0, rd._p(claim), rd._p(self.cand), rd._p(self.win),
+                                                       self.ctx.stream))
+        return _np(self.win[:T.ne]).tolist()
+
+    def apply(self):
+        rd, T = self.rd, self.T
+        alive = torch.ones(T.nf, dtype=torch.uint8, device=self.P.device)
+        self.check(self.lib.sculpt_rmd_qem_apply(T.ref(), rd._p(self.P), rd._p(self.F), rd._p(self.Q), rd._p(self.tgt), rd._p(self.win),
+                                                 rd._p(alive), self.ctx.stream))
+        return _np(self.F)[_np(alive).astype(bool)]
+
+
+def _simplify(cuda, P, F, rule, dtype=torch.int32):
+    from sculptmate_amd import ops
+
+    v, f, i = ops.mesh_simplify(torch.from_numpy(np.ascontiguousarray(P, np.float32)).to(cuda),
+                                torch.from_numpy(np.ascontiguousarray(F)).to(cuda).to(dtype), rule)
+    assert v.dtype == torch.float32 and f.dtype == dtype and i.dtype == torch.int64 and v.is_cuda and f.is_cuda and i.is_cuda
+    return _np(v), _np(f), _np(i)
+
+
+def _same(got, want):
+    """(P, F, index) of the device against the restatement's: positions bit for bit."""
+    assert got[0].shape == want[0].shape and np.array_equal(_bits(got[0]), _bits(want[0]))
+    assert np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2])
+
+
+# ------------------------------------------------------------------------------------------------ 1. stage by stage
+def test_cube_stage_by_stage(cuda):
+    """768 faces, dyadic coordinates, integer quadrics: Q, keys, targets, the winners of the first round and the state after
+    apply, bit for bit; the restatement reports no ambiguous candidate."""
+    P, F = _qemref.cube()
+    S = _qemref.State(P, F)
+    D = _Stage(cuda, P, F)
+    assert np.array_equal(_bits(D.Q), _bits(S.Q))
+    pr = _qemref.proposals(S)
+    assert not any(pr["ambiguous"])
+    cand, tgt = D.cost()
+    assert cand == pr["cand"] and np.array_equal(_bits(tgt), _bits(pr["target"]))
+    assert {0, 1, 2} <= set(pr["branch"][np.array(cand) != NO].tolist())
+    target = 76
+    prk = _qemref.proposals(S, k=_qemref.cap_rank(S.T["nf"], target, S.T["ne"]))
+    win = _qemref.round_winners(S, prk, target)
+    assert D.winners(target) == win and sum(1 for w in win if w) > 1
+    Fn = D.apply()
+    _qemref.apply_round(S, prk, win)
+    assert np.array_equal(Fn, S.F) and np.array_equal(_bits(D.P), _bits(S.P)) and np.array_equal(_bits(D.Q), _bits(S.Q))
+
+
+def test_patch_border_rule(cuda):
+    P, F = _qemref.patch()
+    S = _qemref.State(P, F)
+    D = _Stage(cuda, P, F)
+    assert np.array_equal(_np(D.T.bnd)[:len(P)], S.bnd[:len(P)]) and np.array_equal(_bits(D.Q), _bits(S.Q))
+    pr = _qemref.proposals(S)
+    cand, tgt = D.cost()
+    assert not any(pr["ambiguous"]) and cand == pr["cand"] and np.array_equal(_bits(tgt), _bits(pr["target"]))
+    outline = ((P[:, :2] == 0) | (P[:, :2] == 1)).any(1)
+    on_border = 0
+    for e, key in enumerate(cand):
+        u, v = _qemref.edge_ends(S.T, e)
+        if outline[u] != outline[v]:
+            assert key == NO
+        elif key != NO and outline[u]:
+            on_border += 1
+            mid = (0.5 * (P[u].astype(np.float64) + P[v])).astype(np.float32)
+            assert any(np.array_equal(tgt[e], x) for x in (P[u], P[v], mid))
+    assert on_border
+
+
+@pytest.mark.parametrize("name", ["tetrahedron", "two_triangles", "triangle", "fan70", "fan65", "fan64", "slivers"])
+def test_hand_meshes(cuda, name):
+    """Keys and targets against the restatement, then the whole call.  tetrahedron, triangle: nothing can collapse, the input
+    comes back.  fan: two fans of n faces glued at the rim; above 64 neighbours the hubs are features and no hub edge is a
+    candidate; at 64 they are.  slivers: two coincident vertices, two zero-area faces: no NaN, the zero-length edge wins."""
+    P, F = {"tetrahedron": _qemref.tetrahedron, "two_triangles": _qemref.two_triangles, "fan70": lambda: _qemref.fan(70),
+            "triangle": lambda: (_qemref.two_triangles()[0][:3], np.array([[0, 1, 2]], np.int32)),
+            "fan65": lambda: _qemref.fan(65), "fan64": lambda: _qemref.fan(64), "slivers": _qemref.bipyramid_with_slivers}[name]()
+    S = _qemref.State(P, F)
+    D = _Stage(cuda, P, F)
+    assert np.array_equal(_bits(D.Q), _bits(S.Q)) and np.isfinite(_np(D.Q)).all()
+    pr = _qemref.proposals(S)
+    cand, tgt = D.cost()
+    assert np.isfinite(tgt).all()
+    clear = [e for e in range(S.T["ne"]) if not pr["ambiguous"][e]]
+    assert [cand[e] for e in clear] == [pr["cand"][e] for e in clear]
+    assert all(np.array_equal(_bits(tgt[e]), _bits(pr["target"][e])) for e in clear if cand[e] != NO)
+    if name.startswith("fan"):
+        hub = [cand[e] != NO for e in range(S.T["ne"]) if _qemref.edge_ends(S.T, e)[0] < 2]
+        assert _np(D.T.bnd)[:2].all() == (name != "fan64") and any(hub) == (name == "fan64")
+    target = len(F) // 2
+    if name == "slivers":
+        win = D.winners(target)
+        assert [_qemref.edge_ends(S.T, e) for e, w in enumerate(win) if w] == [(7, 8)]
+    got = _simplify(cuda, P, F, 0.5)
+    want = _qemref.simplify(P, F, target)
+    assert np.isfinite(got[0]).all()
+    assert want[3]["ambiguous"] == 0    # every named mesh: the comparison below is never skipped
+    _same(got, want[:3])
+    if name in ("tetrahedron", "triangle"):
+        assert np.array_equal(_bits(got[0]), _bits(P)) and np.array_equal(got[1], F) and got[2].tolist() == list(range(len(P)))
+
+
+def test_no_face_and_a_target_already_met(cuda):
+    from sculptmate_amd import ops
+    from sculptmate_amd.sf3d import remesh_device as rd
+
+    v = torch.zeros((3, 3), device=cuda)
+    for f in (torch.zeros((0, 3), dtype=torch.int64, device=cuda), torch.tensor([[0, 1, 2]], dtype=torch.int32, device=cuda)):
+        ov, of, oi = ops.mesh_simplify(v, f, 5)   # target >= Nf: the input comes back, nothing is launched
+        assert ov is v and of is f and oi.tolist() == [0, 1, 2]
+    ctx = rd._Ctx()
+    T = rd._Topo(ctx, torch.zeros((0, 3), dtype=torch.int32, device=cuda), 3)
+    Q = torch.ones((3, 10), dtype=torch.float64, device=cuda)
+    rd.check(rd.lib.sculpt_rmd_qem_quadrics(T.ref(), rd._p(v), rd._p(Q), ctx.stream))
+    assert not Q.any()
+    for call in (lambda: rd.lib.sculpt_rmd_qem_cost(T.ref(), None, None, None, None, ctx.stream),
+                 lambda: rd.lib.sculpt_rmd_qem_claim(T.ref(), None, None, None, ctx.stream),
+                 lambda: rd.lib.sculpt_rmd_qem_apply(T.ref(), None, None, None, None, None, None, ctx.stream)):
+        rd.check(call())     # ne == 0: nothing is launched, nothing is dereferenced
+    with pytest.raises(ops.SculptError):
+        rd.check(rd.lib.sculpt_rmd_qem_cost(None, None, None, None, None, ctx.stream))
+
+
+def test_index_types_and_strides(cuda):
+    from sculptmate_amd import ops
+
+    P, F = _qemref.cube(4)
+    v = torch.from_numpy(P).to(cuda)
+    f32, f64 = torch.from_numpy(F).to(cuda), torch.from_numpy(F.astype(np.int64)).to(cuda)
+    a, b = ops.mesh_simplify(v, f32, 0.25), ops.mesh_simplify(v, f64, 0.25)
+    assert a[1].dtype == torch.int32 and b[1].dtype == torch.int64 and a[1].shape[0] <= 48
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1].long(), b[1]) and torch.equal(a[2], b[2])
+    wide = torch.zeros((len(F), 6), dtype=torch.int32, device=cuda)
+    wide[:, ::2] = f32
+    view = wide[:, ::2]
+    vw = torch.zeros((len(P), 5), dtype=torch.float32, device=cuda)
+    vw[:, :3] = v
+    assert not view.is_contiguous() and not vw[:, :3].is_contiguous()
+    c = ops.mesh_simplify(vw[:, :3], view, 0.25)
+    assert all(torch.equal(x, y) for x, y in zip(a, c))
+    d = ops.mesh_simplify(v.double(), f32, 48)
+    assert all(torch.equal(x, y) for x, y in zip(a, d))
+    assert torch.equal(v, torch.from_numpy(P).to(cuda)) and torch.equal(f32, torch.from_numpy(F).to(cuda))   # inputs untouched
+    with pytest.raises(ops.SculptError):
+        ops.mesh_simplify(v, f32.float(), 0.25)
+    with pytest.raises(ops.SculptError):
+        ops.mesh_simplify(v[:, :2], f32, 0.25)
+    with pytest.raises(ops.SculptError):
+        ops.mesh_simplify(v, f32 + 1000, 0.25)
+
+
+# ------------------------------------------------------------------------------------------------------ 2. properties
+def test_cube_to_a_tenth(cuda):
+    """The restatement's result (76 faces unless it stalls earlier), bit for bit, and its properties: closed, Euler 2, the eight
+    corners, flat outward sides.  Volume: V is linear in every vertex with gradient a third of the vector area of its faces, so
+    fp32 rounding of the coordinates (at most 2^-24 each in [0, 1]) moves it by at most (surface 6) x sqrt(3) x 2^-24, whatever
+    the number of vertices (40 here)."""
+    from sculptmate_amd.sf3d import remesh_device as rd
+
+    P, F = _qemref.cube()
+    want = _qemref.reference("cube")
+    got = _simplify(cuda, P, F, 0.1)
+    stats = rd.last_stats()
+    assert want[3]["ambiguous"] == 0 and len(got[1]) == len(want[1]) <= 76
+    _same(got, want[:3])
+    vol = _qemref.cube_checks(got[0], got[1])
+    assert abs(vol - 1.0) <= 6 * np.sqrt(3) * 2.0 ** -24
+    assert stats["rounds"] == want[3]["rounds"] and stats["collapses"] == want[3]["collapses"]
+    print("cube: %d faces, %d rounds, %d readbacks, volume %.9f" % (len(got[1]), stats["rounds"], stats["readbacks"], vol))
+
+
+def test_patch_to_a_tenth(cuda):
+    """Flat, +z, inside its outline with every border vertex on it (tests/test_mesh_simplify_host.py: the area is not kept)."""
+    P, F = _qemref.patch()
+    want = _qemref.reference("patch")
+    got = _simplify(cuda, P, F, 0.1)
+    assert want[3]["ambiguous"] == 0 and len(got[1]) <= 51
+    _same(got, want[:3])
+    assert _qemref.patch_checks(got[0], got[1]) == _qemref.PATCH_AREA
+
+
+@pytest.fixture(scope="module")
+def sphere(cuda):
+    """ops.marching_cubes of the sphere at 32^3 (radius 0.6 of the half-extent), turned outward; lattice units."""
+    from sculptmate_amd import ops
+
+    R = 32
+    v, f = ops.marching_cubes(torch.from_numpy(_qemref.sphere_volume(R)).to(cuda), 0.0)
+    c = (R - 1) / 2.0
+    if _qemref.signed_volume(_np(v) - c, _np(f)) < 0:
+        f = f[:, [0, 2, 1]].contiguous()
+    assert _qemref.closed_manifold(_np(f))
+    return v, f, c, 0.6 * c
+
+
+@pytest.mark.parametrize("ratio", [0.25, 0.05])
+def test_sphere_properties_and_quality(cuda, sphere, ratio):
+    """Closed, Euler 2, at most the target, outward, volume within the polyhedral deficit (_qemref.sphere_checks); and better
+    than decimate_device (mode 0: shortest edge to its midpoint) at the same face count: smaller volume error, smaller radial
+    error of the surface (vertices and face centroids), and at a quarter of the faces also at the vertices alone (at a twentieth that figure is
+    printed -- test_mesh_simplify_host.py says why)."""
+    from sculptmate_amd import ops
+    from sculptmate_amd.sf3d import remesh_device as rd
+
+    v, f, c, r = sphere
+    target = int(np.floor(ratio * f.shape[0]))
+    P, F, index = ops.mesh_simplify(v, f, ratio)
+    stats = rd.last_stats()
+    rad, surf, dvol = _qemref.sphere_checks(_np(P), _np(F), c, r, target)
+    dv, df, _, _ = rd.decimate_device(v, f, num_faces=F.shape[0])
+    assert df.shape[0] == F.shape[0]
+    rad0, surf0, dvol0 = _qemref.sphere_checks(_np(dv), _np(df), c, r, target)
+    print("sphere %d -> %d faces, %d rounds, %d readbacks: quadric vertex %.4f surface %.4f volume %.3f; mode 0 %.4f / %.4f / %.3f" % (
+        f.shape[0], F.shape[0], stats["rounds"], stats["readbacks"], rad, surf, dvol, rad0, surf0, dvol0))
+    assert surf < surf0 and dvol < dvol0
+    if ratio == 0.25:   # the vertices alone: reached at a quarter (DESIGN.md 3.3c says why not at a twentieth)
+        assert rad < rad0
+    idx = _np(index)     # vertex_index: ascending input rows
+    assert len(idx) == P.shape[0] and (np.diff(idx) > 0).all() and idx.max() < v.shape[0]
+
+
+def test_determinism_and_face_order(cuda, sphere):
+    from sculptmate_amd import ops
+
+    v, f, c, r = sphere
+    a, b = ops.mesh_simplify(v, f, 0.25), ops.mesh_simplify(v, f, 0.25)
+    assert all(torch.equal(x, y) for x, y in zip(a, b))
+    perm = torch.from_numpy(np.random.default_rng(7).permutation(f.shape[0])).to(cuda)
+    P, F, _ = ops.mesh_simplify(v, f[perm].contiguous(), 0.25)     # the contract: a valid mesh with the same properties
+    _qemref.sphere_checks(_np(P), _np(F), c, r, int(np.floor(0.25 * f.shape[0])))
+
+
+# --------------------------------------------------------------------------------------------- 3. through the model
+@pytest.fixture(scope="module")
+def model(cuda):
+    """The small synthetic TSR of the other GPU tests, one scene code, the threshold of tests/test_gpu_mesh_components.py (the
+    grid's median) and ONE unsimplified mesh at resolution 64 (shared, never modified)."""
+    from sculptmate_amd import ops
+    from sculptmate_amd.tsr import TSR
+    from sculptmate_amd.tsr.spec import SMALL_CFG
+
+    m = TSR(SMALL_CFG, pos_embed_mode="size")
+    m.load_state_dict(synth.tsr_state(31, SMALL_CFG))
+    m.to(cuda)
+    img = synth.composite_rgb(synth.image_rgba(seed=32, size=SMALL_CFG["cond_image_size"]))
+    codes = m([img], device=cuda)
+    threshold = float(ops.density_grid(codes[0].contiguous(), m.decoder, 64).median())
+    kw = dict(resolution=64, threshold=threshold)
+    plain = m.extract_meshes(codes, enable_texture=True, normals="field", **kw)[0]
+    return dict(m=m, img=img, codes=codes, threshold=threshold, kw=kw, plain=plain)
+
+
+def test_extract_meshes_is_the_three_calls_in_order(model):
+    from sculptmate_amd import ops
+
+    m, plain, kw = model["m"], model["plain"], model["kw"]
+    kv, kf = ops.mesh_keep_components(plain.vertices, plain.faces, "largest")[:2]
+    sv, sf, _ = ops.mesh_simplify(kv, kf, 0.25)
+    assert 0 < sf.shape[0] <= int(0.25 * kf.shape[0])
+    got = m.extract_meshes(model["codes"], simplify=0.25, keep_components="largest", **kw)[0]
+    assert np.array_equal(_bits(got.vertices), _bits(sv)) and torch.equal(got.faces, sf) and got.faces.dtype == plain.faces.dtype
+    assert got.vertex_colors is None and got.vertex_normals is None
+    full = m.extract_meshes(model["codes"], enable_texture=True, normals="field", simplify=0.25, keep_components="largest", **kw)[0]
+    assert np.array_equal(_bits(full.vertices), _bits(sv)) and torch.equal(full.faces, sf)
+    assert tuple(full.vertex_colors.shape) == tuple(full.vertex_normals.shape) == tuple(sv.shape)
+    planes = model["codes"][0].contiguous()
+    color = m.renderer.query_triplane(m.decoder, sv, planes)["color"]
+    assert np.array_equal(_bits(full.vertex_colors), _bits(color))                 # evaluated at the NEW vertices
+    assert np.array_equal(_bits(full.vertex_normals), _bits(m.field_normals(sv, planes)))
+    again = plain.keep_components("largest").simplify(0.25)                           # Mesh.simplify: the same geometry
+    assert torch.equal(again.vertices, sv) and torch.equal(again.faces, sf)
+    assert tuple(again.vertex_colors.shape) == tuple(sv.shape) and tuple(again.vertex_normals.shape) == tuple(sv.shape)
+
+
+def test_host_meshes_and_the_bake_have_the_simplified_sizes(model):
+    from sculptmate_amd import ops
+
+    m, plain, kw = model["m"], model["plain"], model["kw"]
+    kv, kf = ops.mesh_keep_components(plain.vertices, plain.faces, "largest")[:2]
+    sv, sf, _ = ops.mesh_simplify(kv, kf, 0.25)
+    rkw = dict(mc_resolution=64, threshold=model["threshold"], keep_components="largest", simplify=0.25)
+    host = m.run([model["img"]], **rkw)[0]
+    assert isinstance(host.vertices, np.ndarray) and host.vertices.shape == tuple(sv.shape) and host.faces.shape == tuple(sf.shape)
+    two = m.run([model["img"], model["img"]], **rkw)
+    assert [x.faces.shape for x in two] == [tuple(sf.shape)] * 2 and np.array_equal(two[0].faces, two[1].faces)
+    baked = m.extract_meshes(model["codes"], enable_texture=True, bake_texture=64, keep_components="largest", simplify=0.25, **kw)[0]
+    assert tuple(baked.uvs.shape) == (3 * sf.shape[0], 2) and tuple(baked.texture.shape) == (64, 64, 3)
+    assert torch.equal(baked.faces, sf) and np.array_equal(_bits(baked.vertices), _bits(sv))
+    with pytest.raises(ValueError):
+        baked.simplify(0.5)
+    again = m.bake_texture(plain.keep_components("largest").simplify(0.25), model["codes"][0], 64)
+    assert tuple(again.uvs.shape) == tuple(baked.uvs.shape)
+
+
+def test_none_launches_nothing_new_and_changes_nothing(model, monkeypatch):
+    from sculptmate_amd import ops
+    from sculptmate_amd.sf3d import remesh_device as rd
+
+    m, plain, kw = model["m"], model["plain"], model["kw"]
+
+    def refuse(*a, **k):
+        raise AssertionError("simplify=None must not reach the simplifier")
+
+    monkeypatch.setattr(ops, "mesh_simplify", refuse)
+    monkeypatch.setattr(ops, "simplify_rule", refuse)
+    monkeypatch.setattr(rd, "simplify_device", refuse)
+    for name in ("sculpt_rmd_qem_quadrics", "sculpt_rmd_qem_cost", "sculpt_rmd_qem_claim", "sculpt_rmd_qem_apply"):
+        monkeypatch.setattr(rd.lib, name, refuse)
+    for extra in ({}, {"simplify": None}):
+        again = m.extract_meshes(model["codes"], enable_texture=True, normals="field", **kw, **extra)[0]
+        assert np.array_equal(_bits(again.vertices), _bits(plain.vertices)) and torch.equal(again.faces, plain.faces)
+        assert np.array_equal(_bits(again.vertex_colors), _bits(plain.vertex_colors))
+        assert np.array_equal(_bits(again.vertex_normals), _bits(plain.vertex_normals))
+    host = m.run([model["img"]], mc_resolution=64, threshold=model["threshold"])[0]
+    assert host.vertices.shape == tuple(plain.vertices.shape) and np.array_equal(host.faces, _np(plain.faces))
