@@ -44,6 +44,7 @@
 #include <algorithm>
 #include <atomic>
 
+#include "block_scan.h"
 #include "common.h"
 #include "triplane_mlp.h"
 
@@ -386,16 +387,8 @@ __global__ __launch_bounds__(1024) void filter_cells_kernel(const uint32_t *__re
         cell[i] = c;
     }
     // active cells, for the statistics: one atomic per workgroup
-    int tot = __popc(active);
-#pragma unroll
-    for (int o = 32; o; o >>= 1) tot += __shfl_xor(tot, o, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = tot;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int k = 0; k < (int)(blockDim.x >> 6); ++k) t += wsum[k];
-        if (t) atomicAdd(&hdr->n_cells, t);
-    }
+    const int t = block_sum<16>((int)__popc(active), wsum);
+    if (threadIdx.x == 0 && t) atomicAdd(&hdr->n_cells, t);
 }
 
 // One thread per word of 32 points along z; a workgroup reserves one contiguous range of the list for its points (one atomic):
@@ -457,16 +450,7 @@ __global__ __launch_bounds__(1024) void filter_points_kernel(const uint32_t *__r
         entry = ((uint32_t)x << 20) | ((uint32_t)y << 10) | (uint32_t)(32 * w);
     }
     const int n = __popc(r);
-    int incl = n, aincl = aud ? 1 : 0;  // inclusive scans inside the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-        if (STAGE == 1) {
-            const int a = __shfl_up(aincl, o, 64);
-            if (lane >= o) aincl += a;
-        }
-    }
+    const int incl = wave_inclusive_add(n), aincl = STAGE == 1 ? wave_inclusive_add(aud ? 1 : 0) : 0;
     if (lane == 63) { wsum[wv] = incl; asum[wv] = aincl; }
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -6,6 +6,7 @@
 #include <mutex>
 #include <vector>
 
+#include "block_scan.h"
 #include "common.h"
 #include "resample_coeffs.h"
 
@@ -116,14 +117,7 @@ __global__ void __launch_bounds__(IF_THREADS) u2net_input_kernel(const uint8_t *
     out[2 * n + i] = (float)(((double)p[2] / mx - m2) / s2);
 }
 
-// order-preserving map of fp32 onto uint32 (and back), so that integer atomics give the float minimum and maximum
-__device__ __forceinline__ uint32_t f32_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float f32_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// ws[0] = key of the minimum, ws[1] = key of the maximum (set to 0xffffffff / 0 before); NaNs take no part
+// ws[0] = ordered key (f32_to_ordered) of the minimum, ws[1] = of the maximum (set to 0xffffffff / 0 before); NaNs take no part
 __global__ void __launch_bounds__(IF_THREADS) f32_minmax_kernel(const float *__restrict__ d, long n, uint32_t *ws) {
     __shared__ uint32_t smin, smax;
     if (threadIdx.x == 0) {
@@ -135,7 +129,7 @@ __global__ void __launch_bounds__(IF_THREADS) f32_minmax_kernel(const float *__r
     for (long i = (long)blockIdx.x * IF_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * IF_THREADS) {
         const float v = d[i];
         if (v == v) {
-            const uint32_t k = f32_key(v);
+            const uint32_t k = f32_to_ordered(v);
             lo = min(lo, k);
             hi = max(hi, k);
         }
@@ -154,7 +148,7 @@ __global__ void __launch_bounds__(IF_THREADS) u2net_mask_kernel(const float *__r
                                                                 uint8_t *__restrict__ mask) {
     const long i = (long)blockIdx.x * IF_THREADS + threadIdx.x;
     if (i >= n) return;
-    const float mi = f32_unkey(ws[0]), ma = f32_unkey(ws[1]);
+    const float mi = ordered_to_f32(ws[0]), ma = ordered_to_f32(ws[1]);
     const float span = ma - mi;
     uint8_t m = 0;
     if (ma > mi) {   // false as well when the image holds no number at all (both keys untouched: NaN patterns)

@@ -32,6 +32,7 @@
 #include <stdlib.h>
 
 
+#include "block_scan.h"
 #include "common.h"
 #include "mc_luts.h"
 #include "readback_ring.h"
@@ -500,41 +501,6 @@ __device__ int cell_counts(const Tiling &t, int x, int y, int z, int halo_low) {
     return (t.len / 3) | (nown << 16);
 }
 
-// exclusive scan of `val` over the 256-thread block; returns exclusive prefix, total in *total
-__device__ int block_exclusive_scan(int val, int *total) {
-    __shared__ int wsum[MC_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = val;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        int up = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += up;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < MC_BLOCK / 64; ++w) {
-        const int s = wsum[w];
-        if (w < wave) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - val;
-}
-
-__device__ __forceinline__ unsigned f2ord(float f) {
-    unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-static inline float ord2f(unsigned o) {
-    unsigned u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
 struct McHeader {            // first 64 bytes of the workspace
     unsigned long long total_tri;
     unsigned long long total_vert;
@@ -800,12 +766,7 @@ __global__ __launch_bounds__(MC_BLOCK) void mc_classify_brick_kernel(const float
             const int k = k0 + lane;
             const int b = k < n ? s_pk[start + k] : 0;
             const int val = (b & 15) | ((b >> 4) << 16);
-            int inc = val;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int up = __shfl_up(inc, d, 64);
-                if (lane >= d) inc += up;
-            }
+            const int inc = wave_inclusive_add(val);
             if (k < n && s_pool != ~0u)
                 recs[s_pool + start + k].w1 = (unsigned)(carry + inc - val) | rank_bits_to_w1(s_list[lr][k]) | (classic ? 1u << 30 : 0u);
             carry += __shfl(inc, 63, 64);
@@ -855,14 +816,8 @@ __global__ __launch_bounds__(1024) void mc_scan1_kernel(const int *__restrict__ 
     if (i < nblocks) { const float2 mm = block_minmax[i]; mn = mm.x; mx = mm.y; }
     const unsigned long long val = (unsigned long long)(pk & 0xffff) | ((unsigned long long)(pk >> 16) << 32);
     const unsigned na = i < nblocks ? (unsigned)block_nact[i] : 0u;
-    unsigned long long inc = val;
-    unsigned ainc = na;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        unsigned long long up = __shfl_up(inc, d, 64);
-        const unsigned aup = __shfl_up(ainc, d, 64);
-        if (lane >= d) { inc += up; ainc += aup; }
-    }
+    const unsigned long long inc = wave_inclusive_add(val);
+    const unsigned ainc = wave_inclusive_add(na);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         mn = fminf(mn, __shfl_xor(mn, d, 64));
@@ -897,41 +852,34 @@ __global__ __launch_bounds__(1024) void mc_scan2_kernel(unsigned long long *__re
                                                         const float2 *__restrict__ group_minmax, int ngroups,
                                                         McHeader *__restrict__ hdr, unsigned *__restrict__ group_act) {
     __shared__ unsigned long long wsum[16];
-    __shared__ unsigned long long carry_s;
     __shared__ unsigned wasum[16];
-    __shared__ unsigned acarry_s;
-    if (threadIdx.x == 0) acarry_s = 0;
     __shared__ float s_mn[16], s_mx[16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
     float mn = FLT_MAX, mx = -FLT_MAX;
+    // the two scans share one loop and its two barriers (block_scan_in_place once per array would double them); the carries are
+    // per-thread copies: every thread adds the same trip totals
+    unsigned long long carry = 0;
+    unsigned acarry = 0;
     for (int base = 0; base < ngroups; base += 1024) {
         const int i = base + threadIdx.x;
         const unsigned long long val = i < ngroups ? group_tot[i] : 0ull;
         const unsigned aval = i < ngroups ? group_act[i] : 0u;
         if (i < ngroups) { const float2 mm = group_minmax[i]; mn = fminf(mn, mm.x); mx = fmaxf(mx, mm.y); }
-        unsigned long long inc = val;
-        unsigned ainc = aval;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            unsigned long long up = __shfl_up(inc, d, 64);
-            const unsigned aup = __shfl_up(ainc, d, 64);
-            if (lane >= d) { inc += up; ainc += aup; }
-        }
+        const unsigned long long inc = wave_inclusive_add(val);
+        const unsigned ainc = wave_inclusive_add(aval);
         if (lane == 63) { wsum[wave] = inc; wasum[wave] = ainc; }
         __syncthreads();
-        unsigned long long wbase = carry_s, tot = 0;
-        unsigned awbase = acarry_s, atot = 0;
+        unsigned long long wbase = carry, tot = 0;
+        unsigned awbase = acarry, atot = 0;
         for (int w = 0; w < 16; ++w) {
             if (w < wave) { wbase += wsum[w]; awbase += wasum[w]; }
             tot += wsum[w];
             atot += wasum[w];
         }
         if (i < ngroups) { group_tot[i] = wbase + inc - val; group_act[i] = awbase + ainc - aval; }
-        __syncthreads();
-        if (threadIdx.x == 0) { carry_s += tot; acarry_s += atot; }
-        __syncthreads();
+        carry += tot;
+        acarry += atot;
+        __syncthreads();   // wsum / wasum are read: the next trip may write them
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -942,11 +890,11 @@ __global__ __launch_bounds__(1024) void mc_scan2_kernel(unsigned long long *__re
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 0; w < 16; ++w) { mn = fminf(mn, s_mn[w]); mx = fmaxf(mx, s_mx[w]); }
-        hdr->total_tri = carry_s & 0xffffffffull;
-        hdr->total_vert = carry_s >> 32;
-        hdr->total_active = acarry_s;
-        hdr->min_ord = f2ord(mn);
-        hdr->max_ord = f2ord(mx);
+        hdr->total_tri = carry & 0xffffffffull;
+        hdr->total_vert = carry >> 32;
+        hdr->total_active = acarry;
+        hdr->min_ord = f32_to_ordered(mn);
+        hdr->max_ord = f32_to_ordered(mx);
     }
 }
 
@@ -1097,12 +1045,7 @@ __global__ __launch_bounds__(MC_BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8))
                 }
             }
             const bool own = tid < MC_EHROWS && dz >= 0 && dy >= 0;
-            int inc = n, oinc = own ? n : 0;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int up = __shfl_up(inc, d, 64), oup = __shfl_up(oinc, d, 64);
-                if (tid >= d) { inc += up; oinc += oup; }
-            }
+            const int inc = wave_inclusive_add(n), oinc = wave_inclusive_add(own ? n : 0);
             if (tid < MC_EHROWS) s_start[tid + 1] = inc;
             if (own) s_own[dz * MC_EY + dy + 1] = oinc;
             if (tid == 0) { s_start[0] = 0; s_own[0] = 0; }
@@ -1431,7 +1374,7 @@ int sculpt_mc_count_read_ex(int n0, int n1, int n2, double level, unsigned flags
     *n_faces_host = (int64_t)res.total_tri;
     if (n_active_host) *n_active_host = (int64_t)res.total_active;
     // skimage: "Surface level must be within volume data range." (ValueError)
-    const float mn = ord2f(res.min_ord), mx = ord2f(res.max_ord);
+    const float mn = ordered_to_f32(res.min_ord), mx = ordered_to_f32(res.max_ord);
     if (minmax_host) { minmax_host[0] = mn; minmax_host[1] = mx; }
     if (res.nan_seen) {
         set_error("marching_cubes: the volume contains NaN");

@@ -35,9 +35,10 @@
 //        A component without faces (a vertex no face references) is never kept.
 // COMPACT, stable: flags -> per-1024 totals -> one workgroup scans the totals -> the compact kernels recompute the flag, rank it
 //        inside the 1024 with ballots and add the scanned base.  Order is preserved: the result is the input with rows deleted.
-//        (mc.hip's scan carries marching cubes' packed counts, minima and maxima; it is not shared.)
+//        (The count, rank and scan are block_scan.h's.)
 #include <algorithm>
 
+#include "block_scan.h"
 #include "common.h"
 #include "readback_ring.h"
 
@@ -215,29 +216,6 @@ __global__ __launch_bounds__(CC_BLOCK) void cc_count_faces_kernel(const IdxT *__
     cc_aggregated_add<CC_BLOCK / 64>(fcount, ok ? labels[a] : -1, ok, s_lab, s_cnt);
 }
 
-// number of set flags of the workgroup -> *out (thread 0 writes); every thread calls
-__device__ __forceinline__ void cc_block_total(bool flag, unsigned *s_w, unsigned *out) {
-    const unsigned long long m = __ballot(flag);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = (unsigned)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned t = 0u;
-        for (int w = 0; w < CC_CHUNK / 64; ++w) t += s_w[w];   // 16 trips
-        *out = t;
-    }
-}
-
-// the flag's rank among the set flags of the workgroup (exclusive); every thread calls
-__device__ __forceinline__ unsigned cc_block_rank(bool flag, unsigned *s_w) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    if (lane == 0) s_w[wave] = (unsigned)__popcll(m);
-    __syncthreads();
-    unsigned base = 0u;
-    for (int w = 0; w < wave; ++w) base += s_w[w];   // < 16 trips
-    return base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-}
-
 // vertex counts at the roots, the number of roots per 1024 vertices, and the "largest" key
 __global__ __launch_bounds__(CC_CHUNK) void cc_count_verts_kernel(const int *__restrict__ labels, int nv,
                                                                   const unsigned *__restrict__ fcount, unsigned *__restrict__ vcount,
@@ -263,7 +241,8 @@ __global__ __launch_bounds__(CC_CHUNK) void cc_count_verts_kernel(const int *__r
         for (int w = 0; w < CC_CHUNK / 64; ++w) best = s_best[w] > best ? s_best[w] : best;   // 16 trips
         if (best) atomicMax(&hdr->best, best);
     }
-    cc_block_total(root, s_w, bt_root + blockIdx.x);
+    const unsigned nroot = block_flag_count<CC_CHUNK / 64>(root, s_w);
+    if (threadIdx.x == 0) bt_root[blockIdx.x] = nroot;
 }
 
 // is the component of root `root` kept?  `cnt` = its face count
@@ -300,58 +279,24 @@ __global__ __launch_bounds__(CC_CHUNK) void cc_keep_totals_kernel(const IdxT *__
                                                                   unsigned *__restrict__ bt_keepf) {
     __shared__ unsigned s_w[CC_CHUNK / 64];
     const CcRule r = cc_rule(hdr);
-    if ((int)blockIdx.x < nbv) {
-        const long v = (long)blockIdx.x * CC_CHUNK + threadIdx.x;
-        cc_block_total(cc_vertex_kept(r, labels, fcount, v, nv), s_w, bt_keepv + blockIdx.x);
-    } else {
-        const int blk = (int)blockIdx.x - nbv;
-        const long i = (long)blk * CC_CHUNK + threadIdx.x;
-        int a, b, c;
-        cc_block_total(cc_face_kept(r, faces, labels, fcount, i, nf, nv, a, b, c), s_w, bt_keepf + blk);
-    }
-}
-
-// exclusive scan of a[0..n) in place by one workgroup of 1024; returns the total to every thread.  ceil(n / 1024) trips.
-__device__ unsigned cc_scan_in_place(unsigned *__restrict__ a, int n, unsigned *s_w, unsigned *s_carry) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) *s_carry = 0u;
-    __syncthreads();
-    for (int base = 0; base < n; base += CC_CHUNK) {
-        const int i = base + threadIdx.x;
-        const unsigned val = i < n ? a[i] : 0u;
-        unsigned inc = val;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned up = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += up;
-        }
-        if (lane == 63) s_w[wave] = inc;
-        __syncthreads();
-        unsigned wbase = *s_carry, tot = 0u;
-        for (int w = 0; w < CC_CHUNK / 64; ++w) {   // 16 trips
-            if (w < wave) wbase += s_w[w];
-            tot += s_w[w];
-        }
-        if (i < n) a[i] = wbase + inc - val;
-        __syncthreads();
-        if (threadIdx.x == 0) *s_carry += tot;
-        __syncthreads();
-    }
-    return *s_carry;
+    const bool verts = (int)blockIdx.x < nbv;   // workgroup-uniform
+    const int blk = verts ? (int)blockIdx.x : (int)blockIdx.x - nbv;
+    const long i = (long)blk * CC_CHUNK + threadIdx.x;
+    int a, b, c;
+    const bool kept = verts ? cc_vertex_kept(r, labels, fcount, i, nv) : cc_face_kept(r, faces, labels, fcount, i, nf, nv, a, b, c);
+    const unsigned total = block_flag_count<CC_CHUNK / 64>(kept, s_w);
+    if (threadIdx.x == 0) (verts ? bt_keepv : bt_keepf)[blk] = total;
 }
 
 __global__ __launch_bounds__(CC_CHUNK) void cc_scan_totals_kernel(unsigned *__restrict__ bt_root, unsigned *__restrict__ bt_keepv,
                                                                   unsigned *__restrict__ bt_keepf, int nbv, int nbf,
                                                                   CcHeader *__restrict__ hdr) {
     __shared__ unsigned s_w[CC_CHUNK / 64];
-    __shared__ unsigned s_carry;
-    const unsigned nroot = cc_scan_in_place(bt_root, nbv, s_w, &s_carry);
-    __syncthreads();
+    const unsigned nroot = block_scan_in_place<CC_CHUNK / 64>(bt_root, nbv, s_w);
     unsigned kv = 0u, kf = 0u;
     if (bt_keepv) {
-        kv = cc_scan_in_place(bt_keepv, nbv, s_w, &s_carry);
-        __syncthreads();
-        kf = cc_scan_in_place(bt_keepf, nbf, s_w, &s_carry);
+        kv = block_scan_in_place<CC_CHUNK / 64>(bt_keepv, nbv, s_w);
+        kf = block_scan_in_place<CC_CHUNK / 64>(bt_keepf, nbf, s_w);
     }
     if (threadIdx.x == 0) {
         hdr->n_components = nroot;
@@ -370,7 +315,7 @@ __global__ __launch_bounds__(CC_CHUNK) void cc_compact_verts_kernel(const float 
     const CcRule r = cc_rule(hdr);
     const long v = (long)blockIdx.x * CC_CHUNK + threadIdx.x;
     const bool keep = cc_vertex_kept(r, labels, fcount, v, nv);
-    const unsigned long long dst = (unsigned long long)bt_keepv[blockIdx.x] + cc_block_rank(keep, s_w);
+    const unsigned long long dst = (unsigned long long)bt_keepv[blockIdx.x] + block_flag_rank<CC_CHUNK / 64>(keep, s_w);
     if (v < nv) new_id[v] = (keep && dst < cap) ? (int)dst : -1;
     if (keep && dst < cap) {
         out_v[3 * dst] = vertices[3 * v];
@@ -391,7 +336,7 @@ __global__ __launch_bounds__(CC_CHUNK) void cc_compact_faces_kernel(const IdxT *
     const long i = (long)blockIdx.x * CC_CHUNK + threadIdx.x;
     int a = 0, b = 0, c = 0;
     const bool keep = cc_face_kept(r, faces, labels, fcount, i, nf, nv, a, b, c);
-    const unsigned long long dst = (unsigned long long)bt_keepf[blockIdx.x] + cc_block_rank(keep, s_w);
+    const unsigned long long dst = (unsigned long long)bt_keepf[blockIdx.x] + block_flag_rank<CC_CHUNK / 64>(keep, s_w);
     if (keep && dst < cap) {   // (a kept face's three vertices carry its label: all three have a new index)
         out_f[3 * dst] = (IdxT)new_id[a];
         out_f[3 * dst + 1] = (IdxT)new_id[b];
@@ -408,7 +353,7 @@ __global__ __launch_bounds__(CC_CHUNK) void cc_report_kernel(const int *__restri
     __shared__ unsigned s_w[CC_CHUNK / 64];
     const long v = (long)blockIdx.x * CC_CHUNK + threadIdx.x;
     const bool root = v < nv && labels[v] == (int)v;
-    const unsigned long long dst = (unsigned long long)bt_root[blockIdx.x] + cc_block_rank(root, s_w);
+    const unsigned long long dst = (unsigned long long)bt_root[blockIdx.x] + block_flag_rank<CC_CHUNK / 64>(root, s_w);
     if (root && dst < cap) {
         roots[dst] = (int)v;
         face_counts[dst] = (int)fcount[v];

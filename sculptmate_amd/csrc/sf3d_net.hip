@@ -16,6 +16,7 @@
 // All of this is HBM-bound index work: coalesced int32 streams, shuffle-based block scans, no atomics.
 #include <math.h>
 
+#include "block_scan.h"
 #include "common.h"
 
 namespace sculpt {
@@ -187,42 +188,10 @@ __device__ __forceinline__ int tet_index(const float *__restrict__ sdf, const in
     return (sdf[t.x] > 0.f ? 1 : 0) | (sdf[t.y] > 0.f ? 2 : 0) | (sdf[t.z] > 0.f ? 4 : 0) | (sdf[t.w] > 0.f ? 8 : 0);
 }
 
-// block-wide sum of a per-thread value (256 threads)
-__device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, unsigned long long *sh) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    unsigned long long s = sh[0] + sh[1] + sh[2] + sh[3];
-    __syncthreads();
-    return s;
-}
-
-// exclusive prefix of a per-thread value over the block (256 threads); returns prefix, *total = block sum
-__device__ __forceinline__ unsigned long long block_excl_u64(unsigned long long v, unsigned long long *sh,
-                                                             unsigned long long *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    unsigned long long inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        unsigned long long t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    unsigned long long base = 0, tot = 0;
-    for (int i = 0; i < 4; ++i) {
-        if (i < w) base += sh[i];
-        tot += sh[i];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
 // pass 1: per block counts.  edges: crossing flags (low word).  tets: ones (low 32) | twos (high 32).
 __global__ __launch_bounds__(MT_BLOCK) void mtet_count_edges_kernel(const float *__restrict__ sdf, const int2 *__restrict__ edges,
                                                                     long ne, unsigned long long *__restrict__ bsum) {
-    __shared__ unsigned long long sh[4];
+    __shared__ unsigned long long sh[MT_BLOCK / 64];
     const long base = (long)blockIdx.x * MT_TILE;
     unsigned long long c = 0;
 #pragma unroll
@@ -233,13 +202,13 @@ __global__ __launch_bounds__(MT_BLOCK) void mtet_count_edges_kernel(const float 
             c += ((sdf[ab.x] > 0.f) != (sdf[ab.y] > 0.f)) ? 1 : 0;
         }
     }
-    c = block_sum_u64(c, sh);
+    c = block_sum<MT_BLOCK / 64>(c, sh);
     if (threadIdx.x == 0) bsum[blockIdx.x] = c;
 }
 
 __global__ __launch_bounds__(MT_BLOCK) void mtet_count_tets_kernel(const float *__restrict__ sdf, const int4 *__restrict__ tets,
                                                                    long nt, unsigned long long *__restrict__ bsum) {
-    __shared__ unsigned long long sh[4];
+    __shared__ unsigned long long sh[MT_BLOCK / 64];
     const long base = (long)blockIdx.x * MT_TILE;
     unsigned long long c = 0;
 #pragma unroll
@@ -250,7 +219,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mtet_count_tets_kernel(const float *
             c += (n == 1) ? 1ull : (n == 2 ? (1ull << 32) : 0ull);
         }
     }
-    c = block_sum_u64(c, sh);
+    c = block_sum<MT_BLOCK / 64>(c, sh);
     if (threadIdx.x == 0) bsum[blockIdx.x] = c;
 }
 
@@ -258,27 +227,13 @@ __global__ __launch_bounds__(MT_BLOCK) void mtet_count_tets_kernel(const float *
 __global__ __launch_bounds__(MT_BLOCK) void mtet_scan_blocks_kernel(unsigned long long *__restrict__ ebs, int neb,
                                                                     unsigned long long *__restrict__ tbs, int ntb,
                                                                     MtHeader *__restrict__ hd) {
-    __shared__ unsigned long long sh[4];
-    for (int which = 0; which < 2; ++which) {
-        unsigned long long *a = which ? tbs : ebs;
-        const int n = which ? ntb : neb;
-        unsigned long long carry = 0;  // packed halves never overflow: counts < 2^31
-        for (int b0 = 0; b0 < n; b0 += MT_BLOCK) {
-            const int i = b0 + threadIdx.x;
-            const unsigned long long v = i < n ? a[i] : 0ull;
-            unsigned long long tot;
-            const unsigned long long ex = block_excl_u64(v, sh, &tot);
-            if (i < n) a[i] = carry + ex;
-            carry += tot;
-        }
-        if (threadIdx.x == 0) {
-            if (which) {
-                hd->n_ones = (long long)(carry & 0xffffffffull);
-                hd->n_twos = (long long)(carry >> 32);
-            } else {
-                hd->n_verts = (long long)carry;
-            }
-        }
+    __shared__ unsigned long long sh[MT_BLOCK / 64];
+    const unsigned long long nv = block_scan_in_place<MT_BLOCK / 64>(ebs, neb, sh);
+    const unsigned long long nt = block_scan_in_place<MT_BLOCK / 64>(tbs, ntb, sh);  // packed halves never overflow: counts < 2^31
+    if (threadIdx.x == 0) {
+        hd->n_verts = (long long)nv;
+        hd->n_ones = (long long)(nt & 0xffffffffull);
+        hd->n_twos = (long long)(nt >> 32);
     }
 }
 
@@ -289,7 +244,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mtet_emit_verts_kernel(const float *
                                                                    const unsigned long long *__restrict__ bofs,
                                                                    float vmul, float vadd, int *__restrict__ edge_vid,
                                                                    float *__restrict__ verts) {
-    __shared__ unsigned long long sh[4];
+    __shared__ unsigned long long sh[MT_BLOCK / 64];
     const long base = (long)blockIdx.x * MT_TILE + (long)threadIdx.x * MT_ITEMS;
     int2 ab[MT_ITEMS];
     unsigned flags = 0, cnt = 0;
@@ -305,7 +260,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mtet_emit_verts_kernel(const float *
         }
     }
     unsigned long long tot;
-    long id = (long)(bofs[blockIdx.x] + block_excl_u64(cnt, sh, &tot));
+    long id = (long)(bofs[blockIdx.x] + block_exclusive_add<MT_BLOCK / 64>((unsigned long long)cnt, sh, &tot));
 #pragma unroll
     for (int k = 0; k < MT_ITEMS; ++k) {
         const long e = base + k;
@@ -337,7 +292,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mtet_emit_faces_kernel(const float *
                                                                    const int *__restrict__ edge_vid,
                                                                    const unsigned long long *__restrict__ bofs,
                                                                    const MtHeader *__restrict__ hd, long long *__restrict__ faces) {
-    __shared__ unsigned long long sh[4];
+    __shared__ unsigned long long sh[MT_BLOCK / 64];
     const long base = (long)blockIdx.x * MT_TILE + (long)threadIdx.x * MT_ITEMS;
     unsigned char ti[MT_ITEMS];
     unsigned long long cnt = 0;
@@ -352,7 +307,7 @@ __global__ __launch_bounds__(MT_BLOCK) void mtet_emit_faces_kernel(const float *
         }
     }
     unsigned long long tot;
-    const unsigned long long ex = bofs[blockIdx.x] + block_excl_u64(cnt, sh, &tot);
+    const unsigned long long ex = bofs[blockIdx.x] + block_exclusive_add<MT_BLOCK / 64>(cnt, sh, &tot);
     long r1 = (long)(ex & 0xffffffffull), r2 = (long)(ex >> 32);
     const long n_ones = hd->n_ones;
 #pragma unroll

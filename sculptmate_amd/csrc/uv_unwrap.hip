@@ -27,6 +27,7 @@
 
 #include <vector>
 
+#include "block_scan.h"
 #include "common.h"
 #include "fixsum.h"
 
@@ -49,12 +50,6 @@ __device__ __forceinline__ float rn_mul(float a, float b) { return a * b; }
 __device__ __forceinline__ float rn_sqrt(float x) { return (float)sqrt((double)x); }
 
 constexpr int UVB = 256;
-
-__device__ __forceinline__ unsigned uv_f2ord(float f) {
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float uv_ord2f(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
 
 // words of the per-call statistics block (32-bit each)
 enum : int {
@@ -80,8 +75,8 @@ __global__ void uv_stats_init_kernel(unsigned *st) {
     const bool is_max = (i >= ST_BBOX_MAX && i < ST_BBOX_MAX + 3) || (i >= ST_DIV && i < ST_DIV + 3) ||
                         (i >= ST_CH_MAX && i < ST_CH_MAX + 6) || (i >= ST_SL_UMAX && i < ST_SL_UMAX + 6) ||
                         (i >= ST_SL_VMAX && i < ST_SL_VMAX + 6);
-    if (is_min) v = uv_f2ord(FLT_MAX);
-    if (is_max) v = uv_f2ord(-FLT_MAX);
+    if (is_min) v = f32_to_ordered(FLT_MAX);
+    if (is_max) v = f32_to_ordered(-FLT_MAX);
     st[i] = v;
 }
 
@@ -161,8 +156,8 @@ __global__ __launch_bounds__(UVB) void uv_rotate_mesh_kernel(const float *__rest
         }
         if ((threadIdx.x & 63) == 0) {
             const volatile unsigned *sv = st;
-            if (uv_f2ord(a) < sv[ST_BBOX_MIN + r]) atomicMin(&st[ST_BBOX_MIN + r], uv_f2ord(a));
-            if (uv_f2ord(b) > sv[ST_BBOX_MAX + r]) atomicMax(&st[ST_BBOX_MAX + r], uv_f2ord(b));
+            if (f32_to_ordered(a) < sv[ST_BBOX_MIN + r]) atomicMin(&st[ST_BBOX_MIN + r], f32_to_ordered(a));
+            if (f32_to_ordered(b) > sv[ST_BBOX_MAX + r]) atomicMax(&st[ST_BBOX_MAX + r], f32_to_ordered(b));
         }
     }
 }
@@ -178,7 +173,7 @@ __global__ __launch_bounds__(UVB) void uv_box_project_kernel(const float *__rest
                                                              int *__restrict__ chart, unsigned *__restrict__ st) {
     float lo[3], hi[3];
 #pragma unroll
-    for (int r = 0; r < 3; ++r) { lo[r] = uv_ord2f(st[ST_BBOX_MIN + r]); hi[r] = uv_ord2f(st[ST_BBOX_MAX + r]); }
+    for (int r = 0; r < 3; ++r) { lo[r] = ordered_to_f32(st[ST_BBOX_MIN + r]); hi[r] = ordered_to_f32(st[ST_BBOX_MAX + r]); }
     float dmax[3] = {0.f, 0.f, 0.f};
     for (long f = (long)blockIdx.x * blockDim.x + threadIdx.x; f < nf; f += (long)gridDim.x * blockDim.x) {
         int vi[3];
@@ -217,12 +212,12 @@ __global__ __launch_bounds__(UVB) void uv_box_project_kernel(const float *__rest
         float a = dmax[k];
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) a = fmaxf(a, __shfl_xor(a, d, 64));
-        if ((threadIdx.x & 63) == 0) atomicMax(&st[ST_DIV + k], uv_f2ord(a));
+        if ((threadIdx.x & 63) == 0) atomicMax(&st[ST_DIV + k], f32_to_ordered(a));
     }
 }
 
 __global__ __launch_bounds__(UVB) void uv_box_finish_kernel(float *__restrict__ face_uv, long nf, const unsigned *__restrict__ st) {
-    const float div[3] = {uv_ord2f(st[ST_DIV]), uv_ord2f(st[ST_DIV + 1]), uv_ord2f(st[ST_DIV + 2])};
+    const float div[3] = {ordered_to_f32(st[ST_DIV]), ordered_to_f32(st[ST_DIV + 1]), ordered_to_f32(st[ST_DIV + 2])};
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nf * 6; i += (long)gridDim.x * blockDim.x) {
         const int k = (int)((i % 6) >> 1);
         const float x = rn_mul(rn_add(__fdiv_rn(face_uv[i], div[k]), 1.0f), 0.5f);
@@ -386,8 +381,8 @@ __global__ __launch_bounds__(UVB) void uv_rotate_chart_kernel(float *__restrict_
         }
         if ((threadIdx.x & 63) == 0 && a <= b) {
             const volatile unsigned *sv = st;
-            if (uv_f2ord(a) < sv[ST_CH_MIN + c]) atomicMin(&st[ST_CH_MIN + c], uv_f2ord(a));
-            if (uv_f2ord(b) > sv[ST_CH_MAX + c]) atomicMax(&st[ST_CH_MAX + c], uv_f2ord(b));
+            if (f32_to_ordered(a) < sv[ST_CH_MIN + c]) atomicMin(&st[ST_CH_MIN + c], f32_to_ordered(a));
+            if (f32_to_ordered(b) > sv[ST_CH_MAX + c]) atomicMax(&st[ST_CH_MAX + c], f32_to_ordered(b));
         }
     }
 }
@@ -396,7 +391,7 @@ __global__ __launch_bounds__(UVB) void uv_rescale_chart_kernel(float *__restrict
                                                                const unsigned *__restrict__ st) {
     for (long f = (long)blockIdx.x * blockDim.x + threadIdx.x; f < nf; f += (long)gridDim.x * blockDim.x) {
         const int c = chart[f] % 6;
-        const float lo = uv_ord2f(st[ST_CH_MIN + c]), hi = uv_ord2f(st[ST_CH_MAX + c]);
+        const float lo = ordered_to_f32(st[ST_CH_MIN + c]), hi = ordered_to_f32(st[ST_CH_MAX + c]);
         const float span = rn_sub(hi, lo);
 #pragma unroll
         for (int k = 0; k < 6; ++k) face_uv[6 * f + k] = __fdiv_rn(rn_sub(face_uv[6 * f + k], lo), span);
@@ -441,7 +436,7 @@ __device__ __forceinline__ bool inside_strict(const TriRaster &r, float px, floa
 }
 
 __device__ __forceinline__ unsigned long long zkey(float depth, long f) {
-    return ((unsigned long long)uv_f2ord(depth) << 32) | (unsigned long long)(0xffffffffu - (unsigned)f);  // ties: lowest id wins
+    return ((unsigned long long)f32_to_ordered(depth) << 32) | (unsigned long long)(0xffffffffu - (unsigned)f);  // ties: lowest id wins
 }
 
 // PASS 0: draw the triangles of level `level` (assigned / 6 == level) into their chart's z-buffer.
@@ -526,7 +521,7 @@ __global__ __launch_bounds__(UVB) void uv_slice_stats_kernel(const float *__rest
             if ((threadIdx.x & 63) == 0) {
                 // ... and only when the wave's bound improves on what is already there (a plain load: the bounds settle
                 // after the first few thousand faces, the remaining same-address atomics would still serialise in L2)
-                const unsigned o0 = uv_f2ord(a0), o1 = uv_f2ord(a1), p0 = uv_f2ord(b0), p1 = uv_f2ord(b1);
+                const unsigned o0 = f32_to_ordered(a0), o1 = f32_to_ordered(a1), p0 = f32_to_ordered(b0), p1 = f32_to_ordered(b1);
                 const volatile unsigned *sv = st;
                 if (o0 < sv[ST_SL_UMIN + c]) atomicMin(&st[ST_SL_UMIN + c], o0);
                 if (o1 > sv[ST_SL_UMAX + c]) atomicMax(&st[ST_SL_UMAX + c], o1);
@@ -535,43 +530,16 @@ __global__ __launch_bounds__(UVB) void uv_slice_stats_kernel(const float *__rest
             }
         }
     }
-    __shared__ int wc[UVB / 64];
-    const unsigned long long bal = __ballot(rem);
-    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < UVB / 64; ++w) t += wc[w];
-        block_cnt[blockIdx.x] = t;
-    }
+    __shared__ unsigned wc[UVB / 64];
+    const unsigned t = block_flag_count<UVB / 64>(rem, wc);
+    if (threadIdx.x == 0) block_cnt[blockIdx.x] = (int)t;
 }
 
 // exclusive scan of block_cnt in place (one workgroup), total -> st[ST_REMAINING]
 __global__ __launch_bounds__(1024) void uv_scan_blocks_kernel(int *__restrict__ block_cnt, int nb, unsigned *__restrict__ st) {
     __shared__ int wsum[16];
-    __shared__ int carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int base = 0; base < nb; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int v = i < nb ? block_cnt[i] : 0;
-        int x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if ((threadIdx.x & 63) >= d) x += y;
-        }
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = x;
-        __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) woff += wsum[w];
-        const int carry = carry_s;
-        if (i < nb) block_cnt[i] = carry + woff + x - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = carry + woff + x;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) st[ST_REMAINING] = (unsigned)carry_s;
+    const int total = block_scan_in_place<16>(block_cnt, nb, wsum);
+    if (threadIdx.x == 0) st[ST_REMAINING] = (unsigned)total;
 }
 
 __device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
@@ -583,20 +551,15 @@ __global__ __launch_bounds__(UVB) void uv_place_kernel(const float *__restrict__
     const int a = f < nf ? assigned[f] : 0;
     const bool rem = f < nf && a >= 12;
     // rank of this face among the remaining ones, in face order
-    __shared__ int wc[UVB / 64];
-    const unsigned long long bal = __ballot(rem);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wc[wave] = __popcll(bal);
-    __syncthreads();
-    int rank = block_off[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) rank += wc[w];
+    __shared__ unsigned wc[UVB / 64];
+    const int rank = block_off[blockIdx.x] + (int)block_flag_rank<UVB / 64>(rem, wc);
     if (f >= nf) return;
     float uc[3], vc[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { uc[k] = face_uv[6 * f + 2 * k]; vc[k] = face_uv[6 * f + 2 * k + 1]; }
     if (a >= 6 && a < 12) {  // _handle_slice_uvs: fill the patch, at most 2x magnified
-        const float ulo = uv_ord2f(st[ST_SL_UMIN + a - 6]), uhi = uv_ord2f(st[ST_SL_UMAX + a - 6]);
-        const float vlo = uv_ord2f(st[ST_SL_VMIN + a - 6]), vhi = uv_ord2f(st[ST_SL_VMAX + a - 6]);
+        const float ulo = ordered_to_f32(st[ST_SL_UMIN + a - 6]), uhi = ordered_to_f32(st[ST_SL_UMAX + a - 6]);
+        const float vlo = ordered_to_f32(st[ST_SL_VMIN + a - 6]), vhi = ordered_to_f32(st[ST_SL_VMAX + a - 6]);
         const float us = fmaxf(rn_sub(uhi, ulo), 0.5f), vs = fmaxf(rn_sub(vhi, vlo), 0.5f);
 #pragma unroll
         for (int k = 0; k < 3; ++k) { uc[k] = __fdiv_rn(rn_sub(uc[k], ulo), us); vc[k] = __fdiv_rn(rn_sub(vc[k], vlo), vs); }

@@ -515,11 +515,12 @@ def test_workspace_footprint(cuda):
     assert _lib.lib.sculpt_mc_workspace_bytes(512, 512, 512) <= 0.8 * 2 ** 30
 
 
-@pytest.mark.parametrize("shape,seed", [((6, 7, 300), 21), ((5, 300, 9), 22), ((40, 3, 520), 23)])
+@pytest.mark.parametrize("shape,seed", [((6, 7, 300), 21), ((5, 300, 9), 22), ((40, 3, 520), 23), ((1100, 1100, 2), 24)])
 def test_vertex_ids_across_row_segments_and_on_the_low_faces(cuda, shape, seed):
     """Vertex ids come from the OWNER cell's record (a neighbour at offset {0,-1}^3, found through the row's active mask): rows
     longer than one 256-cell segment (the owner may sit in the previous segment), thin volumes where every cell lies on a low
-    face (the rank walk instead of the two record bits), noise (every Lewiner case)."""
+    face (the rank walk instead of the two record bits), noise (every Lewiner case).  The last shape has 1099 x 1099 one-cell
+    rows: 1,207,801 row blocks in 1180 groups, so the scan of the group totals (mc_scan2_kernel) takes a second trip."""
     from sculptmate_amd import ops
 
     vol = np.random.default_rng(seed).standard_normal(shape).astype(np.float32)
