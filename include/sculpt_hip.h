@@ -53,7 +53,7 @@ extern "C" {
  * 4: the two-pass grid's guard: 12 statistics words instead of 8 (sculpt_density_filter_stats fills SCULPT_FILTER_STATS_WORDS),
  *    word 1 covers every re-evaluated point, the audit sample and the sign mismatches are new; the marching-cubes workspace
  *    is a record pool with a capacity (SCULPT_ERR_MC_WORKSPACE, sculpt_mc_workspace_bytes_for, sculpt_mc_count_launch_for,
- *    sculpt_mc_count_read_ex) */
+ *    sculpt_mc_count_read_ex); added without a version change (new symbol only): sculpt_gemm_last_form */
 #define SCULPT_ABI_VERSION 4
 
 typedef void *sculpt_stream_t;
@@ -450,6 +450,14 @@ int sculpt_gemm_bf16_ln(const uint16_t *A, int lda, const uint16_t *W, int ldw, 
                         const float *residual, int ldr, float *out_f32, uint16_t *out_bf16, int ldo,
                         uint16_t *out_bf16_t, int ldt, int n_split, int n_store, int M, int N, int K, int epilogue,
                         const sculpt_ln_fold_t *ln /* or NULL */, sculpt_stream_t stream);
+/* Which tile form the calling thread's last sculpt_gemm_bf16* / sculpt_conv3x3_bf16 launch took, e.g.
+ *   "g128 epi=0 bw=64 nw=8 bm=192 ks=1 res=0 conv=0 gm=0 nmaj=0 stage=0 grid=16x16"   ("none" before the first launch)
+ * g128 / g256: the kernel family (gemm_bf16_kernel / gemm256_kernel); epi: SCULPT_EPI_*; bw / bm: weight / activation rows per
+ * workgroup; nw: waves; ks: k-split pairs; res: the residual form of the 256 family; conv: implicit 3x3 convolution; gm: rows of
+ * the grouped tile order (0 = band order); nmaj: weight-tile-major bands; stage: staged bf16 stores; grid: workgroups x, y.
+ * The launchers only fill a thread-local struct of ints; the text is formatted here, into a thread-local buffer that the next
+ * call on the same thread overwrites.  For tests of the dispatch rules and for A/B tools; never fails. */
+const char *sculpt_gemm_last_form(void);
 /* (mean, M2) of every 64-column slice of x [rows][cols] fp32 -> stats [cols/64][stats_ld][2], and the bf16 copy of x: the
  * producer side of the fold for rows that do not come out of a GEMM (the ViT's embedding output). cols % 64 == 0. */
 int sculpt_row_slice_stats(const float *x, int ldx, int rows, int cols, float *stats, int stats_ld, uint16_t *x_bf16, int ldb,

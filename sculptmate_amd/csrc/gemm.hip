@@ -1075,6 +1075,28 @@ extern "C" int sculpt_gemm_bf16(const uint16_t *A, int lda, const uint16_t *W, i
                                epilogue, stream);
 }
 
+// The tile form of this thread's last bf16 GEMM / implicit-convolution launch: plain ints filled just before the launch (no
+// formatting on the launch path), formatted on request by sculpt_gemm_last_form -- what the tests of the dispatch rules read.
+struct GemmForm {
+    int family;  // 0: nothing launched yet, 128: gemm_bf16_kernel, 256: gemm256_kernel
+    int epi, bw, nw, bm, ks, res, conv;  // the template arguments (bw = weight rows per workgroup)
+    int gm, n_major, stage;              // of the GemmArgs
+    int grid_x, grid_y;
+};
+static thread_local GemmForm t_gemm_form = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static inline void note_form(int family, int epi, int bw, int nw, int bm, bool ks, bool res, bool conv, const GemmArgs &g, dim3 grid) {
+    t_gemm_form = GemmForm{family, epi, bw, nw, bm, ks ? 1 : 0, res ? 1 : 0, conv ? 1 : 0, g.gm, g.n_major, g.stage, (int)grid.x, (int)grid.y};
+}
+
+extern "C" const char *sculpt_gemm_last_form(void) {
+    static thread_local char buf[160];
+    const GemmForm &f = t_gemm_form;
+    if (!f.family) return "none";
+    snprintf(buf, sizeof buf, "g%d epi=%d bw=%d nw=%d bm=%d ks=%d res=%d conv=%d gm=%d nmaj=%d stage=%d grid=%dx%d", f.family, f.epi,
+             f.bw, f.nw, f.bm, f.ks, f.res, f.conv, f.gm, f.n_major, f.stage, f.grid_x, f.grid_y);
+    return buf;
+}
+
 static constexpr long ZERO_FLOATS = 65536;  // a missing bias / colsum vector reads from here: N (GEGLU: 2N) <= 65536
 static const uint16_t *zero_page() {
     // 256 KiB of zeros per device: the out-of-image taps of the implicit convolution and the stand-in for a missing per-column
@@ -1121,11 +1143,21 @@ extern "C" int sculpt_conv3x3_bf16(const uint16_t *in, int ld_in, int n_images, 
     hipStream_t st = as_stream(stream);
     const bool small = (long)(N / 128) * mt < (long)num_cus() * 3 / 2;
     if (epilogue == SCULPT_EPI_RELU) {
-        if (small) hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_RELU, 64, 8, true>), dim3(N / 64, mt), dim3(512), 0, st, g);
-        else hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_RELU, 128, 8, true>), dim3(N / 128, mt), dim3(512), 0, st, g);
+        if (small) {
+            note_form(128, SCULPT_EPI_RELU, 64, 8, BM_DEFAULT, false, false, true, g, dim3(N / 64, mt));
+            hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_RELU, 64, 8, true>), dim3(N / 64, mt), dim3(512), 0, st, g);
+        } else {
+            note_form(128, SCULPT_EPI_RELU, 128, 8, BM_DEFAULT, false, false, true, g, dim3(N / 128, mt));
+            hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_RELU, 128, 8, true>), dim3(N / 128, mt), dim3(512), 0, st, g);
+        }
     } else {
-        if (small) hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 64, 8, true>), dim3(N / 64, mt), dim3(512), 0, st, g);
-        else hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 128, 8, true>), dim3(N / 128, mt), dim3(512), 0, st, g);
+        if (small) {
+            note_form(128, SCULPT_EPI_NONE, 64, 8, BM_DEFAULT, false, false, true, g, dim3(N / 64, mt));
+            hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 64, 8, true>), dim3(N / 64, mt), dim3(512), 0, st, g);
+        } else {
+            note_form(128, SCULPT_EPI_NONE, 128, 8, BM_DEFAULT, false, false, true, g, dim3(N / 128, mt));
+            hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 128, 8, true>), dim3(N / 128, mt), dim3(512), 0, st, g);
+        }
     }
     SC_LAUNCH_CHECK();
     return 0;
@@ -1239,6 +1271,7 @@ extern "C" int sculpt_gemm_bf16_ln(const uint16_t *A, int lda, const uint16_t *W
             if (legal && (fres >= 0 ? fres != 0 : pays_res)) {
                 const dim3 grid(N / 256, cdiv(M, 192));
                 g.gm = group_rows(256, 192, 1, (long)grid.x * grid.y, grid.y);
+                note_form(256, SCULPT_EPI_NONE, 256, 8, 192, false, true, false, g, grid);
                 hipLaunchKernelGGL((gemm256_kernel<SCULPT_EPI_NONE, 192, true>), grid, dim3(512), 0, st, g);
                 SC_LAUNCH_CHECK();
                 return 0;
@@ -1261,10 +1294,15 @@ extern "C" int sculpt_gemm_bf16_ln(const uint16_t *A, int lda, const uint16_t *W
                           (!split || (n_split % nout == 0 && ldt % 8 == 0 && ((uintptr_t)out_bf16_t & 15) == 0)) &&
                           ldo % 8 == 0 && ((uintptr_t)out_bf16 & 15) == 0;
             }
-#define SCULPT_G256(E)                                                                                     \
-    do {                                                                                                   \
-        if (bm192) hipLaunchKernelGGL((gemm256_kernel<E, 192>), grid, dim3(512), 0, st, g);                \
-        else hipLaunchKernelGGL((gemm256_kernel<E, 256>), grid, dim3(512), 0, st, g);                      \
+#define SCULPT_G256(E)                                                               \
+    do {                                                                             \
+        if (bm192) {                                                                 \
+            note_form(256, E, 256, 8, 192, false, false, false, g, grid);            \
+            hipLaunchKernelGGL((gemm256_kernel<E, 192>), grid, dim3(512), 0, st, g); \
+        } else {                                                                     \
+            note_form(256, E, 256, 8, 256, false, false, false, g, grid);            \
+            hipLaunchKernelGGL((gemm256_kernel<E, 256>), grid, dim3(512), 0, st, g); \
+        }                                                                            \
     } while (0)
             if (epilogue == SCULPT_EPI_GEGLU) SCULPT_G256(SCULPT_EPI_GEGLU);
             else if (epilogue == SCULPT_EPI_GELU) SCULPT_G256(SCULPT_EPI_GELU);
@@ -1284,8 +1322,13 @@ extern "C" int sculpt_gemm_bf16_ln(const uint16_t *A, int lda, const uint16_t *W
         SC_REQUIRE(N % 64 == 0, "gemm_bf16(GEGLU): N=%d must be a multiple of 64", N);
         SC_REQUIRE(!residual && !out_bf16_t, "gemm_bf16(GEGLU): residual/transposed output unsupported");
         g.gm = group_rows(128, BM_DEFAULT, 2, (long)(N / 64) * mt, mt);
-        if (nw8) hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_GEGLU, 128, 8>), dim3(N / 64, mt), dim3(512), 0, st, g);
-        else hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_GEGLU, 128, 4>), dim3(N / 64, mt), dim3(256), 0, st, g);
+        if (nw8) {
+            note_form(128, SCULPT_EPI_GEGLU, 128, 8, BM_DEFAULT, false, false, false, g, dim3(N / 64, mt));
+            hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_GEGLU, 128, 8>), dim3(N / 64, mt), dim3(512), 0, st, g);
+        } else {
+            note_form(128, SCULPT_EPI_GEGLU, 128, 4, BM_DEFAULT, false, false, false, g, dim3(N / 64, mt));
+            hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_GEGLU, 128, 4>), dim3(N / 64, mt), dim3(256), 0, st, g);
+        }
     } else {
         SC_REQUIRE(N % 128 == 0, "gemm_bf16: N=%d must be a multiple of 128", N);
         // fill the chip: with fewer than ~1.5 tiles per CU use the 64-row weight tile
@@ -1294,15 +1337,33 @@ extern "C" int sculpt_gemm_bf16_ln(const uint16_t *A, int lda, const uint16_t *W
         const bool small = (long)(N / 128) * mth < (long)num_cus() * 3 / 2;
         g.gm = small ? group_rows(64, BM_DEFAULT, 2, (long)(N / 64) * mt, mt) : group_rows(128, BM_DEFAULT, 2, (long)(N / 128) * mt, mt);
         if (epilogue == SCULPT_EPI_GELU) {
-            if (small && nw8s) hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_GELU, 64, 8>), dim3(N / 64, mt), dim3(512), 0, st, g);
-            else if (small) hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_GELU, 64, 4>), dim3(N / 64, mt), dim3(256), 0, st, g);
-            else if (nw8) hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_GELU, 128, 8>), dim3(N / 128, mt), dim3(512), 0, st, g);
-            else hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_GELU, 128, 4>), dim3(N / 128, mt), dim3(256), 0, st, g);
+            if (small && nw8s) {
+                note_form(128, SCULPT_EPI_GELU, 64, 8, BM_DEFAULT, false, false, false, g, dim3(N / 64, mt));
+                hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_GELU, 64, 8>), dim3(N / 64, mt), dim3(512), 0, st, g);
+            } else if (small) {
+                note_form(128, SCULPT_EPI_GELU, 64, 4, BM_DEFAULT, false, false, false, g, dim3(N / 64, mt));
+                hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_GELU, 64, 4>), dim3(N / 64, mt), dim3(256), 0, st, g);
+            } else if (nw8) {
+                note_form(128, SCULPT_EPI_GELU, 128, 8, BM_DEFAULT, false, false, false, g, dim3(N / 128, mt));
+                hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_GELU, 128, 8>), dim3(N / 128, mt), dim3(512), 0, st, g);
+            } else {
+                note_form(128, SCULPT_EPI_GELU, 128, 4, BM_DEFAULT, false, false, false, g, dim3(N / 128, mt));
+                hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_GELU, 128, 4>), dim3(N / 128, mt), dim3(256), 0, st, g);
+            }
         } else if (epilogue == SCULPT_EPI_RELU) {
-            if (small && nw8s) hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_RELU, 64, 8>), dim3(N / 64, mt), dim3(512), 0, st, g);
-            else if (small) hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_RELU, 64, 4>), dim3(N / 64, mt), dim3(256), 0, st, g);
-            else if (nw8) hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_RELU, 128, 8>), dim3(N / 128, mt), dim3(512), 0, st, g);
-            else hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_RELU, 128, 4>), dim3(N / 128, mt), dim3(256), 0, st, g);
+            if (small && nw8s) {
+                note_form(128, SCULPT_EPI_RELU, 64, 8, BM_DEFAULT, false, false, false, g, dim3(N / 64, mt));
+                hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_RELU, 64, 8>), dim3(N / 64, mt), dim3(512), 0, st, g);
+            } else if (small) {
+                note_form(128, SCULPT_EPI_RELU, 64, 4, BM_DEFAULT, false, false, false, g, dim3(N / 64, mt));
+                hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_RELU, 64, 4>), dim3(N / 64, mt), dim3(256), 0, st, g);
+            } else if (nw8) {
+                note_form(128, SCULPT_EPI_RELU, 128, 8, BM_DEFAULT, false, false, false, g, dim3(N / 128, mt));
+                hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_RELU, 128, 8>), dim3(N / 128, mt), dim3(512), 0, st, g);
+            } else {
+                note_form(128, SCULPT_EPI_RELU, 128, 4, BM_DEFAULT, false, false, false, g, dim3(N / 128, mt));
+                hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_RELU, 128, 4>), dim3(N / 128, mt), dim3(256), 0, st, g);
+            }
         } else if (epilogue == SCULPT_EPI_NONE) {
             // Fewer tiles than CUs: every workgroup has a CU to itself and its K loop runs at that CU's L2 -> LDS fill rate
             // (~57 GB/s, whatever the ring depth or the number of barriers: a six-stage ring and two K-tiles per barrier both
@@ -1320,17 +1381,30 @@ extern "C" int sculpt_gemm_bf16_ln(const uint16_t *A, int lda, const uint16_t *W
                 g.gm = 0;
                 // k-split pairs (see the kernel): FF2 + residual 41.6 -> 38.4 us, plain K = 4096 37.5 -> 33.9, K = 1024 -0.3 us;
                 // ks0: the weight-row split, bit-identical to the 128 x 64 tiles (A/B, tests)
-                if (!form_has(FORM, "ks0"))
+                if (!form_has(FORM, "ks0")) {
+                    note_form(128, SCULPT_EPI_NONE, 64, 8, 192, true, false, false, g, dim3(N / 64, M / 192));
                     hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 64, 8, false, 192, 2, true>), dim3(N / 64, M / 192), dim3(512), 0, st, g);
-                else
+                } else {
+                    note_form(128, SCULPT_EPI_NONE, 64, 8, 192, false, false, false, g, dim3(N / 64, M / 192));
                     hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 64, 8, false, 192>), dim3(N / 64, M / 192), dim3(512), 0, st, g);
+                }
             } else
-            if (small && underfilled && (long)(N / 64) * cdiv(Mh, 64) <= 2L * num_cus())
+            if (small && underfilled && (long)(N / 64) * cdiv(Mh, 64) <= 2L * num_cus()) {
+                note_form(128, SCULPT_EPI_NONE, 64, 8, 64, false, false, false, g, dim3(N / 64, cdiv(M, 64)));
                 hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 64, 8, false, 64>), dim3(N / 64, cdiv(M, 64)), dim3(512), 0, st, g);
-            else if (small && nw8s) hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 64, 8>), dim3(N / 64, mt), dim3(512), 0, st, g);
-            else if (small) hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 64, 4>), dim3(N / 64, mt), dim3(256), 0, st, g);
-            else if (nw8) hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 128, 8>), dim3(N / 128, mt), dim3(512), 0, st, g);
-            else hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 128, 4>), dim3(N / 128, mt), dim3(256), 0, st, g);
+            } else if (small && nw8s) {
+                note_form(128, SCULPT_EPI_NONE, 64, 8, BM_DEFAULT, false, false, false, g, dim3(N / 64, mt));
+                hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 64, 8>), dim3(N / 64, mt), dim3(512), 0, st, g);
+            } else if (small) {
+                note_form(128, SCULPT_EPI_NONE, 64, 4, BM_DEFAULT, false, false, false, g, dim3(N / 64, mt));
+                hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 64, 4>), dim3(N / 64, mt), dim3(256), 0, st, g);
+            } else if (nw8) {
+                note_form(128, SCULPT_EPI_NONE, 128, 8, BM_DEFAULT, false, false, false, g, dim3(N / 128, mt));
+                hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 128, 8>), dim3(N / 128, mt), dim3(512), 0, st, g);
+            } else {
+                note_form(128, SCULPT_EPI_NONE, 128, 4, BM_DEFAULT, false, false, false, g, dim3(N / 128, mt));
+                hipLaunchKernelGGL((gemm_bf16_kernel<SCULPT_EPI_NONE, 128, 4>), dim3(N / 128, mt), dim3(256), 0, st, g);
+            }
         } else {
             SC_REQUIRE(false, "gemm_bf16: unknown epilogue %d", epilogue);
         }

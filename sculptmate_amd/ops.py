@@ -664,6 +664,20 @@ def gemm(A, W, bias=None, residual=None, out_f32=None, out_bf16=None, out_t=None
                                   epilogue, ctypes.byref(ln) if ln is not None else None, _stream()))
 
 
+def gemm_last_form():
+    """The tile form of this thread's last bf16 GEMM / implicit-convolution launch (sculpt_gemm_last_form) as a dict:
+    family ("g128" / "g256"), epi, bw, nw, bm, ks, res, conv, gm, nmaj, stage, grid (x, y), text; {} before the first launch."""
+    text = (lib.sculpt_gemm_last_form() or b"none").decode()
+    if text == "none":
+        return {}
+    words = text.split()
+    form = {"family": words[0], "text": text}
+    for w in words[1:]:
+        k, v = w.split("=")
+        form[k] = tuple(int(x) for x in v.split("x")) if k == "grid" else int(v)
+    return form
+
+
 class _TileRows(threading.local):
     def __init__(self):
         self.v = 0
