@@ -959,6 +959,30 @@ int sculpt_rmd_qem_claim(const sculpt_rmd_topo_t *topo, const unsigned long long
 int sculpt_rmd_qem_apply(const sculpt_rmd_topo_t *topo, float *P, int32_t *F, double *Q, const float *target, const int32_t *win,
                          uint8_t *face_alive, sculpt_stream_t stream);
 
+/* Mesh smoothing ON THE DEVICE: Taubin's lambda|mu filter (csrc/mesh_smooth.hip; sf3d/remesh_device.py smooth_device,
+ * ops.mesh_smooth).  The faces do not change; the positions do.  DEVICE pointers, asynchronous on `stream`, no host wait.
+ * Compiled without floating-point contraction: every position is a fixed sequence of IEEE fp32 operations (restated in
+ * tests/_smoothref.py).  The neighbour table is built once per call from a topology (sculpt_rmd_topo_t):
+ *   sculpt_smooth_edge_keys    keys[2 e] = (u << 32 | v), keys[2 e + 1] = (v << 32 | u) for every edge e = {u, v} of the topology;
+ *                              keys [2 ne].  (caller: sort the keys -- they are distinct, so the order is unique -- and
+ *                              start[u] = the first sorted index with key >= u << 32, [nv + 1])
+ *   sculpt_smooth_neighbours   nb[i] = the low 32 bits of skeys[i]: row u of the CSR (start, nb) holds the distinct neighbours
+ *                              of u in ascending order
+ *   sculpt_smooth_taubin       `iterations` (1 .. 1000) times: a half-step with factor (float)lam, then one with (float)mu;
+ *                              mu == 0: the first alone (plain Laplacian).  0 < lam <= 1; mu == 0 or -1 <= mu < -lam.
+ *                              A half-step, per vertex u of degree deg = start[u + 1] - start[u], p -> q:
+ *                                  s = p[nb[start[u]]], then s = s + p[nb[j]] for the rest of the row in order
+ *                                  q = p + k * (s / (float)deg - p)      (a division, a subtraction, a product, a sum)
+ *                              and q = p where fixed[u] != 0 or deg == 0.  fixed [nv]: sculpt_rmd_boundary on zeroes (an edge at
+ *                              u without exactly two faces).  P [nv][3] in, out [nv][3] (may be P); work_a, work_b: two
+ *                              distinct 16-byte aligned buffers of nv * 4 floats (positions as x y z - rows, read and written
+ *                              in turn).  nb holds n_nb entries, each in [0, nv): the caller's table is trusted, like F.
+ * Null, misaligned or out-of-range arguments are refused with an error code and a message; nv == 0 launches nothing. */
+int sculpt_smooth_edge_keys(const sculpt_rmd_topo_t *topo, int64_t *keys, sculpt_stream_t stream);
+int sculpt_smooth_neighbours(const int64_t *skeys, int64_t n, int32_t *nb, sculpt_stream_t stream);
+int sculpt_smooth_taubin(const int32_t *start, const int32_t *nb, const uint8_t *fixed, int64_t nv, int64_t n_nb, const float *P,
+                         int iterations, double lam, double mu, float *work_a, float *work_b, float *out, sculpt_stream_t stream);
+
 /* Mesh hand-off, HOST side (no GPU work): the face block of a binary little-endian PLY file -- per face `uchar 3` followed by
  * three int32 -- from the int64 faces TSR.run returns (the reference's `t_pos_idx.cpu().numpy()`, TripoSR/tsr/system.py:200).
  * faces_host int64 [n][3] -> records_host uint8 [n][13].  Thread-safe; callers split n over threads (sculptmate_amd/meshio.py). */

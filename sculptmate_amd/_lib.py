@@ -210,6 +210,9 @@ SIGNATURES = {
     "sculpt_rmd_qem_cost": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_rmd_qem_claim": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "sculpt_rmd_qem_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_smooth_edge_keys": (_i, [_vp, _vp, _vp]),
+    "sculpt_smooth_neighbours": (_i, [_vp, _i64, _vp, _vp]),
+    "sculpt_smooth_taubin": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
     "rasterize_cpu": (None, [_vp, _sz, _vp, _sz, ctypes.c_longlong, _vp]),
     "interpolate_cpu": (None, [_vp, _sz, _vp, _sz, _vp, ctypes.c_longlong, _vp]),
 }

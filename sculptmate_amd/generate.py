@@ -34,7 +34,10 @@ class TripoGenerator(GeneratorFacade):
     before it is coloured, baked or handed to Blender (TSR.extract_meshes).
     `simplify` (default None): an int >= 1 (target faces) or a float in (0, 1) (ratio of the faces) reduces every mesh by
     quadric-error edge collapses on the device, after keep_components and before the colours, the bake and the normals
-    (TSR.extract_meshes; ops.mesh_simplify)."""
+    (TSR.extract_meshes; ops.mesh_simplify).
+    `smooth` (default None): an int n in 1 .. 1000 (iterations, lam = 0.5, mu = -0.53) or a tuple (n, lam, mu) smooths every mesh
+    with Taubin's lambda|mu filter on the device, after keep_components and before simplify (TSR.extract_meshes;
+    ops.mesh_smooth)."""
 
     def __init__(self, device):
         super().__init__(device, checkpoint_dir=ROOT_DIR + "/checkpoints/", chunk_size=8192, mc_resolution=256,
@@ -44,6 +47,7 @@ class TripoGenerator(GeneratorFacade):
         self.vertex_normals = None
         self.keep_components = None
         self.simplify = None
+        self.smooth = None
 
     def _construct_model(self):
         model = TSR.from_pretrained(self.checkpoint_dir, config_name="config.yaml", weight_name="model.ckpt",
@@ -61,7 +65,8 @@ class TripoGenerator(GeneratorFacade):
                                                        resolution=self.mc_resolution,
                                                        bake_texture=int(self.bake_texture_resolution or 0),
                                                        normals=self.vertex_normals,
-                                                       keep_components=self.keep_components, simplify=self.simplify)
+                                                       keep_components=self.keep_components, simplify=self.simplify,
+                                                       smooth=self.smooth)
         except Exception as err:
             print(self.run_error_tag, err)
             return STATUS_FAILED

@@ -583,6 +583,17 @@ def simplify_rule(simplify):
     raise ValueError("simplify must be an int >= 1 (target faces) or a float in (0, 1) (ratio of the faces), got %r" % (simplify,))
 
 
+def _device_mesh(vertices, faces, who):
+    """What mesh_simplify and mesh_smooth ask of their tensors: device tensors, float [Nv, 3] and int32 / int64 [Nf, 3]."""
+    for t, name in ((vertices, "vertices"), (faces, "faces")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise SculptError("%s: %s must be a CUDA/HIP tensor (no CPU fallback)" % (who, name))
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.dtype.is_floating_point:
+        raise SculptError("vertices must be float [Nv, 3], got %s %s" % (vertices.dtype, tuple(vertices.shape)))
+    if faces.dtype not in (torch.int32, torch.int64) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise SculptError("faces must be int32 or int64 [Nf, 3], got %s %s" % (faces.dtype, tuple(faces.shape)))
+
+
 def simplify_target(simplify, n_faces):
     """The target face count of `simplify` (simplify_rule) on a mesh of n_faces faces."""
     kind, x = simplify_rule(simplify)
@@ -608,19 +619,66 @@ def mesh_simplify(vertices, faces, simplify):
     simplify_rule(simplify)
     from .sf3d import remesh_device as rmd
 
-    for t, name in ((vertices, "vertices"), (faces, "faces")):   # here too: a target already met returns before simplify_device
-        if not (isinstance(t, torch.Tensor) and t.is_cuda):
-            raise SculptError("mesh_simplify: %s must be a CUDA/HIP tensor (no CPU fallback)" % name)
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.dtype.is_floating_point:
-        raise SculptError("vertices must be float [Nv, 3], got %s %s" % (vertices.dtype, tuple(vertices.shape)))
-    if faces.dtype not in (torch.int32, torch.int64) or faces.dim() != 2 or faces.shape[1] != 3:
-        raise SculptError("faces must be int32 or int64 [Nf, 3], got %s %s" % (faces.dtype, tuple(faces.shape)))
+    _device_mesh(vertices, faces, "mesh_simplify")   # here too: a target already met returns before simplify_device
     nf = faces.shape[0]
     target = simplify_target(simplify, nf)
     if target >= nf:
         return vertices, faces, torch.arange(vertices.shape[0], dtype=torch.int64, device=vertices.device)
     v, f, index = rmd.simplify_device(vertices, faces, target)
     return v, f.to(faces.dtype), index
+
+
+# ----------------------------------------------------------------------------------------------
+# mesh smoothing: Taubin's lambda|mu filter (csrc/mesh_smooth.hip, sf3d/remesh_device.py smooth_device)
+# ----------------------------------------------------------------------------------------------
+SMOOTH_LAMBDA, SMOOTH_MU = 0.5, -0.53   # Taubin's customary pair: a shrink step, then a slightly larger inflate step
+SMOOTH_MAX_ITERATIONS = 1000
+
+
+def smooth_rule(smooth):
+    """`smooth` of mesh_smooth -> (iterations, lam, mu): an int n, 1 <= n <= 1000 (n iterations with lam = 0.5, mu = -0.53), or
+    a 3-tuple (n, lam, mu) with 0 < lam <= 1 and either mu == 0 (plain Laplacian smoothing: it shrinks) or -1 <= mu < -lam
+    (Taubin's pass-band condition).  Anything else -- bool, str, a bare float, NaN, another length -- is a ValueError, raised
+    here, before anything is launched."""
+    import numbers
+
+    def count(n):
+        return (not isinstance(n, (bool, np.bool_)) and isinstance(n, numbers.Integral)
+                and 1 <= int(n) <= SMOOTH_MAX_ITERATIONS)
+
+    def real(x):
+        return not isinstance(x, (bool, np.bool_)) and isinstance(x, numbers.Real)
+
+    if count(smooth):
+        return int(smooth), SMOOTH_LAMBDA, SMOOTH_MU
+    if isinstance(smooth, tuple) and len(smooth) == 3 and count(smooth[0]) and real(smooth[1]) and real(smooth[2]):
+        lam, mu = float(smooth[1]), float(smooth[2])
+        if 0.0 < lam <= 1.0 and (mu == 0.0 or -1.0 <= mu < -lam):   # a NaN fails every comparison
+            return int(smooth[0]), lam, mu
+    raise ValueError("smooth must be an int in 1 .. %d (iterations) or (iterations, lam, mu) with 0 < lam <= 1 and mu == 0 or "
+                     "-1 <= mu < -lam, got %r" % (SMOOTH_MAX_ITERATIONS, smooth))
+
+
+def mesh_smooth(vertices, faces, smooth):
+    """The vertices of the mesh after Taubin's lambda|mu filter, on the device: per iteration every vertex moves by lam towards
+    the centroid of its distinct neighbours, then by mu (negative: away from it) -- a low-pass filter that takes out lattice
+    steps and noise without the shrinkage of plain Laplacian smoothing.  vertices float [Nv, 3], faces int32 / int64 [Nf, 3]
+    (device tensors; CPU tensors are refused); smooth: see smooth_rule.
+    -> vertices' f32 [Nv, 3], a new tensor.  Contract:
+      - the inputs are untouched; vertex and face indices mean what they meant;
+      - a vertex on an edge that does not have exactly two faces (an open border, a non-manifold edge) and a vertex no face
+        names keep their bits; a vertex of any valence is smoothed;
+      - a face index out of range, a repeated index in a face and a non-finite position are a SculptError;
+      - Nf == 0: a copy;
+      - deterministic: a fixed-order gather in fp32 without contraction, two calls give the same bits
+        (tests/_smoothref.py restates it bit for bit);
+      - the host reads back the input check's status and the edge count of the one topology construction; the 2 x iterations
+        half-steps are queued without a wait.  The counts are in sf3d.remesh_device.last_stats()."""
+    n, lam, mu = smooth_rule(smooth)
+    from .sf3d import remesh_device as rmd
+
+    _device_mesh(vertices, faces, "mesh_smooth")
+    return rmd.smooth_device(vertices, faces, n, lam, mu)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@ sculpt_rmd_* in include/sculpt_hip.h), with the contract of the host calls in sf
     subdivide_device(v, f, iters=1) -> (v, f)
     device_remesher(mesh, mode, vertex_count, remesh_steps=10) -> Mesh      the SF3D.remesher hook, opt-in
     simplify_device(v, f, target_faces) -> (v, f, vertex_index)             quadric-error collapse (ops.mesh_simplify)
+    smooth_device(v, f, iterations, lam, mu) -> v                           Taubin lambda|mu smoothing (ops.mesh_smooth)
 
 v and f are HIP tensors (v any float dtype, f any integer dtype); results are float32 [n, 3] / int32 [m, 3] HIP tensors.  CPU
 tensors are refused.  The rules are the host's (csrc/remesh_host.h); its sequential order becomes rounds of independent local
@@ -388,6 +389,47 @@ def simplify_device(v, f, target_faces):
     P, index = _compact_vertices(ctx, P, nv, F, with_index=True)
     ctx.done()
     return P, F, index
+
+
+def _smooth_table(ctx, F, nv):
+    """(start i32 [nv + 1], nb i32 [2 ne], fixed u8 [nv]) of the faces F: row u of the CSR holds the distinct neighbours of u in
+    ascending order; fixed[u] = 1 where an edge at u does not have exactly two faces.  The topology gets a zero `carry`, so the
+    remesher's more-than-64-neighbours feature rule is not applied: a high-valence vertex is smoothed like any other.  The
+    directed keys of the unique edges are distinct, so their sorted order -- and with it the table -- is unique."""
+    dev = F.device
+    T = _Topo(ctx, F, nv, carry=torch.zeros(max(nv, 1), dtype=torch.uint8, device=dev))
+    keys = torch.empty(2 * T.ne, dtype=torch.int64, device=dev)
+    check(lib.sculpt_smooth_edge_keys(T.ref(), _p(keys), ctx.stream))
+    skeys = torch.sort(keys).values
+    start = torch.searchsorted(skeys, torch.arange(nv + 1, dtype=torch.int64, device=dev) << 32, out_int32=True)
+    nb = torch.empty(2 * T.ne, dtype=torch.int32, device=dev)
+    check(lib.sculpt_smooth_neighbours(_p(skeys), 2 * T.ne, _p(nb), ctx.stream))
+    return start, nb, T.bnd[:nv]
+
+
+def _smooth_steps(ctx, P, table, n, lam, mu):
+    """`n` iterations of the two half-steps on P [nv, 3] f32 -> a new tensor; every launch is queued, nothing is read back."""
+    start, nb, fixed = table
+    nv = P.shape[0]
+    work = torch.empty((2, max(nv, 1), 4), dtype=torch.float32, device=P.device)
+    out = torch.empty_like(P)
+    check(lib.sculpt_smooth_taubin(_p(start), _p(nb), _p(fixed), nv, nb.shape[0], _p(P), int(n), float(lam), float(mu),
+                                   _p(work[0]), _p(work[1]), _p(out), ctx.stream))
+    ctx.stats["smooth_iterations"] = int(n)
+    return out
+
+
+def smooth_device(v, f, iterations, lam, mu):
+    """Taubin's lambda|mu filter (csrc/mesh_smooth.hip): `iterations` times a half-step with lam, then one with mu (mu == 0: the
+    first alone), every vertex towards (lam) or away from (mu) the centroid of its distinct neighbours; vertices on an edge
+    without exactly two faces, and vertices no face names, stay.  -> v f32 [nv, 3], a new tensor; the faces are not touched.
+    The host reads back what one topology construction reads (the edge count) and, before it, the input check's status."""
+    P, F = _inputs(v, f, "mesh_smooth")
+    ctx = _Ctx()
+    if F.shape[0] and P.shape[0]:
+        P = _smooth_steps(ctx, P, _smooth_table(ctx, F, P.shape[0]), iterations, lam, mu)
+    ctx.done()
+    return P
 
 
 def decimate_device(v, f, face_ratio=0.1, num_faces=None):

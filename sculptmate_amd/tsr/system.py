@@ -81,6 +81,16 @@ class Mesh:
         return Mesh(v, f, None if self.vertex_colors is None else self.vertex_colors[vi],
                     vertex_normals=None if self.vertex_normals is None else self.vertex_normals[vi])
 
+    def smooth(self, smooth) -> "Mesh":
+        """The mesh after Taubin's lambda|mu smoothing on the device (ops.mesh_smooth): smooth = an int n, 1 <= n <= 1000
+        (n iterations with lam = 0.5, mu = -0.53) or a tuple (n, lam, mu) (ops.smooth_rule).  The faces are the same tensor and
+        the vertices keep their indices, so vertex_colors, uvs and texture are carried over as they are: the topology is
+        unchanged and a baked atlas stays valid.  vertex_normals is dropped: the vertices have moved and the normals would be
+        stale (TSR.field_normals / ops.vertex_normals at the new vertices give fresh ones).  TSR.extract_meshes(smooth=...)
+        smooths before it simplifies; this method lets a caller choose another order."""
+        v = ops.mesh_smooth(self.vertices, self.faces, smooth)
+        return Mesh(v, self.faces, self.vertex_colors, uvs=self.uvs, texture=self.texture)
+
     def to_trimesh(self):  # pragma: no cover (trimesh is optional)
         import trimesh
 
@@ -972,7 +982,7 @@ class TSR(KernelEngine):
 
     def extract_meshes(self, scene_codes, enable_texture=False, resolution: int = 256, threshold: float = 25.0,
                        x_range=None, density_events=None, bake_texture: int = 0, normals=None,
-                       keep_components=None, simplify=None) -> List[Mesh]:
+                       keep_components=None, simplify=None, smooth=None) -> List[Mesh]:
         """The arithmetic of system.py:171-200 without the Blender sink: returns device tensors.
         density_events: optional (start, stop) torch events recorded around the dense-grid launch (bench.py's live
         per-launch timing of the dominant kernel, on the stream it is launched on).
@@ -987,13 +997,19 @@ class TSR(KernelEngine):
         (ops.mesh_keep_components), so the colours, the baked atlas and the normals see only what is kept.
         simplify: None (default): nothing is launched, nothing changes.  An int >= 1 (target faces) or a float in (0, 1) (ratio of
         the faces left after keep_components): quadric-error edge collapses on the device (ops.mesh_simplify) after
-        keep_components and before the colours, the bake and the normals, which are therefore evaluated at the final vertices."""
+        keep_components and before the colours, the bake and the normals, which are therefore evaluated at the final vertices.
+        smooth: None (default): nothing is launched, nothing changes.  An int n in 1 .. 1000 (n iterations with lam = 0.5,
+        mu = -0.53) or a tuple (n, lam, mu) (ops.smooth_rule): Taubin's lambda|mu filter on the device (ops.mesh_smooth) after
+        keep_components and BEFORE simplify, so that the quadrics are built on the clean surface; faces and indices are
+        unchanged.  Mesh.smooth lets a caller choose another order."""
         if normals not in (None, "field", "faces"):
             raise ValueError("normals must be None, 'field' or 'faces', got %r" % (normals,))
         if keep_components is not None:
             ops.keep_rule(keep_components)   # a ValueError before anything is launched
         if simplify is not None:
             ops.simplify_rule(simplify)
+        if smooth is not None:
+            ops.smooth_rule(smooth)
         bake = int(bake_texture) if enable_texture else 0
         self.set_marching_cubes_resolution(resolution)
         r = self.renderer.cfg.radius
@@ -1012,6 +1028,8 @@ class TSR(KernelEngine):
                 v_pos, t_pos_idx = self._extract_filtered(planes, R, mc, dkw, density_events)
                 if keep_components is not None:
                     v_pos, t_pos_idx = ops.mesh_keep_components(v_pos, t_pos_idx, keep_components)[:2]
+                if smooth is not None:
+                    v_pos = ops.mesh_smooth(v_pos, t_pos_idx, smooth)
                 if simplify is not None:
                     v_pos, t_pos_idx = ops.mesh_simplify(v_pos, t_pos_idx, simplify)[:2]
                 out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
@@ -1020,6 +1038,8 @@ class TSR(KernelEngine):
             v_pos, t_pos_idx = mc(vol)   # (both decoder modes have the fp32 range: a NaN here is a NaN of the model)
             if keep_components is not None:
                 v_pos, t_pos_idx = ops.mesh_keep_components(v_pos, t_pos_idx, keep_components)[:2]
+            if smooth is not None:
+                v_pos = ops.mesh_smooth(v_pos, t_pos_idx, smooth)
             if simplify is not None:
                 v_pos, t_pos_idx = ops.mesh_simplify(v_pos, t_pos_idx, simplify)[:2]
             out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
@@ -1122,7 +1142,8 @@ class TSR(KernelEngine):
         triangles, identical result on every rank and identical to the single-GPU mesh
         (sculptmate_amd/slab.py).  Without a process group the slabs run one after the other here.
         It takes no keep_components: components cross the slabs, so the gathered mesh is filtered afterwards, with
-        Mesh.keep_components."""
+        Mesh.keep_components.  It takes no smooth either, for the same reason (a slab's cut is an open border, whose vertices
+        smoothing holds fixed): smooth the gathered mesh with Mesh.smooth."""
         import torch.distributed as dist
 
         from .. import slab
@@ -1146,14 +1167,14 @@ class TSR(KernelEngine):
         return Mesh(v_pos, t_pos_idx, color)
 
     def extract_mesh(self, scene_codes, enable_texture=False, mesh_name="NewMesh", resolution: int = 256,
-                     threshold: float = 25.0, bake_texture: int = 0, normals=None, keep_components=None, simplify=None):
-        """system.py:171-200: same signature (+ bake_texture, normals, keep_components and simplify, see extract_meshes: the sink
-        receives the filtered, simplified mesh); pushes each mesh into the sink (Blender when
+                     threshold: float = 25.0, bake_texture: int = 0, normals=None, keep_components=None, simplify=None, smooth=None):
+        """system.py:171-200: same signature (+ bake_texture, normals, keep_components, simplify and smooth, see extract_meshes: the sink
+        receives the filtered, smoothed, simplified mesh); pushes each mesh into the sink (Blender when
         `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
         the textured sink (per-loop UVs + an image-texture material).  The sinks take no normals (Blender shades a mesh with
         shared vertices smooth by itself); they stay on the returned meshes."""
         meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture, normals=normals,
-                                     keep_components=keep_components, simplify=simplify)
+                                     keep_components=keep_components, simplify=simplify, smooth=smooth)
         sink = self.mesh_sink or _default_sink()
         for m in meshes:
             if m.texture is not None:
@@ -1169,7 +1190,7 @@ class TSR(KernelEngine):
         return meshes
 
     def run_async(self, image, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, tokens=None,
-                  normals=None, keep_components=None, simplify=None):
+                  normals=None, keep_components=None, simplify=None, smooth=None):
         """One host image -> PendingMesh.  The image goes host -> HBM, the forward and the mesh extraction are queued on
         the current stream, and the mesh (the reference's `.cpu().numpy()` at system.py:200) is copied device -> pinned
         host memory on a separate copy stream, so the copy of mesh i runs under the kernels of image i + 1.
@@ -1178,7 +1199,7 @@ class TSR(KernelEngine):
         with torch.no_grad():
             codes = self.forward([image], self.device) if tokens is None else self.forward_tokens(tokens)
             m = self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals,
-                                    keep_components=keep_components, simplify=simplify)[0]
+                                    keep_components=keep_components, simplify=simplify, smooth=smooth)[0]
         return self._mesh_to_host_async(m)
 
     def _mesh_to_host_async(self, m) -> PendingMesh:
@@ -1209,7 +1230,7 @@ class TSR(KernelEngine):
         return PendingMesh(host, done, tuple(leases))
 
     def run(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, batch=None,
-            normals=None, keep_components=None, simplify=None) -> List[Mesh]:
+            normals=None, keep_components=None, simplify=None, smooth=None) -> List[Mesh]:
         """Headless entry point: images -> list of Mesh with host (NumPy) arrays; the device -> host copy of mesh i overlaps the
         kernels that follow it.
         batch (images per transformer pass; None = the default): in the bf16 mode a stacked pass of several images gives each
@@ -1220,20 +1241,21 @@ class TSR(KernelEngine):
         tokenizer look-ahead (run_pipelined).  batch=1 forces that everywhere.
         normals: None, "field" or "faces" (extract_meshes): Mesh.vertex_normals as float32 [Nv, 3] on the host.
         keep_components: None, "largest", an int or a float (extract_meshes): the meshes without their small components.
-        simplify: None, an int or a float (extract_meshes): the meshes reduced by quadric-error collapses on the device."""
+        simplify: None, an int or a float (extract_meshes): the meshes reduced by quadric-error collapses on the device.
+        smooth: None, an int or (n, lam, mu) (extract_meshes): the meshes after Taubin smoothing on the device, before simplify."""
         images = _as_image_list(images)
         if batch is None:
             batch = self.RUN_BATCH if (self.precision == "bf16" and len(images) >= 2) else 1
         if batch <= 1 or len(images) < 2:
             return [p.result() for p in self.run_pipelined(images, mc_resolution, threshold, enable_texture, normals=normals,
-                                                              keep_components=keep_components, simplify=simplify)]
+                                                              keep_components=keep_components, simplify=simplify, smooth=smooth)]
         return [p.result() for p in self.run_batched(images, batch, mc_resolution, threshold, enable_texture, normals=normals,
-                                                        keep_components=keep_components, simplify=simplify)]
+                                                        keep_components=keep_components, simplify=simplify, smooth=smooth)]
 
     RUN_BATCH = 8   # images per transformer pass of TSR.run in the bf16 mode (4: 139.7, 8: 143.5 meshes/s device to device)
 
     def run_batched(self, images, batch: int = 4, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False,
-                    normals=None, keep_components=None, simplify=None):
+                    normals=None, keep_components=None, simplify=None, smooth=None):
         """images (host or device) -> list of PendingMesh through batched forward passes of `batch` images each."""
         images = list(images)
         pending = []
@@ -1244,27 +1266,27 @@ class TSR(KernelEngine):
                 with torch.no_grad():
                     codes = self.forward(images[i:i + self.max_batch], self.device)
                     for m in self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals,
-                                                 keep_components=keep_components, simplify=simplify):
+                                                 keep_components=keep_components, simplify=simplify, smooth=smooth):
                         pending.append(self._mesh_to_host_async(m))
         finally:
             self.max_batch = keep
         return pending
 
     def run_pipelined(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, normals=None,
-                      keep_components=None, simplify=None):
+                      keep_components=None, simplify=None, smooth=None):
         """images (host or device) -> list of PendingMesh, with the tokenizer of image i + 1 queued beside the backbone /
         density grid / marching cubes of image i (tokens_async) and the device -> host copy of mesh i under image i + 1."""
         images = list(images)
         if len(images) < 2:
             return [self.run_async(im, mc_resolution, threshold, enable_texture, normals=normals, keep_components=keep_components,
-                                   simplify=simplify)
+                                   simplify=simplify, smooth=smooth)
                     for im in images]
         pending, nxt = [], self.tokens_async(images[0])
         for i, im in enumerate(images):
             cur = nxt
             nxt = self.tokens_async(images[i + 1]) if i + 1 < len(images) else None
             pending.append(self.run_async(im, mc_resolution, threshold, enable_texture, tokens=cur, normals=normals,
-                                          keep_components=keep_components, simplify=simplify))
+                                          keep_components=keep_components, simplify=simplify, smooth=smooth))
         return pending
 
 
