@@ -983,6 +983,48 @@ int sculpt_smooth_neighbours(const int64_t *skeys, int64_t n, int32_t *nb, sculp
 int sculpt_smooth_taubin(const int32_t *start, const int32_t *nb, const uint8_t *fixed, int64_t nv, int64_t n_nb, const float *P,
                          int iterations, double lam, double mu, float *work_a, float *work_b, float *out, sculpt_stream_t stream);
 
+/* Mesh vertices onto the iso-surface of the density field (csrc/mesh_project.hip; ops.project_to_isosurface, ops.mesh_unfold,
+ * ops.mesh_project).  DEVICE pointers, asynchronous on `stream`, no host wait.  Added without a version
+ * change (new symbols only).
+ *
+ * sculpt_triplane_project: per point a Newton iteration along the gradient of the raw density d (the value and gradient of
+ * sculpt_triplane_density_grad, the same bits) towards d(p) = target, in one launch: 8 points x {value, d/dx, d/dy, d/dz} per
+ * MFMA tile, the state of the iteration in registers, every point stopping on its own.  fp32, the step without contraction:
+ *   an axis a with |p0_a| >= radius is FROZEN: it keeps p0_a bit for bit and its gradient component is taken as 0
+ *   1  (d, g) at p = p0, r = d - target; r not finite: status 3, the result is p0.  best = (p0, r)
+ *   2  for k < max_steps:  |r| <= res_tol: status 0, stop
+ *                          g2 = (gx gx + gy gy) + gz gz on the masked gradient; not > 0 or not finite: status 3, stop
+ *                          s = r / g2; q_a = p_a - s g_a; q_a < -radius -> -radius, q_a > radius -> radius; frozen axes restored
+ *                          (dx dx + dy dy) + dz dz of q - p0 above max_dist max_dist: status 2, stop
+ *                          (d, g) at q, r_q = d - target; not finite: status 3, stop
+ *                          p, r, g = q, r_q, g_q; |r| < |best.r|: best = (p, r)
+ *   3  out of steps: status 0 if |r| <= res_tol, else 1
+ *   points        f32 [N][3]
+ *   out_points    f32 [N][3]   best.p (may not alias points)
+ *   out_residual  f32 [N]      best.r = d(best.p) - target, nullable
+ *   out_status    i32 [N]      0 converged, 1 out of steps, 2 left the trust region, 3 no usable value or gradient; nullable
+ *   out_evals     i32 [N]      evaluations the point used, 1 .. max_steps + 1; nullable
+ * A point's outputs depend on that point alone.  Refused: what sculpt_triplane_density_grad refuses, max_steps outside 0 .. 64,
+ * max_dist or res_tol not positive and finite, a NaN target, a null out_points (with N > 0).  N == 0 is a no-op.
+ *
+ * sculpt_mesh_unfold: the fold guard.  P0 [Nv][3] the positions before the projection, P [Nv][3] after it (updated in place),
+ * faces int64 [Nf][3].  With n0 = (b - a) x (c - a) on P0 and n1 the same on P, a face is INVERTED when n0.n0 > 0 and
+ * n0.n1 <= 0 (dots as (x x + y y) + z z, fp32 without contraction; a face with an index outside [0, Nv) is skipped).  `rounds`
+ * (0 .. 16) times: every vertex of an inverted face takes its P0 row back.  Then the faces still inverted are counted.
+ *   mark_ws  i32 [Nv] workspace (cleared here; 0 untouched, 1 to revert, 2 reverted); may be null with rounds == 0
+ *   stats    i32 [2]  (cleared here) vertices reverted, faces still inverted
+ * Nv == 0 or Nf == 0 clears stats and launches nothing else.
+ * Measured on one MI355X (tools/time_project.py, the 907 205 vertices / 1 680 874 faces of a 256^3 mesh, max_steps 8, warm
+ * medians): sculpt_triplane_project 9.17 ms at 2.13 evaluations per vertex (one evaluation of all vertices: 3.06 ms);
+ * sculpt_mesh_unfold with 4 rounds 0.24 ms. */
+int sculpt_triplane_project(const float *planes_cl /* [3][H][W][C] */, int C, int H, int W, const void *mlp_packed, int n_hidden_64,
+                            const float *points /* [N][3] */, long long N, float radius, int flags /* QUERY_ALIGN_CORNERS */,
+                            float target, int max_steps, float max_dist, float res_tol, float *out_points /* [N][3] */,
+                            float *out_residual /* [N] or null */, int *out_status /* [N] or null */, int *out_evals /* [N] or null */,
+                            sculpt_stream_t stream);
+int sculpt_mesh_unfold(const float *P0, float *P, const int64_t *faces, int64_t Nv, int64_t Nf, int rounds, int *mark_ws, int *stats,
+                       sculpt_stream_t stream);
+
 /* Mesh hand-off, HOST side (no GPU work): the face block of a binary little-endian PLY file -- per face `uchar 3` followed by
  * three int32 -- from the int64 faces TSR.run returns (the reference's `t_pos_idx.cpu().numpy()`, TripoSR/tsr/system.py:200).
  * faces_host int64 [n][3] -> records_host uint8 [n][13].  Thread-safe; callers split n over threads (sculptmate_amd/meshio.py). */

@@ -63,7 +63,7 @@ class MeshWriter:
 
 
 def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture=False, out_dir=None, names=None, fmt="ply",
-                keep=True, writers=4, batch=1, keep_components=None, simplify=None, smooth=None):
+                keep=True, writers=4, batch=1, keep_components=None, simplify=None, smooth=None, project=None):
     """images: the WHOLE batch, identical on every rank (a list of host arrays / PIL images, or callables returning one, so
     that a rank only loads the files it owns).  Returns (local, summary):
       local   {index: Mesh} of the images this rank owns (empty dict with keep=False: meshes are only written);
@@ -79,6 +79,8 @@ def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture
     only when set.
     smooth: None, an int or (n, lam, mu) (TSR.extract_meshes): every mesh after Taubin smoothing, before simplify; handed to the
     model only when set.
+    project: None, True, an int or (n, cells) (TSR.extract_meshes): every mesh with its vertices on the field's iso-surface, the
+    last geometry step; handed to the model only when set.
     A rank that fails still takes part in the one exchange, with an error marker in place of its counts: every rank then
     raises, none is left waiting in a collective the failed rank never enters."""
     import torch.distributed as dist
@@ -96,6 +98,8 @@ def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture
         ckw["simplify"] = simplify
     if smooth is not None:
         ckw["smooth"] = smooth
+    if project is not None:
+        ckw["project"] = project
     writer = MeshWriter(writers) if (out_dir is not None and writers) else None
     failure = None
 

@@ -22,104 +22,10 @@
 #include <algorithm>
 
 #include "common.h"
+#include "field_fwd.h"
 #include "triplane_mlp.h"
 
 namespace sculpt {
-
-// value of lane (lane & ~3): v_mov_b32 with quad_perm:[K,K,K,K]
-template <int K>
-__device__ __forceinline__ float quad_bcast(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), K * 0x55, 0xf, 0xf, true));
-}
-
-// The weights a column of kind `kind` (0 = value, 1 + axis = tangent) hands to layer 0.  wt comes in from point_taps (the value's
-// weights) and stays for kind 0.  A tangent along world axis a gets, per plane, d(weight)/d(pixel coordinate) * d(pixel
-// coordinate)/d(world coordinate) on the plane axis that reads a, and 0 on a plane that does not read it.
-template <bool AC>
-__device__ __forceinline__ void tangent_weights(int kind, float px, float py, float pz, float radius, float span, int H, int W,
-                                                float (&wt)[3][4]) {
-    if (kind == 0) return;
-    const int a = kind - 1;
-    const float q[3] = {to_unit(px, radius, span), to_unit(py, radius, span), to_unit(pz, radius, span)};
-    // d(unit)/d(world) = 2 / span; d(pixel)/d(unit) = size / 2, or (size - 1) / 2 with align_corners
-    const float du = 2.0f / span;
-    const float sx = du * ((float)(AC ? W - 1 : W) * 0.5f), sy = du * ((float)(AC ? H - 1 : H) * 0.5f);
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-        const int ia = pl == 2 ? 1 : 0, ib = pl == 0 ? 1 : 2;
-        const Tap1 tx = tap_of<AC>(q[ia], W), ty = tap_of<AC>(q[ib], H);
-        const float wx = tx.w1, ex = 1.0f - wx, wy = ty.w1, ey = 1.0f - wy;
-        const int x0 = tx.i0, x1 = x0 + 1, y0 = ty.i0, y1 = y0 + 1;
-        const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W;
-        const bool vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
-        float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
-        if (a == ia) {  // d/dfx of (ey ex, ey wx, wy ex, wy wx)
-            d0 = -ey * sx; d1 = ey * sx; d2 = -wy * sx; d3 = wy * sx;
-        } else if (a == ib) {  // d/dfy
-            d0 = -ex * sy; d1 = -wx * sy; d2 = ex * sy; d3 = wx * sy;
-        }
-        wt[pl][0] = (vy0 && vx0) ? d0 : 0.f;
-        wt[pl][1] = (vy0 && vx1) ? d1 : 0.f;
-        wt[pl][2] = (vy1 && vx0) ? d2 : 0.f;
-        wt[pl][3] = (vy1 && vx1) ? d3 : 0.f;
-    }
-}
-
-// The step between two layers on 16 accumulator registers: SiLU on a value column (silu16's operations, the same bits), the
-// chain rule on a tangent column.  Every lane computes the sigmoid of its quad's value column.
-__device__ __forceinline__ f32x16 act16(const f32x16 &acc, bool is_value) {
-    f32x16 o;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const float y = quad_bcast<0>(acc[i]);
-        const float e = __builtin_amdgcn_exp2f(-y);
-        const float sg = __builtin_amdgcn_rcpf(e + 1.0f);
-        const float val = y * sg;
-        const float der = sg * (1.0f + (y * 0.69314718055994530942f) * (1.0f - sg));
-        o[i] = is_value ? val : der * acc[i];
-    }
-    return o;
-}
-
-// hidden_layers (triplane_mlp.h) with act16 between the layers; in: layer-0 accumulators, out: what the last layer reads
-__device__ __forceinline__ void hidden_layers_fwd(const LdsView &L, int NH, int lane, int h, bool is_value, f32x16 &x0,
-                                                  f32x16 &x1) {
-    x0 = act16(x0, is_value);
-    x1 = act16(x1, is_value);
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int l = 0; l < NH; ++l) {
-        f32x16 acc0 = is_value ? lds_bias16(L.bacc, l + 1, h, 0) : zero;
-        f32x16 acc1 = is_value ? lds_bias16(L.bacc, l + 1, h, 1) : zero;
-        const f32x4 *A0 = reinterpret_cast<const f32x4 *>(L.hid) + ((l * 2 + 0) * 8) * 64 + lane;
-        const f32x4 *A1 = reinterpret_cast<const f32x4 *>(L.hid) + ((l * 2 + 1) * 8) * 64 + lane;
-#pragma unroll
-        for (int s4 = 0; s4 < 8; ++s4) {
-            f32x4 a0 = A0[s4 * 64];
-            f32x4 a1 = A1[s4 * 64];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int s = s4 * 4 + j;
-                const float b = (s < 16) ? x0[s & 15] : x1[s & 15];
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[j], b, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], b, acc1, 0, 0, 0);
-            }
-        }
-        x0 = act16(acc0, is_value);
-        x1 = act16(acc1, is_value);
-    }
-}
-
-// last_dot (triplane_mlp.h) of row 0 without the bias
-__device__ __forceinline__ float last_dot0_nobias(const LdsView &L, int h, const f32x16 &x0, const f32x16 &x1) {
-    const float *w = L.wlast + h * 32;
-    float s = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s = fmaf(w[r], x0[r], s);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s = fmaf(w[16 + r], x1[r], s);
-    s += __shfl_xor(s, 32, 64);
-    return s;
-}
 
 template <int C, bool AC>
 __global__ __launch_bounds__(512) void density_grad_kernel(

@@ -1,0 +1,287 @@
+// Mesh vertices onto the iso-surface of the density field, for gfx950 (MI355X): a fused Newton iteration along the field's own
+// gradient (sculpt_triplane_project) and the fold guard that follows it (sculpt_mesh_unfold).  The rule is DESIGN.md section
+// 3.1e; tests/_projref.py restates both halves.
+//
+// project_kernel
+//   * density_grad_kernel's tile (csrc/field_normal.hip, csrc/field_fwd.h): a wave is 8 points x {value, d/dx, d/dy, d/dz}, the
+//     weights are staged in LDS once per workgroup, and one evaluation is that kernel's own sequence of operations, so the raw
+//     density d and the gradient g of an iterate are ops.field_normals' bits at that iterate.
+//   * after an evaluation the eight lanes of a point all hold d and g (three quad broadcasts; the two halves agree after
+//     last_dot0_nobias's xor-shuffle) and run the rule redundantly in registers: current iterate, residual, masked gradient, best
+//     iterate, trust region, status, evaluation count.  No LDS, no memory traffic between two steps.
+//   * a point that has stopped keeps its state; its lanes go on evaluating with the wave (at the point they stopped at) and
+//     ignore the result.  The loop leaves when a 64-bit ballot finds no lane active, at the latest after max_steps + 1
+//     evaluations.  Nothing waits on another wave.
+//   * the rule (rule_update) is compiled without contraction: every value is a fixed sequence of IEEE fp32 operations, which
+//     torch restates one call per operation (tests/_projref.py composed_device).  The evaluator keeps the contraction it has in
+//     field_normal.hip, or its bits would differ from that kernel's.
+//
+// unfold kernels: fp32 without contraction (tests/_projref.py unfold restates them in NumPy bit for bit).
+#include <algorithm>
+
+#include "common.h"
+#include "field_fwd.h"
+#include "triplane_mlp.h"
+
+namespace sculpt {
+
+// what a point carries from one evaluation to the next
+struct ProjState {
+    float px, py, pz;     // current iterate
+    float r;              // its residual d - target
+    float gx, gy, gz;     // its masked gradient
+    float bx, by, bz, br; // best iterate and its residual
+    int status, evals;
+    bool active;
+};
+
+__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) < INFINITY; }
+
+// One turn of the rule after the evaluation (d, g) at the candidate (qx, qy, qz): accept it (k == 0: it is p0), then the
+// checks and the step that lead to the next candidate, which is left in (qx, qy, qz).  DESIGN.md section 3.1e numbers the
+// operations.
+__device__ __forceinline__ void rule_update(ProjState &s, int k, int K, float d, float gx, float gy, float gz, float &qx, float &qy,
+                                            float &qz, float p0x, float p0y, float p0z, bool fx, bool fy, bool fz, float target,
+                                            float radius, float md2, float res_tol) {
+#pragma clang fp contract(off)
+    if (s.active) {
+        s.evals += 1;
+        const float rq = d - target;
+        if (!finite_f(rq)) {
+            s.status = 3;
+            s.active = false;
+            if (k == 0) s.br = rq;
+        } else {
+            s.px = qx, s.py = qy, s.pz = qz;
+            s.r = rq;
+            s.gx = fx ? 0.f : gx, s.gy = fy ? 0.f : gy, s.gz = fz ? 0.f : gz;
+            if (k == 0 || fabsf(rq) < fabsf(s.br)) s.bx = qx, s.by = qy, s.bz = qz, s.br = rq;
+        }
+    }
+    if (!s.active) return;
+    if (k == K) {
+        s.status = fabsf(s.r) <= res_tol ? 0 : 1;
+        s.active = false;
+        return;
+    }
+    if (fabsf(s.r) <= res_tol) {
+        s.status = 0;
+        s.active = false;
+        return;
+    }
+    const float g2 = (s.gx * s.gx + s.gy * s.gy) + s.gz * s.gz;
+    if (!(g2 > 0.f) || !finite_f(g2)) {
+        s.status = 3;
+        s.active = false;
+        return;
+    }
+    const float st = s.r / g2;
+    float nx = s.px - st * s.gx, ny = s.py - st * s.gy, nz = s.pz - st * s.gz;
+    const float lo = -radius;
+    nx = nx < lo ? lo : nx, ny = ny < lo ? lo : ny, nz = nz < lo ? lo : nz;   // comparisons, not fmin / fmax: a NaN stays a NaN
+    nx = nx > radius ? radius : nx, ny = ny > radius ? radius : ny, nz = nz > radius ? radius : nz;
+    nx = fx ? p0x : nx, ny = fy ? p0y : ny, nz = fz ? p0z : nz;
+    const float dx = nx - p0x, dy = ny - p0y, dz = nz - p0z;
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    if (d2 > md2) {
+        s.status = 2;
+        s.active = false;
+        return;
+    }
+    qx = nx, qy = ny, qz = nz;
+}
+
+template <int C, bool AC>
+__global__ __launch_bounds__(512) void project_kernel(
+    const float *__restrict__ planes, int H, int W, const float *__restrict__ blob, const float *__restrict__ pts, long N,
+    float radius, float span, float target, int K, float md2, float res_tol, float *__restrict__ out_pts,
+    float *__restrict__ out_res, int *__restrict__ out_status, int *__restrict__ out_evals, int a0_lds) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
+    const int NH = hd.NH;
+    float *a0s = smem + lds_floats_for(NH);
+    if (a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
+    load_weights_to_lds(smem, blob, hd);
+    const LdsView L = lds_view(smem, NH);
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
+    const int p = lane & 31, h = lane >> 5;
+    const int kind = p & 3;
+    const bool is_value = kind == 0;
+    const long ntiles = (N + 7) / 8;
+    const float *A0g = blob + hd.off_a0;
+    const long HW = (long)H * W;
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+
+    for (long tile = (long)blockIdx.x * nwave + wave; tile < ntiles; tile += (long)gridDim.x * nwave) {
+        long n = tile * 8 + (p >> 2);
+        const bool valid = n < N;
+        if (!valid) n = N - 1;   // a copy of the last point: it runs the same steps and stores nothing
+        const float p0x = pts[3 * n], p0y = pts[3 * n + 1], p0z = pts[3 * n + 2];
+        const bool fx = fabsf(p0x) >= radius, fy = fabsf(p0y) >= radius, fz = fabsf(p0z) >= radius;
+        ProjState s;
+        s.px = s.bx = p0x, s.py = s.by = p0y, s.pz = s.bz = p0z;
+        s.r = s.br = 0.f;
+        s.gx = s.gy = s.gz = 0.f;
+        s.status = 1, s.evals = 0, s.active = true;
+        float qx = p0x, qy = p0y, qz = p0z;
+        for (int k = 0; k <= K; ++k) {   // K <= 64 (checked at the entry): at most K + 1 evaluations
+            // one evaluation at (qx, qy, qz): density_grad_kernel's sequence
+            int off[3][4];
+            float wt[3][4];
+            point_taps<AC>(qx, qy, qz, radius, span, H, W, off, wt);
+            tangent_weights<AC>(kind, qx, qy, qz, radius, span, H, W, wt);
+            f32x16 x0 = is_value ? lds_bias16(L.bacc, 0, h, 0) : zero;
+            f32x16 x1 = is_value ? lds_bias16(L.bacc, 0, h, 1) : zero;
+            layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, x0, x1);
+            hidden_layers_fwd(L, NH, lane, h, is_value, x0, x1);
+            const float sv = last_dot0_nobias(L, h, x0, x1);
+            const float d = quad_bcast<0>(sv) + L.blast[0];
+            const float gx = quad_bcast<1>(sv), gy = quad_bcast<2>(sv), gz = quad_bcast<3>(sv);
+            rule_update(s, k, K, d, gx, gy, gz, qx, qy, qz, p0x, p0y, p0z, fx, fy, fz, target, radius, md2, res_tol);
+            if (__ballot(s.active) == 0ull) break;   // wave-uniform: all eight points have stopped
+        }
+        if (valid && is_value && h == 0) {
+            out_pts[3 * n] = s.bx, out_pts[3 * n + 1] = s.by, out_pts[3 * n + 2] = s.bz;
+            if (out_res) out_res[n] = s.br;
+            if (out_status) out_status[n] = s.status;
+            if (out_evals) out_evals[n] = s.evals;
+        }
+    }
+}
+
+}  // namespace sculpt
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// the fold guard
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+#pragma clang fp contract(off)
+
+constexpr int UNFOLD_BLOCK = 256;
+
+// n = (b - a) x (c - a), each component two products and one difference
+__device__ __forceinline__ void face_cross(const float *__restrict__ P, long a, long b, long c, float &nx, float &ny, float &nz) {
+    const float ux = P[3 * b] - P[3 * a], uy = P[3 * b + 1] - P[3 * a + 1], uz = P[3 * b + 2] - P[3 * a + 2];
+    const float vx = P[3 * c] - P[3 * a], vy = P[3 * c + 1] - P[3 * a + 1], vz = P[3 * c + 2] - P[3 * a + 2];
+    nx = uy * vz - uz * vy;
+    ny = uz * vx - ux * vz;
+    nz = ux * vy - uy * vx;
+}
+
+__device__ __forceinline__ bool face_inverted(const float *__restrict__ P0, const float *__restrict__ P, long a, long b, long c) {
+    float ax, ay, az, bx, by, bz;
+    face_cross(P0, a, b, c, ax, ay, az);
+    face_cross(P, a, b, c, bx, by, bz);
+    const float n00 = (ax * ax + ay * ay) + az * az;
+    const float n01 = (ax * bx + ay * by) + az * bz;
+    return n00 > 0.f && n01 <= 0.f;   // a NaN fails both: such a face is left alone
+}
+
+// mark words: 0 = untouched, 1 = to revert in this round, 2 = reverted.  A face stores 1 into the words of its vertices that
+// are not yet reverted: every writer of a word writes the same value, so the result does not depend on the order.
+__global__ __launch_bounds__(UNFOLD_BLOCK) void unfold_mark_kernel(const float *__restrict__ P0, const float *__restrict__ P,
+                                                                   const int64_t *__restrict__ F, long nv, long nf, int *__restrict__ mark) {
+    const long f = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= nf) return;
+    const int64_t a = F[3 * f], b = F[3 * f + 1], c = F[3 * f + 2];
+    if (a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv) return;   // a face that names no vertex is skipped
+    if (!face_inverted(P0, P, a, b, c)) return;
+    if (mark[a] != 2) mark[a] = 1;
+    if (mark[b] != 2) mark[b] = 1;
+    if (mark[c] != 2) mark[c] = 1;
+}
+
+// stats[slot] += the number of lanes with `one`, one atomic per wave
+__device__ __forceinline__ void wave_count(int *__restrict__ stats, int slot, bool one) {
+    const unsigned long long m = __ballot(one);
+    if (m && (threadIdx.x & 63) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(stats + slot, (int)__popcll(m));
+}
+
+__global__ __launch_bounds__(UNFOLD_BLOCK) void unfold_revert_kernel(const float *__restrict__ P0, float *__restrict__ P, long nv,
+                                                                     int *__restrict__ mark, int *__restrict__ stats) {
+    const long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool hit = v < nv && mark[v] == 1;
+    if (hit) {
+        P[3 * v] = P0[3 * v], P[3 * v + 1] = P0[3 * v + 1], P[3 * v + 2] = P0[3 * v + 2];
+        mark[v] = 2;
+    }
+    wave_count(stats, 0, hit);
+}
+
+__global__ __launch_bounds__(UNFOLD_BLOCK) void unfold_count_kernel(const float *__restrict__ P0, const float *__restrict__ P,
+                                                                    const int64_t *__restrict__ F, long nv, long nf, int *__restrict__ stats) {
+    const long f = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool inv = false;
+    if (f < nf) {
+        const int64_t a = F[3 * f], b = F[3 * f + 1], c = F[3 * f + 2];
+        if (!(a < 0 || b < 0 || c < 0 || a >= nv || b >= nv || c >= nv)) inv = face_inverted(P0, P, a, b, c);
+    }
+    wave_count(stats, 1, inv);
+}
+
+}  // namespace
+
+using namespace sculpt;
+
+extern "C" int sculpt_triplane_project(const float *planes_cl, int C, int H, int W, const void *mlp_packed, int n_hidden_64,
+                                       const float *points, long long N, float radius, int flags, float target, int max_steps,
+                                       float max_dist, float res_tol, float *out_points, float *out_residual, int *out_status,
+                                       int *out_evals, sculpt_stream_t stream) {
+    SC_REQUIRE(C == 40, "triplane_project: built for C=40 channels per plane (got %d)", C);
+    SC_REQUIRE(planes_cl && mlp_packed, "triplane_project: null input");
+    SC_REQUIRE(H >= 1 && W >= 1, "triplane_project: bad plane size %d x %d", H, W);
+    SC_REQUIRE(N >= 0, "triplane_project: negative point count %lld", N);
+    SC_REQUIRE((flags & ~(int)SCULPT_QUERY_ALIGN_CORNERS) == 0, "triplane_project: unknown flags %d", flags);
+    SC_REQUIRE(n_hidden_64 >= 0, "triplane_project: bad n_hidden_64");
+    SC_REQUIRE(radius > 0.f, "triplane_project: radius must be positive");
+    SC_REQUIRE(max_steps >= 0 && max_steps <= 64, "triplane_project: max_steps=%d (0 .. 64)", max_steps);
+    SC_REQUIRE(max_dist > 0.f && max_dist < INFINITY, "triplane_project: max_dist=%g must be positive and finite", (double)max_dist);   // a NaN fails
+    SC_REQUIRE(res_tol > 0.f && res_tol < INFINITY, "triplane_project: res_tol=%g must be positive and finite", (double)res_tol);
+    SC_REQUIRE(target == target, "triplane_project: target is NaN");
+    if (N == 0) return 0;   // empty arrays have no address: nothing to refuse, nothing to launch
+    SC_REQUIRE(out_points, "triplane_project: null out_points");
+    SC_REQUIRE(points, "triplane_project: null points");
+    size_t lds = (size_t)lds_floats_for(n_hidden_64) * sizeof(float);
+    SC_REQUIRE(lds <= 160 * 1024, "triplane_project: %d hidden layers do not fit LDS", n_hidden_64);
+    const size_t a0_bytes = (size_t)3 * C * 64 * sizeof(float);
+    const int a0_lds = lds + a0_bytes <= 160 * 1024 ? 1 : 0;
+    if (a0_lds) lds += a0_bytes;
+    auto kern = (flags & (int)SCULPT_QUERY_ALIGN_CORNERS) ? project_kernel<40, true> : project_kernel<40, false>;
+    SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const long ntiles = ((long)N + 7) / 8;
+    const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
+    const float span = (float)((double)radius - (double)(-radius));
+    const float md2 = max_dist * max_dist;   // one fp32 product, as the rule states it
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W,
+                       reinterpret_cast<const float *>(mlp_packed), points, (long)N, radius, span, target, max_steps, md2, res_tol,
+                       out_points, out_residual, out_status, out_evals, a0_lds);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sculpt_mesh_unfold(const float *P0, float *P, const int64_t *faces, int64_t Nv, int64_t Nf, int rounds, int *mark_ws,
+                                  int *stats, sculpt_stream_t stream) {
+    SC_REQUIRE(Nv >= 0 && Nv < ((int64_t)1 << 31) && Nf >= 0 && Nf < ((int64_t)1 << 31), "mesh_unfold: Nv=%lld, Nf=%lld out of range",
+               (long long)Nv, (long long)Nf);
+    SC_REQUIRE(rounds >= 0 && rounds <= 16, "mesh_unfold: rounds=%d (0 .. 16)", rounds);
+    SC_REQUIRE(stats, "mesh_unfold: null stats");
+    SC_HIP(hipMemsetAsync(stats, 0, 2 * sizeof(int), as_stream(stream)));
+    if (Nv == 0 || Nf == 0) return 0;
+    SC_REQUIRE(P0 && P && faces, "mesh_unfold: null array");
+    SC_REQUIRE(P0 != P, "mesh_unfold: P0 and P must be distinct arrays");
+    SC_REQUIRE(rounds == 0 || mark_ws, "mesh_unfold: null mark workspace");
+    hipStream_t st = as_stream(stream);
+    const dim3 fgrid((unsigned)cdiv(Nf, UNFOLD_BLOCK)), vgrid((unsigned)cdiv(Nv, UNFOLD_BLOCK)), block(UNFOLD_BLOCK);
+    if (rounds > 0) SC_HIP(hipMemsetAsync(mark_ws, 0, (size_t)Nv * sizeof(int), st));
+    for (int r = 0; r < rounds; ++r) {
+        hipLaunchKernelGGL(unfold_mark_kernel, fgrid, block, 0, st, P0, P, faces, (long)Nv, (long)Nf, mark_ws);
+        SC_LAUNCH_CHECK();
+        hipLaunchKernelGGL(unfold_revert_kernel, vgrid, block, 0, st, P0, P, (long)Nv, mark_ws, stats);
+        SC_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(unfold_count_kernel, fgrid, block, 0, st, P0, P, faces, (long)Nv, (long)Nf, stats);
+    SC_LAUNCH_CHECK();
+    return 0;
+}

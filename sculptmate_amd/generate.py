@@ -37,7 +37,11 @@ class TripoGenerator(GeneratorFacade):
     (TSR.extract_meshes; ops.mesh_simplify).
     `smooth` (default None): an int n in 1 .. 1000 (iterations, lam = 0.5, mu = -0.53) or a tuple (n, lam, mu) smooths every mesh
     with Taubin's lambda|mu filter on the device, after keep_components and before simplify (TSR.extract_meshes;
-    ops.mesh_smooth)."""
+    ops.mesh_smooth).
+    `project` (default None): True (8 Newton steps inside one lattice cell), an int n in 1 .. 64 or a tuple (n, cells) moves the
+    vertices of every mesh onto the iso-surface of the density field itself and undoes folded faces, as the last geometry
+    step -- after keep_components, smooth and simplify, before the colours, the bake and the normals (TSR.extract_meshes;
+    ops.mesh_project)."""
 
     def __init__(self, device):
         super().__init__(device, checkpoint_dir=ROOT_DIR + "/checkpoints/", chunk_size=8192, mc_resolution=256,
@@ -48,6 +52,7 @@ class TripoGenerator(GeneratorFacade):
         self.keep_components = None
         self.simplify = None
         self.smooth = None
+        self.project = None
 
     def _construct_model(self):
         model = TSR.from_pretrained(self.checkpoint_dir, config_name="config.yaml", weight_name="model.ckpt",
@@ -66,7 +71,7 @@ class TripoGenerator(GeneratorFacade):
                                                        bake_texture=int(self.bake_texture_resolution or 0),
                                                        normals=self.vertex_normals,
                                                        keep_components=self.keep_components, simplify=self.simplify,
-                                                       smooth=self.smooth)
+                                                       smooth=self.smooth, project=self.project)
         except Exception as err:
             print(self.run_error_tag, err)
             return STATUS_FAILED

@@ -682,6 +682,131 @@ def mesh_smooth(vertices, faces, smooth):
 
 
 # ----------------------------------------------------------------------------------------------
+# projection onto the field's iso-surface: fused Newton kernel + fold guard (csrc/mesh_project.hip)
+# ----------------------------------------------------------------------------------------------
+PROJECT_STEPS, PROJECT_CELLS = 8, 1.0   # what project=True means: at most 8 steps inside a trust radius of one lattice cell
+PROJECT_MAX_STEPS, PROJECT_MAX_CELLS = 64, 8.0
+PROJECT_RES_TOL = 1e-3                  # raw density units: ten times the fp32 noise of the point query (E_ref_density 9.2e-5)
+PROJECT_UNFOLD_ROUNDS = 4
+
+
+def project_rule(project):
+    """`project` of the mesh projection -> (steps, max_cells): True (8 steps, a trust radius of 1 lattice cell), an int n in
+    1 .. 64 (n steps, 1 cell) or a tuple (n, cells) with 0 < cells <= 8.  Anything else -- False, None, a str, a bare float, NaN,
+    another length -- is a ValueError, raised here, before anything is launched."""
+    import numbers
+
+    def count(n):
+        return (not isinstance(n, (bool, np.bool_)) and isinstance(n, numbers.Integral) and 1 <= int(n) <= PROJECT_MAX_STEPS)
+
+    if project is True or (isinstance(project, np.bool_) and bool(project)):
+        return PROJECT_STEPS, PROJECT_CELLS
+    if count(project):
+        return int(project), PROJECT_CELLS
+    if isinstance(project, tuple) and len(project) == 2 and count(project[0]):
+        cells = project[1]
+        if not isinstance(cells, (bool, np.bool_)) and isinstance(cells, numbers.Real) and 0.0 < float(cells) <= PROJECT_MAX_CELLS:
+            return int(project[0]), float(cells)   # a NaN fails the comparison
+    raise ValueError("project must be True, an int in 1 .. %d (steps) or (steps, cells) with 0 < cells <= %g, got %r"
+                     % (PROJECT_MAX_STEPS, PROJECT_MAX_CELLS, project))
+
+
+def _project_args(steps, max_dist, res_tol, target):
+    import numbers
+
+    if isinstance(steps, (bool, np.bool_)) or not isinstance(steps, numbers.Integral) or not 0 <= int(steps) <= PROJECT_MAX_STEPS:
+        raise ValueError("steps must be an int in 0 .. %d, got %r" % (PROJECT_MAX_STEPS, steps))
+    for name, x in (("max_dist", max_dist), ("res_tol", res_tol)):
+        if not (0.0 < float(np.float32(x)) < math.inf):   # as the kernel sees it; a NaN fails the comparison
+            raise ValueError("%s must be positive and finite in fp32, got %r" % (name, x))
+    if not math.isfinite(float(np.float32(target))):
+        raise ValueError("target must be finite, got %r" % (target,))
+
+
+def project_to_isosurface(planes, mlp, points, target, max_dist, steps=PROJECT_STEPS, res_tol=PROJECT_RES_TOL, radius=0.87,
+                          align_corners=False, want=()):
+    """`points` moved onto the iso-surface d(p) = target of the raw density (the `density` of field_normals / triplane_query,
+    before bias and exp), by at most `steps` Newton steps along the density's own gradient, in ONE launch
+    (sculpt_triplane_project; the rule, numbered, is DESIGN.md section 3.1e): p <- p - (d - target) g / |g|^2, clamped to the box
+    [-radius, radius]^3, until |d - target| <= res_tol.  A point never ends further than max_dist (world units) from where it
+    started and comes back as the iterate with the smallest |d - target| it has seen -- never worse than its start.  An axis
+    with |p0_a| >= radius is frozen (bits kept, gradient component 0): a vertex on a face of the box stays on that face.
+    planes: [3,C,H,W] (converted to channel-last here, once) or a ChannelLastPlanes; points [..., 3].
+    -> (points' f32 [..., 3], extras) with extras[k] for k in want:
+       "residual" f32 [...]   d(points') - target: the point query's density there minus target, in fp32
+       "status"   i32 [...]   0 converged, 1 out of steps, 2 the next step left the trust region, 3 no usable value or gradient
+                              (not finite, or a zero gradient: a point outside all three planes)
+       "evals"    i32 [...]   evaluations of (d, g) the point used, 1 .. steps + 1
+    A point's result depends on that point alone.  steps == 0 evaluates once and returns the input points."""
+    want = tuple(want)
+    unknown = set(want) - {"residual", "status", "evals"}
+    if unknown:
+        raise SculptError("project_to_isosurface: unknown output %s" % sorted(unknown))
+    _project_args(steps, max_dist, res_tol, target)
+    if points.shape[-1] != 3:
+        raise SculptError("project_to_isosurface: points %s must be [..., 3]" % (tuple(points.shape),))
+    if not isinstance(planes, ChannelLastPlanes):
+        planes = ChannelLastPlanes(planes)
+    shape = tuple(points.shape[:-1])
+    pts = _req(points.reshape(-1, 3).contiguous(), torch.float32, "points")
+    N = pts.shape[0]
+    out = torch.empty((N, 3), dtype=torch.float32, device=pts.device)
+    ex = {k: torch.empty((N,), dtype=dt, device=pts.device) if k in want else None
+          for k, dt in (("residual", torch.float32), ("status", torch.int32), ("evals", torch.int32))}
+    check(lib.sculpt_triplane_project(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(pts), N,
+                                      float(radius), _lib.QUERY_ALIGN_CORNERS if align_corners else 0, float(target), int(steps),
+                                      float(max_dist), float(res_tol), _ptr(out), _ptr(ex["residual"]), _ptr(ex["status"]),
+                                      _ptr(ex["evals"]), _stream()))
+    return out.view(*shape, 3), {k: v.view(*shape) for k, v in ex.items() if v is not None}
+
+
+def mesh_unfold(v_orig, v_new, faces, rounds=PROJECT_UNFOLD_ROUNDS):
+    """The fold guard of the projection (sculpt_mesh_unfold): v_orig f32 [Nv, 3] the vertices before they were moved, v_new
+    f32 [Nv, 3] after, faces int32 / int64 [Nf, 3] (device tensors).  A face is inverted when its normal on v_new does not point
+    into the half-space of its normal on v_orig (n0.n1 <= 0 with n0.n0 > 0; a degenerate original face is skipped); `rounds`
+    (0 .. 16) times every vertex of an inverted face takes its v_orig row back.
+    -> (v f32 [Nv, 3], a new tensor; stats i32 [2] on the device: vertices reverted, faces still inverted -- unfold_stats reads
+    it).  Nothing waits for the device.  fp32 without contraction: tests/_projref.py unfold restates it bit for bit."""
+    import numbers
+
+    if isinstance(rounds, (bool, np.bool_)) or not isinstance(rounds, numbers.Integral) or not 0 <= int(rounds) <= 16:
+        raise ValueError("rounds must be an int in 0 .. 16, got %r" % (rounds,))
+    _device_mesh(v_orig, faces, "mesh_unfold")
+    _device_mesh(v_new, faces, "mesh_unfold")
+    if tuple(v_orig.shape) != tuple(v_new.shape):
+        raise SculptError("mesh_unfold: v_orig %s and v_new %s differ in shape" % (tuple(v_orig.shape), tuple(v_new.shape)))
+    P0 = v_orig.to(torch.float32).contiguous()
+    P = v_new.to(torch.float32).clone(memory_format=torch.contiguous_format)
+    F = faces.to(torch.int64).contiguous()
+    nv, nf = P.shape[0], F.shape[0]
+    stats = torch.empty((2,), dtype=torch.int32, device=P.device)
+    mark = torch.empty((nv,), dtype=torch.int32, device=P.device) if rounds > 0 and nv > 0 else None
+    check(lib.sculpt_mesh_unfold(_ptr(P0), _ptr(P), _ptr(F), nv, nf, int(rounds), _ptr(mark), _ptr(stats), _stream()))
+    return P, stats
+
+
+def unfold_stats(stats):
+    """mesh_unfold's statistics on the host (this waits for the device): {"reverted": vertices that took their original
+    position back, "inverted": faces still inverted after the last round}."""
+    s = stats.detach().cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
+    return {"reverted": int(s[0]), "inverted": int(s[1])}
+
+
+def mesh_project(planes, mlp, vertices, faces, target, max_dist, steps=PROJECT_STEPS, res_tol=PROJECT_RES_TOL, radius=0.87,
+                 rounds=PROJECT_UNFOLD_ROUNDS, align_corners=False, want=()):
+    """project_to_isosurface on the vertices of a mesh, then mesh_unfold against the vertices it started from: two calls, no
+    host wait.  -> (vertices' f32 [Nv, 3], info): info["stats"] the guard's device statistics (unfold_stats), and
+    info[k] for k in want (project_to_isosurface's extras, of the projection BEFORE the guard: a reverted vertex keeps the
+    record of the projection it lost)."""
+    _device_mesh(vertices, faces, "mesh_project")
+    v0 = vertices.to(torch.float32).contiguous()
+    v1, extras = project_to_isosurface(planes, mlp, v0, target, max_dist, steps=steps, res_tol=res_tol, radius=radius,
+                                       align_corners=align_corners, want=want)
+    v, stats = mesh_unfold(v0, v1, faces, rounds)
+    return v, dict(extras, stats=stats)
+
+
+# ----------------------------------------------------------------------------------------------
 # transformer primitives (bf16 storage as torch.bfloat16 tensors; fp32 accumulate)
 # ----------------------------------------------------------------------------------------------
 BF16 = torch.bfloat16

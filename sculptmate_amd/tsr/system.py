@@ -980,9 +980,48 @@ class TSR(KernelEngine):
                 color = ops.dilate_fill(color.permute(2, 0, 1)[None].contiguous(), mask[None, None], iterations=it)[0].permute(1, 2, 0).contiguous()
         return Mesh(mesh.vertices, mesh.faces, None, uvs=uv, texture=color)
 
+    def _projected(self, v_pos, t_pos_idx, planes, threshold, project, resolution):
+        """ops.mesh_project with this model's field: target = float32(ln(threshold) - density_bias) (computed in double),
+        max_dist = cells x the lattice spacing 2 radius / (resolution - 1)."""
+        steps, cells = ops.project_rule(project)
+        cfg = self.renderer.cfg
+        target = float(np.float32(math.log(float(threshold)) - float(cfg.density_bias)))
+        max_dist = cells * 2.0 * float(cfg.radius) / (int(resolution) - 1)
+        return ops.mesh_project(planes, self.decoder, v_pos, t_pos_idx, target, max_dist, steps=steps, radius=cfg.radius)[0]
+
+    def project_mesh(self, mesh: Mesh, scene_code, threshold: float = 25.0, project=True, resolution=None) -> Mesh:
+        """`mesh` with its vertices on the iso-surface density_act = threshold of the field of `scene_code` ([3, C, H, W] or an
+        ops.ChannelLastPlanes): per vertex at most n Newton steps along the density's gradient inside a trust radius of `cells`
+        lattice cells of a `resolution`^3 lattice (project: True = (8, 1.0), an int n, or (n, cells): ops.project_rule;
+        resolution: default the marching-cubes resolution set last), then the fold guard (ops.mesh_project).  The faces are the
+        same and the vertices keep their indices, so vertex_colors, uvs and texture are carried over as they are;
+        vertex_normals is dropped, as Mesh.smooth drops it: the vertices have moved (TSR.field_normals at the new vertices
+        gives the normals of the surface they now lie on).  What extract_meshes(project=...) does as its last geometry step;
+        also the way to project the gathered mesh of extract_mesh_sharded.  Nothing waits for the device."""
+        steps_cells = ops.project_rule(project)   # a ValueError before anything is launched
+        if not threshold > 0:
+            raise ValueError("TSR.project_mesh: threshold must be positive, got %r" % (threshold,))
+        if self.decoder is None:
+            raise _lib.SculptError("TSR.project_mesh: the model has no weights on a device yet (load_state_dict + to(device))")
+        if resolution is None:
+            if self.isosurface_helper is None:
+                raise ValueError("TSR.project_mesh: no resolution given and no marching-cubes resolution set yet")
+            resolution = self.isosurface_helper.resolution
+        if int(resolution) < 2:
+            raise ValueError("TSR.project_mesh: resolution must be at least 2, got %r" % (resolution,))
+        if not isinstance(scene_code, ops.ChannelLastPlanes):
+            if scene_code.ndim == 5 and scene_code.shape[0] == 1:
+                scene_code = scene_code[0]
+            scene_code = scene_code.to(self.device).contiguous()
+        with torch.no_grad():
+            v = _f32(mesh.vertices, self.device)
+            f = torch.as_tensor(mesh.faces).to(self.device).contiguous()
+            v = self._projected(v, f, scene_code, threshold, steps_cells, resolution)
+        return Mesh(v, mesh.faces, mesh.vertex_colors, uvs=mesh.uvs, texture=mesh.texture)
+
     def extract_meshes(self, scene_codes, enable_texture=False, resolution: int = 256, threshold: float = 25.0,
                        x_range=None, density_events=None, bake_texture: int = 0, normals=None,
-                       keep_components=None, simplify=None, smooth=None) -> List[Mesh]:
+                       keep_components=None, simplify=None, smooth=None, project=None) -> List[Mesh]:
         """The arithmetic of system.py:171-200 without the Blender sink: returns device tensors.
         density_events: optional (start, stop) torch events recorded around the dense-grid launch (bench.py's live
         per-launch timing of the dominant kernel, on the stream it is launched on).
@@ -1001,7 +1040,12 @@ class TSR(KernelEngine):
         smooth: None (default): nothing is launched, nothing changes.  An int n in 1 .. 1000 (n iterations with lam = 0.5,
         mu = -0.53) or a tuple (n, lam, mu) (ops.smooth_rule): Taubin's lambda|mu filter on the device (ops.mesh_smooth) after
         keep_components and BEFORE simplify, so that the quadrics are built on the clean surface; faces and indices are
-        unchanged.  Mesh.smooth lets a caller choose another order."""
+        unchanged.  Mesh.smooth lets a caller choose another order.
+        project: None (default): nothing is launched, nothing changes.  True (8 Newton steps inside a trust radius of one lattice
+        cell), an int n in 1 .. 64 or a tuple (n, cells) (ops.project_rule): every vertex is moved onto the iso-surface
+        density_act = threshold of the field itself and folded faces are undone (ops.mesh_project, TSR.project_mesh) -- the
+        LAST geometry step, after keep_components, smooth and simplify and before the colours, the bake and the normals, which are
+        therefore evaluated at the projected vertices; faces and indices are unchanged.  Needs threshold > 0."""
         if normals not in (None, "field", "faces"):
             raise ValueError("normals must be None, 'field' or 'faces', got %r" % (normals,))
         if keep_components is not None:
@@ -1010,6 +1054,10 @@ class TSR(KernelEngine):
             ops.simplify_rule(simplify)
         if smooth is not None:
             ops.smooth_rule(smooth)
+        if project is not None:
+            ops.project_rule(project)
+            if not threshold > 0:
+                raise ValueError("project needs a positive threshold (the surface is ln(threshold) in the raw density), got %r" % (threshold,))
         bake = int(bake_texture) if enable_texture else 0
         self.set_marching_cubes_resolution(resolution)
         r = self.renderer.cfg.radius
@@ -1032,6 +1080,8 @@ class TSR(KernelEngine):
                     v_pos = ops.mesh_smooth(v_pos, t_pos_idx, smooth)
                 if simplify is not None:
                     v_pos, t_pos_idx = ops.mesh_simplify(v_pos, t_pos_idx, simplify)[:2]
+                if project is not None:
+                    v_pos = self._projected(v_pos, t_pos_idx, planes, threshold, project, R)
                 out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
                 continue
             vol = ops.density_grid(planes, self.decoder, R, precision=self.decoder_precision, events=density_events, **dkw)
@@ -1042,6 +1092,8 @@ class TSR(KernelEngine):
                 v_pos = ops.mesh_smooth(v_pos, t_pos_idx, smooth)
             if simplify is not None:
                 v_pos, t_pos_idx = ops.mesh_simplify(v_pos, t_pos_idx, simplify)[:2]
+            if project is not None:
+                v_pos = self._projected(v_pos, t_pos_idx, planes, threshold, project, R)
             out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
         return out
 
@@ -1143,7 +1195,8 @@ class TSR(KernelEngine):
         (sculptmate_amd/slab.py).  Without a process group the slabs run one after the other here.
         It takes no keep_components: components cross the slabs, so the gathered mesh is filtered afterwards, with
         Mesh.keep_components.  It takes no smooth either, for the same reason (a slab's cut is an open border, whose vertices
-        smoothing holds fixed): smooth the gathered mesh with Mesh.smooth."""
+        smoothing holds fixed): smooth the gathered mesh with Mesh.smooth.  It takes no project: use TSR.project_mesh on the
+        gathered mesh."""
         import torch.distributed as dist
 
         from .. import slab
@@ -1167,14 +1220,14 @@ class TSR(KernelEngine):
         return Mesh(v_pos, t_pos_idx, color)
 
     def extract_mesh(self, scene_codes, enable_texture=False, mesh_name="NewMesh", resolution: int = 256,
-                     threshold: float = 25.0, bake_texture: int = 0, normals=None, keep_components=None, simplify=None, smooth=None):
-        """system.py:171-200: same signature (+ bake_texture, normals, keep_components, simplify and smooth, see extract_meshes: the sink
-        receives the filtered, smoothed, simplified mesh); pushes each mesh into the sink (Blender when
+                     threshold: float = 25.0, bake_texture: int = 0, normals=None, keep_components=None, simplify=None, smooth=None, project=None):
+        """system.py:171-200: same signature (+ bake_texture, normals, keep_components, simplify, smooth and project, see extract_meshes: the sink
+        receives the filtered, smoothed, simplified, projected mesh); pushes each mesh into the sink (Blender when
         `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
         the textured sink (per-loop UVs + an image-texture material).  The sinks take no normals (Blender shades a mesh with
         shared vertices smooth by itself); they stay on the returned meshes."""
         meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture, normals=normals,
-                                     keep_components=keep_components, simplify=simplify, smooth=smooth)
+                                     keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)
         sink = self.mesh_sink or _default_sink()
         for m in meshes:
             if m.texture is not None:
@@ -1190,7 +1243,7 @@ class TSR(KernelEngine):
         return meshes
 
     def run_async(self, image, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, tokens=None,
-                  normals=None, keep_components=None, simplify=None, smooth=None):
+                  normals=None, keep_components=None, simplify=None, smooth=None, project=None):
         """One host image -> PendingMesh.  The image goes host -> HBM, the forward and the mesh extraction are queued on
         the current stream, and the mesh (the reference's `.cpu().numpy()` at system.py:200) is copied device -> pinned
         host memory on a separate copy stream, so the copy of mesh i runs under the kernels of image i + 1.
@@ -1199,7 +1252,7 @@ class TSR(KernelEngine):
         with torch.no_grad():
             codes = self.forward([image], self.device) if tokens is None else self.forward_tokens(tokens)
             m = self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals,
-                                    keep_components=keep_components, simplify=simplify, smooth=smooth)[0]
+                                    keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)[0]
         return self._mesh_to_host_async(m)
 
     def _mesh_to_host_async(self, m) -> PendingMesh:
@@ -1230,7 +1283,7 @@ class TSR(KernelEngine):
         return PendingMesh(host, done, tuple(leases))
 
     def run(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, batch=None,
-            normals=None, keep_components=None, simplify=None, smooth=None) -> List[Mesh]:
+            normals=None, keep_components=None, simplify=None, smooth=None, project=None) -> List[Mesh]:
         """Headless entry point: images -> list of Mesh with host (NumPy) arrays; the device -> host copy of mesh i overlaps the
         kernels that follow it.
         batch (images per transformer pass; None = the default): in the bf16 mode a stacked pass of several images gives each
@@ -1242,20 +1295,21 @@ class TSR(KernelEngine):
         normals: None, "field" or "faces" (extract_meshes): Mesh.vertex_normals as float32 [Nv, 3] on the host.
         keep_components: None, "largest", an int or a float (extract_meshes): the meshes without their small components.
         simplify: None, an int or a float (extract_meshes): the meshes reduced by quadric-error collapses on the device.
-        smooth: None, an int or (n, lam, mu) (extract_meshes): the meshes after Taubin smoothing on the device, before simplify."""
+        smooth: None, an int or (n, lam, mu) (extract_meshes): the meshes after Taubin smoothing on the device, before simplify.
+        project: None, True, an int or (n, cells) (extract_meshes): the vertices on the field's iso-surface, the last geometry step."""
         images = _as_image_list(images)
         if batch is None:
             batch = self.RUN_BATCH if (self.precision == "bf16" and len(images) >= 2) else 1
         if batch <= 1 or len(images) < 2:
             return [p.result() for p in self.run_pipelined(images, mc_resolution, threshold, enable_texture, normals=normals,
-                                                              keep_components=keep_components, simplify=simplify, smooth=smooth)]
+                                                              keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)]
         return [p.result() for p in self.run_batched(images, batch, mc_resolution, threshold, enable_texture, normals=normals,
-                                                        keep_components=keep_components, simplify=simplify, smooth=smooth)]
+                                                        keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)]
 
     RUN_BATCH = 8   # images per transformer pass of TSR.run in the bf16 mode (4: 139.7, 8: 143.5 meshes/s device to device)
 
     def run_batched(self, images, batch: int = 4, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False,
-                    normals=None, keep_components=None, simplify=None, smooth=None):
+                    normals=None, keep_components=None, simplify=None, smooth=None, project=None):
         """images (host or device) -> list of PendingMesh through batched forward passes of `batch` images each."""
         images = list(images)
         pending = []
@@ -1266,27 +1320,27 @@ class TSR(KernelEngine):
                 with torch.no_grad():
                     codes = self.forward(images[i:i + self.max_batch], self.device)
                     for m in self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals,
-                                                 keep_components=keep_components, simplify=simplify, smooth=smooth):
+                                                 keep_components=keep_components, simplify=simplify, smooth=smooth, project=project):
                         pending.append(self._mesh_to_host_async(m))
         finally:
             self.max_batch = keep
         return pending
 
     def run_pipelined(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, normals=None,
-                      keep_components=None, simplify=None, smooth=None):
+                      keep_components=None, simplify=None, smooth=None, project=None):
         """images (host or device) -> list of PendingMesh, with the tokenizer of image i + 1 queued beside the backbone /
         density grid / marching cubes of image i (tokens_async) and the device -> host copy of mesh i under image i + 1."""
         images = list(images)
         if len(images) < 2:
             return [self.run_async(im, mc_resolution, threshold, enable_texture, normals=normals, keep_components=keep_components,
-                                   simplify=simplify, smooth=smooth)
+                                   simplify=simplify, smooth=smooth, project=project)
                     for im in images]
         pending, nxt = [], self.tokens_async(images[0])
         for i, im in enumerate(images):
             cur = nxt
             nxt = self.tokens_async(images[i + 1]) if i + 1 < len(images) else None
             pending.append(self.run_async(im, mc_resolution, threshold, enable_texture, tokens=cur, normals=normals,
-                                          keep_components=keep_components, simplify=simplify, smooth=smooth))
+                                          keep_components=keep_components, simplify=simplify, smooth=smooth, project=project))
         return pending
 
 
