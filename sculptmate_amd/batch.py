@@ -73,14 +73,8 @@ def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture
     submit loop (0: synchronously, inside the loop).
     batch > 1: this rank's images go through the transformer `batch` per pass (TSR.run_batched: the reference's batched forward,
     3.9 instead of 5.3 ms per image at 4); the meshes then differ from single-image calls by the bf16 transformer's rounding.
-    keep_components: None, "largest", an int or a float (TSR.extract_meshes): every mesh without its small connected components;
-    handed to the model only when set.
-    simplify: None, an int or a float (TSR.extract_meshes): every mesh reduced by quadric-error collapses; handed to the model
-    only when set.
-    smooth: None, an int or (n, lam, mu) (TSR.extract_meshes): every mesh after Taubin smoothing, before simplify; handed to the
-    model only when set.
-    project: None, True, an int or (n, cells) (TSR.extract_meshes): every mesh with its vertices on the field's iso-surface, the
-    last geometry step; handed to the model only when set.
+    keep_components, smooth, simplify, project: the geometry options of TSR.extract_meshes, described there; each is handed to
+    the model only when set.
     A rank that fails still takes part in the one exchange, with an error marker in place of its counts: every rank then
     raises, none is left waiting in a collective the failed rank never enters."""
     import torch.distributed as dist
@@ -93,13 +87,8 @@ def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture
     if fmt not in ("ply", "npz", "obj"):
         raise ValueError("format must be 'ply', 'npz' or 'obj'")
     local, counts = {}, []
-    ckw = {} if keep_components is None else {"keep_components": keep_components}
-    if simplify is not None:
-        ckw["simplify"] = simplify
-    if smooth is not None:
-        ckw["smooth"] = smooth
-    if project is not None:
-        ckw["project"] = project
+    ckw = {k: x for k, x in dict(keep_components=keep_components, simplify=simplify, smooth=smooth, project=project).items()
+           if x is not None}
     writer = MeshWriter(writers) if (out_dir is not None and writers) else None
     failure = None
 

@@ -5,6 +5,7 @@ passes raw device pointers + sizes into libsculpt_hip.so.  No function has a CPU
 """
 import ctypes
 import math
+import numbers
 import threading
 import os
 
@@ -461,6 +462,16 @@ _MC_REC_CAPACITY = {} # (device, n0, n1, n2) -> active-cell records of the works
 _MC_SPECULATE = not _lib.form_has("SCULPT_MC_FORM", "nospeculate")   # A/B: the two-phase path every time
 
 
+def _is_count(n, lo, hi=math.inf):
+    """n is an integer in lo .. hi and no bool: what the rules below ask of a count."""
+    return not isinstance(n, (bool, np.bool_)) and isinstance(n, numbers.Integral) and lo <= int(n) <= hi
+
+
+def _is_real(x):
+    """x is a real number and no bool."""
+    return not isinstance(x, (bool, np.bool_)) and isinstance(x, numbers.Real)
+
+
 # ----------------------------------------------------------------------------------------------
 # connected components of a mesh (csrc/mesh_components.hip)
 # ----------------------------------------------------------------------------------------------
@@ -468,19 +479,13 @@ def keep_rule(keep):
     """`keep` of mesh_keep_components -> (rule, min_faces, fraction) of sculpt_mesh_components_launch: "largest", an int >= 1
     (at least that many faces) or a float in (0, 1) (at least that fraction of the largest component's faces).  Anything else,
     bool included, is a ValueError -- raised here, before anything is launched."""
-    import numbers
-
     if isinstance(keep, str):
         if keep == "largest":
             return _lib.CC_KEEP_LARGEST, 0, 0.0
-    elif isinstance(keep, (bool, np.bool_)):
-        pass
-    elif isinstance(keep, numbers.Integral):
-        if int(keep) >= 1:
-            return _lib.CC_KEEP_MIN_FACES, int(keep), 0.0
-    elif isinstance(keep, numbers.Real):
-        if 0.0 < float(keep) < 1.0:
-            return _lib.CC_KEEP_FRACTION, 0, float(keep)
+    elif _is_count(keep, 1):
+        return _lib.CC_KEEP_MIN_FACES, int(keep), 0.0
+    elif _is_real(keep) and 0.0 < float(keep) < 1.0:
+        return _lib.CC_KEEP_FRACTION, 0, float(keep)
     raise ValueError("keep must be 'largest', an int >= 1 (minimum faces) or a float in (0, 1) (fraction of the largest "
                      "component), got %r" % (keep,))
 
@@ -570,16 +575,10 @@ def simplify_rule(simplify):
     """`simplify` of mesh_simplify -> ("faces", n) for an int n >= 1 (a target face count) or ("ratio", x) for a float x in
     (0, 1) (the target is floor(x * Nf)).  Anything else, bool included, is a ValueError -- raised here, before anything is
     launched."""
-    import numbers
-
-    if isinstance(simplify, (bool, np.bool_, str)):
-        pass
-    elif isinstance(simplify, numbers.Integral):
-        if int(simplify) >= 1:
-            return "faces", int(simplify)
-    elif isinstance(simplify, numbers.Real):
-        if 0.0 < float(simplify) < 1.0:
-            return "ratio", float(simplify)
+    if _is_count(simplify, 1):
+        return "faces", int(simplify)
+    if _is_real(simplify) and 0.0 < float(simplify) < 1.0:
+        return "ratio", float(simplify)
     raise ValueError("simplify must be an int >= 1 (target faces) or a float in (0, 1) (ratio of the faces), got %r" % (simplify,))
 
 
@@ -640,18 +639,10 @@ def smooth_rule(smooth):
     a 3-tuple (n, lam, mu) with 0 < lam <= 1 and either mu == 0 (plain Laplacian smoothing: it shrinks) or -1 <= mu < -lam
     (Taubin's pass-band condition).  Anything else -- bool, str, a bare float, NaN, another length -- is a ValueError, raised
     here, before anything is launched."""
-    import numbers
-
-    def count(n):
-        return (not isinstance(n, (bool, np.bool_)) and isinstance(n, numbers.Integral)
-                and 1 <= int(n) <= SMOOTH_MAX_ITERATIONS)
-
-    def real(x):
-        return not isinstance(x, (bool, np.bool_)) and isinstance(x, numbers.Real)
-
-    if count(smooth):
+    if _is_count(smooth, 1, SMOOTH_MAX_ITERATIONS):
         return int(smooth), SMOOTH_LAMBDA, SMOOTH_MU
-    if isinstance(smooth, tuple) and len(smooth) == 3 and count(smooth[0]) and real(smooth[1]) and real(smooth[2]):
+    if (isinstance(smooth, tuple) and len(smooth) == 3 and _is_count(smooth[0], 1, SMOOTH_MAX_ITERATIONS)
+            and _is_real(smooth[1]) and _is_real(smooth[2])):
         lam, mu = float(smooth[1]), float(smooth[2])
         if 0.0 < lam <= 1.0 and (mu == 0.0 or -1.0 <= mu < -lam):   # a NaN fails every comparison
             return int(smooth[0]), lam, mu
@@ -694,27 +685,20 @@ def project_rule(project):
     """`project` of the mesh projection -> (steps, max_cells): True (8 steps, a trust radius of 1 lattice cell), an int n in
     1 .. 64 (n steps, 1 cell) or a tuple (n, cells) with 0 < cells <= 8.  Anything else -- False, None, a str, a bare float, NaN,
     another length -- is a ValueError, raised here, before anything is launched."""
-    import numbers
-
-    def count(n):
-        return (not isinstance(n, (bool, np.bool_)) and isinstance(n, numbers.Integral) and 1 <= int(n) <= PROJECT_MAX_STEPS)
-
     if project is True or (isinstance(project, np.bool_) and bool(project)):
         return PROJECT_STEPS, PROJECT_CELLS
-    if count(project):
+    if _is_count(project, 1, PROJECT_MAX_STEPS):
         return int(project), PROJECT_CELLS
-    if isinstance(project, tuple) and len(project) == 2 and count(project[0]):
+    if isinstance(project, tuple) and len(project) == 2 and _is_count(project[0], 1, PROJECT_MAX_STEPS):
         cells = project[1]
-        if not isinstance(cells, (bool, np.bool_)) and isinstance(cells, numbers.Real) and 0.0 < float(cells) <= PROJECT_MAX_CELLS:
+        if _is_real(cells) and 0.0 < float(cells) <= PROJECT_MAX_CELLS:
             return int(project[0]), float(cells)   # a NaN fails the comparison
     raise ValueError("project must be True, an int in 1 .. %d (steps) or (steps, cells) with 0 < cells <= %g, got %r"
                      % (PROJECT_MAX_STEPS, PROJECT_MAX_CELLS, project))
 
 
 def _project_args(steps, max_dist, res_tol, target):
-    import numbers
-
-    if isinstance(steps, (bool, np.bool_)) or not isinstance(steps, numbers.Integral) or not 0 <= int(steps) <= PROJECT_MAX_STEPS:
+    if not _is_count(steps, 0, PROJECT_MAX_STEPS):
         raise ValueError("steps must be an int in 0 .. %d, got %r" % (PROJECT_MAX_STEPS, steps))
     for name, x in (("max_dist", max_dist), ("res_tol", res_tol)):
         if not (0.0 < float(np.float32(x)) < math.inf):   # as the kernel sees it; a NaN fails the comparison
@@ -767,9 +751,7 @@ def mesh_unfold(v_orig, v_new, faces, rounds=PROJECT_UNFOLD_ROUNDS):
     (0 .. 16) times every vertex of an inverted face takes its v_orig row back.
     -> (v f32 [Nv, 3], a new tensor; stats i32 [2] on the device: vertices reverted, faces still inverted -- unfold_stats reads
     it).  Nothing waits for the device.  fp32 without contraction: tests/_projref.py unfold restates it bit for bit."""
-    import numbers
-
-    if isinstance(rounds, (bool, np.bool_)) or not isinstance(rounds, numbers.Integral) or not 0 <= int(rounds) <= 16:
+    if not _is_count(rounds, 0, 16):
         raise ValueError("rounds must be an int in 0 .. 16, got %r" % (rounds,))
     _device_mesh(v_orig, faces, "mesh_unfold")
     _device_mesh(v_new, faces, "mesh_unfold")

@@ -1048,16 +1048,8 @@ class TSR(KernelEngine):
         therefore evaluated at the projected vertices; faces and indices are unchanged.  Needs threshold > 0."""
         if normals not in (None, "field", "faces"):
             raise ValueError("normals must be None, 'field' or 'faces', got %r" % (normals,))
-        if keep_components is not None:
-            ops.keep_rule(keep_components)   # a ValueError before anything is launched
-        if simplify is not None:
-            ops.simplify_rule(simplify)
-        if smooth is not None:
-            ops.smooth_rule(smooth)
-        if project is not None:
-            ops.project_rule(project)
-            if not threshold > 0:
-                raise ValueError("project needs a positive threshold (the surface is ln(threshold) in the raw density), got %r" % (threshold,))
+        geometry = dict(keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)
+        self._check_geometry(threshold, **geometry)   # a ValueError before anything is launched
         bake = int(bake_texture) if enable_texture else 0
         self.set_marching_cubes_resolution(resolution)
         r = self.renderer.cfg.radius
@@ -1074,28 +1066,40 @@ class TSR(KernelEngine):
             # density_act - threshold == -(-(density_act - threshold))  (system.py:184, isosurface.py:45)
             if self._filter_applies(planes, R, threshold):
                 v_pos, t_pos_idx = self._extract_filtered(planes, R, mc, dkw, density_events)
-                if keep_components is not None:
-                    v_pos, t_pos_idx = ops.mesh_keep_components(v_pos, t_pos_idx, keep_components)[:2]
-                if smooth is not None:
-                    v_pos = ops.mesh_smooth(v_pos, t_pos_idx, smooth)
-                if simplify is not None:
-                    v_pos, t_pos_idx = ops.mesh_simplify(v_pos, t_pos_idx, simplify)[:2]
-                if project is not None:
-                    v_pos = self._projected(v_pos, t_pos_idx, planes, threshold, project, R)
-                out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
-                continue
-            vol = ops.density_grid(planes, self.decoder, R, precision=self.decoder_precision, events=density_events, **dkw)
-            v_pos, t_pos_idx = mc(vol)   # (both decoder modes have the fp32 range: a NaN here is a NaN of the model)
-            if keep_components is not None:
-                v_pos, t_pos_idx = ops.mesh_keep_components(v_pos, t_pos_idx, keep_components)[:2]
-            if smooth is not None:
-                v_pos = ops.mesh_smooth(v_pos, t_pos_idx, smooth)
-            if simplify is not None:
-                v_pos, t_pos_idx = ops.mesh_simplify(v_pos, t_pos_idx, simplify)[:2]
-            if project is not None:
-                v_pos = self._projected(v_pos, t_pos_idx, planes, threshold, project, R)
+            else:
+                vol = ops.density_grid(planes, self.decoder, R, precision=self.decoder_precision, events=density_events, **dkw)
+                v_pos, t_pos_idx = mc(vol)   # (both decoder modes have the fp32 range: a NaN here is a NaN of the model)
+            v_pos, t_pos_idx = self._reshaped(v_pos, t_pos_idx, planes, threshold, R, **geometry)
             out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
         return out
+
+    @staticmethod
+    def _check_geometry(threshold, keep_components=None, simplify=None, smooth=None, project=None):
+        """The rules of the geometry options that are set (ops.*_rule; an option left None is not looked at): a ValueError
+        here comes before anything is launched."""
+        if keep_components is not None:
+            ops.keep_rule(keep_components)
+        if simplify is not None:
+            ops.simplify_rule(simplify)
+        if smooth is not None:
+            ops.smooth_rule(smooth)
+        if project is not None:
+            ops.project_rule(project)
+            if not threshold > 0:
+                raise ValueError("project needs a positive threshold (the surface is ln(threshold) in the raw density), got %r" % (threshold,))
+
+    def _reshaped(self, v_pos, t_pos_idx, planes, threshold, R, keep_components=None, simplify=None, smooth=None, project=None):
+        """The geometry half of extract_meshes, in its fixed order: keep_components -> smooth -> simplify -> project, each only
+        when set -> (v_pos, t_pos_idx).  A new geometry step goes in here, and into _check_geometry, and nowhere else."""
+        if keep_components is not None:
+            v_pos, t_pos_idx = ops.mesh_keep_components(v_pos, t_pos_idx, keep_components)[:2]
+        if smooth is not None:
+            v_pos = ops.mesh_smooth(v_pos, t_pos_idx, smooth)
+        if simplify is not None:
+            v_pos, t_pos_idx = ops.mesh_simplify(v_pos, t_pos_idx, simplify)[:2]
+        if project is not None:
+            v_pos = self._projected(v_pos, t_pos_idx, planes, threshold, project, R)
+        return v_pos, t_pos_idx
 
     def _textured(self, v_pos, t_pos_idx, planes, enable_texture, bake, normals=None):
         """The appearance half of extract_meshes: nothing, vertex colours (system.py:189-193) or a baked texture; and the
@@ -1221,8 +1225,8 @@ class TSR(KernelEngine):
 
     def extract_mesh(self, scene_codes, enable_texture=False, mesh_name="NewMesh", resolution: int = 256,
                      threshold: float = 25.0, bake_texture: int = 0, normals=None, keep_components=None, simplify=None, smooth=None, project=None):
-        """system.py:171-200: same signature (+ bake_texture, normals, keep_components, simplify, smooth and project, see extract_meshes: the sink
-        receives the filtered, smoothed, simplified, projected mesh); pushes each mesh into the sink (Blender when
+        """system.py:171-200: same signature (+ bake_texture, normals and the geometry options keep_components, smooth, simplify,
+        project, all described at extract_meshes: the sink receives the final mesh); pushes each mesh into the sink (Blender when
         `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
         the textured sink (per-loop UVs + an image-texture material).  The sinks take no normals (Blender shades a mesh with
         shared vertices smooth by itself); they stay on the returned meshes."""
@@ -1293,18 +1297,14 @@ class TSR(KernelEngine):
         (test_run_batches_by_default_and_returns_the_serial_meshes).  The limb modes default to one image per pass with the
         tokenizer look-ahead (run_pipelined).  batch=1 forces that everywhere.
         normals: None, "field" or "faces" (extract_meshes): Mesh.vertex_normals as float32 [Nv, 3] on the host.
-        keep_components: None, "largest", an int or a float (extract_meshes): the meshes without their small components.
-        simplify: None, an int or a float (extract_meshes): the meshes reduced by quadric-error collapses on the device.
-        smooth: None, an int or (n, lam, mu) (extract_meshes): the meshes after Taubin smoothing on the device, before simplify.
-        project: None, True, an int or (n, cells) (extract_meshes): the vertices on the field's iso-surface, the last geometry step."""
+        keep_components, smooth, simplify, project: the geometry options of extract_meshes, described there."""
         images = _as_image_list(images)
         if batch is None:
             batch = self.RUN_BATCH if (self.precision == "bf16" and len(images) >= 2) else 1
+        kw = dict(normals=normals, keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)
         if batch <= 1 or len(images) < 2:
-            return [p.result() for p in self.run_pipelined(images, mc_resolution, threshold, enable_texture, normals=normals,
-                                                              keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)]
-        return [p.result() for p in self.run_batched(images, batch, mc_resolution, threshold, enable_texture, normals=normals,
-                                                        keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)]
+            return [p.result() for p in self.run_pipelined(images, mc_resolution, threshold, enable_texture, **kw)]
+        return [p.result() for p in self.run_batched(images, batch, mc_resolution, threshold, enable_texture, **kw)]
 
     RUN_BATCH = 8   # images per transformer pass of TSR.run in the bf16 mode (4: 139.7, 8: 143.5 meshes/s device to device)
 
@@ -1331,16 +1331,14 @@ class TSR(KernelEngine):
         """images (host or device) -> list of PendingMesh, with the tokenizer of image i + 1 queued beside the backbone /
         density grid / marching cubes of image i (tokens_async) and the device -> host copy of mesh i under image i + 1."""
         images = list(images)
+        kw = dict(normals=normals, keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)
         if len(images) < 2:
-            return [self.run_async(im, mc_resolution, threshold, enable_texture, normals=normals, keep_components=keep_components,
-                                   simplify=simplify, smooth=smooth, project=project)
-                    for im in images]
+            return [self.run_async(im, mc_resolution, threshold, enable_texture, **kw) for im in images]
         pending, nxt = [], self.tokens_async(images[0])
         for i, im in enumerate(images):
             cur = nxt
             nxt = self.tokens_async(images[i + 1]) if i + 1 < len(images) else None
-            pending.append(self.run_async(im, mc_resolution, threshold, enable_texture, tokens=cur, normals=normals,
-                                          keep_components=keep_components, simplify=simplify, smooth=smooth, project=project))
+            pending.append(self.run_async(im, mc_resolution, threshold, enable_texture, tokens=cur, **kw))
         return pending
 
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import _tsrmodel
 from oracle import capi
 from sculptmate_amd import synth
 
@@ -130,19 +131,8 @@ def test_refusals_and_the_empty_image(scene, cuda):
 
 @pytest.fixture(scope="module")
 def model(cuda):
-    """A small synthetic TSR, one scene code and a density threshold its random weights reach (the grid's median)."""
-    from sculptmate_amd import ops
-    from sculptmate_amd.tsr import TSR
-    from sculptmate_amd.tsr.spec import SMALL_CFG
-
-    m = TSR(SMALL_CFG, pos_embed_mode="size")
-    m.load_state_dict(synth.tsr_state(31, SMALL_CFG))
-    m.to(cuda)
-    img = synth.composite_rgb(synth.image_rgba(seed=32, size=SMALL_CFG["cond_image_size"]))
-    codes = m([img], device=cuda)
-    threshold = float(ops.density_grid(codes[0].contiguous(), m.decoder, 32).median())
-    plain = m.extract_meshes(codes, enable_texture=True, resolution=32, threshold=threshold)[0]
-    return dict(m=m, codes=codes, threshold=threshold, plain=plain)
+    """The shared small model at resolution 32; the plain mesh carries vertex colours."""
+    return _tsrmodel.small_model(cuda, 32, enable_texture=True)
 
 
 def _dilate(mask, steps):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import _tsrmodel
 from conftest import GOLDEN
 from sculptmate_amd import synth
 
@@ -136,19 +137,8 @@ def test_refusals(scene, cuda):
 
 @pytest.fixture(scope="module")
 def model(cuda):
-    """A small synthetic TSR, one scene code and a density threshold its random weights reach (the grid's median)."""
-    from sculptmate_amd import ops
-    from sculptmate_amd.tsr import TSR
-    from sculptmate_amd.tsr.spec import SMALL_CFG
-
-    m = TSR(SMALL_CFG, pos_embed_mode="size")
-    m.load_state_dict(synth.tsr_state(31, SMALL_CFG))
-    m.to(cuda)
-    img = synth.composite_rgb(synth.image_rgba(seed=32, size=SMALL_CFG["cond_image_size"]))
-    codes = m([img], device=cuda)
-    threshold = float(ops.density_grid(codes[0].contiguous(), m.decoder, 32).median())
-    plain = m.extract_meshes(codes, resolution=32, threshold=threshold)[0]
-    return dict(m=m, img=img, codes=codes, threshold=threshold, plain=plain)
+    """The shared small model at resolution 32 and its bare plain mesh."""
+    return _tsrmodel.small_model(cuda, 32)
 
 
 def test_model_surface(model):

@@ -6,7 +6,6 @@ Point sets:
   (B) the 2043 points of tests/golden/field_normal.npz on their hostile field (zero-padding band, cut-off plane pairs, 128 points
       outside every plane, an 8-aligned run), t = the median of density64 over its set (a), max_dist = one cell of a 64^3 lattice.
 res_tol = 1e-3 throughout.  One fused result per set (steps = 8, every output) is computed once and shared; nothing modifies it."""
-import math
 import os
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 import torch
 
 import _projref as ref
+import _tsrmodel
 from conftest import GOLDEN
 from sculptmate_amd import synth
 
@@ -209,22 +209,8 @@ def test_the_guard_equals_its_restatement(sets, rounds):
 # --------------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(cuda):
-    """A small synthetic TSR, one scene code and a density threshold its random weights reach (the grid's median)."""
-    from sculptmate_amd import ops
-    from sculptmate_amd.tsr import TSR
-    from sculptmate_amd.tsr.spec import SMALL_CFG
-
-    m = TSR(SMALL_CFG, pos_embed_mode="size")
-    m.load_state_dict(synth.tsr_state(31, SMALL_CFG))
-    m.to(cuda)
-    img = synth.composite_rgb(synth.image_rgba(seed=32, size=SMALL_CFG["cond_image_size"]))
-    codes = m([img], device=cuda)
-    threshold = float(ops.density_grid(codes[0].contiguous(), m.decoder, 32).median())
-    plain = m.extract_meshes(codes, resolution=32, threshold=threshold)[0]
-    cfg = m.renderer.cfg
-    target = float(np.float32(math.log(threshold) - float(cfg.density_bias)))
-    return dict(m=m, img=img, codes=codes, threshold=threshold, plain=plain, target=target, cell=2.0 * float(cfg.radius) / 31,
-                radius=float(cfg.radius))
+    """The shared small model at resolution 32, its bare plain mesh and the projection's target / cell / radius."""
+    return _tsrmodel.small_model(cuda, 32, project_keys=True)
 
 
 def test_model_surface(model):

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import _qemref
-from sculptmate_amd import synth
+import _tsrmodel
 
 pytestmark = pytest.mark.gpu
 
@@ -293,21 +293,8 @@ def test_determinism_and_face_order(cuda, sphere):
 # --------------------------------------------------------------------------------------------- 3. through the model
 @pytest.fixture(scope="module")
 def model(cuda):
-    """The small synthetic TSR of the other GPU tests, one scene code, the threshold of tests/test_gpu_mesh_components.py (the
-    grid's median) and ONE unsimplified mesh at resolution 64 (shared, never modified)."""
-    from sculptmate_amd import ops
-    from sculptmate_amd.tsr import TSR
-    from sculptmate_amd.tsr.spec import SMALL_CFG
-
-    m = TSR(SMALL_CFG, pos_embed_mode="size")
-    m.load_state_dict(synth.tsr_state(31, SMALL_CFG))
-    m.to(cuda)
-    img = synth.composite_rgb(synth.image_rgba(seed=32, size=SMALL_CFG["cond_image_size"]))
-    codes = m([img], device=cuda)
-    threshold = float(ops.density_grid(codes[0].contiguous(), m.decoder, 64).median())
-    kw = dict(resolution=64, threshold=threshold)
-    plain = m.extract_meshes(codes, enable_texture=True, normals="field", **kw)[0]
-    return dict(m=m, img=img, codes=codes, threshold=threshold, kw=kw, plain=plain)
+    """The shared small model at resolution 64; the plain mesh carries colours and field normals."""
+    return _tsrmodel.small_model(cuda, 64, enable_texture=True, normals="field")
 
 
 def test_extract_meshes_is_the_three_calls_in_order(model):

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import _smoothref as ref
+import _tsrmodel
 from sculptmate_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -86,21 +87,8 @@ def test_noisy_icosphere_bit_for_bit(cuda, sphere, rule):
 # --------------------------------------------------------------------------------------------------- through the model
 @pytest.fixture(scope="module")
 def model(cuda):
-    """The small synthetic TSR of the other GPU tests, one scene code, the grid's median as the threshold, and ONE plain mesh at
-    resolution 64 (shared, never modified)."""
-    from sculptmate_amd import ops
-    from sculptmate_amd.tsr import TSR
-    from sculptmate_amd.tsr.spec import SMALL_CFG
-
-    m = TSR(SMALL_CFG, pos_embed_mode="size")
-    m.load_state_dict(synth.tsr_state(31, SMALL_CFG))
-    m.to(cuda)
-    img = synth.composite_rgb(synth.image_rgba(seed=32, size=SMALL_CFG["cond_image_size"]))
-    codes = m([img], device=cuda)
-    threshold = float(ops.density_grid(codes[0].contiguous(), m.decoder, 64).median())
-    kw = dict(resolution=64, threshold=threshold)
-    plain = m.extract_meshes(codes, enable_texture=True, normals="field", **kw)[0]
-    return dict(m=m, img=img, codes=codes, threshold=threshold, kw=kw, plain=plain)
+    """The shared small model at resolution 64; the plain mesh carries colours and field normals."""
+    return _tsrmodel.small_model(cuda, 64, enable_texture=True, normals="field")
 
 
 def test_marching_cubes_mesh_of_a_synthetic_field_bit_for_bit(cuda, model):

@@ -14,9 +14,7 @@ the times: the fused kernel skips what the composed route evaluates and throws a
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -24,27 +22,10 @@ if ROOT not in sys.path:
 
 import torch  # noqa: E402
 
+from _timing import seeded_mesh, timed  # noqa: E402
+
 RESOLUTIONS = [2048, 1024]
 MC_RES, THRESHOLD = 256, 25.0
-
-
-def stats(ms):
-    q = statistics.quantiles(ms, n=4)
-    return {"median_ms": round(statistics.median(ms), 3), "q1_ms": round(q[0], 3), "q3_ms": round(q[2], 3),
-            "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "runs": len(ms)}
-
-
-def timed(fn, runs, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(runs):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return stats(out)
 
 
 def main():
@@ -56,20 +37,11 @@ def main():
     a = ap.parse_args()
     if a.runs < 20:
         ap.error("--runs must be at least 20")
-    from sculptmate_amd import ops, synth
+    from sculptmate_amd import ops
     from sculptmate_amd.sf3d.unwrap import BoxProjectionUnwrapper
-    from sculptmate_amd.tsr import TSR
 
     dev = torch.device("cuda:0")
-    sd = synth.tsr_state(seed=0)
-    model = TSR(pos_embed_mode="scale_factor")
-    model.load_state_dict(sd)
-    model.to(dev)
-    img = torch.from_numpy(synth.composite_rgb(synth.image_rgba(seed=100))).to(dev).contiguous()
-    with torch.no_grad():
-        synth.calibrate_tsr_density_bias(model, sd, img, 0.015, THRESHOLD)
-        code = model([img], device=dev)[0].contiguous()
-        mesh = model.extract_meshes([code], False, MC_RES, THRESHOLD)[0]
+    model, code, mesh = seeded_mesh(dev, MC_RES, THRESHOLD)
     v, f = mesh.vertices, mesh.faces
     radius = model.renderer.cfg.radius
     planes = ops.ChannelLastPlanes(code)
@@ -80,8 +52,8 @@ def main():
               "island_padding": a.island_padding, "decoder_hidden_layers": int(model.decoder.n_hidden), "resolutions": {}}
     nrm = ops.vertex_normals(v, f)
     uv, _ = unwrap(v, nrm, f, a.island_padding)
-    shared = {"normals": timed(lambda: ops.vertex_normals(v, f), a.runs, a.warmup),
-              "unwrap": timed(lambda: unwrap(v, nrm, f, a.island_padding), a.runs, a.warmup)}
+    shared = {"normals": timed(lambda: ops.vertex_normals(v, f), a.runs, a.warmup)[1],
+              "unwrap": timed(lambda: unwrap(v, nrm, f, a.island_padding), a.runs, a.warmup)[1]}
     result["mesh_stages"] = shared
     print("mesh: %d vertices, %d faces; normals %.3f ms, unwrap %.3f ms" % (v.shape[0], f.shape[0], shared["normals"]["median_ms"],
                                                                            shared["unwrap"]["median_ms"]), flush=True)
@@ -104,15 +76,15 @@ def main():
         planar = color.permute(2, 0, 1)[None].contiguous()
         entry = {"covered_share": round(share, 4), "covered_texels": int(covered.sum()), "texels": res * res,
                  "fused_equals_composed_on_covered_texels": same,
-                 "rasterise": timed(lambda: ops.bake_rasterize(uv, corner, res), a.runs, a.warmup),
-                 "colour_fused": timed(fused, a.runs, a.warmup),
-                 "colour_composed": timed(composed, a.runs, a.warmup),
-                 "padding": timed(lambda: ops.dilate_fill(planar, mask[None, None], iterations=it), a.runs, a.warmup),
+                 "rasterise": timed(lambda: ops.bake_rasterize(uv, corner, res), a.runs, a.warmup)[1],
+                 "colour_fused": timed(fused, a.runs, a.warmup)[1],
+                 "colour_composed": timed(composed, a.runs, a.warmup)[1],
+                 "padding": timed(lambda: ops.dilate_fill(planar, mask[None, None], iterations=it), a.runs, a.warmup)[1],
                  "padding_iterations": it,
-                 "bake_texture_whole_call": timed(lambda: model.bake_texture(mesh, code, res, a.island_padding), a.runs, a.warmup)}
+                 "bake_texture_whole_call": timed(lambda: model.bake_texture(mesh, code, res, a.island_padding), a.runs, a.warmup)[1]}
         # the colour stage once more in the other order: the second of two routes must not owe its time to the first one's caches
-        entry["colour_composed_again"] = timed(composed, a.runs, a.warmup)
-        entry["colour_fused_again"] = timed(fused, a.runs, a.warmup)
+        entry["colour_composed_again"] = timed(composed, a.runs, a.warmup)[1]
+        entry["colour_fused_again"] = timed(fused, a.runs, a.warmup)[1]
         result["resolutions"][str(res)] = entry
         print("%d^2: covered %.1f %%; rasterise %.3f ms, colour fused %.3f ms (again %.3f), composed %.3f ms (again %.3f), padding %.3f ms, "
               "whole call %.3f ms, identical %s" % (res, 100 * share, entry["rasterise"]["median_ms"], entry["colour_fused"]["median_ms"],

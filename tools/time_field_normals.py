@@ -15,9 +15,7 @@ first one's caches.
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -25,26 +23,9 @@ if ROOT not in sys.path:
 
 import torch  # noqa: E402
 
+from _timing import seeded_mesh, timed  # noqa: E402
+
 MC_RES, THRESHOLD = 256, 25.0
-
-
-def stats(ms):
-    q = statistics.quantiles(ms, n=4)
-    return {"median_ms": round(statistics.median(ms), 4), "q1_ms": round(q[0], 4), "q3_ms": round(q[2], 4),
-            "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4), "runs": len(ms)}
-
-
-def timed(fn, runs, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(runs):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return stats(out)
 
 
 def main():
@@ -55,19 +36,10 @@ def main():
     a = ap.parse_args()
     if a.runs < 20:
         ap.error("--runs must be at least 20")
-    from sculptmate_amd import ops, synth
-    from sculptmate_amd.tsr import TSR
+    from sculptmate_amd import ops
 
     dev = torch.device("cuda:0")
-    sd = synth.tsr_state(seed=0)
-    model = TSR(pos_embed_mode="scale_factor")
-    model.load_state_dict(sd)
-    model.to(dev)
-    img = torch.from_numpy(synth.composite_rgb(synth.image_rgba(seed=100))).to(dev).contiguous()
-    with torch.no_grad():
-        synth.calibrate_tsr_density_bias(model, sd, img, 0.015, THRESHOLD)
-        code = model([img], device=dev)[0].contiguous()
-        mesh = model.extract_meshes([code], False, MC_RES, THRESHOLD)[0]
+    model, code, mesh = seeded_mesh(dev, MC_RES, THRESHOLD)
     v, f = mesh.vertices, mesh.faces
     radius = model.renderer.cfg.radius
     planes = ops.ChannelLastPlanes(code)
@@ -93,13 +65,13 @@ def main():
               "decoder_hidden_layers": int(model.decoder.n_hidden), "density_equals_point_query": same,
               "largest_deviation_from_unit_length": unit, "mean_cosine_field_vs_facet_normals": float(cos.mean()),
               "share_cosine_above_0.9": float((cos > 0.9).float().mean()),
-              "field_normals": timed(field, a.runs, a.warmup),
-              "triplane_query_density": timed(query, a.runs, a.warmup),
-              "vertex_normals": timed(facets, a.runs, a.warmup),
-              "field_normals_all_outputs": timed(field_all, a.runs, a.warmup)}
-    result["vertex_normals_again"] = timed(facets, a.runs, a.warmup)
-    result["triplane_query_density_again"] = timed(query, a.runs, a.warmup)
-    result["field_normals_again"] = timed(field, a.runs, a.warmup)
+              "field_normals": timed(field, a.runs, a.warmup)[1],
+              "triplane_query_density": timed(query, a.runs, a.warmup)[1],
+              "vertex_normals": timed(facets, a.runs, a.warmup)[1],
+              "field_normals_all_outputs": timed(field_all, a.runs, a.warmup)[1]}
+    result["vertex_normals_again"] = timed(facets, a.runs, a.warmup)[1]
+    result["triplane_query_density_again"] = timed(query, a.runs, a.warmup)[1]
+    result["field_normals_again"] = timed(field, a.runs, a.warmup)[1]
     result["ratio_field_normals_to_point_query"] = round(
         result["field_normals"]["median_ms"] / result["triplane_query_density"]["median_ms"], 3)
     print("%d vertices: field_normals %.3f ms (again %.3f), triplane_query density %.3f ms (again %.3f), vertex_normals %.3f ms "

@@ -13,7 +13,6 @@ resize see a realistic object.  The device path's stages are timed in a separate
 import argparse
 import json
 import os
-import statistics
 import sys
 import tempfile
 import time
@@ -25,6 +24,8 @@ if ROOT not in sys.path:
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from PIL import Image  # noqa: E402
+
+from _timing import stats, timed  # noqa: E402
 
 SIZES = [(1024, 1024), (2048, 2048), (4096, 3072)]
 
@@ -41,25 +42,6 @@ def disc_picture(width, height, seed):
     r3 = np.hypot((x3 + 0.5 - 0.52 * 320) / (0.30 * 320), (y3 + 0.5 - 0.47 * 320) / (0.36 * 320))
     d0 = 1.0 / (1.0 + np.exp((r3 - 1.0) * 14.0)) * 0.98 + 0.01
     return pic, d0.astype(np.float32)
-
-
-def stats(ms):
-    q = statistics.quantiles(ms, n=4)
-    return {"median_ms": round(statistics.median(ms), 3), "q1_ms": round(q[0], 3), "q3_ms": round(q[2], 3),
-            "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "runs": len(ms)}
-
-
-def timed(fn, runs, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(runs):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return stats(out)
 
 
 def device_stages(path, ratio, sess, runs, warmup):
@@ -129,7 +111,7 @@ def main():
         return stored["d0"].clone()
 
     x320 = torch.randn(3, 320, 320, device=dev)
-    result = {"device": torch.cuda.get_device_name(0), "ratio": a.ratio, "u2net_forward_320": timed(lambda: real_forward(x320), a.runs, a.warmup),
+    result = {"device": torch.cuda.get_device_name(0), "ratio": a.ratio, "u2net_forward_320": timed(lambda: real_forward(x320), a.runs, a.warmup)[1],
               "sizes": {}}
     sess.net.forward = forward
     with tempfile.TemporaryDirectory() as tmp:
@@ -147,7 +129,7 @@ def main():
                 return preprocessing.preprocess_image_device(path, ratio=a.ratio, session=sess)
 
             same = bool(torch.equal(host(), device()))
-            entry = {"host": timed(host, a.runs, a.warmup), "device": timed(device, a.runs, a.warmup), "bit_identical": same,
+            entry = {"host": timed(host, a.runs, a.warmup)[1], "device": timed(device, a.runs, a.warmup)[1], "bit_identical": same,
                      "device_stages": device_stages(path, a.ratio, sess, a.runs, a.warmup)}
             result["sizes"]["%dx%d" % (width, height)] = entry
             print("%dx%d: host %.1f ms, device %.1f ms, identical %s" % (width, height, entry["host"]["median_ms"],

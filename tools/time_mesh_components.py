@@ -27,7 +27,6 @@ import argparse
 import ctypes
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -38,28 +37,11 @@ if ROOT not in sys.path:
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from _timing import seeded_mesh, stats, timed  # noqa: E402
+
 MC_RES, THRESHOLD = 256, 25.0
 SPHERES = (((96.0, 96.0, 96.0), 57.2), ((200.0, 48.0, 48.0), 20.8), ((200.0, 120.0, 48.0), 16.4), ((200.0, 184.0, 48.0), 13.2),
            ((48.0, 208.0, 200.0), 18.4), ((120.0, 208.0, 200.0), 18.4), ((208.0, 208.0, 248.0), 25.6))
-
-
-def stats(ms):
-    q = statistics.quantiles(ms, n=4)
-    return {"median_ms": round(statistics.median(ms), 4), "q1_ms": round(q[0], 4), "q3_ms": round(q[2], 4),
-            "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4), "runs": len(ms)}
-
-
-def timed(fn, runs, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(runs):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return stats(out)
 
 
 def sphere_volume(dev):
@@ -132,12 +114,12 @@ def measure(name, v, f, runs, warmup, host=True):
            "kept_vertices": knv, "kept_faces": knf, "workspace_bytes": int(lib.sculpt_mesh_components_workspace_bytes(nv, nf))}
     routes = [("label", label), ("launch", launch), ("compact", compact), ("keep", keep), ("report", report)]
     for key, fn in routes:
-        res[key] = timed(fn, runs, warmup)
+        res[key] = timed(fn, runs, warmup)[1]
     launch()   # (report ran under another rule: the workspace compact reads is a "largest" one again)
     for key, fn in reversed(routes):
         if key == "compact":
             launch()
-        res[key + "_again"] = timed(fn, runs, warmup)
+        res[key + "_again"] = timed(fn, runs, warmup)[1]
     res["count_select_scans_ms"] = round(res["launch"]["median_ms"] - res["label"]["median_ms"], 4)
     res["launch_ns_per_face"] = round(res["launch"]["median_ms"] * 1e6 / nf, 4)
     res["keep_ns_per_face"] = round(res["keep"]["median_ms"] * 1e6 / nf, 4)
@@ -172,22 +154,14 @@ def main():
     a = ap.parse_args()
     if a.runs < 20:
         ap.error("--runs must be at least 20")
-    from sculptmate_amd import ops, synth
-    from sculptmate_amd.tsr import TSR
+    from sculptmate_amd import ops
 
     dev = torch.device("cuda:0")
-    sd = synth.tsr_state(seed=0)
-    model = TSR(pos_embed_mode="scale_factor")
-    model.load_state_dict(sd)
-    model.to(dev)
-    img = torch.from_numpy(synth.composite_rgb(synth.image_rgba(seed=100))).to(dev).contiguous()
+    model, code, mesh = seeded_mesh(dev, MC_RES, THRESHOLD)
     with torch.no_grad():
-        synth.calibrate_tsr_density_bias(model, sd, img, 0.015, THRESHOLD)
-        code = model([img], device=dev)[0].contiguous()
-        mesh = model.extract_meshes([code], False, MC_RES, THRESHOLD)[0]
-        extract = timed(lambda: model.extract_meshes([code], False, MC_RES, THRESHOLD), a.runs, a.warmup)
-        extract_kept = timed(lambda: model.extract_meshes([code], False, MC_RES, THRESHOLD, keep_components="largest"), a.runs, a.warmup)
-        extract_again = timed(lambda: model.extract_meshes([code], False, MC_RES, THRESHOLD), a.runs, a.warmup)
+        extract = timed(lambda: model.extract_meshes([code], False, MC_RES, THRESHOLD), a.runs, a.warmup)[1]
+        extract_kept = timed(lambda: model.extract_meshes([code], False, MC_RES, THRESHOLD, keep_components="largest"), a.runs, a.warmup)[1]
+        extract_again = timed(lambda: model.extract_meshes([code], False, MC_RES, THRESHOLD), a.runs, a.warmup)[1]
     sv, sf = ops.marching_cubes(sphere_volume(dev), 0.0, reference_order=True)
     result = {"device": torch.cuda.get_device_name(0), "mc_resolution": MC_RES,
               "extract_meshes": extract, "extract_meshes_keep_largest": extract_kept, "extract_meshes_again": extract_again,

@@ -17,9 +17,7 @@ import argparse
 import json
 import math
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for path in (ROOT, os.path.join(ROOT, "tests")):
@@ -29,26 +27,9 @@ for path in (ROOT, os.path.join(ROOT, "tests")):
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from _timing import seeded_mesh, timed  # noqa: E402
+
 MC_RES, THRESHOLD, STEPS, CELLS, RES_TOL, ROUNDS = 256, 25.0, 8, 1.0, 1e-3, 4
-
-
-def stats(ms):
-    q = statistics.quantiles(ms, n=4)
-    return {"median_ms": round(statistics.median(ms), 4), "q1_ms": round(q[0], 4), "q3_ms": round(q[2], 4),
-            "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4), "runs": len(ms)}
-
-
-def timed(fn, runs, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(runs):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return stats(out)
 
 
 def main():
@@ -60,19 +41,10 @@ def main():
     if a.runs < 20:
         ap.error("--runs must be at least 20")
     import _projref as ref
-    from sculptmate_amd import ops, synth
-    from sculptmate_amd.tsr import TSR
+    from sculptmate_amd import ops
 
     dev = torch.device("cuda:0")
-    sd = synth.tsr_state(seed=0)
-    model = TSR(pos_embed_mode="scale_factor")
-    model.load_state_dict(sd)
-    model.to(dev)
-    img = torch.from_numpy(synth.composite_rgb(synth.image_rgba(seed=100))).to(dev).contiguous()
-    with torch.no_grad():
-        synth.calibrate_tsr_density_bias(model, sd, img, 0.015, THRESHOLD)
-        code = model([img], device=dev)[0].contiguous()
-        mesh = model.extract_meshes([code], False, MC_RES, THRESHOLD)[0]
+    model, code, mesh = seeded_mesh(dev, MC_RES, THRESHOLD)
     v, f = mesh.vertices.contiguous(), mesh.faces
     cfg = model.renderer.cfg
     radius = float(cfg.radius)
@@ -114,15 +86,15 @@ def main():
               "median_displacement_cells": float(moved.median()), "largest_displacement_cells": float(moved.max()),
               "faces_inverted_before_guard": ops.unfold_stats(ops.mesh_unfold(v, p, f, 0)[1])["inverted"],
               "unfold": ops.unfold_stats(st),
-              "fused": timed(fused, a.runs, a.warmup),
-              "composed": timed(composed, a.runs, a.warmup),
-              "unfold_ms": timed(guard, a.runs, a.warmup),
-              "one_evaluation": timed(one_evaluation, a.runs, a.warmup),
-              "fused_all_outputs": timed(fused_all, a.runs, a.warmup)}
-    result["one_evaluation_again"] = timed(one_evaluation, a.runs, a.warmup)
-    result["unfold_ms_again"] = timed(guard, a.runs, a.warmup)
-    result["composed_again"] = timed(composed, a.runs, a.warmup)
-    result["fused_again"] = timed(fused, a.runs, a.warmup)
+              "fused": timed(fused, a.runs, a.warmup)[1],
+              "composed": timed(composed, a.runs, a.warmup)[1],
+              "unfold_ms": timed(guard, a.runs, a.warmup)[1],
+              "one_evaluation": timed(one_evaluation, a.runs, a.warmup)[1],
+              "fused_all_outputs": timed(fused_all, a.runs, a.warmup)[1]}
+    result["one_evaluation_again"] = timed(one_evaluation, a.runs, a.warmup)[1]
+    result["unfold_ms_again"] = timed(guard, a.runs, a.warmup)[1]
+    result["composed_again"] = timed(composed, a.runs, a.warmup)[1]
+    result["fused_again"] = timed(fused, a.runs, a.warmup)[1]
     result["accepted_fused_median_below_composed_q1"] = bool(
         result["fused"]["median_ms"] < result["composed"]["q1_ms"] and result["fused_again"]["median_ms"] < result["composed_again"]["q1_ms"])
     print("%d vertices, %d faces: fused %.3f ms (again %.3f), composed %.3f ms (again %.3f, q1 %.3f / %.3f), unfold %.3f ms (again "

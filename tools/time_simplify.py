@@ -13,7 +13,6 @@ set here."""
 import argparse
 import json
 import os
-import statistics
 import sys
 import time
 
@@ -24,20 +23,15 @@ if ROOT not in sys.path:
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import _timing  # noqa: E402
+
 MC_RES, THRESHOLD = 256, 25.0
 
 
 def timed(fn, runs, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return out, {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "runs": len(ms)}
+    """_timing.timed with the extremes only: a few runs of a long call have no quartiles worth reporting."""
+    out, t = _timing.timed(fn, runs, warmup)
+    return out, {k: t[k] for k in ("median_ms", "min_ms", "max_ms", "runs")}
 
 
 def main():
@@ -48,21 +42,12 @@ def main():
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "time_simplify.json"))
     a = ap.parse_args()
-    from sculptmate_amd import ops, synth
+    from sculptmate_amd import ops
     from sculptmate_amd.sf3d import remesh as rm
     from sculptmate_amd.sf3d import remesh_device as rd
-    from sculptmate_amd.tsr import TSR
 
     dev = torch.device("cuda:0")
-    sd = synth.tsr_state(seed=0)
-    model = TSR(pos_embed_mode="scale_factor")
-    model.load_state_dict(sd)
-    model.to(dev)
-    img = torch.from_numpy(synth.composite_rgb(synth.image_rgba(seed=100))).to(dev).contiguous()
-    with torch.no_grad():
-        synth.calibrate_tsr_density_bias(model, sd, img, 0.015, THRESHOLD)
-        code = model([img], device=dev)[0].contiguous()
-        mesh = model.extract_meshes([code], False, MC_RES, THRESHOLD)[0]
+    model, code, mesh = _timing.seeded_mesh(dev, MC_RES, THRESHOLD)
     (v, f, _, _), keep = timed(lambda: ops.mesh_keep_components(mesh.vertices, mesh.faces, "largest"), a.runs, a.warmup)
     target = ops.simplify_target(a.ratio, f.shape[0])
     print("mesh: %d faces, largest component %d faces / %d vertices, target %d" % (mesh.faces.shape[0], f.shape[0], v.shape[0], target), flush=True)

@@ -12,9 +12,7 @@ the runs.  No threshold is set here."""
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -23,22 +21,9 @@ if ROOT not in sys.path:
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from _timing import seeded_mesh, timed  # noqa: E402
+
 MC_RES, THRESHOLD = 256, 25.0
-
-
-def timed(fn, runs, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        ms.append((time.perf_counter() - t0) * 1e3)
-    q = statistics.quantiles(ms, n=4) if len(ms) >= 2 else [ms[0]] * 3
-    return out, {"median_ms": round(statistics.median(ms), 3), "q1_ms": round(q[0], 3), "q3_ms": round(q[2], 3),
-                 "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3), "runs": len(ms)}
 
 
 def host_route(v, f, n, lam, mu):
@@ -75,20 +60,11 @@ def main():
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "time_smooth.json"))
     a = ap.parse_args()
-    from sculptmate_amd import ops, synth
+    from sculptmate_amd import ops
     from sculptmate_amd.sf3d import remesh_device as rd
-    from sculptmate_amd.tsr import TSR
 
     dev = torch.device("cuda:0")
-    sd = synth.tsr_state(seed=0)
-    model = TSR(pos_embed_mode="scale_factor")
-    model.load_state_dict(sd)
-    model.to(dev)
-    img = torch.from_numpy(synth.composite_rgb(synth.image_rgba(seed=100))).to(dev).contiguous()
-    with torch.no_grad():
-        synth.calibrate_tsr_density_bias(model, sd, img, 0.015, THRESHOLD)
-        code = model([img], device=dev)[0].contiguous()
-        mesh = model.extract_meshes([code], False, MC_RES, THRESHOLD)[0]
+    model, code, mesh = seeded_mesh(dev, MC_RES, THRESHOLD)
     v, f = mesh.vertices, mesh.faces
     n, lam, mu = ops.smooth_rule(a.iterations)
     result = {"device": torch.cuda.get_device_name(0), "mc_resolution": MC_RES, "iterations": n, "lambda": lam, "mu": mu,
