@@ -646,6 +646,11 @@ int sculpt_vit_patchify(const float *image_hwc, int S, int P, const float *mean3
 /* tokens[0] = cls + pos[0]; tokens[1+i] = patch_out[i] + pos[1+i]  (fp32 residual stream) */
 int sculpt_vit_assemble(const float *patch_out, const float *cls, const float *pos, float *tokens,
                         int n_patches, int hidden, sculpt_stream_t stream);
+/* sculpt_vit_assemble and sculpt_row_slice_stats of its n_patches + 1 rows in one launch: tokens [rows][ldt] fp32, their bf16 copy
+ * [rows][ldb] (may be NULL) and stats [hidden/64][stats_ld][2] -- the same bits as the two calls. hidden % 64 == 0; every array
+ * 16-byte aligned. */
+int sculpt_vit_assemble_stats(const float *patch_out, const float *cls, const float *pos, float *tokens, int ldt, int n_patches,
+                              int hidden, float *stats, int stats_ld, uint16_t *tokens_bf16, int ldb, sculpt_stream_t stream);
 
 /* ConvTranspose2d(k=2,s=2) epilogue: g [3*S*S][ldg] fp32 (GEMM output, column = co*4 + dy*2 + dx)
  * + bias[Co] -> planes [3][Co][2S][2S]  (network_utils.py:20-32) */

@@ -135,6 +135,7 @@ SIGNATURES = {
     "sculpt_transpose_add": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "sculpt_vit_patchify": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "sculpt_vit_assemble": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "sculpt_vit_assemble_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "sculpt_upsample_scatter": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp]),
     "sculpt_cast_bf16": (_i, [_vp, _vp, _i64, _vp]),
     "sculpt_dilate_fill": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

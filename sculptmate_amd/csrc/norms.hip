@@ -221,18 +221,13 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float *__restrict_
 
 static inline int grid_for(long n) { return (int)std::min<long>((n + 255) / 256, 2048); }
 
-// one thread per (row, 64-column slice): 16 float4 loads (256 contiguous bytes), two-pass (mean, M2), bf16 copy
-__global__ __launch_bounds__(256) void row_slice_stats_kernel(const float *__restrict__ x, int ldx, int rows, int slots,
-                                                              float *__restrict__ stats, int stats_ld,
-                                                              uint16_t *__restrict__ xb, int ldb) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (long)rows * slots) return;
-    const int slot = (int)(t / rows), row = (int)(t % rows);  // row fastest: the slice-major stores are coalesced
-    const float4 *src = reinterpret_cast<const float4 *>(x + (long)row * ldx + slot * 64);
-    float4 v[16];
+// (mean, M2) of one 64-column slice held as 16 float4, two-pass, and its bf16 copy: ONE summation tree for every kernel that
+// produces slice statistics of rows that do not come out of a GEMM (the statistics are compared bit for bit)
+__device__ __forceinline__ void slice_stats_store(const float4 (&v)[16], int row, int slot, float *__restrict__ stats, int stats_ld,
+                                                  uint16_t *__restrict__ xb, int ldb) {
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) { v[i] = src[i]; s += (v[i].x + v[i].y) + (v[i].z + v[i].w); }
+    for (int i = 0; i < 16; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     const float mean = s * (1.0f / 64.0f);
     float m2 = 0.f;
 #pragma unroll
@@ -251,6 +246,44 @@ __global__ __launch_bounds__(256) void row_slice_stats_kernel(const float *__res
             dst[i] = pk;
         }
     }
+}
+
+// one thread per (row, 64-column slice): 16 float4 loads (256 contiguous bytes), two-pass (mean, M2), bf16 copy
+__global__ __launch_bounds__(256) void row_slice_stats_kernel(const float *__restrict__ x, int ldx, int rows, int slots,
+                                                              float *__restrict__ stats, int stats_ld,
+                                                              uint16_t *__restrict__ xb, int ldb) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)rows * slots) return;
+    const int slot = (int)(t / rows), row = (int)(t % rows);  // row fastest: the slice-major stores are coalesced
+    const float4 *src = reinterpret_cast<const float4 *>(x + (long)row * ldx + slot * 64);
+    float4 v[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = src[i];
+    slice_stats_store(v, row, slot, stats, stats_ld, xb, ldb);
+}
+
+// vit_assemble_kernel + row_slice_stats_kernel in one pass over the token rows: the owner of (row, slice) forms
+// (cls | patch_out) + pos, writes it to the residual stream, and goes on as row_slice_stats_kernel does -- the same fp32 sums of
+// the same values, so tokens, bf16 copy and statistics are the bits of the two launches
+__global__ __launch_bounds__(256) void vit_assemble_stats_kernel(const float *__restrict__ patch_out, const float *__restrict__ cls,
+                                                                 const float *__restrict__ pos, float *__restrict__ tokens, int ldt,
+                                                                 int rows, int slots, float *__restrict__ stats, int stats_ld,
+                                                                 uint16_t *__restrict__ xb, int ldb) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long)rows * slots) return;
+    const int slot = (int)(t / rows), row = (int)(t % rows);
+    const int hidden = slots * 64;
+    const float4 *src = reinterpret_cast<const float4 *>((row == 0 ? cls : patch_out + (long)(row - 1) * hidden) + slot * 64);
+    const float4 *ps = reinterpret_cast<const float4 *>(pos + (long)row * hidden + slot * 64);
+    float4 *dst = reinterpret_cast<float4 *>(tokens + (long)row * ldt + slot * 64);
+    float4 v[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const float4 a = src[i], p = ps[i];
+        v[i] = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
+        dst[i] = v[i];
+    }
+    slice_stats_store(v, row, slot, stats, stats_ld, xb, ldb);
 }
 
 }  // namespace sculpt
@@ -344,6 +377,21 @@ int sculpt_vit_assemble(const float *patch_out, const float *cls, const float *p
     SC_REQUIRE(patch_out && cls && pos && tokens, "vit_assemble: null argument");
     hipLaunchKernelGGL(vit_assemble_kernel, dim3(grid_for((long)(n_patches + 1) * hidden)), dim3(256), 0,
                        as_stream(stream), patch_out, cls, pos, tokens, n_patches, hidden);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+int sculpt_vit_assemble_stats(const float *patch_out, const float *cls, const float *pos, float *tokens, int ldt, int n_patches,
+                              int hidden, float *stats, int stats_ld, uint16_t *tokens_bf16, int ldb, sculpt_stream_t stream) {
+    SC_REQUIRE(patch_out && cls && pos && tokens && stats, "vit_assemble_stats: null argument");
+    SC_REQUIRE(n_patches >= 0 && stats_ld >= n_patches + 1, "vit_assemble_stats: stats_ld=%d < %d rows", stats_ld, n_patches + 1);
+    SC_REQUIRE(hidden >= 64 && hidden % 64 == 0 && ldt >= hidden && ldt % 4 == 0 && (!tokens_bf16 || (ldb >= hidden && ldb % 4 == 0)),
+               "vit_assemble_stats: hidden=%d must be a multiple of 64, ldt / ldb multiples of 4 and >= hidden", hidden);
+    SC_REQUIRE((((uintptr_t)patch_out | (uintptr_t)cls | (uintptr_t)pos | (uintptr_t)tokens) & 15) == 0 && ((uintptr_t)tokens_bf16 & 7) == 0 &&
+               ((uintptr_t)stats & 7) == 0, "vit_assemble_stats: arrays must be 16-byte aligned");
+    const int rows = n_patches + 1, slots = hidden / 64;
+    hipLaunchKernelGGL(vit_assemble_stats_kernel, dim3(cdiv((long)rows * slots, 256)), dim3(256), 0, as_stream(stream), patch_out, cls,
+                       pos, tokens, ldt, rows, slots, stats, stats_ld, tokens_bf16, ldb);
     SC_LAUNCH_CHECK();
     return 0;
 }

@@ -177,9 +177,12 @@ class KernelEngine:
         ops.layernorm(st["h"], g, b, eps, y_f32=st["xn"])
         return self._gemm(st["xn"], L[key], bias=L[key + "_b"], **kw)
 
-    def _res_gemm(self, st, A, W, bias):
-        """h += A . W^T + bias (in place); bf16 mode also refreshes bf16(h) and the slice statistics."""
+    def _res_gemm(self, st, A, W, bias, residual=None):
+        """h += A . W^T + bias (in place); bf16 mode also refreshes bf16(h) and the slice statistics.
+        residual: h = residual + A . W^T + bias instead (the same kernel reading another array: the same bits as the in-place form
+        on a copy of it)."""
         h = st["h"]
+        res = h if residual is None else residual
         if self.precision == "bf16":
-            return ops.gemm(A, W, bias=bias, residual=h, out_f32=h, out_bf16=st["hb"], stats_out=st["stats"])
-        return self._gemm(A, W, bias=bias, residual=h, out_f32=h)
+            return ops.gemm(A, W, bias=bias, residual=res, out_f32=h, out_bf16=st["hb"], stats_out=st["stats"])
+        return self._gemm(A, W, bias=bias, residual=res, out_f32=h)

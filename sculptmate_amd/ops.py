@@ -954,6 +954,15 @@ def vit_assemble(patch_out, cls, pos, tokens):
     check(lib.sculpt_vit_assemble(_ptr(patch_out), _ptr(cls), _ptr(pos), _ptr(tokens), n_patches, hidden, _stream()))
 
 
+def vit_assemble_stats(patch_out, cls, pos, tokens, stats, tokens_bf16=None):
+    """vit_assemble + row_slice_stats of the assembled rows in one launch (the same bits): tokens [n_patches + 1, hidden] fp32,
+    stats [hidden/64][rows >= n_patches + 1][2], tokens_bf16 the bf16 copy."""
+    n_patches, hidden = patch_out.shape[0], patch_out.shape[1]
+    check(lib.sculpt_vit_assemble_stats(_ptr(patch_out), _ptr(cls), _ptr(pos), _ptr(tokens), tokens.stride(0), n_patches, hidden,
+                                        _ptr(stats), stats.shape[1], _ptr(tokens_bf16),
+                                        tokens_bf16.stride(0) if tokens_bf16 is not None else 0, _stream()))
+
+
 def upsample_scatter(g, bias, planes, S, Co):
     check(lib.sculpt_upsample_scatter(_ptr(g), g.stride(0), _ptr(bias), _ptr(planes), S, Co, _stream()))
 

@@ -362,6 +362,7 @@ class TSR(KernelEngine):
         # faster at four images, scene codes 2.7e-3 from the single-image ones: bf16 roundings flip in the LayerNorm statistics)
         self.batch_exact = True
         self._w = None
+        self._head0 = None   # _backbone_head_cached
         self._pos_cache = {}
         self._buf = {}
 
@@ -511,6 +512,7 @@ class TSR(KernelEngine):
                                      [sd["decoder.layers.%d.bias" % (2 * i)] for i in range(n)], dev)
         self._pos_cache = {}
         self._buf = {}
+        self._head0 = None   # the cached head of the backbone belongs to the weights (and the precision / limb format) just replaced
 
     def _pos(self, n_side, dev):
         if n_side not in self._pos_cache:
@@ -550,12 +552,15 @@ class TSR(KernelEngine):
         self._gemm(patches, w["patch_w"], bias=w["patch_b"], out_f32=pout)
         h = self._b("vit_h", (M, H), torch.float32, zero=True)
         pos = self._pos(n_side, imgs[0].device)
-        for b in range(B):
-            ops.vit_assemble(pout[b * npatch:(b + 1) * npatch], w["cls"], pos, h[b * Ts:b * Ts + T])
-            if Ts > T:   # the pad rows of the stacked stream take part in every Linear: start them from zero on every call, or
-                h[b * Ts + T:(b + 1) * Ts].zero_()   # they drift without bound in a long-running process
         st = self._stream_state("vit", h)     # the residual stream + its bf16 copy + slice statistics (LayerNorm fold)
-        self._stats_of(st)                    # rows that do not come out of a GEMM: one small kernel
+        if B == 1 and self.precision == "bf16":   # one image: the rows, their bf16 copy and statistics in one launch (the same bits)
+            ops.vit_assemble_stats(pout, w["cls"], pos, h, st["stats"], st["hb"])
+        else:
+            for b in range(B):
+                ops.vit_assemble(pout[b * npatch:(b + 1) * npatch], w["cls"], pos, h[b * Ts:b * Ts + T])
+                if Ts > T:   # the pad rows of the stacked stream take part in every Linear: start them from zero on every call, or
+                    h[b * Ts + T:(b + 1) * Ts].zero_()   # they drift without bound in a long-running process
+            self._stats_of(st)                # rows that do not come out of a GEMM: one small kernel
         qk = self._b("vit_qk", (M, 2 * H), self.adt)
         vt = self._b("vit_vt", (H, ldt), self.adt, zero=True)
         if self.l3p:   # read only by the next Linear: written as limbs by their producers
@@ -604,9 +609,11 @@ class TSR(KernelEngine):
                    batch, T * 2 * D, T * 2 * D, T, T * D)
         self._res_gemm(st, att, L["sa_o"], L["sa_ob"])
 
-    def _run_blocks(self, st, ctx: torch.Tensor, first_self_attention_done: bool = False, batch: int = 1, ctx_tokens=None):
+    def _run_blocks(self, st, ctx: torch.Tensor, first_self_attention_done: bool = False, batch: int = 1, ctx_tokens=None, head=None):
         """All BasicTransformerBlocks on the fp32 residual stream h [batch*T, D] (updated in place).  ctx [rows, cross_dim]: the
-        image tokens, image b's ctx_tokens rows starting at row b * (rows // batch) (image_tokens' stacking)."""
+        image tokens, image b's ctx_tokens rows starting at row b * (rows // batch) (image_tokens' stacking).
+        head (_backbone_head_cached()): block 0 starts at its cross-attention, from the cached queries; its residual GEMM reads the
+        cached stream and writes st's (one image), or st already holds copies of it (a stacked pass: _broadcast_state)."""
         b, w = self.cfg["backbone"], self._w
         nh, hd = b["num_attention_heads"], b["attention_head_dim"]
         D = nh * hd
@@ -629,11 +636,20 @@ class TSR(KernelEngine):
         scale = self._attn_scale(1.0 / math.sqrt(hd))
         for li, L in enumerate(w["blocks"]):
             ck, cvt = ck_all[:, li * D:(li + 1) * D], cvt_all[li * D:(li + 1) * D]
-            if li > 0 or not first_self_attention_done:
-                self._self_attention(st, L, batch)
-            self._ln_gemm(st, L, "ca_q", 1e-5, out_bf16=q)
-            self._attn(q, ck, cvt, att, T, Tc, nh, scale, batch, T * D, Ts * nL * D, Ts, T * D)
-            self._res_gemm(st, att, L["ca_o"], L["ca_ob"])
+            if li == 0 and head is not None:
+                if batch == 1:
+                    self._attn(head["q0"], ck, cvt, att, T, Tc, nh, scale)
+                    self._res_gemm(st, att, L["ca_o"], L["ca_ob"], residual=head["h0"])   # out of place: the cache is never written
+                else:
+                    q.view(batch, T, D).copy_(head["q0"][None])
+                    self._attn(q, ck, cvt, att, T, Tc, nh, scale, batch, T * D, Ts * nL * D, Ts, T * D)
+                    self._res_gemm(st, att, L["ca_o"], L["ca_ob"])
+            else:
+                if li > 0 or not first_self_attention_done:
+                    self._self_attention(st, L, batch)
+                self._ln_gemm(st, L, "ca_q", 1e-5, out_bf16=q)
+                self._attn(q, ck, cvt, att, T, Tc, nh, scale, batch, T * D, Ts * nL * D, Ts, T * D)
+                self._res_gemm(st, att, L["ca_o"], L["ca_ob"])
             self._ln_gemm(st, L, "ff1", 1e-5, out_bf16=ff, epilogue=_lib.EPI_GEGLU)
             self._res_gemm(st, ff, L["ff2"], L["ff2_b"])
         return st
@@ -655,6 +671,34 @@ class TSR(KernelEngine):
             self._gemm(xn, w["pin_w"], bias=w["pin_b"], out_f32=h)
         return st
 
+    def _backbone_head_cached(self):
+        """Everything in front of block 0's cross-attention depends on the weights alone: _backbone_head, the first block's
+        self-attention and its cross-attention query projection (7 launches in bf16 mode).  Computed once per prepared model, at
+        the first forward, with the kernels and operands a forward would use -- the same bits -- and kept in buffers of their
+        own that no forward writes: h0 (+ hb0, stats0 in bf16 mode) and q0.  _prepare drops it (load_state_dict, to(), a change of
+        precision or limb format all go through there)."""
+        key = (self.precision, self.limb_format, self.l3p)
+        hc = self._head0
+        if hc is not None and hc["key"] == key:
+            return hc
+        with ops.single_image_tiles(0):   # (a caller's stacked-pass tile choice does not apply to this one-image work)
+            st = self._backbone_head()
+            L = self._w["blocks"][0]
+            self._self_attention(st, L)
+            q = self._b("bb_q", st["h"].shape, self.adt)
+            self._ln_gemm(st, L, "ca_q", 1e-5, out_bf16=q)
+        hc = {"key": key, "h0": st["h"].clone(), "q0": q.clone()}
+        if self.precision == "bf16":
+            hc["hb0"], hc["stats0"] = st["hb"].clone(), st["stats"].clone()
+        # once per model: later forwards read the cache from any stream (the tokenizer's, a caller's) without an event of its own
+        torch.cuda.current_stream(self.device).synchronize()
+        self._head0 = hc
+        return hc
+
+    def _head_state(self, hc):
+        """The work state of one image's pass: block 0's residual GEMM fills it from the cached stream."""
+        return self._stream_state("bb", self._b("bb_h", tuple(hc["h0"].shape), torch.float32))
+
     def _backbone_tail(self, st, batch=1):
         w = self._w
         C = self.cfg["tokenizer"]["num_channels"]
@@ -675,21 +719,21 @@ class TSR(KernelEngine):
             outb = out
         return out, outb
 
-    def _broadcast_state(self, st1, batch):
-        """The residual stream of ONE image (the image-independent head of the backbone) copied into a stacked state of `batch`."""
-        T, D = st1["h"].shape
+    def _broadcast_state(self, hc, batch):
+        """The cached residual stream of ONE image (the image-independent head of the backbone) copied into a stacked state of `batch`."""
+        T, D = hc["h0"].shape
         st = self._stream_state("bb", self._b("bb_h", (batch * T, D), torch.float32))
-        st["h"].view(batch, T, D).copy_(st1["h"][None])
+        st["h"].view(batch, T, D).copy_(hc["h0"][None])
         if self.precision == "bf16":
-            st["hb"].view(batch, T, D).copy_(st1["hb"][None])
-            st["stats"].view(-1, batch, T, 2).copy_(st1["stats"][:, None])
+            st["hb"].view(batch, T, D).copy_(hc["hb0"][None])
+            st["stats"].view(-1, batch, T, 2).copy_(hc["stats0"][:, None])
         return st
 
     def encode_images(self, images):
         """encode_image for a batch (system.py:82-115 with batch_size = len(images)): ONE pass of the tokenizer and the backbone
         over the stacked token rows of all images -- weight panels are read once per batch, every Linear is one launch of
         B x 3072 (B x 1025) rows, every attention one launch over B x heads.  The image-independent head of the backbone
-        (GroupNorm, proj_in, first self-attention) is evaluated once, on a second stream under the tokenizer, and copied into
+        (GroupNorm, proj_in, first self-attention, first query projection) comes from the per-model cache and is copied into
         the B streams.  Returns the output tokens of all images stacked: (fp32 [B*3*S*S, C], bf16 copy)."""
         B = len(images)
         if B == 1:
@@ -698,17 +742,7 @@ class TSR(KernelEngine):
         last_tok = getattr(self, "_tok_last", None)
         if last_tok is not None:
             main.wait_event(last_tok)
-        side = getattr(self, "_side_stream", None)
-        if side is None:
-            side = self._side_stream = torch.cuda.Stream(self.device)
-        fork, join = torch.cuda.Event(), torch.cuda.Event()
-        fork.record(main)
-        with torch.cuda.stream(side):
-            side.wait_event(fork)
-            st1 = self._backbone_head()
-            self._self_attention(st1, self._w["blocks"][0])
-            st = self._broadcast_state(st1, B)
-            join.record(side)
+        hc = self._backbone_head_cached()
         # Every GEMM of the pass picks the tile form ONE image takes (ops.single_image_tiles): the stacked pass then accumulates every
         # output and every LayerNorm slice statistic in the single-image order, and each image gets the scene code of its own pass,
         # bit for bit (test_full_size_batched_forward_equals_single_image_passes) -- which is what lets TSR.run batch by default.
@@ -716,39 +750,28 @@ class TSR(KernelEngine):
         n_side = images[0].shape[0] // T["patch_size"]
         with ops.single_image_tiles(n_side * n_side + 1 if self.batch_exact else 0):
             ctx, _ = self.image_tokens(list(images))
-        main.wait_event(join)
+        st = self._broadcast_state(hc, B)
         with ops.single_image_tiles(3 * self.cfg["tokenizer"]["plane_size"] ** 2 if self.batch_exact else 0):
-            st = self._run_blocks(st, ctx, first_self_attention_done=True, batch=B, ctx_tokens=n_side * n_side + 1)
+            st = self._run_blocks(st, ctx, batch=B, ctx_tokens=n_side * n_side + 1, head=hc)
             return self._backbone_tail(st, B)
 
     def backbone_tokens(self, ctx: torch.Tensor):
         """Triplane1DTokenizer + Transformer1D for one image; ctx bf16 [Tc, cross_dim].
         Returns the output tokens token-major: fp32 [3*S*S, C] (+ bf16 copy)."""
-        st = self._run_blocks(self._backbone_head(), ctx)
+        hc = self._backbone_head_cached()
+        st = self._run_blocks(self._head_state(hc), ctx, head=hc)
         return self._backbone_tail(st)
 
     def encode_image(self, image_hwc: torch.Tensor):
-        """image_tokens + backbone_tokens for one [S,S,3] fp32 device image, with the image-independent head of the backbone
-        (GroupNorm, proj_in, first self-attention: 6 launches) issued on a second HIP stream so that it runs under the ViT,
-        whose 1025-token launches leave most CUs idle.  Same kernels on the same operands as the sequential calls:
-        bit-identical tokens."""
+        """image_tokens + backbone_tokens for one [S,S,3] fp32 device image on the current stream.  (Until the head of the backbone
+        was cached per model, it was issued here on a second HIP stream under the ViT.)"""
         main = torch.cuda.current_stream(self.device)
         last_tok = getattr(self, "_tok_last", None)
         if last_tok is not None:  # tokens_async shares the tokenizer's work buffers: finish it first
             main.wait_event(last_tok)
-        side = getattr(self, "_side_stream", None)
-        if side is None:
-            side = self._side_stream = torch.cuda.Stream(self.device)
-        fork, join = torch.cuda.Event(), torch.cuda.Event()
-        fork.record(main)               # everything queued so far (the previous image's readers of these buffers) comes first
-        with torch.cuda.stream(side):
-            side.wait_event(fork)
-            st = self._backbone_head()
-            self._self_attention(st, self._w["blocks"][0])
-            join.record(side)
+        hc = self._backbone_head_cached()
         ctx, _ = self.image_tokens(image_hwc)
-        main.wait_event(join)
-        st = self._run_blocks(st, ctx, first_self_attention_done=True)
+        st = self._run_blocks(self._head_state(hc), ctx, head=hc)
         return self._backbone_tail(st)
 
     def _preprocess(self, im) -> torch.Tensor:
@@ -802,7 +825,8 @@ class TSR(KernelEngine):
         -> scene code fp32 [1, 3, 40, 64, 64]."""
         main = torch.cuda.current_stream(self.device)
         main.wait_event(tokens.ready)
-        st = self._run_blocks(self._backbone_head(), tokens.ctx)
+        hc = self._backbone_head_cached()
+        st = self._run_blocks(self._head_state(hc), tokens.ctx, head=hc)
         consumed = torch.cuda.Event()
         consumed.record(main)
         tokens._slot["consumed"] = consumed
