@@ -130,6 +130,33 @@ int sculpt_render_rays(const float *planes_cl /* [3][H][W][C] */, int C, int H, 
                        float *weights /* nullable [n_rays][S] */,
                        sculpt_stream_t stream);
 
+/* sculpt_render_rays with passes beside the colour: raw per-ray sums over the samples, with the weights w_i of the colour
+ * picture, each exactly 0 for a miss.  Same arguments, same refusals; the three new outputs are nullable.
+ *   depth_sum   f32 [n_rays]       sum_i w_i z_i (sequential in i, fp32, every operation rounded on its own); depth_sum / opacity
+ *                                  is the expected distance along the ray, in units of |rays_d|
+ *   normal_sum  f32 [n_rays][3]    sum_i w_i n_i, n_i = the `normal` of sculpt_triplane_density_grad at o + z_i d, bit for bit
+ *                                  (-grad / |grad| of the raw density, 0 where the gradient is 0 or not finite); world space
+ *   premul      f32 [n_rays][3]    sum_i w_i color_i: comp_rgb before the white background, comp_rgb = premul + (1 - opacity)
+ * With all three NULL this is sculpt_render_rays: the same launch.  Without normal_sum, depth_sum and premul come from the
+ * colour kernel's second form, at the colour kernel's price.  With normal_sum the call is one launch of the forward-mode
+ * kernel (8 rays x {value, d/dx, d/dy, d/dz} per wave, about 4.5 x the colour kernel's time), which writes every output asked
+ * for.  Either way comp_rgb, opacity, z_vals and weights have sculpt_render_rays' bits.  The forward-mode kernel stops
+ * evaluating a tile of 8 rays once the transmittance of each is exactly 0 (every later weight is +0 for a finite field: no
+ * result changes; SCULPT_RENDER_FORM=noskip walks every sample).  A ray's result depends on that ray alone. */
+int sculpt_render_passes(const float *planes_cl /* [3][H][W][C] */, int C, int H, int W,
+                         const void *mlp_packed, int n_hidden_64,
+                         const float *rays_o, const float *rays_d /* [n_rays][3] */, int64_t n_rays,
+                         float radius, float density_bias,
+                         const float *t_vals /* device, [S + 1] */, int S,
+                         float *comp_rgb /* [n_rays][3] */,
+                         float *opacity /* nullable [n_rays] */,
+                         float *z_vals  /* nullable [n_rays][S] */,
+                         float *weights /* nullable [n_rays][S] */,
+                         float *depth_sum  /* nullable [n_rays] */,
+                         float *normal_sum /* nullable [n_rays][3] */,
+                         float *premul     /* nullable [n_rays][3] */,
+                         sculpt_stream_t stream);
+
 /* Texture bake of a scene code: colour of every covered texel of a rasterised UV atlas (sculpt_bake_rasterize), one launch;
  * per covered texel the position (a*u + b*v) + c*w of sculpt_bake_interpolate (gathered through faces[tri] from the indexed
  * vertices) and the colour of sculpt_triplane_query_ex(SCULPT_QUERY_CHANNEL_LAST) at it, bit for bit; the density row of the

@@ -77,6 +77,7 @@ SIGNATURES = {
     "sculpt_triplane_query_ex": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i64, _f, _f, _u, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_planes_channel_last": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "sculpt_render_rays": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_render_passes": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_bake_scene_color": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _i, _sz, _vp, _i, _f, _vp, _vp, _vp]),
     "sculpt_triplane_density_grad": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _f, _i, _vp, _vp, _vp, _vp]),
     "sculpt_density_grid_workspace_bytes": (_sz, [_i, _i]),
@@ -277,5 +278,6 @@ def check(rc):
 
 def form_has(var, token):
     """Non-default kernel forms for tests and A/B: one environment variable per kernel family (SCULPT_GEMM_TILE, SCULPT_L3_TILE,
-    SCULPT_ATTN_FORM, SCULPT_DENSITY_FORM, SCULPT_MC_FORM), a comma-separated list of tokens (csrc/common.h: form_has)."""
+    SCULPT_ATTN_FORM, SCULPT_DENSITY_FORM, SCULPT_MC_FORM, SCULPT_RENDER_FORM), a comma-separated list of tokens (csrc/common.h:
+    form_has)."""
     return any(t == token or t.startswith(token + "=") for t in os.environ.get(var, "").split(",") if t)

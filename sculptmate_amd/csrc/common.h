@@ -41,8 +41,9 @@ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 int num_cus();
 
 // Non-default kernel forms, for the tests that pin each adopted form against another and for A/B timing: ONE environment variable
-// per kernel family (SCULPT_GEMM_TILE, SCULPT_L3_TILE, SCULPT_ATTN_FORM, SCULPT_DENSITY_FORM, SCULPT_MC_FORM), a comma-separated
-// list of tokens read per call.  form_has(var, "nopipe"): the token is there; form_int(var, "gm", -1): the value of "gm=4".
+// per kernel family (SCULPT_GEMM_TILE, SCULPT_L3_TILE, SCULPT_ATTN_FORM, SCULPT_DENSITY_FORM, SCULPT_MC_FORM, SCULPT_RENDER_FORM), a
+// comma-separated list of tokens read per call.  form_has(var, "nopipe"): the token is there; form_int(var, "gm", -1): the value
+// of "gm=4".
 static inline bool form_token(const char *list, const char *token, const char **value) {
     if (!list) return false;
     const size_t n = strlen(token);

@@ -1,7 +1,8 @@
 // The forward-mode evaluator of the raw density: the pieces that turn the point query's MFMA tile (triplane_mlp.h) into
 // 8 points x 4 columns {value, d/dx, d/dy, d/dz}.  Shared by density_grad_kernel (csrc/field_normal.hip, where the shape is
-// described: DESIGN.md section 3.1d) and project_kernel (csrc/mesh_project.hip), so that both evaluate a point with the same
-// operations and give the same bits.  Units that include this are compiled with -fno-slp-vectorize (build.py).
+// described: DESIGN.md section 3.1d), project_kernel (csrc/mesh_project.hip) and render_passes_kernel (csrc/render.hip), so that
+// all three evaluate a point with the same operations and give the same bits.  Units that include this are compiled with
+// -fno-slp-vectorize (build.py).
 #pragma once
 
 #include "common.h"
@@ -102,6 +103,21 @@ __device__ __forceinline__ float last_dot0_nobias(const LdsView &L, int h, const
     for (int r = 0; r < 16; ++r) s = fmaf(w[16 + r], x1[r], s);
     s += __shfl_xor(s, 32, 64);
     return s;
+}
+
+// The unit normal of the iso-surface through a point with density gradient g: -g / |g|, with g scaled by a power of two first
+// so that no square overflows or vanishes; exactly 0 where g is 0 or not finite.  One copy, so that density_grad_kernel and the
+// renderer's render_passes_kernel (csrc/render.hip) give the same bits.
+__device__ __forceinline__ void unit_normal_of(float gx, float gy, float gz, float &nx, float &ny, float &nz) {
+    const float m = fmaxf(fmaxf(fabsf(gx), fabsf(gy)), fabsf(gz));
+    nx = 0.f; ny = 0.f; nz = 0.f;
+    const bool finite = fabsf(gx) < INFINITY && fabsf(gy) < INFINITY && fabsf(gz) < INFINITY;
+    if (finite && m > 0.f) {
+        const int e = -ilogbf(m);
+        const float ux = ldexpf(gx, e), uy = ldexpf(gy, e), uz = ldexpf(gz, e);
+        const float len = sqrtf(ux * ux + uy * uy + uz * uz);
+        nx = -ux / len; ny = -uy / len; nz = -uz / len;
+    }
 }
 
 }  // namespace sculpt

@@ -69,16 +69,8 @@ __global__ __launch_bounds__(512) void density_grad_kernel(
             if (density) density[n] = d;
             if (grad) { grad[3 * n] = gx; grad[3 * n + 1] = gy; grad[3 * n + 2] = gz; }
             if (normal) {
-                // -g / |g|, with g scaled by a power of two first so that no square overflows or vanishes
-                const float m = fmaxf(fmaxf(fabsf(gx), fabsf(gy)), fabsf(gz));
-                float nx = 0.f, ny = 0.f, nz = 0.f;
-                const bool finite = fabsf(gx) < INFINITY && fabsf(gy) < INFINITY && fabsf(gz) < INFINITY;
-                if (finite && m > 0.f) {
-                    const int e = -ilogbf(m);
-                    const float ux = ldexpf(gx, e), uy = ldexpf(gy, e), uz = ldexpf(gz, e);
-                    const float len = sqrtf(ux * ux + uy * uy + uz * uz);
-                    nx = -ux / len; ny = -uy / len; nz = -uz / len;
-                }
+                float nx, ny, nz;
+                unit_normal_of(gx, gy, gz, nx, ny, nz);
                 normal[3 * n] = nx; normal[3 * n + 1] = ny; normal[3 * n + 2] = nz;
             }
         }

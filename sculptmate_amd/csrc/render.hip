@@ -19,9 +19,26 @@
 //     CPU does): z_vals and xyz equal the reference's bit for bit.
 // Three quirks of the reference are kept: |d| < 1e-6 becomes +1e-6 whatever the sign of d; delta is the step of the unit
 // interval t_vals, not a world length; T is multiplied by (1 - alpha + 1e-10).
+//
+// Passes beside the colour (sculpt_render_passes, DESIGN.md section 3.1b "passes"): raw per-ray sums, exactly 0 for a miss.
+//   * depth_sum = sum_s w_s z_s and premul = sum_s w_s c_s (the colour sums before the white background) alone come from the
+//     colour kernel's second form, render_rays_kernel<C, float *, float *>: the same code with one more sum and two more stores.
+//     render_rays_kernel<C> is the kernel it always was, instruction for instruction.
+//   * normal_sum = sum_s w_s n_s needs the field's gradient at every sample: render_passes_kernel, in the forward-mode layout
+//     of density_grad_kernel (csrc/field_normal.hip): a wave owns 8 rays x 4 columns {value, d/dx, d/dy, d/dz}, lane p serves
+//     ray p >> 2 and kind p & 3.  The value column is the point query's own evaluation, so density_act and colour, and with
+//     them w_s and every output of the colour kernel, have the colour kernel's bits (the same ray_box, t_mid block,
+//     density_act_f, color_f, expf and composite); a call that asks for normal_sum is this ONE launch, not two.  n_s is
+//     unit_normal_of (field_fwd.h), the rule and the bits of ops.field_normals at x_s = o + z_s d.  The value lane composites
+//     what the colour kernel composites; the tangent lane of axis k keeps component k of normal_sum.
+//   * exact skipping: once T == 0 on every ray of a tile, every later w_s is alpha * 0 = +0 (alpha is in [0, 1] for a finite
+//     field) and adds nothing to any sum (n_s is finite by construction), so the tile stops evaluating; depths and zero weights
+//     of the tail are still written.  No threshold.  SCULPT_RENDER_FORM=noskip walks every sample (A/B); the two forms differ
+//     only for a field that is not finite (a NaN density where T == 0 gives w = NaN in the walk and +0 in the skip).
 #include <algorithm>
 
 #include "common.h"
+#include "field_fwd.h"
 #include "triplane_mlp.h"
 
 namespace sculpt {
@@ -51,12 +68,16 @@ __device__ __forceinline__ RayHit ray_box(const float o[3], const float d[3], fl
     return r;
 }
 
-template <int C>
+// Without `Passes` this is the colour kernel, argument for argument the one it always was.  render_rays_kernel<C, float *, float *>
+// takes depth_sum [N] and premul [N][3] (each nullable) after a0_lds and is the same code with the two sums added.
+template <int C, class... Passes>
 __global__ __launch_bounds__(512) void render_rays_kernel(
     const float *__restrict__ planes, int H, int W, const float *__restrict__ blob, const float *__restrict__ rays_o,
     const float *__restrict__ rays_d, long N, float radius, float span, float box, float density_bias,
     const float *__restrict__ t_vals, int S, float *__restrict__ comp_rgb, float *__restrict__ opacity,
-    float *__restrict__ z_vals, float *__restrict__ weights, int a0_lds) {
+    float *__restrict__ z_vals, float *__restrict__ weights, int a0_lds, Passes... passes) {
+    static_assert(sizeof...(Passes) == 0 || sizeof...(Passes) == 2, "no passes, or (float *depth_sum, float *premul)");
+    constexpr bool PASSES = sizeof...(Passes) == 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
     const int NH = hd.NH;
@@ -80,7 +101,7 @@ __global__ __launch_bounds__(512) void render_rays_kernel(
         for (int k = 0; k < 3; ++k) { o[k] = rays_o[3 * nc + k]; d[k] = rays_d[3 * nc + k]; }
         const RayHit hit = ray_box(o, d, box);
         const bool valid = live && hit.valid;
-        float T = 1.f, sw = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f;
+        float T = 1.f, sw = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, dz = 0.f;
         if (__builtin_amdgcn_ballot_w64(valid) != 0) {  // wave-uniform
             for (int s = 0; s < S; ++s) {
                 float z, x[3], delta;
@@ -114,6 +135,7 @@ __global__ __launch_bounds__(512) void render_rays_kernel(
                     c0 = c0 + w * r;
                     c1 = c1 + w * g;
                     c2 = c2 + w * b;
+                    if (PASSES) dz = dz + w * z;
                     T = T * ((1.0f - alpha) + 1e-10f);
                 }
                 if (writer) {
@@ -135,7 +157,134 @@ __global__ __launch_bounds__(512) void render_rays_kernel(
             comp_rgb[3 * n + 1] = (valid ? c1 : 0.f) + bg;
             comp_rgb[3 * n + 2] = (valid ? c2 : 0.f) + bg;
             if (opacity) opacity[n] = op;
+            if constexpr (PASSES) {
+                float *const out[2] = {passes...};
+                float *const depth_sum = out[0], *const premul = out[1];
+                if (depth_sum) depth_sum[n] = valid ? dz : 0.f;
+                if (premul) {
+                    premul[3 * n] = valid ? c0 : 0.f;
+                    premul[3 * n + 1] = valid ? c1 : 0.f;
+                    premul[3 * n + 2] = valid ? c2 : 0.f;
+                }
+            }
         }
+    }
+}
+
+// Every output in one launch, for a call that asks for normal_sum: 8 rays x 4 forward-mode columns per wave (see the head of this
+// file).  The value lane of a ray composites what the colour kernel composites, from the same values in the same order; the
+// tangent lane of axis k keeps component k of normal_sum.  All outputs but comp_rgb and normal_sum are nullable.
+template <int C>
+__global__ __launch_bounds__(512) void render_passes_kernel(
+    const float *__restrict__ planes, int H, int W, const float *__restrict__ blob, const float *__restrict__ rays_o,
+    const float *__restrict__ rays_d, long N, float radius, float span, float box, float density_bias,
+    const float *__restrict__ t_vals, int S, float *__restrict__ comp_rgb, float *__restrict__ opacity,
+    float *__restrict__ z_vals, float *__restrict__ weights, float *__restrict__ depth_sum, float *__restrict__ normal_sum,
+    float *__restrict__ premul, int a0_lds, int noskip) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
+    const int NH = hd.NH;
+    float *a0s = smem + lds_floats_for(NH);
+    if (a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
+    load_weights_to_lds(smem, blob, hd);
+    const LdsView L = lds_view(smem, NH);
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
+    const int p = lane & 31, h = lane >> 5;
+    const int kind = p & 3;
+    const bool is_value = kind == 0;
+    const long ntiles = (N + 7) / 8;
+    const float *A0g = blob + hd.off_a0;
+    const long HW = (long)H * W;
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+
+    for (long tile = (long)blockIdx.x * nwave + wave; tile < ntiles; tile += (long)gridDim.x * nwave) {
+        const long n = tile * 8 + (p >> 2);
+        const bool live = n < N, writer = live && is_value && h == 0;
+        const long nc = live ? n : N - 1;
+        float o[3], d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { o[k] = rays_o[3 * nc + k]; d[k] = rays_d[3 * nc + k]; }
+        const RayHit hit = ray_box(o, d, box);
+        const bool valid = live && hit.valid;
+        float T = 1.f, sw = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, dz = 0.f;
+        float nk_sum = 0.f;  // component kind - 1 of normal_sum (not used in the value lane)
+        int s = 0;
+        if (__builtin_amdgcn_ballot_w64(valid) != 0) {  // wave-uniform
+            for (; s < S; ++s) {
+                // every ray of the tile is opaque or a miss: each later weight is alpha * 0 = +0 and changes no sum
+                if (!noskip && __builtin_amdgcn_ballot_w64(valid && T != 0.f) == 0) break;
+                float z, x[3], delta;
+                {   // the colour kernel's block, word for word: the same z and xyz bits
+#pragma clang fp contract(off)
+                    const float ta = t_vals[s], tb = t_vals[s + 1];
+                    const float t_mid = (ta + tb) / 2.0f;
+                    z = hit.t_near * (1.0f - t_mid) + hit.t_far * t_mid;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) x[k] = valid ? o[k] + z * d[k] : 0.f;
+                    delta = tb - ta;
+                }
+                int off[3][4];
+                float wt[3][4];
+                point_taps<false>(x[0], x[1], x[2], radius, span, H, W, off, wt);
+                tangent_weights<false>(kind, x[0], x[1], x[2], radius, span, H, W, wt);
+                f32x16 x0 = is_value ? lds_bias16(L.bacc, 0, h, 0) : zero;
+                f32x16 x1 = is_value ? lds_bias16(L.bacc, 0, h, 1) : zero;
+                layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, x0, x1);
+                hidden_layers_fwd(L, NH, lane, h, is_value, x0, x1);
+                const float q = last_dot0_nobias(L, h, x0, x1);
+                const float dens = density_act_f(quad_bcast<0>(q + L.blast[0]), density_bias);  // last_dot(L, 0, ...) of the value column
+                const float r = color_f(last_dot(L, 1, h, x0, x1));  // the colour of the value column; unused elsewhere
+                const float g = color_f(last_dot(L, 2, h, x0, x1));
+                const float b = color_f(last_dot(L, 3, h, x0, x1));
+                float nrm[3];
+                unit_normal_of(quad_bcast<1>(q), quad_bcast<2>(q), quad_bcast<3>(q), nrm[0], nrm[1], nrm[2]);
+                const float nk = kind == 1 ? nrm[0] : (kind == 2 ? nrm[1] : nrm[2]);
+                float w;
+                {   // the colour kernel's composite, then the two new sums
+#pragma clang fp contract(off)
+                    const float alpha = 1.0f - expf(-delta * dens);
+                    w = alpha * T;
+                    sw = sw + w;
+                    c0 = c0 + w * r;
+                    c1 = c1 + w * g;
+                    c2 = c2 + w * b;
+                    dz = dz + w * z;
+                    nk_sum = nk_sum + w * nk;
+                    T = T * ((1.0f - alpha) + 1e-10f);
+                }
+                if (writer) {
+                    if (z_vals) z_vals[n * S + s] = valid ? z : 0.f;
+                    if (weights) weights[n * S + s] = valid ? w : 0.f;
+                }
+            }
+        }
+        if (writer && (z_vals || weights)) {  // what a skipped tail or a tile of misses leaves: the depths, and weights of +0
+            for (; s < S; ++s) {
+#pragma clang fp contract(off)
+                const float ta = t_vals[s], tb = t_vals[s + 1];
+                const float t_mid = (ta + tb) / 2.0f;
+                const float z = hit.t_near * (1.0f - t_mid) + hit.t_far * t_mid;
+                if (z_vals) z_vals[n * S + s] = valid ? z : 0.f;
+                if (weights) weights[n * S + s] = 0.f;
+            }
+        }
+        if (writer) {
+#pragma clang fp contract(off)
+            const float op = valid ? sw : 0.f;
+            const float bg = 1.0f - op;
+            comp_rgb[3 * n] = (valid ? c0 : 0.f) + bg;
+            comp_rgb[3 * n + 1] = (valid ? c1 : 0.f) + bg;
+            comp_rgb[3 * n + 2] = (valid ? c2 : 0.f) + bg;
+            if (opacity) opacity[n] = op;
+            if (depth_sum) depth_sum[n] = valid ? dz : 0.f;
+            if (premul) {
+                premul[3 * n] = valid ? c0 : 0.f;
+                premul[3 * n + 1] = valid ? c1 : 0.f;
+                premul[3 * n + 2] = valid ? c2 : 0.f;
+            }
+        }
+        if (live && !is_value && h == 0) normal_sum[3 * n + (kind - 1)] = valid ? nk_sum : 0.f;
     }
 }
 
@@ -170,6 +319,51 @@ extern "C" int sculpt_render_rays(const float *planes_cl, int C, int H, int W, c
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W,
                        reinterpret_cast<const float *>(mlp_packed), rays_o, rays_d, (long)n_rays, radius, span, box, density_bias,
                        t_vals, S, comp_rgb, opacity, z_vals, weights, a0_lds);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sculpt_render_passes(const float *planes_cl, int C, int H, int W, const void *mlp_packed, int n_hidden_64,
+                                    const float *rays_o, const float *rays_d, int64_t n_rays, float radius, float density_bias,
+                                    const float *t_vals, int S, float *comp_rgb, float *opacity, float *z_vals, float *weights,
+                                    float *depth_sum, float *normal_sum, float *premul, sculpt_stream_t stream) {
+    if (!depth_sum && !normal_sum && !premul)  // the colour picture alone: sculpt_render_rays' own launch
+        return sculpt_render_rays(planes_cl, C, H, W, mlp_packed, n_hidden_64, rays_o, rays_d, n_rays, radius, density_bias, t_vals, S,
+                                  comp_rgb, opacity, z_vals, weights, stream);
+    SC_REQUIRE(C == 40, "render_passes: built for C=40 channels per plane (got %d)", C);
+    SC_REQUIRE(planes_cl && mlp_packed, "render_passes: null input");
+    SC_REQUIRE(H >= 1 && W >= 1, "render_passes: bad plane size %d x %d", H, W);
+    SC_REQUIRE(n_rays >= 0, "render_passes: negative ray count");
+    SC_REQUIRE(S >= 1, "render_passes: need at least one sample per ray (got %d)", S);
+    SC_REQUIRE(n_hidden_64 >= 0, "render_passes: bad n_hidden_64");
+    SC_REQUIRE(radius > 0.f, "render_passes: radius must be positive");
+    if (n_rays == 0) return 0;
+    SC_REQUIRE(rays_o && rays_d && t_vals && comp_rgb, "render_passes: null rays, t_vals or comp_rgb");
+    size_t lds = (size_t)lds_floats_for(n_hidden_64) * sizeof(float);
+    SC_REQUIRE(lds <= 160 * 1024, "render_passes: %d hidden layers do not fit LDS", n_hidden_64);
+    const size_t a0_bytes = (size_t)3 * C * 64 * sizeof(float);
+    const int a0_lds = lds + a0_bytes <= 160 * 1024 ? 1 : 0;
+    if (a0_lds) lds += a0_bytes;
+    const float span = (float)((double)radius - (double)(-radius));
+    const float box = (float)(1.0 - 1.0e-3) * radius;
+    const float *blob = reinterpret_cast<const float *>(mlp_packed);
+    if (normal_sum) {  // everything in the forward-mode layout, one launch
+        auto kern = render_passes_kernel<40>;
+        SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const long ntiles = ((long)n_rays + 7) / 8;
+        const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
+        const int noskip = form_has("SCULPT_RENDER_FORM", "noskip") ? 1 : 0;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W, blob, rays_o, rays_d, (long)n_rays,
+                           radius, span, box, density_bias, t_vals, S, comp_rgb, opacity, z_vals, weights, depth_sum, normal_sum, premul,
+                           a0_lds, noskip);
+    } else {  // the colour kernel with its two more sums
+        auto kern = render_rays_kernel<40, float *, float *>;
+        SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const long ntiles = ((long)n_rays + 31) / 32;
+        const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W, blob, rays_o, rays_d, (long)n_rays,
+                           radius, span, box, density_bias, t_vals, S, comp_rgb, opacity, z_vals, weights, a0_lds, depth_sum, premul);
+    }
     SC_LAUNCH_CHECK();
     return 0;
 }

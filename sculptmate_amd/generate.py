@@ -77,15 +77,19 @@ class TripoGenerator(GeneratorFacade):
             return STATUS_FAILED
         return STATUS_OK
 
-    def render_views(self, input_image, n_views=8, **camera):
+    def render_views(self, input_image, n_views=8, passes=None, **camera):
         """Turntable previews of what generate_mesh would build from `input_image`: a list of n_views PIL pictures, rendered
-        from the scene code (TSR.render; camera: elevation_deg, camera_distance, fovy_deg, height, width).  Failures follow
-        generate_mesh's convention: STATUS_NOT_LOADED without a model, STATUS_FAILED (message printed) when rendering fails."""
+        from the scene code (TSR.render; camera: elevation_deg, camera_distance, fovy_deg, height, width).  With `passes` (any of
+        "color", "opacity", "rgba", "depth", "normal": TSR.render_passes) a list of n_views dicts {pass: PIL picture} instead.
+        Failures follow generate_mesh's convention: STATUS_NOT_LOADED without a model, STATUS_FAILED (message printed) when
+        rendering fails."""
         if self.model is None:
             return STATUS_NOT_LOADED
         try:
             with torch.no_grad():
                 codes = self.model([input_image], device=self.device)
+            if passes is not None:
+                return self.model.render_passes(codes, n_views=n_views, passes=passes, return_type="pil", **camera)[0]
             return self.model.render(codes, n_views=n_views, return_type="pil", **camera)[0]
         except Exception as err:
             print(self.run_error_tag, err)

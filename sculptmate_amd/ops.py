@@ -106,6 +106,20 @@ def ray_t_vals(n_samples, device):
     return t
 
 
+def _ray_args(who, planes, rays_o, rays_d, n_samples):
+    """What the two ray front-ends check and flatten -> (ChannelLastPlanes, the rays' leading shape, rays_o [N,3], rays_d [N,3], S)."""
+    if tuple(rays_o.shape) != tuple(rays_d.shape) or rays_o.shape[-1] != 3:
+        raise SculptError("%s: rays_o %s and rays_d %s must both be [..., 3]" % (who, tuple(rays_o.shape), tuple(rays_d.shape)))
+    S = int(n_samples)
+    if S < 1:
+        raise SculptError("%s: n_samples must be at least 1" % who)
+    if not isinstance(planes, ChannelLastPlanes):
+        planes = ChannelLastPlanes(planes)
+    ro = _req(rays_o.reshape(-1, 3).contiguous(), torch.float32, "rays_o")
+    rd = _req(rays_d.reshape(-1, 3).contiguous(), torch.float32, "rays_d")
+    return planes, tuple(rays_o.shape[:-1]), ro, rd, S
+
+
 def render_rays(planes, mlp, rays_o, rays_d, radius=0.87, density_bias=-1.0, n_samples=128, want=()):
     """TriplaneNeRFRenderer._forward (nerf_renderer.py:93-152) for one scene code in one launch (sculpt_render_rays).
     planes: [3,C,H,W] (converted to channel-last here, once) or a ChannelLastPlanes; rays_o / rays_d: [..., 3] world rays.
@@ -113,16 +127,7 @@ def render_rays(planes, mlp, rays_o, rays_d, radius=0.87, density_bias=-1.0, n_s
     unknown = set(want) - {"opacity", "z_vals", "weights"}
     if unknown:
         raise SculptError("render_rays: unknown output %s" % sorted(unknown))
-    if tuple(rays_o.shape) != tuple(rays_d.shape) or rays_o.shape[-1] != 3:
-        raise SculptError("render_rays: rays_o %s and rays_d %s must both be [..., 3]" % (tuple(rays_o.shape), tuple(rays_d.shape)))
-    S = int(n_samples)
-    if S < 1:
-        raise SculptError("render_rays: n_samples must be at least 1")
-    if not isinstance(planes, ChannelLastPlanes):
-        planes = ChannelLastPlanes(planes)
-    shape = tuple(rays_o.shape[:-1])
-    ro = _req(rays_o.reshape(-1, 3).contiguous(), torch.float32, "rays_o")
-    rd = _req(rays_d.reshape(-1, 3).contiguous(), torch.float32, "rays_d")
+    planes, shape, ro, rd, S = _ray_args("render_rays", planes, rays_o, rays_d, n_samples)
     N, dev = ro.shape[0], ro.device
     rgb = torch.empty((N, 3), dtype=torch.float32, device=dev)
     out = {k: torch.empty((N,) + w, dtype=torch.float32, device=dev) if k in want else None
@@ -130,6 +135,32 @@ def render_rays(planes, mlp, rays_o, rays_d, radius=0.87, density_bias=-1.0, n_s
     check(lib.sculpt_render_rays(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(ro), _ptr(rd),
                                  N, float(radius), float(density_bias), _ptr(ray_t_vals(S, dev)), S, _ptr(rgb),
                                  _ptr(out["opacity"]), _ptr(out["z_vals"]), _ptr(out["weights"]), _stream()))
+    return rgb.view(*shape, 3), {k: v.view(*shape, *v.shape[1:]) for k, v in out.items() if v is not None}
+
+
+_RENDER_PASSES = (("opacity", ()), ("z_vals", None), ("weights", None), ("depth_sum", ()), ("normal_sum", (3,)), ("premul", (3,)))
+
+
+def render_passes(planes, mlp, rays_o, rays_d, radius=0.87, density_bias=-1.0, n_samples=128, want=()):
+    """render_rays with passes beside the colour picture (sculpt_render_passes): raw per-ray sums over the samples, with the
+    weights of the colour picture, exactly 0 for a ray that misses the box.  Arguments and the first return value as render_rays.
+    extras[k] for k in want: "opacity" [...], "z_vals" [..., S], "weights" [..., S] (render_rays' own bits, whatever else is asked),
+    "depth_sum" [...] = sum w z, "premul" [..., 3] = sum w color (comp_rgb = premul + (1 - opacity)), "normal_sum" [..., 3] =
+    sum w n with n = field_normals' `normal` at the sample points.  tsr/passes.py turns the sums into depth, normal and rgba.
+    Still one launch; with "normal_sum" it is the forward-mode kernel (the field's gradient at every sample, about 4.5 x the time
+    of the colour kernel), without it the colour kernel at its own price.  Nothing per sample is written unless asked for."""
+    names = [k for k, _ in _RENDER_PASSES]
+    unknown = set(want) - set(names)
+    if unknown:
+        raise SculptError("render_passes: unknown output %s" % sorted(unknown))
+    planes, shape, ro, rd, S = _ray_args("render_passes", planes, rays_o, rays_d, n_samples)
+    N, dev = ro.shape[0], ro.device
+    rgb = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    out = {k: torch.empty((N,) + ((S,) if w is None else w), dtype=torch.float32, device=dev) if k in want else None
+           for k, w in _RENDER_PASSES}
+    check(lib.sculpt_render_passes(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(ro), _ptr(rd),
+                                   N, float(radius), float(density_bias), _ptr(ray_t_vals(S, dev)), S, _ptr(rgb),
+                                   *[_ptr(out[k]) for k in names], _stream()))
     return rgb.view(*shape, 3), {k: v.view(*shape, *v.shape[1:]) for k, v in out.items() if v is not None}
 
 

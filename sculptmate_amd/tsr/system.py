@@ -25,6 +25,7 @@ from .. import _lib, ops
 from ..engine import KernelEngine, prepare_ln_linear
 from .posemb import interpolate_pos_embedding
 from .cameras import get_spherical_cameras
+from . import passes as render_pass_rules
 from .utils import ImagePreprocessor
 
 BF16 = torch.bfloat16
@@ -296,6 +297,24 @@ class TriplaneNeRFRenderer:
         return torch.stack([self._forward(decoder, triplane[i], rays_o[i], rays_d[i]) for i in range(triplane.shape[0])], dim=0)
 
     __call__ = forward
+
+    def render_passes(self, decoder, triplane, rays_o, rays_d, passes=("color", "opacity", "depth", "normal")):
+        """forward with passes beside the colour picture -> {pass: tensor with the rays' leading shape} for the passes of
+        tsr/passes.py ("color" [..., 3] is forward's picture bit for bit, "opacity" [...], "rgba" [..., 4] premultiplied, "depth"
+        [...], "normal" [..., 3] in world space).  One launch per scene (ops.render_passes): the ray kernel, or, only when "normal"
+        is asked for, its forward-mode form.  triplane and rays as in forward."""
+        if self.randomized:
+            raise NotImplementedError("TriplaneNeRFRenderer: randomized=True (jittered samples, a training option) is not "
+                                      "implemented; the ray kernel places samples at the interval midpoints")
+        passes = render_pass_rules.check_passes(passes)
+        if not (isinstance(triplane, ops.ChannelLastPlanes) or triplane.ndim == 4):
+            each = [self.render_passes(decoder, triplane[i], rays_o[i], rays_d[i], passes) for i in range(triplane.shape[0])]
+            return {p: torch.stack([e[p] for e in each], dim=0) for p in passes}
+        dev = triplane.data.device if isinstance(triplane, ops.ChannelLastPlanes) else triplane.device
+        rgb, extras = ops.render_passes(triplane, decoder, rays_o.to(dev), rays_d.to(dev), radius=self.cfg.radius,
+                                        density_bias=self.cfg.density_bias, n_samples=self.num_samples_per_ray,
+                                        want=render_pass_rules.wanted(passes))
+        return render_pass_rules.finish(passes, rgb, extras)
 
 
 def _bf(x, dev):
@@ -948,6 +967,32 @@ class TSR(KernelEngine):
                     from PIL import Image
 
                     images.append([Image.fromarray((host[i] * 255.0).astype(np.uint8)) for i in range(n_views)])
+        return images
+
+    def render_passes(self, scene_codes, n_views: int, elevation_deg: float = 0.0, camera_distance: float = 1.9,
+                      fovy_deg: float = 40.0, height: int = 256, width: int = 256,
+                      passes=("color", "opacity", "depth", "normal"), return_type: str = "pt"):
+        """render with passes beside the colour picture -> per scene code a list of n_views dicts {pass: picture}.  passes: any of
+        "color" ([height, width, 3], render's picture bit for bit), "opacity" ([height, width]: what the ray absorbed, the mask of
+        the others), "rgba" ([height, width, 4], premultiplied: a cut-out to lay over a backdrop), "depth" ([height, width]:
+        distance from the camera, 0 where opacity is 0, noisy where it is small) and "normal" ([height, width, 3]: unit normals of
+        the density field in world space, 0 where there is none) -- tsr/passes.py has the rules.  return_type as render; "pil"
+        gives RGB / L / RGBA with straight alpha / mode F / RGB of n * 0.5 + 0.5.  Only what the passes need is computed: the
+        field's gradient (4.5 x the time of the picture alone) only for "normal".  Unknown or no passes: ValueError, before
+        anything is launched."""
+        passes = render_pass_rules.check_passes(passes)
+        if return_type not in render_pass_rules.RETURN_TYPES:
+            raise ValueError("return_type must be 'pt', 'np' or 'pil'")
+        if self.decoder is None:
+            raise _lib.SculptError("TSR.render_passes: the model has no weights on a device yet (load_state_dict + to(device))")
+        rays_o, rays_d = get_spherical_cameras(n_views, elevation_deg, camera_distance, fovy_deg, height, width)
+        rays_o, rays_d = rays_o.to(self.device, non_blocking=True), rays_d.to(self.device, non_blocking=True)
+        images = []
+        with torch.no_grad():
+            for code in scene_codes:
+                planes = ops.ChannelLastPlanes(code.to(self.device))
+                views = self.renderer.render_passes(self.decoder, planes, rays_o, rays_d, passes)
+                images.append(render_pass_rules.convert(views, return_type))
         return images
 
     def field_normals(self, points, scene_code):
