@@ -1015,6 +1015,38 @@ int sculpt_smooth_neighbours(const int64_t *skeys, int64_t n, int32_t *nb, sculp
 int sculpt_smooth_taubin(const int32_t *start, const int32_t *nb, const uint8_t *fixed, int64_t nv, int64_t n_nb, const float *P,
                          int iterations, double lam, double mu, float *work_a, float *work_b, float *out, sculpt_stream_t stream);
 
+/* Distance between triangle surfaces ON THE DEVICE (csrc/mesh_distance.hip; ops.mesh_closest_points, ops.mesh_sample_surface,
+ * ops.mesh_distance).  DEVICE pointers (params_host excepted), asynchronous on `stream`, no host wait.
+ * Compiled without floating-point contraction and restated bit for bit in tests/_distref.py.  Added without a version change
+ * (new symbols only).  The grid is the remesher's (sculpt_rmd_grid_count / sculpt_rmd_grid_fill, params_host = {lo x, y, z,
+ * cell, nx, ny, nz}, items / start the CSR of faces per cell); GP [nv][3], GF [gnf][3] with every index in range (trusted).
+ *   sculpt_surface_closest   per query Q[i] (fp32, widened to fp64): the lexicographic minimum of (d2_f, f) over ALL faces whose
+ *                            d2_f is not NaN, d2_f = |q_f - p|^2 summed (x x + y y) + z z, q_f = Ericson's closest point of face
+ *                            f.  d2 [n] f64, face [n] int32, closest [n][3] = q_face rounded once to fp32.  No face, or only
+ *                            NaN: +inf, -1, the query.  A non-finite query: NaN, -1, the query.  amax: a bound on |coordinate|
+ *                            of every vertex the faces name (it scales the guard of the walk's stopping test).
+ *                            order == records == NULL: the plain form, one thread per query in input order.  Otherwise the
+ *                            sorted form: order [n] = the permutation that sorts the keys of sculpt_surface_cells (int64),
+ *                            records = sculpt_surface_pack's.  Both forms give the same bits on every input.
+ *   sculpt_surface_cells     key [n] int32: the linear index of the query's clamped grid cell; nx ny nz for a non-finite query
+ *   sculpt_surface_pack      records [gnf][16] floats, 16-byte aligned: box min, box max, a, b, c, one pad
+ *   sculpt_surface_weights   area2 [nf] f64 = |cross(b - a, c - a)|; *max_bits = the bits of its maximum; w [nf] int64 =
+ *                            llrint(ldexp(area2, B - e)), e the frexp exponent of the maximum, B = min(40, 62 - bit_length(nf))
+ *   sculpt_surface_sample    n samples from cdf [nf] int64, the inclusive prefix sum of w with cdf[nf - 1] > 0: sample i takes
+ *                            words 3i .. 3i + 2 of splitmix64(seed): face = the first f with cdf[f] > mulhi64(r0, W); u, v =
+ *                            (r >> 40) 2^-24, reflected when u + v > 1; points [n][3] = (a + u (b - a)) + v (c - a) in fp32,
+ *                            face [n] int32, uv [n][2]
+ * Null, misaligned or out-of-range arguments are refused with an error code and a message; n == 0 launches nothing. */
+int sculpt_surface_closest(const float *Q, int64_t n, const int64_t *order, const float *GP, const int32_t *GF, int64_t gnf,
+                           const float *records, const int32_t *items, const int32_t *start, const double *params_host, double amax,
+                           double *d2, int32_t *face, float *closest, sculpt_stream_t stream);
+int sculpt_surface_cells(const float *Q, int64_t n, const double *params_host, int32_t *key, sculpt_stream_t stream);
+int sculpt_surface_pack(const float *GP, const int32_t *GF, int64_t gnf, float *records, sculpt_stream_t stream);
+int sculpt_surface_weights(const float *P, const int32_t *F, int64_t nf, double *area2, unsigned long long *max_bits, int64_t *w,
+                           sculpt_stream_t stream);
+int sculpt_surface_sample(const float *P, const int32_t *F, int64_t nf, const int64_t *cdf, int64_t n, unsigned long long seed,
+                          float *points, int32_t *face, float *uv, sculpt_stream_t stream);
+
 /* Mesh vertices onto the iso-surface of the density field (csrc/mesh_project.hip; ops.project_to_isosurface, ops.mesh_unfold,
  * ops.mesh_project).  DEVICE pointers, asynchronous on `stream`, no host wait.  Added without a version
  * change (new symbols only).

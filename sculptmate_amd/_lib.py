@@ -215,6 +215,11 @@ SIGNATURES = {
     "sculpt_smooth_edge_keys": (_i, [_vp, _vp, _vp]),
     "sculpt_smooth_neighbours": (_i, [_vp, _i64, _vp, _vp]),
     "sculpt_smooth_taubin": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
+    "sculpt_surface_closest": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
+    "sculpt_surface_cells": (_i, [_vp, _i64, _vp, _vp, _vp]),
+    "sculpt_surface_pack": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "sculpt_surface_weights": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "sculpt_surface_sample": (_i, [_vp, _vp, _i64, _vp, _i64, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     "sculpt_triplane_project": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _f, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_mesh_unfold": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp]),
     "rasterize_cpu": (None, [_vp, _sz, _vp, _sz, ctypes.c_longlong, _vp]),
@@ -278,6 +283,6 @@ def check(rc):
 
 def form_has(var, token):
     """Non-default kernel forms for tests and A/B: one environment variable per kernel family (SCULPT_GEMM_TILE, SCULPT_L3_TILE,
-    SCULPT_ATTN_FORM, SCULPT_DENSITY_FORM, SCULPT_MC_FORM, SCULPT_RENDER_FORM), a comma-separated list of tokens (csrc/common.h:
+    SCULPT_ATTN_FORM, SCULPT_DENSITY_FORM, SCULPT_MC_FORM, SCULPT_RENDER_FORM, SCULPT_DISTANCE_FORM), a comma-separated list of tokens (csrc/common.h:
     form_has)."""
     return any(t == token or t.startswith(token + "=") for t in os.environ.get(var, "").split(",") if t)

@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "remesh_topo.h"
+#include "surface_grid.h"
 
 namespace {
 
@@ -352,30 +353,7 @@ __global__ void split_faces_kernel(Topo T, const float *__restrict__ P, const in
     for (int i = 0; i < 3 * nt; ++i) Fo[3 * first + i] = t[i];
 }
 
-// ---- closest point on the input surface (uniform grid) --------------------------------------------------------------------
-struct Grid {
-    const float *P;
-    const int32_t *F, *items, *start;
-    double lo[3], cell;
-    int n[3];
-    long nf;
-};
-
-__device__ inline int grid_clamp(double q, int n) { return max(0, min(n - 1, (int)floor(q))); }
-
-__device__ void grid_range(const Grid &G, long f, int lo[3], int hi[3]) {
-    for (int k = 0; k < 3; ++k) {
-        double mn = 1e300, mx = -1e300;
-        for (int j = 0; j < 3; ++j) {
-            const double c = (double)G.P[3 * G.F[3 * f + j] + k];
-            mn = fmin(mn, c);
-            mx = fmax(mx, c);
-        }
-        lo[k] = grid_clamp((mn - G.lo[k]) / G.cell, G.n[k]);
-        hi[k] = grid_clamp((mx - G.lo[k]) / G.cell, G.n[k]);
-    }
-}
-
+// ---- closest point on the input surface (uniform grid: Grid, grid_range and closest_on_triangle are surface_grid.h) ---------
 __global__ void grid_count_kernel(Grid G, int32_t *__restrict__ cnt) {
     const long f = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= G.nf) return;
@@ -398,27 +376,6 @@ __global__ void grid_fill_kernel(Grid G, const int32_t *__restrict__ off_incl, i
                 cell[o] = (int32_t)(((long)z * G.n[1] + y) * G.n[0] + x);
                 face[o++] = (int32_t)f;
             }
-}
-
-// Ericson, Real-Time Collision Detection, 5.1.5 (remesh_host.h closest_on_triangle)
-__device__ D3 closest_on_triangle(D3 p, D3 a, D3 b, D3 c) {
-    const D3 ab = b - a, ac = c - a, ap = p - a;
-    const double d1 = dot(ab, ap), d2 = dot(ac, ap);
-    if (d1 <= 0 && d2 <= 0) return a;
-    const D3 bp = p - b;
-    const double d3 = dot(ab, bp), d4 = dot(ac, bp);
-    if (d3 >= 0 && d4 <= d3) return b;
-    const double vc = d1 * d4 - d3 * d2;
-    if (vc <= 0 && d1 >= 0 && d3 <= 0) return a + (d1 / (d1 - d3)) * ab;
-    const D3 cp = p - c;
-    const double d5 = dot(ab, cp), d6 = dot(ac, cp);
-    if (d6 >= 0 && d5 <= d6) return c;
-    const double vb = d5 * d2 - d1 * d6;
-    if (vb <= 0 && d2 >= 0 && d6 <= 0) return a + (d2 / (d2 - d6)) * ac;
-    const double va = d3 * d6 - d5 * d4;
-    if (va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0) return b + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) * (c - b);
-    const double den = 1.0 / (va + vb + vc);
-    return a + (vb * den) * ab + (vc * den) * ac;
 }
 
 // expanding Chebyshev shells of cells around p's cell until nothing unvisited can be closer (remesh_host.h SurfaceGrid::closest)
@@ -603,21 +560,6 @@ __global__ void halfedge_lengths_kernel(const float *__restrict__ P, const int32
     double s = 0;
     for (int k = 0; k < 3; ++k) s += norm(ld(P, F[3 * f + k]) - ld(P, F[3 * f + (k + 1) % 3]));
     len[f] = s;
-}
-
-Grid grid_of(const float *GP, const int32_t *GF, long gnf, const int32_t *items, const int32_t *start, const double *params) {
-    Grid G;
-    G.P = GP;
-    G.F = GF;
-    G.items = items;
-    G.start = start;
-    G.nf = gnf;
-    for (int k = 0; k < 3; ++k) {
-        G.lo[k] = params ? params[k] : 0.0;
-        G.n[k] = params ? (int)params[4 + k] : 1;
-    }
-    G.cell = params ? params[3] : 1.0;
-    return G;
 }
 
 }  // namespace

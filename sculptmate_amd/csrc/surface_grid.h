@@ -1,0 +1,73 @@
+// The uniform grid over a triangle surface and the closest point of one triangle, shared by the remesher's projection
+// (csrc/remesh_device.hip: grid_closest, relax_kernel) and the surface distance queries (csrc/mesh_distance.hip).  One copy;
+// every translation unit that includes it gets its own (anonymous namespace).  Include it after remesh_topo.h's D3 helpers and,
+// like that file, AFTER `#pragma clang fp contract(off)` in a unit that wants its arithmetic uncontracted: the two units compile
+// closest_on_triangle under different contraction settings on purpose (the remesher keeps the bits it always had, the distance
+// queries are restated operation for operation in NumPy).
+#pragma once
+
+#include "remesh_topo.h"
+
+namespace {
+
+struct Grid {
+    const float *P;
+    const int32_t *F, *items, *start;
+    double lo[3], cell;
+    int n[3];
+    long nf;
+};
+
+__device__ inline int grid_clamp(double q, int n) { return max(0, min(n - 1, (int)floor(q))); }
+
+__device__ void grid_range(const Grid &G, long f, int lo[3], int hi[3]) {
+    for (int k = 0; k < 3; ++k) {
+        double mn = 1e300, mx = -1e300;
+        for (int j = 0; j < 3; ++j) {
+            const double c = (double)G.P[3 * G.F[3 * f + j] + k];
+            mn = fmin(mn, c);
+            mx = fmax(mx, c);
+        }
+        lo[k] = grid_clamp((mn - G.lo[k]) / G.cell, G.n[k]);
+        hi[k] = grid_clamp((mx - G.lo[k]) / G.cell, G.n[k]);
+    }
+}
+
+// Ericson, Real-Time Collision Detection, 5.1.5 (remesh_host.h closest_on_triangle)
+__device__ D3 closest_on_triangle(D3 p, D3 a, D3 b, D3 c) {
+    const D3 ab = b - a, ac = c - a, ap = p - a;
+    const double d1 = dot(ab, ap), d2 = dot(ac, ap);
+    if (d1 <= 0 && d2 <= 0) return a;
+    const D3 bp = p - b;
+    const double d3 = dot(ab, bp), d4 = dot(ac, bp);
+    if (d3 >= 0 && d4 <= d3) return b;
+    const double vc = d1 * d4 - d3 * d2;
+    if (vc <= 0 && d1 >= 0 && d3 <= 0) return a + (d1 / (d1 - d3)) * ab;
+    const D3 cp = p - c;
+    const double d5 = dot(ab, cp), d6 = dot(ac, cp);
+    if (d6 >= 0 && d5 <= d6) return c;
+    const double vb = d5 * d2 - d1 * d6;
+    if (vb <= 0 && d2 >= 0 && d6 <= 0) return a + (d2 / (d2 - d6)) * ac;
+    const double va = d3 * d6 - d5 * d4;
+    if (va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0) return b + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) * (c - b);
+    const double den = 1.0 / (va + vb + vc);
+    return a + (vb * den) * ab + (vc * den) * ac;
+}
+
+// the grid of params = {lo x, y, z, cell, nx, ny, nz} (include/sculpt_hip.h sculpt_rmd_grid_*); null params: one unit cell
+Grid grid_of(const float *GP, const int32_t *GF, long gnf, const int32_t *items, const int32_t *start, const double *params) {
+    Grid G;
+    G.P = GP;
+    G.F = GF;
+    G.items = items;
+    G.start = start;
+    G.nf = gnf;
+    for (int k = 0; k < 3; ++k) {
+        G.lo[k] = params ? params[k] : 0.0;
+        G.n[k] = params ? (int)params[4 + k] : 1;
+    }
+    G.cell = params ? params[3] : 1.0;
+    return G;
+}
+
+}  // namespace

@@ -704,6 +704,204 @@ def mesh_smooth(vertices, faces, smooth):
 
 
 # ----------------------------------------------------------------------------------------------
+# distance between surfaces: area-uniform samples, closest points, Chamfer / Hausdorff / F-score (csrc/mesh_distance.hip,
+# DESIGN.md 3.3e)
+# ----------------------------------------------------------------------------------------------
+DISTANCE_SAMPLES = 100_000
+
+
+def sample_rule(n, seed):
+    """(n, seed) of mesh_sample_surface -> (int n >= 0, int 0 <= seed < 2^64).  Anything else, bool included, is a ValueError --
+    raised here, before anything is launched."""
+    if _is_count(n, 0) and _is_count(seed, 0, 2 ** 64 - 1):
+        return int(n), int(seed)
+    raise ValueError("n must be an int >= 0 and seed an int in 0 .. 2^64 - 1, got n=%r, seed=%r" % (n, seed))
+
+
+def _threshold_rule(threshold):
+    if threshold is None:
+        return None
+    if _is_real(threshold) and float(threshold) > 0.0 and float(threshold) < math.inf:   # a NaN fails the comparison
+        return float(threshold)
+    raise ValueError("threshold must be None or a finite number > 0, got %r" % (threshold,))
+
+
+def _surface(vertices, faces, who):
+    """(P f32 [Nv, 3], F int32 [Nf, 3]) of a device mesh after the remesher's input check: a face index out of range and a
+    non-finite vertex are a SculptError; a face that names a vertex twice passes (it is a degenerate triangle like any other)."""
+    from .sf3d import remesh_device as rmd
+
+    _device_mesh(vertices, faces, who)
+    return rmd._inputs(vertices, faces, who, allow_repeated=True)
+
+
+class _SurfaceIndex:
+    """The remesher's uniform grid over a surface, and the packed face records of the sorted query form (built on first use)."""
+
+    def __init__(self, P, F):
+        from .sf3d import remesh_device as rmd
+
+        self.P, self.F = P, F
+        self.ctx = rmd._Ctx()
+        self.grid = rmd._Grid(self.ctx, P, F)
+        self._records = None
+
+    def records(self):
+        if self._records is None:
+            self._records = torch.empty((max(self.F.shape[0], 1), 16), dtype=torch.float32, device=self.P.device)
+            check(lib.sculpt_surface_pack(_ptr(self.P), _ptr(self.F), self.F.shape[0], _ptr(self._records), _stream()))
+        return self._records
+
+    def closest(self, points):
+        """points f32 [N, 3] contiguous, N > 0 -> (d2 f64 [N], face int32 [N], closest f32 [N, 3])."""
+        g, dev, n, nf = self.grid, points.device, points.shape[0], self.F.shape[0]
+        d2 = torch.empty(n, dtype=torch.float64, device=dev)
+        face = torch.empty(n, dtype=torch.int32, device=dev)
+        closest = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        order = records = None
+        if not _lib.form_has("SCULPT_DISTANCE_FORM", "plain") and nf:
+            key = torch.empty(n, dtype=torch.int32, device=dev)
+            check(lib.sculpt_surface_cells(_ptr(points), n, g.params, _ptr(key), _stream()))
+            order = torch.sort(key, stable=True).indices   # stable: one permutation, though any would give the same results
+            records = self.records()
+        check(lib.sculpt_surface_closest(_ptr(points), n, _ptr(order) if order is not None else None, _ptr(self.P) if nf else None,
+                                         _ptr(self.F) if nf else None, nf, _ptr(records) if records is not None else None,
+                                         _ptr(g.items) if nf else None, _ptr(g.start) if nf else None, g.params, float(g.amax),
+                                         _ptr(d2), _ptr(face), _ptr(closest), _stream()))
+        return d2, face, closest
+
+
+def _query_points(points, who):
+    if not (isinstance(points, torch.Tensor) and points.is_cuda):
+        raise SculptError("%s: points must be a CUDA/HIP tensor (no CPU fallback)" % who)
+    if points.dim() != 2 or points.shape[1] != 3 or not points.dtype.is_floating_point:
+        raise SculptError("points must be float [N, 3], got %s %s" % (points.dtype, tuple(points.shape)))
+    return points.detach().to(torch.float32).contiguous()
+
+
+def _closest(index, points):
+    if points.shape[0] == 0:
+        dev = points.device
+        return (torch.empty(0, dtype=torch.float64, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty((0, 3), dtype=torch.float32, device=dev))
+    d2, face, closest = index.closest(points)
+    return d2, face.long(), closest
+
+
+def mesh_closest_points(points, vertices, faces):
+    """The closest point of a triangle mesh to each of N query points, on the device.  points float [N, 3], vertices float
+    [Nv, 3], faces int32 / int64 [Nf, 3] (device tensors; CPU tensors are refused).
+    -> (d2 f64 [N] squared distance, face i64 [N] the winning face, closest f32 [N, 3] its closest point rounded once).
+    Contract (csrc/mesh_distance.hip; tests/_distref.py restates it by brute force, bit for bit):
+      - positions are fp32 (other float dtypes are converted first), the arithmetic is fp64 without contraction;
+      - per face f: q_f = Ericson's closest point, d2_f = |q_f - p|^2; the answer is the lexicographic minimum of (d2_f, f)
+        over ALL faces whose d2_f is not NaN -- of several faces at the same distance the lowest index wins;
+      - no face, or every face NaN (collinear corners can give NaN): d2 = +inf, face = -1, closest = the query;
+      - a non-finite query: d2 = NaN, face = -1, closest = the query;
+      - a face index out of range and a non-finite vertex are a SculptError; N == 0 launches nothing;
+      - the uniform grid only accelerates; SCULPT_DISTANCE_FORM=plain selects the one-thread-per-query-in-input-order form,
+        the default sorts the queries by grid cell and culls faces by their boxes: the same bits on every input;
+      - the host reads back the input check's status and the grid's two small results (bounds, list length)."""
+    pts = _query_points(points, "mesh_closest_points")
+    P, F = _surface(vertices, faces, "mesh_closest_points")
+    if pts.shape[0] == 0:
+        return _closest(None, pts)
+    return _closest(_SurfaceIndex(P, F), pts)
+
+
+def _weights(P, F):
+    nf = F.shape[0]
+    w = torch.zeros(nf, dtype=torch.int64, device=P.device)
+    if nf:
+        area2 = torch.empty(nf, dtype=torch.float64, device=P.device)
+        mbits = torch.empty(1, dtype=torch.int64, device=P.device)
+        check(lib.sculpt_surface_weights(_ptr(P), _ptr(F), nf, _ptr(area2), _ptr(mbits), _ptr(w), _stream()))
+    return w
+
+
+def _sample(P, F, n, seed):
+    dev, nf = P.device, F.shape[0]
+    W = 0
+    if nf:
+        cdf = torch.cumsum(_weights(P, F), 0)   # int64: exact in any order
+        W = int(cdf[-1].item())
+    if W <= 0:
+        raise SculptError("mesh_sample_surface: the mesh has no face with area to sample")
+    points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    uv = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    check(lib.sculpt_surface_sample(_ptr(P), _ptr(F), nf, _ptr(cdf), n, seed, _ptr(points), _ptr(face), _ptr(uv), _stream()))
+    return points, face.long(), uv
+
+
+def surface_weights(vertices, faces):
+    """The integer area weights mesh_sample_surface draws faces by: w i64 [Nf] (csrc/mesh_distance.hip: twice the area in fp64,
+    scaled by a power of two so that the largest is at most 2^B, rounded to nearest even)."""
+    return _weights(*_surface(vertices, faces, "surface_weights"))
+
+
+def mesh_sample_surface(vertices, faces, n, seed=0):
+    """n points distributed uniformly over the area of a triangle mesh, on the device.  vertices float [Nv, 3], faces int32 /
+    int64 [Nf, 3] (device tensors); n an int >= 0, seed an int in 0 .. 2^64 - 1 (sample_rule).
+    -> (points f32 [n, 3], face i64 [n], uv f32 [n, 2]): point = (a + u (b - a)) + v (c - a) of its face's corners.
+    The rule is integer wherever order could matter (csrc/mesh_distance.hip header; tests/_distref.py restates it bit for bit):
+    quantised area weights, their exact prefix sum, the splitmix64 stream of `seed`, three words per sample.  A face without area
+    is never drawn; a mesh without any (or without faces) is a SculptError when n > 0.  n == 0 launches nothing.  One readback:
+    the total weight (after the input check's status)."""
+    n, seed = sample_rule(n, seed)
+    _device_mesh(vertices, faces, "mesh_sample_surface")
+    if n == 0:
+        dev = vertices.device
+        return (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty((0, 2), dtype=torch.float32, device=dev))
+    P, F = _surface(vertices, faces, "mesh_sample_surface")
+    return _sample(P, F, n, seed)
+
+
+def _one_way(d2, tau):
+    d = torch.sqrt(d2)
+    below = (d < tau).sum().to(torch.float64) if tau is not None else d.new_zeros(())
+    return [d.mean(), torch.sqrt(d2.mean()), d.max(), below]
+
+
+def mesh_distance(vertices_a, faces_a, vertices_b, faces_b, samples=DISTANCE_SAMPLES, seed=0, threshold=None):
+    """How far two triangle surfaces are from each other, whatever their topology: the distances from points on A to the
+    closest point of B and back.  samples: an int >= 1 -- that many area-uniform points per mesh (mesh_sample_surface with
+    `seed` on A and seed + 1 mod 2^64 on B) -- or None: the meshes' own vertices (deterministic and free of sampling noise: "how
+    far did this option move the surface").  threshold: None or tau > 0.
+    -> dict of Python floats:
+        a_to_b, b_to_a   {"mean", "rms", "max"} of d = sqrt(d2) in fp64
+        chamfer          (mean a->b + mean b->a) / 2
+        hausdorff        the larger max
+        precision, recall, fscore   (with a threshold) the share of a->b / b->a distances below tau, and 2 P R / (P + R)
+                                    (0 when P + R == 0)
+    The queries are mesh_closest_points; the reductions are torch calls and one small tensor is read back."""
+    tau = _threshold_rule(threshold)
+    if samples is not None:
+        samples, seed = sample_rule(samples, seed)
+        if samples < 1:
+            raise ValueError("samples must be None or an int >= 1, got %r" % (samples,))
+    A = _surface(vertices_a, faces_a, "mesh_distance")
+    B = _surface(vertices_b, faces_b, "mesh_distance")
+    if samples is None:
+        qa, qb = A[0], B[0]
+        if qa.shape[0] == 0 or qb.shape[0] == 0:
+            raise SculptError("mesh_distance: a mesh without vertices has no distance")
+    else:
+        qa = _sample(A[0], A[1], samples, seed)[0]
+        qb = _sample(B[0], B[1], samples, (seed + 1) % 2 ** 64)[0]
+    ab = _SurfaceIndex(*B).closest(qa)[0]
+    ba = _SurfaceIndex(*A).closest(qb)[0]
+    r = torch.stack(_one_way(ab, tau) + _one_way(ba, tau)).tolist()
+    out = {"a_to_b": {"mean": r[0], "rms": r[1], "max": r[2]}, "b_to_a": {"mean": r[4], "rms": r[5], "max": r[6]},
+           "chamfer": 0.5 * (r[0] + r[4]), "hausdorff": max(r[2], r[6])}
+    if tau is not None:
+        p, q = r[3] / ab.shape[0], r[7] / ba.shape[0]
+        out.update(precision=p, recall=q, fscore=2.0 * p * q / (p + q) if p + q > 0 else 0.0)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # projection onto the field's iso-surface: fused Newton kernel + fold guard (csrc/mesh_project.hip, DESIGN.md 3.1e)
 # ----------------------------------------------------------------------------------------------
 PROJECT_STEPS, PROJECT_CELLS = 8, 1.0   # what project=True means: at most 8 steps inside a trust radius of one lattice cell

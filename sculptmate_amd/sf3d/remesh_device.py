@@ -58,7 +58,8 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
 
 
-def _inputs(v, f, who, check_faces=True):
+def _inputs(v, f, who, check_faces=True, allow_repeated=False):
+    """allow_repeated: a face that names a vertex twice passes (a distance query can live with it; a topology pass cannot)."""
     for t, name in ((v, "v"), (f, "f")):
         if not (isinstance(t, torch.Tensor) and t.is_cuda):
             raise SculptError("%s: %s must be a CUDA/HIP tensor (no CPU fallback)" % (who, name))
@@ -80,7 +81,7 @@ def _inputs(v, f, who, check_faces=True):
         s = int(status.item())
         if s & 1:
             raise SculptError("%s: face index out of range" % who)
-        if s & 2:
+        if s & 2 and not allow_repeated:
             raise SculptError("%s: degenerate face (repeated vertex index)" % who)
         if s & 4:
             raise SculptError("%s: non-finite vertex position" % who)
@@ -288,11 +289,13 @@ class _Grid:
         if nf == 0:
             self.params = (ctypes.c_double * 7)(0, 0, 0, 1, 1, 1, 1)
             self.items = self.start = None
+            self.amax = 0.0
             return
         pts = GP[GF.reshape(-1).long()].to(torch.float64)
         lo, hi = pts.min(0).values, pts.max(0).values
         b = ctx.read(lo[0:1], lo[1:2], lo[2:3], hi[0:1], hi[1:2], hi[2:3])
         lo3, ext = b[:3], [b[3 + k] - b[k] for k in range(3)]
+        self.amax = max(abs(x) for x in b)  # the largest |coordinate| of the surface (ops.mesh_closest_points)
         longest = max(ext)
         per_side = max(1.0, min(math.sqrt(nf / 2.0), (4.0 * nf) ** (1.0 / 3.0)))
         cell = longest / per_side if longest > 0 else 1.0

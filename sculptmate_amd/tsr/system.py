@@ -92,6 +92,18 @@ class Mesh:
         v = ops.mesh_smooth(self.vertices, self.faces, smooth)
         return Mesh(v, self.faces, self.vertex_colors, uvs=self.uvs, texture=self.texture)
 
+    def sample_surface(self, n, seed=0):
+        """n points uniform over this mesh's area (ops.mesh_sample_surface on its device tensors; host arrays are refused like
+        any CPU tensor) -> (points f32 [n, 3], face i64 [n], uv f32 [n, 2]); the same (n, seed) gives the same bits."""
+        return ops.mesh_sample_surface(self.vertices, self.faces, n, seed)
+
+    def distance_to(self, other: "Mesh", samples=ops.DISTANCE_SAMPLES, seed=0, threshold=None) -> dict:
+        """How far this surface is from `other`'s, whatever their topologies (ops.mesh_distance on the two meshes' device
+        tensors): Chamfer and Hausdorff distance, mean / rms / max in both directions and, with a threshold, precision, recall
+        and F-score.  samples=None measures from the meshes' own vertices: what an option such as smooth or simplify did to the
+        surface, without sampling noise."""
+        return ops.mesh_distance(self.vertices, self.faces, other.vertices, other.faces, samples=samples, seed=seed, threshold=threshold)
+
     def to_trimesh(self):  # pragma: no cover (trimesh is optional)
         import trimesh
 
