@@ -1047,6 +1047,34 @@ int sculpt_surface_weights(const float *P, const int32_t *F, int64_t nf, double 
 int sculpt_surface_sample(const float *P, const int32_t *F, int64_t nf, const int64_t *cdf, int64_t n, unsigned long long seed,
                           float *points, int32_t *face, float *uv, sculpt_stream_t stream);
 
+/* Rays against a triangle surface (csrc/mesh_ray.hip; ops.mesh_ray_cast, ops.mesh_occlusion).  Compiled
+ * without floating-point contraction and restated bit for bit in tests/_rayref.py.  Added without a version change (new symbols
+ * only).  The grid, the records, the order and amax are those of sculpt_surface_closest; the grid must cover the surface: lo is
+ * the least coordinate of the vertices the faces name, and lo + n cell is not below their greatest one on an axis with n < 1024.
+ *   sculpt_surface_ray_cast   per ray (O[i], D[i]) (fp32, widened to fp64) over tmin <= t <= tmax (0 <= tmin <= tmax, tmax may
+ *                             be +inf): the lexicographic minimum of (t_f, f) over ALL faces that the two-sided per-face rule
+ *                             at the top of csrc/mesh_ray.hip reports hit (Moeller-Trumbore in fp64 with a relative
+ *                             determinant test, then the box clause: the hit point lies within E = 2^-40 max(|o|_inf, amax) of
+ *                             the face's bounding box).  t [n] f64, face [n] int32, uv [n][2] = (u, v) of the winner rounded
+ *                             once.  No hit, or a zero direction: +inf, -1, 0.  A non-finite origin or direction: NaN, -1, 0.
+ *                             order == records == NULL: the plain form, one thread per ray in input order; otherwise the sorted
+ *                             form (order [n] sorts the keys of sculpt_surface_cells of the origins).  The same bits either way.
+ *   sculpt_surface_occlusion  ao [n] f32 of the points P [n][3] with normals N [n][3] under the k directions dirs [k][3] shared
+ *                             by all points, 1 <= k <= 1024, in fp32 without contraction: w_j = (n.x d.x + n.y d.y) + n.z d.z;
+ *                             direction j takes part iff w_j > 0; its ray runs from p + offset n (the product rounded, then the
+ *                             sum) along dirs[j] over [0, max_distance] and is occluded iff sculpt_surface_ray_cast would
+ *                             report a face; ao = (sum of w_j of the rays that hit nothing) / (sum of all w_j), both summed in
+ *                             the order of j; 1 when no direction takes part; NaN for a non-finite p or n.  records as above
+ *                             (always needed with gnf > 0); order [n] or NULL (the points in input order).
+ * Null, misaligned or out-of-range arguments are refused with an error code and a message; n == 0 launches nothing. */
+int sculpt_surface_ray_cast(const float *O, const float *D, int64_t n, const int64_t *order, const float *GP, const int32_t *GF,
+                            int64_t gnf, const float *records, const int32_t *items, const int32_t *start, const double *params_host,
+                            double amax, double tmin, double tmax, double *t, int32_t *face, float *uv, sculpt_stream_t stream);
+int sculpt_surface_occlusion(const float *P, const float *N, int64_t n, const int64_t *order, const float *dirs, int k, float offset,
+                             float max_distance, const float *GP, const int32_t *GF, int64_t gnf, const float *records,
+                             const int32_t *items, const int32_t *start, const double *params_host, double amax, float *ao,
+                             sculpt_stream_t stream);
+
 /* Mesh vertices onto the iso-surface of the density field (csrc/mesh_project.hip; ops.project_to_isosurface, ops.mesh_unfold,
  * ops.mesh_project).  DEVICE pointers, asynchronous on `stream`, no host wait.  Added without a version
  * change (new symbols only).

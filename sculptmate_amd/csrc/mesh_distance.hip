@@ -266,17 +266,6 @@ __global__ void sample_kernel(const float *__restrict__ P, const int32_t *__rest
     uv[2 * i] = u, uv[2 * i + 1] = v;
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-int check_grid(const char *who, const float *GP, const int32_t *GF, int64_t gnf, const double *params) {
-    SC_REQUIRE(gnf >= 0 && 3 * gnf < ((int64_t)1 << 31), "%s: %lld faces do not fit int32 indices", who, (long long)gnf);
-    SC_REQUIRE(params, "%s: null grid params", who);
-    SC_REQUIRE(gnf == 0 || (GP && GF), "%s: null mesh", who);
-    for (int k = 0; k < 3; ++k) SC_REQUIRE(params[4 + k] >= 1 && params[4 + k] <= 1024, "%s: grid side %g (1 .. 1024)", who, params[4 + k]);
-    SC_REQUIRE(params[3] > 0 && params[3] < INFINITY, "%s: grid cell %g", who, params[3]);
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {

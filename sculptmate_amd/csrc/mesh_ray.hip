@@ -1,0 +1,313 @@
+// Rays against a triangle surface ON THE DEVICE (sculpt_surface_ray_cast, sculpt_surface_occlusion, include/sculpt_hip.h; driven
+// by sculptmate_amd/ops.py mesh_ray_cast / mesh_occlusion): the closest face a ray hits, and the ambient occlusion of points under
+// a shared set of directions.  The unit is compiled with floating-point contraction OFF (the pragma below, before the shared
+// helpers), so every value is a fixed sequence of IEEE operations that tests/_rayref.py restates in NumPy bit for bit.
+//
+// ---- the per-face rule (the contract) ----------------------------------------------------------------------------------------
+// Ray (o, d): fp32 widened to fp64.  Corners a, b, c: fp32 widened to fp64.  Range 0 <= tmin <= tmax, tmax may be +inf.  The face
+// is two-sided.  dot(x, y) = (x.x y.x + x.y y.y) + x.z y.z, cross as written in remesh_topo.h (two products, one difference).
+//     e1 = b - a; e2 = c - a; pv = cross(d, e2); det = dot(e1, pv)
+//     miss unless det det > 2^-60 (dot(e1, e1) dot(pv, pv))         (parallel, degenerate, NaN: all misses)
+//     inv = 1 / det; tv = o - a; u = dot(tv, pv) inv;               miss unless u >= 0 && u <= 1
+//     qv = cross(tv, e1);        v = dot(d, qv) inv;                miss unless v >= 0 && u + v <= 1
+//     t = dot(e2, qv) inv;                                          miss unless t >= tmin && t <= tmax
+//     h = o + t d (per component: the product rounded, then the sum)
+//                                miss unless box_min - E <= h <= box_max + E in every component
+// box_min / box_max: the min / max of the fp32 corners; E = 2^-40 S, S = max(|o|_inf, amax), amax the caller's bound on |coordinate|
+// of every vertex a face names (as in sculpt_surface_closest).  The BOX CLAUSE is part of the rule, not an optimisation: it makes
+// every reported hit a geometric fact -- the computed hit point lies within E of the face's box -- and the grid walk below is
+// proven against that fact alone.  A face seen nearly edge-on can give a wild t that "hits" far from the face; the clause
+// discards it.  On rays of ordinary shape it discards nothing.  (An infinite t passes t <= +inf and fails the clause.)
+// Answer per ray: the lexicographic minimum of (t_f, f) over ALL faces that hit; t, face and (u, v) are the winner's, (u, v)
+// rounded once to fp32.  No hit: t = +inf, face = -1, uv = 0.  A zero direction hits nothing.  A non-finite origin or direction:
+// t = NaN, face = -1, uv = 0, and the grid is never entered.  Watertightness along shared edges is NOT promised: u, v and
+// u + v are rounded per face, so a ray through an edge may pass between the two faces.
+// The answer is a property of the inputs alone: the grid, the order of the threads and the form of the kernel only decide which
+// faces are SKIPPED, and a face is skipped only when it provably cannot be that minimum.
+//
+// ---- why a skipped face cannot win -------------------------------------------------------------------------------------------
+// Notation: f a face that hits at t_f with computed hit point h; h' = h clamped into f's box, so |h' - h|_inf <= E; best the least
+// t found so far (+inf at first); W = 4 E the walk's slack; x(t) = o + t d exactly; a the dominant axis (|d_a| >= |d_k|, d_a != 0).
+// What the grid must be: lo_k <= every coordinate of a named vertex <= up_k, up_k = lo_k + n_k cell when n_k < 1024 (the
+// remesher's n_k = floor(extent / cell) + 1, up to its roundings of a few 2^-52 S) and up_k = amax when n_k is at its cap.
+// (A) Roundings.  |h_k|, |o_k|, |lo_k| <= 2 S and |up_k| <= 4 S, so |h_k - x_k(t_f)| <= 2^-53 (|t_f d_k| + |h_k|) <= 2^-50 S.  A
+//     plane parameter t(X) = fl(fl(X - o_k) fl(1 / d_k)) has a relative error below 2^-51, that is |t(X) d_k - (X - o_k)| <= 2^-48 S,
+//     and a position fl(o_k + fl(t d_k)) the walk computes at a parameter inside the clipped range is within 2^-49 S of x_k(t).
+//     All of these together stay below E = 2^-40 S, which is why W - E = 3 E of room is left on every comparison below.
+// (B) Slab lemma (used three times).  If every hit point of f has h_k >= X - E (h_k <= X + E), then t_f is not on the far side
+//     of the COMPUTED parameter of the plane X - W (X + W): by (A) x_k(t_f) >= X - E - 2^-50 S, while the computed parameter
+//     stands for a plane no higher than X - W + 2^-47 S < X - E - 2^-50 S.  With d_k == 0, h_k = o_k exactly and the test is
+//     o_k < X - W.  So: (B1) clipping the ray to [lo - W, up + W] on every axis removes no hit (box clause: h is within E of f's
+//     box, which lies inside [lo, up]); a ray that misses those bounds hits nothing.  (B2) The cull of the default form -- the
+//     same slab test against f's own box widened by W, over [tmin, min(tmax, best)], f skipped only when the interval is empty
+//     STRICTLY (lo_t > hi_t) -- skips no face with t_f <= best.  The box is exact in fp32 (min / max of fp32 corners).
+// (C) The walk.  The cell of a coordinate is floor(g(x)) clamped to 0 .. n - 1, g(x) = fl(fl(x - lo) / cell), the same monotone
+//     function that lists the faces (grid_range); f is listed in every cell of its box's clamped range, hence in cell(h').
+//     The walk steps the cell layers i along a in the direction of d, from the layer of x_a(t0) - W to that of x_a(t1) + W
+//     ([t0, t1] the clipped range; signs for d_a > 0); monotone g and (A) put the layer i* of h'_a in between.  For a layer i it
+//     takes ts = the computed parameter of the layer's entry plane lo_a + i cell moved W outwards (t0 for the first layer, whose
+//     entry side may be the unbounded end layer) and te likewise for the exit plane (t1 for the last layer), te also cut to
+//     best.  floor(g(h'_a)) = i* bounds h'_a by the layer's planes up to 2^-49 S, so by (B) ts(i*) <= t_f <= te(i*) unless
+//     t_f > best.  In that layer it visits, on each other axis k, the cells from cell(min(p0, p1) - W) to cell(max(p0, p1) + W),
+//     p0, p1 the computed positions at ts, te: x_k is linear, so x_k(t_f) lies between x_k(ts) and x_k(te), h'_k within
+//     E + 2^-49 S + 2^-50 S < W of it, and monotone g puts cell(h'_k) inside the visited range.  So every face with
+//     t_f <= best that is listed in no visited cell of a visited layer does not exist: cell(h') is visited.
+//     The walk keeps the minimum over every face it evaluates, wherever the hit lies -- it never asks that the hit be in the
+//     current cell -- so evaluating a face early (it is listed in several cells) is harmless.
+// (D) Stopping.  ts(i) is monotone along the walk (each operation in it is monotone), and a face whose layer i* is still ahead
+//     has t_f >= ts(i*) >= ts(i).  The walk stops before layer i only when ts(i) > best STRICTLY: then every face still ahead
+//     has t_f > best and loses.  A face that TIES the best, t_f == best, sits in a layer with ts <= best and is still
+//     visited: it may carry a lower index.  `>=` would drop it.  The slack is in ts itself (the plane moved W outwards).
+//
+// ---- forms (SCULPT_DISTANCE_FORM, read by ops: the family of csrc/mesh_distance.hip) ---------------------------------------
+//   plain     one thread per ray in input order; a face is three index loads and three dependent position gathers; no cull.
+//   default   the rays sorted by the grid cell of their origin (sculpt_surface_cells + the caller's stable sort); faces come from
+//             the packed 64-byte records (sculpt_surface_pack), the first two 16-byte loads enough for the cull (B2).
+// Both evaluate the same rule on the same fp64 inputs: the same bits on every input (tests/test_gpu_mesh_ray.py).
+//
+// ---- occlusion ---------------------------------------------------------------------------------------------------------------
+// One thread per point (sorted by cell), a loop over the K directions shared by all points, so the 64 lanes of a wave cast nearly
+// the same ray at the same time.  fp32 without contraction: w_k = (n.x D.x + n.y D.y) + n.z D.z; the direction takes part iff
+// w_k > 0; origin = p + offset n per component (the product rounded, then the sum); the ray (origin, D_k) over [0, max_distance]
+// is occluded iff the rule above reports a face (the walk returns at the first face that hits: best stays +inf until then, so
+// nothing is cut short); open = sum of w_k of the rays that hit nothing, all = sum of every taking-part w_k, both in the order of
+// k in registers; ao = open / all, 1 when all == 0, NaN for a non-finite p or n.  A non-finite origin or direction hits nothing,
+// as in the closest-hit form.  No atomics, no ray is written to memory.
+#pragma clang fp contract(off)
+
+#include <limits.h>
+
+#include "remesh_topo.h"
+#include "surface_grid.h"
+
+namespace {
+
+constexpr double kBoxSlack = 0x1p-40;   // E = kBoxSlack * S
+constexpr double kDetRel = 0x1p-60;
+constexpr double kWalkSlack = 4.0;      // W = kWalkSlack * E
+constexpr int kMaxDirections = 1024;
+
+struct Ray {
+    D3 o, d;
+    double tmin, tmax, E;
+};
+
+struct Hit {
+    double t;
+    int f;
+    double u, v;
+};
+
+// the per-face rule of the header
+__device__ inline bool hit_face(const Ray &R, D3 a, D3 b, D3 c, double &t, double &u, double &v) {
+    const D3 e1 = b - a, e2 = c - a, pv = cross(R.d, e2);
+    const double det = dot(e1, pv);
+    if (!(det * det > kDetRel * (dot(e1, e1) * dot(pv, pv)))) return false;
+    const double inv = 1.0 / det;
+    const D3 tv = R.o - a;
+    u = dot(tv, pv) * inv;
+    if (!(u >= 0.0 && u <= 1.0)) return false;
+    const D3 qv = cross(tv, e1);
+    v = dot(R.d, qv) * inv;
+    if (!(v >= 0.0 && u + v <= 1.0)) return false;
+    t = dot(e2, qv) * inv;
+    if (!(t >= R.tmin && t <= R.tmax)) return false;
+    const D3 h = R.o + t * R.d;
+    const double E = R.E;
+    return h.x >= fmin(a.x, fmin(b.x, c.x)) - E && h.x <= fmax(a.x, fmax(b.x, c.x)) + E &&
+           h.y >= fmin(a.y, fmin(b.y, c.y)) - E && h.y <= fmax(a.y, fmax(b.y, c.y)) + E &&
+           h.z >= fmin(a.z, fmin(b.z, c.z)) - E && h.z <= fmax(a.z, fmax(b.z, c.z)) + E;
+}
+
+__device__ inline void consider(Hit &B, const Ray &R, D3 a, D3 b, D3 c, int f) {
+    double t, u, v;
+    if (!hit_face(R, a, b, c, t, u, v)) return;
+    if (t < B.t || (t == B.t && f < B.f)) {
+        B.t = t;
+        B.f = f;
+        B.u = u;
+        B.v = v;
+    }
+}
+
+// (B): the parameters at which axis k is inside [mn - W, mx + W], intersected into [lo_t, hi_t]; false: never inside
+__device__ inline bool slab(double o, double d, double inv, double mn, double mx, double W, double &lo_t, double &hi_t) {
+    if (d == 0.0) return !(o < mn - W || o > mx + W);
+    const double ta = ((mn - W) - o) * inv, tb = ((mx + W) - o) * inv;
+    lo_t = fmax(lo_t, fmin(ta, tb));
+    hi_t = fmin(hi_t, fmax(ta, tb));
+    return true;
+}
+
+__device__ inline double pick(double x, double y, double z, int k) { return k == 0 ? x : (k == 1 ? y : z); }
+
+// floor(q) clamped to 0 .. n - 1: grid_clamp's value, clamped before the conversion so that no q leaves the range of int
+__device__ inline int cell_of(double q, int n) { return (int)fmin(fmax(floor(q), 0.0), (double)(n - 1)); }
+
+// The walk of (C) / (D) for a finite ray with d != 0 over a surface with faces.  kAny: return at the first face that hits.
+template <bool kPacked, bool kAny>
+__device__ void cast(const Grid &G, const float4 *__restrict__ rec, D3 o, D3 d, double tmin, double tmax, double amax, Hit &B) {
+    const double S = fmax(amax, fmax(fabs(o.x), fmax(fabs(o.y), fabs(o.z))));
+    const double E = kBoxSlack * S, W = kWalkSlack * E;
+    const Ray R = {o, d, tmin, tmax, E};
+    const D3 inv = {d.x == 0.0 ? 0.0 : 1.0 / d.x, d.y == 0.0 ? 0.0 : 1.0 / d.y, d.z == 0.0 ? 0.0 : 1.0 / d.z};
+    const double ax = fabs(d.x), ay = fabs(d.y), az = fabs(d.z);
+    const int a = (ax >= ay && ax >= az) ? 0 : (ay >= az ? 1 : 2);
+    // axis 0 of the walk is the dominant one; 1 and 2 follow it cyclically
+    double po[3], pd[3], pi[3], plo[3];
+    int pn[3];
+    long ps[3];
+    const long stride[3] = {1, G.n[0], (long)G.n[0] * G.n[1]};
+    double t0 = tmin, t1 = tmax;
+    for (int j = 0; j < 3; ++j) {
+        const int k = (a + j) % 3;
+        po[j] = pick(o.x, o.y, o.z, k);
+        pd[j] = pick(d.x, d.y, d.z, k);
+        pi[j] = pick(inv.x, inv.y, inv.z, k);
+        plo[j] = pick(G.lo[0], G.lo[1], G.lo[2], k);
+        pn[j] = k == 0 ? G.n[0] : (k == 1 ? G.n[1] : G.n[2]);
+        ps[j] = k == 0 ? stride[0] : (k == 1 ? stride[1] : stride[2]);
+        const double up = pn[j] < 1024 ? plo[j] + pn[j] * G.cell : amax;
+        if (!slab(po[j], pd[j], pi[j], plo[j], up, W, t0, t1)) return;  // (B1)
+    }
+    if (t0 > t1) return;
+    const double sg = pd[0] > 0.0 ? 1.0 : -1.0;
+    const int step = pd[0] > 0.0 ? 1 : -1;
+    const int i0 = cell_of((((po[0] + t0 * pd[0]) - sg * W) - plo[0]) / G.cell, pn[0]);
+    const int i1 = cell_of((((po[0] + t1 * pd[0]) + sg * W) - plo[0]) / G.cell, pn[0]);
+    for (int i = i0; step > 0 ? i <= i1 : i >= i1; i += step) {
+        const double xin = plo[0] + (step > 0 ? i : i + 1) * G.cell, xout = plo[0] + (step > 0 ? i + 1 : i) * G.cell;
+        const double ts = i == i0 ? t0 : fmax(t0, ((xin - sg * W) - po[0]) * pi[0]);
+        if (ts > B.t) break;  // (D): strictly
+        const double te = fmin(i == i1 ? t1 : fmin(t1, ((xout + sg * W) - po[0]) * pi[0]), B.t);
+        if (ts > te) continue;
+        int lo[3], hi[3];
+        for (int j = 1; j < 3; ++j) {
+            const double p0 = po[j] + ts * pd[j], p1 = po[j] + te * pd[j];
+            lo[j] = cell_of(((fmin(p0, p1) - W) - plo[j]) / G.cell, pn[j]);
+            hi[j] = cell_of(((fmax(p0, p1) + W) - plo[j]) / G.cell, pn[j]);
+        }
+        for (int z = lo[2]; z <= hi[2]; ++z) {
+            for (int y = lo[1]; y <= hi[1]; ++y) {
+                const long ci = i * ps[0] + y * ps[1] + z * ps[2];
+                const int end = G.start[ci + 1];
+                for (int it = G.start[ci]; it < end; ++it) {
+                    const int f = G.items[it];
+                    if (kPacked) {
+                        const float4 r0 = rec[4 * (long)f], r1 = rec[4 * (long)f + 1];
+                        double lo_t = tmin, hi_t = fmin(tmax, B.t);  // (B2)
+                        if (!slab(o.x, d.x, inv.x, (double)r0.x, (double)r0.w, W, lo_t, hi_t)) continue;
+                        if (!slab(o.y, d.y, inv.y, (double)r0.y, (double)r1.x, W, lo_t, hi_t)) continue;
+                        if (!slab(o.z, d.z, inv.z, (double)r0.z, (double)r1.y, W, lo_t, hi_t)) continue;
+                        if (lo_t > hi_t) continue;
+                        const float4 r2 = rec[4 * (long)f + 2], r3 = rec[4 * (long)f + 3];
+                        consider(B, R, {(double)r1.z, (double)r1.w, (double)r2.x}, {(double)r2.y, (double)r2.z, (double)r2.w},
+                                 {(double)r3.x, (double)r3.y, (double)r3.z}, f);
+                    } else {
+                        consider(B, R, ld(G.P, G.F[3 * f]), ld(G.P, G.F[3 * f + 1]), ld(G.P, G.F[3 * f + 2]), f);
+                    }
+                    if (kAny && B.f != INT_MAX) return;
+                }
+            }
+        }
+    }
+}
+
+__device__ inline bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+template <bool kPacked>
+__global__ void __launch_bounds__(kThreads)
+ray_kernel(Grid G, const float *__restrict__ O, const float *__restrict__ Dr, long n, const int64_t *__restrict__ order,
+           const float4 *__restrict__ rec, double amax, double tmin, double tmax, double *__restrict__ to, int32_t *__restrict__ fo,
+           float *__restrict__ uvo) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long j = kPacked ? (long)order[i] : i;
+    const float ox = O[3 * j], oy = O[3 * j + 1], oz = O[3 * j + 2];
+    const float dx = Dr[3 * j], dy = Dr[3 * j + 1], dz = Dr[3 * j + 2];
+    Hit B = {INFINITY, INT_MAX, 0.0, 0.0};
+    const bool finite = finite3(ox, oy, oz) && finite3(dx, dy, dz);
+    if (finite && G.nf > 0 && !(dx == 0.0f && dy == 0.0f && dz == 0.0f))
+        cast<kPacked, false>(G, rec, {(double)ox, (double)oy, (double)oz}, {(double)dx, (double)dy, (double)dz}, tmin, tmax, amax, B);
+    const bool found = B.f != INT_MAX;
+    to[j] = finite ? B.t : (double)NAN;
+    fo[j] = found ? B.f : -1;
+    uvo[2 * j] = found ? (float)B.u : 0.0f;
+    uvo[2 * j + 1] = found ? (float)B.v : 0.0f;
+}
+
+__global__ void __launch_bounds__(kThreads)
+occlusion_kernel(Grid G, const float *__restrict__ P, const float *__restrict__ Nr, long n, const int64_t *__restrict__ order,
+                 const float *__restrict__ dirs, int K, float offset, float max_distance, const float4 *__restrict__ rec, double amax,
+                 float *__restrict__ ao) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long j = order ? (long)order[i] : i;
+    const float px = P[3 * j], py = P[3 * j + 1], pz = P[3 * j + 2];
+    const float nx = Nr[3 * j], ny = Nr[3 * j + 1], nz = Nr[3 * j + 2];
+    if (!(finite3(px, py, pz) && finite3(nx, ny, nz))) {
+        ao[j] = NAN;
+        return;
+    }
+    const float ox = px + offset * nx, oy = py + offset * ny, oz = pz + offset * nz;
+    const bool castable = finite3(ox, oy, oz) && G.nf > 0;
+    const D3 o = {(double)ox, (double)oy, (double)oz};
+    float open = 0.0f, all = 0.0f;
+    for (int k = 0; k < K; ++k) {
+        const float dx = dirs[3 * k], dy = dirs[3 * k + 1], dz = dirs[3 * k + 2];
+        const float w = (nx * dx + ny * dy) + nz * dz;
+        if (!(w > 0.0f)) continue;
+        all += w;
+        Hit B = {INFINITY, INT_MAX, 0.0, 0.0};
+        if (castable && finite3(dx, dy, dz))  // w > 0: the direction is not zero
+            cast<true, true>(G, rec, o, {(double)dx, (double)dy, (double)dz}, 0.0, (double)max_distance, amax, B);
+        if (B.f == INT_MAX) open += w;
+    }
+    ao[j] = all == 0.0f ? 1.0f : open / all;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sculpt_surface_ray_cast(const float *O, const float *D, int64_t n, const int64_t *order, const float *GP, const int32_t *GF,
+                            int64_t gnf, const float *records, const int32_t *items, const int32_t *start, const double *params_host,
+                            double amax, double tmin, double tmax, double *t, int32_t *face, float *uv, sculpt_stream_t stream) {
+    SC_REQUIRE(n >= 0 && 3 * n < ((int64_t)1 << 40), "surface_ray_cast: n=%lld out of range", (long long)n);
+    SC_REQUIRE(amax >= 0 && amax < INFINITY, "surface_ray_cast: amax=%g", amax);  // a NaN fails the comparison
+    SC_REQUIRE(tmin >= 0 && tmin <= tmax, "surface_ray_cast: the range must satisfy 0 <= tmin <= tmax, got [%g, %g]", tmin, tmax);
+    SC_REQUIRE((order == nullptr) == (records == nullptr), "surface_ray_cast: the sorted form takes both the order and the records");
+    if (n == 0) return 0;
+    if (int rc = check_grid("surface_ray_cast", GP, GF, gnf, params_host)) return rc;
+    SC_REQUIRE(O && D && t && face && uv, "surface_ray_cast: null array");
+    SC_REQUIRE(gnf == 0 || (items && start), "surface_ray_cast: null grid lists");
+    const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
+    if (order) {
+        SC_REQUIRE(aligned16(records), "surface_ray_cast: records not 16-byte aligned");
+        RMD_LAUNCH(ray_kernel<true>, n, G, O, D, (long)n, order, reinterpret_cast<const float4 *>(records), amax, tmin, tmax, t, face, uv);
+    } else {
+        RMD_LAUNCH(ray_kernel<false>, n, G, O, D, (long)n, nullptr, nullptr, amax, tmin, tmax, t, face, uv);
+    }
+    return 0;
+}
+
+int sculpt_surface_occlusion(const float *P, const float *N, int64_t n, const int64_t *order, const float *dirs, int k, float offset,
+                             float max_distance, const float *GP, const int32_t *GF, int64_t gnf, const float *records,
+                             const int32_t *items, const int32_t *start, const double *params_host, double amax, float *ao,
+                             sculpt_stream_t stream) {
+    SC_REQUIRE(n >= 0 && 3 * n < ((int64_t)1 << 40), "surface_occlusion: n=%lld out of range", (long long)n);
+    SC_REQUIRE(amax >= 0 && amax < INFINITY, "surface_occlusion: amax=%g", amax);  // a NaN fails the comparison
+    SC_REQUIRE(k >= 1 && k <= kMaxDirections, "surface_occlusion: %d directions (1 .. %d)", k, kMaxDirections);
+    SC_REQUIRE(max_distance >= 0, "surface_occlusion: max_distance=%g", (double)max_distance);
+    SC_REQUIRE(isfinite(offset), "surface_occlusion: offset=%g", (double)offset);
+    if (n == 0) return 0;
+    if (int rc = check_grid("surface_occlusion", GP, GF, gnf, params_host)) return rc;
+    SC_REQUIRE(P && N && dirs && ao, "surface_occlusion: null array");
+    SC_REQUIRE(gnf == 0 || (items && start && records), "surface_occlusion: null grid lists or records");
+    SC_REQUIRE(aligned16(records), "surface_occlusion: records not 16-byte aligned");
+    const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
+    RMD_LAUNCH(occlusion_kernel, n, G, P, N, (long)n, order, dirs, k, offset, max_distance, reinterpret_cast<const float4 *>(records), amax, ao);
+    return 0;
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
 // The uniform grid over a triangle surface and the closest point of one triangle, shared by the remesher's projection
-// (csrc/remesh_device.hip: grid_closest, relax_kernel) and the surface distance queries (csrc/mesh_distance.hip).  One copy;
+// (csrc/remesh_device.hip: grid_closest, relax_kernel), the surface distance queries (csrc/mesh_distance.hip) and the ray
+// queries (csrc/mesh_ray.hip, which uses the grid and its checks, not the closest point).  One copy;
 // every translation unit that includes it gets its own (anonymous namespace).  Include it after remesh_topo.h's D3 helpers and,
 // like that file, AFTER `#pragma clang fp contract(off)` in a unit that wants its arithmetic uncontracted: the two units compile
 // closest_on_triangle under different contraction settings on purpose (the remesher keeps the bits it always had, the distance
@@ -68,6 +69,18 @@ Grid grid_of(const float *GP, const int32_t *GF, long gnf, const int32_t *items,
     }
     G.cell = params ? params[3] : 1.0;
     return G;
+}
+
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// what the surface queries (csrc/mesh_distance.hip, csrc/mesh_ray.hip) ask of a grid before they launch
+inline int check_grid(const char *who, const float *GP, const int32_t *GF, int64_t gnf, const double *params) {
+    SC_REQUIRE(gnf >= 0 && 3 * gnf < ((int64_t)1 << 31), "%s: %lld faces do not fit int32 indices", who, (long long)gnf);
+    SC_REQUIRE(params, "%s: null grid params", who);
+    SC_REQUIRE(gnf == 0 || (GP && GF), "%s: null mesh", who);
+    for (int k = 0; k < 3; ++k) SC_REQUIRE(params[4 + k] >= 1 && params[4 + k] <= 1024, "%s: grid side %g (1 .. 1024)", who, params[4 + k]);
+    SC_REQUIRE(params[3] > 0 && params[3] < INFINITY, "%s: grid cell %g", who, params[3]);
+    return 0;
 }
 
 }  // namespace

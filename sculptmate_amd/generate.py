@@ -41,7 +41,10 @@ class TripoGenerator(GeneratorFacade):
     `project` (default None): True (8 Newton steps inside one lattice cell), an int n in 1 .. 64 or a tuple (n, cells) moves the
     vertices of every mesh onto the iso-surface of the density field itself and undoes folded faces, as the last geometry
     step -- after keep_components, smooth and simplify, before the colours, the bake and the normals (TSR.extract_meshes;
-    ops.mesh_project)."""
+    ops.mesh_project).
+    `occlusion` (default None): True (64 directions), an int k in 1 .. 1024 or a tuple (k, max_distance) leaves the ambient
+    occlusion of every final mesh against itself on the meshes in `last_meshes` (Mesh.vertex_occlusion, f32 [Nv], 1 = open:
+    TSR.extract_meshes; ops.mesh_occlusion); Mesh.export writes it into .ply and .glb.  The Blender sinks take none."""
 
     def __init__(self, device):
         super().__init__(device, checkpoint_dir=ROOT_DIR + "/checkpoints/", chunk_size=8192, mc_resolution=256,
@@ -53,6 +56,7 @@ class TripoGenerator(GeneratorFacade):
         self.simplify = None
         self.smooth = None
         self.project = None
+        self.occlusion = None
 
     def _construct_model(self):
         model = TSR.from_pretrained(self.checkpoint_dir, config_name="config.yaml", weight_name="model.ckpt",
@@ -71,7 +75,7 @@ class TripoGenerator(GeneratorFacade):
                                                        bake_texture=int(self.bake_texture_resolution or 0),
                                                        normals=self.vertex_normals,
                                                        keep_components=self.keep_components, simplify=self.simplify,
-                                                       smooth=self.smooth, project=self.project)
+                                                       smooth=self.smooth, project=self.project, occlusion=self.occlusion)
         except Exception as err:
             print(self.run_error_tag, err)
             return STATUS_FAILED

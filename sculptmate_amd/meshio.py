@@ -8,6 +8,13 @@ users export them through trimesh, which is not a dependency here.
 import numpy as np
 
 
+def _occlusion_for(occlusion, nv, who):
+    ao = np.asarray(occlusion, np.float32)
+    if ao.shape != (nv,):
+        raise ValueError("%s: occlusion %s must be [Nv] = [%d]" % (who, ao.shape, nv))
+    return ao
+
+
 def _normals_for(normals, nv, who):
     n = np.asarray(normals, np.float32)
     if n.shape != (nv, 3):
@@ -19,15 +26,17 @@ class MeshArrays(tuple):
     """What read_obj / read_ply return: the tuple (vertices, faces, colours | None) they always returned, with the normals
     of the file (f32 [Nv, 3], or None) beside it as `.normals`."""
 
-    def __new__(cls, vertices, faces, colors, normals=None):
+    def __new__(cls, vertices, faces, colors, normals=None, occlusion=None):
         self = tuple.__new__(cls, (vertices, faces, colors))
         self.normals = normals
+        self.occlusion = occlusion   # read_ply: the float property `ao`, f32 [Nv] | None
         return self
 
 
 def write_obj(path, vertices, faces, vertex_colors=None, normals=None):
     """`v x y z [r g b]` / `f a b c` (1-based), one numpy formatting pass per block.  normals f32 [Nv, 3] (one per vertex):
-    `vn x y z` lines after the vertices and `f a//a b//b c//c` faces."""
+    `vn x y z` lines after the vertices and `f a//a b//b c//c` faces.  OBJ has no slot for a per-vertex scalar: a mesh's
+    vertex_occlusion is not written (write_ply and write_glb take it)."""
     v = np.asarray(vertices, np.float64)
     f = np.asarray(faces, np.int64) + 1
     if vertex_colors is not None:
@@ -158,11 +167,13 @@ def decode_png(data):
 
 
 def write_glb(path, vertices, faces, vertex_colors=None, normals=None, uvs=None, basecolor_tex=None,
-              normal_tex=None, roughness=None, metallic=None, name="mesh", uv_origin="bottom_left"):
+              normal_tex=None, roughness=None, metallic=None, name="mesh", uv_origin="bottom_left", occlusion=None):
     """Write one triangle mesh as binary glTF.  `uvs` as SF3D.run_image returns them have their origin at the BOTTOM-left
     of the top-down texture image (the baker samples row y at v = 1 - y/R, texture_baker/common.py:104-142, and the
     reference hands them to Blender unchanged, sf3d/system.py:539-545); glTF puts the origin at the top-left, so
-    TEXCOORD_0 is written as (u, 1 - v) unless uv_origin="top_left".  roughness / metallic are SF3D's scalar factors."""
+    TEXCOORD_0 is written as (u, 1 - v) unless uv_origin="top_left".  roughness / metallic are SF3D's scalar factors.
+    occlusion: f32 [Nv] per vertex (Mesh.vertex_occlusion) -> the custom attribute _OCCLUSION, a float scalar; None (default):
+    the file is what it was without the keyword, byte for byte."""
     if uv_origin not in ("bottom_left", "top_left"):
         raise ValueError("uv_origin must be 'bottom_left' or 'top_left'")
     v = np.ascontiguousarray(vertices, np.float32)
@@ -200,6 +211,9 @@ def write_glb(path, vertices, faces, vertex_colors=None, normals=None, uvs=None,
     if vertex_colors is not None:
         col = np.ascontiguousarray(vertex_colors, np.float32)
         attributes["COLOR_0"] = add_accessor(col, "VEC3" if col.shape[1] == 3 else "VEC4", _FLOAT, _ARRAY_BUFFER)
+    if occlusion is not None:
+        attributes["_OCCLUSION"] = add_accessor(np.ascontiguousarray(_occlusion_for(occlusion, len(v), "write_glb")), "SCALAR", _FLOAT,
+                                                _ARRAY_BUFFER)
     indices = add_accessor(idx.astype(np.uint32).reshape(-1), "SCALAR", _UINT32, _ELEMENT_ARRAY_BUFFER)
 
     pbr = {}
@@ -241,7 +255,7 @@ def write_glb(path, vertices, faces, vertex_colors=None, normals=None, uvs=None,
 
 
 def read_glb(path, uv_origin="bottom_left"):
-    """Read back what write_glb wrote -> dict(vertices, faces, normals, uvs, vertex_colors, basecolor_tex, normal_tex,
+    """Read back what write_glb wrote -> dict(vertices, faces, normals, uvs, vertex_colors, occlusion, basecolor_tex, normal_tex,
     roughness, metallic); uvs are returned in `uv_origin` convention (see write_glb).  Not a general glTF loader: one
     buffer, one primitive, tightly packed accessors."""
     with open(path, "rb") as fh:
@@ -285,13 +299,14 @@ def read_glb(path, uv_origin="bottom_left"):
         "normals": accessor(att["NORMAL"]) if "NORMAL" in att else None,
         "uvs": st,
         "vertex_colors": accessor(att["COLOR_0"]) if "COLOR_0" in att else None,
+        "occlusion": accessor(att["_OCCLUSION"]).reshape(-1) if "_OCCLUSION" in att else None,
         "basecolor_tex": texture(pbr.get("baseColorTexture")),
         "normal_tex": texture(mat.get("normalTexture")),
         "roughness": pbr["roughnessFactor"], "metallic": pbr["metallicFactor"],
     }
 
 
-def _ply_layout(vertices, faces, vertex_colors, normals=None):
+def _ply_layout(vertices, faces, vertex_colors, normals=None, occlusion=None):
     """(header bytes, vertex block as a C-contiguous array whose bytes ARE the block, int faces [Nf,3]) of write_ply's file."""
     v = np.ascontiguousarray(vertices, np.float32)
     f = np.asarray(faces)
@@ -302,6 +317,9 @@ def _ply_layout(vertices, faces, vertex_colors, normals=None):
     if normals is not None:
         head += ["property float nx", "property float ny", "property float nz"]
         v = np.ascontiguousarray(np.concatenate([v, _normals_for(normals, len(v), "write_ply")], 1))   # [Nv,6]: xyz, nx ny nz
+    if occlusion is not None:
+        head += ["property float ao"]
+        v = np.ascontiguousarray(np.concatenate([v, _occlusion_for(occlusion, len(v), "write_ply")[:, None]], 1))   # ..., ao
     if vertex_colors is not None:
         head += ["property uchar red", "property uchar green", "property uchar blue"]
         c8 = np.round(np.clip(np.asarray(vertex_colors, np.float64), 0, 1) * 255).astype(np.uint8)
@@ -345,15 +363,16 @@ def _ply_face_records(f):
 PLY_CHUNK_FACES = 1 << 18   # faces converted + written per task (3.4 MB of records)
 
 
-def write_ply(path, vertices, faces, vertex_colors=None, pool=None, normals=None):
-    """Binary little-endian PLY: float32 xyz, optional float32 nx ny nz (normals f32 [Nv, 3]), optional uchar rgb, faces as
+def write_ply(path, vertices, faces, vertex_colors=None, pool=None, normals=None, occlusion=None):
+    """Binary little-endian PLY: float32 xyz, optional float32 nx ny nz (normals f32 [Nv, 3]), optional float32 ao (occlusion
+    f32 [Nv], Mesh.vertex_occlusion; None: the file is what it was without the keyword), optional uchar rgb, faces as
     `uchar 3` + int32 triplets.
     The file is laid out up front (header, vertex block, 13-byte face records) and written with positioned writes, the face
     records converted chunk by chunk; with `pool` (a concurrent.futures executor) the chunks are converted and written in
     parallel -- NumPy copies and os.pwrite release the GIL -- and the same bytes land in the file either way."""
     import os
 
-    head, vblock, f = _ply_layout(vertices, faces, vertex_colors, normals)
+    head, vblock, f = _ply_layout(vertices, faces, vertex_colors, normals, occlusion)
     v_off = len(head)
     f_off = v_off + vblock.nbytes
     fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
@@ -395,7 +414,7 @@ def write_npz(path, vertices, faces, vertex_colors=None):
 
 def read_ply(path):
     """Read back what write_ply wrote -> MeshArrays (vertices f32, faces i64, colours f32 in [0,1] | None), `.normals` f32
-    [Nv, 3] | None."""
+    [Nv, 3] | None, `.occlusion` f32 [Nv] | None."""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -404,15 +423,16 @@ def read_ply(path):
     nf = int([h for h in head if h.startswith("element face")][0].split()[-1])
     coloured = any(h == "property uchar red" for h in head)
     with_normals = any(h == "property float nx" for h in head)
+    with_ao = any(h == "property float ao" for h in head)
     fields = ([("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")] if with_normals else [])
-              + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if coloured else []))
+              + ([("ao", "<f4")] if with_ao else []) + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if coloured else []))
     vdt = np.dtype(fields)
     vrec = np.frombuffer(data, vdt, nv, end)
     frec = np.frombuffer(data, np.dtype([("n", "u1"), ("i", "<i4", (3,))]), nf, end + nv * vdt.itemsize)
     v = np.stack([vrec["x"], vrec["y"], vrec["z"]], 1)
     c = np.stack([vrec["red"], vrec["green"], vrec["blue"]], 1).astype(np.float32) / 255.0 if coloured else None
     n = np.stack([vrec["nx"], vrec["ny"], vrec["nz"]], 1) if with_normals else None
-    return MeshArrays(v, frec["i"].astype(np.int64), c, n)
+    return MeshArrays(v, frec["i"].astype(np.int64), c, n, np.array(vrec["ao"]) if with_ao else None)
 
 
 def write_sf3d_glb(path, mesh, name="mesh"):

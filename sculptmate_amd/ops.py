@@ -736,7 +736,8 @@ def _surface(vertices, faces, who):
 
 
 class _SurfaceIndex:
-    """The remesher's uniform grid over a surface, and the packed face records of the sorted query form (built on first use)."""
+    """The remesher's uniform grid over a surface, and the packed face records of the sorted query form (built on first use):
+    one index serves the closest-point, ray and occlusion queries of a call."""
 
     def __init__(self, P, F):
         from .sf3d import remesh_device as rmd
@@ -758,17 +759,57 @@ class _SurfaceIndex:
         d2 = torch.empty(n, dtype=torch.float64, device=dev)
         face = torch.empty(n, dtype=torch.int32, device=dev)
         closest = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        order = records = None
-        if not _lib.form_has("SCULPT_DISTANCE_FORM", "plain") and nf:
-            key = torch.empty(n, dtype=torch.int32, device=dev)
-            check(lib.sculpt_surface_cells(_ptr(points), n, g.params, _ptr(key), _stream()))
-            order = torch.sort(key, stable=True).indices   # stable: one permutation, though any would give the same results
-            records = self.records()
+        order, records = self._sorted(points)
         check(lib.sculpt_surface_closest(_ptr(points), n, _ptr(order) if order is not None else None, _ptr(self.P) if nf else None,
                                          _ptr(self.F) if nf else None, nf, _ptr(records) if records is not None else None,
                                          _ptr(g.items) if nf else None, _ptr(g.start) if nf else None, g.params, float(g.amax),
                                          _ptr(d2), _ptr(face), _ptr(closest), _stream()))
         return d2, face, closest
+
+    def _sorted(self, points, always=False):
+        """(order, records) of the sorted query form for points f32 [N, 3], or (None, None) for the plain form (unless `always`)
+        and for a surface without faces."""
+        if (_lib.form_has("SCULPT_DISTANCE_FORM", "plain") and not always) or not self.F.shape[0]:
+            return None, None
+        n = points.shape[0]
+        key = torch.empty(n, dtype=torch.int32, device=points.device)
+        check(lib.sculpt_surface_cells(_ptr(points), n, self.grid.params, _ptr(key), _stream()))
+        # stable: one permutation, though any would give the same results
+        return torch.sort(key, stable=True).indices, self.records()
+
+    def _grid_args(self):
+        g, nf = self.grid, self.F.shape[0]
+        return (_ptr(self.P) if nf else None, _ptr(self.F) if nf else None, nf), (_ptr(g.items) if nf else None,
+                                                                                   _ptr(g.start) if nf else None, g.params, float(g.amax))
+
+    def ray_cast(self, origins, directions, t_min=0.0, t_max=math.inf):
+        """origins, directions f32 [N, 3] contiguous, N > 0 -> (t f64 [N], face int32 [N], uv f32 [N, 2])."""
+        dev, n = origins.device, origins.shape[0]
+        t = torch.empty(n, dtype=torch.float64, device=dev)
+        face = torch.empty(n, dtype=torch.int32, device=dev)
+        uv = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        order, records = self._sorted(origins)   # by the cell of the origin
+        mesh, grid = self._grid_args()
+        check(lib.sculpt_surface_ray_cast(_ptr(origins), _ptr(directions), n, _ptr(order) if order is not None else None, *mesh,
+                                          _ptr(records) if records is not None else None, *grid, float(t_min), float(t_max),
+                                          _ptr(t), _ptr(face), _ptr(uv), _stream()))
+        return t, face, uv
+
+    def longest_side(self):
+        """The longest side of the surface's bounds (0 without faces): the grid has read them back."""
+        return float(self.grid.longest)
+
+    def occlusion(self, points, normals, dirs, offset, max_distance):
+        """points, normals f32 [N, 3], dirs f32 [K, 3], all contiguous on the device, N > 0 -> ao f32 [N] in ONE launch; the
+        points are sorted by cell whatever SCULPT_DISTANCE_FORM says (the fused kernel has one form)."""
+        n = points.shape[0]
+        ao = torch.empty(n, dtype=torch.float32, device=points.device)
+        order, records = self._sorted(points, always=True)
+        mesh, grid = self._grid_args()
+        check(lib.sculpt_surface_occlusion(_ptr(points), _ptr(normals), n, _ptr(order) if order is not None else None, _ptr(dirs),
+                                           dirs.shape[0], float(offset), float(max_distance), *mesh,
+                                           _ptr(records) if records is not None else None, *grid, _ptr(ao), _stream()))
+        return ao
 
 
 def _query_points(points, who):
@@ -899,6 +940,157 @@ def mesh_distance(vertices_a, faces_a, vertices_b, faces_b, samples=DISTANCE_SAM
         p, q = r[3] / ab.shape[0], r[7] / ba.shape[0]
         out.update(precision=p, recall=q, fscore=2.0 * p * q / (p + q) if p + q > 0 else 0.0)
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# rays against a surface: closest hit, ambient occlusion (csrc/mesh_ray.hip)
+# ----------------------------------------------------------------------------------------------
+OCCLUSION_DIRECTIONS = 64          # what occlusion=True means
+OCCLUSION_MAX_DIRECTIONS = 1024
+OCCLUSION_OFFSET = 2.0 ** -13      # the default origin offset along the normal, in longest sides of the surface's bounds
+GOLDEN_ANGLE = math.pi * (3.0 - math.sqrt(5.0))
+
+
+def _ray_range(t_min, t_max):
+    if _is_real(t_min) and _is_real(t_max) and 0.0 <= float(t_min) <= float(t_max):   # a NaN fails the comparison
+        return float(t_min), float(t_max)
+    raise ValueError("the ray range must satisfy 0 <= t_min <= t_max (t_max may be inf), got t_min=%r, t_max=%r" % (t_min, t_max))
+
+
+def _rays(origins, directions, who):
+    o, d = _query_points(origins, who), _query_points(directions, who)
+    if o.shape != d.shape:
+        raise SculptError("%s: origins %s and directions %s differ in shape" % (who, tuple(o.shape), tuple(d.shape)))
+    return o, d
+
+
+def mesh_ray_cast(origins, directions, vertices, faces, t_min=0.0, t_max=math.inf):
+    """The closest face of a triangle mesh that each of N rays hits, on the device.  origins, directions float [N, 3], vertices
+    float [Nv, 3], faces int32 / int64 [Nf, 3] (device tensors; CPU tensors are refused); 0 <= t_min <= t_max, t_max may be inf
+    (anything else is a ValueError before any launch).  The direction need not be a unit vector: t is in units of it.
+    -> (t f64 [N], face i64 [N] the face hit, uv f32 [N, 2] its (u, v): the hit is (1 - u - v) a + u b + v c).
+    Contract (csrc/mesh_ray.hip; tests/_rayref.py restates it by brute force, bit for bit):
+      - positions are fp32 (other float dtypes are converted first), the arithmetic is fp64 without contraction;
+      - per face: Moeller-Trumbore, two-sided, with a relative determinant test (a ray in the plane of a face misses it) and
+        the box clause (the computed hit point lies within 2^-40 of the coordinates' magnitude of the face's bounding box);
+        the answer is the lexicographic minimum of (t_f, f) over ALL faces that hit -- of several faces at the same t the
+        lowest index wins;
+      - no hit, or a zero direction: t = +inf, face = -1, uv = 0; a non-finite origin or direction: t = NaN, face = -1, uv = 0;
+      - watertightness along shared edges is NOT promised: the barycentric tests are rounded per face, so a ray through an
+        edge or a vertex may pass between the faces that meet there;
+      - a face index out of range and a non-finite vertex are a SculptError; N == 0 launches nothing;
+      - the uniform grid only accelerates; SCULPT_DISTANCE_FORM=plain selects the one-thread-per-ray-in-input-order form, the
+        default sorts the rays by the grid cell of their origin and culls faces by their boxes: the same bits on every input;
+      - the host reads back the input check's status and the grid's two small results (bounds, list length)."""
+    t_min, t_max = _ray_range(t_min, t_max)
+    o, d = _rays(origins, directions, "mesh_ray_cast")
+    P, F = _surface(vertices, faces, "mesh_ray_cast")
+    return _ray_cast(_SurfaceIndex(P, F) if o.shape[0] else None, o, d, t_min, t_max)
+
+
+def _ray_cast(index, o, d, t_min, t_max):
+    if o.shape[0] == 0:
+        dev = o.device
+        return (torch.empty(0, dtype=torch.float64, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                torch.empty((0, 2), dtype=torch.float32, device=dev))
+    t, face, uv = index.ray_cast(o, d, t_min, t_max)
+    return t, face.long(), uv
+
+
+def occlusion_directions(k, seed=0):
+    """The k directions of the ambient occlusion: the golden-angle spiral on the unit sphere, z_i = 1 - (2 i + 1) / k,
+    phi_i = i x the golden angle + seed radians (`seed`, an int in 0 .. 2^31 - 1, rotates the set about z), computed on the host
+    in NumPy fp64 and rounded once -> np.float32 [k, 3].  k in 1 .. 1024.  Deterministic; needs no device."""
+    if not (_is_count(k, 1, OCCLUSION_MAX_DIRECTIONS) and _is_count(seed, 0, 2 ** 31 - 1)):
+        raise ValueError("k must be an int in 1 .. %d and seed an int in 0 .. 2^31 - 1, got k=%r, seed=%r"
+                         % (OCCLUSION_MAX_DIRECTIONS, k, seed))
+    i = np.arange(int(k), dtype=np.float64)
+    z = 1.0 - (2.0 * i + 1.0) / float(int(k))
+    r = np.sqrt(1.0 - z * z)
+    phi = i * GOLDEN_ANGLE + float(int(seed))
+    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], 1)
+    return (d / np.sqrt((d * d).sum(1, keepdims=True))).astype(np.float32)
+
+
+def occlusion_rule(occlusion):
+    """`occlusion` of the ambient occlusion -> (k, max_distance): True (64 directions, rays of any length), an int k in
+    1 .. 1024 or a tuple (k, max_distance) with max_distance > 0 (inf allowed) or None (any length) -- so a rule's own result is
+    a rule.  Anything else -- False, None, a str, a bare float, NaN, another length -- is a ValueError, raised here, before
+    anything is launched."""
+    if occlusion is True or (isinstance(occlusion, np.bool_) and bool(occlusion)):
+        return OCCLUSION_DIRECTIONS, None
+    if _is_count(occlusion, 1, OCCLUSION_MAX_DIRECTIONS):
+        return int(occlusion), None
+    if isinstance(occlusion, tuple) and len(occlusion) == 2 and _is_count(occlusion[0], 1, OCCLUSION_MAX_DIRECTIONS):
+        far = occlusion[1]
+        if far is None:
+            return int(occlusion[0]), None
+        if _is_real(far) and float(far) > 0.0:   # a NaN fails the comparison
+            return int(occlusion[0]), float(far)
+    raise ValueError("occlusion must be True, an int in 1 .. %d (directions) or (directions, max_distance) with max_distance > 0, "
+                     "got %r" % (OCCLUSION_MAX_DIRECTIONS, occlusion))
+
+
+def _occlusion_args(points, normals, vertices, faces, occlusion, offset, seed, who):
+    k, far = occlusion_rule(occlusion)
+    if offset is not None and not (_is_real(offset) and math.isfinite(float(np.float32(offset)))):
+        raise ValueError("offset must be None or a finite number, got %r" % (offset,))
+    dirs = occlusion_directions(k, seed)      # checks the seed
+    pts, nrm = _query_points(points, who), _query_points(normals, who)
+    if pts.shape != nrm.shape:
+        raise SculptError("%s: points %s and normals %s differ in shape" % (who, tuple(pts.shape), tuple(nrm.shape)))
+    P, F = _surface(vertices, faces, who)
+    if pts.shape[0] == 0:
+        return None, pts, nrm, None, 0.0, math.inf
+    index = _SurfaceIndex(P, F)
+    if offset is None:
+        offset = OCCLUSION_OFFSET * index.longest_side()
+    far = math.inf if far is None else float(np.float32(far))
+    return index, pts, nrm, torch.from_numpy(dirs).to(pts.device), float(np.float32(offset)), far
+
+
+def mesh_occlusion(points, normals, vertices, faces, occlusion=True, offset=None, seed=0):
+    """The ambient occlusion of N points with normals against a triangle mesh, on the device, in ONE launch
+    (sculpt_surface_occlusion): the cosine-weighted share of the directions above a point's tangent plane along which a ray
+    leaves without hitting the mesh.  points, normals float [N, 3], vertices float [Nv, 3], faces int32 / int64 [Nf, 3] (device
+    tensors); occlusion: True, k or (k, max_distance) (occlusion_rule); offset: how far along the normal the rays start (None:
+    2^-13 of the longest side of the surface's bounds), rounded to fp32; seed rotates the direction set (occlusion_directions).
+    -> ao f32 [N] in [0, 1]: 1 sees everything, 0 is fully occluded.  In fp32 without contraction, with D the directions:
+    w_k = (n.x D_k.x + n.y D_k.y) + n.z D_k.z; direction k takes part iff w_k > 0; its ray runs from p + offset n over
+    [0, max_distance] and is occluded iff mesh_ray_cast would report a face; ao = (sum of w_k of the free rays) / (sum of all
+    taking-part w_k), both in the order of k; 1 when no direction takes part (a zero normal); NaN for a non-finite p or n.  The
+    normals are used as given (not normalised: ao is a ratio).  Bit for bit what mesh_occlusion_composed computes with one
+    mesh_ray_cast per direction (tests/test_gpu_mesh_ray.py).  N == 0 launches nothing."""
+    index, pts, nrm, dirs, offset, far = _occlusion_args(points, normals, vertices, faces, occlusion, offset, seed, "mesh_occlusion")
+    if index is None:
+        return torch.empty(0, dtype=torch.float32, device=pts.device)
+    return index.occlusion(pts, nrm, dirs, offset, far)
+
+
+def mesh_occlusion_composed(points, normals, vertices, faces, occlusion=True, offset=None, seed=0):
+    """mesh_occlusion by the composed route: one closest-hit query of every point per direction (mesh_ray_cast's kernels on one
+    shared grid) and torch reductions in the kernel's order.  The yardstick the fused kernel is tested (same bits) and timed
+    against (tools/time_occlusion.py); K launches and K sorts instead of one."""
+    index, pts, nrm, dirs, offset, far = _occlusion_args(points, normals, vertices, faces, occlusion, offset, seed,
+                                                         "mesh_occlusion_composed")
+    if index is None:
+        return torch.empty(0, dtype=torch.float32, device=pts.device)
+    return _occlusion_composed(index, pts, nrm, dirs, offset, far)
+
+
+def _occlusion_composed(index, pts, nrm, dirs, offset, far):
+    origin = pts + nrm * offset                # fp32: the product rounded, then the sum
+    open_, all_ = torch.zeros_like(pts[:, 0]), torch.zeros_like(pts[:, 0])
+    for k in range(dirs.shape[0]):
+        d = dirs[k]
+        w = (nrm[:, 0] * d[0] + nrm[:, 1] * d[1]) + nrm[:, 2] * d[2]
+        part = w > 0
+        face = index.ray_cast(origin, d.expand(pts.shape[0], 3).contiguous(), 0.0, far)[1]
+        all_ = torch.where(part, all_ + w, all_)
+        open_ = torch.where(part & (face < 0), open_ + w, open_)
+    ao = torch.where(all_ == 0, torch.ones_like(all_), open_ / all_)
+    bad = ~(torch.isfinite(pts).all(1) & torch.isfinite(nrm).all(1))
+    return torch.where(bad, torch.full_like(ao, math.nan), ao)
 
 
 # ----------------------------------------------------------------------------------------------

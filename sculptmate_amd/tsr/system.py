@@ -37,23 +37,26 @@ from .spec import DEFAULT_CFG, IMAGE_MEAN, IMAGE_STD, param_spec  # noqa: E402,F
 class Mesh:
     """What run() returns per image: trimesh-constructible arrays."""
 
-    def __init__(self, vertices, faces, vertex_colors=None, uvs=None, texture=None, vertex_normals=None):
+    def __init__(self, vertices, faces, vertex_colors=None, uvs=None, texture=None, vertex_normals=None, vertex_occlusion=None):
         """uvs / texture: what TSR.bake_texture adds -- uvs f32 [3*Nf, 2] per face corner (origin bottom-left, the convention of
         sf3d and meshio.write_glb), texture f32 [res, res, 3] in [0, 1] with row 0 at the top.
-        vertex_normals: f32 [Nv, 3] unit normals per shared vertex (extract_meshes(normals=...)), also on a baked mesh."""
+        vertex_normals: f32 [Nv, 3] unit normals per shared vertex (extract_meshes(normals=...)), also on a baked mesh.
+        vertex_occlusion: f32 [Nv] ambient occlusion per shared vertex, 1 = open, 0 = occluded (extract_meshes(occlusion=...),
+        Mesh.ambient_occlusion), also on a baked mesh."""
         self.vertices = vertices
         self.faces = faces
         self.vertex_colors = vertex_colors
         self.uvs = uvs
         self.texture = texture
         self.vertex_normals = vertex_normals
+        self.vertex_occlusion = vertex_occlusion
 
     def keep_components(self, keep) -> "Mesh":
         """The mesh without its small connected components (the "floaters" a thresholded density field leaves around the
         object): keep = "largest", an int >= 1 (components of at least that many faces) or a float in (0, 1) (at least that
         fraction of the largest component's faces) -- ops.mesh_keep_components on this mesh's device tensors (a mesh of host
-        arrays, as TSR.run returns them, is refused there like any CPU tensor).  Rows keep their order; vertex_colors and
-        vertex_normals follow their vertices (vertex_index), the per-corner uvs of a baked mesh their faces (face_index, three
+        arrays, as TSR.run returns them, is refused there like any CPU tensor).  Rows keep their order; vertex_colors,
+        vertex_normals and vertex_occlusion follow their vertices (vertex_index), the per-corner uvs of a baked mesh their faces (face_index, three
         rows per face); the texture is untouched (the dropped charts stay in it, unused)."""
         v, f, vi, fi = ops.mesh_keep_components(self.vertices, self.faces, keep)
 
@@ -65,14 +68,15 @@ class Mesh:
             three = torch.arange(3, device=fi.device) if isinstance(fi, torch.Tensor) else np.arange(3)
             corner = (fi[:, None] * 3 + three).reshape(-1)
         return Mesh(v, f, rows(self.vertex_colors, vi), uvs=rows(self.uvs, corner), texture=self.texture,
-                    vertex_normals=rows(self.vertex_normals, vi))
+                    vertex_normals=rows(self.vertex_normals, vi), vertex_occlusion=rows(self.vertex_occlusion, vi))
 
     def simplify(self, simplify) -> "Mesh":
         """The mesh reduced to a target face count by quadric-error edge collapses on the device (ops.mesh_simplify): simplify =
         an int >= 1 (target faces) or a float in (0, 1) (ratio of the faces).  vertex_colors and vertex_normals follow
         vertex_index -- the values of the input vertex each output vertex descends from.  That is an approximation: the vertex
         has moved to its collapses' target point; TSR.extract_meshes(simplify=...) evaluates colours and normals at the final
-        vertices instead.  A baked mesh (uvs / texture) is refused: its atlas belongs to the faces it was baked for, so simplify
+        vertices instead.  vertex_occlusion is dropped: it is stale once the vertices have moved.  A baked mesh (uvs / texture)
+        is refused: its atlas belongs to the faces it was baked for, so simplify
         before baking."""
         ops.simplify_rule(simplify)
         if self.uvs is not None or self.texture is not None:
@@ -86,8 +90,8 @@ class Mesh:
         """The mesh after Taubin's lambda|mu smoothing on the device (ops.mesh_smooth): smooth = an int n, 1 <= n <= 1000
         (n iterations with lam = 0.5, mu = -0.53) or a tuple (n, lam, mu) (ops.smooth_rule).  The faces are the same tensor and
         the vertices keep their indices, so vertex_colors, uvs and texture are carried over as they are: the topology is
-        unchanged and a baked atlas stays valid.  vertex_normals is dropped: the vertices have moved and the normals would be
-        stale (TSR.field_normals / ops.vertex_normals at the new vertices give fresh ones).  TSR.extract_meshes(smooth=...)
+        unchanged and a baked atlas stays valid.  vertex_normals and vertex_occlusion are dropped: the vertices have moved and
+        they would be stale (TSR.field_normals / ops.vertex_normals at the new vertices give fresh ones).  TSR.extract_meshes(smooth=...)
         smooths before it simplifies; this method lets a caller choose another order."""
         v = ops.mesh_smooth(self.vertices, self.faces, smooth)
         return Mesh(v, self.faces, self.vertex_colors, uvs=self.uvs, texture=self.texture)
@@ -103,6 +107,25 @@ class Mesh:
         and F-score.  samples=None measures from the meshes' own vertices: what an option such as smooth or simplify did to the
         surface, without sampling noise."""
         return ops.mesh_distance(self.vertices, self.faces, other.vertices, other.faces, samples=samples, seed=seed, threshold=threshold)
+
+    def ray_cast(self, origins, directions, t_min=0.0, t_max=math.inf):
+        """The closest face of this mesh that each ray hits (ops.mesh_ray_cast on its device tensors; host arrays are refused
+        like any CPU tensor) -> (t f64 [N], face i64 [N], uv f32 [N, 2]); no hit: t = +inf, face = -1."""
+        return ops.mesh_ray_cast(origins, directions, self.vertices, self.faces, t_min, t_max)
+
+    def ambient_occlusion(self, occlusion=True, seed=0, outward=1.0):
+        """Ambient occlusion per vertex -> f32 [Nv], 1 = open, 0 = occluded (ops.mesh_occlusion on this mesh's device tensors;
+        host arrays are refused): the points are the vertices, the normals outward * ops.vertex_normals(vertices, faces) --
+        always the facet-average normals of THIS mesh, whether or not vertex_normals is set.  occlusion: True (64 directions),
+        k or (k, max_distance) (ops.occlusion_rule); seed rotates the direction set; outward: +1 when the faces wind
+        counter-clockwise seen from outside, -1 otherwise (TSR.WINDING_OUTWARD for the meshes of TSR.extract_meshes).  The
+        result is not stored: assign it to vertex_occlusion to carry and export it."""
+        ops.occlusion_rule(occlusion)
+        if not (ops._is_real(outward) and math.isfinite(float(outward))):
+            raise ValueError("outward must be a finite number (+1 or -1), got %r" % (outward,))
+        ops._device_mesh(self.vertices, self.faces, "Mesh.ambient_occlusion")
+        normals = float(outward) * ops.vertex_normals(self.vertices, self.faces)
+        return ops.mesh_occlusion(self.vertices, normals, self.vertices, self.faces, occlusion, seed=seed)
 
     def to_trimesh(self):  # pragma: no cover (trimesh is optional)
         import trimesh
@@ -124,7 +147,9 @@ class Mesh:
         trimesh object their extract_mesh returns.  A baked mesh (uvs + texture) goes out textured: .glb with TEXCOORD_0 and the
         base-colour texture (glTF has one index per vertex, so positions are un-indexed to 3*Nf vertices there and only there),
         .obj with `vt` lines, `f v/vt` faces and a .mtl + .png beside the file (positions stay shared).  vertex_normals, when the
-        mesh has them, go into every format (glTF NORMAL, `vn`, nx ny nz); the un-indexed .glb gets normals[faces] per corner."""
+        mesh has them, go into every format (glTF NORMAL, `vn`, nx ny nz); the un-indexed .glb gets normals[faces] per corner.
+        vertex_occlusion, when set, goes into .ply (a float property `ao`) and .glb (the custom attribute _OCCLUSION; the
+        un-indexed .glb gets ao[faces] per corner); .obj has no slot for it."""
         from .. import meshio
 
         ext = str(path).rsplit(".", 1)[-1].lower()
@@ -136,12 +161,14 @@ class Mesh:
             picture = np.asarray(self.texture_image())
             vn = None if self.vertex_normals is None else _host(self.vertex_normals)
             if ext == "glb":
+                extra = {} if self.vertex_occlusion is None else {"occlusion": _host(self.vertex_occlusion)[f.reshape(-1)]}
                 meshio.write_glb(str(path), v[f.reshape(-1)], np.arange(f.size, dtype=np.int64).reshape(-1, 3), uvs=uv,
-                                 basecolor_tex=picture, normals=None if vn is None else vn[f.reshape(-1)])
+                                 basecolor_tex=picture, normals=None if vn is None else vn[f.reshape(-1)], **extra)
             else:
                 meshio.write_obj_textured(str(path), v, f, uv, picture, normals=vn)
             return
-        writer(str(path), self.vertices, self.faces, vertex_colors=self.vertex_colors, normals=self.vertex_normals)
+        extra = {} if self.vertex_occlusion is None or ext == "obj" else {"occlusion": _host(self.vertex_occlusion)}
+        writer(str(path), self.vertices, self.faces, vertex_colors=self.vertex_colors, normals=self.vertex_normals, **extra)
 
 
 def _host(x):
@@ -1102,7 +1129,7 @@ class TSR(KernelEngine):
 
     def extract_meshes(self, scene_codes, enable_texture=False, resolution: int = 256, threshold: float = 25.0,
                        x_range=None, density_events=None, bake_texture: int = 0, normals=None,
-                       keep_components=None, simplify=None, smooth=None, project=None) -> List[Mesh]:
+                       keep_components=None, simplify=None, smooth=None, project=None, occlusion=None) -> List[Mesh]:
         """The arithmetic of system.py:171-200 without the Blender sink: returns device tensors.
         density_events: optional (start, stop) torch events recorded around the dense-grid launch (bench.py's live
         per-launch timing of the dominant kernel, on the stream it is launched on).
@@ -1126,9 +1153,18 @@ class TSR(KernelEngine):
         cell), an int n in 1 .. 64 or a tuple (n, cells) (ops.project_rule): every vertex is moved onto the iso-surface
         density_act = threshold of the field itself and folded faces are undone (ops.mesh_project, TSR.project_mesh) -- the
         LAST geometry step, after keep_components, smooth and simplify and before the colours, the bake and the normals, which are
-        therefore evaluated at the projected vertices; faces and indices are unchanged.  Needs threshold > 0."""
+        therefore evaluated at the projected vertices; faces and indices are unchanged.  Needs threshold > 0.
+        occlusion: None (default): nothing is launched, nothing changes.  True (64 directions), an int k in 1 .. 1024 or a tuple
+        (k, max_distance) (ops.occlusion_rule): Mesh.vertex_occlusion = the ambient occlusion of the final mesh against itself,
+        f32 [Nv], 1 = open, 0 = occluded -- Mesh.ambient_occlusion(occlusion, outward=TSR.WINDING_OUTWARD), one fused ray
+        kernel (ops.mesh_occlusion) over the mesh's own grid.  Not a geometry step: it is computed with the colours and the
+        normals, after the geometry chain, and changes no vertex and no face.  run, run_async, run_batched, run_pipelined,
+        batch.run_sharded and extract_mesh_sharded do not take the option yet (their host hand-off copies four arrays): call
+        Mesh.ambient_occlusion on a device mesh instead."""
         if normals not in (None, "field", "faces"):
             raise ValueError("normals must be None, 'field' or 'faces', got %r" % (normals,))
+        if occlusion is not None:
+            ops.occlusion_rule(occlusion)   # a ValueError before anything is launched
         geometry = dict(keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)
         self._check_geometry(threshold, **geometry)   # a ValueError before anything is launched
         bake = int(bake_texture) if enable_texture else 0
@@ -1151,7 +1187,7 @@ class TSR(KernelEngine):
                 vol = ops.density_grid(planes, self.decoder, R, precision=self.decoder_precision, events=density_events, **dkw)
                 v_pos, t_pos_idx = mc(vol)   # (both decoder modes have the fp32 range: a NaN here is a NaN of the model)
             v_pos, t_pos_idx = self._reshaped(v_pos, t_pos_idx, planes, threshold, R, **geometry)
-            out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals))
+            out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals, occlusion))
         return out
 
     @staticmethod
@@ -1182,9 +1218,15 @@ class TSR(KernelEngine):
             v_pos = self._projected(v_pos, t_pos_idx, planes, threshold, project, R)
         return v_pos, t_pos_idx
 
-    def _textured(self, v_pos, t_pos_idx, planes, enable_texture, bake, normals=None):
+    # What turns ops.vertex_normals of an extract_meshes mesh outwards: marching cubes (reference_order: face columns [1, 0, 2])
+    # on density_act - threshold, positive inside, winds its faces counter-clockwise seen from outside -- on the analytic
+    # sphere every face's cross(b - a, c - a) points away from the centre.  tests/test_gpu_mesh_ray.py pins the sign against
+    # TSR.field_normals on the model's mesh.
+    WINDING_OUTWARD = 1.0
+
+    def _textured(self, v_pos, t_pos_idx, planes, enable_texture, bake, normals=None, occlusion=None):
         """The appearance half of extract_meshes: nothing, vertex colours (system.py:189-193) or a baked texture; and the
-        vertex normals when asked for."""
+        vertex normals and the ambient occlusion when asked for."""
         if enable_texture and bake > 0:
             mesh = self.bake_texture(Mesh(v_pos, t_pos_idx), planes, bake)
         else:
@@ -1196,6 +1238,8 @@ class TSR(KernelEngine):
             mesh.vertex_normals = self.field_normals(v_pos, planes)
         elif normals == "faces":
             mesh.vertex_normals = ops.vertex_normals(v_pos, t_pos_idx)
+        if occlusion is not None:
+            mesh.vertex_occlusion = Mesh(v_pos, t_pos_idx).ambient_occlusion(occlusion, outward=self.WINDING_OUTWARD)
         return mesh
 
     # -- the two-pass ("filtered") density grid: calibration, guard, fallback (csrc/density_filter.hip)
@@ -1305,14 +1349,16 @@ class TSR(KernelEngine):
         return Mesh(v_pos, t_pos_idx, color)
 
     def extract_mesh(self, scene_codes, enable_texture=False, mesh_name="NewMesh", resolution: int = 256,
-                     threshold: float = 25.0, bake_texture: int = 0, normals=None, keep_components=None, simplify=None, smooth=None, project=None):
-        """system.py:171-200: same signature (+ bake_texture, normals and the geometry options keep_components, smooth, simplify,
-        project, all described at extract_meshes: the sink receives the final mesh); pushes each mesh into the sink (Blender when
+                     threshold: float = 25.0, bake_texture: int = 0, normals=None, keep_components=None, simplify=None, smooth=None, project=None,
+                     occlusion=None):
+        """system.py:171-200: same signature (+ bake_texture, normals, occlusion and the geometry options keep_components, smooth,
+        simplify, project, all described at extract_meshes: the sink receives the final mesh); pushes each mesh into the sink (Blender when
         `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
         the textured sink (per-loop UVs + an image-texture material).  The sinks take no normals (Blender shades a mesh with
-        shared vertices smooth by itself); they stay on the returned meshes."""
+        shared vertices smooth by itself) and no occlusion; both stay on the returned meshes."""
         meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture, normals=normals,
-                                     keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)
+                                     keep_components=keep_components, simplify=simplify, smooth=smooth, project=project,
+                                     occlusion=occlusion)
         sink = self.mesh_sink or _default_sink()
         for m in meshes:
             if m.texture is not None:
