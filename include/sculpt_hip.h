@@ -1015,6 +1015,35 @@ int sculpt_smooth_neighbours(const int64_t *skeys, int64_t n, int32_t *nb, sculp
 int sculpt_smooth_taubin(const int32_t *start, const int32_t *nb, const uint8_t *fixed, int64_t nv, int64_t n_nb, const float *P,
                          int iterations, double lam, double mu, float *work_a, float *work_b, float *out, sculpt_stream_t stream);
 
+/* Loop subdivision ON THE DEVICE, one level per pair of calls (csrc/mesh_subdivide.hip; sf3d/remesh_device.py
+ * loop_subdivide_device, ops.mesh_subdivide).  DEVICE pointers, asynchronous on `stream`, no host wait.
+ * Added without a version change (new symbols only).  Compiled without floating-point contraction and restated bit for bit in
+ * tests/_loopref.py.  The faces and the numbering are sculpt_rmd_subdivide's: new vertex nv + rank_incl[h] - 1 for the edge
+ * whose first half-edge is h (rank_incl: the inclusive prefix sum of sculpt_rmd_first_halfedge), face (a, b, c) -> (a, ab, ca),
+ * (b, bc, ab), (c, ca, bc), (ab, bc, ca) at rows 4 f .. 4 f + 3.  An edge is classified by its face count es[e + 1] - es[e]
+ * alone -- 2: interior, 1: border, 3 or more: non-manifold; topo->bnd is not read.
+ *   sculpt_subdiv_classify   cls [nv][4] int32 (16-byte aligned; zeroed here, then integer atomics only: one possible result) =
+ *                            {border edges at u, 1 + the largest other end of one, nv - the smallest, 1 if a non-manifold edge
+ *                            touches u}; rows [nv][4] floats (16-byte aligned) = the positions P [nv][3] as x y z - rows.
+ *   sculpt_subdiv_loop       Po [nv + ne][3], Fo [4 nf][3] and, with A [nv][channels] (1 <= channels <= 8; A and Ao both or
+ *                            neither), Ao [nv + ne][channels].  Per component in fp64 from the fp32 values, exactly these
+ *                            operations, rounded once to fp32:
+ *                              odd vertex of edge {u, v}: interior, a and b the third vertices of its two faces:
+ *                                    0.375 * (P[u] + P[v]) + 0.125 * (P[a] + P[b]);   otherwise 0.5 * (P[u] + P[v])
+ *                              even vertex u with fan n = vfs[u + 1] - vfs[u]:
+ *                                n == 0, a non-manifold edge at u, or border edges at u neither 0 nor 2 (a corner): its bits;
+ *                                two border edges with other ends a, b (a crease): 0.75 * P[u] + 0.125 * (P[a] + P[b]);
+ *                                otherwise beta = n == 3 ? 0.1875 : 3.0 / (8.0 * n) (Warren), S = the sum left to right, over
+ *                                the corners 3 f + k of u's fan in vfc order, of P[F[3 f + (k + 1) % 3]] and then
+ *                                P[F[3 f + (k + 2) % 3]], starting as the first term (every neighbour enters twice):
+ *                                    (1.0 - n * beta) * P[u] + (0.5 * beta) * S
+ *                            The attributes go through the same masks.  The outputs must not alias the inputs.
+ * A null topology or array, a misaligned buffer, channels out of range and counts whose level would leave int32 (nv + ne,
+ * 12 nf) are refused with an error code and a message; nf == 0 launches nothing (the caller returns copies). */
+int sculpt_subdiv_classify(const sculpt_rmd_topo_t *topo, const float *P, int32_t *cls, float *rows, sculpt_stream_t stream);
+int sculpt_subdiv_loop(const sculpt_rmd_topo_t *topo, const int32_t *cls, const float *rows, const int32_t *rank_incl, const float *A,
+                       int channels, float *Po, int32_t *Fo, float *Ao, sculpt_stream_t stream);
+
 /* Distance between triangle surfaces ON THE DEVICE (csrc/mesh_distance.hip; ops.mesh_closest_points, ops.mesh_sample_surface,
  * ops.mesh_distance).  DEVICE pointers (params_host excepted), asynchronous on `stream`, no host wait.
  * Compiled without floating-point contraction and restated bit for bit in tests/_distref.py.  Added without a version change

@@ -215,6 +215,8 @@ SIGNATURES = {
     "sculpt_smooth_edge_keys": (_i, [_vp, _vp, _vp]),
     "sculpt_smooth_neighbours": (_i, [_vp, _i64, _vp, _vp]),
     "sculpt_smooth_taubin": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
+    "sculpt_subdiv_classify": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "sculpt_subdiv_loop": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "sculpt_surface_closest": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
     "sculpt_surface_cells": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "sculpt_surface_pack": (_i, [_vp, _vp, _i64, _vp, _vp]),

@@ -63,7 +63,7 @@ class MeshWriter:
 
 
 def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture=False, out_dir=None, names=None, fmt="ply",
-                keep=True, writers=4, batch=1, keep_components=None, simplify=None, smooth=None, project=None):
+                keep=True, writers=4, batch=1, keep_components=None, simplify=None, smooth=None, project=None, subdivide=None):
     """images: the WHOLE batch, identical on every rank (a list of host arrays / PIL images, or callables returning one, so
     that a rank only loads the files it owns).  Returns (local, summary):
       local   {index: Mesh} of the images this rank owns (empty dict with keep=False: meshes are only written);
@@ -73,7 +73,7 @@ def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture
     submit loop (0: synchronously, inside the loop).
     batch > 1: this rank's images go through the transformer `batch` per pass (TSR.run_batched: the reference's batched forward,
     3.9 instead of 5.3 ms per image at 4); the meshes then differ from single-image calls by the bf16 transformer's rounding.
-    keep_components, smooth, simplify, project: the geometry options of TSR.extract_meshes, described there; each is handed to
+    keep_components, smooth, simplify, subdivide, project: the geometry options of TSR.extract_meshes, described there; each is handed to
     the model only when set.
     A rank that fails still takes part in the one exchange, with an error marker in place of its counts: every rank then
     raises, none is left waiting in a collective the failed rank never enters."""
@@ -87,8 +87,8 @@ def run_sharded(model, images, mc_resolution=256, threshold=25.0, enable_texture
     if fmt not in ("ply", "npz", "obj"):
         raise ValueError("format must be 'ply', 'npz' or 'obj'")
     local, counts = {}, []
-    ckw = {k: x for k, x in dict(keep_components=keep_components, simplify=simplify, smooth=smooth, project=project).items()
-           if x is not None}
+    ckw = {k: x for k, x in dict(keep_components=keep_components, simplify=simplify, smooth=smooth, project=project,
+                                 subdivide=subdivide).items() if x is not None}
     writer = MeshWriter(writers) if (out_dir is not None and writers) else None
     failure = None
 

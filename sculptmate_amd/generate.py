@@ -40,8 +40,11 @@ class TripoGenerator(GeneratorFacade):
     ops.mesh_smooth).
     `project` (default None): True (8 Newton steps inside one lattice cell), an int n in 1 .. 64 or a tuple (n, cells) moves the
     vertices of every mesh onto the iso-surface of the density field itself and undoes folded faces, as the last geometry
-    step -- after keep_components, smooth and simplify, before the colours, the bake and the normals (TSR.extract_meshes;
-    ops.mesh_project).
+    step -- after keep_components, smooth, simplify and subdivide, before the colours, the bake and the normals
+    (TSR.extract_meshes; ops.mesh_project).
+    `subdivide` (default None): an int n in 1 .. 6 (levels of the Loop scheme) or a tuple (n, "loop" | "midpoint") refines every
+    mesh 1 -> 4 faces per level on the device, after simplify and before project: the simplified mesh becomes the control cage
+    of a semi-regular, multires-friendly surface (TSR.extract_meshes; ops.mesh_subdivide).
     `occlusion` (default None): True (64 directions), an int k in 1 .. 1024 or a tuple (k, max_distance) leaves the ambient
     occlusion of every final mesh against itself on the meshes in `last_meshes` (Mesh.vertex_occlusion, f32 [Nv], 1 = open:
     TSR.extract_meshes; ops.mesh_occlusion); Mesh.export writes it into .ply and .glb.  The Blender sinks take none."""
@@ -56,6 +59,7 @@ class TripoGenerator(GeneratorFacade):
         self.simplify = None
         self.smooth = None
         self.project = None
+        self.subdivide = None
         self.occlusion = None
 
     def _construct_model(self):
@@ -75,7 +79,8 @@ class TripoGenerator(GeneratorFacade):
                                                        bake_texture=int(self.bake_texture_resolution or 0),
                                                        normals=self.vertex_normals,
                                                        keep_components=self.keep_components, simplify=self.simplify,
-                                                       smooth=self.smooth, project=self.project, occlusion=self.occlusion)
+                                                       smooth=self.smooth, project=self.project, subdivide=self.subdivide,
+                                                       occlusion=self.occlusion)
         except Exception as err:
             print(self.run_error_tag, err)
             return STATUS_FAILED

@@ -704,6 +704,73 @@ def mesh_smooth(vertices, faces, smooth):
 
 
 # ----------------------------------------------------------------------------------------------
+# mesh subdivision: the Loop scheme (csrc/mesh_subdivide.hip, sf3d/remesh_device.py loop_subdivide_device)
+# ----------------------------------------------------------------------------------------------
+SUBDIVIDE_MAX_LEVELS = 6
+SUBDIVIDE_SCHEMES = ("loop", "midpoint")
+
+
+def subdivide_rule(subdivide):
+    """`subdivide` of mesh_subdivide -> (levels, scheme): an int n, 1 <= n <= 6 (n levels of the Loop scheme), or a tuple
+    (n, "loop" | "midpoint").  Anything else -- bool, float, 0, 7, NaN, another string or length -- is a ValueError, raised here,
+    before anything is launched."""
+    if _is_count(subdivide, 1, SUBDIVIDE_MAX_LEVELS):
+        return int(subdivide), "loop"
+    if (isinstance(subdivide, tuple) and len(subdivide) == 2 and _is_count(subdivide[0], 1, SUBDIVIDE_MAX_LEVELS)
+            and isinstance(subdivide[1], str) and subdivide[1] in SUBDIVIDE_SCHEMES):
+        return int(subdivide[0]), subdivide[1]
+    raise ValueError("subdivide must be an int in 1 .. %d (levels of the Loop scheme) or (levels, 'loop' | 'midpoint'), got %r"
+                     % (SUBDIVIDE_MAX_LEVELS, subdivide))
+
+
+def mesh_subdivide(vertices, faces, subdivide, attributes=None):
+    """The mesh refined 1 -> 4 faces per level, on the device: a subdivision surface of the input taken as a control cage (the
+    Loop scheme with Warren's weights), or its plain midpoint upsampling.  vertices float [Nv, 3], faces int32 / int64 [Nf, 3],
+    attributes None or float [Nv, C] with 1 <= C <= 8 (device tensors; CPU tensors are refused); subdivide: see subdivide_rule.
+    -> (vertices' f32 [Nv + Ne.., 3], faces' [4^levels Nf, 3] in faces' dtype, attributes' f32 [.., C] or None), new tensors.
+    Contract, per level:
+      - faces and numbering are those of sf3d.remesh_device.subdivide_device: the old vertices keep their indices, the vertex
+        of an edge gets Nv + (rank of the edge's first appearance over the half-edges) - 1, and face (a, b, c) becomes
+        (a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca) at rows 4 f .. 4 f + 3; orientation is kept;
+      - an edge is interior with two faces, a border edge with one, non-manifold with three or more; every component below is
+        computed in fp64 from the fp32 values with exactly the operations written, and rounded once to fp32;
+      - the new vertex of an interior edge {u, v} whose two faces have the third vertices a, b:
+        0.375 * (P[u] + P[v]) + 0.125 * (P[a] + P[b]); of a border or non-manifold edge: the midpoint 0.5 * (P[u] + P[v]);
+      - an old vertex u with n corners in the faces: no face, a non-manifold edge at u, or a number of border edges at u that
+        is neither 0 nor 2 (a corner) -- it keeps its bits; exactly two border edges, with other ends a, b (a crease) --
+        0.75 * P[u] + 0.125 * (P[a] + P[b]); otherwise beta = 0.1875 for n == 3, else 3.0 / (8.0 * n), S = the sum over the
+        faces around u in face order of the face's next and then its last vertex after u (every neighbour enters twice), and
+        (1.0 - n * beta) * P[u] + (0.5 * beta) * S.  A vertex of any valence follows these rules;
+      - attributes go through the same masks, so values in [0, 1] stay there up to one ulp;
+      - scheme "midpoint": subdivide_device itself -- every new vertex the fp32 midpoint, old vertices unmoved, attributes
+        refined the same way (linearly);
+      - the inputs are untouched; a face index out of range, a repeated index in a face and a non-finite position are a
+        SculptError, and so is a level whose 3 x faces would leave int32;
+      - Nf == 0: copies;
+      - deterministic: integer atomics for the classification, a fixed-order gather in fp64 without contraction for the
+        values; two calls give the same bits (tests/_loopref.py restates it bit for bit);
+      - per level the host reads back the edge count of the level's one topology construction, and before the first level the
+        input check's status.  The counts are in sf3d.remesh_device.last_stats()."""
+    levels, scheme = subdivide_rule(subdivide)
+    from .sf3d import remesh_device as rmd
+
+    _device_mesh(vertices, faces, "mesh_subdivide")
+    if scheme == "loop":
+        v, f, a = rmd.loop_subdivide_device(vertices, faces, levels, attributes)
+        return v, f.to(faces.dtype), a
+    rmd._inputs(vertices, faces, "mesh_subdivide")   # the input check of the Loop route; subdivide_device itself skips it
+    a = rmd._attributes(attributes, vertices.shape[0], "mesh_subdivide")
+    if faces.shape[0] == 0:
+        levels = 0
+    v, f = rmd.subdivide_device(vertices, faces, levels)
+    if a is not None and levels:
+        # the fp32 midpoint of three columns at a time is the linear refinement of those columns
+        cols = [torch.nn.functional.pad(a[:, c:c + 3], (0, max(0, c + 3 - a.shape[1]))) for c in range(0, a.shape[1], 3)]
+        a = torch.cat([rmd.subdivide_device(x, faces, levels)[0] for x in cols], 1)[:, :a.shape[1]].contiguous()
+    return v, f.to(faces.dtype), a
+
+
+# ----------------------------------------------------------------------------------------------
 # distance between surfaces: area-uniform samples, closest points, Chamfer / Hausdorff / F-score (csrc/mesh_distance.hip,
 # DESIGN.md 3.3e)
 # ----------------------------------------------------------------------------------------------

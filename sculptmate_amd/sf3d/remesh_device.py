@@ -7,6 +7,7 @@ sculpt_rmd_* in include/sculpt_hip.h), with the contract of the host calls in sf
     device_remesher(mesh, mode, vertex_count, remesh_steps=10) -> Mesh      the SF3D.remesher hook, opt-in
     simplify_device(v, f, target_faces) -> (v, f, vertex_index)             quadric-error collapse (ops.mesh_simplify)
     smooth_device(v, f, iterations, lam, mu) -> v                           Taubin lambda|mu smoothing (ops.mesh_smooth)
+    loop_subdivide_device(v, f, levels, attributes=None) -> (v, f, attributes)   Loop subdivision (ops.mesh_subdivide)
 
 v and f are HIP tensors (v any float dtype, f any integer dtype); results are float32 [n, 3] / int32 [m, 3] HIP tensors.  CPU
 tensors are refused.  The rules are the host's (csrc/remesh_host.h); its sequential order becomes rounds of independent local
@@ -355,6 +356,66 @@ def subdivide_device(v, f, iters=1):
         P, F = Po, Fo
     ctx.done()
     return P, F
+
+
+LOOP_MAX_CHANNELS = 8  # csrc/mesh_subdivide.hip kMaxChannels
+
+
+def _loop_topology(ctx, F, nv):
+    """The topology of one Loop level.  A zero `carry`, as in _smooth_table: the kernels classify by the edges' face counts and
+    never read bnd, so the scan for vertices of more than 64 neighbours is not run."""
+    return _Topo(ctx, F, nv, carry=torch.zeros(max(nv, 1), dtype=torch.uint8, device=F.device))
+
+
+def _loop_level(ctx, T, P, A=None):
+    """One Loop level on the topology T of (P, T.F): the numbering (sculpt_rmd_first_halfedge, as subdivide_device), then the two
+    launches of csrc/mesh_subdivide.hip -> (P' [nv + ne, 3], F' [4 nf, 3], A' or None); nothing is read back."""
+    dev, s, nv = P.device, ctx.stream, T.nv
+    first = torch.empty(3 * T.nf, dtype=torch.int32, device=dev)
+    check(lib.sculpt_rmd_first_halfedge(T.ref(), _p(first), s))
+    rank = torch.cumsum(first, 0, dtype=torch.int32)
+    cls = torch.empty((nv, 4), dtype=torch.int32, device=dev)
+    rows = torch.empty((nv, 4), dtype=torch.float32, device=dev)
+    check(lib.sculpt_subdiv_classify(T.ref(), _p(P), _p(cls), _p(rows), s))
+    Po = torch.empty((nv + T.ne, 3), dtype=torch.float32, device=dev)
+    Fo = torch.empty((4 * T.nf, 3), dtype=torch.int32, device=dev)
+    Ao = None if A is None else torch.empty((nv + T.ne, A.shape[1]), dtype=torch.float32, device=dev)
+    check(lib.sculpt_subdiv_loop(T.ref(), _p(cls), _p(rows), _p(rank), _p(A), 0 if A is None else A.shape[1], _p(Po), _p(Fo), _p(Ao), s))
+    return Po, Fo, Ao
+
+
+def _attributes(attributes, nv, who):
+    """attributes of a subdivision -> an owned f32 [nv, C] device tensor, 1 <= C <= LOOP_MAX_CHANNELS (None stays None)."""
+    if attributes is None:
+        return None
+    a = attributes
+    if not (isinstance(a, torch.Tensor) and a.is_cuda):
+        raise SculptError("%s: attributes must be a CUDA/HIP tensor (no CPU fallback)" % who)
+    if not a.dtype.is_floating_point or a.dim() != 2 or a.shape[0] != nv or not 1 <= a.shape[1] <= LOOP_MAX_CHANNELS:
+        raise SculptError("%s: attributes must be float [%d, C] with 1 <= C <= %d (a row per vertex), got %s %s"
+                          % (who, nv, LOOP_MAX_CHANNELS, a.dtype, tuple(a.shape)))
+    return a.detach().to(torch.float32).clone().contiguous()
+
+
+def loop_subdivide_device(v, f, levels, attributes=None):
+    """`levels` levels of Loop subdivision (csrc/mesh_subdivide.hip; the contract is in include/sculpt_hip.h and
+    ops.mesh_subdivide): the faces and the numbering of subdivide_device, the positions and the optional attributes (float
+    [nv, C], C <= 8) by the scheme's masks, in fp64 rounded once.  -> (v f32 [n, 3], f int32 [m, 3], attributes f32 [n, C] or
+    None), new tensors.  A face index out of range, a repeated index in a face and a non-finite position are a SculptError.  One
+    topology construction per level, whose edge count is the level's one readback; no faces: copies."""
+    levels = int(levels)
+    if not 0 <= levels <= 12:
+        raise SculptError("mesh_subdivide: levels=%d out of range" % levels)
+    P, F = _inputs(v, f, "mesh_subdivide")
+    A = _attributes(attributes, P.shape[0], "mesh_subdivide")
+    if F.shape[0] * 4.0 ** levels >= 1.5e9:  # subdivide_device's bound
+        raise SculptError("mesh_subdivide: %d faces x 4^%d does not fit int32 indices" % (F.shape[0], levels))
+    ctx = _Ctx()
+    if F.shape[0]:
+        for _ in range(levels):
+            P, F, A = _loop_level(ctx, _loop_topology(ctx, F, P.shape[0]), P, A)
+    ctx.done()
+    return P, F, A
 
 
 def _decimate(ctx, P, F, target):

@@ -96,6 +96,19 @@ class Mesh:
         v = ops.mesh_smooth(self.vertices, self.faces, smooth)
         return Mesh(v, self.faces, self.vertex_colors, uvs=self.uvs, texture=self.texture)
 
+    def subdivide(self, subdivide) -> "Mesh":
+        """The mesh refined 1 -> 4 faces per level on the device (ops.mesh_subdivide): subdivide = an int n, 1 <= n <= 6 (n
+        levels of the Loop scheme: the surface the mesh spans as a control cage) or a tuple (n, "loop" | "midpoint")
+        (ops.subdivide_rule).  vertex_colors go through the same masks as the positions (attributes=), so they stay in their
+        range.  vertex_normals and vertex_occlusion are dropped: they are stale on the refined surface.  A baked mesh
+        (uvs / texture) is refused: its atlas belongs to the faces it was baked for, so subdivide before baking."""
+        ops.subdivide_rule(subdivide)
+        if self.uvs is not None or self.texture is not None:
+            raise ValueError("Mesh.subdivide: this mesh has a baked texture; subdivide before baking "
+                             "(TSR.extract_meshes(subdivide=..., bake_texture=...))")
+        v, f, colors = ops.mesh_subdivide(self.vertices, self.faces, subdivide, attributes=self.vertex_colors)
+        return Mesh(v, f, colors)
+
     def sample_surface(self, n, seed=0):
         """n points uniform over this mesh's area (ops.mesh_sample_surface on its device tensors; host arrays are refused like
         any CPU tensor) -> (points f32 [n, 3], face i64 [n], uv f32 [n, 2]); the same (n, seed) gives the same bits."""
@@ -1129,7 +1142,7 @@ class TSR(KernelEngine):
 
     def extract_meshes(self, scene_codes, enable_texture=False, resolution: int = 256, threshold: float = 25.0,
                        x_range=None, density_events=None, bake_texture: int = 0, normals=None,
-                       keep_components=None, simplify=None, smooth=None, project=None, occlusion=None) -> List[Mesh]:
+                       keep_components=None, simplify=None, smooth=None, project=None, subdivide=None, occlusion=None) -> List[Mesh]:
         """The arithmetic of system.py:171-200 without the Blender sink: returns device tensors.
         density_events: optional (start, stop) torch events recorded around the dense-grid launch (bench.py's live
         per-launch timing of the dominant kernel, on the stream it is launched on).
@@ -1152,8 +1165,13 @@ class TSR(KernelEngine):
         project: None (default): nothing is launched, nothing changes.  True (8 Newton steps inside a trust radius of one lattice
         cell), an int n in 1 .. 64 or a tuple (n, cells) (ops.project_rule): every vertex is moved onto the iso-surface
         density_act = threshold of the field itself and folded faces are undone (ops.mesh_project, TSR.project_mesh) -- the
-        LAST geometry step, after keep_components, smooth and simplify and before the colours, the bake and the normals, which are
-        therefore evaluated at the projected vertices; faces and indices are unchanged.  Needs threshold > 0.
+        LAST geometry step, after keep_components, smooth, simplify and subdivide and before the colours, the bake and the normals,
+        which are therefore evaluated at the projected vertices; faces and indices are unchanged.  Needs threshold > 0.
+        subdivide: None (default): nothing is launched, nothing changes.  An int n in 1 .. 6 (n levels of the Loop scheme) or a
+        tuple (n, "loop" | "midpoint") (ops.subdivide_rule): every face becomes four per level on the device
+        (ops.mesh_subdivide) AFTER simplify and BEFORE project -- simplify leaves a light, irregular cage, subdivide refines it
+        into a semi-regular surface, and project puts the vertices that now exist between the lattice points onto the field's
+        iso-surface.  Mesh.subdivide lets a caller choose another order.
         occlusion: None (default): nothing is launched, nothing changes.  True (64 directions), an int k in 1 .. 1024 or a tuple
         (k, max_distance) (ops.occlusion_rule): Mesh.vertex_occlusion = the ambient occlusion of the final mesh against itself,
         f32 [Nv], 1 = open, 0 = occluded -- Mesh.ambient_occlusion(occlusion, outward=TSR.WINDING_OUTWARD), one fused ray
@@ -1165,7 +1183,7 @@ class TSR(KernelEngine):
             raise ValueError("normals must be None, 'field' or 'faces', got %r" % (normals,))
         if occlusion is not None:
             ops.occlusion_rule(occlusion)   # a ValueError before anything is launched
-        geometry = dict(keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)
+        geometry = dict(keep_components=keep_components, simplify=simplify, smooth=smooth, project=project, subdivide=subdivide)
         self._check_geometry(threshold, **geometry)   # a ValueError before anything is launched
         bake = int(bake_texture) if enable_texture else 0
         self.set_marching_cubes_resolution(resolution)
@@ -1191,7 +1209,7 @@ class TSR(KernelEngine):
         return out
 
     @staticmethod
-    def _check_geometry(threshold, keep_components=None, simplify=None, smooth=None, project=None):
+    def _check_geometry(threshold, keep_components=None, simplify=None, smooth=None, project=None, subdivide=None):
         """The rules of the geometry options that are set (ops.*_rule; an option left None is not looked at): a ValueError
         here comes before anything is launched."""
         if keep_components is not None:
@@ -1200,20 +1218,25 @@ class TSR(KernelEngine):
             ops.simplify_rule(simplify)
         if smooth is not None:
             ops.smooth_rule(smooth)
+        if subdivide is not None:
+            ops.subdivide_rule(subdivide)
         if project is not None:
             ops.project_rule(project)
             if not threshold > 0:
                 raise ValueError("project needs a positive threshold (the surface is ln(threshold) in the raw density), got %r" % (threshold,))
 
-    def _reshaped(self, v_pos, t_pos_idx, planes, threshold, R, keep_components=None, simplify=None, smooth=None, project=None):
-        """The geometry half of extract_meshes, in its fixed order: keep_components -> smooth -> simplify -> project, each only
-        when set -> (v_pos, t_pos_idx).  A new geometry step goes in here, and into _check_geometry, and nowhere else."""
+    def _reshaped(self, v_pos, t_pos_idx, planes, threshold, R, keep_components=None, simplify=None, smooth=None, project=None,
+                  subdivide=None):
+        """The geometry half of extract_meshes, in its fixed order: keep_components -> smooth -> simplify -> subdivide -> project,
+        each only when set -> (v_pos, t_pos_idx).  A new geometry step goes in here, and into _check_geometry, and nowhere else."""
         if keep_components is not None:
             v_pos, t_pos_idx = ops.mesh_keep_components(v_pos, t_pos_idx, keep_components)[:2]
         if smooth is not None:
             v_pos = ops.mesh_smooth(v_pos, t_pos_idx, smooth)
         if simplify is not None:
             v_pos, t_pos_idx = ops.mesh_simplify(v_pos, t_pos_idx, simplify)[:2]
+        if subdivide is not None:
+            v_pos, t_pos_idx = ops.mesh_subdivide(v_pos, t_pos_idx, subdivide)[:2]
         if project is not None:
             v_pos = self._projected(v_pos, t_pos_idx, planes, threshold, project, R)
         return v_pos, t_pos_idx
@@ -1325,6 +1348,7 @@ class TSR(KernelEngine):
         It takes no keep_components: components cross the slabs, so the gathered mesh is filtered afterwards, with
         Mesh.keep_components.  It takes no smooth either, for the same reason (a slab's cut is an open border, whose vertices
         smoothing holds fixed): smooth the gathered mesh with Mesh.smooth.  It takes no project: use TSR.project_mesh on the
+        gathered mesh.  It takes no subdivide either (a slab's cut would be refined as a crease): use Mesh.subdivide on the
         gathered mesh."""
         import torch.distributed as dist
 
@@ -1350,15 +1374,15 @@ class TSR(KernelEngine):
 
     def extract_mesh(self, scene_codes, enable_texture=False, mesh_name="NewMesh", resolution: int = 256,
                      threshold: float = 25.0, bake_texture: int = 0, normals=None, keep_components=None, simplify=None, smooth=None, project=None,
-                     occlusion=None):
+                     subdivide=None, occlusion=None):
         """system.py:171-200: same signature (+ bake_texture, normals, occlusion and the geometry options keep_components, smooth,
-        simplify, project, all described at extract_meshes: the sink receives the final mesh); pushes each mesh into the sink (Blender when
+        simplify, subdivide, project, all described at extract_meshes: the sink receives the final mesh); pushes each mesh into the sink (Blender when
         `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
         the textured sink (per-loop UVs + an image-texture material).  The sinks take no normals (Blender shades a mesh with
         shared vertices smooth by itself) and no occlusion; both stay on the returned meshes."""
         meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture, normals=normals,
                                      keep_components=keep_components, simplify=simplify, smooth=smooth, project=project,
-                                     occlusion=occlusion)
+                                     subdivide=subdivide, occlusion=occlusion)
         sink = self.mesh_sink or _default_sink()
         for m in meshes:
             if m.texture is not None:
@@ -1374,7 +1398,7 @@ class TSR(KernelEngine):
         return meshes
 
     def run_async(self, image, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, tokens=None,
-                  normals=None, keep_components=None, simplify=None, smooth=None, project=None):
+                  normals=None, keep_components=None, simplify=None, smooth=None, project=None, subdivide=None):
         """One host image -> PendingMesh.  The image goes host -> HBM, the forward and the mesh extraction are queued on
         the current stream, and the mesh (the reference's `.cpu().numpy()` at system.py:200) is copied device -> pinned
         host memory on a separate copy stream, so the copy of mesh i runs under the kernels of image i + 1.
@@ -1383,7 +1407,8 @@ class TSR(KernelEngine):
         with torch.no_grad():
             codes = self.forward([image], self.device) if tokens is None else self.forward_tokens(tokens)
             m = self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals,
-                                    keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)[0]
+                                    keep_components=keep_components, simplify=simplify, smooth=smooth, project=project,
+                                    subdivide=subdivide)[0]
         return self._mesh_to_host_async(m)
 
     def _mesh_to_host_async(self, m) -> PendingMesh:
@@ -1414,7 +1439,7 @@ class TSR(KernelEngine):
         return PendingMesh(host, done, tuple(leases))
 
     def run(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, batch=None,
-            normals=None, keep_components=None, simplify=None, smooth=None, project=None) -> List[Mesh]:
+            normals=None, keep_components=None, simplify=None, smooth=None, project=None, subdivide=None) -> List[Mesh]:
         """Headless entry point: images -> list of Mesh with host (NumPy) arrays; the device -> host copy of mesh i overlaps the
         kernels that follow it.
         batch (images per transformer pass; None = the default): in the bf16 mode a stacked pass of several images gives each
@@ -1424,11 +1449,11 @@ class TSR(KernelEngine):
         (test_run_batches_by_default_and_returns_the_serial_meshes).  The limb modes default to one image per pass with the
         tokenizer look-ahead (run_pipelined).  batch=1 forces that everywhere.
         normals: None, "field" or "faces" (extract_meshes): Mesh.vertex_normals as float32 [Nv, 3] on the host.
-        keep_components, smooth, simplify, project: the geometry options of extract_meshes, described there."""
+        keep_components, smooth, simplify, subdivide, project: the geometry options of extract_meshes, described there."""
         images = _as_image_list(images)
         if batch is None:
             batch = self.RUN_BATCH if (self.precision == "bf16" and len(images) >= 2) else 1
-        kw = dict(normals=normals, keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)
+        kw = dict(normals=normals, keep_components=keep_components, simplify=simplify, smooth=smooth, project=project, subdivide=subdivide)
         if batch <= 1 or len(images) < 2:
             return [p.result() for p in self.run_pipelined(images, mc_resolution, threshold, enable_texture, **kw)]
         return [p.result() for p in self.run_batched(images, batch, mc_resolution, threshold, enable_texture, **kw)]
@@ -1436,7 +1461,7 @@ class TSR(KernelEngine):
     RUN_BATCH = 8   # images per transformer pass of TSR.run in the bf16 mode (4: 139.7, 8: 143.5 meshes/s device to device)
 
     def run_batched(self, images, batch: int = 4, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False,
-                    normals=None, keep_components=None, simplify=None, smooth=None, project=None):
+                    normals=None, keep_components=None, simplify=None, smooth=None, project=None, subdivide=None):
         """images (host or device) -> list of PendingMesh through batched forward passes of `batch` images each."""
         images = list(images)
         pending = []
@@ -1447,18 +1472,19 @@ class TSR(KernelEngine):
                 with torch.no_grad():
                     codes = self.forward(images[i:i + self.max_batch], self.device)
                     for m in self.extract_meshes(codes, enable_texture, mc_resolution, threshold, normals=normals,
-                                                 keep_components=keep_components, simplify=simplify, smooth=smooth, project=project):
+                                                 keep_components=keep_components, simplify=simplify, smooth=smooth, project=project,
+                                                 subdivide=subdivide):
                         pending.append(self._mesh_to_host_async(m))
         finally:
             self.max_batch = keep
         return pending
 
     def run_pipelined(self, images, mc_resolution: int = 256, threshold: float = 25.0, enable_texture: bool = False, normals=None,
-                      keep_components=None, simplify=None, smooth=None, project=None):
+                      keep_components=None, simplify=None, smooth=None, project=None, subdivide=None):
         """images (host or device) -> list of PendingMesh, with the tokenizer of image i + 1 queued beside the backbone /
         density grid / marching cubes of image i (tokens_async) and the device -> host copy of mesh i under image i + 1."""
         images = list(images)
-        kw = dict(normals=normals, keep_components=keep_components, simplify=simplify, smooth=smooth, project=project)
+        kw = dict(normals=normals, keep_components=keep_components, simplify=simplify, smooth=smooth, project=project, subdivide=subdivide)
         if len(images) < 2:
             return [self.run_async(im, mc_resolution, threshold, enable_texture, **kw) for im in images]
         pending, nxt = [], self.tokens_async(images[0])

@@ -1,7 +1,7 @@
 """Time the surface distance queries (csrc/mesh_distance.hip, ops.mesh_closest_points / mesh_sample_surface / mesh_distance) on
 the mesh they are meant for -- extract_meshes at 256^3 of the full-size TSR with seeded weights -- and measure with them what
-the mesh options do to that surface: mesh_distance(plain, X, samples=None) for X = smooth=10, simplify=0.1 and project=True, in
-lattice cells.
+the mesh options do to that surface: mesh_distance(plain, X, samples=None) for X = smooth=10, simplify=0.1, project=True, the
+simplified mesh refined by subdivide=1 (with and without project) and simplify=0.4, in lattice cells.
 
     python tools/time_mesh_distance.py [--runs 7] [--warmup 2] [--samples 1000000] [--out profiles/time_mesh_distance.json]
 
@@ -85,7 +85,12 @@ def main():
     with torch.no_grad():
         variants = {"smooth=10": model.extract_meshes([code], False, MC_RES, THRESHOLD, smooth=10)[0],
                     "simplify=0.1": model.extract_meshes([code], False, MC_RES, THRESHOLD, simplify=0.1)[0],
-                    "project=True": model.extract_meshes([code], False, MC_RES, THRESHOLD, project=True)[0]}
+                    "project=True": model.extract_meshes([code], False, MC_RES, THRESHOLD, project=True)[0],
+                    # what subdivision gives back to the simplified cage, against a simplification to about as many faces
+                    "simplify=0.1, subdivide=1": model.extract_meshes([code], False, MC_RES, THRESHOLD, simplify=0.1, subdivide=1)[0],
+                    "simplify=0.1, subdivide=1, project=True": model.extract_meshes([code], False, MC_RES, THRESHOLD, simplify=0.1,
+                                                                                    subdivide=1, project=True)[0],
+                    "simplify=0.4": model.extract_meshes([code], False, MC_RES, THRESHOLD, simplify=0.4)[0]}
     simp = variants["simplify=0.1"]
     Ps, Fs = ops._surface(simp.vertices, simp.faces, "time_mesh_distance")
     forms, same2 = both_forms(ops._SurfaceIndex(Ps, Fs), P, a.runs, a.warmup)
