@@ -178,6 +178,42 @@ int sculpt_bake_scene_color(const float *planes_cl /* [3][H][W][C] */, int C, in
                             float *color /* [res][res][3] */, uint8_t *mask /* nullable [res][res] */,
                             sculpt_stream_t stream);
 
+/* Per-corner tangent frames of a UV-mapped triangle mesh, one thread per face, every operation rounded on its own:
+ *   v_pos f32 [nv][3], faces i32 or i64 [nf][3], uvs f32 [3 nf][2] per face corner (origin bottom-left),
+ *   corner_normals f32 [3 nf][3] unit normals per face corner (DEVICE)  ->  tangents f32 [3 nf][4] = (T.xyz, w)
+ * Face: t = dP/du = (e1 dv2 - e2 dv1) / det, b = dP/dv = (e2 du1 - e1 du2) / det, det = du1 dv2 - du2 dv1.  Corner with normal
+ * N: T = normalize(t - N (N.t)), w = +1 if cross(N, T).b >= 0, else -1 (a chart mirrored in the atlas gets -1).
+ * Degenerate (det 0 or not finite, a vertex index outside [0, nv) -- nothing is read through it --, or t parallel to N):
+ * T = normalize(cross(N, e_a)) with a the axis of N's smallest component in magnitude (the lowest on a tie), w = +1; (1, 0, 0, +1)
+ * if N is 0 or not finite.  The order of operations is written down in csrc/bake_normal.hip.  nf == 0 is a no-op. */
+int sculpt_corner_tangents(const float *v_pos /* [nv][3] */, size_t nv, const void *faces /* [nf][3] */, int faces_i64, size_t nf,
+                           const float *uvs /* [3 nf][2] */, const float *corner_normals /* [3 nf][3] */,
+                           float *tangents /* [3 nf][4] */, sculpt_stream_t stream);
+
+/* Normal-map bake of a scene code: the unit normal of the density field at every covered texel of a rasterised UV atlas, one
+ * launch.  Per covered texel the position of sculpt_bake_scene_color (the bits of sculpt_bake_interpolate) and the `normal` of
+ * sculpt_triplane_density_grad (flags 0) at it, bit for bit: the world normal n.
+ *   corner_normals, corner_tangents both NULL: object space, normal = n.
+ *   both given (f32 [3 nf][3] and [3 nf][4], sculpt_corner_tangents): tangent space in the MikkTSpace / glTF convention of
+ *     un-normalised interpolated frames.  With the texel's barycentrics (u, v, w) and its face's corner rows,
+ *     N = (N0 u + N1 v) + N2 w, T likewise, B = s cross(N, T), s = the w of the face's first corner; the stored unit vector
+ *     (x, y, z) is the one with normalize(x T + y B + z N) = n, i.e. normalize(nT gnn - nN gtn, nB, nN gtt - nT gtn) with
+ *     gtt = T.T, gnn = N.N, gtn = T.N, nT = n.T, nN = n.N, nB = n.B.  The flat (0, 0, 1) is stored where gtt gnn - gtn^2 <= 0,
+ *     a component is not finite or n is 0.  The order of operations is written down in csrc/bake_normal.hip.
+ *   normal  f32 [res][res][3]  in [-1, 1], not encoded; exactly +0 where the texel is not covered
+ *   mask    u8  [res][res]     1 where covered; may be NULL
+ * Index guard and independence as for sculpt_bake_scene_color: a texel whose tri or vertex indices are out of range counts as
+ * not covered, and a texel's result depends on that texel alone.  res == 0 is a no-op. */
+int sculpt_bake_scene_normal(const float *planes_cl /* [3][H][W][C] */, int C, int H, int W,
+                             const void *mlp_packed, int n_hidden_64,
+                             const float *v_pos /* [nv][3] */, size_t nv,
+                             const void *faces /* [nf][3] */, int faces_i64, size_t nf,
+                             const float *rast /* [res][res][4] = (u, v, w, tri) or (0,0,0,-1) */, int res,
+                             float radius,
+                             const float *corner_normals /* nullable [3 nf][3] */, const float *corner_tangents /* nullable [3 nf][4] */,
+                             float *normal /* [res][res][3] */, uint8_t *mask /* nullable [res][res] */,
+                             sculpt_stream_t stream);
+
 /* Gradient of the raw density (the decoder's output 0, before bias and exp) with respect to the query point, in world units,
  * and the outward unit normal of the density's iso-surface through the point: forward-mode differentiation of
  * sculpt_triplane_query_ex(SCULPT_QUERY_CHANNEL_LAST), one launch, 8 points x {value, d/dx, d/dy, d/dz} per MFMA tile.

@@ -79,6 +79,8 @@ SIGNATURES = {
     "sculpt_render_rays": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_render_passes": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_bake_scene_color": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _i, _sz, _vp, _i, _f, _vp, _vp, _vp]),
+    "sculpt_corner_tangents": (_i, [_vp, _sz, _vp, _i, _sz, _vp, _vp, _vp, _vp]),
+    "sculpt_bake_scene_normal": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _i, _sz, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_triplane_density_grad": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _f, _i, _vp, _vp, _vp, _vp]),
     "sculpt_density_grid_workspace_bytes": (_sz, [_i, _i]),
     "sculpt_plane_features": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),

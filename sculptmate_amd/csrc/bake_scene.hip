@@ -11,7 +11,7 @@
 //     hidden layers, the three colour rows of the last layer and the colour activation are the point query's own functions
 //     (triplane_mlp.h): a covered texel's colour is the bits ops.triplane_query gives at the interpolated position from
 //     channel-last planes.  The density row is not evaluated.
-//   * the position is (a*u + b*v) + c*w per component with contraction off: the bits of bake_interpolate_kernel (csrc/baker.hip),
+//   * the position (texel_position, bake_texel.h) is (a*u + b*v) + c*w per component with contraction off: the bits of bake_interpolate_kernel (csrc/baker.hip),
 //     gathered through faces[t] from the indexed vertex array.
 //   * a tile with no covered texel is skipped (wave-uniform ballot) and stores zeros; an uncovered texel in a mixed tile samples
 //     the box centre and stores 0, 0, 0 and mask 0.  A texel's result depends on that texel alone.
@@ -19,36 +19,11 @@
 //     nothing is read through such an index.
 #include <algorithm>
 
+#include "bake_texel.h"
 #include "common.h"
 #include "triplane_mlp.h"
 
 namespace sculpt {
-
-struct Texel {
-    float x[3];
-    bool covered;
-};
-
-// rast = (u, v, w, tri) or (0, 0, 0, -1) -> interpolated position, or the box centre for a texel that is not covered
-__device__ __forceinline__ Texel texel_position(const float4 r, const float *__restrict__ v_pos, long nv, const void *__restrict__ faces,
-                                                int faces_i64, long nf) {
-#pragma clang fp contract(off)
-    Texel tx;
-    tx.x[0] = tx.x[1] = tx.x[2] = 0.f;
-    tx.covered = false;
-    if (!(r.w >= 0.f && r.w < 2147483648.f)) return tx;  // also a NaN
-    const long t = (long)(int)r.w;
-    if (t >= nf) return tx;
-    long i[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        i[k] = faces_i64 ? (long)reinterpret_cast<const long long *>(faces)[3 * t + k] : (long)reinterpret_cast<const int *>(faces)[3 * t + k];
-    if (i[0] < 0 || i[0] >= nv || i[1] < 0 || i[1] >= nv || i[2] < 0 || i[2] >= nv) return tx;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) tx.x[k] = v_pos[3 * i[0] + k] * r.x + v_pos[3 * i[1] + k] * r.y + v_pos[3 * i[2] + k] * r.z;
-    tx.covered = true;
-    return tx;
-}
 
 template <int C>
 __global__ __launch_bounds__(512) void bake_scene_color_kernel(

@@ -47,7 +47,11 @@ class TripoGenerator(GeneratorFacade):
     of a semi-regular, multires-friendly surface (TSR.extract_meshes; ops.mesh_subdivide).
     `occlusion` (default None): True (64 directions), an int k in 1 .. 1024 or a tuple (k, max_distance) leaves the ambient
     occlusion of every final mesh against itself on the meshes in `last_meshes` (Mesh.vertex_occlusion, f32 [Nv], 1 = open:
-    TSR.extract_meshes; ops.mesh_occlusion); Mesh.export writes it into .ply and .glb.  The Blender sinks take none."""
+    TSR.extract_meshes; ops.mesh_occlusion); Mesh.export writes it into .ply and .glb.  The Blender sinks take none.
+    `normal_map` (default None): "tangent" or "object" adds a normal map baked from the density field to every mesh a texture
+    is baked for (bake_texture_resolution > 0), at the texture's resolution and over its atlas (TSR.bake_normal_map): the
+    surface detail that simplify removed, carried over to the low-poly mesh.  It is copied to the model (TSR.normal_map) before
+    every generate_mesh; Mesh.export writes the map, and the textured Blender sink wires a tangent-space one to the material."""
 
     def __init__(self, device):
         super().__init__(device, checkpoint_dir=ROOT_DIR + "/checkpoints/", chunk_size=8192, mc_resolution=256,
@@ -61,6 +65,7 @@ class TripoGenerator(GeneratorFacade):
         self.project = None
         self.subdivide = None
         self.occlusion = None
+        self.normal_map = None
 
     def _construct_model(self):
         model = TSR.from_pretrained(self.checkpoint_dir, config_name="config.yaml", weight_name="model.ckpt",
@@ -74,6 +79,7 @@ class TripoGenerator(GeneratorFacade):
         try:
             with torch.no_grad():
                 codes = self.model([input_image], device=self.device)
+            self.model.normal_map = self.normal_map
             self.last_meshes = self.model.extract_mesh(codes, enable_texture=enable_texture, mesh_name=input_name,
                                                        resolution=self.mc_resolution,
                                                        bake_texture=int(self.bake_texture_resolution or 0),

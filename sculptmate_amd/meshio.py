@@ -54,11 +54,13 @@ def write_obj(path, vertices, faces, vertex_colors=None, normals=None):
             np.savetxt(fh, np.repeat(f, 2, axis=1), fmt="f %d//%d %d//%d %d//%d")
 
 
-def write_obj_textured(path, vertices, faces, uvs, texture, normals=None):
+def write_obj_textured(path, vertices, faces, uvs, texture, normals=None, normal_map=None):
     """A mesh with per-corner UVs and a base-colour picture: `v` lines (positions stay shared), one `vt u v` line per face
     corner (uvs f32 [3*Nf, 2], origin bottom-left -- OBJ's own convention), `f v/vt` faces (1-based), and beside the file
     NAME.mtl (`map_Kd NAME.png`) and NAME.png (texture uint8 [H,W,3], row 0 at the top).  normals f32 [Nv, 3] (one per shared
-    vertex): `vn` lines after the `vt` lines and `f v/vt/vn` faces."""
+    vertex): `vn` lines after the `vt` lines and `f v/vt/vn` faces.  texture may be None when only a normal map was baked: no
+    `map_Kd` line and no NAME.png then.  normal_map uint8 [H,W,3] (Mesh.normal_map_image): `map_Bump -bm 1 NAME_normal.png` in the
+    .mtl and NAME_normal.png beside it; None (default): the files are what they were without the keyword."""
     import os
 
     v = np.asarray(vertices, np.float64)
@@ -82,9 +84,17 @@ def write_obj_textured(path, vertices, faces, uvs, texture, normals=None):
         else:
             np.savetxt(fh, np.stack([f, corner, f], 2).reshape(-1, 9) + 1, fmt="f %d/%d/%d %d/%d/%d %d/%d/%d")
     with open(stem + ".mtl", "w") as fh:
-        fh.write("# sculptmate_amd\nnewmtl %s_material\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd %s.png\n" % (name, name))
-    with open(stem + ".png", "wb") as fh:
-        fh.write(encode_png(texture))
+        fh.write("# sculptmate_amd\nnewmtl %s_material\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\n" % name)
+        if texture is not None:
+            fh.write("map_Kd %s.png\n" % name)
+        if normal_map is not None:
+            fh.write("map_Bump -bm 1 %s_normal.png\n" % name)
+    if texture is not None:
+        with open(stem + ".png", "wb") as fh:
+            fh.write(encode_png(texture))
+    if normal_map is not None:
+        with open(stem + "_normal.png", "wb") as fh:
+            fh.write(encode_png(normal_map))
 
 
 def read_obj(path):
@@ -167,13 +177,19 @@ def decode_png(data):
 
 
 def write_glb(path, vertices, faces, vertex_colors=None, normals=None, uvs=None, basecolor_tex=None,
-              normal_tex=None, roughness=None, metallic=None, name="mesh", uv_origin="bottom_left", occlusion=None):
+              normal_tex=None, roughness=None, metallic=None, name="mesh", uv_origin="bottom_left", occlusion=None, tangents=None,
+              extra_images=None):
     """Write one triangle mesh as binary glTF.  `uvs` as SF3D.run_image returns them have their origin at the BOTTOM-left
     of the top-down texture image (the baker samples row y at v = 1 - y/R, texture_baker/common.py:104-142, and the
     reference hands them to Blender unchanged, sf3d/system.py:539-545); glTF puts the origin at the top-left, so
     TEXCOORD_0 is written as (u, 1 - v) unless uv_origin="top_left".  roughness / metallic are SF3D's scalar factors.
     occlusion: f32 [Nv] per vertex (Mesh.vertex_occlusion) -> the custom attribute _OCCLUSION, a float scalar; None (default):
-    the file is what it was without the keyword, byte for byte."""
+    the file is what it was without the keyword, byte for byte.
+    tangents: f32 [Nv, 4] = (T.xyz, w) per vertex (Mesh.corner_tangents on the un-indexed mesh) -> glTF's TANGENT, the frame a
+    viewer decodes normal_tex in; None (default): no such attribute, the same bytes as before.
+    extra_images: {name: uint8 picture} stored as further PNG images that no material refers to, listed by name in the mesh's
+    `extras` ({"images": {name: image index}}): the way an object-space normal map travels, which glTF's normalTexture (tangent
+    space by definition) cannot carry.  None or empty (default): the same bytes as before."""
     if uv_origin not in ("bottom_left", "top_left"):
         raise ValueError("uv_origin must be 'bottom_left' or 'top_left'")
     v = np.ascontiguousarray(vertices, np.float32)
@@ -214,6 +230,11 @@ def write_glb(path, vertices, faces, vertex_colors=None, normals=None, uvs=None,
     if occlusion is not None:
         attributes["_OCCLUSION"] = add_accessor(np.ascontiguousarray(_occlusion_for(occlusion, len(v), "write_glb")), "SCALAR", _FLOAT,
                                                 _ARRAY_BUFFER)
+    if tangents is not None:
+        tng = np.ascontiguousarray(tangents, np.float32)
+        if tng.shape != (len(v), 4):
+            raise ValueError("write_glb: tangents %s must be [Nv, 4] = [%d, 4]" % (tng.shape, len(v)))
+        attributes["TANGENT"] = add_accessor(tng, "VEC4", _FLOAT, _ARRAY_BUFFER)
     indices = add_accessor(idx.astype(np.uint32).reshape(-1), "SCALAR", _UINT32, _ELEMENT_ARRAY_BUFFER)
 
     pbr = {}
@@ -239,8 +260,17 @@ def write_glb(path, vertices, faces, vertex_colors=None, normals=None, uvs=None,
                                                    "mode": 4}]}],
         "materials": [material], "accessors": accessors, "bufferViews": views,
     }
+    if extra_images:
+        named = {}
+        for key in sorted(extra_images):
+            images.append({"bufferView": add_view(encode_png(extra_images[key])), "mimeType": "image/png", "name": key})
+            named[key] = len(images) - 1
+        doc["meshes"][0]["extras"] = {"images": named}
     if textures:
-        doc["textures"], doc["images"] = textures, images
+        doc["textures"] = textures
+    if images:
+        doc["images"] = images
+    if textures:
         doc["samplers"] = [{"magFilter": 9729, "minFilter": 9987, "wrapS": 33071, "wrapT": 33071}]
     while len(blob) % 4:
         blob.append(0)
@@ -255,8 +285,8 @@ def write_glb(path, vertices, faces, vertex_colors=None, normals=None, uvs=None,
 
 
 def read_glb(path, uv_origin="bottom_left"):
-    """Read back what write_glb wrote -> dict(vertices, faces, normals, uvs, vertex_colors, occlusion, basecolor_tex, normal_tex,
-    roughness, metallic); uvs are returned in `uv_origin` convention (see write_glb).  Not a general glTF loader: one
+    """Read back what write_glb wrote -> dict(vertices, faces, normals, tangents, uvs, vertex_colors, occlusion, basecolor_tex,
+    normal_tex, roughness, metallic, extra_images); uvs are returned in `uv_origin` convention (see write_glb).  Not a general glTF loader: one
     buffer, one primitive, tightly packed accessors."""
     with open(path, "rb") as fh:
         data = fh.read()
@@ -297,12 +327,15 @@ def read_glb(path, uv_origin="bottom_left"):
         "vertices": accessor(att["POSITION"]),
         "faces": accessor(prim["indices"]).reshape(-1, 3).astype(np.int64),
         "normals": accessor(att["NORMAL"]) if "NORMAL" in att else None,
+        "tangents": accessor(att["TANGENT"]) if "TANGENT" in att else None,
         "uvs": st,
         "vertex_colors": accessor(att["COLOR_0"]) if "COLOR_0" in att else None,
         "occlusion": accessor(att["_OCCLUSION"]).reshape(-1) if "_OCCLUSION" in att else None,
         "basecolor_tex": texture(pbr.get("baseColorTexture")),
         "normal_tex": texture(mat.get("normalTexture")),
         "roughness": pbr["roughnessFactor"], "metallic": pbr["metallicFactor"],
+        "extra_images": {key: decode_png(view_bytes(doc["images"][i]["bufferView"]))
+                         for key, i in doc["meshes"][0].get("extras", {}).get("images", {}).items()},
     }
 
 

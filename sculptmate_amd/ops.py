@@ -1484,6 +1484,24 @@ def bake_interpolate(attr, rast, face_indices):
     return out
 
 
+def _bake_scene_args(who, planes, v_pos, faces, rast):
+    """The arguments the atlas bakes of a scene code share, checked -> (channel-last planes, v, f, rast, res)."""
+    if not isinstance(planes, ChannelLastPlanes):
+        planes = ChannelLastPlanes(planes)
+    v = _req(v_pos.contiguous() if isinstance(v_pos, torch.Tensor) else v_pos, torch.float32, "v_pos")
+    if not (isinstance(faces, torch.Tensor) and faces.is_cuda):
+        raise SculptError("faces must be a CUDA/HIP tensor (no CPU fallback)")
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise SculptError("%s: faces must be int32 or int64, got %s" % (who, faces.dtype))
+    f = faces.contiguous()
+    r = _req(rast.contiguous() if isinstance(rast, torch.Tensor) else rast, torch.float32, "rast")
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise SculptError("%s: v_pos %s must be [Nv, 3] and faces %s [Nf, 3]" % (who, tuple(v.shape), tuple(f.shape)))
+    if r.ndim != 3 or r.shape[0] != r.shape[1] or r.shape[2] != 4:
+        raise SculptError("%s: rast %s must be [res, res, 4]" % (who, tuple(r.shape)))
+    return planes, v, f, r, r.shape[0]
+
+
 def bake_scene_color(planes, mlp, v_pos, faces, rast, radius=0.87):
     """Colour of a TripoSR scene code at every covered texel of a rasterised atlas, one launch (sculpt_bake_scene_color):
     the position bake_interpolate gives and the colour triplane_query gives there from channel-last planes, bit for bit, with
@@ -1491,26 +1509,75 @@ def bake_scene_color(planes, mlp, v_pos, faces, rast, radius=0.87):
     planes: [3,C,H,W] (converted to channel-last here, once) or a ChannelLastPlanes; v_pos f32 [Nv,3]; faces i32 / i64 [Nf,3]
     indexing v_pos; rast f32 [res,res,4] from bake_rasterize.  -> (color f32 [res,res,3], exactly 0 where not covered;
     mask bool [res,res])."""
-    if not isinstance(planes, ChannelLastPlanes):
-        planes = ChannelLastPlanes(planes)
-    v = _req(v_pos.contiguous() if isinstance(v_pos, torch.Tensor) else v_pos, torch.float32, "v_pos")
-    if not (isinstance(faces, torch.Tensor) and faces.is_cuda):
-        raise SculptError("faces must be a CUDA/HIP tensor (no CPU fallback)")
-    if faces.dtype not in (torch.int32, torch.int64):
-        raise SculptError("bake_scene_color: faces must be int32 or int64, got %s" % faces.dtype)
-    f = faces.contiguous()
-    r = _req(rast.contiguous() if isinstance(rast, torch.Tensor) else rast, torch.float32, "rast")
-    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
-        raise SculptError("bake_scene_color: v_pos %s must be [Nv, 3] and faces %s [Nf, 3]" % (tuple(v.shape), tuple(f.shape)))
-    if r.ndim != 3 or r.shape[0] != r.shape[1] or r.shape[2] != 4:
-        raise SculptError("bake_scene_color: rast %s must be [res, res, 4]" % (tuple(r.shape),))
-    res = r.shape[0]
+    planes, v, f, r, res = _bake_scene_args("bake_scene_color", planes, v_pos, faces, rast)
     color = torch.empty((res, res, 3), dtype=torch.float32, device=r.device)
     mask = torch.empty((res, res), dtype=torch.uint8, device=r.device)
     check(lib.sculpt_bake_scene_color(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(v), v.shape[0],
                                       _ptr(f), int(f.dtype == torch.int64), f.shape[0], _ptr(r), res, float(radius), _ptr(color),
                                       _ptr(mask), _stream()))
     return color, mask.view(torch.bool)
+
+
+def corner_tangents(v_pos, faces, uvs, corner_normals):
+    """Per-corner tangent frames of a UV-mapped mesh (sculpt_corner_tangents, one thread per face): v_pos f32 [Nv,3]; faces
+    i32 / i64 [Nf,3]; uvs f32 [3Nf,2] per face corner, origin bottom-left (Mesh.uvs); corner_normals f32 [3Nf,3] unit normals
+    per face corner -> f32 [3Nf,4] = (T.xyz, w): T the face's dP/du made perpendicular to the corner's normal and normalised,
+    w = +1 / -1 the handedness (cross(N, T) * w points along dP/dv; a chart mirrored in the atlas gets -1).  A face without UV
+    area, or a corner whose normal is parallel to dP/du, gets a unit vector perpendicular to the normal (its cross product with
+    the axis of its smallest component) and w = +1."""
+    v = _req(v_pos.contiguous() if isinstance(v_pos, torch.Tensor) else v_pos, torch.float32, "v_pos")
+    if not (isinstance(faces, torch.Tensor) and faces.is_cuda):
+        raise SculptError("faces must be a CUDA/HIP tensor (no CPU fallback)")
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise SculptError("corner_tangents: faces must be int32 or int64, got %s" % faces.dtype)
+    f = faces.contiguous()
+    uv = _req(uvs.contiguous() if isinstance(uvs, torch.Tensor) else uvs, torch.float32, "uvs")
+    cn = _req(corner_normals.contiguous() if isinstance(corner_normals, torch.Tensor) else corner_normals, torch.float32,
+              "corner_normals")
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise SculptError("corner_tangents: v_pos %s must be [Nv, 3] and faces %s [Nf, 3]" % (tuple(v.shape), tuple(f.shape)))
+    nf = f.shape[0]
+    if tuple(uv.shape) != (3 * nf, 2) or tuple(cn.shape) != (3 * nf, 3):
+        raise SculptError("corner_tangents: uvs %s must be [%d, 2] and corner_normals %s [%d, 3] (three rows per face)"
+                          % (tuple(uv.shape), 3 * nf, tuple(cn.shape), 3 * nf))
+    out = torch.empty((3 * nf, 4), dtype=torch.float32, device=v.device)
+    check(lib.sculpt_corner_tangents(_ptr(v), v.shape[0], _ptr(f), int(f.dtype == torch.int64), nf, _ptr(uv), _ptr(cn), _ptr(out),
+                                     _stream()))
+    return out
+
+
+def bake_scene_normal(planes, mlp, v_pos, faces, rast, radius=0.87, frame=None):
+    """Unit normal of a TripoSR scene code's density field at every covered texel of a rasterised atlas, one launch
+    (sculpt_bake_scene_normal): the position bake_interpolate gives and the normal field_normals gives there, bit for bit, with
+    no position image in between and no decoder work on texels outside the charts.
+    planes, v_pos, faces, rast: as for bake_scene_color.  frame=None: object space, the world normal itself.
+    frame=(corner_normals f32 [3Nf,3], corner_tangents f32 [3Nf,4] from ops.corner_tangents): tangent space in the MikkTSpace /
+    Blender / glTF convention (frames interpolated un-normalised, B = w * cross(N, T)): the stored unit vector (x, y, z) decodes
+    as normalize(x T + y B + z N); the flat (0, 0, 1) where the interpolated frame is singular.
+    -> (normal f32 [res,res,3] in [-1, 1], not encoded, exactly 0 where not covered; mask bool [res,res])."""
+    if isinstance(rast, torch.Tensor) and not rast.is_contiguous():   # a view of a larger image is a caller's mistake, not copied
+        raise SculptError("bake_scene_normal: rast must be contiguous")
+    planes, v, f, r, res = _bake_scene_args("bake_scene_normal", planes, v_pos, faces, rast)
+    cn = ct = None
+    if frame is not None:
+        if not (isinstance(frame, (tuple, list)) and len(frame) == 2):
+            raise SculptError("bake_scene_normal: frame must be None or (corner_normals, corner_tangents)")
+        cn = _req(frame[0], torch.float32, "corner_normals")
+        ct = _req(frame[1], torch.float32, "corner_tangents")
+        nf = f.shape[0]
+        if tuple(cn.shape) != (3 * nf, 3) or tuple(ct.shape) != (3 * nf, 4):
+            raise SculptError("bake_scene_normal: corner_normals %s must be [%d, 3] and corner_tangents %s [%d, 4] (three rows per "
+                              "face)" % (tuple(cn.shape), 3 * nf, tuple(ct.shape), 3 * nf))
+    normal = torch.empty((res, res, 3), dtype=torch.float32, device=r.device)
+    mask = torch.empty((res, res), dtype=torch.uint8, device=r.device)
+    if res == 0:
+        return normal, mask.view(torch.bool)
+    if frame is not None and f.shape[0] == 0:   # no face, no frame rows: nothing is covered, and an empty tensor has no address
+        cn = ct = None
+    check(lib.sculpt_bake_scene_normal(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(v), v.shape[0],
+                                       _ptr(f), int(f.dtype == torch.int64), f.shape[0], _ptr(r), res, float(radius), _ptr(cn),
+                                       _ptr(ct), _ptr(normal), _ptr(mask), _stream()))
+    return normal, mask.view(torch.bool)
 
 
 def resize_aa_bilinear(img_hwc, size):

@@ -38,11 +38,13 @@ def import_obj_blender(verts, faces, vertex_colors=None, name="NewMesh"):
     return new_object
 
 
-def import_textured_blender(verts, faces, uvs, texture_image, name="NewMesh"):
+def import_textured_blender(verts, faces, uvs, texture_image, name="NewMesh", normal_image=None):
     """The sink of a baked mesh (TSR.bake_texture): shared vertices, per-loop UVs (uvs f32 [3*Nf, 2] in face-corner order,
     origin bottom-left as Blender has it) and a material whose image texture feeds the Principled BSDF's Base Color;
     Roughness 1 and IOR 1.00 as the vertex-colour material above sets them.  Blender's UV layers are per loop, so nothing is
-    un-indexed; the loop order must be faces.ravel() for uvs to land on the right corners, which is verified, not assumed."""
+    un-indexed; the loop order must be faces.ravel() for uvs to land on the right corners, which is verified, not assumed.
+    normal_image: a tangent-space normal map (Mesh.normal_map_image of TSR.bake_normal_map) -> a second image texture
+    (colour space Non-Color) -> a Normal Map node -> the BSDF's Normal input; None (default): the node graph without them."""
     import bpy
 
     from ..sf3d.blender_sink import _image
@@ -76,4 +78,10 @@ def import_textured_blender(verts, faces, uvs, texture_image, name="NewMesh"):
     links.new(bsdf.outputs["BSDF"], out_node.inputs["Surface"])
     bsdf.inputs["Roughness"].default_value = 1
     bsdf.inputs["IOR"].default_value = 1.00
+    if normal_image is not None:
+        nm_tex = nodes.new(type="ShaderNodeTexImage")
+        nm_tex.image = _image(bpy, "%s_Normal" % name, normal_image.convert("RGBA"), non_color=True)
+        nm = nodes.new(type="ShaderNodeNormalMap")
+        links.new(nm_tex.outputs["Color"], nm.inputs["Color"])
+        links.new(nm.outputs["Normal"], bsdf.inputs["Normal"])
     return new_object

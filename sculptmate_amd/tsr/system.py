@@ -50,6 +50,13 @@ class Mesh:
         self.texture = texture
         self.vertex_normals = vertex_normals
         self.vertex_occlusion = vertex_occlusion
+        # What TSR.bake_normal_map adds (attributes, not constructor parameters): normal_map f32 [res, res, 3], the unit normal
+        # encoded 0.5 + 0.5 n, row 0 at the top, in the atlas of `uvs`; normal_map_space "tangent" | "object"; and the frame a
+        # tangent-space map is decoded in, per face corner: corner_normals f32 [3*Nf, 3], corner_tangents f32 [3*Nf, 4] = (T, w).
+        self.normal_map = None
+        self.normal_map_space = None
+        self.corner_normals = None
+        self.corner_tangents = None
 
     def keep_components(self, keep) -> "Mesh":
         """The mesh without its small connected components (the "floaters" a thresholded density field leaves around the
@@ -57,18 +64,22 @@ class Mesh:
         fraction of the largest component's faces) -- ops.mesh_keep_components on this mesh's device tensors (a mesh of host
         arrays, as TSR.run returns them, is refused there like any CPU tensor).  Rows keep their order; vertex_colors,
         vertex_normals and vertex_occlusion follow their vertices (vertex_index), the per-corner uvs of a baked mesh their faces (face_index, three
-        rows per face); the texture is untouched (the dropped charts stay in it, unused)."""
+        rows per face); the texture is untouched (the dropped charts stay in it, unused).  A baked normal map
+        (TSR.bake_normal_map) is carried the same way: the map as it is, corner_normals and corner_tangents through face_index."""
         v, f, vi, fi = ops.mesh_keep_components(self.vertices, self.faces, keep)
 
         def rows(x, index):
             return None if x is None else x[index]
 
         corner = None
-        if self.uvs is not None:
+        if self.uvs is not None or self.corner_normals is not None or self.corner_tangents is not None:
             three = torch.arange(3, device=fi.device) if isinstance(fi, torch.Tensor) else np.arange(3)
             corner = (fi[:, None] * 3 + three).reshape(-1)
-        return Mesh(v, f, rows(self.vertex_colors, vi), uvs=rows(self.uvs, corner), texture=self.texture,
-                    vertex_normals=rows(self.vertex_normals, vi), vertex_occlusion=rows(self.vertex_occlusion, vi))
+        out = Mesh(v, f, rows(self.vertex_colors, vi), uvs=rows(self.uvs, corner), texture=self.texture,
+                   vertex_normals=rows(self.vertex_normals, vi), vertex_occlusion=rows(self.vertex_occlusion, vi))
+        out.normal_map, out.normal_map_space = self.normal_map, self.normal_map_space
+        out.corner_normals, out.corner_tangents = rows(self.corner_normals, corner), rows(self.corner_tangents, corner)
+        return out
 
     def simplify(self, simplify) -> "Mesh":
         """The mesh reduced to a target face count by quadric-error edge collapses on the device (ops.mesh_simplify): simplify =
@@ -155,6 +166,16 @@ class Mesh:
             raise ValueError("Mesh.texture_image: this mesh has no baked texture (TSR.bake_texture)")
         return Image.fromarray(float32_to_uint8_np(_host(self.texture).astype(np.float32), dither=False))
 
+    def normal_map_image(self):
+        """The baked normal map as a uint8 RGB PIL picture, as texture_image makes one: floor(256 x) clipped to 0..255, no dither."""
+        from PIL import Image
+
+        from ..sf3d.bake import float32_to_uint8_np
+
+        if self.normal_map is None:
+            raise ValueError("Mesh.normal_map_image: this mesh has no baked normal map (TSR.bake_normal_map)")
+        return Image.fromarray(float32_to_uint8_np(_host(self.normal_map).astype(np.float32), dither=False))
+
     def export(self, path):
         """Write .obj / .ply / .glb by extension (sculptmate_amd/meshio.py), the call upstream users make on the
         trimesh object their extract_mesh returns.  A baked mesh (uvs + texture) goes out textured: .glb with TEXCOORD_0 and the
@@ -162,23 +183,41 @@ class Mesh:
         .obj with `vt` lines, `f v/vt` faces and a .mtl + .png beside the file (positions stay shared).  vertex_normals, when the
         mesh has them, go into every format (glTF NORMAL, `vn`, nx ny nz); the un-indexed .glb gets normals[faces] per corner.
         vertex_occlusion, when set, goes into .ply (a float property `ao`) and .glb (the custom attribute _OCCLUSION; the
-        un-indexed .glb gets ao[faces] per corner); .obj has no slot for it."""
+        un-indexed .glb gets ao[faces] per corner); .obj has no slot for it.
+        A baked normal map (TSR.bake_normal_map; uvs + normal_map, with or without a texture) goes the textured way too.  A
+        tangent-space map: .glb gets normalTexture, NORMAL from corner_normals and TANGENT (VEC4) from corner_tangents, the frame
+        it was baked in; .obj gets `map_Bump -bm 1 NAME_normal.png` in the .mtl and the PNG beside it.  An object-space map is
+        never written as glTF's normalTexture (which is tangent space by definition): the .glb carries it as a further PNG image
+        that no material refers to, named in the mesh's extras ({"images": {"normal_map_object": index}}); the .obj gets the
+        same map_Bump line, to be read as object space by whoever asked for one."""
         from .. import meshio
 
         ext = str(path).rsplit(".", 1)[-1].lower()
         writer = {"obj": meshio.write_obj, "ply": meshio.write_ply, "glb": meshio.write_glb}.get(ext)
         if writer is None:
             raise ValueError(f"unsupported mesh format .{ext} (obj, ply, glb)")
-        if self.uvs is not None and self.texture is not None and ext in ("glb", "obj"):
+        if self.uvs is not None and (self.texture is not None or self.normal_map is not None) and ext in ("glb", "obj"):
             v, f, uv = _host(self.vertices), _host(self.faces), _host(self.uvs)
-            picture = np.asarray(self.texture_image())
+            picture = None if self.texture is None else np.asarray(self.texture_image())
             vn = None if self.vertex_normals is None else _host(self.vertex_normals)
+            bump = None if self.normal_map is None else np.asarray(self.normal_map_image())
             if ext == "glb":
                 extra = {} if self.vertex_occlusion is None else {"occlusion": _host(self.vertex_occlusion)[f.reshape(-1)]}
+                normals = None if vn is None else vn[f.reshape(-1)]
+                if bump is not None:   # the frame the map was baked in, per corner
+                    if self.corner_normals is not None:
+                        normals = _host(self.corner_normals)
+                    if self.normal_map_space == "tangent":
+                        extra["normal_tex"] = bump
+                        if self.corner_tangents is not None:
+                            extra["tangents"] = _host(self.corner_tangents)
+                    else:
+                        extra["extra_images"] = {"normal_map_object": bump}
                 meshio.write_glb(str(path), v[f.reshape(-1)], np.arange(f.size, dtype=np.int64).reshape(-1, 3), uvs=uv,
-                                 basecolor_tex=picture, normals=None if vn is None else vn[f.reshape(-1)], **extra)
+                                 basecolor_tex=picture, normals=normals, **extra)
             else:
-                meshio.write_obj_textured(str(path), v, f, uv, picture, normals=vn)
+                extra = {} if bump is None else {"normal_map": bump}
+                meshio.write_obj_textured(str(path), v, f, uv, picture, normals=vn, **extra)
             return
         extra = {} if self.vertex_occlusion is None or ext == "obj" else {"occlusion": _host(self.vertex_occlusion)}
         writer(str(path), self.vertices, self.faces, vertex_colors=self.vertex_colors, normals=self.vertex_normals, **extra)
@@ -424,6 +463,9 @@ class TSR(KernelEngine):
         self.mesh_sink = None  # callable(verts, faces, colors, name); default: bpy if importable
         self.textured_mesh_sink = None  # callable(verts, faces, uvs, image, name) for baked meshes; default: bpy if importable
         self._unwrapper = None  # the cached BoxProjectionUnwrapper of bake_texture
+        # None | "tangent" | "object": when set, extract_meshes adds a normal map (bake_normal_map) to every mesh it bakes a
+        # texture for, at the texture's resolution, and extract_mesh hands it to the textured sink
+        self.normal_map = None
         # forward(): images per transformer pass.  1 (default): image by image.  > 1: the reference's batched pass
         # (system.py:82-115) over stacked token rows; in the bf16 mode it gives each image the bits of its single-image pass
         # (every GEMM keeps the single-image tile form: encode_images), which is why run() batches by default there
@@ -1083,8 +1125,20 @@ class TSR(KernelEngine):
         if scene_code.ndim == 5 and scene_code.shape[0] == 1:
             scene_code = scene_code[0]
         with torch.no_grad():
-            v = _f32(mesh.vertices, self.device)
-            f = torch.as_tensor(mesh.faces).to(self.device).contiguous()
+            v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper)
+            planes = scene_code if isinstance(scene_code, ops.ChannelLastPlanes) else ops.ChannelLastPlanes(scene_code.to(self.device))
+            color, mask = ops.bake_scene_color(planes, self.decoder, v, f, rast, radius=self.renderer.cfg.radius)
+            color = self._padded(color, mask, res)
+        return Mesh(mesh.vertices, mesh.faces, None, uvs=uv, texture=color)
+
+    def _atlas(self, mesh, res, island_padding, unwrapper, keep_uvs=False):
+        """What the two bakes share: the mesh on the device, its per-corner UVs (the mesh's own with keep_uvs, when it has
+        some; else the unwrapper's) and the atlas rasterised at `res` -> (v f32 [Nv,3], f [Nf,3], uv f32 [3Nf,2], rast)."""
+        v = _f32(mesh.vertices, self.device)
+        f = torch.as_tensor(mesh.faces).to(self.device).contiguous()
+        if keep_uvs and mesh.uvs is not None:
+            uv = _f32(mesh.uvs, self.device)
+        else:
             if unwrapper is None:
                 if self._unwrapper is None:
                     from ..sf3d.unwrap import BoxProjectionUnwrapper
@@ -1093,13 +1147,61 @@ class TSR(KernelEngine):
                 unwrapper = self._unwrapper
             uv, corner = unwrapper(v, ops.vertex_normals(v, f), f, island_padding)
             uv = uv.to(torch.float32)[corner.reshape(-1).long()].contiguous()   # per corner, whatever rows the unwrapper shares
-            rast = ops.bake_rasterize(uv, torch.arange(3 * f.shape[0], device=self.device, dtype=torch.int32).view(-1, 3), res)
+        rast = ops.bake_rasterize(uv, torch.arange(3 * f.shape[0], device=self.device, dtype=torch.int32).view(-1, 3), res)
+        return v, f, uv, rast
+
+    @staticmethod
+    def _padded(image, mask, res):
+        """The padding rule of the SF3D bake: res // 150 rounds of ops.dilate_fill around the charts."""
+        it = res // 150
+        if it > 0:
+            image = ops.dilate_fill(image.permute(2, 0, 1)[None].contiguous(), mask[None, None], iterations=it)[0].permute(1, 2, 0).contiguous()
+        return image
+
+    NORMAL_MAP_FLAT = {"tangent": (0.5, 0.5, 1.0), "object": (0.5, 0.5, 0.5)}
+
+    def bake_normal_map(self, mesh: Mesh, scene_code, resolution=None, space="tangent", island_padding: float = 0.02,
+                        unwrapper=None) -> Mesh:
+        """The last step of a high-to-low workflow: the surface detail of the density field of `scene_code` ([3, C, H, W]),
+        which simplify removed from the geometry, baked into a normal map over `mesh`'s atlas.  Per covered texel the field's
+        outward unit normal (-grad density / |grad density|, ops.field_normals' bits) at the texel's point on the mesh, either as
+        it is (space="object") or in the mesh's own tangent frame (space="tangent", the MikkTSpace / Blender / glTF convention).
+        Atlas: a mesh that has uvs keeps them and `resolution` defaults to its texture's size; a mesh without is unwrapped as
+        bake_texture does and `resolution` defaults to 2048.
+        Stages: ops.vertex_normals * WINDING_OUTWARD -> per-corner normals [faces] -> ops.corner_tangents -> ops.bake_rasterize
+        -> ops.bake_scene_normal (one fused launch) -> encode 0.5 + 0.5 n -> ops.dilate_fill with res // 150 rounds; texels the
+        padding does not reach hold the flat value, (0.5, 0.5, 1) in tangent space and (0.5, 0.5, 0.5) in object space.
+        -> a Mesh with the input's vertices, faces, vertex colours, uvs (or the new ones) and texture, plus normal_map f32
+        [res, res, 3] (row 0 at the top), normal_map_space, corner_normals [3*Nf, 3] and corner_tangents [3*Nf, 4], on the
+        device.  Nothing here waits for the device beyond what the unwrapper reads back."""
+        if space not in self.NORMAL_MAP_FLAT:
+            raise ValueError("TSR.bake_normal_map: space must be 'tangent' or 'object', got %r" % (space,))
+        if self.decoder is None:
+            raise _lib.SculptError("TSR.bake_normal_map: the model has no weights on a device yet (load_state_dict + to(device))")
+        if resolution is None:
+            resolution = mesh.texture.shape[0] if (mesh.uvs is not None and mesh.texture is not None) else 2048
+        res = int(resolution)
+        if res < 1:
+            raise ValueError("TSR.bake_normal_map: resolution must be positive")
+        if not isinstance(scene_code, ops.ChannelLastPlanes) and scene_code.ndim == 5 and scene_code.shape[0] == 1:
+            scene_code = scene_code[0]
+        with torch.no_grad():
+            v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper, keep_uvs=True)
+            corner_n = (self.WINDING_OUTWARD * ops.vertex_normals(v, f))[f.reshape(-1).long()].contiguous()
+            corner_t = ops.corner_tangents(v, f, uv, corner_n)
             planes = scene_code if isinstance(scene_code, ops.ChannelLastPlanes) else ops.ChannelLastPlanes(scene_code.to(self.device))
-            color, mask = ops.bake_scene_color(planes, self.decoder, v, f, rast, radius=self.renderer.cfg.radius)
-            it = res // 150
-            if it > 0:
-                color = ops.dilate_fill(color.permute(2, 0, 1)[None].contiguous(), mask[None, None], iterations=it)[0].permute(1, 2, 0).contiguous()
-        return Mesh(mesh.vertices, mesh.faces, None, uvs=uv, texture=color)
+            n, mask = ops.bake_scene_normal(planes, self.decoder, v, f, rast, radius=self.renderer.cfg.radius,
+                                            frame=(corner_n, corner_t) if space == "tangent" else None)
+            flat = torch.tensor(self.NORMAL_MAP_FLAT[space], dtype=torch.float32, device=self.device)
+            # dilate_fill averages over a texel's neighbourhood as it finds it, so the image is 0 outside the charts going in; an
+            # encoded unit normal has a component above 0, and so has every average of some: a texel that is still (0, 0, 0)
+            # coming out is one the padding did not reach
+            coded = self._padded(torch.where(mask[..., None], 0.5 + 0.5 * n, torch.zeros_like(n)), mask, res)
+            coded = torch.where((coded != 0).any(-1, keepdim=True), coded, flat)
+        out = Mesh(mesh.vertices, mesh.faces, mesh.vertex_colors, uvs=mesh.uvs if mesh.uvs is not None else uv, texture=mesh.texture,
+                   vertex_normals=mesh.vertex_normals, vertex_occlusion=mesh.vertex_occlusion)
+        out.normal_map, out.normal_map_space, out.corner_normals, out.corner_tangents = coded, space, corner_n, corner_t
+        return out
 
     def _projected(self, v_pos, t_pos_idx, planes, threshold, project, resolution):
         """ops.mesh_project with this model's field: target = float32(ln(threshold) - density_bias) (computed in double),
@@ -1147,7 +1249,9 @@ class TSR(KernelEngine):
         density_events: optional (start, stop) torch events recorded around the dense-grid launch (bench.py's live
         per-launch timing of the dominant kernel, on the stream it is launched on).
         bake_texture: with enable_texture, a resolution > 0 bakes a UV texture of that size (TSR.bake_texture) instead of
-        computing vertex colours; 0 (default): vertex colours as before.
+        computing vertex colours; 0 (default): vertex colours as before.  With self.normal_map = "tangent" | "object" (an
+        instance setting, default None) every mesh a texture is baked for also gets a normal map over the same atlas at the same
+        resolution (TSR.bake_normal_map): Mesh.normal_map, normal_map_space, corner_normals, corner_tangents.
         normals: None (default): Mesh.vertex_normals stays unset.  "field": the outward unit normals of the density field at the
         vertices (TSR.field_normals: the gradient of the field whose iso-surface the mesh is).  "faces": area-weighted averages of
         the facet normals (ops.vertex_normals).  Either way f32 [Nv, 3] per shared vertex, also on a baked mesh.
@@ -1252,6 +1356,8 @@ class TSR(KernelEngine):
         vertex normals and the ambient occlusion when asked for."""
         if enable_texture and bake > 0:
             mesh = self.bake_texture(Mesh(v_pos, t_pos_idx), planes, bake)
+            if self.normal_map is not None:   # the same atlas, the texture's resolution
+                mesh = self.bake_normal_map(mesh, planes, space=self.normal_map)
         else:
             color = None
             if enable_texture:
@@ -1378,7 +1484,8 @@ class TSR(KernelEngine):
         """system.py:171-200: same signature (+ bake_texture, normals, occlusion and the geometry options keep_components, smooth,
         simplify, subdivide, project, all described at extract_meshes: the sink receives the final mesh); pushes each mesh into the sink (Blender when
         `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
-        the textured sink (per-loop UVs + an image-texture material).  The sinks take no normals (Blender shades a mesh with
+        the textured sink (per-loop UVs + an image-texture material; with self.normal_map = "tangent" also normal_image=, the
+        baked normal map, which Blender's sink wires through a Normal Map node).  The sinks take no normals (Blender shades a mesh with
         shared vertices smooth by itself) and no occlusion; both stay on the returned meshes."""
         meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture, normals=normals,
                                      keep_components=keep_components, simplify=simplify, smooth=smooth, project=project,
@@ -1388,7 +1495,12 @@ class TSR(KernelEngine):
             if m.texture is not None:
                 tsink = self.textured_mesh_sink or (_default_textured_sink() if self.mesh_sink is None else None)
                 if tsink is not None:
-                    tsink(_host(m.vertices), _host(m.faces), _host(m.uvs), m.texture_image(), mesh_name)
+                    # only a model whose normal_map is set hands the sink a normal image: a five-argument sink stays valid.  An
+                    # object-space map is not one a Normal Map node in its default (tangent) setting can decode: it stays on the mesh
+                    extra = {}
+                    if self.normal_map is not None and m.normal_map is not None and m.normal_map_space == "tangent":
+                        extra["normal_image"] = m.normal_map_image()
+                    tsink(_host(m.vertices), _host(m.faces), _host(m.uvs), m.texture_image(), mesh_name, **extra)
                 elif sink is not None:   # a caller's own four-argument sink: the geometry, without colours
                     sink(_host(m.vertices), _host(m.faces), None, mesh_name)
                 continue
