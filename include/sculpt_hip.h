@@ -1140,6 +1140,27 @@ int sculpt_surface_occlusion(const float *P, const float *N, int64_t n, const in
                              const int32_t *items, const int32_t *start, const double *params_host, double amax, float *ao,
                              sculpt_stream_t stream);
 
+/* Ambient-occlusion bake over a rasterised atlas (csrc/mesh_ray.hip; ops.bake_occlusion, TSR.bake_occlusion_map; DESIGN.md section
+ * 3.3h): sculpt_surface_occlusion at every covered texel of the atlas of a LOW mesh (v_pos [nv][3], faces [nf][3] int32 or int64,
+ * per-vertex normals v_nrm [nv][3]) against the surface S of the grid (GP, GF, gnf, records, items, start, params_host, amax: as
+ * for sculpt_surface_occlusion; records always needed with gnf > 0), in one launch.  Added without a version change (a new symbol
+ * only).  Per texel of rast f32 [res][res][4] = (u, v, w, tri), in fp32 without contraction unless said otherwise:
+ *   1  not covered (tri negative, NaN, >= nf, or a vertex index outside [0, nv): nothing is read through it): ao = 0, mask = 0
+ *   2  p and n: the bits of sculpt_bake_interpolate applied to v_pos and to v_nrm, (a0 u + a1 v) + a2 w per component
+ *   3  a non-finite p or n: ao = NaN, mask = 1
+ *   4  cage > 0: c = cage n, o = p + c, d = -c; the closest hit (t, f) of sculpt_surface_ray_cast's rule over 0 <= t <= 2.  A hit:
+ *      q = fp32(o + t d) (fp64 product and sum, one rounding to fp32); g = cross(b - a, c - a) of f's corners in fp64, negated
+ *      when dot(g, n) < 0; m = fp32(g / sqrt(dot(g, g))) when that length is positive and finite, else n.  No hit, or
+ *      cage == 0: (q, m) = (p, n)
+ *   5  ao = sculpt_surface_occlusion's value at q with normal m under dirs [k][3], offset and max_distance; mask = 1
+ * ao f32 [res][res], mask u8 [res][res].  1 <= k <= 1024, cage >= 0 and finite, offset finite, max_distance >= 0, res <= 32768.
+ * Null, misaligned (rast and records: 16 bytes) or out-of-range arguments are refused with an error code and a message;
+ * res == 0 launches nothing. */
+int sculpt_bake_occlusion(const float *rast, int res, const float *v_pos, size_t nv, const void *faces, int faces_i64, size_t nf,
+                          const float *v_nrm, const float *dirs, int k, float offset, float max_distance, float cage, const float *GP,
+                          const int32_t *GF, int64_t gnf, const float *records, const int32_t *items, const int32_t *start,
+                          const double *params_host, double amax, float *ao, uint8_t *mask, sculpt_stream_t stream);
+
 /* Mesh vertices onto the iso-surface of the density field (csrc/mesh_project.hip; ops.project_to_isosurface, ops.mesh_unfold,
  * ops.mesh_project).  DEVICE pointers, asynchronous on `stream`, no host wait.  Added without a version
  * change (new symbols only).

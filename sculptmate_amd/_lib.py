@@ -226,6 +226,8 @@ SIGNATURES = {
     "sculpt_surface_sample": (_i, [_vp, _vp, _i64, _vp, _i64, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     "sculpt_surface_ray_cast": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "sculpt_surface_occlusion": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp]),
+    "sculpt_bake_occlusion": (_i, [_vp, _i, _vp, _sz, _vp, _i, _sz, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp,
+                                   _vp, _vp]),
     "sculpt_triplane_project": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _f, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_mesh_unfold": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp]),
     "rasterize_cpu": (None, [_vp, _sz, _vp, _sz, ctypes.c_longlong, _vp]),

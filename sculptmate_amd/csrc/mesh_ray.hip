@@ -73,12 +73,35 @@
 // nothing is cut short); open = sum of w_k of the rays that hit nothing, all = sum of every taking-part w_k, both in the order of
 // k in registers; ao = open / all, 1 when all == 0, NaN for a non-finite p or n.  A non-finite origin or direction hits nothing,
 // as in the closest-hit form.  No atomics, no ray is written to memory.
+//
+// ---- the atlas bake (sculpt_bake_occlusion; ops.bake_occlusion, TSR.bake_occlusion_map) ---------------------
+// The occlusion above at every covered texel of a rasterised atlas of a LOW mesh, against the surface S the grid is built over
+// (the low mesh itself, or the high-poly surface it was simplified from), in one launch.  Per texel, fp32 unless said otherwise:
+//   1  coverage and position p: texel_position (bake_texel.h), index guard included; not covered: ao = 0, mask = 0
+//   2  normal n_c = (v_nrm[i0]_c u + v_nrm[i1]_c v) + v_nrm[i2]_c w: sculpt_bake_interpolate's bits on v_nrm
+//   3  a non-finite p or n: ao = NaN, mask = 1
+//   4  snap, only with cage > 0: c = cage n, o = p + c, d = -c; the closest hit of (o, d) over [0, 2] by the rule above.  No hit
+//      (a non-finite o or a zero d included): (q, m) = (p, n).  A hit (t, f): q_k = fp32(o_k + t d_k) (fp64: the product rounded,
+//      the sum rounded, then one rounding to fp32); g = cross(b - a, c - a) of f's corners in fp64, negated when dot(g, n) < 0;
+//      len = sqrt(dot(g, g)); m = fp32(g / len) per component when 0 < len < inf, else m = n.  cage == 0: (q, m) = (p, n).
+//   5  ao = the occlusion above at q with normal m; mask = 1
+// Shape: a tile of 32 x 32 texels is read by workgroups of 256, four rast rows per thread, in the order of the sixteen 8 x 8
+// sub-blocks (a wave reads one sub-block per pass).  Covered finite texels are ranked in that order (block_scan.h) and compacted
+// into LDS as (p, n, where), so the 64 texels of a wave come from at most a few neighbouring 8 x 8 blocks and cast nearly
+// parallel rays from nearby origins -- without keys, sort or permutation.  One texel's 64 rays take a lane milliseconds, so a
+// lane computes ONE texel: a tile is launched as four workgroups (blockIdx.z), each of which reads the whole tile (64 KB of
+// rast, nothing beside the rays), ranks it, keeps ranks 256 z .. 256 z + 255 and ends after the read when it has none.  The
+// first of the four writes the texels no list holds (not covered: 0; not finite: NaN).  The tiling only decides where a texel
+// is computed: its value depends on its own rast row alone.  What this shape costs against a global sorted list on a
+// fragmented atlas (part-filled waves), and what else was measured, is in DESIGN.md 3.3h.
 #pragma clang fp contract(off)
 
 #include <limits.h>
 
 #include "remesh_topo.h"
 #include "surface_grid.h"
+#include "bake_texel.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -236,19 +259,10 @@ ray_kernel(Grid G, const float *__restrict__ O, const float *__restrict__ Dr, lo
     uvo[2 * j + 1] = found ? (float)B.v : 0.0f;
 }
 
-__global__ void __launch_bounds__(kThreads)
-occlusion_kernel(Grid G, const float *__restrict__ P, const float *__restrict__ Nr, long n, const int64_t *__restrict__ order,
-                 const float *__restrict__ dirs, int K, float offset, float max_distance, const float4 *__restrict__ rec, double amax,
-                 float *__restrict__ ao) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const long j = order ? (long)order[i] : i;
-    const float px = P[3 * j], py = P[3 * j + 1], pz = P[3 * j + 2];
-    const float nx = Nr[3 * j], ny = Nr[3 * j + 1], nz = Nr[3 * j + 2];
-    if (!(finite3(px, py, pz) && finite3(nx, ny, nz))) {
-        ao[j] = NAN;
-        return;
-    }
+// The occlusion rule of the header at one FINITE point p with normal n: one copy for the point list and for the atlas bake.
+__device__ __forceinline__ float occlusion_at(const Grid &G, const float4 *__restrict__ rec, float px, float py, float pz, float nx,
+                                              float ny, float nz, const float *__restrict__ dirs, int K, float offset,
+                                              float max_distance, double amax) {
     const float ox = px + offset * nx, oy = py + offset * ny, oz = pz + offset * nz;
     const bool castable = finite3(ox, oy, oz) && G.nf > 0;
     const D3 o = {(double)ox, (double)oy, (double)oz};
@@ -263,7 +277,116 @@ occlusion_kernel(Grid G, const float *__restrict__ P, const float *__restrict__ 
             cast<true, true>(G, rec, o, {(double)dx, (double)dy, (double)dz}, 0.0, (double)max_distance, amax, B);
         if (B.f == INT_MAX) open += w;
     }
-    ao[j] = all == 0.0f ? 1.0f : open / all;
+    return all == 0.0f ? 1.0f : open / all;
+}
+
+__global__ void __launch_bounds__(kThreads)
+occlusion_kernel(Grid G, const float *__restrict__ P, const float *__restrict__ Nr, long n, const int64_t *__restrict__ order,
+                 const float *__restrict__ dirs, int K, float offset, float max_distance, const float4 *__restrict__ rec, double amax,
+                 float *__restrict__ ao) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long j = order ? (long)order[i] : i;
+    const float px = P[3 * j], py = P[3 * j + 1], pz = P[3 * j + 2];
+    const float nx = Nr[3 * j], ny = Nr[3 * j + 1], nz = Nr[3 * j + 2];
+    if (!(finite3(px, py, pz) && finite3(nx, ny, nz))) {
+        ao[j] = NAN;
+        return;
+    }
+    ao[j] = occlusion_at(G, rec, px, py, pz, nx, ny, nz, dirs, K, offset, max_distance, amax);
+}
+
+// Step 4 of the atlas bake: (p, n) -> (q, m) in place.
+__device__ inline void snap_to_surface(const Grid &G, const float4 *__restrict__ rec, float cage, double amax, float (&p)[3], float (&n)[3]) {
+    const float cx = cage * n[0], cy = cage * n[1], cz = cage * n[2];
+    const float ox = p[0] + cx, oy = p[1] + cy, oz = p[2] + cz;
+    const float dx = -cx, dy = -cy, dz = -cz;
+    if (!(finite3(ox, oy, oz) && finite3(dx, dy, dz)) || G.nf <= 0 || (dx == 0.0f && dy == 0.0f && dz == 0.0f)) return;
+    const D3 o = {(double)ox, (double)oy, (double)oz}, d = {(double)dx, (double)dy, (double)dz};
+    Hit B = {INFINITY, INT_MAX, 0.0, 0.0};
+    cast<true, false>(G, rec, o, d, 0.0, 2.0, amax, B);
+    if (B.f == INT_MAX) return;
+    const D3 h = o + B.t * d;
+    const float4 r1 = rec[4 * (long)B.f + 1], r2 = rec[4 * (long)B.f + 2], r3 = rec[4 * (long)B.f + 3];
+    const D3 a = {(double)r1.z, (double)r1.w, (double)r2.x}, b = {(double)r2.y, (double)r2.z, (double)r2.w},
+             c = {(double)r3.x, (double)r3.y, (double)r3.z};
+    D3 g = cross(b - a, c - a);
+    if (dot(g, {(double)n[0], (double)n[1], (double)n[2]}) < 0.0) g = {-g.x, -g.y, -g.z};
+    const double len = sqrt(dot(g, g));
+    p[0] = (float)h.x;
+    p[1] = (float)h.y;
+    p[2] = (float)h.z;
+    if (len > 0.0 && len < (double)INFINITY) {
+        n[0] = (float)(g.x / len);
+        n[1] = (float)(g.y / len);
+        n[2] = (float)(g.z / len);
+    }
+}
+
+constexpr int kTile = 32;                    // texels per side of a workgroup's tile: 16 or 32 (DESIGN.md 3.3h has both measured)
+constexpr int kTileTexels = kTile * kTile;
+constexpr int kPasses = kTileTexels / kThreads;   // passes of the read: every wave takes one 8 x 8 sub-block per pass
+constexpr int kSubs = kTile / 8;                  // sub-blocks per side
+static_assert(kThreads == 256 && (kTile == 16 || kTile == 32), "the sub-block order below is written for 4 waves and 8 x 8 sub-blocks");
+
+// blockIdx.z = which 256 entries of the tile's list this workgroup computes (kPasses workgroups per tile, every one reads the
+// tile: 64 KB of rast against milliseconds of rays); a lane computes at most one texel, so no workgroup outlives one texel's rays.
+template <bool kSnap>
+__global__ void __launch_bounds__(kThreads)
+bake_occlusion_kernel(Grid G, const float4 *__restrict__ rast, int res, const float *__restrict__ v_pos, long nv,
+                      const void *__restrict__ faces, int faces_i64, long nf, const float *__restrict__ v_nrm,
+                      const float *__restrict__ dirs, int K, float offset, float max_distance, float cage,
+                      const float4 *__restrict__ rec, double amax, float *__restrict__ ao, uint8_t *__restrict__ mask) {
+    __shared__ float s_pn[6][kThreads];          // this workgroup's share of the compacted list: p.xyz, n.xyz
+    __shared__ unsigned short s_where[kThreads];  // (y << 5) | x inside the tile
+    __shared__ unsigned s_w[kPasses][kThreads / 64];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile;
+    const unsigned first = blockIdx.z * kThreads;  // the share: ranks first .. first + 255
+    unsigned base = 0u;
+    for (int pass = 0; pass < kPasses; ++pass) {
+        const int sub = pass * 4 + wave;  // the 8 x 8 sub-block, row-major in the tile
+        const int tx = (sub % kSubs) * 8 + (lane & 7), ty = (sub / kSubs) * 8 + (lane >> 3);
+        const int x = x0 + tx, y = y0 + ty;
+        const bool live = x < res && y < res;
+        bool listed = false;
+        float p[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f};
+        if (live) {
+            const long at = (long)y * res + x;
+            const float4 r = rast[at];
+            const Texel t = texel_position(r, v_pos, nv, faces, faces_i64, nf);
+            if (t.covered) {
+                for (int k = 0; k < 3; ++k) {
+                    p[k] = t.x[k];
+                    n[k] = (v_nrm[3 * t.i[0] + k] * r.x + v_nrm[3 * t.i[1] + k] * r.y) + v_nrm[3 * t.i[2] + k] * r.z;
+                }
+                listed = finite3(p[0], p[1], p[2]) && finite3(n[0], n[1], n[2]);
+            }
+            if (blockIdx.z == 0) {  // the texels no list holds are written once, by the tile's first workgroup
+                if (!listed) ao[at] = t.covered ? NAN : 0.0f;
+                mask[at] = t.covered ? 1 : 0;
+            }
+        }
+        const unsigned rank = base + block_flag_rank<kThreads / 64>(listed, s_w[pass]) - first;  // one barrier; a row of s_w per pass
+        if (listed && rank < (unsigned)kThreads) {  // (a rank below `first` wraps to a large number)
+            for (int k = 0; k < 3; ++k) {
+                s_pn[k][rank] = p[k];
+                s_pn[3 + k][rank] = n[k];
+            }
+            s_where[rank] = (unsigned short)((ty << 5) | tx);
+        }
+        for (int w = 0; w < kThreads / 64; ++w) base += s_w[pass][w];
+    }
+    __syncthreads();
+    if (base <= first || (unsigned)tid >= base - first) return;  // base: the tile's count, the same in every thread
+    float p[3] = {s_pn[0][tid], s_pn[1][tid], s_pn[2][tid]}, n[3] = {s_pn[3][tid], s_pn[4][tid], s_pn[5][tid]};
+    const int where = s_where[tid];
+    if (kSnap) snap_to_surface(G, rec, cage, amax, p, n);
+    const long at = (long)(y0 + (where >> 5)) * res + (x0 + (where & 31));
+    // a snapped point is finite (a hit has a finite t inside [0, 2]) unless the sum overflowed: the rule's NaN then
+    ao[at] = finite3(p[0], p[1], p[2]) && finite3(n[0], n[1], n[2])
+                 ? occlusion_at(G, rec, p[0], p[1], p[2], n[0], n[1], n[2], dirs, K, offset, max_distance, amax)
+                 : NAN;
 }
 
 }  // namespace
@@ -307,6 +430,34 @@ int sculpt_surface_occlusion(const float *P, const float *N, int64_t n, const in
     SC_REQUIRE(aligned16(records), "surface_occlusion: records not 16-byte aligned");
     const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
     RMD_LAUNCH(occlusion_kernel, n, G, P, N, (long)n, order, dirs, k, offset, max_distance, reinterpret_cast<const float4 *>(records), amax, ao);
+    return 0;
+}
+
+int sculpt_bake_occlusion(const float *rast, int res, const float *v_pos, size_t nv, const void *faces, int faces_i64, size_t nf,
+                          const float *v_nrm, const float *dirs, int k, float offset, float max_distance, float cage, const float *GP,
+                          const int32_t *GF, int64_t gnf, const float *records, const int32_t *items, const int32_t *start,
+                          const double *params_host, double amax, float *ao, uint8_t *mask, sculpt_stream_t stream) {
+    SC_REQUIRE(res >= 0 && res <= 32768, "bake_occlusion: resolution %d (0 .. 32768)", res);
+    SC_REQUIRE(nv <= (size_t)1 << 40 && nf <= (size_t)1 << 40, "bake_occlusion: mesh too large");
+    SC_REQUIRE(amax >= 0 && amax < INFINITY, "bake_occlusion: amax=%g", amax);  // a NaN fails the comparison
+    SC_REQUIRE(k >= 1 && k <= kMaxDirections, "bake_occlusion: %d directions (1 .. %d)", k, kMaxDirections);
+    SC_REQUIRE(max_distance >= 0, "bake_occlusion: max_distance=%g", (double)max_distance);
+    SC_REQUIRE(isfinite(offset), "bake_occlusion: offset=%g", (double)offset);
+    SC_REQUIRE(cage >= 0 && isfinite(cage), "bake_occlusion: cage=%g (0: no snap, or positive and finite)", (double)cage);
+    if (res == 0) return 0;
+    if (int rc = check_grid("bake_occlusion", GP, GF, gnf, params_host)) return rc;
+    SC_REQUIRE(rast && dirs && ao && mask, "bake_occlusion: null array");
+    SC_REQUIRE(aligned16(rast), "bake_occlusion: rast not 16-byte aligned");
+    SC_REQUIRE(nf == 0 || (v_pos && faces && v_nrm && nv > 0), "bake_occlusion: null mesh");
+    SC_REQUIRE(gnf == 0 || (items && start && records), "bake_occlusion: null grid lists or records");
+    SC_REQUIRE(aligned16(records), "bake_occlusion: records not 16-byte aligned");
+    const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
+    const unsigned tiles = (unsigned)((res + kTile - 1) / kTile);
+    hipLaunchKernelGGL(cage > 0.0f ? bake_occlusion_kernel<true> : bake_occlusion_kernel<false>, dim3(tiles, tiles, kPasses),
+                       dim3(kThreads), 0, as_stream(stream), G,
+                       reinterpret_cast<const float4 *>(rast), res, v_pos, (long)nv, faces, faces_i64, (long)nf, v_nrm, dirs, k, offset,
+                       max_distance, cage, reinterpret_cast<const float4 *>(records), amax, ao, mask);
+    SC_LAUNCH_CHECK();
     return 0;
 }
 

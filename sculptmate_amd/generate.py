@@ -51,7 +51,11 @@ class TripoGenerator(GeneratorFacade):
     `normal_map` (default None): "tangent" or "object" adds a normal map baked from the density field to every mesh a texture
     is baked for (bake_texture_resolution > 0), at the texture's resolution and over its atlas (TSR.bake_normal_map): the
     surface detail that simplify removed, carried over to the low-poly mesh.  It is copied to the model (TSR.normal_map) before
-    every generate_mesh; Mesh.export writes the map, and the textured Blender sink wires a tangent-space one to the material."""
+    every generate_mesh; Mesh.export writes the map, and the textured Blender sink wires a tangent-space one to the material.
+    `occlusion_map` (default None): True, an int k or a tuple (k, max_distance) adds an ambient-occlusion map to every mesh a
+    texture is baked for, over the same atlas at the same resolution, baked against the mesh as it was before simplify
+    (TSR.bake_occlusion_map; copied to the model as TSR.occlusion_map).  Mesh.export writes it (glTF occlusionTexture, `map_Ka`);
+    the Blender sinks take none: the .glb carries it to Blender's own importer."""
 
     def __init__(self, device):
         super().__init__(device, checkpoint_dir=ROOT_DIR + "/checkpoints/", chunk_size=8192, mc_resolution=256,
@@ -66,6 +70,7 @@ class TripoGenerator(GeneratorFacade):
         self.subdivide = None
         self.occlusion = None
         self.normal_map = None
+        self.occlusion_map = None
 
     def _construct_model(self):
         model = TSR.from_pretrained(self.checkpoint_dir, config_name="config.yaml", weight_name="model.ckpt",
@@ -80,6 +85,7 @@ class TripoGenerator(GeneratorFacade):
             with torch.no_grad():
                 codes = self.model([input_image], device=self.device)
             self.model.normal_map = self.normal_map
+            self.model.occlusion_map = self.occlusion_map
             self.last_meshes = self.model.extract_mesh(codes, enable_texture=enable_texture, mesh_name=input_name,
                                                        resolution=self.mc_resolution,
                                                        bake_texture=int(self.bake_texture_resolution or 0),

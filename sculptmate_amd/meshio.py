@@ -54,13 +54,14 @@ def write_obj(path, vertices, faces, vertex_colors=None, normals=None):
             np.savetxt(fh, np.repeat(f, 2, axis=1), fmt="f %d//%d %d//%d %d//%d")
 
 
-def write_obj_textured(path, vertices, faces, uvs, texture, normals=None, normal_map=None):
+def write_obj_textured(path, vertices, faces, uvs, texture, normals=None, normal_map=None, occlusion_map=None):
     """A mesh with per-corner UVs and a base-colour picture: `v` lines (positions stay shared), one `vt u v` line per face
     corner (uvs f32 [3*Nf, 2], origin bottom-left -- OBJ's own convention), `f v/vt` faces (1-based), and beside the file
     NAME.mtl (`map_Kd NAME.png`) and NAME.png (texture uint8 [H,W,3], row 0 at the top).  normals f32 [Nv, 3] (one per shared
     vertex): `vn` lines after the `vt` lines and `f v/vt/vn` faces.  texture may be None when only a normal map was baked: no
     `map_Kd` line and no NAME.png then.  normal_map uint8 [H,W,3] (Mesh.normal_map_image): `map_Bump -bm 1 NAME_normal.png` in the
-    .mtl and NAME_normal.png beside it; None (default): the files are what they were without the keyword."""
+    .mtl and NAME_normal.png beside it; None (default): the files are what they were without the keyword.  occlusion_map uint8
+    [H,W,3] (Mesh.occlusion_map_image): `map_Ka NAME_ao.png` and NAME_ao.png, likewise."""
     import os
 
     v = np.asarray(vertices, np.float64)
@@ -89,12 +90,17 @@ def write_obj_textured(path, vertices, faces, uvs, texture, normals=None, normal
             fh.write("map_Kd %s.png\n" % name)
         if normal_map is not None:
             fh.write("map_Bump -bm 1 %s_normal.png\n" % name)
+        if occlusion_map is not None:
+            fh.write("map_Ka %s_ao.png\n" % name)
     if texture is not None:
         with open(stem + ".png", "wb") as fh:
             fh.write(encode_png(texture))
     if normal_map is not None:
         with open(stem + "_normal.png", "wb") as fh:
             fh.write(encode_png(normal_map))
+    if occlusion_map is not None:
+        with open(stem + "_ao.png", "wb") as fh:
+            fh.write(encode_png(occlusion_map))
 
 
 def read_obj(path):
@@ -177,14 +183,16 @@ def decode_png(data):
 
 
 def write_glb(path, vertices, faces, vertex_colors=None, normals=None, uvs=None, basecolor_tex=None,
-              normal_tex=None, roughness=None, metallic=None, name="mesh", uv_origin="bottom_left", occlusion=None, tangents=None,
-              extra_images=None):
+              normal_tex=None, roughness=None, metallic=None, name="mesh", uv_origin="bottom_left", occlusion=None, occlusion_tex=None,
+              tangents=None, extra_images=None):
     """Write one triangle mesh as binary glTF.  `uvs` as SF3D.run_image returns them have their origin at the BOTTOM-left
     of the top-down texture image (the baker samples row y at v = 1 - y/R, texture_baker/common.py:104-142, and the
     reference hands them to Blender unchanged, sf3d/system.py:539-545); glTF puts the origin at the top-left, so
     TEXCOORD_0 is written as (u, 1 - v) unless uv_origin="top_left".  roughness / metallic are SF3D's scalar factors.
     occlusion: f32 [Nv] per vertex (Mesh.vertex_occlusion) -> the custom attribute _OCCLUSION, a float scalar; None (default):
     the file is what it was without the keyword, byte for byte.
+    occlusion_tex: uint8 picture [H,W,3] (Mesh.occlusion_map_image) -> material.occlusionTexture, in the atlas of TEXCOORD_0; a
+    viewer reads its red channel; the strength is left at glTF's default (1).  None (default): the same bytes as before.
     tangents: f32 [Nv, 4] = (T.xyz, w) per vertex (Mesh.corner_tangents on the un-indexed mesh) -> glTF's TANGENT, the frame a
     viewer decodes normal_tex in; None (default): no such attribute, the same bytes as before.
     extra_images: {name: uint8 picture} stored as further PNG images that no material refers to, listed by name in the mesh's
@@ -250,6 +258,8 @@ def write_glb(path, vertices, faces, vertex_colors=None, normals=None, uvs=None,
         pbr["baseColorTexture"] = add_texture(basecolor_tex)
     if normal_tex is not None:
         material["normalTexture"] = add_texture(normal_tex)
+    if occlusion_tex is not None:
+        material["occlusionTexture"] = add_texture(occlusion_tex)
     pbr["roughnessFactor"] = 1.0 if roughness is None else float(np.asarray(roughness).reshape(-1)[0])
     pbr["metallicFactor"] = 0.0 if metallic is None else float(np.asarray(metallic).reshape(-1)[0])
 
@@ -286,7 +296,7 @@ def write_glb(path, vertices, faces, vertex_colors=None, normals=None, uvs=None,
 
 def read_glb(path, uv_origin="bottom_left"):
     """Read back what write_glb wrote -> dict(vertices, faces, normals, tangents, uvs, vertex_colors, occlusion, basecolor_tex,
-    normal_tex, roughness, metallic, extra_images); uvs are returned in `uv_origin` convention (see write_glb).  Not a general glTF loader: one
+    normal_tex, occlusion_tex, roughness, metallic, extra_images); uvs are returned in `uv_origin` convention (see write_glb).  Not a general glTF loader: one
     buffer, one primitive, tightly packed accessors."""
     with open(path, "rb") as fh:
         data = fh.read()
@@ -333,6 +343,7 @@ def read_glb(path, uv_origin="bottom_left"):
         "occlusion": accessor(att["_OCCLUSION"]).reshape(-1) if "_OCCLUSION" in att else None,
         "basecolor_tex": texture(pbr.get("baseColorTexture")),
         "normal_tex": texture(mat.get("normalTexture")),
+        "occlusion_tex": texture(mat.get("occlusionTexture")),
         "roughness": pbr["roughnessFactor"], "metallic": pbr["metallicFactor"],
         "extra_images": {key: decode_png(view_bytes(doc["images"][i]["bufferView"]))
                          for key, i in doc["meshes"][0].get("extras", {}).get("images", {}).items()},

@@ -1161,6 +1161,153 @@ def _occlusion_composed(index, pts, nrm, dirs, offset, far):
 
 
 # ----------------------------------------------------------------------------------------------
+# ambient occlusion baked over an atlas (csrc/mesh_ray.hip sculpt_bake_occlusion)
+# ----------------------------------------------------------------------------------------------
+OCCLUSION_CAGE = 2.0 ** -6         # the default snap distance of a bake against a source, in longest sides of the source's bounds
+
+
+def _bake_occlusion_args(who, v_pos, faces, normals, rast, occlusion, offset, seed, source, cage):
+    """Rules first (ValueError, nothing launched), then the tensors (SculptError), then the index over S.
+    -> (index or None when res == 0, v, f, nrm, rast, dirs, offset, far, cage)."""
+    k, far = occlusion_rule(occlusion)
+    if offset is not None and not (_is_real(offset) and math.isfinite(float(np.float32(offset)))):
+        raise ValueError("offset must be None or a finite number, got %r" % (offset,))
+    dirs = occlusion_directions(k, seed)      # checks the seed
+    if source is None:
+        if cage is not None:
+            raise ValueError("%s: cage snaps the texels onto a source surface; without a source it must be None, got %r" % (who, cage))
+    else:
+        if not (isinstance(source, (tuple, list)) and len(source) == 2):
+            raise ValueError("%s: source must be None or (vertices, faces), got %r" % (who, type(source).__name__))
+        if cage is not None and not (_is_real(cage) and 0.0 < float(np.float32(cage)) < math.inf):   # a NaN fails the comparison
+            raise ValueError("cage must be None or a finite number > 0, got %r" % (cage,))
+    v = _req(v_pos.contiguous() if isinstance(v_pos, torch.Tensor) else v_pos, torch.float32, "v_pos")
+    if not (isinstance(faces, torch.Tensor) and faces.is_cuda):
+        raise SculptError("faces must be a CUDA/HIP tensor (no CPU fallback)")
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise SculptError("%s: faces must be int32 or int64, got %s" % (who, faces.dtype))
+    f = faces.contiguous()
+    nrm = _req(normals.contiguous() if isinstance(normals, torch.Tensor) else normals, torch.float32, "normals")
+    r = _req(rast.contiguous() if isinstance(rast, torch.Tensor) else rast, torch.float32, "rast")
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or nrm.shape != v.shape:
+        raise SculptError("%s: v_pos %s must be [Nv, 3], normals %s the same and faces %s [Nf, 3]"
+                          % (who, tuple(v.shape), tuple(nrm.shape), tuple(f.shape)))
+    if r.ndim != 3 or r.shape[0] != r.shape[1] or r.shape[2] != 4:
+        raise SculptError("%s: rast %s must be [res, res, 4]" % (who, tuple(r.shape)))
+    P, F = _surface(v, f, who) if source is None else _surface(source[0], source[1], who)
+    if r.shape[0] == 0:
+        return None, v, f, nrm, r, None, 0.0, math.inf, 0.0
+    index = _SurfaceIndex(P, F)
+    if offset is None:
+        offset = OCCLUSION_OFFSET * index.longest_side()
+    if source is None:
+        cage = 0.0
+    elif cage is None:
+        cage = OCCLUSION_CAGE * index.longest_side()
+    far = math.inf if far is None else float(np.float32(far))
+    return index, v, f, nrm, r, torch.from_numpy(dirs).to(v.device), float(np.float32(offset)), far, float(np.float32(cage))
+
+
+def bake_occlusion(v_pos, faces, normals, rast, occlusion=True, offset=None, seed=0, source=None, cage=None):
+    """The ambient occlusion of a surface S at every covered texel of a rasterised atlas of a (low-poly) mesh, in ONE launch
+    (sculpt_bake_occlusion): no position or normal image, no index list, no sort.  v_pos f32 [Nv, 3], faces i32 / i64 [Nf, 3],
+    normals f32 [Nv, 3] per vertex, rast f32 [res, res, 4] from bake_rasterize (device tensors; CPU tensors are refused);
+    occlusion, offset, seed: as for mesh_occlusion (offset=None: 2^-13 of the longest side of S's bounds).
+    source=None: S is the mesh itself, cage must be None.  source=(vertices, faces): S is that surface -- the high-poly mesh the
+    low one was simplified from -- and every texel is first SNAPPED onto it: the closest hit of the ray from p + cage n towards
+    p - cage n replaces p, and that face's unit normal (on n's side) replaces n; a texel whose ray hits nothing keeps (p, n).
+    cage=None: 2^-6 of the longest side of S's bounds; else a finite number > 0, rounded to fp32.
+    -> (ao f32 [res, res] in [0, 1], exactly 0 where not covered, NaN where the interpolated position or normal is not finite;
+    mask bool [res, res], the coverage).  Per texel the rule at the top of csrc/mesh_ray.hip ("the atlas bake"): a property of
+    the inputs alone, bit for bit what bake_occlusion_composed computes (tests/test_gpu_bake_occlusion.py; tests/_aomapref.py
+    restates it in NumPy).  A rast row whose triangle is negative, NaN or out of range, or names a vertex out of range, is not
+    covered.  res == 0 launches nothing."""
+    index, v, f, nrm, r, dirs, offset, far, cage = _bake_occlusion_args("bake_occlusion", v_pos, faces, normals, rast, occlusion,
+                                                                        offset, seed, source, cage)
+    return _bake_occlusion_fused(index, v, f, nrm, r, dirs, offset, far, cage)
+
+
+def _bake_occlusion_fused(index, v, f, nrm, r, dirs, offset, far, cage):
+    res = r.shape[0]
+    ao = torch.empty((res, res), dtype=torch.float32, device=r.device)
+    mask = torch.empty((res, res), dtype=torch.uint8, device=r.device)
+    if index is None:
+        return ao, mask.view(torch.bool)
+    mesh, grid = index._grid_args()
+    records = index.records() if index.F.shape[0] else None
+    check(lib.sculpt_bake_occlusion(_ptr(r), res, _ptr(v), v.shape[0], _ptr(f), int(f.dtype == torch.int64), f.shape[0], _ptr(nrm),
+                                    _ptr(dirs), dirs.shape[0], offset, far, cage, *mesh, _ptr(records), *grid, _ptr(ao), _ptr(mask),
+                                    _stream()))
+    return ao, mask.view(torch.bool)
+
+
+def bake_occlusion_composed(v_pos, faces, normals, rast, occlusion=True, offset=None, seed=0, source=None, cage=None):
+    """bake_occlusion by the pieces that were there before it: bake_interpolate of the positions and of the normals (two
+    [res, res, 3] images), nonzero of the coverage, with a source one closest-hit query (mesh_ray_cast's kernels) and the snap in
+    torch fp64 / fp32 elementwise operations, then the point-list occlusion kernel (a cell sort) and a scatter.  The yardstick the
+    fused kernel is tested (same bits) and timed against (tools/time_occlusion_map.py)."""
+    index, v, f, nrm, r, dirs, offset, far, cage = _bake_occlusion_args("bake_occlusion_composed", v_pos, faces, normals, rast,
+                                                                        occlusion, offset, seed, source, cage)
+    return _bake_occlusion_composed(index, v, f, nrm, r, dirs, offset, far, cage)
+
+
+def _bake_occlusion_composed(index, v, f, nrm, r, dirs, offset, far, cage):
+    res, nv, nf = r.shape[0], v.shape[0], f.shape[0]
+    ao = torch.zeros(res * res, dtype=torch.float32, device=r.device)
+    cov = torch.zeros((res, res), dtype=torch.bool, device=r.device)
+    if index is None or nf == 0 or nv == 0:
+        return ao.view(res, res), cov
+    # the coverage of texel_position, so that bake_interpolate (which guards nothing) reads through checked rows only
+    tri = r[..., 3]
+    cov = (tri >= 0) & (tri < 2147483648.0)                     # a NaN fails both
+    t = torch.where(cov, tri, torch.zeros_like(tri)).to(torch.int64)
+    cov = cov & (t < nf)
+    rows = f[t.clamp(max=nf - 1)].to(torch.int64)               # [res, res, 3]
+    cov = cov & ((rows >= 0) & (rows < nv)).all(-1)
+    clean = torch.where(cov[..., None], r, r.new_tensor([0.0, 0.0, 0.0, -1.0])).contiguous()
+    at = torch.nonzero(cov.reshape(-1))[:, 0]
+    if at.numel() == 0:
+        return ao.view(res, res), cov
+    pts = bake_interpolate(v, clean, f).reshape(-1, 3)[at].contiguous()
+    nr = bake_interpolate(nrm, clean, f).reshape(-1, 3)[at].contiguous()
+    if cage > 0.0 and index.F.shape[0]:
+        pts, nr = _snap_composed(index, pts, nr, cage)
+    ao[at] = index.occlusion(pts, nr, dirs, offset, far)
+    return ao.view(res, res), cov
+
+
+def bake_occlusion_route():
+    """What TSR.bake_occlusion_map calls: bake_occlusion_composed, unless SCULPT_DISTANCE_FORM holds the token `fusedbake`
+    (then bake_occlusion).  The two give the same bits; on the atlas the map is baked over -- the box-projection unwrap of a
+    simplified 256^3 mesh at 2048^2, a fragmented atlas with 12 % coverage -- the composed route's global list fills every wave
+    and is the faster one (tools/time_occlusion_map.py), so it is the default."""
+    return bake_occlusion if _lib.form_has("SCULPT_DISTANCE_FORM", "fusedbake") else bake_occlusion_composed
+
+
+def _snap_composed(index, pts, nr, cage, want_stats=False):
+    """Step 4 of the atlas bake in torch: every operation is one elementwise kernel, so nothing is contracted."""
+    c = nr * cage                                # fp32
+    o, d = pts + c, -c
+    t, face, _ = index.ray_cast(o.contiguous(), d.contiguous(), 0.0, 2.0)
+    hit = face >= 0
+    fi = face.clamp(min=0).long()
+    q = (o.double() + t[:, None] * d.double()).float()          # a product, a sum, one rounding to fp32
+    P, F = index.P.double(), index.F.long()
+    a, b, cc = P[F[fi, 0]], P[F[fi, 1]], P[F[fi, 2]]
+    e1, e2 = b - a, cc - a
+    g = torch.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                     e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
+    nd = nr.double()
+    flip = ((g[:, 0] * nd[:, 0] + g[:, 1] * nd[:, 1]) + g[:, 2] * nd[:, 2]) < 0
+    g = torch.where(flip[:, None], -g, g)
+    ln = torch.sqrt((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2])
+    good = hit & (ln > 0) & (ln < math.inf)
+    m = (g / ln[:, None]).float()
+    out = torch.where(hit[:, None], q, pts).contiguous(), torch.where(good[:, None], m, nr).contiguous()
+    return out + (hit,) if want_stats else out
+
+
+# ----------------------------------------------------------------------------------------------
 # projection onto the field's iso-surface: fused Newton kernel + fold guard (csrc/mesh_project.hip, DESIGN.md 3.1e)
 # ----------------------------------------------------------------------------------------------
 PROJECT_STEPS, PROJECT_CELLS = 8, 1.0   # what project=True means: at most 8 steps inside a trust radius of one lattice cell

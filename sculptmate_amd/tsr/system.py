@@ -57,6 +57,10 @@ class Mesh:
         self.normal_map_space = None
         self.corner_normals = None
         self.corner_tangents = None
+        # What TSR.bake_occlusion_map adds (attributes too): occlusion_map f32 [res, res], ambient occlusion in the atlas of `uvs`,
+        # row 0 at the top, 1 = open, 0 = occluded; occlusion_map_rule = (k, max_distance), the rule it was baked under.
+        self.occlusion_map = None
+        self.occlusion_map_rule = None
 
     def keep_components(self, keep) -> "Mesh":
         """The mesh without its small connected components (the "floaters" a thresholded density field leaves around the
@@ -65,7 +69,8 @@ class Mesh:
         arrays, as TSR.run returns them, is refused there like any CPU tensor).  Rows keep their order; vertex_colors,
         vertex_normals and vertex_occlusion follow their vertices (vertex_index), the per-corner uvs of a baked mesh their faces (face_index, three
         rows per face); the texture is untouched (the dropped charts stay in it, unused).  A baked normal map
-        (TSR.bake_normal_map) is carried the same way: the map as it is, corner_normals and corner_tangents through face_index."""
+        (TSR.bake_normal_map) is carried the same way: the map as it is, corner_normals and corner_tangents through face_index; a
+        baked occlusion map (TSR.bake_occlusion_map) as it is, with its rule."""
         v, f, vi, fi = ops.mesh_keep_components(self.vertices, self.faces, keep)
 
         def rows(x, index):
@@ -79,6 +84,7 @@ class Mesh:
                    vertex_normals=rows(self.vertex_normals, vi), vertex_occlusion=rows(self.vertex_occlusion, vi))
         out.normal_map, out.normal_map_space = self.normal_map, self.normal_map_space
         out.corner_normals, out.corner_tangents = rows(self.corner_normals, corner), rows(self.corner_tangents, corner)
+        out.occlusion_map, out.occlusion_map_rule = self.occlusion_map, self.occlusion_map_rule
         return out
 
     def simplify(self, simplify) -> "Mesh":
@@ -176,6 +182,18 @@ class Mesh:
             raise ValueError("Mesh.normal_map_image: this mesh has no baked normal map (TSR.bake_normal_map)")
         return Image.fromarray(float32_to_uint8_np(_host(self.normal_map).astype(np.float32), dither=False))
 
+    def occlusion_map_image(self):
+        """The baked occlusion map as a uint8 RGB PIL picture with three equal channels (glTF reads the red one), quantised as
+        normal_map_image quantises: floor(256 x) clipped to 0..255, no dither."""
+        from PIL import Image
+
+        from ..sf3d.bake import float32_to_uint8_np
+
+        if self.occlusion_map is None:
+            raise ValueError("Mesh.occlusion_map_image: this mesh has no baked occlusion map (TSR.bake_occlusion_map)")
+        grey = _host(self.occlusion_map).astype(np.float32)
+        return Image.fromarray(float32_to_uint8_np(np.repeat(grey[:, :, None], 3, axis=2), dither=False))
+
     def export(self, path):
         """Write .obj / .ply / .glb by extension (sculptmate_amd/meshio.py), the call upstream users make on the
         trimesh object their extract_mesh returns.  A baked mesh (uvs + texture) goes out textured: .glb with TEXCOORD_0 and the
@@ -189,20 +207,27 @@ class Mesh:
         it was baked in; .obj gets `map_Bump -bm 1 NAME_normal.png` in the .mtl and the PNG beside it.  An object-space map is
         never written as glTF's normalTexture (which is tangent space by definition): the .glb carries it as a further PNG image
         that no material refers to, named in the mesh's extras ({"images": {"normal_map_object": index}}); the .obj gets the
-        same map_Bump line, to be read as object space by whoever asked for one."""
+        same map_Bump line, to be read as object space by whoever asked for one.
+        A baked occlusion map (TSR.bake_occlusion_map; uvs + occlusion_map, with or without a texture or normal map) goes the
+        textured way as well: .glb gets material.occlusionTexture (three equal channels; glTF reads the red one, strength at its
+        default of 1), .obj gets `map_Ka NAME_ao.png` in the .mtl and the PNG beside it."""
         from .. import meshio
 
         ext = str(path).rsplit(".", 1)[-1].lower()
         writer = {"obj": meshio.write_obj, "ply": meshio.write_ply, "glb": meshio.write_glb}.get(ext)
         if writer is None:
             raise ValueError(f"unsupported mesh format .{ext} (obj, ply, glb)")
-        if self.uvs is not None and (self.texture is not None or self.normal_map is not None) and ext in ("glb", "obj"):
+        baked = self.texture is not None or self.normal_map is not None or self.occlusion_map is not None
+        if self.uvs is not None and baked and ext in ("glb", "obj"):
             v, f, uv = _host(self.vertices), _host(self.faces), _host(self.uvs)
             picture = None if self.texture is None else np.asarray(self.texture_image())
             vn = None if self.vertex_normals is None else _host(self.vertex_normals)
             bump = None if self.normal_map is None else np.asarray(self.normal_map_image())
+            shade = None if self.occlusion_map is None else np.asarray(self.occlusion_map_image())
             if ext == "glb":
                 extra = {} if self.vertex_occlusion is None else {"occlusion": _host(self.vertex_occlusion)[f.reshape(-1)]}
+                if shade is not None:
+                    extra["occlusion_tex"] = shade
                 normals = None if vn is None else vn[f.reshape(-1)]
                 if bump is not None:   # the frame the map was baked in, per corner
                     if self.corner_normals is not None:
@@ -217,6 +242,8 @@ class Mesh:
                                  basecolor_tex=picture, normals=normals, **extra)
             else:
                 extra = {} if bump is None else {"normal_map": bump}
+                if shade is not None:
+                    extra["occlusion_map"] = shade
                 meshio.write_obj_textured(str(path), v, f, uv, picture, normals=vn, **extra)
             return
         extra = {} if self.vertex_occlusion is None or ext == "obj" else {"occlusion": _host(self.vertex_occlusion)}
@@ -466,6 +493,12 @@ class TSR(KernelEngine):
         # None | "tangent" | "object": when set, extract_meshes adds a normal map (bake_normal_map) to every mesh it bakes a
         # texture for, at the texture's resolution, and extract_mesh hands it to the textured sink
         self.normal_map = None
+        # None | what ops.occlusion_rule accepts (True, k, (k, max_distance)): when set, extract_meshes adds an ambient-occlusion
+        # map (bake_occlusion_map) to every mesh it bakes a texture for, over the texture's atlas at its resolution, against the
+        # mesh as it entered simplify (when simplify is given; else against itself).  _reshaped leaves that mesh in
+        # _occlusion_source for _textured, which takes it out again.
+        self.occlusion_map = None
+        self._occlusion_source = None
         # forward(): images per transformer pass.  1 (default): image by image.  > 1: the reference's batched pass
         # (system.py:82-115) over stacked token rows; in the bf16 mode it gives each image the bits of its single-image pass
         # (every GEMM keeps the single-image tile form: encode_images), which is why run() batches by default there
@@ -1160,6 +1193,11 @@ class TSR(KernelEngine):
 
     NORMAL_MAP_FLAT = {"tangent": (0.5, 0.5, 1.0), "object": (0.5, 0.5, 0.5)}
 
+    # class-level defaults of the two attributes __init__ sets: extract_meshes reads them on every call, also on an object that
+    # was made without __init__
+    occlusion_map = None
+    _occlusion_source = None
+
     def bake_normal_map(self, mesh: Mesh, scene_code, resolution=None, space="tangent", island_padding: float = 0.02,
                         unwrapper=None) -> Mesh:
         """The last step of a high-to-low workflow: the surface detail of the density field of `scene_code` ([3, C, H, W]),
@@ -1201,6 +1239,60 @@ class TSR(KernelEngine):
         out = Mesh(mesh.vertices, mesh.faces, mesh.vertex_colors, uvs=mesh.uvs if mesh.uvs is not None else uv, texture=mesh.texture,
                    vertex_normals=mesh.vertex_normals, vertex_occlusion=mesh.vertex_occlusion)
         out.normal_map, out.normal_map_space, out.corner_normals, out.corner_tangents = coded, space, corner_n, corner_t
+        out.occlusion_map, out.occlusion_map_rule = mesh.occlusion_map, mesh.occlusion_map_rule
+        return out
+
+    def bake_occlusion_map(self, mesh: Mesh, source=None, resolution=None, occlusion=True, cage=None, seed=0,
+                           island_padding: float = 0.02, unwrapper=None) -> Mesh:
+        """What a baker pairs with the normal map: the ambient occlusion of the HIGH-poly surface in the low-poly mesh's atlas,
+        glTF's material.occlusionTexture.  Per covered texel the cosine-weighted share of `occlusion`'s directions (True: 64, k,
+        or (k, max_distance): ops.occlusion_rule; `seed` rotates the set) along which a ray leaves without hitting the surface
+        (ops.bake_occlusion_route: the composed route by default, the one fused launch of ops.bake_occlusion with
+        SCULPT_DISTANCE_FORM=fusedbake; the same bits, the composed one is faster on these atlases).  source=None: the mesh against itself, cage must be None.  source=a Mesh (the
+        mesh as it was before simplify): every texel's point is first snapped onto that surface along the low mesh's normal,
+        within `cage` on either side (None: 2^-6 of the longest side of the source's bounds), and takes that surface's facet
+        normal; a texel whose ray finds nothing keeps its own point and normal.
+        Atlas: as bake_normal_map -- a mesh that has uvs keeps them and `resolution` defaults to its texture's (else its normal
+        map's) size; a mesh without is unwrapped as bake_texture does and `resolution` defaults to 2048.  Needs a device, no weights.
+        Stages: ops.vertex_normals * WINDING_OUTWARD -> ops.bake_rasterize -> the occlusion bake -> ops.dilate_fill with
+        res // 150 rounds (on the value + 1, since 0 is a legitimate occlusion: what is still 0 afterwards was not reached);
+        texels the padding does not reach, and texels whose point or normal is not finite, hold 1.0 (open).
+        -> a Mesh with everything the input carried plus occlusion_map f32 [res, res] (row 0 at the top, 1 = open) and
+        occlusion_map_rule = (k, max_distance), on the device."""
+        rule = ops.occlusion_rule(occlusion)   # a ValueError before anything is launched
+        if self.device is None:
+            raise _lib.SculptError("TSR.bake_occlusion_map: the model is on no device yet (to(device))")
+        if source is not None and not isinstance(source, Mesh):
+            raise ValueError("TSR.bake_occlusion_map: source must be a Mesh or None, got %r" % (type(source).__name__,))
+        if source is None and cage is not None:
+            raise ValueError("TSR.bake_occlusion_map: cage snaps the texels onto a source; without a source it must be None")
+        if resolution is None:
+            if mesh.uvs is not None and mesh.texture is not None:
+                resolution = mesh.texture.shape[0]
+            elif mesh.uvs is not None and mesh.normal_map is not None:
+                resolution = mesh.normal_map.shape[0]
+            else:
+                resolution = 2048
+        res = int(resolution)
+        if res < 1:
+            raise ValueError("TSR.bake_occlusion_map: resolution must be positive")
+        with torch.no_grad():
+            v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper, keep_uvs=True)
+            normals = (self.WINDING_OUTWARD * ops.vertex_normals(v, f)).contiguous()
+            src = None
+            if source is not None:
+                src = (_f32(source.vertices, self.device), torch.as_tensor(source.faces).to(self.device).contiguous())
+            ao, mask = ops.bake_occlusion_route()(v, f, normals, rast, occlusion=rule, seed=seed, source=src, cage=cage)
+            valid = mask & torch.isfinite(ao)
+            shifted = torch.where(valid, ao + 1.0, torch.zeros_like(ao))
+            spread = self._padded(shifted[..., None].expand(res, res, 3), valid, res)[..., 0]
+            padded = torch.where(spread != 0, (spread - 1.0).clamp(0.0, 1.0), torch.ones_like(ao))
+            ao_map = torch.where(valid, ao, torch.where(mask, torch.ones_like(ao), padded)).contiguous()
+        out = Mesh(mesh.vertices, mesh.faces, mesh.vertex_colors, uvs=mesh.uvs if mesh.uvs is not None else uv, texture=mesh.texture,
+                   vertex_normals=mesh.vertex_normals, vertex_occlusion=mesh.vertex_occlusion)
+        out.normal_map, out.normal_map_space = mesh.normal_map, mesh.normal_map_space
+        out.corner_normals, out.corner_tangents = mesh.corner_normals, mesh.corner_tangents
+        out.occlusion_map, out.occlusion_map_rule = ao_map, rule
         return out
 
     def _projected(self, v_pos, t_pos_idx, planes, threshold, project, resolution):
@@ -1251,7 +1343,10 @@ class TSR(KernelEngine):
         bake_texture: with enable_texture, a resolution > 0 bakes a UV texture of that size (TSR.bake_texture) instead of
         computing vertex colours; 0 (default): vertex colours as before.  With self.normal_map = "tangent" | "object" (an
         instance setting, default None) every mesh a texture is baked for also gets a normal map over the same atlas at the same
-        resolution (TSR.bake_normal_map): Mesh.normal_map, normal_map_space, corner_normals, corner_tangents.
+        resolution (TSR.bake_normal_map): Mesh.normal_map, normal_map_space, corner_normals, corner_tangents.  With
+        self.occlusion_map = True | k | (k, max_distance) (an instance setting too, default None: nothing more is launched) it also
+        gets an ambient-occlusion map over that atlas (TSR.bake_occlusion_map: Mesh.occlusion_map, occlusion_map_rule), baked
+        against the mesh as it entered simplify when simplify is given, else against itself.
         normals: None (default): Mesh.vertex_normals stays unset.  "field": the outward unit normals of the density field at the
         vertices (TSR.field_normals: the gradient of the field whose iso-surface the mesh is).  "faces": area-weighted averages of
         the facet normals (ops.vertex_normals).  Either way f32 [Nv, 3] per shared vertex, also on a baked mesh.
@@ -1287,6 +1382,8 @@ class TSR(KernelEngine):
             raise ValueError("normals must be None, 'field' or 'faces', got %r" % (normals,))
         if occlusion is not None:
             ops.occlusion_rule(occlusion)   # a ValueError before anything is launched
+        if self.occlusion_map is not None:
+            ops.occlusion_rule(self.occlusion_map)
         geometry = dict(keep_components=keep_components, simplify=simplify, smooth=smooth, project=project, subdivide=subdivide)
         self._check_geometry(threshold, **geometry)   # a ValueError before anything is launched
         bake = int(bake_texture) if enable_texture else 0
@@ -1337,7 +1434,10 @@ class TSR(KernelEngine):
             v_pos, t_pos_idx = ops.mesh_keep_components(v_pos, t_pos_idx, keep_components)[:2]
         if smooth is not None:
             v_pos = ops.mesh_smooth(v_pos, t_pos_idx, smooth)
+        self._occlusion_source = None
         if simplify is not None:
+            if self.occlusion_map is not None:   # the high-poly surface the occlusion map is baked against (_textured)
+                self._occlusion_source = Mesh(v_pos, t_pos_idx)
             v_pos, t_pos_idx = ops.mesh_simplify(v_pos, t_pos_idx, simplify)[:2]
         if subdivide is not None:
             v_pos, t_pos_idx = ops.mesh_subdivide(v_pos, t_pos_idx, subdivide)[:2]
@@ -1354,10 +1454,13 @@ class TSR(KernelEngine):
     def _textured(self, v_pos, t_pos_idx, planes, enable_texture, bake, normals=None, occlusion=None):
         """The appearance half of extract_meshes: nothing, vertex colours (system.py:189-193) or a baked texture; and the
         vertex normals and the ambient occlusion when asked for."""
+        source, self._occlusion_source = self._occlusion_source, None
         if enable_texture and bake > 0:
             mesh = self.bake_texture(Mesh(v_pos, t_pos_idx), planes, bake)
             if self.normal_map is not None:   # the same atlas, the texture's resolution
                 mesh = self.bake_normal_map(mesh, planes, space=self.normal_map)
+            if self.occlusion_map is not None:   # the same atlas and resolution too; against the mesh as it entered simplify
+                mesh = self.bake_occlusion_map(mesh, source=source, occlusion=self.occlusion_map)
         else:
             color = None
             if enable_texture:
