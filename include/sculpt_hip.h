@@ -1161,6 +1161,36 @@ int sculpt_bake_occlusion(const float *rast, int res, const float *v_pos, size_t
                           const int32_t *GF, int64_t gnf, const float *records, const int32_t *items, const int32_t *start,
                           const double *params_host, double amax, float *ao, uint8_t *mask, sculpt_stream_t stream);
 
+/* Ray-cast views of a mesh with its attributes and baked maps (csrc/mesh_ray.hip; ops.mesh_render, Mesh.render, TSR.render_mesh;
+ * DESIGN.md section 3.3i): every ray of rays_o / rays_d f32 [n_images][height][width][3] followed to its closest hit by
+ * sculpt_surface_ray_cast's rule over [0, +inf] and the hit shaded, in one launch.  Added without a version change (a new symbol and
+ * two structs only).  The grid arguments are those of sculpt_surface_occlusion (records always needed with gnf > 0).  The per-ray
+ * rule -- weights, map lookup, albedo, geometric and shading normal, occlusion, the value and the background of every pass -- is
+ * the header comment "the mesh render" of csrc/mesh_ray.hip.
+ * material: DEVICE pointers, each null when the mesh has none.  uvs [3 gnf][2] per corner; texture [res][res][3], normal_map
+ * [res][res][3], occlusion_map [res][res] (row 0 at the top; each needs uvs and its side in 1 .. 32768); corner_normals [3 gnf][3]
+ * and corner_tangents [3 gnf][4] (both or neither; given: the normal map is in tangent space, else in object space);
+ * vertex_colors [nv][vertex_color_channels] (3 or 4), vertex_normals [nv][3], vertex_occlusion [nv].  The caller vouches for the row
+ * counts; map indices are clamped by the rule.
+ * out: DEVICE pointers of the pictures to write, null for a pass that is not wanted (at least one is): color, shaded, normal
+ * f32 [n][3]; rgba f32 [n][4]; opacity, depth, occlusion f32 [n]; face int32 [n]; n = n_images height width.
+ * light: HOST pointer to the unit direction towards the light, or null for a headlight (-d / |d| per ray).  outward: the sign the
+ * geometric normal is multiplied by.  height == 1 takes the rays as one row per image.  Null, misaligned (records: 16 bytes) or
+ * out-of-range arguments are refused with an error code and a message; no rays launches nothing. */
+typedef struct sculpt_render_material {
+    const float *uvs, *texture, *normal_map, *corner_normals, *corner_tangents, *occlusion_map, *vertex_colors, *vertex_normals,
+        *vertex_occlusion;
+    int texture_res, normal_map_res, occlusion_map_res, vertex_color_channels;
+} sculpt_render_material;
+typedef struct sculpt_render_outputs {
+    float *color, *shaded, *opacity, *rgba, *depth, *normal, *occlusion;
+    int32_t *face;
+} sculpt_render_outputs;
+int sculpt_surface_render(const float *rays_o, const float *rays_d, int64_t n_images, int64_t height, int64_t width, const float *GP,
+                          const int32_t *GF, int64_t gnf, const float *records, const int32_t *items, const int32_t *start,
+                          const double *params_host, double amax, const sculpt_render_material *material, float ambient,
+                          const float *light, double outward, const sculpt_render_outputs *out, sculpt_stream_t stream);
+
 /* Mesh vertices onto the iso-surface of the density field (csrc/mesh_project.hip; ops.project_to_isosurface, ops.mesh_unfold,
  * ops.mesh_project).  DEVICE pointers, asynchronous on `stream`, no host wait.  Added without a version
  * change (new symbols only).

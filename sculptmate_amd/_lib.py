@@ -228,6 +228,7 @@ SIGNATURES = {
     "sculpt_surface_occlusion": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp]),
     "sculpt_bake_occlusion": (_i, [_vp, _i, _vp, _sz, _vp, _i, _sz, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp,
                                    _vp, _vp]),
+    "sculpt_surface_render": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _f, _vp, _d, _vp, _vp]),
     "sculpt_triplane_project": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _f, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_mesh_unfold": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp]),
     "rasterize_cpu": (None, [_vp, _sz, _vp, _sz, ctypes.c_longlong, _vp]),
@@ -248,6 +249,19 @@ class RmdTopo(ctypes.Structure):
     """sculpt_rmd_topo_t (include/sculpt_hip.h)."""
     _fields_ = [("F", _vp), ("skeys", _vp), ("she", _vp), ("es", _vp), ("fe", _vp), ("vfs", _vp), ("vfc", _vp), ("bnd", _vp),
                 ("nf", _i64), ("nv", _i64), ("ne", _i64)]
+
+
+class RenderMaterial(ctypes.Structure):
+    """sculpt_render_material (include/sculpt_hip.h)."""
+    _fields_ = [("uvs", _vp), ("texture", _vp), ("normal_map", _vp), ("corner_normals", _vp), ("corner_tangents", _vp),
+                ("occlusion_map", _vp), ("vertex_colors", _vp), ("vertex_normals", _vp), ("vertex_occlusion", _vp),
+                ("texture_res", _i), ("normal_map_res", _i), ("occlusion_map_res", _i), ("vertex_color_channels", _i)]
+
+
+class RenderOutputs(ctypes.Structure):
+    """sculpt_render_outputs (include/sculpt_hip.h)."""
+    _fields_ = [("color", _vp), ("shaded", _vp), ("opacity", _vp), ("rgba", _vp), ("depth", _vp), ("normal", _vp), ("occlusion", _vp),
+                ("face", _vp)]
 
 
 class LnFold(ctypes.Structure):

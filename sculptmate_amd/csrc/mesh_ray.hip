@@ -94,6 +94,43 @@
 // first of the four writes the texels no list holds (not covered: 0; not finite: NaN).  The tiling only decides where a texel
 // is computed: its value depends on its own rast row alone.  What this shape costs against a global sorted list on a
 // fragmented atlas (part-filled waves), and what else was measured, is in DESIGN.md 3.3h.
+// ---- the mesh render (sculpt_surface_render; ops.mesh_render, Mesh.render, TSR.render_mesh) ------------------
+// A camera ray followed to the surface and the hit shaded from the mesh's own attributes and baked maps, in one launch: the
+// inverse of every convention the bakes define.  Per ray (o, d), fp32 without contraction unless said otherwise, every operation
+// rounded on its own; tests/_meshrenderref.py restates it in NumPy and ops.mesh_render_composed in torch, bit for bit.
+//   hit      (t, f, u, v): the closest hit of (o, d) over [0, +inf] by the rule above (cast<true, false>).  A miss, a zero
+//            direction and a non-finite origin or direction give the BACKGROUND of every pass; depth is NaN for the non-finite.
+//   weights  w1 = fp32(u), w2 = fp32(v), w0 = (1 - w1) - w2.  An attribute with rows A0, A1, A2 -- per vertex through faces[f], or
+//            per corner at 3f, 3f+1, 3f+2 -- is (A0 w0 + A1 w1) + A2 w2 (bake_interpolate_kernel's expression order).
+//   lookup   of a map of side R (row 0 at the top, C channels) at the interpolated uvs (U, V): X = U R, Y = (1 - V) R -- the
+//            inverse of the rasteriser's rule (csrc/baker.hip: texel (x, y) holds the value at (x / R, 1 - y / R)), so X is a texel
+//            INDEX, not a texel-centre coordinate.  A non-finite X or Y (every non-finite U or V gives one): X = Y = 0.
+//            x0 = floor(X), fx = X - x0, columns x0 and x0 + 1 each clamped to [0, R - 1] AFTER the fraction is taken; y likewise.
+//            value = ((T00 (1 - fx) + T10 fx) (1 - fy)) + ((T01 (1 - fx) + T11 fx) fy), Txy the texel of column x., row y.
+//            Nothing is read through an unclamped index.
+//   albedo   the first the mesh has of: the texture looked up; vertex_colors interpolated (the first three channels); 0.8.
+//   g        the geometric normal: cross(b - a, c - a) of f's corners in fp64, each component times `outward`, len =
+//            sqrt(dot(g, g)); fp32(g / len) per component when 0 < len < inf, else (0, 0, 0).
+//   unit(x)  s = (x.x x.x + x.y x.y) + x.z x.z, len = sqrt(s) (correctly rounded), x / len per component; applies only when
+//            0 < len < inf.
+//   n        the shading normal, the first of these that applies:
+//            1  an object-space normal map: unit(m), m = 2 lookup - 1
+//            2  a tangent-space normal map: N, T the corner normals and tangents interpolated un-normalised (csrc/bake_normal.hip),
+//               B = s cross(N, T) with s = corner_tangents[3f].w, m = 2 lookup - 1, unit((m.x T + m.y B) + m.z N) per component --
+//               the inverse that bake's header promises
+//            3  unit(vertex_normals interpolated)
+//            4  g
+//   a        the occlusion map looked up, else vertex_occlusion interpolated, else 1.
+//   passes   color = albedo [1, 1, 1]; opacity = 1 [0]; rgba = (albedo, 1) [0, 0, 0, 0]; depth = fp32(t) [0; NaN]; normal = n
+//            [0, 0, 0]; occlusion = a [1]; face = f [-1]; shaded = albedo k [1, 1, 1] with
+//            k = ambient a + (1 - ambient) max(0, (n.x l.x + n.y l.y) + n.z l.z), the max 0 unless the dot is > 0, and l the
+//            caller's unit light direction or, without one, the headlight unit(-d) ((0, 0, 0) when that does not apply).
+// Shape: a wave owns an 8 x 8 pixel tile (rays [n_images][H][W][3]; one row of rays, H == 1, is cut into runs of 64 instead), so
+// its 64 rays enter the grid through neighbouring cells and walk the same layers; a workgroup is 2 x 2 such tiles, one ray per
+// lane from start to end, idle lanes at the image's edges.  A tile whose rays all miss the grid's bounds ends at the clip (B1).
+// The material comes by value as nullable pointers and sizes, so which maps exist is a wave-uniform branch on kernel arguments,
+// and it is read only in the second phase, after the walk has its final hit.  Only the passes whose pointer is given are
+// computed and stored.  The value of a ray depends on that ray alone.
 #pragma clang fp contract(off)
 
 #include <limits.h>
@@ -389,6 +426,201 @@ bake_occlusion_kernel(Grid G, const float4 *__restrict__ rast, int res, const fl
                  : NAN;
 }
 
+// ---- the mesh render ---------------------------------------------------------------------------------------------------------
+struct Material {
+    const float *uvs;             // [3 nf][2] per corner, or null
+    const float *texture;         // [tex_res][tex_res][3]
+    const float *normal_map;      // [nmap_res][nmap_res][3]
+    const float *corner_n;        // [3 nf][3]: a tangent-space normal map's frame (null: the map is in object space)
+    const float *corner_t;        // [3 nf][4]
+    const float *occlusion_map;   // [occ_res][occ_res]
+    const float *v_col;           // [nv][col_stride]
+    const float *v_nrm;           // [nv][3]
+    const float *v_occ;           // [nv]
+    int tex_res, nmap_res, occ_res, col_stride;
+};
+
+struct RenderOut {
+    float *color, *shaded, *opacity, *rgba, *depth, *normal, *occlusion;
+    int32_t *face;
+};
+
+// the lookup of the header: kC channels of a map of side R at (U, V)
+template <int kC>
+__device__ inline void map_lookup(const float *__restrict__ map, int R, float U, float V, float (&out)[kC]) {
+    const float Rf = (float)R;
+    float X = U * Rf, Y = (1.0f - V) * Rf;
+    if (!(isfinite(X) && isfinite(Y))) X = Y = 0.0f;
+    const float xf = floorf(X), yf = floorf(Y), top = (float)(R - 1);
+    const float fx = X - xf, fy = Y - yf, gx = 1.0f - fx, gy = 1.0f - fy;
+    const long x0 = (long)fminf(fmaxf(xf, 0.0f), top), x1 = (long)fminf(fmaxf(xf + 1.0f, 0.0f), top);
+    const long y0 = (long)fminf(fmaxf(yf, 0.0f), top), y1 = (long)fminf(fmaxf(yf + 1.0f, 0.0f), top);
+    const float *r0 = map + (y0 * R) * kC, *r1 = map + (y1 * R) * kC;
+#pragma unroll
+    for (int c = 0; c < kC; ++c)
+        out[c] = ((r0[x0 * kC + c] * gx + r0[x1 * kC + c] * fx) * gy) + ((r1[x0 * kC + c] * gx + r1[x1 * kC + c] * fx) * fy);
+}
+
+// unit(x) of the header in place; false (x untouched) when it does not apply
+__device__ inline bool unit3(float (&x)[3]) {
+    const float s = (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2];
+    const float len = (float)sqrt((double)s);   // the correctly rounded fp32 root
+    if (!(len > 0.0f && len < INFINITY)) return false;
+    x[0] = x[0] / len;
+    x[1] = x[1] / len;
+    x[2] = x[2] / len;
+    return true;
+}
+
+// the second phase: everything after the hit (B.f a face) is final
+__device__ void shade_hit(const Grid &G, const float4 *__restrict__ rec, const Material &M, const RenderOut &O, const Hit &B,
+                          float dx, float dy, float dz, float ambient, int has_light, float lx, float ly, float lz, double outward,
+                          long at) {
+    const long f = B.f;
+    const float w1 = (float)B.u, w2 = (float)B.v, w0 = (1.0f - w1) - w2;
+    const long i0 = G.F[3 * f], i1 = G.F[3 * f + 1], i2 = G.F[3 * f + 2];
+    float U = 0.0f, V = 0.0f;
+    if (M.uvs) {
+        const float *q = M.uvs + 6 * f;
+        U = (q[0] * w0 + q[2] * w1) + q[4] * w2;
+        V = (q[1] * w0 + q[3] * w1) + q[5] * w2;
+    }
+    const bool want_albedo = O.color || O.shaded || O.rgba;
+    float albedo[3] = {0.8f, 0.8f, 0.8f};
+    if (want_albedo) {
+        if (M.texture) {
+            map_lookup<3>(M.texture, M.tex_res, U, V, albedo);
+        } else if (M.v_col) {
+            const long s = M.col_stride;
+            for (int c = 0; c < 3; ++c) albedo[c] = (M.v_col[s * i0 + c] * w0 + M.v_col[s * i1 + c] * w1) + M.v_col[s * i2 + c] * w2;
+        }
+    }
+    float n[3] = {0.0f, 0.0f, 0.0f};
+    if (O.normal || O.shaded) {
+        bool done = false;
+        if (M.normal_map) {
+            float m[3];
+            map_lookup<3>(M.normal_map, M.nmap_res, U, V, m);
+            for (int c = 0; c < 3; ++c) m[c] = 2.0f * m[c] - 1.0f;
+            if (M.corner_n) {
+                const float *cn = M.corner_n + 9 * f, *ct = M.corner_t + 12 * f;
+                float N[3], T[3];
+                for (int c = 0; c < 3; ++c) {
+                    N[c] = (cn[c] * w0 + cn[3 + c] * w1) + cn[6 + c] * w2;
+                    T[c] = (ct[c] * w0 + ct[4 + c] * w1) + ct[8 + c] * w2;
+                }
+                const float s = ct[3];
+                const float Bv[3] = {s * (N[1] * T[2] - N[2] * T[1]), s * (N[2] * T[0] - N[0] * T[2]), s * (N[0] * T[1] - N[1] * T[0])};
+                for (int c = 0; c < 3; ++c) n[c] = (m[0] * T[c] + m[1] * Bv[c]) + m[2] * N[c];
+            } else {
+                for (int c = 0; c < 3; ++c) n[c] = m[c];
+            }
+            done = unit3(n);
+        }
+        if (!done && M.v_nrm) {
+            for (int c = 0; c < 3; ++c) n[c] = (M.v_nrm[3 * i0 + c] * w0 + M.v_nrm[3 * i1 + c] * w1) + M.v_nrm[3 * i2 + c] * w2;
+            done = unit3(n);
+        }
+        if (!done) {
+            const float4 r1 = rec[4 * f + 1], r2 = rec[4 * f + 2], r3 = rec[4 * f + 3];
+            const D3 a = {(double)r1.z, (double)r1.w, (double)r2.x}, b = {(double)r2.y, (double)r2.z, (double)r2.w},
+                     c = {(double)r3.x, (double)r3.y, (double)r3.z};
+            D3 g = cross(b - a, c - a);
+            g = {g.x * outward, g.y * outward, g.z * outward};
+            const double len = sqrt(dot(g, g));
+            const bool ok = len > 0.0 && len < (double)INFINITY;
+            n[0] = ok ? (float)(g.x / len) : 0.0f;
+            n[1] = ok ? (float)(g.y / len) : 0.0f;
+            n[2] = ok ? (float)(g.z / len) : 0.0f;
+        }
+    }
+    float ao = 1.0f;
+    if (O.occlusion || O.shaded) {
+        if (M.occlusion_map) {
+            float v[1];
+            map_lookup<1>(M.occlusion_map, M.occ_res, U, V, v);
+            ao = v[0];
+        } else if (M.v_occ) {
+            ao = (M.v_occ[i0] * w0 + M.v_occ[i1] * w1) + M.v_occ[i2] * w2;
+        }
+    }
+    if (O.color) {
+        O.color[3 * at] = albedo[0];
+        O.color[3 * at + 1] = albedo[1];
+        O.color[3 * at + 2] = albedo[2];
+    }
+    if (O.shaded) {
+        float l[3] = {lx, ly, lz};
+        if (!has_light) {
+            l[0] = -dx;
+            l[1] = -dy;
+            l[2] = -dz;
+            if (!unit3(l)) l[0] = l[1] = l[2] = 0.0f;
+        }
+        const float ndl = (n[0] * l[0] + n[1] * l[1]) + n[2] * l[2];
+        const float k = ambient * ao + (1.0f - ambient) * (ndl > 0.0f ? ndl : 0.0f);
+        O.shaded[3 * at] = albedo[0] * k;
+        O.shaded[3 * at + 1] = albedo[1] * k;
+        O.shaded[3 * at + 2] = albedo[2] * k;
+    }
+    if (O.opacity) O.opacity[at] = 1.0f;
+    if (O.rgba) {
+        O.rgba[4 * at] = albedo[0];
+        O.rgba[4 * at + 1] = albedo[1];
+        O.rgba[4 * at + 2] = albedo[2];
+        O.rgba[4 * at + 3] = 1.0f;
+    }
+    if (O.depth) O.depth[at] = (float)B.t;
+    if (O.normal) {
+        O.normal[3 * at] = n[0];
+        O.normal[3 * at + 1] = n[1];
+        O.normal[3 * at + 2] = n[2];
+    }
+    if (O.occlusion) O.occlusion[at] = ao;
+    if (O.face) O.face[at] = (int32_t)f;
+}
+
+__device__ inline void store_background(const RenderOut &O, long at, bool finite) {
+    if (O.color) O.color[3 * at] = O.color[3 * at + 1] = O.color[3 * at + 2] = 1.0f;
+    if (O.shaded) O.shaded[3 * at] = O.shaded[3 * at + 1] = O.shaded[3 * at + 2] = 1.0f;
+    if (O.opacity) O.opacity[at] = 0.0f;
+    if (O.rgba) O.rgba[4 * at] = O.rgba[4 * at + 1] = O.rgba[4 * at + 2] = O.rgba[4 * at + 3] = 0.0f;
+    if (O.depth) O.depth[at] = finite ? 0.0f : NAN;
+    if (O.normal) O.normal[3 * at] = O.normal[3 * at + 1] = O.normal[3 * at + 2] = 0.0f;
+    if (O.occlusion) O.occlusion[at] = 1.0f;
+    if (O.face) O.face[at] = -1;
+}
+
+// kRow: H == 1, a wave takes 64 consecutive rays; else a wave takes an 8 x 8 tile and the workgroup 16 x 16 pixels
+template <bool kRow>
+__global__ void __launch_bounds__(kThreads)
+render_kernel(Grid G, const float *__restrict__ Ro, const float *__restrict__ Rd, int H, long W, const float4 *__restrict__ rec,
+              double amax, Material M, RenderOut O, float ambient, int has_light, float lx, float ly, float lz, double outward) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    long x;
+    int y;
+    if (kRow) {
+        x = (long)blockIdx.x * kThreads + tid;
+        y = 0;
+    } else {
+        x = (long)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+        y = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+    }
+    if (x >= W || y >= H) return;
+    const long at = ((long)blockIdx.z * H + y) * W + x;
+    const float ox = Ro[3 * at], oy = Ro[3 * at + 1], oz = Ro[3 * at + 2];
+    const float dx = Rd[3 * at], dy = Rd[3 * at + 1], dz = Rd[3 * at + 2];
+    Hit B = {INFINITY, INT_MAX, 0.0, 0.0};
+    const bool finite = finite3(ox, oy, oz) && finite3(dx, dy, dz);
+    if (finite && G.nf > 0 && !(dx == 0.0f && dy == 0.0f && dz == 0.0f))
+        cast<true, false>(G, rec, {(double)ox, (double)oy, (double)oz}, {(double)dx, (double)dy, (double)dz}, 0.0, (double)INFINITY, amax, B);
+    if (B.f == INT_MAX) {
+        store_background(O, at, finite);
+        return;
+    }
+    shade_hit(G, rec, M, O, B, dx, dy, dz, ambient, has_light, lx, ly, lz, outward, at);
+}
+
 }  // namespace
 
 extern "C" {
@@ -457,6 +689,54 @@ int sculpt_bake_occlusion(const float *rast, int res, const float *v_pos, size_t
                        dim3(kThreads), 0, as_stream(stream), G,
                        reinterpret_cast<const float4 *>(rast), res, v_pos, (long)nv, faces, faces_i64, (long)nf, v_nrm, dirs, k, offset,
                        max_distance, cage, reinterpret_cast<const float4 *>(records), amax, ao, mask);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+int sculpt_surface_render(const float *rays_o, const float *rays_d, int64_t n_images, int64_t height, int64_t width, const float *GP,
+                          const int32_t *GF, int64_t gnf, const float *records, const int32_t *items, const int32_t *start,
+                          const double *params_host, double amax, const sculpt_render_material *material, float ambient,
+                          const float *light, double outward, const sculpt_render_outputs *out, sculpt_stream_t stream) {
+    SC_REQUIRE(n_images >= 0 && height >= 0 && width >= 0, "surface_render: negative image size");
+    SC_REQUIRE(n_images <= 65535 && height <= ((int64_t)1 << 19) && width < ((int64_t)1 << 31),
+               "surface_render: %lld images of %lld x %lld are too many or too large", (long long)n_images, (long long)height, (long long)width);
+    SC_REQUIRE((double)n_images * (double)height * (double)width * 4.0 < 0x1p40, "surface_render: too many rays");
+    SC_REQUIRE(amax >= 0 && amax < INFINITY, "surface_render: amax=%g", amax);  // a NaN fails the comparison
+    SC_REQUIRE(isfinite(ambient) && isfinite(outward), "surface_render: ambient=%g, outward=%g", (double)ambient, outward);
+    SC_REQUIRE(material && out, "surface_render: null material or outputs");
+    if (n_images == 0 || height == 0 || width == 0) return 0;
+    if (int rc = check_grid("surface_render", GP, GF, gnf, params_host)) return rc;
+    SC_REQUIRE(rays_o && rays_d, "surface_render: null rays");
+    SC_REQUIRE(gnf == 0 || (items && start && records), "surface_render: null grid lists or records");
+    SC_REQUIRE(aligned16(records), "surface_render: records not 16-byte aligned");
+    SC_REQUIRE(out->color || out->shaded || out->opacity || out->rgba || out->depth || out->normal || out->occlusion || out->face,
+               "surface_render: no pass asked for");
+    const sculpt_render_material &m = *material;
+    SC_REQUIRE(!m.texture || (m.uvs && m.texture_res >= 1), "surface_render: a texture needs uvs and a side >= 1");
+    SC_REQUIRE(!m.normal_map || (m.uvs && m.normal_map_res >= 1), "surface_render: a normal map needs uvs and a side >= 1");
+    SC_REQUIRE(!m.occlusion_map || (m.uvs && m.occlusion_map_res >= 1), "surface_render: an occlusion map needs uvs and a side >= 1");
+    SC_REQUIRE(m.texture_res <= 32768 && m.normal_map_res <= 32768 && m.occlusion_map_res <= 32768, "surface_render: map side above 32768");
+    SC_REQUIRE((m.corner_normals == nullptr) == (m.corner_tangents == nullptr),
+               "surface_render: corner_normals and corner_tangents come together (both or neither)");
+    SC_REQUIRE(!m.corner_normals || m.normal_map, "surface_render: a tangent frame without a normal map");
+    SC_REQUIRE(!m.vertex_colors || m.vertex_color_channels == 3 || m.vertex_color_channels == 4, "surface_render: vertex colours of %d channels",
+               m.vertex_color_channels);
+    const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
+    const Material M = {m.uvs, m.texture, m.normal_map, m.corner_normals, m.corner_tangents, m.occlusion_map, m.vertex_colors,
+                        m.vertex_normals, m.vertex_occlusion, m.texture_res, m.normal_map_res, m.occlusion_map_res, m.vertex_color_channels};
+    const RenderOut O = {out->color, out->shaded, out->opacity, out->rgba, out->depth, out->normal, out->occlusion, out->face};
+    const float zero[3] = {0.0f, 0.0f, 0.0f};
+    const float *l = light ? light : zero;
+    const float4 *rec = reinterpret_cast<const float4 *>(records);
+    if (height == 1) {
+        hipLaunchKernelGGL(render_kernel<true>, dim3((unsigned)((width + kThreads - 1) / kThreads), 1, (unsigned)n_images), dim3(kThreads), 0,
+                           as_stream(stream), G, rays_o, rays_d, 1, (long)width, rec, amax, M, O, ambient, light ? 1 : 0, l[0], l[1], l[2],
+                           outward);
+    } else {
+        hipLaunchKernelGGL(render_kernel<false>, dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16), (unsigned)n_images),
+                           dim3(kThreads), 0, as_stream(stream), G, rays_o, rays_d, (int)height, (long)width, rec, amax, M, O, ambient,
+                           light ? 1 : 0, l[0], l[1], l[2], outward);
+    }
     SC_LAUNCH_CHECK();
     return 0;
 }

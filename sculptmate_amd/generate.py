@@ -115,3 +115,19 @@ class TripoGenerator(GeneratorFacade):
         except Exception as err:
             print(self.run_error_tag, err)
             return STATUS_FAILED
+
+    def render_mesh_views(self, mesh, n_views=8, passes=None, **camera):
+        """Turntable previews of a finished mesh -- one of last_meshes, with whatever was baked onto it -- under render_views'
+        cameras (TSR.render_mesh; camera: elevation_deg, camera_distance, fovy_deg, height, width, and ambient / light): a list
+        of n_views PIL pictures of the "shaded" pass, or with `passes` a list of n_views dicts {pass: PIL picture}.  Failures
+        follow render_views' convention: STATUS_NOT_LOADED without a model, STATUS_FAILED (message printed) when rendering fails."""
+        if self.model is None:
+            return STATUS_NOT_LOADED
+        try:
+            if passes is not None:
+                return self.model.render_mesh(mesh, n_views=n_views, passes=passes, return_type="pil", **camera)
+            views = self.model.render_mesh(mesh, n_views=n_views, passes=("shaded",), return_type="pil", **camera)
+            return [v["shaded"] for v in views]
+        except Exception as err:
+            print(self.run_error_tag, err)
+            return STATUS_FAILED

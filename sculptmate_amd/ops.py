@@ -1308,6 +1308,337 @@ def _snap_composed(index, pts, nr, cage, want_stats=False):
 
 
 # ----------------------------------------------------------------------------------------------
+# ray-cast views of a mesh with its attributes and baked maps (csrc/mesh_ray.hip sculpt_surface_render)
+# ----------------------------------------------------------------------------------------------
+MESH_RENDER_GREY = 0.8             # the albedo of a mesh that has neither a texture nor vertex colours
+MESH_RENDER_AMBIENT = 0.3
+# pass -> (trailing shape, dtype, background)
+MESH_RENDER_PASSES = {"color": ((3,), torch.float32, 1.0), "shaded": ((3,), torch.float32, 1.0), "opacity": ((), torch.float32, 0.0),
+                      "rgba": ((4,), torch.float32, 0.0), "depth": ((), torch.float32, 0.0), "normal": ((3,), torch.float32, 0.0),
+                      "occlusion": ((), torch.float32, 1.0), "face": ((), torch.int32, -1)}
+_MESH_RENDER_MAPS = ("texture", "normal_map", "occlusion_map")
+
+
+def mesh_render_passes(passes):
+    """-> the passes of mesh_render as a tuple without repeats, in the order given; ValueError when there is none or one is
+    unknown (tsr/passes.py check_passes, over this renderer's names)."""
+    if isinstance(passes, str):
+        passes = (passes,)
+    passes = tuple(dict.fromkeys(passes))
+    unknown = [p for p in passes if p not in MESH_RENDER_PASSES]
+    if unknown:
+        raise ValueError("unknown pass %s (any of %s)" % (unknown, ", ".join(MESH_RENDER_PASSES)))
+    if not passes:
+        raise ValueError("passes is empty (any of %s)" % ", ".join(MESH_RENDER_PASSES))
+    return passes
+
+
+def mesh_render_light(light):
+    """`light` of mesh_render -> None (a headlight) or the unit direction towards the light as np.float32 [3], normalised in
+    fp64 and rounded once; anything but None or three finite numbers that are not all 0 is a ValueError."""
+    if light is None:
+        return None
+    try:
+        l = np.asarray(light, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        l = np.zeros(0)
+    n = float(np.sqrt((l * l).sum())) if l.shape == (3,) and np.isfinite(l).all() else 0.0
+    if not (0.0 < n < math.inf):
+        raise ValueError("light must be None (a headlight) or a finite direction (x, y, z) that is not 0, got %r" % (light,))
+    return (l / n).astype(np.float32)
+
+
+class _RenderJob:
+    """The checked arguments of one mesh_render call: rules first (ValueError, nothing launched), then the tensors (SculptError),
+    then one index over the mesh, shared by all views."""
+
+    def __init__(self, who, rays_o, rays_d, vertices, faces, passes, material, ambient, light, outward):
+        self.passes = mesh_render_passes(passes)
+        m = dict(material)
+        space = m.pop("normal_map_space", None)
+        if space not in (None, "tangent", "object"):
+            raise ValueError("%s: normal_map_space must be 'tangent' or 'object', got %r" % (who, space))
+        if m.get("normal_map") is not None:
+            if space is None:
+                raise ValueError("%s: a normal_map needs its normal_map_space ('tangent' or 'object')" % who)
+            if space == "tangent" and (m.get("corner_normals") is None or m.get("corner_tangents") is None):
+                raise ValueError("%s: a tangent-space normal_map needs the frame it was baked in (corner_normals and corner_tangents)" % who)
+        for name in _MESH_RENDER_MAPS:
+            if m.get(name) is not None and m.get("uvs") is None:
+                raise ValueError("%s: a %s needs the uvs it is looked up through" % (who, name))
+        if not (_is_real(ambient) and math.isfinite(float(np.float32(ambient)))):
+            raise ValueError("ambient must be a finite number, got %r" % (ambient,))
+        if not (_is_real(outward) and math.isfinite(float(outward))):
+            raise ValueError("outward must be a finite number (+1 or -1), got %r" % (outward,))
+        self.ambient, self.outward, self.light = float(np.float32(ambient)), float(outward), mesh_render_light(light)
+        for r, name in ((rays_o, "rays_o"), (rays_d, "rays_d")):
+            if not (isinstance(r, torch.Tensor) and r.is_cuda):
+                raise SculptError("%s: %s must be a CUDA/HIP tensor (no CPU fallback)" % (who, name))
+            if r.dim() not in (2, 4) or r.shape[-1] != 3 or not r.dtype.is_floating_point:
+                raise SculptError("%s: %s must be float [N, 3] or [n_images, H, W, 3], got %s %s" % (who, name, r.dtype, tuple(r.shape)))
+        if rays_o.shape != rays_d.shape:
+            raise SculptError("%s: rays_o %s and rays_d %s differ in shape" % (who, tuple(rays_o.shape), tuple(rays_d.shape)))
+        self.o, self.d = rays_o.detach().to(torch.float32).contiguous(), rays_d.detach().to(torch.float32).contiguous()
+        self.lead = tuple(self.o.shape[:-1])
+        self.images = (1, 1, self.lead[0]) if len(self.lead) == 1 else self.lead       # (n_images, H, W)
+        P, F = _surface(vertices, faces, who)
+        nv, nf = P.shape[0], F.shape[0]
+        if m.get("normal_map") is None or space == "object":     # the frame belongs to a tangent-space map
+            m["corner_normals"] = m["corner_tangents"] = None
+        rows = {"uvs": (3 * nf, 2), "corner_normals": (3 * nf, 3), "corner_tangents": (3 * nf, 4), "vertex_normals": (nv, 3),
+                "vertex_occlusion": (nv,)}
+        self.m = {}
+        for name in ("uvs", "texture", "normal_map", "corner_normals", "corner_tangents", "occlusion_map", "vertex_colors",
+                     "vertex_normals", "vertex_occlusion"):
+            t = m.pop(name, None)
+            if t is not None:
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype.is_floating_point):
+                    raise SculptError("%s: %s must be a float CUDA/HIP tensor (no CPU fallback)" % (who, name))
+                t = t.detach().to(torch.float32).contiguous()
+                shape = tuple(t.shape)
+                if name in rows:
+                    ok = shape == rows[name]
+                elif name == "vertex_colors":
+                    ok = len(shape) == 2 and shape[0] == nv and shape[1] in (3, 4)
+                else:
+                    ok = shape[:2] == (shape[0], shape[0]) and 1 <= shape[0] <= 32768 and shape[2:] == ((3,) if name != "occlusion_map" else ())
+                if not ok:
+                    raise SculptError("%s: %s has shape %s for a mesh of %d vertices and %d faces" % (who, name, shape, nv, nf))
+            self.m[name] = t
+        if m:
+            raise TypeError("%s: unknown material entries %s" % (who, sorted(m)))
+        self.n = self.o.shape[0] if len(self.lead) == 1 else self.lead[0] * self.lead[1] * self.lead[2]
+        self.index = _SurfaceIndex(P, F) if self.n else None
+
+    def empty(self):
+        dev = self.o.device
+        return {p: torch.empty(self.lead + MESH_RENDER_PASSES[p][0], dtype=MESH_RENDER_PASSES[p][1], device=dev) for p in self.passes}
+
+
+def _render_material(uvs, texture, normal_map, normal_map_space, corner_normals, corner_tangents, occlusion_map, vertex_colors,
+              vertex_normals, vertex_occlusion):
+    return dict(uvs=uvs, texture=texture, normal_map=normal_map, normal_map_space=normal_map_space, corner_normals=corner_normals,
+                corner_tangents=corner_tangents, occlusion_map=occlusion_map, vertex_colors=vertex_colors,
+                vertex_normals=vertex_normals, vertex_occlusion=vertex_occlusion)
+
+
+def mesh_render(rays_o, rays_d, vertices, faces, passes=("color",), uvs=None, texture=None, normal_map=None, normal_map_space=None,
+                corner_normals=None, corner_tangents=None, occlusion_map=None, vertex_colors=None, vertex_normals=None,
+                vertex_occlusion=None, ambient=MESH_RENDER_AMBIENT, light=None, outward=1.0):
+    """Pictures of a triangle mesh with its attributes and baked maps, ray cast on the device in ONE launch after the index build
+    (sculpt_surface_render): every ray is followed to its closest hit by mesh_ray_cast's rule and the hit is shaded.  rays_o,
+    rays_d float [n_images, H, W, 3] (a wave takes an 8 x 8 tile of an image) or [N, 3] (one row); vertices float [Nv, 3], faces
+    int32 / int64 [Nf, 3]; all device tensors, CPU tensors are refused.  The material, every entry optional: uvs f32 [3*Nf, 2]
+    per corner (origin bottom-left), texture [R, R, 3], normal_map [R, R, 3] holding 0.5 + 0.5 n with normal_map_space "object" or
+    "tangent" (then with corner_normals [3*Nf, 3] and corner_tangents [3*Nf, 4], the frame it was baked in), occlusion_map [R, R]
+    (row 0 of a map at the top; each map needs uvs), vertex_colors [Nv, 3 or 4], vertex_normals [Nv, 3], vertex_occlusion [Nv].
+    -> {pass: tensor} with the rays' leading shape; passes (value [background]):
+      "color"     [..., 3]  the albedo, unlit: texture, else vertex colours, else MESH_RENDER_GREY [1, 1, 1]
+      "shaded"    [..., 3]  albedo * (ambient * a + (1 - ambient) * max(0, n . l)); l = -d / |d| (a headlight) or the unit
+                            vector of `light`, the direction towards a fixed light [1, 1, 1]
+      "opacity"   [...]     1 [0]
+      "rgba"      [..., 4]  colour and opacity, premultiplied [0, 0, 0, 0]
+      "depth"     [...]     fp32(t), in units of the direction's length [0; NaN for a non-finite ray]
+      "normal"    [..., 3]  the shading normal n in world space: the normal map decoded, else the vertex normals interpolated,
+                            else the face's own normal times `outward` [0, 0, 0]
+      "occlusion" [...]     a: the occlusion map, else the vertex occlusion interpolated, else 1 [1]
+      "face"      [...]     int32, the face hit [-1]
+    A miss, a zero direction and a non-finite ray get the background.  The per-ray rule is in the header of csrc/mesh_ray.hip
+    ("the mesh render"): a property of the ray and the mesh alone, bit for bit what mesh_render_composed computes and what
+    tests/_meshrenderref.py restates in NumPy.  Only the passes asked for are computed.  Unknown or no passes, a normal_map
+    without its space or frame, a map without uvs: ValueError before anything is launched.  Zero rays launch nothing; a mesh
+    without faces renders the background."""
+    job = _RenderJob("mesh_render", rays_o, rays_d, vertices, faces, passes,
+                     _render_material(uvs, texture, normal_map, normal_map_space, corner_normals, corner_tangents, occlusion_map,
+                               vertex_colors, vertex_normals, vertex_occlusion), ambient, light, outward)
+    return _mesh_render_fused(job)
+
+
+def _mesh_render_fused(job):
+    out = job.empty()
+    if job.index is None:
+        return out
+    m, index = job.m, job.index
+    res = {k: (m[k].shape[0] if m[k] is not None else 0) for k in _MESH_RENDER_MAPS}
+    material = _lib.RenderMaterial(*[_ptr(m[k]) for k in ("uvs", "texture", "normal_map", "corner_normals", "corner_tangents",
+                                                         "occlusion_map", "vertex_colors", "vertex_normals", "vertex_occlusion")],
+                                   res["texture"], res["normal_map"], res["occlusion_map"],
+                                   m["vertex_colors"].shape[1] if m["vertex_colors"] is not None else 0)
+    outputs = _lib.RenderOutputs(*[_ptr(out.get(p)) for p in ("color", "shaded", "opacity", "rgba", "depth", "normal", "occlusion", "face")])
+    light = None if job.light is None else job.light.ctypes.data_as(ctypes.c_void_p)
+    mesh, grid = index._grid_args()
+    records = index.records() if index.F.shape[0] else None
+    n_images, height, width = job.images
+    check(lib.sculpt_surface_render(_ptr(job.o), _ptr(job.d), n_images, height, width, *mesh, _ptr(records), *grid,
+                                    ctypes.byref(material), job.ambient, light, job.outward, ctypes.byref(outputs), _stream()))
+    return out
+
+
+def mesh_render_composed(rays_o, rays_d, vertices, faces, passes=("color",), uvs=None, texture=None, normal_map=None,
+                         normal_map_space=None, corner_normals=None, corner_tangents=None, occlusion_map=None, vertex_colors=None,
+                         vertex_normals=None, vertex_occlusion=None, ambient=MESH_RENDER_AMBIENT, light=None, outward=1.0):
+    """mesh_render by the pieces that were there before it: one closest-hit query of all rays (mesh_ray_cast's kernels, which
+    write the hits to memory) and torch gathers and elementwise operations, each rounded on its own, in the kernel's order.  The
+    yardstick the fused kernel is tested (same bits) and timed against (tools/time_mesh_render.py)."""
+    job = _RenderJob("mesh_render_composed", rays_o, rays_d, vertices, faces, passes,
+                     _render_material(uvs, texture, normal_map, normal_map_space, corner_normals, corner_tangents, occlusion_map,
+                               vertex_colors, vertex_normals, vertex_occlusion), ambient, light, outward)
+    return _mesh_render_composed(job)
+
+
+def _interp3(rows0, rows1, rows2, w0, w1, w2):
+    """(A0 w0 + A1 w1) + A2 w2 over rows [n, C] (or [n]) with weights [n]."""
+    if rows0.dim() == 2:
+        w0, w1, w2 = w0[:, None], w1[:, None], w2[:, None]
+    return (rows0 * w0 + rows1 * w1) + rows2 * w2
+
+
+def _map_lookup(image, U, V):
+    """The lookup of the rule in torch: image f32 [R, R] or [R, R, C], U, V f32 [n] -> [n] or [n, C]."""
+    R = image.shape[0]
+    X, Y = U * float(R), (1.0 - V) * float(R)
+    bad = ~(torch.isfinite(X) & torch.isfinite(Y))
+    X, Y = torch.where(bad, torch.zeros_like(X), X), torch.where(bad, torch.zeros_like(Y), Y)
+    xf, yf = torch.floor(X), torch.floor(Y)
+    fx, fy = X - xf, Y - yf
+    gx, gy = 1.0 - fx, 1.0 - fy
+    top = float(R - 1)
+    x0, x1 = xf.clamp(0.0, top).long(), (xf + 1.0).clamp(0.0, top).long()
+    y0, y1 = yf.clamp(0.0, top).long(), (yf + 1.0).clamp(0.0, top).long()
+    if image.dim() == 3:
+        fx, fy, gx, gy = fx[:, None], fy[:, None], gx[:, None], gy[:, None]
+    return ((image[y0, x0] * gx + image[y0, x1] * fx) * gy) + ((image[y1, x0] * gx + image[y1, x1] * fx) * fy)
+
+
+def _unit3(x):
+    """unit(x) of the rule over rows [n, 3] -> (x / len, where it applies bool [n]); the root is taken in fp64 and rounded, which
+    is the correctly rounded fp32 root."""
+    s = (x[:, 0] * x[:, 0] + x[:, 1] * x[:, 1]) + x[:, 2] * x[:, 2]
+    ln = torch.sqrt(s.double()).float()
+    ok = (ln > 0) & (ln < math.inf)
+    return x / ln[:, None], ok
+
+
+def _mesh_render_composed(job):
+    out = job.empty()
+    if job.index is None:
+        return out
+    m, index, passes = job.m, job.index, job.passes
+    o, d = job.o.reshape(-1, 3), job.d.reshape(-1, 3)
+    n, nf = o.shape[0], index.F.shape[0]
+    finite = torch.isfinite(o).all(1) & torch.isfinite(d).all(1)
+    flat = {p: out[p].view((n,) + MESH_RENDER_PASSES[p][0]) for p in passes}
+
+    def store(p, value, hit):
+        shape, dtype, bg = MESH_RENDER_PASSES[p]
+        back = torch.full((n,) + shape, bg, dtype=dtype, device=o.device)
+        if p == "depth":
+            back = torch.where(finite, back, torch.full_like(back, math.nan))
+        if value is None:
+            flat[p].copy_(back)
+        else:
+            flat[p].copy_(torch.where(hit if not shape else hit[:, None], value, back))
+
+    if nf == 0:
+        for p in passes:
+            store(p, None, None)
+        return out
+    t, face, uv = index.ray_cast(o, d, 0.0, math.inf)
+    hit = face >= 0
+    fi = face.clamp(min=0).long()
+    w1, w2 = uv[:, 0], uv[:, 1]
+    w0 = (1.0 - w1) - w2
+    F = index.F.long()
+    i0, i1, i2 = F[fi, 0], F[fi, 1], F[fi, 2]
+    c0, c1, c2 = 3 * fi, 3 * fi + 1, 3 * fi + 2
+
+    def per_vertex(a):
+        return _interp3(a[i0], a[i1], a[i2], w0, w1, w2)
+
+    def per_corner(a):
+        return _interp3(a[c0], a[c1], a[c2], w0, w1, w2)
+
+    U = V = None
+    if m["uvs"] is not None:
+        q = per_corner(m["uvs"])
+        U, V = q[:, 0], q[:, 1]
+    albedo = None
+    if any(p in passes for p in ("color", "shaded", "rgba")):
+        if m["texture"] is not None:
+            albedo = _map_lookup(m["texture"], U, V)
+        elif m["vertex_colors"] is not None:
+            albedo = per_vertex(m["vertex_colors"][:, :3].contiguous())
+        else:
+            albedo = torch.full((n, 3), MESH_RENDER_GREY, dtype=torch.float32, device=o.device)
+    normal = None
+    if "normal" in passes or "shaded" in passes:
+        P = index.P.double()
+        a, b, c = P[i0], P[i1], P[i2]
+        e1, e2 = b - a, c - a
+        g = torch.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                         e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1) * job.outward
+        ln = torch.sqrt((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2])
+        ok = (ln > 0) & (ln < math.inf)
+        normal = torch.where(ok[:, None], (g / ln[:, None]).float(), torch.zeros((n, 3), dtype=torch.float32, device=o.device))
+        if m["vertex_normals"] is not None:
+            x, ok = _unit3(per_vertex(m["vertex_normals"]))
+            normal = torch.where(ok[:, None], x, normal)
+        if m["normal_map"] is not None:
+            mm = 2.0 * _map_lookup(m["normal_map"], U, V) - 1.0
+            if m["corner_normals"] is not None:
+                N, T = per_corner(m["corner_normals"]), per_corner(m["corner_tangents"][:, :3].contiguous())
+                s = m["corner_tangents"][c0, 3]
+                B = torch.stack([s * (N[:, 1] * T[:, 2] - N[:, 2] * T[:, 1]), s * (N[:, 2] * T[:, 0] - N[:, 0] * T[:, 2]),
+                                 s * (N[:, 0] * T[:, 1] - N[:, 1] * T[:, 0])], 1)
+                mm = (mm[:, 0:1] * T + mm[:, 1:2] * B) + mm[:, 2:3] * N
+            x, ok = _unit3(mm)
+            normal = torch.where(ok[:, None], x, normal)
+    ao = None
+    if "occlusion" in passes or "shaded" in passes:
+        if m["occlusion_map"] is not None:
+            ao = _map_lookup(m["occlusion_map"], U, V)
+        elif m["vertex_occlusion"] is not None:
+            ao = per_vertex(m["vertex_occlusion"])
+        else:
+            ao = torch.ones(n, dtype=torch.float32, device=o.device)
+    for p in passes:
+        if p == "color":
+            store(p, albedo, hit)
+        elif p == "shaded":
+            if job.light is None:
+                x, ok = _unit3(-d)
+                l = torch.where(ok[:, None], x, torch.zeros_like(x))
+            else:
+                l = torch.from_numpy(job.light).to(o.device).expand(n, 3)
+            ndl = (normal[:, 0] * l[:, 0] + normal[:, 1] * l[:, 1]) + normal[:, 2] * l[:, 2]
+            amb = torch.tensor(job.ambient, dtype=torch.float32, device=o.device)
+            k = amb * ao + (1.0 - amb) * torch.where(ndl > 0, ndl, torch.zeros_like(ndl))
+            store(p, albedo * k[:, None], hit)
+        elif p == "opacity":
+            store(p, torch.ones(n, dtype=torch.float32, device=o.device), hit)
+        elif p == "rgba":
+            store(p, torch.cat([albedo, torch.ones((n, 1), dtype=torch.float32, device=o.device)], 1), hit)
+        elif p == "depth":
+            store(p, t.float(), hit)
+        elif p == "normal":
+            store(p, normal, hit)
+        elif p == "occlusion":
+            store(p, ao, hit)
+        else:
+            store(p, face, hit)
+    return out
+
+
+def mesh_render_route():
+    """What Mesh.render and TSR.render_mesh call: mesh_render, the fused kernel, unless SCULPT_DISTANCE_FORM holds the token
+    `composedrender` (then mesh_render_composed; `fusedrender` names the fused one).  The two give the same bits
+    (tests/test_gpu_mesh_render.py); tools/time_mesh_render.py times one against the other."""
+    if _lib.form_has("SCULPT_DISTANCE_FORM", "fusedrender"):
+        return mesh_render
+    return mesh_render_composed if _lib.form_has("SCULPT_DISTANCE_FORM", "composedrender") else mesh_render
+
+
+# ----------------------------------------------------------------------------------------------
 # projection onto the field's iso-surface: fused Newton kernel + fold guard (csrc/mesh_project.hip, DESIGN.md 3.1e)
 # ----------------------------------------------------------------------------------------------
 PROJECT_STEPS, PROJECT_CELLS = 8, 1.0   # what project=True means: at most 8 steps inside a trust radius of one lattice cell

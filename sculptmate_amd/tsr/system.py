@@ -157,6 +157,23 @@ class Mesh:
         normals = float(outward) * ops.vertex_normals(self.vertices, self.faces)
         return ops.mesh_occlusion(self.vertices, normals, self.vertices, self.faces, occlusion, seed=seed)
 
+    def render(self, rays_o, rays_d, passes=("color",), ambient=0.3, light=None, outward=1.0):
+        """Pictures of this mesh with everything it carries -- uvs and texture, normal map and its frame, occlusion map, vertex
+        colours, normals and occlusion -- ray cast on the device (ops.mesh_render on its device tensors; host arrays are refused
+        like any CPU tensor).  rays_o, rays_d float [n_images, H, W, 3] or [N, 3] -> {pass: tensor} with the rays' leading
+        shape; passes: any of "color", "shaded", "opacity", "rgba", "depth", "normal", "occlusion", "face" (ops.mesh_render has
+        their values and backgrounds).  outward: +1 when the faces wind counter-clockwise seen from outside, -1 otherwise
+        (TSR.WINDING_OUTWARD for the meshes of TSR.extract_meshes); it orients the face normal a mesh without a normal map
+        and vertex normals is shaded with.  A map without the uvs it belongs to is not used."""
+        has_uvs = self.uvs is not None
+        return ops.mesh_render_route()(rays_o, rays_d, self.vertices, self.faces, passes=passes, uvs=self.uvs,
+                                       texture=self.texture if has_uvs else None,
+                                       normal_map=self.normal_map if has_uvs else None, normal_map_space=self.normal_map_space,
+                                       corner_normals=self.corner_normals, corner_tangents=self.corner_tangents,
+                                       occlusion_map=self.occlusion_map if has_uvs else None, vertex_colors=self.vertex_colors,
+                                       vertex_normals=self.vertex_normals, vertex_occlusion=self.vertex_occlusion,
+                                       ambient=ambient, light=light, outward=outward)
+
     def to_trimesh(self):  # pragma: no cover (trimesh is optional)
         import trimesh
 
@@ -252,6 +269,18 @@ class Mesh:
 
 def _host(x):
     return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _mesh_pass_to_pil(name, image):
+    """One view of a pass of TSR.render_mesh as a PIL image: the passes tsr/passes.py knows as it makes them, "shaded" as
+    "color" (clipped first: a light can exceed 1), "occlusion" as "opacity" (L), "face" as mode I (int32, untouched)."""
+    from PIL import Image
+
+    if name == "face":
+        return Image.fromarray(np.ascontiguousarray(image, dtype=np.int32))
+    if name == "shaded":
+        return render_pass_rules.to_pil("color", np.clip(np.nan_to_num(np.asarray(image, np.float32)), 0.0, 1.0))
+    return render_pass_rules.to_pil("opacity" if name == "occlusion" else name, image)
 
 
 class _PinnedPool:
@@ -1121,6 +1150,41 @@ class TSR(KernelEngine):
                 views = self.renderer.render_passes(self.decoder, planes, rays_o, rays_d, passes)
                 images.append(render_pass_rules.convert(views, return_type))
         return images
+
+    def render_mesh(self, mesh: Mesh, n_views: int, elevation_deg: float = 0.0, camera_distance: float = 1.9, fovy_deg: float = 40.0,
+                    height: int = 256, width: int = 256, passes=("color",), return_type: str = "pt", ambient: float = 0.3,
+                    light=None):
+        """Turntable pictures of the finished MESH -- what extract_meshes, simplify and the bakes produced, as an engine that
+        loads the exported asset would show it -- under the cameras of render and render_passes: pixel (i, j) of view k is
+        the same ray in all three.  -> a list of n_views dicts {pass: picture}.  passes: any of "color" ([height, width, 3]:
+        texture, else vertex colours, else grey, unlit on white: the counterpart of render's picture), "shaded" (lit by a
+        headlight, or from `light`, the direction towards a fixed light; `ambient` is the share the occlusion scales),
+        "opacity", "rgba" (premultiplied), "depth", "normal" (the normal map decoded through the exported frame, in world
+        space), "occlusion" and "face" (int32 [height, width], -1 off the mesh) -- Mesh.render / ops.mesh_render have the rules.
+        return_type as render_passes: "pt" (device tensors, nothing is synchronised beyond the index build), "np" or "pil"
+        (occlusion as L, face as mode I, the others as tsr/passes.py makes them).  Needs a device, no weights.  All views are one
+        launch over one index of the mesh.  Unknown or no passes: ValueError, before anything is launched."""
+        passes = ops.mesh_render_passes(passes)
+        if return_type not in render_pass_rules.RETURN_TYPES:
+            raise ValueError("return_type must be 'pt', 'np' or 'pil'")
+        if self.device is None:
+            raise _lib.SculptError("TSR.render_mesh: the model is on no device yet (to(device))")
+        rays_o, rays_d = get_spherical_cameras(n_views, elevation_deg, camera_distance, fovy_deg, height, width)
+        rays_o, rays_d = rays_o.to(self.device, non_blocking=True), rays_d.to(self.device, non_blocking=True)
+        on_device = Mesh(_f32(mesh.vertices, self.device), torch.as_tensor(mesh.faces).to(self.device).contiguous())
+        for name in ("vertex_colors", "uvs", "texture", "vertex_normals", "vertex_occlusion", "normal_map", "corner_normals",
+                     "corner_tangents", "occlusion_map"):
+            value = getattr(mesh, name)
+            setattr(on_device, name, None if value is None else _f32(value, self.device))
+        on_device.normal_map_space = mesh.normal_map_space
+        with torch.no_grad():
+            views = on_device.render(rays_o, rays_d, passes=passes, ambient=ambient, light=light, outward=self.WINDING_OUTWARD)
+        if return_type == "pt":
+            return render_pass_rules.convert(views, "pt")
+        host = [{p: v.cpu().numpy() for p, v in view.items()} for view in render_pass_rules.convert(views, "pt")]
+        if return_type == "np":
+            return host
+        return [{p: _mesh_pass_to_pil(p, v) for p, v in view.items()} for view in host]
 
     def field_normals(self, points, scene_code):
         """Outward unit normals of the density field of `scene_code` ([3, C, H, W] or an ops.ChannelLastPlanes) at `points`
