@@ -413,6 +413,56 @@ int sculpt_mc_emit_capped(const float *vol, int n0, int n1, int n2, double level
                           int64_t cap_faces, int *top_plane_map /* or NULL */, sculpt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Surface nets: the all-quad dual of marching cubes (csrc/surface_nets.hip; added without a version change: new symbols only).
+ * One vertex INSIDE every cell the surface passes through, one quad across every sign-changing lattice edge whose four cells exist.
+ * The rule, which tests/_snref.py restates in NumPy and the kernels meet bit for bit:
+ *   vol      f32 [n0][n1][n2] C order on the device, every n >= 2, at most 2^30 points and n0 * n1 * ceil(n2 / 32) < 2^27 (1024^3
+ *            fits; any other shape is refused with a message); level a double.
+ *   inside   inside(p) = vol[p] > levelf, levelf the largest float <= level (marching cubes' predicate); a NaN is outside.
+ *            sign_planes (or NULL): the caller's planes of that predicate -- sign_planes[(i0 * n1 + i1) * words_per_row + i2 / 32]
+ *            bit i2 % 32, what sculpt_density_grid_filtered leaves behind for level 0; bits past n2 are ignored.  With them the
+ *            count phase never reads the volume; the emit phase reads it at the corners of active cells only, where its sign
+ *            must be the planes'.
+ *   cells    cell (i0, i1, i2), 0 <= i_c <= n_c - 2, has the 8 points i + {0,1}^3; it is ACTIVE when its corners are neither all
+ *            inside nor all outside.  One vertex per active cell, numbered in lexicographic order of (i0, i1, i2), i0 slowest.
+ *   vertex   in fp64 from the fp32 values, no contraction, in this order: walk the cell's 12 edges -- the four along axis 0,
+ *            then axis 1, then axis 2; within an axis the offsets on the two other axes go (0,0), (0,1), (1,0), (1,1), the lower
+ *            axis first.  An edge with low corner offset lo (0 on its own axis), end values a (low) and b (high) and inside(a)
+ *            != inside(b):  t = (level - a) / (b - a), a t that is not finite is 0.5;  s_c = s_c + (lo_c + (c == axis ? t : 0));
+ *            n = n + 1.  Then p_c = i_c + s_c / n, rounded once to fp32: the LATTICE-UNIT position.  The returned vertex is
+ *            marching cubes' map of it in fp32: o = p / vert_div, then rounded(o * vert_mul) + vert_add.
+ *   quads    a lattice edge along axis a with low end p, p_a <= n_a - 2; u = (a + 1) % 3, v = (a + 2) % 3.  It is ELIGIBLE when
+ *            inside differs at its ends and 1 <= p_u <= n_u - 2 and 1 <= p_v <= n_v - 2 (its four cells exist: a sign change on
+ *            the box's boundary gives no quad, the surface is open there as marching cubes' is).  With c(du, dv) the vertex of
+ *            the cell whose low corner is p + du e_u + dv e_v, the quad is [c(-1,-1), c(0,-1), c(0,0), c(-1,0)] when p is
+ *            inside and that list reversed when p is outside: counter-clockwise seen from outside when inside is positive.
+ *            Quads are ordered by the key (linear index of p) * 3 + a.
+ *   faces    faces[2q], faces[2q + 1] split quad q = [q0, q1, q2, q3] along its shorter diagonal: d02, d13 = the fp64 squared
+ *            lengths ((dx dx + dy dy) + dz dz) from the fp32 lattice-unit positions; d13 < d02: (q0,q1,q3), (q1,q2,q3),
+ *            otherwise (q0,q1,q2), (q0,q2,q3).
+ * A cell with an ambiguous sign pattern still gets ONE vertex: on a noisy field the mesh has non-manifold edges.
+ * Two phases.  sculpt_surface_nets_count queues the masks and scans, copies the two totals into a pinned slot behind an event
+ * (the way of sculpt_mc_count_launch / _read: it waits for that event only, never for the stream; not graph-capturable) and
+ * returns them; no active cell: SCULPT_ERR_SN_EMPTY.  n_verts > 0 with n_quads == 0 is a valid result (a 2x2x2 volume).
+ * sculpt_surface_nets_emit writes verts f32 [n_verts][3], quads [n_quads][4] (or NULL: not wanted) and faces [2 n_quads][3] (or
+ * NULL) of int32, or of int64 under SCULPT_SN_INDEX_I64, into the caller's buffers; same vol, shape, level and workspace as
+ * the count, which must not have been touched in between.  No atomics anywhere: ids are popcounts over bit masks plus scanned
+ * prefixes, so the result does not depend on scheduling.
+ * The workspace is DETERMINISTIC: sculpt_surface_nets_workspace_bytes is a function of the shape alone (bit masks -- six words per
+ * 32 points -- plus two words per 8192 points; 12.6 MB at 256^3; 0 for a shape that is refused), 16-byte aligned.  There is no
+ * record pool and no overflow protocol.
+ * ------------------------------------------------------------------------------------------ */
+#define SCULPT_SN_INDEX_I64 1u
+#define SCULPT_ERR_SN_EMPTY 17 /* no cell has corners on both sides of the level */
+size_t sculpt_surface_nets_workspace_bytes(int n0, int n1, int n2);
+int sculpt_surface_nets_count(const float *vol, const uint32_t *sign_planes /* or NULL */, int words_per_row, int n0, int n1, int n2,
+                              double level, unsigned flags, void *workspace, int64_t *n_verts_host, int64_t *n_quads_host,
+                              sculpt_stream_t stream);
+int sculpt_surface_nets_emit(const float *vol, int n0, int n1, int n2, double level, unsigned flags, void *workspace, float vert_div,
+                             float vert_mul, float vert_add, float *verts, void *quads /* or NULL */, void *faces /* or NULL */,
+                             sculpt_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Connected components of an indexed triangle mesh, and the mesh without its small ones (csrc/mesh_components.hip).
  *   faces   int32 or int64 (faces_i64 != 0) [n_faces][3], on the device, over n_vertices SHARED vertices (what sculpt_mc_emit
  *           writes): two faces are connected when they name a common vertex.  0 <= n_vertices, n_faces < 2^31.

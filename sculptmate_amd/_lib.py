@@ -102,6 +102,9 @@ SIGNATURES = {
     "sculpt_mc_count_launch": (_i, [_vp, _i, _i, _i, ctypes.c_double, _u, _vp, _vp]),
     "sculpt_mc_count_read": (_i, [_i, _i, _i, ctypes.c_double, _u, _vp, _pi64, _pi64, _vp, _vp]),
     "sculpt_mc_emit_capped": (_i, [_vp, _i, _i, _i, ctypes.c_double, _u, _vp, _f, _f, _f, _i, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "sculpt_surface_nets_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sculpt_surface_nets_count": (_i, [_vp, _vp, _i, _i, _i, _i, _d, _u, _vp, _pi64, _pi64, _vp]),
+    "sculpt_surface_nets_emit": (_i, [_vp, _i, _i, _i, _d, _u, _vp, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "sculpt_mesh_components_workspace_bytes": (_sz, [_i64, _i64]),
     "sculpt_mesh_components_launch": (_i, [_vp, _i, _i64, _i64, _i, _i64, _d, _vp, _vp]),
     "sculpt_mesh_components_read": (_i, [_vp, _pi64]),
@@ -283,6 +286,8 @@ ERR_MC_NAN = 13
 ERR_MC_WORKSPACE = 14
 ERR_MC_NO_COUNT = 15
 ERR_MESH_COMPONENTS = 16
+SN_INDEX_I64 = 1
+ERR_SN_EMPTY = 17
 CC_KEEP_NONE, CC_KEEP_LARGEST, CC_KEEP_MIN_FACES, CC_KEEP_FRACTION = 0, 1, 2, 3
 EPI_NONE, EPI_GELU, EPI_GEGLU, EPI_RELU = 0, 1, 2, 3
 QUERY_ALIGN_CORNERS = 1

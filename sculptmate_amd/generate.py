@@ -45,6 +45,9 @@ class TripoGenerator(GeneratorFacade):
     `subdivide` (default None): an int n in 1 .. 6 (levels of the Loop scheme) or a tuple (n, "loop" | "midpoint") refines every
     mesh 1 -> 4 faces per level on the device, after simplify and before project: the simplified mesh becomes the control cage
     of a semi-regular, multires-friendly surface (TSR.extract_meshes; ops.mesh_subdivide).
+    `isosurface` (default "marching_cubes"): "surface_nets" extracts every mesh with surface nets on the device instead -- one
+    vertex inside every cell the surface passes through, an all-quad mesh (Mesh.quads, which the plain Blender sink and
+    Mesh.export's .obj receive) beside its triangles, no sliver triangles (TSR.extract_meshes; ops.surface_nets).
     `occlusion` (default None): True (64 directions), an int k in 1 .. 1024 or a tuple (k, max_distance) leaves the ambient
     occlusion of every final mesh against itself on the meshes in `last_meshes` (Mesh.vertex_occlusion, f32 [Nv], 1 = open:
     TSR.extract_meshes; ops.mesh_occlusion); Mesh.export writes it into .ply and .glb.  The Blender sinks take none.
@@ -69,6 +72,7 @@ class TripoGenerator(GeneratorFacade):
         self.project = None
         self.subdivide = None
         self.occlusion = None
+        self.isosurface = "marching_cubes"
         self.normal_map = None
         self.occlusion_map = None
 
@@ -89,7 +93,7 @@ class TripoGenerator(GeneratorFacade):
             self.last_meshes = self.model.extract_mesh(codes, enable_texture=enable_texture, mesh_name=input_name,
                                                        resolution=self.mc_resolution,
                                                        bake_texture=int(self.bake_texture_resolution or 0),
-                                                       normals=self.vertex_normals,
+                                                       normals=self.vertex_normals, isosurface=self.isosurface,
                                                        keep_components=self.keep_components, simplify=self.simplify,
                                                        smooth=self.smooth, project=self.project, subdivide=self.subdivide,
                                                        occlusion=self.occlusion)

@@ -33,12 +33,19 @@ class MeshArrays(tuple):
         return self
 
 
-def write_obj(path, vertices, faces, vertex_colors=None, normals=None):
+def write_obj(path, vertices, faces, vertex_colors=None, normals=None, quads=None):
     """`v x y z [r g b]` / `f a b c` (1-based), one numpy formatting pass per block.  normals f32 [Nv, 3] (one per vertex):
     `vn x y z` lines after the vertices and `f a//a b//b c//c` faces.  OBJ has no slot for a per-vertex scalar: a mesh's
-    vertex_occlusion is not written (write_ply and write_glb take it)."""
+    vertex_occlusion is not written (write_ply and write_glb take it).  quads int [Nq, 4] (Mesh.quads; None: the file is what
+    it was without the keyword): the faces written are the quads, `f a b c d` / `f a//a b//b c//c d//d`, in place of `faces`."""
     v = np.asarray(vertices, np.float64)
+    if quads is not None:
+        q = np.asarray(quads, np.int64)
+        if q.ndim != 2 or q.shape[1] != 4:
+            raise ValueError("write_obj: quads %s must be [Nq, 4]" % (q.shape,))
+        faces = q
     f = np.asarray(faces, np.int64) + 1
+    k = f.shape[1] if f.ndim == 2 else 3
     if vertex_colors is not None:
         v = np.concatenate([v, np.asarray(vertex_colors, np.float64)], 1)
         fmt = "v %.7g %.7g %.7g %.5f %.5f %.5f"
@@ -48,10 +55,10 @@ def write_obj(path, vertices, faces, vertex_colors=None, normals=None):
         fh.write("# sculptmate_amd\n")
         np.savetxt(fh, v, fmt=fmt)
         if normals is None:
-            np.savetxt(fh, f, fmt="f %d %d %d")
+            np.savetxt(fh, f, fmt="f" + " %d" * k)
         else:
             np.savetxt(fh, _normals_for(normals, len(v), "write_obj").astype(np.float64), fmt="vn %.7g %.7g %.7g")
-            np.savetxt(fh, np.repeat(f, 2, axis=1), fmt="f %d//%d %d//%d %d//%d")
+            np.savetxt(fh, np.repeat(f, 2, axis=1), fmt="f" + " %d//%d" * k)
 
 
 def write_obj_textured(path, vertices, faces, uvs, texture, normals=None, normal_map=None, occlusion_map=None):
@@ -104,7 +111,7 @@ def write_obj_textured(path, vertices, faces, uvs, texture, normals=None, normal
 
 
 def read_obj(path):
-    """-> MeshArrays (vertices f32, faces i64 of the position indices, colours f32 | None), `.normals` f32 [Nv, 3] | None: the
+    """-> MeshArrays (vertices f32, faces i64 of the position indices -- [Nf, 3], or [Nq, 4] for a file of quads --, colours f32 | None), `.normals` f32 [Nv, 3] | None: the
     `vn` lines brought into vertex order through the faces' normal indices (the writers above give every vertex one normal)."""
     vs, cs, fs, ns, fn = [], [], [], [], []
     with open(path) as fh:
@@ -119,9 +126,9 @@ def read_obj(path):
             elif p[0] == "vn":
                 ns.append([float(x) for x in p[1:4]])
             elif p[0] == "f":
-                fs.append([int(x.split("/")[0]) - 1 for x in p[1:4]])
+                fs.append([int(x.split("/")[0]) - 1 for x in p[1:]])   # triangles, or the quads of write_obj(quads=): one size per file
                 if ns:
-                    fn.append([int(x.split("/")[2]) - 1 for x in p[1:4]])
+                    fn.append([int(x.split("/")[2]) - 1 for x in p[1:]])
     v, f = np.array(vs, np.float32), np.array(fs, np.int64)
     normals = None
     if ns:

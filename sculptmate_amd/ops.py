@@ -493,6 +493,59 @@ _MC_REC_CAPACITY = {} # (device, n0, n1, n2) -> active-cell records of the works
 _MC_SPECULATE = not _lib.form_has("SCULPT_MC_FORM", "nospeculate")   # A/B: the two-phase path every time
 
 
+ISOSURFACES = ("marching_cubes", "surface_nets")
+
+
+def isosurface_rule(isosurface):
+    """The extractor names TSR.extract_meshes(isosurface=...) takes; anything else is a ValueError."""
+    if not isinstance(isosurface, str) or isosurface not in ISOSURFACES:
+        raise ValueError("isosurface must be one of %s, got %r" % (", ".join(repr(s) for s in ISOSURFACES), isosurface))
+    return isosurface
+
+
+def surface_nets(vol, level=0.0, vert_div=1.0, vert_mul=1.0, vert_add=0.0, faces_i64=False, sign_planes=None):
+    """Surface nets on the device (sculpt_surface_nets_*; include/sculpt_hip.h states the rule, tests/_snref.py restates it):
+    one vertex inside every cell of vol f32 [n0, n1, n2] whose corners lie on both sides of `level` (inside = vol > level), one
+    quad across every sign-changing lattice edge whose four cells exist -> (verts f32 [Nv, 3], quads [Nq, 4], faces [2 Nq, 3]),
+    indices int32 or, with faces_i64, int64.  verts are the lattice-unit positions through marching_cubes' affine map
+    (/ vert_div, * vert_mul, + vert_add); faces[2q], faces[2q + 1] split quad q along its shorter diagonal; with a positive
+    inside every quad and triangle winds counter-clockwise seen from outside.  The mesh is open where the surface meets the
+    box, and a cell with an ambiguous sign pattern still has one vertex, so a noisy field gives non-manifold edges.
+    sign_planes: as marching_cubes takes them (what density_grid_filtered leaves behind for level 0): the count phase then
+    reads no value of the volume.  Raises RuntimeError when no cell is active; Nv > 0 with Nq == 0 is a valid result."""
+    vol = _req(vol, torch.float32, "vol")
+    if vol.dim() != 3:
+        raise SculptError("surface_nets: vol must be [n0, n1, n2], got %s" % (tuple(vol.shape),))
+    n0, n1, n2 = vol.shape
+    nbytes = lib.sculpt_surface_nets_workspace_bytes(n0, n1, n2)
+    if nbytes == 0:
+        raise SculptError(_lib.last_error(), 2)
+    ws = _workspace(("sn", vol.device), nbytes, vol.device)
+    planes, ld = None, 0
+    if sign_planes is not None:
+        if not (isinstance(sign_planes, torch.Tensor) and sign_planes.device == vol.device and sign_planes.dim() == 2
+                and sign_planes.shape[0] == n0 * n1 and sign_planes.stride(1) == 1 and sign_planes.element_size() == 4
+                and not sign_planes.dtype.is_floating_point and sign_planes.shape[1] >= (n2 + 31) // 32):
+            raise SculptError("surface_nets: sign_planes must be int32 / uint32 [n0 * n1][>= ceil(n2 / 32)] on the volume's device")
+        _check_sign_planes_current(sign_planes)
+        planes, ld = sign_planes, sign_planes.stride(0)
+    flags = _lib.SN_INDEX_I64 if faces_i64 else 0
+    nv, nq = ctypes.c_int64(), ctypes.c_int64()
+    rc = lib.sculpt_surface_nets_count(_ptr(vol), _ptr(planes), ld, n0, n1, n2, float(level), flags, _ptr(ws), ctypes.byref(nv),
+                                       ctypes.byref(nq), _stream())
+    if rc == _lib.ERR_SN_EMPTY:
+        raise RuntimeError(_lib.last_error())
+    check(rc)
+    idt = torch.int64 if faces_i64 else torch.int32
+    verts = torch.empty((nv.value, 3), dtype=torch.float32, device=vol.device)
+    quads = torch.empty((nq.value, 4), dtype=idt, device=vol.device)
+    faces = torch.empty((2 * nq.value, 3), dtype=idt, device=vol.device)
+    check(lib.sculpt_surface_nets_emit(_ptr(vol), n0, n1, n2, float(level), flags, _ptr(ws), float(vert_div), float(vert_mul),
+                                       float(vert_add), _ptr(verts), _ptr(quads) if nq.value else None,
+                                       _ptr(faces) if nq.value else None, _stream()))
+    return verts, quads, faces
+
+
 def _is_count(n, lo, hi=math.inf):
     """n is an integer in lo .. hi and no bool: what the rules below ask of a count."""
     return not isinstance(n, (bool, np.bool_)) and isinstance(n, numbers.Integral) and lo <= int(n) <= hi

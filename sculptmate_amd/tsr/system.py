@@ -37,6 +37,8 @@ from .spec import DEFAULT_CFG, IMAGE_MEAN, IMAGE_STD, param_spec  # noqa: E402,F
 class Mesh:
     """What run() returns per image: trimesh-constructible arrays."""
 
+    quads = None   # (a mesh object made before the attribute existed has none either)
+
     def __init__(self, vertices, faces, vertex_colors=None, uvs=None, texture=None, vertex_normals=None, vertex_occlusion=None):
         """uvs / texture: what TSR.bake_texture adds -- uvs f32 [3*Nf, 2] per face corner (origin bottom-left, the convention of
         sf3d and meshio.write_glb), texture f32 [res, res, 3] in [0, 1] with row 0 at the top.
@@ -61,6 +63,11 @@ class Mesh:
         # row 0 at the top, 1 = open, 0 = occluded; occlusion_map_rule = (k, max_distance), the rule it was baked under.
         self.occlusion_map = None
         self.occlusion_map_rule = None
+        # What extract_meshes(isosurface="surface_nets") adds (an attribute too): quads int [Nq, 4], the all-quad mesh over the
+        # same vertices, while `faces` are still the extractor's -- faces[2q], faces[2q + 1] are quad q split along its shorter
+        # diagonal.  smooth and project keep it (faces and vertex numbering stay); keep_components, simplify and subdivide
+        # make new faces and drop it.
+        self.quads = None
 
     def keep_components(self, keep) -> "Mesh":
         """The mesh without its small connected components (the "floaters" a thresholded density field leaves around the
@@ -111,7 +118,9 @@ class Mesh:
         they would be stale (TSR.field_normals / ops.vertex_normals at the new vertices give fresh ones).  TSR.extract_meshes(smooth=...)
         smooths before it simplifies; this method lets a caller choose another order."""
         v = ops.mesh_smooth(self.vertices, self.faces, smooth)
-        return Mesh(v, self.faces, self.vertex_colors, uvs=self.uvs, texture=self.texture)
+        out = Mesh(v, self.faces, self.vertex_colors, uvs=self.uvs, texture=self.texture)
+        out.quads = self.quads   # the faces are the same: the quads they came from still cover them
+        return out
 
     def subdivide(self, subdivide) -> "Mesh":
         """The mesh refined 1 -> 4 faces per level on the device (ops.mesh_subdivide): subdivide = an int n, 1 <= n <= 6 (n
@@ -225,6 +234,8 @@ class Mesh:
         never written as glTF's normalTexture (which is tangent space by definition): the .glb carries it as a further PNG image
         that no material refers to, named in the mesh's extras ({"images": {"normal_map_object": index}}); the .obj gets the
         same map_Bump line, to be read as object space by whoever asked for one.
+        An unbaked mesh with quads (extract_meshes(isosurface="surface_nets")) goes into .obj as quads, `f a b c d`; .ply, .glb
+        and every baked path write the triangles.
         A baked occlusion map (TSR.bake_occlusion_map; uvs + occlusion_map, with or without a texture or normal map) goes the
         textured way as well: .glb gets material.occlusionTexture (three equal channels; glTF reads the red one, strength at its
         default of 1), .obj gets `map_Ka NAME_ao.png` in the .mtl and the PNG beside it."""
@@ -264,6 +275,8 @@ class Mesh:
                 meshio.write_obj_textured(str(path), v, f, uv, picture, normals=vn, **extra)
             return
         extra = {} if self.vertex_occlusion is None or ext == "obj" else {"occlusion": _host(self.vertex_occlusion)}
+        if ext == "obj" and self.quads is not None:   # the all-quad mesh of surface nets: `f a b c d` lines (.ply and .glb stay triangles)
+            extra["quads"] = _host(self.quads)
         writer(str(path), self.vertices, self.faces, vertex_colors=self.vertex_colors, normals=self.vertex_normals, **extra)
 
 
@@ -1396,10 +1409,12 @@ class TSR(KernelEngine):
             v = _f32(mesh.vertices, self.device)
             f = torch.as_tensor(mesh.faces).to(self.device).contiguous()
             v = self._projected(v, f, scene_code, threshold, steps_cells, resolution)
-        return Mesh(v, mesh.faces, mesh.vertex_colors, uvs=mesh.uvs, texture=mesh.texture)
+        out = Mesh(v, mesh.faces, mesh.vertex_colors, uvs=mesh.uvs, texture=mesh.texture)
+        out.quads = mesh.quads
+        return out
 
     def extract_meshes(self, scene_codes, enable_texture=False, resolution: int = 256, threshold: float = 25.0,
-                       x_range=None, density_events=None, bake_texture: int = 0, normals=None,
+                       x_range=None, density_events=None, bake_texture: int = 0, normals=None, isosurface="marching_cubes",
                        keep_components=None, simplify=None, smooth=None, project=None, subdivide=None, occlusion=None) -> List[Mesh]:
         """The arithmetic of system.py:171-200 without the Blender sink: returns device tensors.
         density_events: optional (start, stop) torch events recorded around the dense-grid launch (bench.py's live
@@ -1411,6 +1426,16 @@ class TSR(KernelEngine):
         self.occlusion_map = True | k | (k, max_distance) (an instance setting too, default None: nothing more is launched) it also
         gets an ambient-occlusion map over that atlas (TSR.bake_occlusion_map: Mesh.occlusion_map, occlusion_map_rule), baked
         against the mesh as it entered simplify when simplify is given, else against itself.
+        isosurface: "marching_cubes" (default: the reference's Lewiner mesh, bit for bit what it was without the keyword) or
+        "surface_nets" (ops.surface_nets: one vertex inside every cell the surface passes through, one quad across every
+        sign-changing lattice edge -- no sliver triangles, and an all-quad mesh in Mesh.quads beside the triangles in
+        Mesh.faces, which split each quad along its shorter diagonal and wind like marching cubes' (TSR.WINDING_OUTWARD)).
+        Both take the two-pass grid and its sign planes under the same guard.  Mesh.quads stays while the faces are the
+        extractor's: smooth and project keep it, keep_components, simplify and subdivide drop it.  The mesh is open where
+        the surface meets the box, and naive surface nets puts ONE vertex into a cell with an ambiguous sign pattern, so a
+        noisy field gives non-manifold edges (the mesh steps classify and hold such vertices).  project=True after it puts the
+        vertices onto the field's iso-surface (dual contouring in effect).  Anything else is a ValueError before any launch.
+        run, run_async, run_batched, run_pipelined, batch.run_sharded and extract_mesh_sharded do not take the option yet.
         normals: None (default): Mesh.vertex_normals stays unset.  "field": the outward unit normals of the density field at the
         vertices (TSR.field_normals: the gradient of the field whose iso-surface the mesh is).  "faces": area-weighted averages of
         the facet normals (ops.vertex_normals).  Either way f32 [Nv, 3] per shared vertex, also on a baked mesh.
@@ -1444,6 +1469,7 @@ class TSR(KernelEngine):
         Mesh.ambient_occlusion on a device mesh instead."""
         if normals not in (None, "field", "faces"):
             raise ValueError("normals must be None, 'field' or 'faces', got %r" % (normals,))
+        ops.isosurface_rule(isosurface)   # a ValueError before anything is launched
         if occlusion is not None:
             ops.occlusion_rule(occlusion)   # a ValueError before anything is launched
         if self.occlusion_map is not None:
@@ -1455,11 +1481,19 @@ class TSR(KernelEngine):
         r = self.renderer.cfg.radius
         R = resolution
         out = []
-        def mc(v, sign_planes=None):
-            return ops.marching_cubes(v.view(R, R, R), 0.0, reference_order=True, vert_div=R - 1.0, vert_mul=r - (-r), vert_add=-r,
-                                      sign_planes=sign_planes)
+        quads_of = {}   # what the surface-nets extractor leaves beside the (vertices, faces) that _extract_filtered hands on
+        if isosurface == "surface_nets":
+            def mc(v, sign_planes=None):
+                v_pos, quads_of["quads"], faces = ops.surface_nets(v.view(R, R, R), 0.0, vert_div=R - 1.0, vert_mul=r - (-r), vert_add=-r,
+                                                                   faces_i64=True, sign_planes=sign_planes)
+                return v_pos, faces
+        else:
+            def mc(v, sign_planes=None):
+                return ops.marching_cubes(v.view(R, R, R), 0.0, reference_order=True, vert_div=R - 1.0, vert_mul=r - (-r), vert_add=-r,
+                                          sign_planes=sign_planes)
 
         mc.takes_sign_planes = True
+        keeps_faces = keep_components is None and simplify is None and subdivide is None
         for scene_code in scene_codes:
             planes = scene_code.contiguous()
             dkw = dict(radius=r, density_bias=self.renderer.cfg.density_bias, out_add=-threshold)
@@ -1471,6 +1505,8 @@ class TSR(KernelEngine):
                 v_pos, t_pos_idx = mc(vol)   # (both decoder modes have the fp32 range: a NaN here is a NaN of the model)
             v_pos, t_pos_idx = self._reshaped(v_pos, t_pos_idx, planes, threshold, R, **geometry)
             out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals, occlusion))
+            if keeps_faces:   # the faces are still the extractor's
+                out[-1].quads = quads_of.pop("quads", None)
         return out
 
     @staticmethod
@@ -1646,16 +1682,18 @@ class TSR(KernelEngine):
         return Mesh(v_pos, t_pos_idx, color)
 
     def extract_mesh(self, scene_codes, enable_texture=False, mesh_name="NewMesh", resolution: int = 256,
-                     threshold: float = 25.0, bake_texture: int = 0, normals=None, keep_components=None, simplify=None, smooth=None, project=None,
-                     subdivide=None, occlusion=None):
+                     threshold: float = 25.0, bake_texture: int = 0, normals=None, isosurface="marching_cubes", keep_components=None,
+                     simplify=None, smooth=None, project=None, subdivide=None, occlusion=None):
         """system.py:171-200: same signature (+ bake_texture, normals, occlusion and the geometry options keep_components, smooth,
         simplify, subdivide, project, all described at extract_meshes: the sink receives the final mesh); pushes each mesh into the sink (Blender when
         `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
         the textured sink (per-loop UVs + an image-texture material; with self.normal_map = "tangent" also normal_image=, the
         baked normal map, which Blender's sink wires through a Normal Map node).  The sinks take no normals (Blender shades a mesh with
-        shared vertices smooth by itself) and no occlusion; both stay on the returned meshes."""
+        shared vertices smooth by itself) and no occlusion; both stay on the returned meshes.  isosurface (extract_meshes): a mesh with
+        quads goes to the plain sink as quads, in place of the faces (Blender's from_pydata takes any polygon size); the
+        textured sink stays on triangles, which its per-corner UVs belong to."""
         meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture, normals=normals,
-                                     keep_components=keep_components, simplify=simplify, smooth=smooth, project=project,
+                                     isosurface=isosurface, keep_components=keep_components, simplify=simplify, smooth=smooth, project=project,
                                      subdivide=subdivide, occlusion=occlusion)
         sink = self.mesh_sink or _default_sink()
         for m in meshes:
@@ -1672,7 +1710,7 @@ class TSR(KernelEngine):
                     sink(_host(m.vertices), _host(m.faces), None, mesh_name)
                 continue
             if sink is not None:
-                sink(m.vertices.cpu().numpy(), m.faces.cpu().numpy(),
+                sink(m.vertices.cpu().numpy(), (m.faces if m.quads is None else m.quads).cpu().numpy(),
                      None if m.vertex_colors is None else m.vertex_colors.cpu().numpy(), mesh_name)
         return meshes
 
