@@ -26,347 +26,13 @@ from ..engine import KernelEngine, prepare_ln_linear
 from .posemb import interpolate_pos_embedding
 from .cameras import get_spherical_cameras
 from . import passes as render_pass_rules
+from .mesh import TENSOR_FIELDS, Mesh, PendingMesh, _PinnedLease, _PinnedPool, _host, _mesh_pass_to_pil  # noqa: F401
 from .utils import ImagePreprocessor
 
 BF16 = torch.bfloat16
 LOG2E = 1.4426950408889634
 
 from .spec import DEFAULT_CFG, IMAGE_MEAN, IMAGE_STD, param_spec  # noqa: E402,F401
-
-
-class Mesh:
-    """What run() returns per image: trimesh-constructible arrays."""
-
-    quads = None   # (a mesh object made before the attribute existed has none either)
-
-    def __init__(self, vertices, faces, vertex_colors=None, uvs=None, texture=None, vertex_normals=None, vertex_occlusion=None):
-        """uvs / texture: what TSR.bake_texture adds -- uvs f32 [3*Nf, 2] per face corner (origin bottom-left, the convention of
-        sf3d and meshio.write_glb), texture f32 [res, res, 3] in [0, 1] with row 0 at the top.
-        vertex_normals: f32 [Nv, 3] unit normals per shared vertex (extract_meshes(normals=...)), also on a baked mesh.
-        vertex_occlusion: f32 [Nv] ambient occlusion per shared vertex, 1 = open, 0 = occluded (extract_meshes(occlusion=...),
-        Mesh.ambient_occlusion), also on a baked mesh."""
-        self.vertices = vertices
-        self.faces = faces
-        self.vertex_colors = vertex_colors
-        self.uvs = uvs
-        self.texture = texture
-        self.vertex_normals = vertex_normals
-        self.vertex_occlusion = vertex_occlusion
-        # What TSR.bake_normal_map adds (attributes, not constructor parameters): normal_map f32 [res, res, 3], the unit normal
-        # encoded 0.5 + 0.5 n, row 0 at the top, in the atlas of `uvs`; normal_map_space "tangent" | "object"; and the frame a
-        # tangent-space map is decoded in, per face corner: corner_normals f32 [3*Nf, 3], corner_tangents f32 [3*Nf, 4] = (T, w).
-        self.normal_map = None
-        self.normal_map_space = None
-        self.corner_normals = None
-        self.corner_tangents = None
-        # What TSR.bake_occlusion_map adds (attributes too): occlusion_map f32 [res, res], ambient occlusion in the atlas of `uvs`,
-        # row 0 at the top, 1 = open, 0 = occluded; occlusion_map_rule = (k, max_distance), the rule it was baked under.
-        self.occlusion_map = None
-        self.occlusion_map_rule = None
-        # What extract_meshes(isosurface="surface_nets") adds (an attribute too): quads int [Nq, 4], the all-quad mesh over the
-        # same vertices, while `faces` are still the extractor's -- faces[2q], faces[2q + 1] are quad q split along its shorter
-        # diagonal.  smooth and project keep it (faces and vertex numbering stay); keep_components, simplify and subdivide
-        # make new faces and drop it.
-        self.quads = None
-
-    def keep_components(self, keep) -> "Mesh":
-        """The mesh without its small connected components (the "floaters" a thresholded density field leaves around the
-        object): keep = "largest", an int >= 1 (components of at least that many faces) or a float in (0, 1) (at least that
-        fraction of the largest component's faces) -- ops.mesh_keep_components on this mesh's device tensors (a mesh of host
-        arrays, as TSR.run returns them, is refused there like any CPU tensor).  Rows keep their order; vertex_colors,
-        vertex_normals and vertex_occlusion follow their vertices (vertex_index), the per-corner uvs of a baked mesh their faces (face_index, three
-        rows per face); the texture is untouched (the dropped charts stay in it, unused).  A baked normal map
-        (TSR.bake_normal_map) is carried the same way: the map as it is, corner_normals and corner_tangents through face_index; a
-        baked occlusion map (TSR.bake_occlusion_map) as it is, with its rule."""
-        v, f, vi, fi = ops.mesh_keep_components(self.vertices, self.faces, keep)
-
-        def rows(x, index):
-            return None if x is None else x[index]
-
-        corner = None
-        if self.uvs is not None or self.corner_normals is not None or self.corner_tangents is not None:
-            three = torch.arange(3, device=fi.device) if isinstance(fi, torch.Tensor) else np.arange(3)
-            corner = (fi[:, None] * 3 + three).reshape(-1)
-        out = Mesh(v, f, rows(self.vertex_colors, vi), uvs=rows(self.uvs, corner), texture=self.texture,
-                   vertex_normals=rows(self.vertex_normals, vi), vertex_occlusion=rows(self.vertex_occlusion, vi))
-        out.normal_map, out.normal_map_space = self.normal_map, self.normal_map_space
-        out.corner_normals, out.corner_tangents = rows(self.corner_normals, corner), rows(self.corner_tangents, corner)
-        out.occlusion_map, out.occlusion_map_rule = self.occlusion_map, self.occlusion_map_rule
-        return out
-
-    def simplify(self, simplify) -> "Mesh":
-        """The mesh reduced to a target face count by quadric-error edge collapses on the device (ops.mesh_simplify): simplify =
-        an int >= 1 (target faces) or a float in (0, 1) (ratio of the faces).  vertex_colors and vertex_normals follow
-        vertex_index -- the values of the input vertex each output vertex descends from.  That is an approximation: the vertex
-        has moved to its collapses' target point; TSR.extract_meshes(simplify=...) evaluates colours and normals at the final
-        vertices instead.  vertex_occlusion is dropped: it is stale once the vertices have moved.  A baked mesh (uvs / texture)
-        is refused: its atlas belongs to the faces it was baked for, so simplify
-        before baking."""
-        ops.simplify_rule(simplify)
-        if self.uvs is not None or self.texture is not None:
-            raise ValueError("Mesh.simplify: this mesh has a baked texture; simplify before baking "
-                             "(TSR.extract_meshes(simplify=..., bake_texture=...))")
-        v, f, vi = ops.mesh_simplify(self.vertices, self.faces, simplify)
-        return Mesh(v, f, None if self.vertex_colors is None else self.vertex_colors[vi],
-                    vertex_normals=None if self.vertex_normals is None else self.vertex_normals[vi])
-
-    def smooth(self, smooth) -> "Mesh":
-        """The mesh after Taubin's lambda|mu smoothing on the device (ops.mesh_smooth): smooth = an int n, 1 <= n <= 1000
-        (n iterations with lam = 0.5, mu = -0.53) or a tuple (n, lam, mu) (ops.smooth_rule).  The faces are the same tensor and
-        the vertices keep their indices, so vertex_colors, uvs and texture are carried over as they are: the topology is
-        unchanged and a baked atlas stays valid.  vertex_normals and vertex_occlusion are dropped: the vertices have moved and
-        they would be stale (TSR.field_normals / ops.vertex_normals at the new vertices give fresh ones).  TSR.extract_meshes(smooth=...)
-        smooths before it simplifies; this method lets a caller choose another order."""
-        v = ops.mesh_smooth(self.vertices, self.faces, smooth)
-        out = Mesh(v, self.faces, self.vertex_colors, uvs=self.uvs, texture=self.texture)
-        out.quads = self.quads   # the faces are the same: the quads they came from still cover them
-        return out
-
-    def subdivide(self, subdivide) -> "Mesh":
-        """The mesh refined 1 -> 4 faces per level on the device (ops.mesh_subdivide): subdivide = an int n, 1 <= n <= 6 (n
-        levels of the Loop scheme: the surface the mesh spans as a control cage) or a tuple (n, "loop" | "midpoint")
-        (ops.subdivide_rule).  vertex_colors go through the same masks as the positions (attributes=), so they stay in their
-        range.  vertex_normals and vertex_occlusion are dropped: they are stale on the refined surface.  A baked mesh
-        (uvs / texture) is refused: its atlas belongs to the faces it was baked for, so subdivide before baking."""
-        ops.subdivide_rule(subdivide)
-        if self.uvs is not None or self.texture is not None:
-            raise ValueError("Mesh.subdivide: this mesh has a baked texture; subdivide before baking "
-                             "(TSR.extract_meshes(subdivide=..., bake_texture=...))")
-        v, f, colors = ops.mesh_subdivide(self.vertices, self.faces, subdivide, attributes=self.vertex_colors)
-        return Mesh(v, f, colors)
-
-    def sample_surface(self, n, seed=0):
-        """n points uniform over this mesh's area (ops.mesh_sample_surface on its device tensors; host arrays are refused like
-        any CPU tensor) -> (points f32 [n, 3], face i64 [n], uv f32 [n, 2]); the same (n, seed) gives the same bits."""
-        return ops.mesh_sample_surface(self.vertices, self.faces, n, seed)
-
-    def distance_to(self, other: "Mesh", samples=ops.DISTANCE_SAMPLES, seed=0, threshold=None) -> dict:
-        """How far this surface is from `other`'s, whatever their topologies (ops.mesh_distance on the two meshes' device
-        tensors): Chamfer and Hausdorff distance, mean / rms / max in both directions and, with a threshold, precision, recall
-        and F-score.  samples=None measures from the meshes' own vertices: what an option such as smooth or simplify did to the
-        surface, without sampling noise."""
-        return ops.mesh_distance(self.vertices, self.faces, other.vertices, other.faces, samples=samples, seed=seed, threshold=threshold)
-
-    def ray_cast(self, origins, directions, t_min=0.0, t_max=math.inf):
-        """The closest face of this mesh that each ray hits (ops.mesh_ray_cast on its device tensors; host arrays are refused
-        like any CPU tensor) -> (t f64 [N], face i64 [N], uv f32 [N, 2]); no hit: t = +inf, face = -1."""
-        return ops.mesh_ray_cast(origins, directions, self.vertices, self.faces, t_min, t_max)
-
-    def ambient_occlusion(self, occlusion=True, seed=0, outward=1.0):
-        """Ambient occlusion per vertex -> f32 [Nv], 1 = open, 0 = occluded (ops.mesh_occlusion on this mesh's device tensors;
-        host arrays are refused): the points are the vertices, the normals outward * ops.vertex_normals(vertices, faces) --
-        always the facet-average normals of THIS mesh, whether or not vertex_normals is set.  occlusion: True (64 directions),
-        k or (k, max_distance) (ops.occlusion_rule); seed rotates the direction set; outward: +1 when the faces wind
-        counter-clockwise seen from outside, -1 otherwise (TSR.WINDING_OUTWARD for the meshes of TSR.extract_meshes).  The
-        result is not stored: assign it to vertex_occlusion to carry and export it."""
-        ops.occlusion_rule(occlusion)
-        if not (ops._is_real(outward) and math.isfinite(float(outward))):
-            raise ValueError("outward must be a finite number (+1 or -1), got %r" % (outward,))
-        ops._device_mesh(self.vertices, self.faces, "Mesh.ambient_occlusion")
-        normals = float(outward) * ops.vertex_normals(self.vertices, self.faces)
-        return ops.mesh_occlusion(self.vertices, normals, self.vertices, self.faces, occlusion, seed=seed)
-
-    def render(self, rays_o, rays_d, passes=("color",), ambient=0.3, light=None, outward=1.0):
-        """Pictures of this mesh with everything it carries -- uvs and texture, normal map and its frame, occlusion map, vertex
-        colours, normals and occlusion -- ray cast on the device (ops.mesh_render on its device tensors; host arrays are refused
-        like any CPU tensor).  rays_o, rays_d float [n_images, H, W, 3] or [N, 3] -> {pass: tensor} with the rays' leading
-        shape; passes: any of "color", "shaded", "opacity", "rgba", "depth", "normal", "occlusion", "face" (ops.mesh_render has
-        their values and backgrounds).  outward: +1 when the faces wind counter-clockwise seen from outside, -1 otherwise
-        (TSR.WINDING_OUTWARD for the meshes of TSR.extract_meshes); it orients the face normal a mesh without a normal map
-        and vertex normals is shaded with.  A map without the uvs it belongs to is not used."""
-        has_uvs = self.uvs is not None
-        return ops.mesh_render_route()(rays_o, rays_d, self.vertices, self.faces, passes=passes, uvs=self.uvs,
-                                       texture=self.texture if has_uvs else None,
-                                       normal_map=self.normal_map if has_uvs else None, normal_map_space=self.normal_map_space,
-                                       corner_normals=self.corner_normals, corner_tangents=self.corner_tangents,
-                                       occlusion_map=self.occlusion_map if has_uvs else None, vertex_colors=self.vertex_colors,
-                                       vertex_normals=self.vertex_normals, vertex_occlusion=self.vertex_occlusion,
-                                       ambient=ambient, light=light, outward=outward)
-
-    def to_trimesh(self):  # pragma: no cover (trimesh is optional)
-        import trimesh
-
-        return trimesh.Trimesh(vertices=self.vertices, faces=self.faces, vertex_colors=self.vertex_colors)
-
-    def texture_image(self):
-        """The baked texture as a uint8 RGB PIL picture: floor(256 x) clipped to 0..255, no dither (deterministic)."""
-        from PIL import Image
-
-        from ..sf3d.bake import float32_to_uint8_np
-
-        if self.texture is None:
-            raise ValueError("Mesh.texture_image: this mesh has no baked texture (TSR.bake_texture)")
-        return Image.fromarray(float32_to_uint8_np(_host(self.texture).astype(np.float32), dither=False))
-
-    def normal_map_image(self):
-        """The baked normal map as a uint8 RGB PIL picture, as texture_image makes one: floor(256 x) clipped to 0..255, no dither."""
-        from PIL import Image
-
-        from ..sf3d.bake import float32_to_uint8_np
-
-        if self.normal_map is None:
-            raise ValueError("Mesh.normal_map_image: this mesh has no baked normal map (TSR.bake_normal_map)")
-        return Image.fromarray(float32_to_uint8_np(_host(self.normal_map).astype(np.float32), dither=False))
-
-    def occlusion_map_image(self):
-        """The baked occlusion map as a uint8 RGB PIL picture with three equal channels (glTF reads the red one), quantised as
-        normal_map_image quantises: floor(256 x) clipped to 0..255, no dither."""
-        from PIL import Image
-
-        from ..sf3d.bake import float32_to_uint8_np
-
-        if self.occlusion_map is None:
-            raise ValueError("Mesh.occlusion_map_image: this mesh has no baked occlusion map (TSR.bake_occlusion_map)")
-        grey = _host(self.occlusion_map).astype(np.float32)
-        return Image.fromarray(float32_to_uint8_np(np.repeat(grey[:, :, None], 3, axis=2), dither=False))
-
-    def export(self, path):
-        """Write .obj / .ply / .glb by extension (sculptmate_amd/meshio.py), the call upstream users make on the
-        trimesh object their extract_mesh returns.  A baked mesh (uvs + texture) goes out textured: .glb with TEXCOORD_0 and the
-        base-colour texture (glTF has one index per vertex, so positions are un-indexed to 3*Nf vertices there and only there),
-        .obj with `vt` lines, `f v/vt` faces and a .mtl + .png beside the file (positions stay shared).  vertex_normals, when the
-        mesh has them, go into every format (glTF NORMAL, `vn`, nx ny nz); the un-indexed .glb gets normals[faces] per corner.
-        vertex_occlusion, when set, goes into .ply (a float property `ao`) and .glb (the custom attribute _OCCLUSION; the
-        un-indexed .glb gets ao[faces] per corner); .obj has no slot for it.
-        A baked normal map (TSR.bake_normal_map; uvs + normal_map, with or without a texture) goes the textured way too.  A
-        tangent-space map: .glb gets normalTexture, NORMAL from corner_normals and TANGENT (VEC4) from corner_tangents, the frame
-        it was baked in; .obj gets `map_Bump -bm 1 NAME_normal.png` in the .mtl and the PNG beside it.  An object-space map is
-        never written as glTF's normalTexture (which is tangent space by definition): the .glb carries it as a further PNG image
-        that no material refers to, named in the mesh's extras ({"images": {"normal_map_object": index}}); the .obj gets the
-        same map_Bump line, to be read as object space by whoever asked for one.
-        An unbaked mesh with quads (extract_meshes(isosurface="surface_nets")) goes into .obj as quads, `f a b c d`; .ply, .glb
-        and every baked path write the triangles.
-        A baked occlusion map (TSR.bake_occlusion_map; uvs + occlusion_map, with or without a texture or normal map) goes the
-        textured way as well: .glb gets material.occlusionTexture (three equal channels; glTF reads the red one, strength at its
-        default of 1), .obj gets `map_Ka NAME_ao.png` in the .mtl and the PNG beside it."""
-        from .. import meshio
-
-        ext = str(path).rsplit(".", 1)[-1].lower()
-        writer = {"obj": meshio.write_obj, "ply": meshio.write_ply, "glb": meshio.write_glb}.get(ext)
-        if writer is None:
-            raise ValueError(f"unsupported mesh format .{ext} (obj, ply, glb)")
-        baked = self.texture is not None or self.normal_map is not None or self.occlusion_map is not None
-        if self.uvs is not None and baked and ext in ("glb", "obj"):
-            v, f, uv = _host(self.vertices), _host(self.faces), _host(self.uvs)
-            picture = None if self.texture is None else np.asarray(self.texture_image())
-            vn = None if self.vertex_normals is None else _host(self.vertex_normals)
-            bump = None if self.normal_map is None else np.asarray(self.normal_map_image())
-            shade = None if self.occlusion_map is None else np.asarray(self.occlusion_map_image())
-            if ext == "glb":
-                extra = {} if self.vertex_occlusion is None else {"occlusion": _host(self.vertex_occlusion)[f.reshape(-1)]}
-                if shade is not None:
-                    extra["occlusion_tex"] = shade
-                normals = None if vn is None else vn[f.reshape(-1)]
-                if bump is not None:   # the frame the map was baked in, per corner
-                    if self.corner_normals is not None:
-                        normals = _host(self.corner_normals)
-                    if self.normal_map_space == "tangent":
-                        extra["normal_tex"] = bump
-                        if self.corner_tangents is not None:
-                            extra["tangents"] = _host(self.corner_tangents)
-                    else:
-                        extra["extra_images"] = {"normal_map_object": bump}
-                meshio.write_glb(str(path), v[f.reshape(-1)], np.arange(f.size, dtype=np.int64).reshape(-1, 3), uvs=uv,
-                                 basecolor_tex=picture, normals=normals, **extra)
-            else:
-                extra = {} if bump is None else {"normal_map": bump}
-                if shade is not None:
-                    extra["occlusion_map"] = shade
-                meshio.write_obj_textured(str(path), v, f, uv, picture, normals=vn, **extra)
-            return
-        extra = {} if self.vertex_occlusion is None or ext == "obj" else {"occlusion": _host(self.vertex_occlusion)}
-        if ext == "obj" and self.quads is not None:   # the all-quad mesh of surface nets: `f a b c d` lines (.ply and .glb stay triangles)
-            extra["quads"] = _host(self.quads)
-        writer(str(path), self.vertices, self.faces, vertex_colors=self.vertex_colors, normals=self.vertex_normals, **extra)
-
-
-def _host(x):
-    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
-
-
-def _mesh_pass_to_pil(name, image):
-    """One view of a pass of TSR.render_mesh as a PIL image: the passes tsr/passes.py knows as it makes them, "shaded" as
-    "color" (clipped first: a light can exceed 1), "occlusion" as "opacity" (L), "face" as mode I (int32, untouched)."""
-    from PIL import Image
-
-    if name == "face":
-        return Image.fromarray(np.ascontiguousarray(image, dtype=np.int32))
-    if name == "shaded":
-        return render_pass_rules.to_pil("color", np.clip(np.nan_to_num(np.asarray(image, np.float32)), 0.0, 1.0))
-    return render_pass_rules.to_pil("opacity" if name == "occlusion" else name, image)
-
-
-class _PinnedPool:
-    """Pinned host buffers for the mesh hand-off, recycled by size class (next power of two of the byte count).  A pinned
-    allocation is a driver call of ~0.5 ms that can stall the device queue; mesh sizes differ from image to image, so an
-    exact-size cache never hits."""
-
-    def __init__(self):
-        self.free = {}
-
-    def take(self, shape, dtype):
-        n = 1
-        for d in shape:
-            n *= int(d)
-        esize = torch.empty((), dtype=dtype).element_size()
-        nbytes = n * esize
-        cap = 1 << (max(nbytes, 16) - 1).bit_length()   # at least one element of any dtype: an empty mesh array gets a real buffer
-        lst = self.free.get(cap)
-        buf = lst.pop() if lst else torch.empty(cap, dtype=torch.uint8, pin_memory=True)
-        view = buf[:max(nbytes, esize)].view(dtype)[:n].view(shape)
-        return _PinnedLease(self, cap, buf), view
-
-    def give(self, cap, buf):
-        self.free.setdefault(cap, []).append(buf)
-
-
-class _PinnedLease:
-    """One pinned buffer on loan.  It goes back to the pool when the lease dies -- or, once `hand_over(array)` has tied it to
-    the NumPy array that views it, when THAT array (and every view of it) is gone."""
-
-    def __init__(self, pool, cap, buf):
-        self.pool, self.cap, self.buf = pool, cap, buf
-
-    def hand_over(self, array):
-        import weakref
-
-        pool, cap, buf = self.pool, self.cap, self.buf
-        self.buf = None
-        weakref.finalize(array, pool.give, cap, buf)
-
-    def __del__(self):
-        try:
-            if self.buf is not None:
-                self.pool.give(self.cap, self.buf)
-        except Exception:  # interpreter shutdown
-            pass
-
-
-class PendingMesh:
-    """A mesh whose device -> pinned-host copy is in flight (TSR.run_async)."""
-
-    def __init__(self, host_tensors, done_event, leases=()):
-        self._host = host_tensors
-        self._done = done_event
-        self._leases = leases
-        self._mesh = None
-
-    def done(self) -> bool:
-        return self._done.query()
-
-    def result(self) -> Mesh:
-        """The arrays are views of pinned host buffers; a buffer returns to the pool when its array -- and every view or
-        slice taken from it -- has been released (it does not matter whether the Mesh object itself is kept)."""
-        if self._mesh is None:
-            self._done.synchronize()
-            arrays = [None if t is None else t.numpy() for t in self._host]
-            for lease, a in zip(self._leases, [a for a in arrays if a is not None]):
-                lease.hand_over(a)
-            # later calls return the SAME Mesh: a second set of views would carry no lease, and the buffers could go back to
-            # the pool (and be overwritten by a later run_async) while it is still alive
-            self._leases, self._host = (), None
-            self._mesh = Mesh(arrays[0], arrays[1], arrays[2], vertex_normals=arrays[3])
-        return self._mesh
 
 
 _MC_SIGN_PLANES = not _lib.form_has("SCULPT_MC_FORM", "noplanes")   # A/B: the plain count phase over the whole volume
@@ -475,6 +141,18 @@ class TriplaneNeRFRenderer:
                                         density_bias=self.cfg.density_bias, n_samples=self.num_samples_per_ray,
                                         want=render_pass_rules.wanted(passes))
         return render_pass_rules.finish(passes, rgb, extras)
+
+
+def _atlas_resolution(resolution, mesh, caller, maps):
+    """The resolution of a bake over `mesh`'s atlas: the one given; else, on a mesh that has uvs, the size of the first of
+    `maps` it carries; else 2048.  Below 1: ValueError in the caller's name."""
+    if resolution is None:
+        sized = [getattr(mesh, name) for name in maps if mesh.uvs is not None and getattr(mesh, name) is not None]
+        resolution = sized[0].shape[0] if sized else 2048
+    res = int(resolution)
+    if res < 1:
+        raise ValueError("TSR.%s: resolution must be positive" % caller)
+    return res
 
 
 def _bf(x, dev):
@@ -1109,6 +787,25 @@ class TSR(KernelEngine):
     __call__ = forward
 
     # ------------------------------------------------------------------ previews
+    def _need_weights(self, caller):
+        if self.decoder is None:
+            raise _lib.SculptError("TSR.%s: the model has no weights on a device yet (load_state_dict + to(device))" % caller)
+
+    def _field(self, scene_code, channel_last=True):
+        """The scene code as the kernels take it: an ops.ChannelLastPlanes as it is; a tensor [3, C, H, W] (or [1, 3, C, H, W]: the
+        leading 1 is dropped) on the model's device and, with channel_last, made into an ops.ChannelLastPlanes (one launch)."""
+        if isinstance(scene_code, ops.ChannelLastPlanes):
+            return scene_code
+        if scene_code.ndim == 5 and scene_code.shape[0] == 1:
+            scene_code = scene_code[0]
+        scene_code = scene_code.to(self.device)
+        return ops.ChannelLastPlanes(scene_code) if channel_last else scene_code
+
+    def _turntable_rays(self, n_views, elevation_deg, camera_distance, fovy_deg, height, width):
+        """The cameras of render, render_passes and render_mesh (get_spherical_cameras) on the device -> (rays_o, rays_d)."""
+        rays_o, rays_d = get_spherical_cameras(n_views, elevation_deg, camera_distance, fovy_deg, height, width)
+        return rays_o.to(self.device, non_blocking=True), rays_d.to(self.device, non_blocking=True)
+
     def render(self, scene_codes, n_views: int, elevation_deg: float = 0.0, camera_distance: float = 1.9, fovy_deg: float = 40.0,
                height: int = 256, width: int = 256, return_type: str = "pt"):
         """Upstream TripoSR's `model.render`: turntable pictures straight from the scene codes -> per scene code a list of n_views pictures.
@@ -1117,14 +814,12 @@ class TSR(KernelEngine):
         planes converted to channel-last once."""
         if return_type not in ("pt", "np", "pil"):
             raise ValueError("return_type must be 'pt', 'np' or 'pil'")
-        if self.decoder is None:
-            raise _lib.SculptError("TSR.render: the model has no weights on a device yet (load_state_dict + to(device))")
-        rays_o, rays_d = get_spherical_cameras(n_views, elevation_deg, camera_distance, fovy_deg, height, width)
-        rays_o, rays_d = rays_o.to(self.device, non_blocking=True), rays_d.to(self.device, non_blocking=True)
+        self._need_weights("render")
+        rays_o, rays_d = self._turntable_rays(n_views, elevation_deg, camera_distance, fovy_deg, height, width)
         images = []
         with torch.no_grad():
             for code in scene_codes:
-                planes = ops.ChannelLastPlanes(code.to(self.device))
+                planes = self._field(code)
                 views = self.renderer(self.decoder, planes, rays_o, rays_d)
                 if return_type == "pt":
                     images.append(list(views.unbind(0)))
@@ -1152,14 +847,12 @@ class TSR(KernelEngine):
         passes = render_pass_rules.check_passes(passes)
         if return_type not in render_pass_rules.RETURN_TYPES:
             raise ValueError("return_type must be 'pt', 'np' or 'pil'")
-        if self.decoder is None:
-            raise _lib.SculptError("TSR.render_passes: the model has no weights on a device yet (load_state_dict + to(device))")
-        rays_o, rays_d = get_spherical_cameras(n_views, elevation_deg, camera_distance, fovy_deg, height, width)
-        rays_o, rays_d = rays_o.to(self.device, non_blocking=True), rays_d.to(self.device, non_blocking=True)
+        self._need_weights("render_passes")
+        rays_o, rays_d = self._turntable_rays(n_views, elevation_deg, camera_distance, fovy_deg, height, width)
         images = []
         with torch.no_grad():
             for code in scene_codes:
-                planes = ops.ChannelLastPlanes(code.to(self.device))
+                planes = self._field(code)
                 views = self.renderer.render_passes(self.decoder, planes, rays_o, rays_d, passes)
                 images.append(render_pass_rules.convert(views, return_type))
         return images
@@ -1182,14 +875,10 @@ class TSR(KernelEngine):
             raise ValueError("return_type must be 'pt', 'np' or 'pil'")
         if self.device is None:
             raise _lib.SculptError("TSR.render_mesh: the model is on no device yet (to(device))")
-        rays_o, rays_d = get_spherical_cameras(n_views, elevation_deg, camera_distance, fovy_deg, height, width)
-        rays_o, rays_d = rays_o.to(self.device, non_blocking=True), rays_d.to(self.device, non_blocking=True)
-        on_device = Mesh(_f32(mesh.vertices, self.device), torch.as_tensor(mesh.faces).to(self.device).contiguous())
-        for name in ("vertex_colors", "uvs", "texture", "vertex_normals", "vertex_occlusion", "normal_map", "corner_normals",
-                     "corner_tangents", "occlusion_map"):
-            value = getattr(mesh, name)
-            setattr(on_device, name, None if value is None else _f32(value, self.device))
-        on_device.normal_map_space = mesh.normal_map_space
+        rays_o, rays_d = self._turntable_rays(n_views, elevation_deg, camera_distance, fovy_deg, height, width)
+        on_device = mesh._derive(_f32(mesh.vertices, self.device), torch.as_tensor(mesh.faces).to(self.device).contiguous(),
+                                 normal_map_space=mesh.normal_map_space,
+                                 **{name: None if getattr(mesh, name) is None else _f32(getattr(mesh, name), self.device) for name in TENSOR_FIELDS})
         with torch.no_grad():
             views = on_device.render(rays_o, rays_d, passes=passes, ambient=ambient, light=light, outward=self.WINDING_OUTWARD)
         if return_type == "pt":
@@ -1203,12 +892,8 @@ class TSR(KernelEngine):
         """Outward unit normals of the density field of `scene_code` ([3, C, H, W] or an ops.ChannelLastPlanes) at `points`
         [..., 3] in world units: -grad / |grad| of the raw density, one launch (ops.field_normals) -> f32 [..., 3] on the
         device, exactly 0 where the gradient is 0 (a point outside the scene's box on every axis)."""
-        if self.decoder is None:
-            raise _lib.SculptError("TSR.field_normals: the model has no weights on a device yet (load_state_dict + to(device))")
-        if not isinstance(scene_code, ops.ChannelLastPlanes):
-            if scene_code.ndim == 5 and scene_code.shape[0] == 1:
-                scene_code = scene_code[0]
-            scene_code = scene_code.to(self.device)
+        self._need_weights("field_normals")
+        scene_code = self._field(scene_code, channel_last=False)   # the renderer takes the plain tensor
         with torch.no_grad():
             return self.renderer.query_normals(self.decoder, _f32(points, self.device), scene_code)
 
@@ -1227,19 +912,15 @@ class TSR(KernelEngine):
         deterministic stand-in) -> ops.bake_rasterize on the per-corner UVs -> ops.bake_scene_color (one fused launch) ->
         ops.dilate_fill with res // 150 iterations, the padding rule of the SF3D bake.  Nothing here waits for the device (the
         box-projection unwrapper itself reads two small sums back)."""
-        if self.decoder is None:
-            raise _lib.SculptError("TSR.bake_texture: the model has no weights on a device yet (load_state_dict + to(device))")
+        self._need_weights("bake_texture")
         res = int(texture_resolution)
         if res < 1:
             raise ValueError("TSR.bake_texture: texture_resolution must be positive")
-        if scene_code.ndim == 5 and scene_code.shape[0] == 1:
-            scene_code = scene_code[0]
         with torch.no_grad():
             v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper)
-            planes = scene_code if isinstance(scene_code, ops.ChannelLastPlanes) else ops.ChannelLastPlanes(scene_code.to(self.device))
-            color, mask = ops.bake_scene_color(planes, self.decoder, v, f, rast, radius=self.renderer.cfg.radius)
+            color, mask = ops.bake_scene_color(self._field(scene_code), self.decoder, v, f, rast, radius=self.renderer.cfg.radius)
             color = self._padded(color, mask, res)
-        return Mesh(mesh.vertices, mesh.faces, None, uvs=uv, texture=color)
+        return Mesh(mesh.vertices, mesh.faces, None, uvs=uv, texture=color)   # nothing of `mesh` but its geometry is carried
 
     def _atlas(self, mesh, res, island_padding, unwrapper, keep_uvs=False):
         """What the two bakes share: the mesh on the device, its per-corner UVs (the mesh's own with keep_uvs, when it has
@@ -1291,21 +972,13 @@ class TSR(KernelEngine):
         device.  Nothing here waits for the device beyond what the unwrapper reads back."""
         if space not in self.NORMAL_MAP_FLAT:
             raise ValueError("TSR.bake_normal_map: space must be 'tangent' or 'object', got %r" % (space,))
-        if self.decoder is None:
-            raise _lib.SculptError("TSR.bake_normal_map: the model has no weights on a device yet (load_state_dict + to(device))")
-        if resolution is None:
-            resolution = mesh.texture.shape[0] if (mesh.uvs is not None and mesh.texture is not None) else 2048
-        res = int(resolution)
-        if res < 1:
-            raise ValueError("TSR.bake_normal_map: resolution must be positive")
-        if not isinstance(scene_code, ops.ChannelLastPlanes) and scene_code.ndim == 5 and scene_code.shape[0] == 1:
-            scene_code = scene_code[0]
+        self._need_weights("bake_normal_map")
+        res = _atlas_resolution(resolution, mesh, "bake_normal_map", ("texture",))
         with torch.no_grad():
             v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper, keep_uvs=True)
             corner_n = (self.WINDING_OUTWARD * ops.vertex_normals(v, f))[f.reshape(-1).long()].contiguous()
             corner_t = ops.corner_tangents(v, f, uv, corner_n)
-            planes = scene_code if isinstance(scene_code, ops.ChannelLastPlanes) else ops.ChannelLastPlanes(scene_code.to(self.device))
-            n, mask = ops.bake_scene_normal(planes, self.decoder, v, f, rast, radius=self.renderer.cfg.radius,
+            n, mask = ops.bake_scene_normal(self._field(scene_code), self.decoder, v, f, rast, radius=self.renderer.cfg.radius,
                                             frame=(corner_n, corner_t) if space == "tangent" else None)
             flat = torch.tensor(self.NORMAL_MAP_FLAT[space], dtype=torch.float32, device=self.device)
             # dilate_fill averages over a texel's neighbourhood as it finds it, so the image is 0 outside the charts going in; an
@@ -1313,11 +986,9 @@ class TSR(KernelEngine):
             # coming out is one the padding did not reach
             coded = self._padded(torch.where(mask[..., None], 0.5 + 0.5 * n, torch.zeros_like(n)), mask, res)
             coded = torch.where((coded != 0).any(-1, keepdim=True), coded, flat)
-        out = Mesh(mesh.vertices, mesh.faces, mesh.vertex_colors, uvs=mesh.uvs if mesh.uvs is not None else uv, texture=mesh.texture,
-                   vertex_normals=mesh.vertex_normals, vertex_occlusion=mesh.vertex_occlusion)
-        out.normal_map, out.normal_map_space, out.corner_normals, out.corner_tangents = coded, space, corner_n, corner_t
-        out.occlusion_map, out.occlusion_map_rule = mesh.occlusion_map, mesh.occlusion_map_rule
-        return out
+        return mesh._derive(mesh.vertices, mesh.faces, ("vertex_colors", "texture", "vertex_normals", "vertex_occlusion", "occlusion_map"),
+                            uvs=mesh.uvs if mesh.uvs is not None else uv, normal_map=coded, normal_map_space=space,
+                            corner_normals=corner_n, corner_tangents=corner_t)
 
     def bake_occlusion_map(self, mesh: Mesh, source=None, resolution=None, occlusion=True, cage=None, seed=0,
                            island_padding: float = 0.02, unwrapper=None) -> Mesh:
@@ -1343,34 +1014,20 @@ class TSR(KernelEngine):
             raise ValueError("TSR.bake_occlusion_map: source must be a Mesh or None, got %r" % (type(source).__name__,))
         if source is None and cage is not None:
             raise ValueError("TSR.bake_occlusion_map: cage snaps the texels onto a source; without a source it must be None")
-        if resolution is None:
-            if mesh.uvs is not None and mesh.texture is not None:
-                resolution = mesh.texture.shape[0]
-            elif mesh.uvs is not None and mesh.normal_map is not None:
-                resolution = mesh.normal_map.shape[0]
-            else:
-                resolution = 2048
-        res = int(resolution)
-        if res < 1:
-            raise ValueError("TSR.bake_occlusion_map: resolution must be positive")
+        res = _atlas_resolution(resolution, mesh, "bake_occlusion_map", ("texture", "normal_map"))
         with torch.no_grad():
             v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper, keep_uvs=True)
             normals = (self.WINDING_OUTWARD * ops.vertex_normals(v, f)).contiguous()
-            src = None
-            if source is not None:
-                src = (_f32(source.vertices, self.device), torch.as_tensor(source.faces).to(self.device).contiguous())
+            src = None if source is None else (_f32(source.vertices, self.device), torch.as_tensor(source.faces).to(self.device).contiguous())
             ao, mask = ops.bake_occlusion_route()(v, f, normals, rast, occlusion=rule, seed=seed, source=src, cage=cage)
             valid = mask & torch.isfinite(ao)
             shifted = torch.where(valid, ao + 1.0, torch.zeros_like(ao))
             spread = self._padded(shifted[..., None].expand(res, res, 3), valid, res)[..., 0]
             padded = torch.where(spread != 0, (spread - 1.0).clamp(0.0, 1.0), torch.ones_like(ao))
             ao_map = torch.where(valid, ao, torch.where(mask, torch.ones_like(ao), padded)).contiguous()
-        out = Mesh(mesh.vertices, mesh.faces, mesh.vertex_colors, uvs=mesh.uvs if mesh.uvs is not None else uv, texture=mesh.texture,
-                   vertex_normals=mesh.vertex_normals, vertex_occlusion=mesh.vertex_occlusion)
-        out.normal_map, out.normal_map_space = mesh.normal_map, mesh.normal_map_space
-        out.corner_normals, out.corner_tangents = mesh.corner_normals, mesh.corner_tangents
-        out.occlusion_map, out.occlusion_map_rule = ao_map, rule
-        return out
+        return mesh._derive(mesh.vertices, mesh.faces, ("vertex_colors", "texture", "vertex_normals", "vertex_occlusion", "normal_map",
+                                                        "corner_normals", "corner_tangents"),
+                            uvs=mesh.uvs if mesh.uvs is not None else uv, occlusion_map=ao_map, occlusion_map_rule=rule)
 
     def _projected(self, v_pos, t_pos_idx, planes, threshold, project, resolution):
         """ops.mesh_project with this model's field: target = float32(ln(threshold) - density_bias) (computed in double),
@@ -1393,8 +1050,7 @@ class TSR(KernelEngine):
         steps_cells = ops.project_rule(project)   # a ValueError before anything is launched
         if not threshold > 0:
             raise ValueError("TSR.project_mesh: threshold must be positive, got %r" % (threshold,))
-        if self.decoder is None:
-            raise _lib.SculptError("TSR.project_mesh: the model has no weights on a device yet (load_state_dict + to(device))")
+        self._need_weights("project_mesh")
         if resolution is None:
             if self.isosurface_helper is None:
                 raise ValueError("TSR.project_mesh: no resolution given and no marching-cubes resolution set yet")
@@ -1402,16 +1058,12 @@ class TSR(KernelEngine):
         if int(resolution) < 2:
             raise ValueError("TSR.project_mesh: resolution must be at least 2, got %r" % (resolution,))
         if not isinstance(scene_code, ops.ChannelLastPlanes):
-            if scene_code.ndim == 5 and scene_code.shape[0] == 1:
-                scene_code = scene_code[0]
-            scene_code = scene_code.to(self.device).contiguous()
+            scene_code = self._field(scene_code, channel_last=False).contiguous()
         with torch.no_grad():
             v = _f32(mesh.vertices, self.device)
             f = torch.as_tensor(mesh.faces).to(self.device).contiguous()
             v = self._projected(v, f, scene_code, threshold, steps_cells, resolution)
-        out = Mesh(v, mesh.faces, mesh.vertex_colors, uvs=mesh.uvs, texture=mesh.texture)
-        out.quads = mesh.quads
-        return out
+        return mesh._derive(v, mesh.faces, ("vertex_colors", "uvs", "texture", "quads"))
 
     def extract_meshes(self, scene_codes, enable_texture=False, resolution: int = 256, threshold: float = 25.0,
                        x_range=None, density_events=None, bake_texture: int = 0, normals=None, isosurface="marching_cubes",
