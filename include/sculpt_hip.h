@@ -1130,6 +1130,65 @@ int sculpt_subdiv_classify(const sculpt_rmd_topo_t *topo, const float *P, int32_
 int sculpt_subdiv_loop(const sculpt_rmd_topo_t *topo, const int32_t *cls, const float *rows, const int32_t *rank_incl, const float *A,
                        int channels, float *Po, int32_t *Fo, float *Ao, sculpt_stream_t stream);
 
+/* Catmull-Clark subdivision ON THE DEVICE, one level per pair of calls, triangles or quads in and all quads out
+ * (csrc/mesh_catmull.hip; sf3d/remesh_device.py catmull_clark_device, ops.mesh_catmull_clark).  DEVICE
+ * pointers, asynchronous on `stream`, no host wait.  Added without a version change (new symbols only).  Compiled without
+ * floating-point contraction and restated bit for bit in tests/_catmullref.py.
+ * THE RULE.  P fp32 [nv][3], F int32 [nf][k], k = 3 or 4, uniform per call.  Half-edge h = k f + c runs F[f][c] ->
+ * F[f][(c + 1) % k].  An edge is the unordered pair of its ends; edge e (0-based) is its rank by first appearance over
+ * h = 0, 1, ...; with two faces it is interior, with one a border edge, with three or more non-manifold; its faces are listed in
+ * half-edge order.  Every component below is computed in fp64 from the fp32 values with exactly the operations written, left
+ * to right, without contraction, and rounded once to fp32; where a face point appears inside another rule it is the unrounded
+ * fp64 value of the same operations.
+ *   numbering    old vertices keep 0 .. nv - 1; the face point of f is nv + f; the edge point of e is nv + nf + e.
+ *                nv' = nv + nf + ne, nq' = k nf.
+ *   quads        corner c of face f becomes row k f + c =
+ *                    (F[f][c], edge point of half-edge (f, c), nv + f, edge point of half-edge (f, (c - 1) % k));
+ *                orientation is kept.
+ *   face point   Fp(f) = (((P[c0] + P[c1]) + P[c2]) [+ P[c3]]) / (double)k
+ *   edge point   of {u, v}: interior, faces f0, f1:  0.25 * ((P[u] + P[v]) + (Fp(f0) + Fp(f1)));
+ *                border or non-manifold:             0.5 * (P[u] + P[v])
+ *   old vertex   u with n corners in the faces (its fan, in ascending corner index k f + c):
+ *                  n == 0, a non-manifold edge at u, or border edges at u neither 0 nor 2 (a corner): its bits;
+ *                  two border edges with other ends a < b (a crease): 0.75 * P[u] + 0.125 * (P[a] + P[b]);
+ *                  otherwise, m = (double)n:  ((m - 2.0) * P[u] + (0.5 * SN + SQ) / m) / m, where SN is the sum over the
+ *                  fan in order of P[F[f][(c + 1) % k]] and then P[F[f][(c - 1) % k]] of each corner (f, c), starting as the
+ *                  first term (every neighbour enters twice: no dependence on orientation), and SQ the sum over the fan of
+ *                  Fp(f), starting as the first term.  Any valence follows these rules.
+ *   attributes   [nv][channels], 1 <= channels <= 8, go through the same masks.
+ *   triangles    rows 2 q, 2 q + 1 split quad q = (q0, q1, q2, q3) along its shorter diagonal, sculpt_surface_nets_emit's
+ *                split on the REFINED fp32 positions: d02 = |P'[q0] - P'[q2]|^2, d13 = |P'[q1] - P'[q3]|^2 in fp64 as
+ *                (dx dx + dy dy) + dz dz; d13 < d02: (q0, q1, q3), (q1, q2, q3); otherwise (a tie included): (q0, q1, q2),
+ *                (q0, q2, q3).
+ * THE CALLS.  The topology is the triangle passes' (sorted half-edge keys, vertex -> corner CSR) for k corners; the caller
+ * sorts and scans as for sculpt_rmd_topo_t, and sculpt_rmd_edge_heads / sculpt_rmd_edge_fill serve any k (they take nh = k nf).
+ *   sculpt_catmull_validate        status bit 0: face index out of range, 1: repeated index in a face, 2: non-finite position
+ *   sculpt_catmull_halfedge_keys   keys [k nf]: (min << 32 | max) of every half-edge's ends
+ *   sculpt_catmull_first_halfedge  first [k nf] = 1 where h is the lowest half-edge of its edge (rank_incl: its inclusive
+ *                                  prefix sum; the edge whose first half-edge is h has rank rank_incl[h] - 1)
+ *   sculpt_catmull_classify        cls [nv][4] int32 and rows [nv][4] floats, as sculpt_subdiv_classify writes them
+ *   sculpt_catmull_refine          ONE launch: Po [nv + nf + ne][3], Qo [k nf][4], To [2 k nf][3] and, with A [nv][channels]
+ *                                  (A and Ao both or neither), Ao [nv + nf + ne][channels].  The outputs must not alias the inputs.
+ * A null topology or array, a misaligned buffer, k other than 3 or 4, channels out of range and counts whose level would leave
+ * int32 (nv + nf + ne, 4 k nf) are refused with an error code and a message; nf == 0 launches nothing (the caller returns copies). */
+typedef struct sculpt_catmull_topo {
+    const int32_t *F;      /* [nf][k] */
+    const int64_t *skeys;  /* [k nf] half-edge keys, sorted */
+    const int32_t *she;    /* [k nf] half-edge ids in sorted order */
+    const int32_t *es;     /* [ne + 1] first sorted index of every edge (in sorted-key order) */
+    const int32_t *fe;     /* [k nf] edge of every half-edge */
+    const int32_t *vfs;    /* [nv + 1] vertex -> corner offsets */
+    const int32_t *vfc;    /* [k nf] corners (k f + c) by vertex, in corner order */
+    int64_t nf, nv, ne;
+    int32_t k;
+} sculpt_catmull_topo_t;
+int sculpt_catmull_validate(const float *P, int64_t nv, const int32_t *F, int64_t nf, int k, int32_t *status, sculpt_stream_t stream);
+int sculpt_catmull_halfedge_keys(const int32_t *F, int64_t nf, int k, int64_t *keys, sculpt_stream_t stream);
+int sculpt_catmull_first_halfedge(const sculpt_catmull_topo_t *topo, int32_t *first, sculpt_stream_t stream);
+int sculpt_catmull_classify(const sculpt_catmull_topo_t *topo, const float *P, int32_t *cls, float *rows, sculpt_stream_t stream);
+int sculpt_catmull_refine(const sculpt_catmull_topo_t *topo, const int32_t *cls, const float *rows, const int32_t *rank_incl,
+                          const float *A, int channels, float *Po, int32_t *Qo, int32_t *To, float *Ao, sculpt_stream_t stream);
+
 /* Distance between triangle surfaces ON THE DEVICE (csrc/mesh_distance.hip; ops.mesh_closest_points, ops.mesh_sample_surface,
  * ops.mesh_distance).  DEVICE pointers (params_host excepted), asynchronous on `stream`, no host wait.
  * Compiled without floating-point contraction and restated bit for bit in tests/_distref.py.  Added without a version change

@@ -222,6 +222,11 @@ SIGNATURES = {
     "sculpt_smooth_taubin": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
     "sculpt_subdiv_classify": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "sculpt_subdiv_loop": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "sculpt_catmull_validate": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp]),
+    "sculpt_catmull_halfedge_keys": (_i, [_vp, _i64, _i, _vp, _vp]),
+    "sculpt_catmull_first_halfedge": (_i, [_vp, _vp, _vp]),
+    "sculpt_catmull_classify": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "sculpt_catmull_refine": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_surface_closest": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
     "sculpt_surface_cells": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "sculpt_surface_pack": (_i, [_vp, _vp, _i64, _vp, _vp]),
@@ -252,6 +257,12 @@ class RmdTopo(ctypes.Structure):
     """sculpt_rmd_topo_t (include/sculpt_hip.h)."""
     _fields_ = [("F", _vp), ("skeys", _vp), ("she", _vp), ("es", _vp), ("fe", _vp), ("vfs", _vp), ("vfc", _vp), ("bnd", _vp),
                 ("nf", _i64), ("nv", _i64), ("ne", _i64)]
+
+
+class CatmullTopo(ctypes.Structure):
+    """sculpt_catmull_topo_t (include/sculpt_hip.h)."""
+    _fields_ = [("F", _vp), ("skeys", _vp), ("she", _vp), ("es", _vp), ("fe", _vp), ("vfs", _vp), ("vfc", _vp),
+                ("nf", _i64), ("nv", _i64), ("ne", _i64), ("k", ctypes.c_int32)]
 
 
 class RenderMaterial(ctypes.Structure):

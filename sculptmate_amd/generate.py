@@ -44,7 +44,9 @@ class TripoGenerator(GeneratorFacade):
     (TSR.extract_meshes; ops.mesh_project).
     `subdivide` (default None): an int n in 1 .. 6 (levels of the Loop scheme) or a tuple (n, "loop" | "midpoint") refines every
     mesh 1 -> 4 faces per level on the device, after simplify and before project: the simplified mesh becomes the control cage
-    of a semi-regular, multires-friendly surface (TSR.extract_meshes; ops.mesh_subdivide).
+    of a semi-regular, multires-friendly surface (TSR.extract_meshes; ops.mesh_subdivide).  (n, "catmull_clark") is the
+    all-quad scheme of Blender's Subdivision Surface and Multires modifiers: it refines the quads of isosurface="surface_nets",
+    or turns every triangle into three quads, and the plain sink receives the refined quads (ops.mesh_catmull_clark).
     `isosurface` (default "marching_cubes"): "surface_nets" extracts every mesh with surface nets on the device instead -- one
     vertex inside every cell the surface passes through, an all-quad mesh (Mesh.quads, which the plain Blender sink and
     Mesh.export's .obj receive) beside its triangles, no sliver triangles (TSR.extract_meshes; ops.surface_nets).

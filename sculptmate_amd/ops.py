@@ -760,20 +760,20 @@ def mesh_smooth(vertices, faces, smooth):
 # mesh subdivision: the Loop scheme (csrc/mesh_subdivide.hip, sf3d/remesh_device.py loop_subdivide_device)
 # ----------------------------------------------------------------------------------------------
 SUBDIVIDE_MAX_LEVELS = 6
-SUBDIVIDE_SCHEMES = ("loop", "midpoint")
+SUBDIVIDE_SCHEMES = ("loop", "midpoint", "catmull_clark")
 
 
 def subdivide_rule(subdivide):
     """`subdivide` of mesh_subdivide -> (levels, scheme): an int n, 1 <= n <= 6 (n levels of the Loop scheme), or a tuple
-    (n, "loop" | "midpoint").  Anything else -- bool, float, 0, 7, NaN, another string or length -- is a ValueError, raised here,
-    before anything is launched."""
+    (n, "loop" | "midpoint" | "catmull_clark").  Anything else -- bool, float, 0, 7, NaN, another string (the hyphenated
+    "catmull-clark" too) or length -- is a ValueError, raised here, before anything is launched."""
     if _is_count(subdivide, 1, SUBDIVIDE_MAX_LEVELS):
         return int(subdivide), "loop"
     if (isinstance(subdivide, tuple) and len(subdivide) == 2 and _is_count(subdivide[0], 1, SUBDIVIDE_MAX_LEVELS)
             and isinstance(subdivide[1], str) and subdivide[1] in SUBDIVIDE_SCHEMES):
         return int(subdivide[0]), subdivide[1]
-    raise ValueError("subdivide must be an int in 1 .. %d (levels of the Loop scheme) or (levels, 'loop' | 'midpoint'), got %r"
-                     % (SUBDIVIDE_MAX_LEVELS, subdivide))
+    raise ValueError("subdivide must be an int in 1 .. %d (levels of the Loop scheme) or (levels, 'loop' | 'midpoint' | "
+                     "'catmull_clark'), got %r" % (SUBDIVIDE_MAX_LEVELS, subdivide))
 
 
 def mesh_subdivide(vertices, faces, subdivide, attributes=None):
@@ -797,6 +797,8 @@ def mesh_subdivide(vertices, faces, subdivide, attributes=None):
       - attributes go through the same masks, so values in [0, 1] stay there up to one ulp;
       - scheme "midpoint": subdivide_device itself -- every new vertex the fp32 midpoint, old vertices unmoved, attributes
         refined the same way (linearly);
+      - scheme "catmull_clark": (vertices', triangles', attributes') of mesh_catmull_clark on the triangles given -- another
+        rule, numbering and face count (6 x 4^(levels - 1) triangles per face); call mesh_catmull_clark for the quads;
       - the inputs are untouched; a face index out of range, a repeated index in a face and a non-finite position are a
         SculptError, and so is a level whose 3 x faces would leave int32;
       - Nf == 0: copies;
@@ -808,6 +810,9 @@ def mesh_subdivide(vertices, faces, subdivide, attributes=None):
     from .sf3d import remesh_device as rmd
 
     _device_mesh(vertices, faces, "mesh_subdivide")
+    if scheme == "catmull_clark":
+        v, _, t, a = mesh_catmull_clark(vertices, faces, levels, attributes)
+        return v, t, a
     if scheme == "loop":
         v, f, a = rmd.loop_subdivide_device(vertices, faces, levels, attributes)
         return v, f.to(faces.dtype), a
@@ -821,6 +826,46 @@ def mesh_subdivide(vertices, faces, subdivide, attributes=None):
         cols = [torch.nn.functional.pad(a[:, c:c + 3], (0, max(0, c + 3 - a.shape[1]))) for c in range(0, a.shape[1], 3)]
         a = torch.cat([rmd.subdivide_device(x, faces, levels)[0] for x in cols], 1)[:, :a.shape[1]].contiguous()
     return v, f.to(faces.dtype), a
+
+
+def mesh_catmull_clark(vertices, faces, levels, attributes=None):
+    """Catmull-Clark subdivision on the device: the mesh of triangles or of quads taken as a control cage and refined into an
+    ALL-QUAD mesh, the scheme of Blender's Subdivision Surface and Multires modifiers (csrc/mesh_catmull.hip).
+    vertices float [Nv, 3], faces int32 / int64 [Nf, 3] or [Nf, 4] (one width per call; only the first level can see
+    triangles), levels 1 .. 6, attributes None or float [Nv, C] with 1 <= C <= 8 (device tensors; CPU tensors are refused).
+    -> (vertices' f32, quads' [.., 4] and triangles' [.., 3] in faces' dtype, attributes' f32 or None), new tensors.  Contract,
+    per level on faces of k corners (include/sculpt_hip.h states the rule operation for operation):
+      - old vertices keep their indices, the face point of f is Nv + f, the edge point of edge e -- e its rank by first
+        appearance over the half-edges k f + c -- is Nv + Nf + e; corner c of face f becomes quad k f + c = (F[f, c], edge point
+        of half-edge (f, c), face point, edge point of half-edge (f, c - 1)); orientation is kept; Nv' = Nv + Nf + Ne,
+        Nq' = k Nf: a triangle becomes three quads, a quad four;
+      - an edge is interior with two faces, a border edge with one, non-manifold with three or more; every component is
+        computed in fp64 from the fp32 values with exactly the operations written, left to right, and rounded once to fp32
+        (a face point inside another rule is its unrounded fp64 value);
+      - face point: (((P[c0] + P[c1]) + P[c2]) [+ P[c3]]) / k;  edge point of an interior edge {u, v} with faces f0, f1:
+        0.25 * ((P[u] + P[v]) + (Fp(f0) + Fp(f1))), of a border or non-manifold edge: 0.5 * (P[u] + P[v]);
+      - an old vertex u with n corners in the faces: no face, a non-manifold edge at u, or a number of border edges at u that
+        is neither 0 nor 2 (a corner) -- it keeps its bits; exactly two border edges with other ends a < b (a crease) --
+        0.75 * P[u] + 0.125 * (P[a] + P[b]); otherwise ((n - 2.0) * P[u] + (0.5 * SN + SQ) / n) / n, SN the sum over u's corners
+        in ascending order of the face's next and then its last vertex around u (every neighbour enters twice, so the result
+        does not depend on how the faces wind), SQ the sum of their face points.  A vertex of any valence follows these rules;
+      - attributes go through the same masks;
+      - triangles' rows 2 q, 2 q + 1 split quad q along its shorter diagonal, the rule of ops.surface_nets on the refined fp32
+        positions: d13 < d02 gives (q0, q1, q3), (q1, q2, q3), otherwise (a tie included) (q0, q1, q2), (q0, q2, q3);
+      - the inputs are untouched; a CPU tensor, a face index out of range, a repeated index in a face, a non-finite position,
+        another face width and a level whose 4 x quads would leave int32 are a SculptError;
+      - Nf == 0: copies, empty quads and empty triangles;
+      - deterministic: integer atomics for the classification, a fixed-order gather in fp64 without contraction for the
+        values; two calls give the same bits (tests/_catmullref.py restates it bit for bit);
+      - two launches per level (classify, then one fused launch for positions, attributes, quads and triangles) behind the
+        sorts; per level the host reads back the edge count of the level's one topology construction, and before the first
+        level the input check's status.  The counts are in sf3d.remesh_device.last_stats()."""
+    from .sf3d import remesh_device as rmd
+
+    if not _is_count(levels, 1, SUBDIVIDE_MAX_LEVELS):
+        raise SculptError("mesh_catmull_clark: levels must be an int in 1 .. %d, got %r" % (SUBDIVIDE_MAX_LEVELS, levels))
+    v, q, t, a = rmd.catmull_clark_device(vertices, faces, int(levels), attributes)
+    return v, q.to(faces.dtype), t.to(faces.dtype), a
 
 
 # ----------------------------------------------------------------------------------------------

@@ -418,6 +418,108 @@ def loop_subdivide_device(v, f, levels, attributes=None):
     return P, F, A
 
 
+class _PolyTopo:
+    """Edge table and vertex -> corner CSR of the faces F [nf, k], k = 3 or 4 (sculpt_catmull_topo_t): _Topo's construction for
+    k corners, without the boundary flags -- the Catmull-Clark kernels classify by the edges' face counts."""
+
+    def __init__(self, ctx, F, nv):
+        ctx.stats["passes"] += 1
+        dev, s = F.device, ctx.stream
+        nf, k = F.shape
+        nh = k * nf
+        self.F, self.nf, self.nv, self.k = F, nf, nv, k
+        keys = torch.empty(nh, dtype=torch.int64, device=dev)
+        check(lib.sculpt_catmull_halfedge_keys(_p(F), nf, k, _p(keys), s))
+        self.skeys, sperm = torch.sort(keys, stable=True)
+        head = torch.empty(nh, dtype=torch.int32, device=dev)
+        check(lib.sculpt_rmd_edge_heads(_p(self.skeys), nh, _p(head), s))
+        eid = torch.cumsum(head, 0, dtype=torch.int32)
+        self.she = torch.empty(nh, dtype=torch.int32, device=dev)
+        self.fe = torch.empty(nh, dtype=torch.int32, device=dev)
+        self.es = torch.empty(nh + 1, dtype=torch.int32, device=dev)  # es[ne] = k nf
+        check(lib.sculpt_rmd_edge_fill(_p(sperm), _p(eid), nh, _p(self.she), _p(self.fe), _p(self.es), s))
+        self.ne = ctx.read(eid[-1:])
+        sv, vperm = torch.sort(F.reshape(-1), stable=True)
+        self.vfc = vperm.to(torch.int32)
+        self.vfs = torch.searchsorted(sv, torch.arange(nv + 1, dtype=torch.int32, device=dev), out_int32=True)
+        self.c = _lib.CatmullTopo(F.data_ptr(), self.skeys.data_ptr(), self.she.data_ptr(), self.es.data_ptr(), self.fe.data_ptr(),
+                                  self.vfs.data_ptr(), self.vfc.data_ptr(), nf, nv, self.ne, k)
+
+    def ref(self):
+        return ctypes.c_void_p(ctypes.addressof(self.c))
+
+
+def _catmull_level(ctx, T, P, A=None):
+    """One Catmull-Clark level on the topology T of (P, T.F): the numbering, then the two launches of csrc/mesh_catmull.hip ->
+    (P' [nv + nf + ne, 3], quads [k nf, 4], triangles [2 k nf, 3], A' or None); nothing is read back."""
+    dev, s, nv = P.device, ctx.stream, T.nv
+    first = torch.empty(T.k * T.nf, dtype=torch.int32, device=dev)
+    check(lib.sculpt_catmull_first_halfedge(T.ref(), _p(first), s))
+    rank = torch.cumsum(first, 0, dtype=torch.int32)
+    cls = torch.empty((nv, 4), dtype=torch.int32, device=dev)
+    rows = torch.empty((nv, 4), dtype=torch.float32, device=dev)
+    check(lib.sculpt_catmull_classify(T.ref(), _p(P), _p(cls), _p(rows), s))
+    n = nv + T.nf + T.ne
+    Po = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    Qo = torch.empty((T.k * T.nf, 4), dtype=torch.int32, device=dev)
+    To = torch.empty((2 * T.k * T.nf, 3), dtype=torch.int32, device=dev)
+    Ao = None if A is None else torch.empty((n, A.shape[1]), dtype=torch.float32, device=dev)
+    check(lib.sculpt_catmull_refine(T.ref(), _p(cls), _p(rows), _p(rank), _p(A), 0 if A is None else A.shape[1], _p(Po), _p(Qo), _p(To),
+                                    _p(Ao), s))
+    return Po, Qo, To, Ao
+
+
+def catmull_clark_device(v, f, levels, attributes=None):
+    """`levels` (1 .. 6) levels of Catmull-Clark subdivision (csrc/mesh_catmull.hip; the rule is in include/sculpt_hip.h, the
+    contract in ops.mesh_catmull_clark).  f: [nf, 3] or [nf, 4]; only the first level can see triangles.  -> (v f32 [n, 3],
+    quads int32 [m, 4], triangles int32 [2 m, 3], attributes f32 [n, C] or None), new tensors.  One topology construction per
+    level, whose edge count is the level's one readback; before the first, the input check's status.  No faces: copies, and
+    empty quads and triangles."""
+    who = "mesh_catmull_clark"
+    levels = int(levels)
+    if not 1 <= levels <= 6:
+        raise SculptError("%s: levels=%d out of range (1 .. 6)" % (who, levels))
+    for t, name in ((v, "vertices"), (f, "faces")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise SculptError("%s: %s must be a CUDA/HIP tensor (no CPU fallback)" % (who, name))
+    if not v.dtype.is_floating_point or v.dim() != 2 or v.shape[1] != 3:
+        raise SculptError("%s: vertices must be float [Nv, 3], got %s %s" % (who, v.dtype, tuple(v.shape)))
+    if f.dtype not in (torch.int32, torch.int64):
+        raise SculptError("%s: faces must be int32 or int64, got %s" % (who, f.dtype))
+    if f.dim() != 2 or f.shape[1] not in (3, 4):
+        raise SculptError("%s: faces must be [Nf, 3] or [Nf, 4], got %s" % (who, tuple(f.shape)))
+    P = v.detach().reshape(-1, 3).to(torch.float32).clone().contiguous()
+    nv, (nf, k) = P.shape[0], f.shape
+    if nv >= 1 << 31 or nf >= 1 << 27:
+        raise SculptError("%s: mesh too large for int32 indices" % who)
+    A = _attributes(attributes, nv, who)
+    ctx = _Ctx()
+    if nf and (int(f.min()) < 0 or int(f.max()) >= nv):  # before the int32 cast can wrap an index into range
+        raise SculptError("%s: face index out of range" % who)
+    F = f.detach().to(torch.int32).clone().contiguous()
+    if nv or nf:
+        status = torch.empty(1, dtype=torch.int32, device=P.device)
+        check(lib.sculpt_catmull_validate(_p(P), nv, _p(F), nf, k, _p(status), ctx.stream))
+        st = int(ctx.read(status))
+        if st & 1:
+            raise SculptError("%s: face index out of range" % who)
+        if st & 2:
+            raise SculptError("%s: degenerate face (repeated vertex index)" % who)
+        if st & 4:
+            raise SculptError("%s: non-finite vertex position" % who)
+    # every level turns nq quads into 4 nq (the first: k nf); the last level's 4 x quads index entries must stay in int32
+    if 4 * k * nf * 4 ** (levels - 1) >= 1 << 31:
+        raise SculptError("%s: %d faces of %d corners x 4^%d does not fit int32 indices" % (who, nf, k, levels - 1))
+    Q = torch.empty((0, 4), dtype=torch.int32, device=P.device)
+    Tr = torch.empty((0, 3), dtype=torch.int32, device=P.device)
+    if nf:
+        for _ in range(levels):
+            P, Q, Tr, A = _catmull_level(ctx, _PolyTopo(ctx, F, P.shape[0]), P, A)
+            F = Q
+    ctx.done()
+    return P, Q, Tr, A
+
+
 def _decimate(ctx, P, F, target):
     V = P
     T = None

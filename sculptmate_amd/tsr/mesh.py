@@ -32,7 +32,8 @@ class Mesh:
     the extractor's faces (FACE_FIELDS): quads int [Nq, 4], the all-quad mesh over the same vertices that
       extract_meshes(isosurface="surface_nets") adds, while `faces` are still the extractor's -- faces[2q], faces[2q + 1] are
       quad q split along its shorter diagonal.  smooth and project keep it (faces and vertex numbering stay); keep_components,
-      simplify and subdivide make new faces and drop it.
+      simplify and the triangle schemes of subdivide (Loop, midpoint) make new faces and drop it; subdivide with
+      (n, "catmull_clark") sets it anew, to the refined quads, on any mesh.
     A step that makes one mesh from another names what it carries over (_derive); what it does not name is None on its result."""
 
     quads = None   # (a mesh object made before the attribute existed has none either)
@@ -115,11 +116,18 @@ class Mesh:
         levels of the Loop scheme: the surface the mesh spans as a control cage) or a tuple (n, "loop" | "midpoint")
         (ops.subdivide_rule).  vertex_colors go through the same masks as the positions (attributes=), so they stay in their
         range.  vertex_normals and vertex_occlusion are dropped: they are stale on the refined surface.  A baked mesh
-        (uvs / texture) is refused: its atlas belongs to the faces it was baked for, so subdivide before baking."""
-        ops.subdivide_rule(subdivide)
+        (uvs / texture) is refused: its atlas belongs to the faces it was baked for, so subdivide before baking.
+        (n, "catmull_clark") is the all-quad scheme (ops.mesh_catmull_clark): it starts from `quads` when the mesh has them,
+        else from `faces` (a triangle becomes three quads), and the result carries the refined quads in `quads` and their
+        split along the shorter diagonal in `faces`.  The Loop and midpoint schemes refine triangles and drop `quads`."""
+        levels, scheme = ops.subdivide_rule(subdivide)
         if self.uvs is not None or self.texture is not None:
             raise ValueError("Mesh.subdivide: this mesh has a baked texture; subdivide before baking "
                              "(TSR.extract_meshes(subdivide=..., bake_texture=...))")
+        if scheme == "catmull_clark":
+            cage = self.faces if self.quads is None else self.quads
+            v, q, f, colors = ops.mesh_catmull_clark(self.vertices, cage, levels, attributes=self.vertex_colors)
+            return self._derive(v, f, vertex_colors=colors, quads=q)
         v, f, colors = ops.mesh_subdivide(self.vertices, self.faces, subdivide, attributes=self.vertex_colors)
         return self._derive(v, f, vertex_colors=colors)
 

@@ -955,6 +955,7 @@ class TSR(KernelEngine):
     # was made without __init__
     occlusion_map = None
     _occlusion_source = None
+    _quads = None   # extract_meshes -> _reshaped: the extractor's quads as a Catmull-Clark cage; and back: the refined quads
 
     def bake_normal_map(self, mesh: Mesh, scene_code, resolution=None, space="tangent", island_padding: float = 0.02,
                         unwrapper=None) -> Mesh:
@@ -1083,7 +1084,8 @@ class TSR(KernelEngine):
         sign-changing lattice edge -- no sliver triangles, and an all-quad mesh in Mesh.quads beside the triangles in
         Mesh.faces, which split each quad along its shorter diagonal and wind like marching cubes' (TSR.WINDING_OUTWARD)).
         Both take the two-pass grid and its sign planes under the same guard.  Mesh.quads stays while the faces are the
-        extractor's: smooth and project keep it, keep_components, simplify and subdivide drop it.  The mesh is open where
+        extractor's: smooth and project keep it, keep_components, simplify and the triangle schemes of subdivide drop it;
+        subdivide=(n, "catmull_clark") refines it (below).  The mesh is open where
         the surface meets the box, and naive surface nets puts ONE vertex into a cell with an ambiguous sign pattern, so a
         noisy field gives non-manifold edges (the mesh steps classify and hold such vertices).  project=True after it puts the
         vertices onto the field's iso-surface (dual contouring in effect).  Anything else is a ValueError before any launch.
@@ -1108,10 +1110,16 @@ class TSR(KernelEngine):
         LAST geometry step, after keep_components, smooth, simplify and subdivide and before the colours, the bake and the normals,
         which are therefore evaluated at the projected vertices; faces and indices are unchanged.  Needs threshold > 0.
         subdivide: None (default): nothing is launched, nothing changes.  An int n in 1 .. 6 (n levels of the Loop scheme) or a
-        tuple (n, "loop" | "midpoint") (ops.subdivide_rule): every face becomes four per level on the device
+        tuple (n, "loop" | "midpoint" | "catmull_clark") (ops.subdivide_rule): every face becomes four per level on the device
         (ops.mesh_subdivide) AFTER simplify and BEFORE project -- simplify leaves a light, irregular cage, subdivide refines it
         into a semi-regular surface, and project puts the vertices that now exist between the lattice points onto the field's
-        iso-surface.  Mesh.subdivide lets a caller choose another order.
+        iso-surface.  Mesh.subdivide lets a caller choose another order.  (n, "catmull_clark") is the all-quad scheme of
+        Blender's Subdivision Surface and Multires modifiers (ops.mesh_catmull_clark), at the same place in the chain: it starts
+        from the extractor's quads while they are still valid (isosurface="surface_nets" with no keep_components and no
+        simplify; every quad becomes four per level), otherwise from the triangles (every triangle becomes three quads, then
+        four per level -- simplify=0.1, subdivide=(1, "catmull_clark") is an all-quad, semi-regular mesh of about the marching
+        cubes face budget).  Mesh.quads then holds the refined quads and Mesh.faces their split along the shorter diagonal;
+        a following project keeps both; normals=, colours and the bakes see the final triangles.
         occlusion: None (default): nothing is launched, nothing changes.  True (64 directions), an int k in 1 .. 1024 or a tuple
         (k, max_distance) (ops.occlusion_rule): Mesh.vertex_occlusion = the ambient occlusion of the final mesh against itself,
         f32 [Nv], 1 = open, 0 = occluded -- Mesh.ambient_occlusion(occlusion, outward=TSR.WINDING_OUTWARD), one fused ray
@@ -1146,6 +1154,7 @@ class TSR(KernelEngine):
 
         mc.takes_sign_planes = True
         keeps_faces = keep_components is None and simplify is None and subdivide is None
+        catmull_clark = self._is_catmull_clark(subdivide)
         for scene_code in scene_codes:
             planes = scene_code.contiguous()
             dkw = dict(radius=r, density_bias=self.renderer.cfg.density_bias, out_add=-threshold)
@@ -1155,11 +1164,22 @@ class TSR(KernelEngine):
             else:
                 vol = ops.density_grid(planes, self.decoder, R, precision=self.decoder_precision, events=density_events, **dkw)
                 v_pos, t_pos_idx = mc(vol)   # (both decoder modes have the fp32 range: a NaN here is a NaN of the model)
+            quads = quads_of.pop("quads", None)
+            # Catmull-Clark refines the extractor's quads while they still cover the faces (smooth keeps them), else the triangles
+            self._quads = quads if catmull_clark and keep_components is None and simplify is None else None
             v_pos, t_pos_idx = self._reshaped(v_pos, t_pos_idx, planes, threshold, R, **geometry)
             out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals, occlusion))
+            refined, self._quads = self._quads, None
             if keeps_faces:   # the faces are still the extractor's
-                out[-1].quads = quads_of.pop("quads", None)
+                out[-1].quads = quads
+            elif catmull_clark:   # the faces are the split of the refined quads
+                out[-1].quads = refined
         return out
+
+    @staticmethod
+    def _is_catmull_clark(subdivide):
+        """Whether a `subdivide` that ops.subdivide_rule accepts names the all-quad scheme (only a tuple can)."""
+        return isinstance(subdivide, tuple) and len(subdivide) == 2 and subdivide[1] == "catmull_clark"
 
     @staticmethod
     def _check_geometry(threshold, keep_components=None, simplify=None, smooth=None, project=None, subdivide=None):
@@ -1192,7 +1212,11 @@ class TSR(KernelEngine):
                 self._occlusion_source = Mesh(v_pos, t_pos_idx)
             v_pos, t_pos_idx = ops.mesh_simplify(v_pos, t_pos_idx, simplify)[:2]
         if subdivide is not None:
-            v_pos, t_pos_idx = ops.mesh_subdivide(v_pos, t_pos_idx, subdivide)[:2]
+            if self._is_catmull_clark(subdivide):   # the quads extract_meshes left in _quads, else the triangles; the refined quads go back
+                cage = t_pos_idx if self._quads is None else self._quads
+                v_pos, self._quads, t_pos_idx = ops.mesh_catmull_clark(v_pos, cage, subdivide[0])[:3]
+            else:
+                v_pos, t_pos_idx = ops.mesh_subdivide(v_pos, t_pos_idx, subdivide)[:2]
         if project is not None:
             v_pos = self._projected(v_pos, t_pos_idx, planes, threshold, project, R)
         return v_pos, t_pos_idx
