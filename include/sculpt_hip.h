@@ -53,7 +53,8 @@ extern "C" {
  * 4: the two-pass grid's guard: 12 statistics words instead of 8 (sculpt_density_filter_stats fills SCULPT_FILTER_STATS_WORDS),
  *    word 1 covers every re-evaluated point, the audit sample and the sign mismatches are new; the marching-cubes workspace
  *    is a record pool with a capacity (SCULPT_ERR_MC_WORKSPACE, sculpt_mc_workspace_bytes_for, sculpt_mc_count_launch_for,
- *    sculpt_mc_count_read_ex); added without a version change (new symbol only): sculpt_gemm_last_form */
+ *    sculpt_mc_count_read_ex); added without a version change (new symbols only): sculpt_gemm_last_form,
+ *    sculpt_attention_last_form */
 #define SCULPT_ABI_VERSION 4
 
 typedef void *sculpt_stream_t;
@@ -571,6 +572,11 @@ int sculpt_gemm_bf16_ln(const uint16_t *A, int lda, const uint16_t *W, int ldw, 
  * The launchers only fill a thread-local struct of ints; the text is formatted here, into a thread-local buffer that the next
  * call on the same thread overwrites.  For tests of the dispatch rules and for A/B tools; never fails. */
 const char *sculpt_gemm_last_form(void);
+/* Which kernel the calling thread's last sculpt_attention_bf16* launch started, e.g.
+ *   "attn kernel=pipe nqb=6 pre=1 batch=3 grid=16x48"   ("none" before the first launch)
+ * kernel: plain (attention_kernel) / pipe (attention_pipe_kernel); nqb: 32-query blocks per workgroup (4 / 6 / 8); pre: pre-scaled
+ * queries; batch: entries of the launch; grid: workgroups x, y.  Filled and formatted like sculpt_gemm_last_form; never fails. */
+const char *sculpt_attention_last_form(void);
 /* (mean, M2) of every 64-column slice of x [rows][cols] fp32 -> stats [cols/64][stats_ld][2], and the bf16 copy of x: the
  * producer side of the fold for rows that do not come out of a GEMM (the ViT's embedding output). cols % 64 == 0. */
 int sculpt_row_slice_stats(const float *x, int ldx, int rows, int cols, float *stats, int stats_ld, uint16_t *x_bf16, int ldb,

@@ -116,6 +116,7 @@ SIGNATURES = {
     "sculpt_gemm_bf16_ln": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sculpt_row_slice_stats": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "sculpt_gemm_last_form": (ctypes.c_char_p, []),
+    "sculpt_attention_last_form": (ctypes.c_char_p, []),
     "sculpt_conv3x3_bf16": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "sculpt_im2col3x3_dilated": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sculpt_maxpool2x2_ceil": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),

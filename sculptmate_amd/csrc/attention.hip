@@ -319,6 +319,25 @@ __global__ __launch_bounds__(NQB * 128, 4) void attention_kernel(const uint16_t 
 
 using namespace sculpt;
 
+// Which kernel this thread's last bf16 attention launch started: plain ints filled just before the launch (no formatting on the
+// launch path), formatted on request by sculpt_attention_last_form -- what the tests of the dispatch rule read.
+struct AttnForm {
+    int launched;  // 0: nothing launched yet
+    int pipe;      // 1: attention_pipe_kernel<nqb>, 0: attention_kernel<nqb, pre>
+    int nqb, pre, batch;
+    int grid_x, grid_y;
+};
+static thread_local AttnForm t_attn_form = {0, 0, 0, 0, 0, 0, 0};
+
+extern "C" const char *sculpt_attention_last_form(void) {
+    static thread_local char buf[96];
+    const AttnForm &f = t_attn_form;
+    if (!f.launched) return "none";
+    snprintf(buf, sizeof buf, "attn kernel=%s nqb=%d pre=%d batch=%d grid=%dx%d", f.pipe ? "pipe" : "plain", f.nqb, f.pre, f.batch,
+             f.grid_x, f.grid_y);
+    return buf;
+}
+
 static int attention_launch(const uint16_t *Q, int ldq, const uint16_t *K, int ldk, const uint16_t *Vt, int ldvt, uint16_t *O,
                             int ldo, int Tq, int Tk, int heads, float scale, bool prescaled, sculpt_stream_t stream,
                             int batch = 1, long q_bs = 0, long k_bs = 0, long vt_bs = 0, long o_bs = 0) {
@@ -373,6 +392,7 @@ static int attention_launch(const uint16_t *Q, int ldq, const uint16_t *K, int l
     hipLaunchKernelGGL((attention_kernel<NQB, PRE>), grid, block, 0, st, Q, ldq, K, ldk, Vt, ldvt, O, ldo, Tq, Tk, SC, ab)
     // SCULPT_ATTN_FORM=nopipe: the phase-separated loop for pre-scaled queries too (tests pin the pipelined kernel against it)
     const bool pipe = prescaled && nqb != 8 && !form_has("SCULPT_ATTN_FORM", "nopipe");
+    t_attn_form = AttnForm{1, pipe ? 1 : 0, nqb, prescaled ? 1 : 0, batch, (int)grid.x, (int)grid.y};
     if (pipe) {
         attention_pipe_launch(nqb, grid, block, st, Q, ldq, K, ldk, Vt, ldvt, O, ldo, Tq, Tk, ab);
     } else if (prescaled) {  // Q carries scale * log2(e) already

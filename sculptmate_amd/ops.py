@@ -1975,6 +1975,19 @@ def attention(Q, K, Vt, O, Tq, Tk, heads, scale, batch=1, q_bs=0, k_bs=0, vt_bs=
                                         O.stride(0), Tq, Tk, heads, float(scale), _stream()))
 
 
+def attention_last_form():
+    """The kernel this thread's last bf16 attention launch started (sculpt_attention_last_form) as a dict: kernel ("plain" /
+    "pipe"), nqb, pre, batch, grid (x, y), text; {} before the first launch."""
+    text = (lib.sculpt_attention_last_form() or b"none").decode()
+    if text == "none":
+        return {}
+    form = {"text": text}
+    for w in text.split()[1:]:
+        k, v = w.split("=")
+        form[k] = v if k == "kernel" else tuple(int(x) for x in v.split("x")) if k == "grid" else int(v)
+    return form
+
+
 def layernorm(x, gamma, beta, eps, y=None, y_f32=None, rows=None, y_lt=None):
     """y_lt (a Limbs, fp32 x only): the normalised rows as three bf16 limbs, limb-tiled (sculpt_layernorm_limbs); y_f32 optional."""
     rows = x.shape[0] if rows is None else rows
