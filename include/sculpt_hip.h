@@ -1348,6 +1348,32 @@ int sculpt_triplane_project(const float *planes_cl /* [3][H][W][C] */, int C, in
 int sculpt_mesh_unfold(const float *P0, float *P, const int64_t *faces, int64_t Nv, int64_t Nf, int rounds, int *mark_ws, int *stats,
                        sculpt_stream_t stream);
 
+/* Bake at the surface (csrc/bake_surface.hip; ops.bake_scene_surface): every covered texel of a rasterised
+ * UV atlas is first projected from its point on the low-poly face onto the iso-surface d(p) = target of the raw density, and the
+ * field's unit normal is read THERE; one launch.  DEVICE pointers, asynchronous on `stream`, no host wait.  Added without a
+ * version change (a new symbol only).  Arguments: those of sculpt_bake_scene_normal, then target, max_steps, max_dist, res_tol
+ * of sculpt_triplane_project (flags 0).  Per covered texel (the index guard of sculpt_bake_scene_color):
+ *   p0 = the texel's position, the bits of sculpt_bake_interpolate;
+ *   (point, residual, status, evals) = what sculpt_triplane_project returns for p0 under the same parameters, bit for bit
+ *     (the numbered rule above: frozen axes, trust region, best iterate, statuses 0 .. 3);
+ *   normal, no frame = the `normal` of sculpt_triplane_density_grad (flags 0) at `point`, bit for bit: the raw gradient of the
+ *     evaluation that made `point` the best iterate is kept, no further evaluation is run;
+ *   normal, frame given = that world normal through the tangent-space transform of sculpt_bake_scene_normal at the texel's own
+ *     barycentrics (the low-poly face and its interpolated frame do not move).
+ *   max_steps == 0: point = p0 and normal = sculpt_bake_scene_normal's output, bit for bit, in both spaces.
+ * Outputs, each nullable:
+ *   point     f32 [res][res][3]     normal  f32 [res][res][3]  in [-1, 1], not encoded
+ *   residual  f32 [res][res]        status  i32 [res][res]     evals  i32 [res][res]     mask  u8 [res][res]
+ * A texel that is not covered gets point, normal and residual exactly +0, status -1, evals 0, mask 0.  A texel's outputs depend
+ * on that texel alone.  Refused: what sculpt_bake_scene_normal refuses (but every output may be null), max_steps outside 0 .. 64,
+ * max_dist or res_tol not positive and finite, a NaN target.  res == 0 is a no-op. */
+int sculpt_bake_scene_surface(const float *planes_cl /* [3][H][W][C] */, int C, int H, int W, const void *mlp_packed, int n_hidden_64,
+                              const float *v_pos /* [nv][3] */, size_t nv, const void *faces /* [nf][3] */, int faces_i64, size_t nf,
+                              const float *rast /* [res][res][4] = (u, v, w, tri) or (0,0,0,-1) */, int res, float radius,
+                              const float *corner_normals /* nullable [3 nf][3] */, const float *corner_tangents /* nullable [3 nf][4] */,
+                              float target, int max_steps, float max_dist, float res_tol, float *point, float *normal, float *residual,
+                              int *status, int *evals, uint8_t *mask, sculpt_stream_t stream);
+
 /* Mesh hand-off, HOST side (no GPU work): the face block of a binary little-endian PLY file -- per face `uchar 3` followed by
  * three int32 -- from the int64 faces TSR.run returns (the reference's `t_pos_idx.cpu().numpy()`, TripoSR/tsr/system.py:200).
  * faces_host int64 [n][3] -> records_host uint8 [n][13].  Thread-safe; callers split n over threads (sculptmate_amd/meshio.py). */

@@ -240,6 +240,8 @@ SIGNATURES = {
     "sculpt_surface_render": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _f, _vp, _d, _vp, _vp]),
     "sculpt_triplane_project": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, ctypes.c_longlong, _f, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_mesh_unfold": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp]),
+    "sculpt_bake_scene_surface": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _i, _sz, _vp, _i, _f, _vp, _vp, _f, _i, _f, _f, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp]),
     "rasterize_cpu": (None, [_vp, _sz, _vp, _sz, ctypes.c_longlong, _vp]),
     "interpolate_cpu": (None, [_vp, _sz, _vp, _sz, _vp, ctypes.c_longlong, _vp]),
 }

@@ -1,0 +1,79 @@
+// The projection rule of DESIGN.md section 3.1e: one copy, so that project_kernel (csrc/mesh_project.hip) and
+// bake_scene_surface_kernel (csrc/bake_surface.hip) move a point by the same sequence of IEEE fp32 operations.  The rule is
+// compiled without contraction; tests/_projref.py restates it (newton in NumPy, composed_device one torch call per operation).
+#pragma once
+
+#include "common.h"
+
+namespace sculpt {
+
+// what a point carries from one evaluation to the next
+struct ProjState {
+    float px, py, pz;     // current iterate
+    float r;              // its residual d - target
+    float gx, gy, gz;     // its masked gradient
+    float bx, by, bz, br; // best iterate and its residual
+    int status, evals;
+    bool active;
+};
+
+__device__ __forceinline__ bool finite_f(float x) { return fabsf(x) < INFINITY; }
+
+// One turn of the rule after the evaluation (d, g) at the candidate (qx, qy, qz): accept it (k == 0: it is p0), then the
+// checks and the step that lead to the next candidate, which is left in (qx, qy, qz).  DESIGN.md section 3.1e numbers the
+// operations.  -> whether the candidate that was just evaluated is now the best iterate (bx, by, bz): a caller that wants
+// something else of the best iterate than its residual -- the raw gradient, for the normal there -- keeps it on true.
+__device__ __forceinline__ bool rule_update(ProjState &s, int k, int K, float d, float gx, float gy, float gz, float &qx, float &qy,
+                                            float &qz, float p0x, float p0y, float p0z, bool fx, bool fy, bool fz, float target,
+                                            float radius, float md2, float res_tol) {
+#pragma clang fp contract(off)
+    bool took = false;
+    if (s.active) {
+        s.evals += 1;
+        const float rq = d - target;
+        if (!finite_f(rq)) {
+            s.status = 3;
+            s.active = false;
+            if (k == 0) s.br = rq, took = true;   // the best iterate is p0, which is the candidate
+        } else {
+            s.px = qx, s.py = qy, s.pz = qz;
+            s.r = rq;
+            s.gx = fx ? 0.f : gx, s.gy = fy ? 0.f : gy, s.gz = fz ? 0.f : gz;
+            if (k == 0 || fabsf(rq) < fabsf(s.br)) s.bx = qx, s.by = qy, s.bz = qz, s.br = rq, took = true;
+        }
+    }
+    if (!s.active) return took;
+    if (k == K) {
+        s.status = fabsf(s.r) <= res_tol ? 0 : 1;
+        s.active = false;
+        return took;
+    }
+    if (fabsf(s.r) <= res_tol) {
+        s.status = 0;
+        s.active = false;
+        return took;
+    }
+    const float g2 = (s.gx * s.gx + s.gy * s.gy) + s.gz * s.gz;
+    if (!(g2 > 0.f) || !finite_f(g2)) {
+        s.status = 3;
+        s.active = false;
+        return took;
+    }
+    const float st = s.r / g2;
+    float nx = s.px - st * s.gx, ny = s.py - st * s.gy, nz = s.pz - st * s.gz;
+    const float lo = -radius;
+    nx = nx < lo ? lo : nx, ny = ny < lo ? lo : ny, nz = nz < lo ? lo : nz;   // comparisons, not fmin / fmax: a NaN stays a NaN
+    nx = nx > radius ? radius : nx, ny = ny > radius ? radius : ny, nz = nz > radius ? radius : nz;
+    nx = fx ? p0x : nx, ny = fy ? p0y : ny, nz = fz ? p0z : nz;
+    const float dx = nx - p0x, dy = ny - p0y, dz = nz - p0z;
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    if (d2 > md2) {
+        s.status = 2;
+        s.active = false;
+        return took;
+    }
+    qx = nx, qy = ny, qz = nz;
+    return took;
+}
+
+}  // namespace sculpt

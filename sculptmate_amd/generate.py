@@ -60,7 +60,10 @@ class TripoGenerator(GeneratorFacade):
     `occlusion_map` (default None): True, an int k or a tuple (k, max_distance) adds an ambient-occlusion map to every mesh a
     texture is baked for, over the same atlas at the same resolution, baked against the mesh as it was before simplify
     (TSR.bake_occlusion_map; copied to the model as TSR.occlusion_map).  Mesh.export writes it (glTF occlusionTexture, `map_Ka`);
-    the Blender sinks take none: the .glb carries it to Blender's own importer."""
+    the Blender sinks take none: the .glb carries it to Blender's own importer.
+    `bake_project` (default None): True, an int n or a tuple (n, cells) (ops.project_rule) bakes the texture, and the normal map
+    when `normal_map` is set, AT THE SURFACE: every texel is first projected from the low-poly face onto the field's
+    iso-surface (TSR.bake_surface_maps; copied to the model as TSR.bake_project)."""
 
     def __init__(self, device):
         super().__init__(device, checkpoint_dir=ROOT_DIR + "/checkpoints/", chunk_size=8192, mc_resolution=256,
@@ -77,6 +80,7 @@ class TripoGenerator(GeneratorFacade):
         self.isosurface = "marching_cubes"
         self.normal_map = None
         self.occlusion_map = None
+        self.bake_project = None
 
     def _construct_model(self):
         model = TSR.from_pretrained(self.checkpoint_dir, config_name="config.yaml", weight_name="model.ckpt",
@@ -92,6 +96,7 @@ class TripoGenerator(GeneratorFacade):
                 codes = self.model([input_image], device=self.device)
             self.model.normal_map = self.normal_map
             self.model.occlusion_map = self.occlusion_map
+            self.model.bake_project = self.bake_project
             self.last_meshes = self.model.extract_mesh(codes, enable_texture=enable_texture, mesh_name=input_name,
                                                        resolution=self.mc_resolution,
                                                        bake_texture=int(self.bake_texture_resolution or 0),

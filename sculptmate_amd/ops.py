@@ -2169,6 +2169,142 @@ def bake_scene_normal(planes, mlp, v_pos, faces, rast, radius=0.87, frame=None):
     return normal, mask.view(torch.bool)
 
 
+# ----------------------------------------------------------------------------------------------
+# bake at the surface: project each texel onto the iso-surface first (csrc/bake_surface.hip)
+# ----------------------------------------------------------------------------------------------
+_SURFACE_EXTRAS = (("residual", torch.float32), ("status", torch.int32), ("evals", torch.int32))
+
+
+def _bake_surface_args(who, planes, v_pos, faces, rast, target, max_dist, steps, res_tol, frame, want):
+    """The checks the two routes of the surface bake share: _bake_scene_args, _project_args and the frame checks of
+    bake_scene_normal -> (channel-last planes, v, f, rast, res, corner_normals or None, corner_tangents or None, want)."""
+    want = tuple(want)
+    unknown = set(want) - {k for k, _ in _SURFACE_EXTRAS}
+    if unknown:
+        raise SculptError("%s: unknown output %s" % (who, sorted(unknown)))
+    _project_args(steps, max_dist, res_tol, target)
+    planes, v, f, r, res = _bake_scene_args(who, planes, v_pos, faces, rast)
+    cn = ct = None
+    if frame is not None:
+        if not (isinstance(frame, (tuple, list)) and len(frame) == 2):
+            raise SculptError("%s: frame must be None or (corner_normals, corner_tangents)" % who)
+        cn = _req(frame[0], torch.float32, "corner_normals")
+        ct = _req(frame[1], torch.float32, "corner_tangents")
+        nf = f.shape[0]
+        if tuple(cn.shape) != (3 * nf, 3) or tuple(ct.shape) != (3 * nf, 4):
+            raise SculptError("%s: corner_normals %s must be [%d, 3] and corner_tangents %s [%d, 4] (three rows per face)"
+                              % (who, tuple(cn.shape), 3 * nf, tuple(ct.shape), 3 * nf))
+        if nf == 0:   # no face, no frame rows: nothing is covered, and an empty tensor has no address
+            cn = ct = None
+    return planes, v, f, r, res, cn, ct, want
+
+
+def bake_scene_surface(planes, mlp, v_pos, faces, rast, target, max_dist, steps=PROJECT_STEPS, res_tol=PROJECT_RES_TOL, radius=0.87,
+                       frame=None, want=()):
+    """What a baker does, in ONE launch (sculpt_bake_scene_surface): every covered texel of a rasterised atlas goes from its
+    point on the low-poly face to the high-poly surface -- here the iso-surface d(p) = target of the scene code's raw density,
+    reached by project_to_isosurface's rule (at most `steps` Newton steps inside the trust radius max_dist) --
+    and the field's unit normal is read there.  Per covered texel, bit for bit: point, and the extras, are what
+    project_to_isosurface returns for the position bake_interpolate gives; normal is what field_normals gives at `point`,
+    as it is (frame=None, object space) or through bake_scene_normal's tangent-space transform at the texel's own barycentrics
+    (frame=(corner_normals, corner_tangents): the low-poly face and its frame do not move).  steps == 0 is bake_scene_normal.
+    planes, v_pos, faces, rast, radius, frame: as for bake_scene_normal; target, max_dist, steps, res_tol: as for
+    project_to_isosurface.
+    -> (point f32 [res,res,3], normal f32 [res,res,3] not encoded, mask bool [res,res], extras) with extras[k] for k in want:
+    "residual" f32 [res,res], "status" i32 [res,res] (0 .. 3 as project_to_isosurface; -1 where not covered), "evals" i32
+    [res,res].  Where a texel is not covered point, normal and residual are exactly 0 and evals is 0.  A texel's outputs depend
+    on that texel alone."""
+    planes, v, f, r, res, cn, ct, want = _bake_surface_args("bake_scene_surface", planes, v_pos, faces, rast, target, max_dist, steps,
+                                                             res_tol, frame, want)
+    dev = r.device
+    point = torch.empty((res, res, 3), dtype=torch.float32, device=dev)
+    normal = torch.empty((res, res, 3), dtype=torch.float32, device=dev)
+    mask = torch.empty((res, res), dtype=torch.uint8, device=dev)
+    ex = {k: torch.empty((res, res), dtype=dt, device=dev) if k in want else None for k, dt in _SURFACE_EXTRAS}
+    if res > 0:
+        check(lib.sculpt_bake_scene_surface(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(v),
+                                            v.shape[0], _ptr(f), int(f.dtype == torch.int64), f.shape[0], _ptr(r), res, float(radius),
+                                            _ptr(cn), _ptr(ct), float(target), int(steps), float(max_dist), float(res_tol), _ptr(point),
+                                            _ptr(normal), _ptr(ex["residual"]), _ptr(ex["status"]), _ptr(ex["evals"]), _ptr(mask),
+                                            _stream()))
+    return point, normal, mask.view(torch.bool), {k: t for k, t in ex.items() if t is not None}
+
+
+def _tangent_space_composed(n, bary, tri, cn, ct):
+    """bake_scene_normal's tangent-space transform (csrc/tangent_frame.h) in torch, one fp32 call per operation in the kernel's
+    order: world normals n [M,3], barycentrics [M,3], face index [M] (long) -> the stored vectors [M,3]."""
+    def dot(a, b):
+        return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+
+    def cross(a, b):
+        return torch.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
+                            a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], 1)
+
+    cn3, ct4 = cn.view(-1, 3, 3)[tri], ct.view(-1, 3, 4)[tri]
+    u, v, w = bary[:, 0:1], bary[:, 1:2], bary[:, 2:3]
+    N = (cn3[:, 0] * u + cn3[:, 1] * v) + cn3[:, 2] * w
+    T = (ct4[:, 0, :3] * u + ct4[:, 1, :3] * v) + ct4[:, 2, :3] * w
+    B = ct4[:, 0, 3:4] * cross(N, T)
+    gtt, gnn, gtn = dot(T, T), dot(N, N), dot(T, N)
+    D = gtt * gnn - gtn * gtn
+    nT, nN, nB = dot(n, T), dot(n, N), dot(n, B)
+    x, y, z = nT * gnn - nN * gtn, nB, nN * gtt - nT * gtn
+    length = torch.sqrt((x * x + y * y) + z * z)
+    ok = (D > 0) & (length > 0) & (length < math.inf) & ~(n == 0).all(1)
+    flat = torch.tensor([0.0, 0.0, 1.0], dtype=n.dtype, device=n.device)
+    return torch.where(ok[:, None], torch.stack([x / length, y / length, z / length], 1), flat)
+
+
+def bake_scene_surface_composed(planes, mlp, v_pos, faces, rast, target, max_dist, steps=PROJECT_STEPS, res_tol=PROJECT_RES_TOL,
+                                radius=0.87, frame=None, want=()):
+    """bake_scene_surface from ops that were there before it, the restatement the fused kernel is held to bit for bit and the
+    route it is timed against: bake_interpolate -> the covered texels (nonzero: this waits for the device) ->
+    project_to_isosurface -> field_normals at the projected points -> the tangent-space transform in torch, one call per
+    operation -> scatter into images that are 0 (status -1) elsewhere.  Same arguments, same result: the coverage is
+    texel_position's (a texel whose tri or vertex rows are out of range, or whose tri is a NaN, is not covered), worked out here
+    in torch, and bake_interpolate, which guards nothing, reads through checked rows only."""
+    planes, v, f, r, res, cn, ct, want = _bake_surface_args("bake_scene_surface_composed", planes, v_pos, faces, rast, target, max_dist,
+                                                             steps, res_tol, frame, want)
+    dev = r.device
+    point = torch.zeros((res, res, 3), dtype=torch.float32, device=dev)
+    normal = torch.zeros((res, res, 3), dtype=torch.float32, device=dev)
+    ex = {"residual": torch.zeros((res, res), dtype=torch.float32, device=dev),
+          "status": torch.full((res, res), -1, dtype=torch.int32, device=dev),
+          "evals": torch.zeros((res, res), dtype=torch.int32, device=dev)}
+    nv, nf = v.shape[0], f.shape[0]
+    tri = r[..., 3]
+    covered = (tri >= 0) & (tri < 2147483648.0)                     # a NaN fails both
+    if nf == 0 or nv == 0:
+        covered = torch.zeros_like(covered)
+    else:
+        t = torch.where(covered, tri, torch.zeros_like(tri)).to(torch.int64)
+        covered = covered & (t < nf)
+        rows = f[t.clamp(max=nf - 1)].to(torch.int64)               # [res, res, 3]
+        covered = covered & ((rows >= 0) & (rows < nv)).all(-1)
+        r = torch.where(covered[..., None], r, r.new_tensor([0.0, 0.0, 0.0, -1.0])).contiguous()
+    idx = covered.reshape(-1).nonzero()[:, 0]
+    if idx.numel() > 0:
+        pos = bake_interpolate(v, r, f).reshape(-1, 3)[idx].contiguous()
+        p, got = project_to_isosurface(planes, mlp, pos, target, max_dist, steps=steps, res_tol=res_tol, radius=radius,
+                                       want=("residual", "status", "evals"))
+        n = field_normals(planes, mlp, p, radius=radius)["normal"]
+        if cn is not None:
+            texel = r.reshape(-1, 4)[idx]
+            n = _tangent_space_composed(n, texel[:, :3], texel[:, 3].to(torch.int32).long(), cn, ct)
+        point.view(-1, 3)[idx] = p
+        normal.view(-1, 3)[idx] = n
+        for k in ex:
+            ex[k].view(-1)[idx] = got[k]
+    return point, normal, covered, {k: ex[k] for k in want}
+
+
+def bake_surface_route():
+    """What TSR.bake_surface_maps calls: bake_scene_surface_composed, unless SCULPT_DISTANCE_FORM holds the token `fusedsurface`
+    (then bake_scene_surface, the one fused launch).  The two give the same bits; the composed route is the default because it
+    is the faster one on the flagship atlas (DESIGN.md 3.1g has the figures)."""
+    return bake_scene_surface if _lib.form_has("SCULPT_DISTANCE_FORM", "fusedsurface") else bake_scene_surface_composed
+
+
 def resize_aa_bilinear(img_hwc, size):
     """F.interpolate(bilinear, align_corners=False, antialias=True) to (size, size) on an HWC fp32 device image
     (ImagePreprocessor.convert_and_resize, tsr/utils.py:82-88)."""

@@ -955,6 +955,9 @@ class TSR(KernelEngine):
     # was made without __init__
     occlusion_map = None
     _occlusion_source = None
+    # None | what ops.project_rule accepts (True, n, (n, cells)): when set, extract_meshes bakes the texture, and the normal map when
+    # self.normal_map is set, AT THE SURFACE (bake_surface_maps) with its own threshold and resolution.  None: nothing new is launched
+    bake_project = None
     _quads = None   # extract_meshes -> _reshaped: the extractor's quads as a Catmull-Clark cage; and back: the refined quads
 
     def bake_normal_map(self, mesh: Mesh, scene_code, resolution=None, space="tangent", island_padding: float = 0.02,
@@ -981,15 +984,77 @@ class TSR(KernelEngine):
             corner_t = ops.corner_tangents(v, f, uv, corner_n)
             n, mask = ops.bake_scene_normal(self._field(scene_code), self.decoder, v, f, rast, radius=self.renderer.cfg.radius,
                                             frame=(corner_n, corner_t) if space == "tangent" else None)
-            flat = torch.tensor(self.NORMAL_MAP_FLAT[space], dtype=torch.float32, device=self.device)
-            # dilate_fill averages over a texel's neighbourhood as it finds it, so the image is 0 outside the charts going in; an
-            # encoded unit normal has a component above 0, and so has every average of some: a texel that is still (0, 0, 0)
-            # coming out is one the padding did not reach
-            coded = self._padded(torch.where(mask[..., None], 0.5 + 0.5 * n, torch.zeros_like(n)), mask, res)
-            coded = torch.where((coded != 0).any(-1, keepdim=True), coded, flat)
+            coded = self._coded_normals(n, mask, res, space)
         return mesh._derive(mesh.vertices, mesh.faces, ("vertex_colors", "texture", "vertex_normals", "vertex_occlusion", "occlusion_map"),
                             uvs=mesh.uvs if mesh.uvs is not None else uv, normal_map=coded, normal_map_space=space,
                             corner_normals=corner_n, corner_tangents=corner_t)
+
+    def bake_surface_maps(self, mesh: Mesh, scene_code, threshold: float = 25.0, project=True, resolution=None, atlas_resolution=None,
+                          texture=True, normal_map="tangent", island_padding: float = 0.02, unwrapper=None) -> Mesh:
+        """bake_texture and bake_normal_map as a baker does them: every covered texel first goes from its point on the low-poly
+        face to the HIGH-poly surface -- the iso-surface density_act = threshold of the field of `scene_code`, reached by
+        project_mesh's rule (project: True = (8, 1.0), an int n, or (n, cells) of a `resolution`^3 lattice: ops.project_rule;
+        resolution: default the marching-cubes resolution set last) -- and colour and normal are read THERE.  After simplify the
+        face interiors lie off the surface by their chord error, which project= on the vertices does not cure.
+        One atlas (a mesh that has uvs keeps them; atlas_resolution defaults as in bake_normal_map) and ONE projection of the
+        texels (ops.bake_surface_route: ops.bake_scene_surface_composed by default, the single fused launch of
+        ops.bake_scene_surface with SCULPT_DISTANCE_FORM=fusedsurface; the same bits, the composed route is the faster one on
+        these atlases) serve both maps: the normal map (normal_map: "tangent",
+        "object" or None) comes out of that projection, the texture (texture=True) is the colour field at the projected points of the
+        covered texels through the point query (ops.triplane_query on channel-last planes: picking the covered texels waits for
+        the device).  The low-poly frame does not move: corner_normals and corner_tangents are bake_normal_map's.  Padding, flat
+        values and encoding are exactly those of bake_texture / bake_normal_map.
+        -> a Mesh with the input's vertices, faces and what bake_normal_map carries, plus uvs, texture and / or normal_map,
+        normal_map_space, corner_normals, corner_tangents, on the device.  texture=False with normal_map=None is a ValueError."""
+        steps, cells = ops.project_rule(project)   # a ValueError before anything is launched
+        if normal_map is not None and normal_map not in self.NORMAL_MAP_FLAT:
+            raise ValueError("TSR.bake_surface_maps: normal_map must be None, 'tangent' or 'object', got %r" % (normal_map,))
+        if not texture and normal_map is None:
+            raise ValueError("TSR.bake_surface_maps: nothing to bake (texture=False and normal_map=None)")
+        if not threshold > 0:
+            raise ValueError("TSR.bake_surface_maps: threshold must be positive, got %r" % (threshold,))
+        self._need_weights("bake_surface_maps")
+        if resolution is None:
+            if self.isosurface_helper is None:
+                raise ValueError("TSR.bake_surface_maps: no resolution given and no marching-cubes resolution set yet")
+            resolution = self.isosurface_helper.resolution
+        if int(resolution) < 2:
+            raise ValueError("TSR.bake_surface_maps: resolution must be at least 2, got %r" % (resolution,))
+        res = _atlas_resolution(atlas_resolution, mesh, "bake_surface_maps", ("texture", "normal_map"))
+        cfg = self.renderer.cfg
+        target = float(np.float32(math.log(float(threshold)) - float(cfg.density_bias)))   # as _projected
+        max_dist = cells * 2.0 * float(cfg.radius) / (int(resolution) - 1)
+        with torch.no_grad():
+            v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper, keep_uvs=True)
+            planes = self._field(scene_code)
+            corner_n = corner_t = None
+            if normal_map is not None:
+                corner_n = (self.WINDING_OUTWARD * ops.vertex_normals(v, f))[f.reshape(-1).long()].contiguous()
+                corner_t = ops.corner_tangents(v, f, uv, corner_n)
+            point, n, mask, _ = ops.bake_surface_route()(planes, self.decoder, v, f, rast, target, max_dist, steps=steps,
+                                                         radius=cfg.radius, frame=(corner_n, corner_t) if normal_map == "tangent" else None)
+            new = {}
+            if texture:
+                color = torch.zeros_like(point)
+                color[mask] = ops.triplane_query(planes, self.decoder, point[mask], radius=cfg.radius, density_bias=cfg.density_bias,
+                                                 want=("color",))["color"]
+                new["texture"] = self._padded(color, mask, res)
+            if normal_map is not None:
+                new.update(normal_map=self._coded_normals(n, mask, res, normal_map), normal_map_space=normal_map,
+                           corner_normals=corner_n, corner_tangents=corner_t)
+        # a baked texture replaces the vertex colours, as in bake_texture; a map that is not baked here stays (with its tag)
+        keep = ("vertex_normals", "vertex_occlusion", "occlusion_map") + (() if texture else ("vertex_colors", "texture")) \
+            + (() if normal_map is not None else ("normal_map", "corner_normals", "corner_tangents"))
+        return mesh._derive(mesh.vertices, mesh.faces, keep, uvs=mesh.uvs if mesh.uvs is not None else uv, **new)
+
+    def _coded_normals(self, n, mask, res, space):
+        """A normal image as a map: encoded 0.5 + 0.5 n, padded, the flat value where the padding does not reach."""
+        flat = torch.tensor(self.NORMAL_MAP_FLAT[space], dtype=torch.float32, device=self.device)
+        # dilate_fill averages over a texel's neighbourhood as it finds it, so the image is 0 outside the charts going in; an
+        # encoded unit normal has a component above 0, and so has every average of some: a texel that is still (0, 0, 0)
+        # coming out is one the padding did not reach
+        coded = self._padded(torch.where(mask[..., None], 0.5 + 0.5 * n, torch.zeros_like(n)), mask, res)
+        return torch.where((coded != 0).any(-1, keepdim=True), coded, flat)
 
     def bake_occlusion_map(self, mesh: Mesh, source=None, resolution=None, occlusion=True, cage=None, seed=0,
                            island_padding: float = 0.02, unwrapper=None) -> Mesh:
@@ -1078,7 +1143,10 @@ class TSR(KernelEngine):
         resolution (TSR.bake_normal_map): Mesh.normal_map, normal_map_space, corner_normals, corner_tangents.  With
         self.occlusion_map = True | k | (k, max_distance) (an instance setting too, default None: nothing more is launched) it also
         gets an ambient-occlusion map over that atlas (TSR.bake_occlusion_map: Mesh.occlusion_map, occlusion_map_rule), baked
-        against the mesh as it entered simplify when simplify is given, else against itself.
+        against the mesh as it entered simplify when simplify is given, else against itself.  With self.bake_project = True | n |
+        (n, cells) (an instance setting too, default None: nothing new is launched) the texture, and the normal map when
+        self.normal_map is set, are baked AT THE SURFACE: every texel is projected from the low-poly face onto the iso-surface
+        of this call's threshold first (TSR.bake_surface_maps, one projection for both maps).
         isosurface: "marching_cubes" (default: the reference's Lewiner mesh, bit for bit what it was without the keyword) or
         "surface_nets" (ops.surface_nets: one vertex inside every cell the surface passes through, one quad across every
         sign-changing lattice edge -- no sliver triangles, and an all-quad mesh in Mesh.quads beside the triangles in
@@ -1134,6 +1202,10 @@ class TSR(KernelEngine):
             ops.occlusion_rule(occlusion)   # a ValueError before anything is launched
         if self.occlusion_map is not None:
             ops.occlusion_rule(self.occlusion_map)
+        if self.bake_project is not None:
+            ops.project_rule(self.bake_project)
+            if not threshold > 0:
+                raise ValueError("bake_project needs a positive threshold (the surface is ln(threshold) in the raw density), got %r" % (threshold,))
         geometry = dict(keep_components=keep_components, simplify=simplify, smooth=smooth, project=project, subdivide=subdivide)
         self._check_geometry(threshold, **geometry)   # a ValueError before anything is launched
         bake = int(bake_texture) if enable_texture else 0
@@ -1168,7 +1240,7 @@ class TSR(KernelEngine):
             # Catmull-Clark refines the extractor's quads while they still cover the faces (smooth keeps them), else the triangles
             self._quads = quads if catmull_clark and keep_components is None and simplify is None else None
             v_pos, t_pos_idx = self._reshaped(v_pos, t_pos_idx, planes, threshold, R, **geometry)
-            out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals, occlusion))
+            out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals, occlusion, threshold=threshold, R=R))
             refined, self._quads = self._quads, None
             if keeps_faces:   # the faces are still the extractor's
                 out[-1].quads = quads
@@ -1227,11 +1299,17 @@ class TSR(KernelEngine):
     # TSR.field_normals on the model's mesh.
     WINDING_OUTWARD = 1.0
 
-    def _textured(self, v_pos, t_pos_idx, planes, enable_texture, bake, normals=None, occlusion=None):
+    def _textured(self, v_pos, t_pos_idx, planes, enable_texture, bake, normals=None, occlusion=None, threshold=25.0, R=None):
         """The appearance half of extract_meshes: nothing, vertex colours (system.py:189-193) or a baked texture; and the
-        vertex normals and the ambient occlusion when asked for."""
+        vertex normals and the ambient occlusion when asked for.  threshold, R: the surface and the lattice of the extraction,
+        for the bake at the surface (self.bake_project)."""
         source, self._occlusion_source = self._occlusion_source, None
-        if enable_texture and bake > 0:
+        if enable_texture and bake > 0 and self.bake_project is not None:   # both maps from one projection of the texels
+            mesh = self.bake_surface_maps(Mesh(v_pos, t_pos_idx), planes, threshold=threshold, project=self.bake_project, resolution=R,
+                                          atlas_resolution=bake, normal_map=self.normal_map)
+            if self.occlusion_map is not None:
+                mesh = self.bake_occlusion_map(mesh, source=source, occlusion=self.occlusion_map)
+        elif enable_texture and bake > 0:
             mesh = self.bake_texture(Mesh(v_pos, t_pos_idx), planes, bake)
             if self.normal_map is not None:   # the same atlas, the texture's resolution
                 mesh = self.bake_normal_map(mesh, planes, space=self.normal_map)
