@@ -1374,6 +1374,58 @@ int sculpt_bake_scene_surface(const float *planes_cl /* [3][H][W][C] */, int C, 
                               float target, int max_steps, float max_dist, float res_tol, float *point, float *normal, float *residual,
                               int *status, int *evals, uint8_t *mask, sculpt_stream_t stream);
 
+/* Displacement bake (csrc/mesh_project.hip, csrc/bake_displacement.hip; ops.project_along, ops.bake_texel_list,
+ * ops.bake_displacement).  DEVICE pointers, asynchronous on `stream`, no host wait.  Added without a
+ * version change (new symbols only).
+ *
+ * sculpt_triplane_project_along: per point a safeguarded Newton search for d(p0 + s n) = target along the line through p0 with
+ * the unit direction n = N / sqrt(N.N), in sculpt_triplane_project's tile (the value and gradient of
+ * sculpt_triplane_density_grad, the same bits).  fp32, the rule without contraction:
+ *   0  N.N = (x x + y y) + z z not finite or not > 0: status 3, height +0, residual +0, evals 0.  s = +0, no bracket
+ *   for k = 0 .. max_steps:
+ *   1  q_a = p0_a + s n_a; (d, g) at q; r = d - target
+ *   2  r not finite: status 3, stop (at k == 0 the best iterate is (0, r))
+ *   3  k == 0 or |r| < |best.r|: best = (s, r)
+ *   4  |r| <= res_tol: status 0, stop.  k == max_steps: status 1, stop
+ *   5  r < 0: a = s.  r > 0: b = s
+ *   6  gn = (gx nx + gy ny) + gz nz; c = s - r / gn; c < -max_dist -> -max_dist, then c > max_dist -> max_dist (comparisons)
+ *   7  a and b both set and c not strictly inside (min(a, b), max(a, b)): c = 0.5 (a + b)
+ *   8  c not finite: status 3, stop.  c == s: status 2, stop
+ *   9  any |p0_a + c n_a| > radius: status 2, stop
+ *   10 s = c
+ *   points, directions  f32 [N][3]
+ *   count        device int32 or null: the number of points is min(max(*count, 0), N), read on the device; rows past it are
+ *                neither read nor written
+ *   scatter      int32 [N] or null: result i is stored at row scatter[i] (a row outside 0 .. out_rows is dropped) instead of i
+ *   out_rows     the rows of the outputs; must be N without a scatter list
+ *   out_height   f32  best.s: signed, world units, positive along n        out_residual  f32  best.r, nullable
+ *   out_status   i32  0 converged, 1 out of steps, 2 left the trust region (|s| <= max_dist and the box), 3 no usable value,
+ *                gradient or direction; nullable                           out_evals     i32  0 .. max_steps + 1, nullable
+ * A point's outputs depend on that point alone.  Refused: what sculpt_triplane_project refuses.  N == 0 is a no-op.
+ *
+ * sculpt_bake_texel_list: the covered texels of rast (tri >= 0 and the index guard of sculpt_bake_scene_color) as flat indices
+ * in row-major order -- torch.nonzero of the coverage, by per-block counts and scans, no atomics -- and their number in *count.
+ *   workspace   sculpt_bake_texel_list_workspace_bytes(res) bytes
+ *   list        i32 [res res]   rows 0 .. *count - 1 are written
+ *   p0          f32 [res res][3], nullable: per listed texel its position, the bits of sculpt_bake_interpolate
+ *   directions  f32 [res res][3], nullable (needs normals f32 [nv][3]): per listed texel (N0 u + N1 v) + N2 w of the per-vertex
+ *               normals at the face's corners, un-normalised, fp32 without contraction
+ *   mask        u8 [res][res], nullable: 1 covered, 0 not
+ *   height, residual f32, status, evals i32 [res][res], each nullable: written for texels that are NOT covered only, with what
+ *               sculpt_triplane_project_along (scatter = list, count = count) leaves out: +0, +0, -1, 0
+ * res == 0 stores *count = 0 and launches nothing else. */
+size_t sculpt_bake_texel_list_workspace_bytes(int res);
+int sculpt_bake_texel_list(const float *v_pos /* [nv][3] */, size_t nv, const void *faces /* [nf][3] */, int faces_i64, size_t nf,
+                           const float *normals /* nullable [nv][3] */, const float *rast /* [res][res][4] */, int res, void *workspace,
+                           int *list, int *count, float *p0, float *directions, uint8_t *mask, float *height, float *residual,
+                           int *status, int *evals, sculpt_stream_t stream);
+int sculpt_triplane_project_along(const float *planes_cl /* [3][H][W][C] */, int C, int H, int W, const void *mlp_packed,
+                                  int n_hidden_64, const float *points /* [N][3] */, const float *directions /* [N][3] */, long long N,
+                                  const int *count /* device, nullable */, float radius, int flags /* QUERY_ALIGN_CORNERS */, float target,
+                                  int max_steps, float max_dist, float res_tol, const int *scatter /* [N] or null */, long long out_rows,
+                                  float *out_height, float *out_residual /* or null */, int *out_status /* or null */,
+                                  int *out_evals /* or null */, sculpt_stream_t stream);
+
 /* Mesh hand-off, HOST side (no GPU work): the face block of a binary little-endian PLY file -- per face `uchar 3` followed by
  * three int32 -- from the int64 faces TSR.run returns (the reference's `t_pos_idx.cpu().numpy()`, TripoSR/tsr/system.py:200).
  * faces_host int64 [n][3] -> records_host uint8 [n][13].  Thread-safe; callers split n over threads (sculptmate_amd/meshio.py). */

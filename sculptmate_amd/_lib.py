@@ -242,6 +242,10 @@ SIGNATURES = {
     "sculpt_mesh_unfold": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp]),
     "sculpt_bake_scene_surface": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _i, _sz, _vp, _i, _f, _vp, _vp, _f, _i, _f, _f, _vp, _vp,
                                        _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_bake_texel_list_workspace_bytes": (_sz, [_i]),
+    "sculpt_bake_texel_list": (_i, [_vp, _sz, _vp, _i, _sz, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_triplane_project_along": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, ctypes.c_longlong, _vp, _f, _i, _f, _i, _f, _f, _vp,
+                                           ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp]),
     "rasterize_cpu": (None, [_vp, _sz, _vp, _sz, ctypes.c_longlong, _vp]),
     "interpolate_cpu": (None, [_vp, _sz, _vp, _sz, _vp, ctypes.c_longlong, _vp]),
 }

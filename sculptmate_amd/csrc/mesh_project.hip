@@ -1,6 +1,7 @@
 // Mesh vertices onto the iso-surface of the density field, for gfx950 (MI355X): a fused Newton iteration along the field's own
 // gradient (sculpt_triplane_project) and the fold guard that follows it (sculpt_mesh_unfold).  The rule is DESIGN.md section
-// 3.1e; tests/_projref.py restates both halves.
+// 3.1e; tests/_projref.py restates both halves.  sculpt_triplane_project_along is the same tile searching along a given line
+// (section 3.1h, tests/_dispref.py).
 //
 // project_kernel
 //   * density_grad_kernel's tile (csrc/field_normal.hip, csrc/field_fwd.h): a wave is 8 points x {value, d/dx, d/dy, d/dz}, the
@@ -82,6 +83,81 @@ __global__ __launch_bounds__(512) void project_kernel(
             if (out_res) out_res[n] = s.br;
             if (out_status) out_status[n] = s.status;
             if (out_evals) out_evals[n] = s.evals;
+        }
+    }
+}
+
+// The line search of DESIGN.md section 3.1h in project_kernel's shape: the same tile, the same evaluation, the rule
+// (line_update, csrc/project_rule.h) run redundantly by the eight lanes of a point, the loop left on a ballot.  The point count
+// comes as a value or from device memory (`count`, clamped to 0 .. cap: the covered-texel list of csrc/bake_displacement.hip is
+// made without a host wait); result i goes to row scatter[i] when a scatter list is given (rows outside 0 .. out_rows are
+// dropped).  A point whose direction has no finite positive length never starts: status 3, height +0, no evaluation.
+template <int C, bool AC>
+__global__ __launch_bounds__(512) void project_along_kernel(
+    const float *__restrict__ planes, int H, int W, const float *__restrict__ blob, const float *__restrict__ pts,
+    const float *__restrict__ dirs, long cap, const int *__restrict__ count, float radius, float span, float target, int K,
+    float max_dist, float res_tol, const int *__restrict__ scatter, long out_rows, float *__restrict__ out_height,
+    float *__restrict__ out_res, int *__restrict__ out_status, int *__restrict__ out_evals, int a0_lds) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
+    const int NH = hd.NH;
+    float *a0s = smem + lds_floats_for(NH);
+    if (a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
+    load_weights_to_lds(smem, blob, hd);
+    const LdsView L = lds_view(smem, NH);
+
+    long N = cap;
+    if (count) {
+        const long c = (long)*count;
+        N = c < 0 ? 0 : (c < cap ? c : cap);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
+    const int p = lane & 31, h = lane >> 5;
+    const int kind = p & 3;
+    const bool is_value = kind == 0;
+    const long ntiles = (N + 7) / 8;
+    const float *A0g = blob + hd.off_a0;
+    const long HW = (long)H * W;
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+
+    for (long tile = (long)blockIdx.x * nwave + wave; tile < ntiles; tile += (long)gridDim.x * nwave) {
+        long n = tile * 8 + (p >> 2);
+        const bool valid = n < N;
+        if (!valid) n = N - 1;   // a copy of the last point (N >= 1 here): it runs the same steps and stores nothing
+        const float p0x = pts[3 * n], p0y = pts[3 * n + 1], p0z = pts[3 * n + 2];
+        float nx, ny, nz;
+        const bool has_dir = line_direction(dirs[3 * n], dirs[3 * n + 1], dirs[3 * n + 2], nx, ny, nz);
+        LineState s;
+        s.s = s.bs = s.br = 0.f;
+        s.a = s.b = 0.f;
+        s.has_a = s.has_b = false;
+        s.status = has_dir ? 1 : 3, s.evals = 0, s.active = has_dir;
+        for (int k = 0; k <= K; ++k) {   // K <= 64 (checked at the entry): at most K + 1 evaluations
+            float qx, qy, qz;
+            line_point(p0x, p0y, p0z, nx, ny, nz, s.s, qx, qy, qz);
+            // one evaluation at (qx, qy, qz): density_grad_kernel's sequence
+            int off[3][4];
+            float wt[3][4];
+            point_taps<AC>(qx, qy, qz, radius, span, H, W, off, wt);
+            tangent_weights<AC>(kind, qx, qy, qz, radius, span, H, W, wt);
+            f32x16 x0 = is_value ? lds_bias16(L.bacc, 0, h, 0) : zero;
+            f32x16 x1 = is_value ? lds_bias16(L.bacc, 0, h, 1) : zero;
+            layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, x0, x1);
+            hidden_layers_fwd(L, NH, lane, h, is_value, x0, x1);
+            const float sv = last_dot0_nobias(L, h, x0, x1);
+            const float d = quad_bcast<0>(sv) + L.blast[0];
+            const float gx = quad_bcast<1>(sv), gy = quad_bcast<2>(sv), gz = quad_bcast<3>(sv);
+            line_update(s, k, K, d, gx, gy, gz, p0x, p0y, p0z, nx, ny, nz, target, radius, max_dist, res_tol);
+            if (__ballot(s.active) == 0ull) break;   // wave-uniform: all eight points have stopped
+        }
+        if (valid && is_value && h == 0) {
+            const long o = scatter ? (long)scatter[n] : n;
+            if (o >= 0 && o < out_rows) {
+                out_height[o] = s.bs;
+                if (out_res) out_res[o] = s.br;
+                if (out_status) out_status[o] = s.status;
+                if (out_evals) out_evals[o] = s.evals;
+            }
         }
     }
 }
@@ -193,6 +269,43 @@ extern "C" int sculpt_triplane_project(const float *planes_cl, int C, int H, int
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W,
                        reinterpret_cast<const float *>(mlp_packed), points, (long)N, radius, span, target, max_steps, md2, res_tol,
                        out_points, out_residual, out_status, out_evals, a0_lds);
+    SC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sculpt_triplane_project_along(const float *planes_cl, int C, int H, int W, const void *mlp_packed, int n_hidden_64,
+                                             const float *points, const float *directions, long long N, const int *count,
+                                             float radius, int flags, float target, int max_steps, float max_dist, float res_tol,
+                                             const int *scatter, long long out_rows, float *out_height, float *out_residual,
+                                             int *out_status, int *out_evals, sculpt_stream_t stream) {
+    SC_REQUIRE(C == 40, "triplane_project_along: built for C=40 channels per plane (got %d)", C);
+    SC_REQUIRE(planes_cl && mlp_packed, "triplane_project_along: null input");
+    SC_REQUIRE(H >= 1 && W >= 1, "triplane_project_along: bad plane size %d x %d", H, W);
+    SC_REQUIRE(N >= 0, "triplane_project_along: negative point count %lld", N);
+    SC_REQUIRE((flags & ~(int)SCULPT_QUERY_ALIGN_CORNERS) == 0, "triplane_project_along: unknown flags %d", flags);
+    SC_REQUIRE(n_hidden_64 >= 0, "triplane_project_along: bad n_hidden_64");
+    SC_REQUIRE(radius > 0.f, "triplane_project_along: radius must be positive");
+    SC_REQUIRE(max_steps >= 0 && max_steps <= 64, "triplane_project_along: max_steps=%d (0 .. 64)", max_steps);
+    SC_REQUIRE(max_dist > 0.f && max_dist < INFINITY, "triplane_project_along: max_dist=%g must be positive and finite", (double)max_dist);   // a NaN fails
+    SC_REQUIRE(res_tol > 0.f && res_tol < INFINITY, "triplane_project_along: res_tol=%g must be positive and finite", (double)res_tol);
+    SC_REQUIRE(target == target, "triplane_project_along: target is NaN");
+    SC_REQUIRE(scatter ? out_rows >= 0 : out_rows == N, "triplane_project_along: out_rows=%lld (the rows of the outputs; N without a scatter list)", out_rows);
+    if (N == 0 || (scatter && out_rows == 0)) return 0;   // empty arrays have no address: nothing to refuse, nothing to launch
+    SC_REQUIRE(out_height, "triplane_project_along: null out_height");
+    SC_REQUIRE(points && directions, "triplane_project_along: null points or directions");
+    size_t lds = (size_t)lds_floats_for(n_hidden_64) * sizeof(float);
+    SC_REQUIRE(lds <= 160 * 1024, "triplane_project_along: %d hidden layers do not fit LDS", n_hidden_64);
+    const size_t a0_bytes = (size_t)3 * C * 64 * sizeof(float);
+    const int a0_lds = lds + a0_bytes <= 160 * 1024 ? 1 : 0;
+    if (a0_lds) lds += a0_bytes;
+    auto kern = (flags & (int)SCULPT_QUERY_ALIGN_CORNERS) ? project_along_kernel<40, true> : project_along_kernel<40, false>;
+    SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const long ntiles = ((long)N + 7) / 8;
+    const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
+    const float span = (float)((double)radius - (double)(-radius));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W,
+                       reinterpret_cast<const float *>(mlp_packed), points, directions, (long)N, count, radius, span, target, max_steps,
+                       max_dist, res_tol, scatter, (long)out_rows, out_height, out_residual, out_status, out_evals, a0_lds);
     SC_LAUNCH_CHECK();
     return 0;
 }

@@ -76,4 +76,95 @@ __device__ __forceinline__ bool rule_update(ProjState &s, int k, int K, float d,
     return took;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The line rule of DESIGN.md section 3.1h: a safeguarded Newton search for d(p0 + s n) = target along the fixed unit direction n
+// (sculpt_triplane_project_along, csrc/mesh_project.hip).  tests/_dispref.py restates it (line_search in NumPy, composed_device
+// one torch call per operation).
+// ---------------------------------------------------------------------------------------------------------------------------
+struct LineState {
+    float s;              // current parameter along the line
+    float bs, br;         // best parameter (the height) and its residual
+    float a, b;           // the last parameters with r < 0 and with r > 0: a sign change once both are set
+    bool has_a, has_b;
+    int status, evals;
+    bool active;
+};
+
+// N -> the unit direction n = N / sqrt(N.N); false (and n = 0) when N.N is not finite or not > 0
+__device__ __forceinline__ bool line_direction(float Nx, float Ny, float Nz, float &nx, float &ny, float &nz) {
+#pragma clang fp contract(off)
+    const float nn = (Nx * Nx + Ny * Ny) + Nz * Nz;
+    if (!(nn > 0.f) || !finite_f(nn)) {
+        nx = ny = nz = 0.f;
+        return false;
+    }
+    const float len = sqrtf(nn);
+    nx = Nx / len, ny = Ny / len, nz = Nz / len;
+    return true;
+}
+
+// the point of the line at parameter s: one product and one sum per axis
+__device__ __forceinline__ void line_point(float p0x, float p0y, float p0z, float nx, float ny, float nz, float s, float &qx, float &qy,
+                                           float &qz) {
+#pragma clang fp contract(off)
+    qx = p0x + s * nx, qy = p0y + s * ny, qz = p0z + s * nz;
+}
+
+// One turn of the line rule after the evaluation (d, g) at line_point(st.s): steps 1 .. 10 of section 3.1h.  A point that has
+// stopped is left as it is.
+__device__ __forceinline__ void line_update(LineState &st, int k, int K, float d, float gx, float gy, float gz, float p0x, float p0y,
+                                            float p0z, float nx, float ny, float nz, float target, float radius, float max_dist,
+                                            float res_tol) {
+#pragma clang fp contract(off)
+    if (!st.active) return;
+    st.evals += 1;
+    const float r = d - target;
+    if (!finite_f(r)) {
+        st.status = 3;
+        st.active = false;
+        if (k == 0) st.bs = 0.f, st.br = r;
+        return;
+    }
+    if (k == 0 || fabsf(r) < fabsf(st.br)) st.bs = st.s, st.br = r;
+    if (fabsf(r) <= res_tol) {
+        st.status = 0;
+        st.active = false;
+        return;
+    }
+    if (k == K) {
+        st.status = 1;
+        st.active = false;
+        return;
+    }
+    if (r < 0.f) st.a = st.s, st.has_a = true;
+    if (r > 0.f) st.b = st.s, st.has_b = true;
+    const float gn = (gx * nx + gy * ny) + gz * nz;
+    float c = st.s - r / gn;
+    const float lo = -max_dist;
+    c = c < lo ? lo : c;   // comparisons, not fmin / fmax: a NaN stays a NaN
+    c = c > max_dist ? max_dist : c;
+    if (st.has_a && st.has_b) {
+        const float blo = st.a < st.b ? st.a : st.b, bhi = st.a < st.b ? st.b : st.a;
+        if (!(c > blo && c < bhi)) c = 0.5f * (st.a + st.b);
+    }
+    if (!finite_f(c)) {
+        st.status = 3;
+        st.active = false;
+        return;
+    }
+    if (c == st.s) {   // pinned at the end of the trust interval
+        st.status = 2;
+        st.active = false;
+        return;
+    }
+    float cx, cy, cz;
+    line_point(p0x, p0y, p0z, nx, ny, nz, c, cx, cy, cz);
+    if (fabsf(cx) > radius || fabsf(cy) > radius || fabsf(cz) > radius) {   // the box is part of the trust region
+        st.status = 2;
+        st.active = false;
+        return;
+    }
+    st.s = c;
+}
+
 }  // namespace sculpt

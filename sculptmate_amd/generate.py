@@ -63,7 +63,11 @@ class TripoGenerator(GeneratorFacade):
     the Blender sinks take none: the .glb carries it to Blender's own importer.
     `bake_project` (default None): True, an int n or a tuple (n, cells) (ops.project_rule) bakes the texture, and the normal map
     when `normal_map` is set, AT THE SURFACE: every texel is first projected from the low-poly face onto the field's
-    iso-surface (TSR.bake_surface_maps; copied to the model as TSR.bake_project)."""
+    iso-surface (TSR.bake_surface_maps; copied to the model as TSR.bake_project).
+    `displacement_map` (default None): True, an int n or a tuple (n, cells) (ops.displacement_rule) bakes a displacement map --
+    the height along the low-poly normal up to the field's iso-surface -- beside every baked texture, over its atlas
+    (TSR.bake_displacement_map; copied to the model as TSR.displacement_map).  It comes back as the mesh's plain attribute
+    `displacement`; Mesh.export(path, displacement=mesh.displacement) writes it."""
 
     def __init__(self, device):
         super().__init__(device, checkpoint_dir=ROOT_DIR + "/checkpoints/", chunk_size=8192, mc_resolution=256,
@@ -81,6 +85,7 @@ class TripoGenerator(GeneratorFacade):
         self.normal_map = None
         self.occlusion_map = None
         self.bake_project = None
+        self.displacement_map = None
 
     def _construct_model(self):
         model = TSR.from_pretrained(self.checkpoint_dir, config_name="config.yaml", weight_name="model.ckpt",
@@ -97,6 +102,7 @@ class TripoGenerator(GeneratorFacade):
             self.model.normal_map = self.normal_map
             self.model.occlusion_map = self.occlusion_map
             self.model.bake_project = self.bake_project
+            self.model.displacement_map = self.displacement_map
             self.last_meshes = self.model.extract_mesh(codes, enable_texture=enable_texture, mesh_name=input_name,
                                                        resolution=self.mc_resolution,
                                                        bake_texture=int(self.bake_texture_resolution or 0),

@@ -301,6 +301,55 @@ def write_glb(path, vertices, faces, vertex_colors=None, normals=None, uvs=None,
         fh.write(struct.pack("<II", len(blob), _CHUNK_BIN) + bytes(blob))
 
 
+def add_glb_displacement(path, png, scale, midlevel):
+    """A displacement map into a .glb that write_glb wrote: `png` (the bytes of a tsr.displacement.DisplacementMap's 16-bit grey
+    PNG) becomes a further image named "displacement" that no material refers to -- glTF has no core displacement slot, so it
+    travels as the object-space normal map does -- and the mesh's `extras` name it with what a displacement node needs:
+    {"displacement": {"image": index, "scale": scale, "midlevel": midlevel}}.  The file is rewritten in place."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    magic, version, total = struct.unpack("<III", data[:12])
+    if magic != _GLB_MAGIC or version != 2 or total != len(data):
+        raise ValueError("not a glTF 2.0 binary container")
+    n_json, tag = struct.unpack("<II", data[12:20])
+    assert tag == _CHUNK_JSON
+    doc = json.loads(data[20:20 + n_json])
+    n_bin, tag = struct.unpack("<II", data[20 + n_json:28 + n_json])
+    assert tag == _CHUNK_BIN
+    blob = bytearray(data[28 + n_json:28 + n_json + n_bin])
+    while len(blob) % 4:
+        blob.append(0)
+    doc["bufferViews"].append({"buffer": 0, "byteOffset": len(blob), "byteLength": len(png)})
+    blob.extend(png)
+    while len(blob) % 4:
+        blob.append(0)
+    images = doc.setdefault("images", [])
+    images.append({"bufferView": len(doc["bufferViews"]) - 1, "mimeType": "image/png", "name": "displacement"})
+    doc["meshes"][0].setdefault("extras", {})["displacement"] = {"image": len(images) - 1, "scale": float(scale),
+                                                                 "midlevel": float(midlevel)}
+    doc["buffers"] = [{"byteLength": len(blob)}]
+    text = json.dumps(doc, separators=(",", ":")).encode()
+    text += b" " * (-len(text) % 4)
+    with open(path, "wb") as fh:
+        fh.write(struct.pack("<III", _GLB_MAGIC, 2, 12 + 8 + len(text) + 8 + len(blob)))
+        fh.write(struct.pack("<II", len(text), _CHUNK_JSON) + text)
+        fh.write(struct.pack("<II", len(blob), _CHUNK_BIN) + bytes(blob))
+
+
+def add_obj_displacement(path, png, scale):
+    """A displacement map beside an .obj that write_obj_textured wrote: NAME_disp.png (`png`: the bytes of a
+    tsr.displacement.DisplacementMap's 16-bit grey PNG, midlevel 0.5) and the line `disp -mm <-scale/2> <scale> NAME_disp.png`
+    -- base and gain of the stored 0 .. 1 value, in world units -- at the end of NAME.mtl."""
+    import os
+
+    stem = os.path.splitext(str(path))[0]
+    name = os.path.basename(stem)
+    with open(stem + ".mtl", "a") as fh:
+        fh.write("disp -mm %.9g %.9g %s_disp.png\n" % (-0.5 * float(scale), float(scale), name))
+    with open(stem + "_disp.png", "wb") as fh:
+        fh.write(png)
+
+
 def read_glb(path, uv_origin="bottom_left"):
     """Read back what write_glb wrote -> dict(vertices, faces, normals, tangents, uvs, vertex_colors, occlusion, basecolor_tex,
     normal_tex, occlusion_tex, roughness, metallic, extra_images); uvs are returned in `uv_origin` convention (see write_glb).  Not a general glTF loader: one

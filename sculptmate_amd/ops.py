@@ -2305,6 +2305,213 @@ def bake_surface_route():
     return bake_scene_surface if _lib.form_has("SCULPT_DISTANCE_FORM", "fusedsurface") else bake_scene_surface_composed
 
 
+# ----------------------------------------------------------------------------------------------
+# displacement bake: each texel to the iso-surface along the low-poly normal (csrc/bake_displacement.hip)
+# ----------------------------------------------------------------------------------------------
+DISPLACEMENT_STEPS, DISPLACEMENT_CELLS = 8, 2.0   # what displacement=True means: at most 8 steps within 2 lattice cells
+
+
+def displacement_rule(displacement):
+    """`displacement` of the displacement bake -> (steps, max_cells): True (8 steps within 2 lattice cells on either side), an
+    int n in 1 .. 64 (n steps, 2 cells) or a tuple (n, cells) with 0 < cells <= 8.  Anything else -- False, None, a str, a bare
+    float, NaN, another length -- is a ValueError, raised here, before anything is launched."""
+    if displacement is True or (isinstance(displacement, np.bool_) and bool(displacement)):
+        return DISPLACEMENT_STEPS, DISPLACEMENT_CELLS
+    if _is_count(displacement, 1, PROJECT_MAX_STEPS):
+        return int(displacement), DISPLACEMENT_CELLS
+    if isinstance(displacement, tuple) and len(displacement) == 2 and _is_count(displacement[0], 1, PROJECT_MAX_STEPS):
+        cells = displacement[1]
+        if _is_real(cells) and 0.0 < float(cells) <= PROJECT_MAX_CELLS:
+            return int(displacement[0]), float(cells)   # a NaN fails the comparison
+    raise ValueError("displacement must be True, an int in 1 .. %d (steps) or (steps, cells) with 0 < cells <= %g, got %r"
+                     % (PROJECT_MAX_STEPS, PROJECT_MAX_CELLS, displacement))
+
+
+def _project_along_launch(planes, mlp, pts, dirs, n, count, radius, align_corners, target, steps, max_dist, res_tol, scatter, rows,
+                          height, ex):
+    check(lib.sculpt_triplane_project_along(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(pts),
+                                            _ptr(dirs), n, _ptr(count), float(radius), _lib.QUERY_ALIGN_CORNERS if align_corners else 0,
+                                            float(target), int(steps), float(max_dist), float(res_tol), _ptr(scatter), rows,
+                                            _ptr(height), _ptr(ex["residual"]), _ptr(ex["status"]), _ptr(ex["evals"]), _stream()))
+
+
+def project_along(planes, mlp, points, directions, target, max_dist, steps=DISPLACEMENT_STEPS, res_tol=PROJECT_RES_TOL, radius=0.87,
+                  align_corners=False, want=(), count=None, out=None):
+    """Per point the signed height h along the unit direction n = directions / |directions| at which the raw density reaches
+    `target`: d(points + h n) = target, found by a safeguarded Newton search along that line in ONE launch
+    (sculpt_triplane_project_along; the rule, numbered, is DESIGN.md section 3.1h): the Newton step of the density along the
+    line, kept within |h| <= max_dist and the box [-radius, radius]^3, replaced by the midpoint of the last sign change whenever
+    it would leave it, until |d - target| <= res_tol.  The point never leaves the line, and the height that comes back is the
+    one with the smallest |d - target| seen -- never worse than h = 0.
+    planes: [3,C,H,W] (converted to channel-last here, once) or a ChannelLastPlanes; points, directions [..., 3].
+    -> (height f32 [...], extras) with extras[k] for k in want:
+       "residual" f32 [...]   d(points + height n) - target: the point query's density there minus target, in fp32
+       "status"   i32 [...]   0 converged, 1 out of steps, 2 the search left the trust region, 3 no usable value, gradient or
+                              direction (a zero or non-finite direction: height 0, evals 0)
+       "evals"    i32 [...]   evaluations of (d, g) the point used, 0 .. steps + 1
+    count: a device int32 tensor of one element -- only the first min(count, N) points are read, and only their rows of the
+    outputs are written; out: a dict of preallocated flat outputs ("height" and the extras) to write into, for the rows that
+    must stay untouched.  A point's result depends on that point alone."""
+    want = tuple(want)
+    unknown = set(want) - {"residual", "status", "evals"}
+    if unknown:
+        raise SculptError("project_along: unknown output %s" % sorted(unknown))
+    _project_args(steps, max_dist, res_tol, target)
+    if points.shape[-1] != 3 or tuple(points.shape) != tuple(directions.shape):
+        raise SculptError("project_along: points %s and directions %s must both be [..., 3]" % (tuple(points.shape), tuple(directions.shape)))
+    if not isinstance(planes, ChannelLastPlanes):
+        planes = ChannelLastPlanes(planes)
+    shape = tuple(points.shape[:-1])
+    pts = _req(points.reshape(-1, 3).contiguous(), torch.float32, "points")
+    dirs = _req(directions.reshape(-1, 3).contiguous(), torch.float32, "directions")
+    N = pts.shape[0]
+    if count is not None:
+        count = _req(count, torch.int32, "count")
+        if count.numel() != 1:
+            raise SculptError("project_along: count must hold one int32")
+    kinds = (("height", torch.float32), ("residual", torch.float32), ("status", torch.int32), ("evals", torch.int32))
+    ex = {}
+    for k, dt in kinds:
+        if k != "height" and k not in want:
+            ex[k] = None
+        elif out is not None and k in out:
+            ex[k] = _req(out[k], dt, k)
+            if ex[k].numel() != N:
+                raise SculptError("project_along: out[%r] must hold %d elements" % (k, N))
+        else:
+            ex[k] = torch.empty((N,), dtype=dt, device=pts.device)
+    _project_along_launch(planes, mlp, pts, dirs, N, count, radius, align_corners, target, steps, max_dist, res_tol, None, N,
+                          ex["height"], ex)
+    return ex["height"].view(*shape), {k: ex[k].view(*shape) for k in want}
+
+
+def bake_texel_list(v_pos, faces, rast, normals=None):
+    """The covered texels of a rasterised atlas as a list on the device, with NO host wait (sculpt_bake_texel_list: per-block
+    counts and scans, no atomics): v_pos f32 [Nv,3], faces i32 / i64 [Nf,3], rast f32 [res,res,4] from bake_rasterize, normals
+    f32 [Nv,3] or None.  "Covered" is the index guard of the scene bakes (tri >= 0 and in range, its vertex rows in range).
+    -> dict(list i32 [res*res]: rows 0 .. count-1 are the flat indices of the covered texels in row-major order, the rest is not
+    written; count i32 [1] on the device; p0 f32 [res*res,3]: per listed texel the position bake_interpolate gives; directions
+    f32 [res*res,3] (with normals): per listed texel the per-vertex normals interpolated un-normalised, (N0 u + N1 v) + N2 w;
+    mask bool [res,res])."""
+    if not (isinstance(rast, torch.Tensor) and rast.is_contiguous()):
+        raise SculptError("bake_texel_list: rast must be a contiguous tensor")
+    v = _req(v_pos.contiguous() if isinstance(v_pos, torch.Tensor) else v_pos, torch.float32, "v_pos")
+    if not (isinstance(faces, torch.Tensor) and faces.is_cuda) or faces.dtype not in (torch.int32, torch.int64):
+        raise SculptError("bake_texel_list: faces must be an int32 or int64 CUDA/HIP tensor")
+    f = faces.contiguous()
+    r = _req(rast, torch.float32, "rast")
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or r.ndim != 3 or r.shape[0] != r.shape[1] or r.shape[2] != 4:
+        raise SculptError("bake_texel_list: v_pos [Nv,3], faces [Nf,3], rast [res,res,4]")
+    nrm = None
+    if normals is not None:
+        nrm = _req(normals.contiguous(), torch.float32, "normals")
+        if tuple(nrm.shape) != tuple(v.shape):
+            raise SculptError("bake_texel_list: normals %s must be per vertex %s" % (tuple(nrm.shape), tuple(v.shape)))
+    return _texel_list(v, f, r, nrm, None)
+
+
+def _texel_list(v, f, r, nrm, images):
+    res, dev = r.shape[0], r.device
+    n = res * res
+    got = {"list": torch.empty((n,), dtype=torch.int32, device=dev), "count": torch.empty((1,), dtype=torch.int32, device=dev),
+           "p0": torch.empty((n, 3), dtype=torch.float32, device=dev),
+           "directions": torch.empty((n, 3), dtype=torch.float32, device=dev) if nrm is not None else None,
+           "mask": torch.empty((res, res), dtype=torch.uint8, device=dev)}
+    ws = torch.empty((max(1, int(lib.sculpt_bake_texel_list_workspace_bytes(res))),), dtype=torch.uint8, device=dev)
+    im = images or {}
+    check(lib.sculpt_bake_texel_list(_ptr(v), v.shape[0], _ptr(f), int(f.dtype == torch.int64), f.shape[0], _ptr(nrm), _ptr(r), res,
+                                     _ptr(ws), _ptr(got["list"]), _ptr(got["count"]), _ptr(got["p0"]), _ptr(got["directions"]),
+                                     _ptr(got["mask"]), _ptr(im.get("height")), _ptr(im.get("residual")), _ptr(im.get("status")),
+                                     _ptr(im.get("evals")), _stream()))
+    got["mask"] = got["mask"].view(torch.bool)
+    return {k: t for k, t in got.items() if t is not None}
+
+
+_DISPLACEMENT_IMAGES = (("height", torch.float32), ("residual", torch.float32), ("status", torch.int32), ("evals", torch.int32))
+
+
+def _bake_displacement_args(who, planes, v_pos, faces, normals, rast, target, max_dist, steps, res_tol, want):
+    want = tuple(want)
+    unknown = set(want) - {"residual", "status", "evals"}
+    if unknown:
+        raise SculptError("%s: unknown output %s" % (who, sorted(unknown)))
+    _project_args(steps, max_dist, res_tol, target)
+    if isinstance(rast, torch.Tensor) and not rast.is_contiguous():
+        raise SculptError("%s: rast must be contiguous" % who)
+    planes, v, f, r, res = _bake_scene_args(who, planes, v_pos, faces, rast)
+    nrm = _req(normals.contiguous() if isinstance(normals, torch.Tensor) else normals, torch.float32, "normals")
+    if tuple(nrm.shape) != tuple(v.shape):
+        raise SculptError("%s: normals %s must be per vertex %s" % (who, tuple(nrm.shape), tuple(v.shape)))
+    return planes, v, f, nrm, r, res, want
+
+
+def bake_displacement(planes, mlp, v_pos, faces, normals, rast, target, max_dist, steps=DISPLACEMENT_STEPS, res_tol=PROJECT_RES_TOL,
+                      radius=0.87, want=()):
+    """The displacement bake without a host wait: per covered texel of a rasterised atlas the signed height along the low-poly
+    normal at which the scene code's raw density reaches `target` -- project_along's rule from the texel's point p0
+    (bake_interpolate's bits) along the per-vertex `normals` f32 [Nv,3] interpolated at the texel.  Two calls:
+    sculpt_bake_texel_list (the covered texels as a list on the device, their p0 and directions, the images' values outside the
+    charts) and sculpt_triplane_project_along over that list, which reads the list's length on the device and scatters into
+    the images.  planes, v_pos, faces, rast, radius: as for bake_scene_normal; target, max_dist, steps, res_tol: as for
+    project_along.
+    -> (height f32 [res,res], mask bool [res,res], extras) with extras[k] for k in want: "residual" f32, "status" i32 (0 .. 3
+    as project_along; -1 where not covered), "evals" i32, each [res,res].  Where a texel is not covered height and residual are
+    exactly 0 and evals is 0.  A texel's outputs depend on that texel alone."""
+    planes, v, f, nrm, r, res, want = _bake_displacement_args("bake_displacement", planes, v_pos, faces, normals, rast, target, max_dist,
+                                                              steps, res_tol, want)
+    dev = r.device
+    im = {k: torch.empty((res, res), dtype=dt, device=dev) if k == "height" or k in want else None for k, dt in _DISPLACEMENT_IMAGES}
+    if res == 0:
+        return im["height"], torch.empty((0, 0), dtype=torch.bool, device=dev), {k: im[k] for k in want}
+    got = _texel_list(v, f, r, nrm, im)
+    _project_along_launch(planes, mlp, got["p0"], got["directions"], res * res, got["count"], radius, False, target, steps, max_dist,
+                          res_tol, got["list"], res * res, im["height"], im)
+    return im["height"], got["mask"], {k: im[k] for k in want}
+
+
+def bake_displacement_composed(planes, mlp, v_pos, faces, normals, rast, target, max_dist, steps=DISPLACEMENT_STEPS,
+                               res_tol=PROJECT_RES_TOL, radius=0.87, want=()):
+    """bake_displacement from ops that stand on their own, the restatement it is held to bit for bit and the route it is timed
+    against (SCULPT_DISTANCE_FORM=composeddisplacement selects it in TSR.bake_displacement_map): the coverage in torch (bake_scene_surface_composed's) -> bake_interpolate of the positions and of the normals ->
+    the covered texels (nonzero: this waits for the device) -> project_along -> scatter into images that are 0 (status -1)
+    elsewhere.  Same arguments, same result."""
+    planes, v, f, nrm, r, res, want = _bake_displacement_args("bake_displacement_composed", planes, v_pos, faces, normals, rast, target,
+                                                              max_dist, steps, res_tol, want)
+    dev = r.device
+    im = {"height": torch.zeros((res, res), dtype=torch.float32, device=dev),
+          "residual": torch.zeros((res, res), dtype=torch.float32, device=dev),
+          "status": torch.full((res, res), -1, dtype=torch.int32, device=dev),
+          "evals": torch.zeros((res, res), dtype=torch.int32, device=dev)}
+    nv, nf = v.shape[0], f.shape[0]
+    tri = r[..., 3]
+    covered = (tri >= 0) & (tri < 2147483648.0)                     # a NaN fails both
+    if nf == 0 or nv == 0:
+        covered = torch.zeros_like(covered)
+    else:
+        t = torch.where(covered, tri, torch.zeros_like(tri)).to(torch.int64)
+        covered = covered & (t < nf)
+        rows = f[t.clamp(max=nf - 1)].to(torch.int64)               # [res, res, 3]
+        covered = covered & ((rows >= 0) & (rows < nv)).all(-1)
+        r = torch.where(covered[..., None], r, r.new_tensor([0.0, 0.0, 0.0, -1.0])).contiguous()
+    idx = covered.reshape(-1).nonzero()[:, 0]
+    if idx.numel() > 0:
+        pos = bake_interpolate(v, r, f).reshape(-1, 3)[idx].contiguous()
+        dirs = bake_interpolate(nrm, r, f).reshape(-1, 3)[idx].contiguous()
+        h, got = project_along(planes, mlp, pos, dirs, target, max_dist, steps=steps, res_tol=res_tol, radius=radius,
+                               want=("residual", "status", "evals"))
+        im["height"].view(-1)[idx] = h
+        for k in got:
+            im[k].view(-1)[idx] = got[k]
+    return im["height"], covered, {k: im[k] for k in want}
+
+
+def bake_displacement_route():
+    """What TSR.bake_displacement_map calls: bake_displacement, the route without a host wait, unless SCULPT_DISTANCE_FORM holds
+    the token `composeddisplacement` (then bake_displacement_composed).  The two give the same bits; the no-wait route is the
+    default because it is the faster one on the flagship atlases, in both orders (DESIGN.md 3.1h has the figures)."""
+    return bake_displacement_composed if _lib.form_has("SCULPT_DISTANCE_FORM", "composeddisplacement") else bake_displacement
+
+
 def resize_aa_bilinear(img_hwc, size):
     """F.interpolate(bilinear, align_corners=False, antialias=True) to (size, size) on an HWC fp32 device image
     (ImagePreprocessor.convert_and_resize, tsr/utils.py:82-88)."""

@@ -85,3 +85,37 @@ def import_textured_blender(verts, faces, uvs, texture_image, name="NewMesh", no
         links.new(nm_tex.outputs["Color"], nm.inputs["Color"])
         links.new(nm.outputs["Normal"], bsdf.inputs["Normal"])
     return new_object
+
+
+def add_displacement_blender(obj, displacement, name=None):
+    """A baked displacement map (tsr.displacement.DisplacementMap of TSR.bake_displacement_map) onto the first material of
+    `obj`, an object one of the sinks above made with the map's atlas as its UV layer: a Non-Color image texture (the 16-bit
+    picture as floats, code / 65535) -> a Displacement node with the map's midlevel and scale -> the material output's
+    Displacement socket.  The material is set to displace ("BOTH": true displacement where the mesh is subdivided, bump
+    elsewhere); nothing else of the node graph is touched.  -> the Displacement node."""
+    import bpy
+
+    name = name or obj.name
+    materials = obj.data.materials
+    if len(materials) == 0:
+        raise ValueError("add_displacement_blender: the object has no material (import it with one of the sinks first)")
+    mat = materials[0]
+    code = np.flip(np.asarray(displacement.image(), np.float32) / np.float32(65535.0), axis=0)   # Blender's row 0 is the bottom
+    res_y, res_x = code.shape
+    img = bpy.data.images.new("%s_Displacement" % name, width=res_x, height=res_y)
+    rgba = np.stack([code, code, code, np.ones_like(code)], axis=2)
+    img.pixels.foreach_set(rgba.ravel())
+    img.colorspace_settings.name = "Non-Color"
+    nodes, links = mat.node_tree.nodes, mat.node_tree.links
+    out_node = next((n for n in nodes if n.type in ("ShaderNodeOutputMaterial", "OUTPUT_MATERIAL")), None)
+    if out_node is None:
+        out_node = nodes.new(type="ShaderNodeOutputMaterial")
+    tex = nodes.new(type="ShaderNodeTexImage")
+    tex.image = img
+    disp = nodes.new(type="ShaderNodeDisplacement")
+    disp.inputs["Midlevel"].default_value = float(displacement.midlevel)
+    disp.inputs["Scale"].default_value = float(displacement.scale)
+    links.new(tex.outputs["Color"], disp.inputs["Height"])
+    links.new(disp.outputs["Displacement"], out_node.inputs["Displacement"])
+    mat.displacement_method = "BOTH"
+    return disp

@@ -210,7 +210,7 @@ class Mesh:
         normal_map_image quantises: floor(256 x) clipped to 0..255, no dither."""
         return self._map_image("occlusion_map", "Mesh.occlusion_map_image: this mesh has no baked occlusion map (TSR.bake_occlusion_map)", grey=True)
 
-    def export(self, path):
+    def export(self, path, displacement=None):
         """Write .obj / .ply / .glb by extension (sculptmate_amd/meshio.py), the call upstream users make on the
         trimesh object their extract_mesh returns.  A baked mesh (uvs + texture) goes out textured: .glb with TEXCOORD_0 and the
         base-colour texture (glTF has one index per vertex, so positions are un-indexed to 3*Nf vertices there and only there),
@@ -228,14 +228,21 @@ class Mesh:
         and every baked path write the triangles.
         A baked occlusion map (TSR.bake_occlusion_map; uvs + occlusion_map, with or without a texture or normal map) goes the
         textured way as well: .glb gets material.occlusionTexture (three equal channels; glTF reads the red one, strength at its
-        default of 1), .obj gets `map_Ka NAME_ao.png` in the .mtl and the PNG beside it."""
+        default of 1), .obj gets `map_Ka NAME_ao.png` in the .mtl and the PNG beside it.
+        displacement: a tsr.displacement.DisplacementMap baked over this mesh's atlas (TSR.bake_displacement_map; the mesh needs
+        its uvs) goes the textured way as a 16-bit grey PNG: .obj gets `disp -mm <-scale/2> <scale> NAME_disp.png` in the .mtl
+        and the PNG beside it; .glb gets it as a further image named in the mesh's extras with `scale` and `midlevel` (glTF has
+        no core displacement slot, so it follows the object-space normal map).  None (default): every file is byte for byte
+        what it was without the keyword.  .ply has no slot for it."""
         from .. import meshio
 
         ext = str(path).rsplit(".", 1)[-1].lower()
         writer = {"obj": meshio.write_obj, "ply": meshio.write_ply, "glb": meshio.write_glb}.get(ext)
         if writer is None:
             raise ValueError(f"unsupported mesh format .{ext} (obj, ply, glb)")
-        baked = self.texture is not None or self.normal_map is not None or self.occlusion_map is not None
+        if displacement is not None and self.uvs is None:
+            raise ValueError("Mesh.export: a displacement map belongs to an atlas; this mesh has no uvs (TSR.bake_displacement_map returns the mesh with them)")
+        baked = self.texture is not None or self.normal_map is not None or self.occlusion_map is not None or displacement is not None
         if self.uvs is not None and baked and ext in ("glb", "obj"):
             v, f, uv = _host(self.vertices), _host(self.faces), _host(self.uvs)
             picture = None if self.texture is None else np.asarray(self.texture_image())
@@ -258,11 +265,15 @@ class Mesh:
                         extra["extra_images"] = {"normal_map_object": bump}
                 meshio.write_glb(str(path), v[f.reshape(-1)], np.arange(f.size, dtype=np.int64).reshape(-1, 3), uvs=uv,
                                  basecolor_tex=picture, normals=normals, **extra)
+                if displacement is not None:
+                    meshio.add_glb_displacement(str(path), displacement.png_bytes(), displacement.scale, displacement.midlevel)
             else:
                 extra = {} if bump is None else {"normal_map": bump}
                 if shade is not None:
                     extra["occlusion_map"] = shade
                 meshio.write_obj_textured(str(path), v, f, uv, picture, normals=vn, **extra)
+                if displacement is not None:
+                    meshio.add_obj_displacement(str(path), displacement.png_bytes(), displacement.scale)
             return
         extra = {} if self.vertex_occlusion is None or ext == "obj" else {"occlusion": _host(self.vertex_occlusion)}
         if ext == "obj" and self.quads is not None:   # the all-quad mesh of surface nets: `f a b c d` lines (.ply and .glb stay triangles)

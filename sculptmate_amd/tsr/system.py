@@ -958,6 +958,10 @@ class TSR(KernelEngine):
     # None | what ops.project_rule accepts (True, n, (n, cells)): when set, extract_meshes bakes the texture, and the normal map when
     # self.normal_map is set, AT THE SURFACE (bake_surface_maps) with its own threshold and resolution.  None: nothing new is launched
     bake_project = None
+    # None | what ops.displacement_rule accepts (True, n, (n, cells)): when set, extract_meshes bakes a displacement map beside a
+    # texture bake (bake_displacement_map on the baked mesh's atlas) and leaves it on the mesh as the plain attribute
+    # `displacement` (a tsr.displacement.DisplacementMap, no Mesh field).  None: nothing new is launched
+    displacement_map = None
     _quads = None   # extract_meshes -> _reshaped: the extractor's quads as a Catmull-Clark cage; and back: the refined quads
 
     def bake_normal_map(self, mesh: Mesh, scene_code, resolution=None, space="tangent", island_padding: float = 0.02,
@@ -1046,6 +1050,54 @@ class TSR(KernelEngine):
         keep = ("vertex_normals", "vertex_occlusion", "occlusion_map") + (() if texture else ("vertex_colors", "texture")) \
             + (() if normal_map is not None else ("normal_map", "corner_normals", "corner_tangents"))
         return mesh._derive(mesh.vertices, mesh.faces, keep, uvs=mesh.uvs if mesh.uvs is not None else uv, **new)
+
+    def bake_displacement_map(self, mesh: Mesh, scene_code, threshold: float = 25.0, displacement=True, resolution=None,
+                              atlas_resolution=None, island_padding: float = 0.02, unwrapper=None):
+        """The map a Multires / displacement workflow needs: per texel of `mesh`'s atlas the signed height along the LOW-poly
+        normal at which the field of `scene_code` reaches its iso-surface density_act = threshold.  Subdividing the low mesh
+        and displacing by it gives back the detail that simplify removed; a normal map only shades that detail.
+        displacement: True = (8 steps, 2 cells), an int n, or (n, cells) of a `resolution`^3 lattice (ops.displacement_rule;
+        resolution: default the marching-cubes resolution set last): the search stays within max_dist = cells x the lattice
+        spacing on either side of the face.  The direction is the per-vertex normal ops.vertex_normals * WINDING_OUTWARD -- the
+        one bake_normal_map builds its frame from -- interpolated at the texel; the search is the safeguarded Newton rule of
+        DESIGN.md 3.1h (ops.bake_displacement_route: ops.bake_displacement, which lists the covered texels on the device and
+        never waits for it, by default; the composed route with SCULPT_DISTANCE_FORM=composeddisplacement; the same bits).
+        Atlas: as bake_normal_map -- a mesh that has uvs keeps them, one without is unwrapped and comes back with them.
+        -> (mesh, DisplacementMap): the mesh as it came, with uvs; the map (tsr/displacement.py) holds the rule's height where
+        the texel converged and +0 elsewhere, padded by res // 150 rounds of ops.dilate_fill like the other maps, with mask,
+        status, max_dist, midlevel = 0.5 and scale = 2 max_dist.  It is no Mesh field: hand it to Mesh.export(path,
+        displacement=map)."""
+        from .displacement import DisplacementMap
+
+        steps, cells = ops.displacement_rule(displacement)   # a ValueError before anything is launched
+        if not threshold > 0:
+            raise ValueError("TSR.bake_displacement_map: threshold must be positive, got %r" % (threshold,))
+        self._need_weights("bake_displacement_map")
+        if resolution is None:
+            if self.isosurface_helper is None:
+                raise ValueError("TSR.bake_displacement_map: no resolution given and no marching-cubes resolution set yet")
+            resolution = self.isosurface_helper.resolution
+        if int(resolution) < 2:
+            raise ValueError("TSR.bake_displacement_map: resolution must be at least 2, got %r" % (resolution,))
+        res = _atlas_resolution(atlas_resolution, mesh, "bake_displacement_map", ("texture", "normal_map", "occlusion_map"))
+        cfg = self.renderer.cfg
+        target = float(np.float32(math.log(float(threshold)) - float(cfg.density_bias)))   # as _projected
+        max_dist = cells * 2.0 * float(cfg.radius) / (int(resolution) - 1)
+        with torch.no_grad():
+            v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper, keep_uvs=True)
+            planes = self._field(scene_code)
+            normals = (self.WINDING_OUTWARD * ops.vertex_normals(v, f)).contiguous()
+            route = ops.bake_displacement_route()
+            height, mask, ex = route(planes, self.decoder, v, f, normals, rast, target, max_dist, steps=steps, radius=cfg.radius,
+                                     want=("residual", "status", "evals"))
+            before = route(planes, self.decoder, v, f, normals, rast, target, max_dist, steps=0, radius=cfg.radius,
+                           want=("residual",))[2]["residual"]   # one evaluation at h = 0: what info() compares with
+            kept = torch.where(ex["status"] == 0, height, torch.zeros_like(height))
+            padded = self._padded(kept[..., None].expand(res, res, 3), mask, res)[..., 0].contiguous()
+        out = mesh if mesh.uvs is not None else mesh._derive(mesh.vertices, mesh.faces,
+                                                             ("vertex_colors", "vertex_normals", "vertex_occlusion", "quads"), uvs=uv)
+        return out, DisplacementMap(padded, mask, ex["status"], max_dist, evals=ex["evals"], residual0=before, residual=ex["residual"],
+                                    rule=(steps, cells))
 
     def _coded_normals(self, n, mask, res, space):
         """A normal image as a map: encoded 0.5 + 0.5 n, padded, the flat value where the padding does not reach."""
@@ -1202,6 +1254,10 @@ class TSR(KernelEngine):
             ops.occlusion_rule(occlusion)   # a ValueError before anything is launched
         if self.occlusion_map is not None:
             ops.occlusion_rule(self.occlusion_map)
+        if self.displacement_map is not None:
+            ops.displacement_rule(self.displacement_map)
+            if not threshold > 0:
+                raise ValueError("displacement_map needs a positive threshold (the surface is ln(threshold) in the raw density), got %r" % (threshold,))
         if self.bake_project is not None:
             ops.project_rule(self.bake_project)
             if not threshold > 0:
@@ -1320,6 +1376,9 @@ class TSR(KernelEngine):
             if enable_texture:
                 color = self.renderer.query_triplane(self.decoder, v_pos, planes)["color"]
             mesh = Mesh(v_pos, t_pos_idx, color)
+        if enable_texture and bake > 0 and self.displacement_map is not None:   # the texture's atlas and resolution
+            mesh, mesh.displacement = self.bake_displacement_map(mesh, planes, threshold=threshold, displacement=self.displacement_map,
+                                                                 resolution=R)
         if normals == "field":
             mesh.vertex_normals = self.field_normals(v_pos, planes)
         elif normals == "faces":
