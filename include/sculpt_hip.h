@@ -1426,6 +1426,69 @@ int sculpt_triplane_project_along(const float *planes_cl /* [3][H][W][C] */, int
                                   float *out_height, float *out_residual /* or null */, int *out_status /* or null */,
                                   int *out_evals /* or null */, sculpt_stream_t stream);
 
+/* UV CHART ATLAS ON THE DEVICE (csrc/uv_charts.hip; sf3d/unwrap.py ChartUnwrapper; restated in tests/_chartref.py): charts that
+ * are connected pieces of surface, shelf-packed.  DEVICE pointers, asynchronous on `stream`.  Compiled without floating-point
+ * contraction; every fp64 operation below is one IEEE operation on the fp32 inputs widened exactly.  Integer atomics only: two
+ * calls give the same bits.  P f32 [nv][3] finite, F int32 [nf][3] in range (the caller validates: sculpt_rmd_validate).
+ * THE RULE, per round (the caller repeats 2 .. 6 until a round evicts nothing, at most 8 rounds; layer starts at 0):
+ * 1 DIRECTION  a, b, c = the face's corners.  n = cross(b - a, c - a) in fp64 (differences, then products, then one subtraction
+ *              per component: n_x = u_y v_z - u_z v_y, n_y = u_z v_x - u_x v_z, n_z = u_x v_y - u_y v_x).  k = the axis of the
+ *              largest |n_k|, ties to the lowest k; d = 2 k + (n_k < 0).  Per corner (p, q) = (v[(k + 1) % 3], v[(k + 2) % 3]),
+ *              swapped when n_k < 0: fp32 bits, unchanged.  n = 0 gives d = 0.  A non-degenerate face has positive area in (p, q).
+ * 2 CHARTS     The half-edges 3 f + j (F[f][j] -> F[f][(j + 1) % 3]) sorted by their undirected key (min << 32 | max), as the
+ *              remesh passes sort them (sculpt_rmd_halfedge_keys, a stable sort).  Two faces are joined when their key occurs
+ *              exactly twice, the two half-edges start at different vertices (opposite directions), the faces differ, have the
+ *              same d, the same layer, and that layer is < max_layers (a face at max_layers is a "single": never joined).
+ *              Lock-free union-find over the faces (the scheme of csrc/mesh_components.hip): label[f] = the smallest face index
+ *              of f's chart, exact.  chart[f] = the rank of label[f] among the roots in ascending order; n_charts = the roots.
+ * 3 RECTANGLES per chart the fp32 minimum and maximum of p and of q over its corners (atomicMin / atomicMax on the ordered-float
+ *              key of csrc/block_scan.h: -0 orders below +0) -> rect = (pmin, pmax, qmin, qmax).  w = (double)pmax - (double)pmin,
+ *              h likewise.  h > w: the chart is TURNED, (p', q') = (q - qmin, pmax - p) and (w, h) swap; else (p - pmin, q - qmin).
+ *              extent = (w, h) after the turn, w >= h.  sort_key = -(the int64 bits of h); slots >= n_charts get INT64_MAX, rect 0.
+ *              (caller: order = the stable ascending argsort of sort_key: h descending, chart ids ascending among equals.)
+ * 4 PACK       g = the gutter in UV units (the caller passes island_padding / 8).  Q(s, e) = (int64)ceil((s * e + g) * 2^20).
+ *              At scale s, in sorted order j: Wq = Q(s, w), Hq = Q(s, h); cum[j] = the sum of Wq before j.  A row that starts at
+ *              `start` holds the charts j >= start with cum[j + 1] - cum[start] <= 2^20; its height is Hq[start]; rows stack from
+ *              y = 0.  s is FEASIBLE when every Wq <= 2^20 and the row heights sum to <= 2^20.  Search: w_max = m 2^e (0.5 <= m
+ *              < 1, frexp) gives s0 = 2^(1 - e) (so 1 <= s0 w_max < 2); w_max = 0 gives s0 = 1.  s = s0, halved while infeasible
+ *              (more than 80 halvings: error, the atlas cannot hold that many gutters).  If s0 itself was feasible it is taken.
+ *              Otherwise t = 2 s, then up to 11 times t = t * 0.9375, taking the first feasible t; if none, s.  cell[c] = (x, y)
+ *              of chart c's cell in units of 2^-20: x = cum[j] - cum[start of its row], y = the row's y.  One workgroup: the
+ *              scans run over its 1024 threads, the row walk is one thread with a binary search in cum per row.
+ * 5 PLACE      per corner u = fp32((x 2^-20 + 0.5 g) + s p'), v = fp32((y 2^-20 + 0.5 g) + s q'), p' and q' the fp64 differences
+ *              of 3.  Corners of one chart that share a vertex get the same bits.
+ * 6 CONFLICTS  rast_low = sculpt_bake_rasterize of uv with the faces in order, rast_high = with the face list reversed (triangle
+ *              t' there is face nf - 1 - t').  At every texel both cover with different faces lo < hi, the sample point is the
+ *              rasteriser's: px = fp32(x) / fp32(res), py = 1 - fp32(y) / fp32(res) in fp32.  In fp64, for a face with UV corners
+ *              A, B, C: e0 = (Bx - Ax)(py - Ay) - (By - Ay)(px - Ax), e1 and e2 likewise from (B, C) and (C, A); the sample is
+ *              STRICTLY inside when all three are > 0 or all three < 0.  Strictly inside both: evicted[hi] = 1,
+ *              chart_conflict[chart[lo]] = chart_conflict[chart[hi]] = 1.  sculpt_uv_chart_evict then, mode 0: layer[f] += 1
+ *              where evicted[f]; mode 1 (the caller's 8th round): layer[f] = max_layers for every face of a chart with
+ *              chart_conflict set, and nothing else; mode 2: layers untouched.  All modes count the evicted faces.
+ * The workspace (sculpt_uv_chart_workspace_bytes, 0 for nf out of [0, 2^24): the rasteriser carries face ids in fp32) starts
+ * with eight int64 words the caller may copy to the host after any call: n_charts, evicted faces, error bits (1: a union-find
+ * walk left its step budget, 2: no feasible scale), rows, scale evaluations, the scale (fp64 bits), conflicting texels, 0.
+ * sculpt_uv_chart_label starts a round: it clears those words.  Arrays: direction, layer, label, chart, evicted,
+ * chart_conflict int32 [nf]; pq f32 [nf][3][2]; rect f32 [nf][4]; extent f64 [nf][2]; sort_key, order int64 [nf];
+ * cell int64 [nf][2]; uv f32 [3 nf][2].  nf == 0 launches nothing.  Null arguments are refused with an error code. */
+size_t sculpt_uv_chart_workspace_bytes(int64_t n_faces);
+int sculpt_uv_chart_directions(const float *P, int64_t nv, const int32_t *F, int64_t nf, int32_t *direction, float *pq,
+                               sculpt_stream_t stream);
+int sculpt_uv_chart_label(const int64_t *skeys /* [3 nf] sorted */, const int64_t *sperm /* [3 nf] half-edge ids in that order */,
+                          const int32_t *F, int64_t nf, const int32_t *direction, const int32_t *layer, int max_layers, int32_t *label,
+                          void *workspace, sculpt_stream_t stream);
+int sculpt_uv_chart_rects(const float *pq, const int32_t *label, int64_t nf, int32_t *chart, float *rect, double *extent,
+                          int64_t *sort_key, void *workspace, sculpt_stream_t stream);
+int sculpt_uv_chart_pack(const int64_t *order, const double *extent, int64_t nf, double gutter, int64_t *cell, void *workspace,
+                         sculpt_stream_t stream);
+int sculpt_uv_chart_place(const float *pq, const int32_t *chart, const float *rect, const int64_t *cell, int64_t nf, double gutter,
+                          const void *workspace, float *uv, sculpt_stream_t stream);
+int sculpt_uv_chart_conflicts(const float *rast_low /* [res][res][4] */, const float *rast_high, int res, const float *uv,
+                              const int32_t *chart, int64_t nf, int32_t *evicted, int32_t *chart_conflict, void *workspace,
+                              sculpt_stream_t stream);
+int sculpt_uv_chart_evict(const int32_t *evicted, const int32_t *chart_conflict, const int32_t *chart, int64_t nf, int max_layers,
+                          int mode, int32_t *layer, void *workspace, sculpt_stream_t stream);
+
 /* Mesh hand-off, HOST side (no GPU work): the face block of a binary little-endian PLY file -- per face `uchar 3` followed by
  * three int32 -- from the int64 faces TSR.run returns (the reference's `t_pos_idx.cpu().numpy()`, TripoSR/tsr/system.py:200).
  * faces_host int64 [n][3] -> records_host uint8 [n][13].  Thread-safe; callers split n over threads (sculptmate_amd/meshio.py). */

@@ -111,6 +111,14 @@ SIGNATURES = {
     "sculpt_mesh_components_compact": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "sculpt_mesh_components_report": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_mesh_component_labels": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp]),
+    "sculpt_uv_chart_workspace_bytes": (_sz, [_i64]),
+    "sculpt_uv_chart_directions": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "sculpt_uv_chart_label": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp]),
+    "sculpt_uv_chart_rects": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_uv_chart_pack": (_i, [_vp, _vp, _i64, _d, _vp, _vp, _vp]),
+    "sculpt_uv_chart_place": (_i, [_vp, _vp, _vp, _vp, _i64, _d, _vp, _vp, _vp]),
+    "sculpt_uv_chart_conflicts": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "sculpt_uv_chart_evict": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     "sculpt_gemm_bf16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "sculpt_gemm_bf16_ex": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "sculpt_gemm_bf16_ln": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -67,7 +67,9 @@ class TripoGenerator(GeneratorFacade):
     `displacement_map` (default None): True, an int n or a tuple (n, cells) (ops.displacement_rule) bakes a displacement map --
     the height along the low-poly normal up to the field's iso-surface -- beside every baked texture, over its atlas
     (TSR.bake_displacement_map; copied to the model as TSR.displacement_map).  It comes back as the mesh's plain attribute
-    `displacement`; Mesh.export(path, displacement=mesh.displacement) writes it."""
+    `displacement`; Mesh.export(path, displacement=mesh.displacement) writes it.
+    `atlas` (default "box"): "charts" unwraps every mesh a map is baked for with sf3d.unwrap.ChartUnwrapper -- charts that are
+    connected pieces of surface -- instead of the box projection (copied to the model as TSR.atlas)."""
 
     def __init__(self, device):
         super().__init__(device, checkpoint_dir=ROOT_DIR + "/checkpoints/", chunk_size=8192, mc_resolution=256,
@@ -86,6 +88,7 @@ class TripoGenerator(GeneratorFacade):
         self.occlusion_map = None
         self.bake_project = None
         self.displacement_map = None
+        self.atlas = "box"
 
     def _construct_model(self):
         model = TSR.from_pretrained(self.checkpoint_dir, config_name="config.yaml", weight_name="model.ckpt",
@@ -103,6 +106,7 @@ class TripoGenerator(GeneratorFacade):
             self.model.occlusion_map = self.occlusion_map
             self.model.bake_project = self.bake_project
             self.model.displacement_map = self.displacement_map
+            self.model.atlas = self.atlas
             self.last_meshes = self.model.extract_mesh(codes, enable_texture=enable_texture, mesh_name=input_name,
                                                        resolution=self.mc_resolution,
                                                        bake_texture=int(self.bake_texture_resolution or 0),

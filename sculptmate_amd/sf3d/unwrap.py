@@ -169,3 +169,125 @@ class BoxProjectionUnwrapper:
         self.last = dict(rot=rot, angles=angles, chart=chart, assigned=assigned, face_uv=uv, rot_pos=rp, rot_nrm=rn)
         indices = torch.arange(3 * f.shape[0], device=v.device, dtype=f.dtype).reshape(-1, 3)
         return placed, indices
+
+
+class ChartUnwrapper:
+    """Callable UV unwrapper whose charts are CONNECTED pieces of surface, however many layers the object has (csrc/uv_charts.hip;
+    the rule is stated in include/sculpt_hip.h under "UV CHART ATLAS" and restated in tests/_chartref.py).  The hook signature of
+    BoxProjectionUnwrapper: unwrapper(v_pos, v_nrm, faces, island_padding) -> (uv f32 [3*Nf, 2], indices [Nf, 3] = arange); the
+    normals are not used.  Per round: faces of one axis direction and one layer that share a manifold, consistently wound edge
+    form a chart (union-find) -> per-chart rectangles -> shelf pack, gutter island_padding / GUTTER_DIVISOR -> place -> the
+    placed UVs rasterised twice at `raster_resolution` (lowest / highest face wins); a face strictly overlapping a lower one
+    moves up a layer, from `max_layers` on it is a chart of its own.  At most MAX_ROUNDS rounds.  The host reads eight integers
+    per round; no rectangle or UV crosses to it.  Two calls give the same bits.
+    `last` (tests, tools): direction, layer, chart int32 [Nf]; rect f32 [n_charts, 4] (pmin, pmax, qmin, qmax); extent f64
+    [n_charts, 2]; cell int64 [n_charts, 2]; scale (float); n_charts, rows, rounds (int); evicted (list, per round); conflicts."""
+
+    GUTTER_DIVISOR = 8.0   # gutter = island_padding / 8 in UV units: 5 texels at 2048^2 for the default 0.02
+    MAX_ROUNDS = 8
+
+    def __init__(self, raster_resolution: int = 1024, max_layers: int = 4):
+        self.raster_resolution = int(raster_resolution)
+        self.max_layers = int(max_layers)
+        if self.raster_resolution < 1 or self.max_layers < 0:
+            raise ValueError("ChartUnwrapper: raster_resolution must be positive and max_layers >= 0")
+        self.last = {}
+        self.stage_ms = None   # tools set a dict: every stage then ends with a synchronise and adds its wall time (ms) here
+
+    def _mark(self, name):
+        if self.stage_ms is not None:
+            import time
+
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            if name is not None:
+                self.stage_ms[name] = self.stage_ms.get(name, 0.0) + (now - self._t0) * 1e3
+            self._t0 = now
+
+    def _round(self, a, mode):
+        """Steps 2 .. 6 once -> the header's eight words (one read-back)."""
+        from .. import ops
+
+        nf, s, dev = a["nf"], _stream(), a["F"].device
+        check(lib.sculpt_uv_chart_label(_ptr(a["skeys"]), _ptr(a["sperm"]), _ptr(a["F"]), nf, _ptr(a["direction"]), _ptr(a["layer"]),
+                                        self.max_layers, _ptr(a["label"]), _ptr(a["ws"]), s))
+        check(lib.sculpt_uv_chart_rects(_ptr(a["pq"]), _ptr(a["label"]), nf, _ptr(a["chart"]), _ptr(a["rect"]), _ptr(a["extent"]),
+                                        _ptr(a["sort_key"]), _ptr(a["ws"]), s))
+        self._mark("charts_and_rectangles")
+        order = torch.sort(a["sort_key"], stable=True).indices
+        self._mark("sort")
+        check(lib.sculpt_uv_chart_pack(_ptr(order), _ptr(a["extent"]), nf, a["gutter"], _ptr(a["cell"]), _ptr(a["ws"]), s))
+        self._mark("pack")
+        check(lib.sculpt_uv_chart_place(_ptr(a["pq"]), _ptr(a["chart"]), _ptr(a["rect"]), _ptr(a["cell"]), nf, a["gutter"], _ptr(a["ws"]),
+                                        _ptr(a["uv"]), s))
+        self._mark("place")
+        low = ops.bake_rasterize(a["uv"], a["corners"], self.raster_resolution)
+        high = ops.bake_rasterize(a["uv"], a["corners_reversed"], self.raster_resolution)
+        self._mark("rasterise_twice")
+        check(lib.sculpt_uv_chart_conflicts(_ptr(low), _ptr(high), self.raster_resolution, _ptr(a["uv"]), _ptr(a["chart"]), nf,
+                                            _ptr(a["evicted"]), _ptr(a["chart_conflict"]), _ptr(a["ws"]), s))
+        check(lib.sculpt_uv_chart_evict(_ptr(a["evicted"]), _ptr(a["chart_conflict"]), _ptr(a["chart"]), nf, self.max_layers, mode,
+                                        _ptr(a["layer"]), _ptr(a["ws"]), s))
+        words = a["ws"][:64].view(torch.int64).cpu()
+        self._mark("conflicts_and_read_back")
+        hdr = dict(n_charts=int(words[0]), evicted=int(words[1]), error=int(words[2]), rows=int(words[3]), evaluations=int(words[4]),
+                   scale=float(words[5:6].view(torch.float64)[0]), conflict_texels=int(words[6]))
+        if hdr["error"] & 1:
+            raise _lib.SculptError("ChartUnwrapper: a union-find walk ran out of its step budget: a defect, the result is not valid")
+        if hdr["error"] & 2:
+            raise _lib.SculptError("ChartUnwrapper: no scale packs %d charts with a gutter of %g: lower island_padding"
+                                   % (hdr["n_charts"], a["gutter"]))
+        return hdr
+
+    def __call__(self, vertex_positions, vertex_normals, triangle_idxs, island_padding):
+        from .. import ops
+
+        v, f = vertex_positions, triangle_idxs
+        if not (isinstance(v, torch.Tensor) and v.is_cuda):
+            raise _lib.SculptError("ChartUnwrapper runs on an MI355X only (device %s; there is no CPU fallback)"
+                                   % (v.device if isinstance(v, torch.Tensor) else type(v).__name__))
+        if not isinstance(f, torch.Tensor) or f.dtype not in (torch.int32, torch.int64):
+            raise _lib.SculptError("ChartUnwrapper: faces must be int32 or int64")
+        gutter = float(island_padding) / self.GUTTER_DIVISOR
+        if not (0.0 <= gutter < 0.5):
+            raise ValueError("ChartUnwrapper: island_padding %r (0 <= island_padding < %g)" % (island_padding, 0.5 * self.GUTTER_DIVISOR))
+        dev = v.device
+        if f.shape[0] == 0:
+            self.last = {}
+            return torch.zeros((0, 2), dtype=torch.float32, device=dev), f.reshape(0, 3)
+        self._mark(None)
+        P, F = ops._surface(v, f, "ChartUnwrapper")   # index out of range, non-finite position: SculptError
+        self._mark("input_check")
+        nv, nf = P.shape[0], F.shape[0]
+        size = int(lib.sculpt_uv_chart_workspace_bytes(nf))
+        if size == 0:
+            raise _lib.SculptError("ChartUnwrapper: %d faces (fewer than 2^24: the rasteriser carries face ids in fp32)" % nf)
+        s = _stream()
+        i32 = dict(dtype=torch.int32, device=dev)
+        a = dict(nf=nf, F=F, gutter=gutter, ws=torch.empty(size, dtype=torch.uint8, device=dev),
+                 direction=torch.empty(nf, **i32), layer=torch.zeros(nf, **i32), label=torch.empty(nf, **i32),
+                 chart=torch.empty(nf, **i32), evicted=torch.empty(nf, **i32), chart_conflict=torch.empty(nf, **i32),
+                 pq=torch.empty((nf, 3, 2), dtype=torch.float32, device=dev), rect=torch.empty((nf, 4), dtype=torch.float32, device=dev),
+                 extent=torch.empty((nf, 2), dtype=torch.float64, device=dev), sort_key=torch.empty(nf, dtype=torch.int64, device=dev),
+                 cell=torch.zeros((nf, 2), dtype=torch.int64, device=dev), uv=torch.empty((3 * nf, 2), dtype=torch.float32, device=dev))
+        a["corners"] = torch.arange(3 * nf, **i32).view(-1, 3)
+        a["corners_reversed"] = a["corners"].flip(0).contiguous()
+        check(lib.sculpt_uv_chart_directions(_ptr(P), nv, _ptr(F), nf, _ptr(a["direction"]), _ptr(a["pq"]), s))
+        keys = torch.empty(3 * nf, dtype=torch.int64, device=dev)   # the half-edge table of the remesh passes
+        check(lib.sculpt_rmd_halfedge_keys(_ptr(F), nf, _ptr(keys), s))
+        a["skeys"], a["sperm"] = torch.sort(keys, stable=True)
+        self._mark("directions_and_half_edges")
+        evicted, conflicts = [], 0
+        for r in range(self.MAX_ROUNDS):
+            hdr = self._round(a, 1 if r == self.MAX_ROUNDS - 1 else 0)
+            evicted.append(hdr["evicted"])
+            if hdr["evicted"] == 0:
+                break
+        else:   # the cap: the conflicting charts went to pieces; one last pack and test
+            hdr = self._round(a, 2)
+            conflicts = hdr["evicted"]
+        n = hdr["n_charts"]
+        self.last = dict(direction=a["direction"], layer=a["layer"], chart=a["chart"], rect=a["rect"][:n], extent=a["extent"][:n],
+                         cell=a["cell"][:n], scale=hdr["scale"], n_charts=n, rows=hdr["rows"], rounds=len(evicted), evicted=evicted,
+                         conflicts=conflicts, evaluations=hdr["evaluations"])
+        return a["uv"], torch.arange(3 * nf, device=dev, dtype=f.dtype).reshape(-1, 3)

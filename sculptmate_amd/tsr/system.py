@@ -210,6 +210,7 @@ class TSR(KernelEngine):
         self.mesh_sink = None  # callable(verts, faces, colors, name); default: bpy if importable
         self.textured_mesh_sink = None  # callable(verts, faces, uvs, image, name) for baked meshes; default: bpy if importable
         self._unwrapper = None  # the cached BoxProjectionUnwrapper of bake_texture
+        self.atlas = "box"  # "box" | "charts": which unwrapper _atlas makes when none is passed (see the class-level default)
         # None | "tangent" | "object": when set, extract_meshes adds a normal map (bake_normal_map) to every mesh it bakes a
         # texture for, at the texture's resolution, and extract_mesh hands it to the textured sink
         self.normal_map = None
@@ -911,7 +912,8 @@ class TSR(KernelEngine):
         sf3d.unwrap.BoxProjectionUnwrapper; sf3d.bake.cell_atlas_unwrapper, the hook form of ops.uv_cell_atlas, is the
         deterministic stand-in) -> ops.bake_rasterize on the per-corner UVs -> ops.bake_scene_color (one fused launch) ->
         ops.dilate_fill with res // 150 iterations, the padding rule of the SF3D bake.  Nothing here waits for the device (the
-        box-projection unwrapper itself reads two small sums back)."""
+        box-projection unwrapper itself reads two small sums back).  With self.atlas = "charts" (an instance setting, default
+        "box") the default unwrapper is one cached sf3d.unwrap.ChartUnwrapper: connected charts, eight integers read per round."""
         self._need_weights("bake_texture")
         res = int(texture_resolution)
         if res < 1:
@@ -925,11 +927,19 @@ class TSR(KernelEngine):
     def _atlas(self, mesh, res, island_padding, unwrapper, keep_uvs=False):
         """What the two bakes share: the mesh on the device, its per-corner UVs (the mesh's own with keep_uvs, when it has
         some; else the unwrapper's) and the atlas rasterised at `res` -> (v f32 [Nv,3], f [Nf,3], uv f32 [3Nf,2], rast)."""
+        if self.atlas not in self.ATLASES:   # before anything is launched
+            raise ValueError("TSR.atlas must be one of %s, got %r" % (", ".join(repr(a) for a in self.ATLASES), self.atlas))
         v = _f32(mesh.vertices, self.device)
         f = torch.as_tensor(mesh.faces).to(self.device).contiguous()
         if keep_uvs and mesh.uvs is not None:
             uv = _f32(mesh.uvs, self.device)
         else:
+            if unwrapper is None and self.atlas == "charts":
+                if self._chart_unwrapper is None:
+                    from ..sf3d.unwrap import ChartUnwrapper
+
+                    self._chart_unwrapper = ChartUnwrapper()
+                unwrapper = self._chart_unwrapper
             if unwrapper is None:
                 if self._unwrapper is None:
                     from ..sf3d.unwrap import BoxProjectionUnwrapper
@@ -962,6 +972,12 @@ class TSR(KernelEngine):
     # texture bake (bake_displacement_map on the baked mesh's atlas) and leaves it on the mesh as the plain attribute
     # `displacement` (a tsr.displacement.DisplacementMap, no Mesh field).  None: nothing new is launched
     displacement_map = None
+    # "box" | "charts": the unwrapper _atlas makes when no unwrapper= is passed.  "box": sf3d.unwrap.BoxProjectionUnwrapper, as
+    # before.  "charts": sf3d.unwrap.ChartUnwrapper -- charts that are connected pieces of surface, however many layers the
+    # object has, shelf-packed.  Anything else is a ValueError before a launch.
+    ATLASES = ("box", "charts")
+    atlas = "box"
+    _chart_unwrapper = None   # the cached ChartUnwrapper
     _quads = None   # extract_meshes -> _reshaped: the extractor's quads as a Catmull-Clark cage; and back: the refined quads
 
     def bake_normal_map(self, mesh: Mesh, scene_code, resolution=None, space="tangent", island_padding: float = 0.02,
