@@ -18,7 +18,8 @@ ARCH = "gfx950"
 # v_pk_mul_f32, which cost ~10 issue cycles each and break the overlap with the bf16 MFMAs they are interleaved with
 # (tools/micro/mfma_fill.hip); the kernels that want packed operations ask for them with vector types.  render.hip shares
 # triplane.hip's per-sample code (triplane_mlp.h) and is compiled like it; so do bake_scene.hip and field_normal.hip;
-# mesh_project.hip, bake_normal.hip and bake_surface.hip run field_normal.hip's evaluator (field_fwd.h) and must give its bits.
+# field_normal.hip, mesh_project.hip, bake_normal.hip, bake_surface.hip and render.hip all call the one forward-mode evaluation
+# (field_eval_fwd, field_fwd.h) and must give each other's bits, so they share the flag.
 PER_FILE_FLAGS = {"bake_normal.hip": ["-fno-slp-vectorize"], "bake_surface.hip": ["-fno-slp-vectorize"], "triplane.hip": ["-fno-slp-vectorize"], "render.hip": ["-fno-slp-vectorize"], "bake_scene.hip": ["-fno-slp-vectorize"], "field_normal.hip": ["-fno-slp-vectorize"], "mesh_project.hip": ["-fno-slp-vectorize"], "density_filter.hip": ["-fno-slp-vectorize"], "attention_pipe.hip": ["-fno-slp-vectorize"],
                   "gemm_l3.hip": ["-fno-slp-vectorize"], "attention_l3.hip": ["-fno-slp-vectorize"], "attention_l2.hip": ["-fno-slp-vectorize"]}
 

@@ -4,18 +4,16 @@
 // Shape:
 //   * bake_scene_normal_kernel.  A wave owns a SPAN of 64 consecutive texels, one per lane.  It computes the texel's position
 //     with texel_position (bake_texel.h: the bits of bake_scene_color_kernel and bake_interpolate_kernel), ballots the coverage
-//     and compacts the covered positions to the low lanes in rank order (mbcnt rank, one ds_permute: covered lane -> lane `rank`,
-//     uncovered lane -> lane `count + its rank among the uncovered`, a permutation of the 64 lanes).  It then runs
-//     ceil(count / 8) forward-mode tiles of field_fwd.h -- 8 points x {value, d/dx, d/dy, d/dz} per 32-column MFMA tile, the
-//     operations of density_grad_kernel (csrc/field_normal.hip) -- over ranks 8k .. 8k + 7, gathers the eight unit normals of a
-//     tile into lanes 8k .. 8k + 7 and, after the last tile, sends every normal back to its texel's lane (ds_bpermute through
-//     the same permutation).  A span with no covered texel runs no tile and stores zeros.  Columns past `count` in the last
-//     tile evaluate an uncovered texel's position (the box centre); nothing of theirs is stored.
+//     and hands both to the span compaction of field_fwd.h (span_compact .. span_return: the covered positions to the low lanes
+//     in rank order, ceil(count / 8) tiles over ranks 8k .. 8k + 7, every result back to its texel's lane).  A tile is one
+//     field_eval_fwd -- 8 points x {value, d/dx, d/dy, d/dz}, the call density_grad_kernel (csrc/field_normal.hip) makes --
+//     and unit_normal_of.  A span with no covered texel runs no tile and stores zeros.  Columns past `count` in the last tile
+//     evaluate an uncovered texel's position (the box centre); nothing of theirs is stored.
 //   * a column's bits depend on that column alone (an MFMA column reads its own B column), so a covered texel's world normal is
 //     the `normal` of sculpt_triplane_density_grad at the position of sculpt_bake_interpolate, bit for bit, wherever in which
 //     span the texel sits.
-//   * 512 threads, hidden weights (and layer 0's, when they fit) in LDS exactly as in density_grad_kernel; the compaction uses
-//     lane permutes, no LDS of its own.
+//   * 512 threads, hidden weights (and layer 0's, when they fit) in LDS: field_prologue and the launch plan of field_kernel.h,
+//     as in density_grad_kernel; the compaction uses lane permutes, no LDS of its own.
 //
 // The tangent-space transform (frame given), per covered texel with barycentrics (u, v, w), face t, corner rows 3t, 3t+1, 3t+2 and
 // world normal n; every operation rounded on its own (contraction off), in this order:
@@ -37,8 +35,6 @@
 //   Degenerate: when !(0 < |det| < inf), a vertex index is out of range (nothing is read through it) or !(0 < l < inf), the corner
 //   gets T = normalize(cross(N, e_a)), a = the axis of N's smallest component in magnitude (the lowest axis on a tie), and w = +1;
 //   if that is no finite unit vector either (N is 0 or not finite) it gets (1, 0, 0, +1).
-#include <algorithm>
-
 #include "bake_texel.h"
 #include "common.h"
 #include "field_fwd.h"
@@ -54,23 +50,11 @@ __global__ __launch_bounds__(512) void bake_scene_normal_kernel(
     const float *__restrict__ corner_n, const float *__restrict__ corner_t, float *__restrict__ normal, uint8_t *__restrict__ mask,
     int a0_lds) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
-    const int NH = hd.NH;
-    float *a0s = smem + lds_floats_for(NH);
-    if (a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
-    load_weights_to_lds(smem, blob, hd);
-    const LdsView L = lds_view(smem, NH);
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const int p = lane & 31, h = lane >> 5;
-    const int kind = p & 3;
-    const bool is_value = kind == 0;
+    const FieldCtx c = field_prologue<C>(smem, blob, a0_lds);
+    const int lane = c.lane, p = c.p, kind = p & 3;
     const long nspans = (N + 63) / 64;
-    const float *A0g = blob + hd.off_a0;
-    const long HW = (long)H * W;
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-    for (long sp = (long)blockIdx.x * nwave + wave; sp < nspans; sp += (long)gridDim.x * nwave) {
+    for (long sp = (long)blockIdx.x * c.nwave + c.wave; sp < nspans; sp += (long)gridDim.x * c.nwave) {
         const long n = sp * 64 + lane;
         const bool live = n < N;
         const float4 r = rast[live ? n : N - 1];
@@ -79,39 +63,18 @@ __global__ __launch_bounds__(512) void bake_scene_normal_kernel(
         const unsigned long long m = __builtin_amdgcn_ballot_w64(covered);
         float wn[3] = {0.f, 0.f, 0.f};
         if (m != 0) {  // wave-uniform
-            const int count = __popcll(m);
-            const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            const int slot = covered ? below : count + (lane - below);  // a permutation of 0 .. 63
-            // lane `rank` <- the position of the covered texel of that rank
-            const float cx = __int_as_float(__builtin_amdgcn_ds_permute(slot * 4, __float_as_int(tx.x[0])));
-            const float cy = __int_as_float(__builtin_amdgcn_ds_permute(slot * 4, __float_as_int(tx.x[1])));
-            const float cz = __int_as_float(__builtin_amdgcn_ds_permute(slot * 4, __float_as_int(tx.x[2])));
+            const SpanRanks sr = span_compact(m, covered, lane, tx.x);
             float rx = 0.f, ry = 0.f, rz = 0.f;  // the normal of rank `lane`
-            const int ntile = (count + 7) >> 3;  // <= 8
-            for (int k = 0; k < ntile; ++k) {
-                const int src = k * 8 + (p >> 2);  // < 64
-                const float px = __shfl(cx, src, 64), py = __shfl(cy, src, 64), pz = __shfl(cz, src, 64);
-                int off[3][4];
-                float wt[3][4];
-                point_taps<false>(px, py, pz, radius, span_w, H, W, off, wt);
-                tangent_weights<false>(kind, px, py, pz, radius, span_w, H, W, wt);
-                f32x16 x0 = is_value ? lds_bias16(L.bacc, 0, h, 0) : zero;
-                f32x16 x1 = is_value ? lds_bias16(L.bacc, 0, h, 1) : zero;
-                layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, x0, x1);
-                hidden_layers_fwd(L, NH, lane, h, is_value, x0, x1);
-                const float s = last_dot0_nobias(L, h, x0, x1);
-                const float gx = quad_bcast<1>(s), gy = quad_bcast<2>(s), gz = quad_bcast<3>(s);
+            for (int k = 0; k < span_tiles(sr); ++k) {
+                float px, py, pz;
+                span_tile_point(sr, k, p, px, py, pz);
+                const float s = field_eval_fwd<C, false>(c, planes, H, W, radius, span_w, a0_lds, kind, px, py, pz);
                 float nx, ny, nz;
-                unit_normal_of(gx, gy, gz, nx, ny, nz);
-                // point j of the tile sits in lane 4 j: into lane 8 k + j
-                const int from = 4 * (lane & 7);
-                const float qx = __shfl(nx, from, 64), qy = __shfl(ny, from, 64), qz = __shfl(nz, from, 64);
-                if ((lane >> 3) == k) { rx = qx; ry = qy; rz = qz; }
+                unit_normal_of(quad_bcast<1>(s), quad_bcast<2>(s), quad_bcast<3>(s), nx, ny, nz);
+                const float qx = span_gather(nx, lane), qy = span_gather(ny, lane), qz = span_gather(nz, lane);
+                if (span_keeps(k, lane)) { rx = qx; ry = qy; rz = qz; }
             }
-            // back to the texel's own lane
-            const float bx = __int_as_float(__builtin_amdgcn_ds_bpermute(slot * 4, __float_as_int(rx)));
-            const float by = __int_as_float(__builtin_amdgcn_ds_bpermute(slot * 4, __float_as_int(ry)));
-            const float bz = __int_as_float(__builtin_amdgcn_ds_bpermute(slot * 4, __float_as_int(rz)));
+            const float bx = span_return(sr, rx), by = span_return(sr, ry), bz = span_return(sr, rz);
             if (covered) { wn[0] = bx; wn[1] = by; wn[2] = bz; }
         }
         if (live) {
@@ -208,32 +171,26 @@ extern "C" int sculpt_bake_scene_normal(const float *planes_cl, int C, int H, in
                                         const float *v_pos, size_t nv, const void *faces, int faces_i64, size_t nf, const float *rast,
                                         int res, float radius, const float *corner_normals, const float *corner_tangents,
                                         float *normal, uint8_t *mask, sculpt_stream_t stream) {
-    SC_REQUIRE(C == 40, "bake_scene_normal: built for C=40 channels per plane (got %d)", C);
-    SC_REQUIRE(planes_cl && mlp_packed, "bake_scene_normal: null input");
-    SC_REQUIRE(H >= 1 && W >= 1, "bake_scene_normal: bad plane size %d x %d", H, W);
-    SC_REQUIRE(res >= 0, "bake_scene_normal: negative resolution");
-    SC_REQUIRE(n_hidden_64 >= 0, "bake_scene_normal: bad n_hidden_64");
-    SC_REQUIRE(radius > 0.f, "bake_scene_normal: radius must be positive");
+    FieldPlan plan;
+    if (const int e = field_plan("bake_scene_normal", C, planes_cl, mlp_packed, H, W, n_hidden_64, radius, plan, [&] {
+            SC_REQUIRE(res >= 0, "bake_scene_normal: negative resolution");
+            return 0;
+        }))
+        return e;
     SC_REQUIRE(nv <= (size_t)1 << 40 && nf <= (size_t)1 << 40, "bake_scene_normal: mesh too large");
     SC_REQUIRE((corner_normals == nullptr) == (corner_tangents == nullptr),
                "bake_scene_normal: corner_normals and corner_tangents come together (both or neither)");
     if (res == 0) return 0;
     SC_REQUIRE(rast && normal, "bake_scene_normal: null rast or normal");
     SC_REQUIRE(nf == 0 || (v_pos && faces && nv > 0), "bake_scene_normal: null mesh");
-    size_t lds = (size_t)lds_floats_for(n_hidden_64) * sizeof(float);
-    SC_REQUIRE(lds <= 160 * 1024, "bake_scene_normal: %d hidden layers do not fit LDS", n_hidden_64);
-    const size_t a0_bytes = (size_t)3 * C * 64 * sizeof(float);
-    const int a0_lds = lds + a0_bytes <= 160 * 1024 ? 1 : 0;
-    if (a0_lds) lds += a0_bytes;
     auto kern = corner_normals ? bake_scene_normal_kernel<40, true> : bake_scene_normal_kernel<40, false>;
-    SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const long N = (long)res * res;
-    const long nspans = (N + 63) / 64;
-    const int grid = (int)std::min<long>((nspans + 7) / 8, num_cus());
-    const float span = (float)((double)radius - (double)(-radius));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W,
+    int grid;
+    if (const int e = field_grid(plan, kern, (N + 63) / 64, grid)) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), plan.lds, as_stream(stream), planes_cl, H, W,
                        reinterpret_cast<const float *>(mlp_packed), v_pos, (long)nv, faces, faces_i64, (long)nf,
-                       reinterpret_cast<const float4 *>(rast), N, radius, span, corner_normals, corner_tangents, normal, mask, a0_lds);
+                       reinterpret_cast<const float4 *>(rast), N, radius, plan.span, corner_normals, corner_tangents, normal, mask,
+                       plan.a0_lds);
     SC_LAUNCH_CHECK();
     return 0;
 }

@@ -13,14 +13,14 @@
 //     channel-last planes.  The density row is not evaluated.
 //   * the position (texel_position, bake_texel.h) is (a*u + b*v) + c*w per component with contraction off: the bits of bake_interpolate_kernel (csrc/baker.hip),
 //     gathered through faces[t] from the indexed vertex array.
+//   * weights into LDS and the launch plan: field_prologue / field_plan / field_grid (field_kernel.h), as in render_rays_kernel.
 //   * a tile with no covered texel is skipped (wave-uniform ballot) and stores zeros; an uncovered texel in a mixed tile samples
 //     the box centre and stores 0, 0, 0 and mask 0.  A texel's result depends on that texel alone.
 //   * index guard: a texel whose triangle index is outside [0, nf) or whose vertex indices are outside [0, nv) is uncovered;
 //     nothing is read through such an index.
-#include <algorithm>
-
 #include "bake_texel.h"
 #include "common.h"
+#include "field_kernel.h"
 #include "triplane_mlp.h"
 
 namespace sculpt {
@@ -31,20 +31,13 @@ __global__ __launch_bounds__(512) void bake_scene_color_kernel(
     const void *__restrict__ faces, int faces_i64, long nf, const float4 *__restrict__ rast, long N, float radius, float span,
     float *__restrict__ color, uint8_t *__restrict__ mask, int a0_lds) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
-    const int NH = hd.NH;
-    float *a0s = smem + lds_floats_for(NH);
-    if (a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
-    load_weights_to_lds(smem, blob, hd);
-    const LdsView L = lds_view(smem, NH);
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const int p = lane & 31, h = lane >> 5;
+    const FieldCtx c = field_prologue<C>(smem, blob, a0_lds);
+    const LdsView &L = c.L;
+    const int lane = c.lane, p = c.p, h = c.h;
     const long ntiles = (N + 31) / 32;
-    const float *A0g = blob + hd.off_a0;
     const long HW = (long)H * W;
 
-    for (long tile = (long)blockIdx.x * nwave + wave; tile < ntiles; tile += (long)gridDim.x * nwave) {
+    for (long tile = (long)blockIdx.x * c.nwave + c.wave; tile < ntiles; tile += (long)gridDim.x * c.nwave) {
         const long n = tile * 32 + p;
         const bool live = n < N, writer = live && h == 0;
         const Texel tx = texel_position(rast[live ? n : N - 1], v_pos, nv, faces, faces_i64, nf);
@@ -56,9 +49,9 @@ __global__ __launch_bounds__(512) void bake_scene_color_kernel(
             point_taps<false>(tx.x[0], tx.x[1], tx.x[2], radius, span, H, W, off, wt);
             f32x16 acc0 = lds_bias16(L.bacc, 0, h, 0);
             f32x16 acc1 = lds_bias16(L.bacc, 0, h, 1);
-            layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, acc0, acc1);
+            layer0_channel_last<C>(planes, HW, off, wt, c.a0s, c.A0g, a0_lds, lane, h, acc0, acc1);
             f32x16 x0 = silu16(acc0), x1 = silu16(acc1);
-            hidden_layers(L, NH, lane, h, x0, x1);
+            hidden_layers(L, c.NH, lane, h, x0, x1);
             r = color_f(last_dot(L, 1, h, x0, x1));
             g = color_f(last_dot(L, 2, h, x0, x1));
             b = color_f(last_dot(L, 3, h, x0, x1));
@@ -79,30 +72,23 @@ using namespace sculpt;
 extern "C" int sculpt_bake_scene_color(const float *planes_cl, int C, int H, int W, const void *mlp_packed, int n_hidden_64,
                                        const float *v_pos, size_t nv, const void *faces, int faces_i64, size_t nf, const float *rast,
                                        int res, float radius, float *color, uint8_t *mask, sculpt_stream_t stream) {
-    SC_REQUIRE(C == 40, "bake_scene_color: built for C=40 channels per plane (got %d)", C);
-    SC_REQUIRE(planes_cl && mlp_packed, "bake_scene_color: null input");
-    SC_REQUIRE(H >= 1 && W >= 1, "bake_scene_color: bad plane size %d x %d", H, W);
-    SC_REQUIRE(res >= 0, "bake_scene_color: negative resolution");
-    SC_REQUIRE(n_hidden_64 >= 0, "bake_scene_color: bad n_hidden_64");
-    SC_REQUIRE(radius > 0.f, "bake_scene_color: radius must be positive");
+    FieldPlan plan;
+    if (const int e = field_plan("bake_scene_color", C, planes_cl, mlp_packed, H, W, n_hidden_64, radius, plan, [&] {
+            SC_REQUIRE(res >= 0, "bake_scene_color: negative resolution");
+            return 0;
+        }))
+        return e;
     SC_REQUIRE(nv <= (size_t)1 << 40 && nf <= (size_t)1 << 40, "bake_scene_color: mesh too large");
     if (res == 0) return 0;
     SC_REQUIRE(rast && color, "bake_scene_color: null rast or color");
     SC_REQUIRE(nf == 0 || (v_pos && faces && nv > 0), "bake_scene_color: null mesh");
-    size_t lds = (size_t)lds_floats_for(n_hidden_64) * sizeof(float);
-    SC_REQUIRE(lds <= 160 * 1024, "bake_scene_color: %d hidden layers do not fit LDS", n_hidden_64);
-    const size_t a0_bytes = (size_t)3 * C * 64 * sizeof(float);
-    const int a0_lds = lds + a0_bytes <= 160 * 1024 ? 1 : 0;
-    if (a0_lds) lds += a0_bytes;
     auto kern = bake_scene_color_kernel<40>;
-    SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const long N = (long)res * res;
-    const long ntiles = (N + 31) / 32;
-    const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
-    const float span = (float)((double)radius - (double)(-radius));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W,
+    int grid;
+    if (const int e = field_grid(plan, kern, (N + 31) / 32, grid)) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), plan.lds, as_stream(stream), planes_cl, H, W,
                        reinterpret_cast<const float *>(mlp_packed), v_pos, (long)nv, faces, faces_i64, (long)nf,
-                       reinterpret_cast<const float4 *>(rast), N, radius, span, color, mask, a0_lds);
+                       reinterpret_cast<const float4 *>(rast), N, radius, plan.span, color, mask, plan.a0_lds);
     SC_LAUNCH_CHECK();
     return 0;
 }

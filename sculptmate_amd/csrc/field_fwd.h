@@ -1,11 +1,14 @@
 // The forward-mode evaluator of the raw density: the pieces that turn the point query's MFMA tile (triplane_mlp.h) into
-// 8 points x 4 columns {value, d/dx, d/dy, d/dz}.  Shared by density_grad_kernel (csrc/field_normal.hip, where the shape is
-// described: DESIGN.md section 3.1d), project_kernel (csrc/mesh_project.hip) and render_passes_kernel (csrc/render.hip), so that
-// all three evaluate a point with the same operations and give the same bits.  Units that include this are compiled with
-// -fno-slp-vectorize (build.py).
+// 8 points x 4 columns {value, d/dx, d/dy, d/dz} (the shape is described in csrc/field_normal.hip and DESIGN.md section 3.1d),
+// and field_eval_fwd, the ONE evaluation of a point made of them.  Its callers evaluate a point with the same operations and
+// give the same bits: density_grad_kernel (csrc/field_normal.hip), project_kernel and project_along_kernel
+// (csrc/mesh_project.hip), bake_scene_normal_kernel (csrc/bake_normal.hip), bake_scene_surface_kernel (csrc/bake_surface.hip)
+// and render_passes_kernel (csrc/render.hip).  The two bakes also share the span compaction at the end of this file.  Units that
+// include this are compiled with -fno-slp-vectorize (build.py).
 #pragma once
 
 #include "common.h"
+#include "field_kernel.h"
 #include "triplane_mlp.h"
 
 namespace sculpt {
@@ -105,6 +108,33 @@ __device__ __forceinline__ float last_dot0_nobias(const LdsView &L, int h, const
     return s;
 }
 
+// One evaluation at (px, py, pz) of the column of kind `kind` (0 = value, 1 + axis = tangent; p & 3 in the tile): layer 0 with the
+// column's weights, its accumulators started at the bias for a value and at 0 for a tangent, the hidden layers, row 0 of the last
+// layer.  -> the raw density without the last bias (value) or its derivative along the axis (tangent); x0, x1 are left holding
+// what the last layer read, for a caller that wants its other rows.
+template <int C, bool AC>
+__device__ __forceinline__ float field_eval_fwd(const FieldCtx &c, const float *planes, int H, int W, float radius, float span,
+                                                int a0_lds, int kind, float px, float py, float pz, f32x16 &x0, f32x16 &x1) {
+    const bool is_value = kind == 0;
+    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int off[3][4];
+    float wt[3][4];
+    point_taps<AC>(px, py, pz, radius, span, H, W, off, wt);
+    tangent_weights<AC>(kind, px, py, pz, radius, span, H, W, wt);
+    x0 = is_value ? lds_bias16(c.L.bacc, 0, c.h, 0) : zero;
+    x1 = is_value ? lds_bias16(c.L.bacc, 0, c.h, 1) : zero;
+    layer0_channel_last<C>(planes, (long)H * W, off, wt, c.a0s, c.A0g, a0_lds, c.lane, c.h, x0, x1);
+    hidden_layers_fwd(c.L, c.NH, c.lane, c.h, is_value, x0, x1);
+    return last_dot0_nobias(c.L, c.h, x0, x1);
+}
+
+template <int C, bool AC>
+__device__ __forceinline__ float field_eval_fwd(const FieldCtx &c, const float *planes, int H, int W, float radius, float span,
+                                                int a0_lds, int kind, float px, float py, float pz) {
+    f32x16 x0, x1;
+    return field_eval_fwd<C, AC>(c, planes, H, W, radius, span, a0_lds, kind, px, py, pz, x0, x1);
+}
+
 // The unit normal of the iso-surface through a point with density gradient g: -g / |g|, with g scaled by a power of two first
 // so that no square overflows or vanishes; exactly 0 where g is 0 or not finite.  One copy, so that density_grad_kernel and the
 // renderer's render_passes_kernel (csrc/render.hip) give the same bits.
@@ -118,6 +148,54 @@ __device__ __forceinline__ void unit_normal_of(float gx, float gy, float gz, flo
         const float len = sqrtf(ux * ux + uy * uy + uz * uz);
         nx = -ux / len; ny = -uy / len; nz = -uz / len;
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The span compaction of the bakes.  A wave owns a span of 64 texels, one per lane, of which some are
+// covered.  span_compact brings the covered texels' positions to the low lanes in rank order; the wave then runs
+// ceil(count / 8) forward-mode tiles, tile k over ranks 8k .. 8k + 7 (span_tile_point); span_gather brings a tile's results to
+// lanes 8k .. 8k + 7, and after the last tile span_return sends what lane `rank` holds back to its texel's lane.  Lane
+// permutes only, no LDS.  Call with at least one lane covered (the ballot is wave-uniform: a span with none runs no tile).
+// ---------------------------------------------------------------------------------------------------------------------------
+struct SpanRanks {
+    int count;          // covered texels of the span
+    int slot;           // covered lane -> its rank; uncovered lane -> count + its rank among the uncovered: a permutation of 0 .. 63
+    float cx, cy, cz;   // lane `rank` holds the position of the covered texel of that rank
+};
+
+__device__ __forceinline__ SpanRanks span_compact(unsigned long long m, bool covered, int lane, const float (&x)[3]) {
+    SpanRanks s;
+    s.count = __popcll(m);
+    const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    s.slot = covered ? below : s.count + (lane - below);
+    s.cx = __int_as_float(__builtin_amdgcn_ds_permute(s.slot * 4, __float_as_int(x[0])));
+    s.cy = __int_as_float(__builtin_amdgcn_ds_permute(s.slot * 4, __float_as_int(x[1])));
+    s.cz = __int_as_float(__builtin_amdgcn_ds_permute(s.slot * 4, __float_as_int(x[2])));
+    return s;
+}
+
+__device__ __forceinline__ int span_tiles(const SpanRanks &s) { return (s.count + 7) >> 3; }  // <= 8
+
+// the point of column p in tile k -> its rank (< 64).  A rank >= count is an uncovered texel's position (the box centre): the
+// column evaluates with the wave and nothing of its result is kept.
+__device__ __forceinline__ int span_tile_point(const SpanRanks &s, int k, int p, float &px, float &py, float &pz) {
+    const int src = k * 8 + (p >> 2);
+    px = __shfl(s.cx, src, 64), py = __shfl(s.cy, src, 64), pz = __shfl(s.cz, src, 64);
+    return src;
+}
+
+// point j of a tile sits in lane 4 j: lane 8 k + j <- v of point j (float or int); the lanes 8k .. 8k + 7 keep it (span_keeps)
+template <class T>
+__device__ __forceinline__ T span_gather(T v, int lane) {
+    return __shfl(v, 4 * (lane & 7), 64);
+}
+
+__device__ __forceinline__ bool span_keeps(int k, int lane) { return (lane >> 3) == k; }
+
+// what lane `rank` holds, back in the texel's own lane (float or int)
+template <class T>
+__device__ __forceinline__ T span_return(const SpanRanks &s, T r) {
+    return __builtin_bit_cast(T, __builtin_amdgcn_ds_bpermute(s.slot * 4, __builtin_bit_cast(int, r)));
 }
 
 }  // namespace sculpt

@@ -19,8 +19,8 @@
 //   * a column's bits depend on that column alone (an MFMA column reads its own B column), and a value column runs the point
 //     query's own operations: `density` is ops.triplane_query's from channel-last planes bit for bit, and a point's result does
 //     not depend on N or on where in which tile the point sits.
-#include <algorithm>
-
+// The steps above are field_eval_fwd (csrc/field_fwd.h), the one copy every forward-mode kernel calls; the prologue and the launch
+// plan are csrc/field_kernel.h's.
 #include "common.h"
 #include "field_fwd.h"
 #include "triplane_mlp.h"
@@ -32,40 +32,21 @@ __global__ __launch_bounds__(512) void density_grad_kernel(
     const float *__restrict__ planes, int H, int W, const float *__restrict__ blob, const float *__restrict__ pts, long N,
     float radius, float span, float *__restrict__ grad, float *__restrict__ normal, float *__restrict__ density, int a0_lds) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
-    const int NH = hd.NH;
-    float *a0s = smem + lds_floats_for(NH);
-    if (a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
-    load_weights_to_lds(smem, blob, hd);
-    const LdsView L = lds_view(smem, NH);
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const int p = lane & 31, h = lane >> 5;
-    const int kind = p & 3;
+    const FieldCtx c = field_prologue<C>(smem, blob, a0_lds);
+    const int p = c.p, kind = p & 3;
     const bool is_value = kind == 0;
     const long ntiles = (N + 7) / 8;
-    const float *A0g = blob + hd.off_a0;
-    const long HW = (long)H * W;
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-    for (long tile = (long)blockIdx.x * nwave + wave; tile < ntiles; tile += (long)gridDim.x * nwave) {
+    for (long tile = (long)blockIdx.x * c.nwave + c.wave; tile < ntiles; tile += (long)gridDim.x * c.nwave) {
         long n = tile * 8 + (p >> 2);
         const bool valid = n < N;
         if (!valid) n = N - 1;
-        const float px = pts[3 * n], py = pts[3 * n + 1], pz = pts[3 * n + 2];
-        int off[3][4];
-        float wt[3][4];
-        point_taps<AC>(px, py, pz, radius, span, H, W, off, wt);
-        tangent_weights<AC>(kind, px, py, pz, radius, span, H, W, wt);
-        f32x16 x0 = is_value ? lds_bias16(L.bacc, 0, h, 0) : zero;
-        f32x16 x1 = is_value ? lds_bias16(L.bacc, 0, h, 1) : zero;
-        layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, x0, x1);
-        hidden_layers_fwd(L, NH, lane, h, is_value, x0, x1);
-        const float s = last_dot0_nobias(L, h, x0, x1);
-        const float d = s + L.blast[0];
+        const float s =
+            field_eval_fwd<C, AC>(c, planes, H, W, radius, span, a0_lds, kind, pts[3 * n], pts[3 * n + 1], pts[3 * n + 2]);
+        const float d = s + c.L.blast[0];
         // the quad's three tangents into the point's lane
         const float gx = quad_bcast<1>(s), gy = quad_bcast<2>(s), gz = quad_bcast<3>(s);
-        if (valid && is_value && h == 0) {
+        if (valid && is_value && c.h == 0) {
             if (density) density[n] = d;
             if (grad) { grad[3 * n] = gx; grad[3 * n + 1] = gy; grad[3 * n + 2] = gz; }
             if (normal) {
@@ -84,28 +65,22 @@ using namespace sculpt;
 extern "C" int sculpt_triplane_density_grad(const float *planes_cl, int C, int H, int W, const void *mlp_packed, int n_hidden_64,
                                             const float *points, long long N, float radius, int flags, float *grad,
                                             float *normal, float *density, sculpt_stream_t stream) {
-    SC_REQUIRE(C == 40, "triplane_density_grad: built for C=40 channels per plane (got %d)", C);
-    SC_REQUIRE(planes_cl && mlp_packed, "triplane_density_grad: null input");
-    SC_REQUIRE(H >= 1 && W >= 1, "triplane_density_grad: bad plane size %d x %d", H, W);
-    SC_REQUIRE(N >= 0, "triplane_density_grad: negative point count %lld", N);
-    SC_REQUIRE((flags & ~(int)SCULPT_QUERY_ALIGN_CORNERS) == 0, "triplane_density_grad: unknown flags %d", flags);
-    SC_REQUIRE(n_hidden_64 >= 0, "triplane_density_grad: bad n_hidden_64");
-    SC_REQUIRE(radius > 0.f, "triplane_density_grad: radius must be positive");
+    FieldPlan plan;
+    if (const int e = field_plan("triplane_density_grad", C, planes_cl, mlp_packed, H, W, n_hidden_64, radius, plan, [&] {
+            SC_REQUIRE(N >= 0, "triplane_density_grad: negative point count %lld", N);
+            SC_REQUIRE((flags & ~(int)SCULPT_QUERY_ALIGN_CORNERS) == 0, "triplane_density_grad: unknown flags %d", flags);
+            return 0;
+        }))
+        return e;
     if (N == 0) return 0;   // empty arrays have no address: nothing to refuse, nothing to launch
     SC_REQUIRE(grad || normal || density, "triplane_density_grad: no output asked for (grad, normal and density are all null)");
     SC_REQUIRE(points, "triplane_density_grad: null points");
-    size_t lds = (size_t)lds_floats_for(n_hidden_64) * sizeof(float);
-    SC_REQUIRE(lds <= 160 * 1024, "triplane_density_grad: %d hidden layers do not fit LDS", n_hidden_64);
-    const size_t a0_bytes = (size_t)3 * C * 64 * sizeof(float);
-    const int a0_lds = lds + a0_bytes <= 160 * 1024 ? 1 : 0;
-    if (a0_lds) lds += a0_bytes;
     auto kern = (flags & (int)SCULPT_QUERY_ALIGN_CORNERS) ? density_grad_kernel<40, true> : density_grad_kernel<40, false>;
-    SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long ntiles = ((long)N + 7) / 8;
-    const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
-    const float span = (float)((double)radius - (double)(-radius));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W,
-                       reinterpret_cast<const float *>(mlp_packed), points, (long)N, radius, span, grad, normal, density, a0_lds);
+    int grid;
+    if (const int e = field_grid(plan, kern, ((long)N + 7) / 8, grid)) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), plan.lds, as_stream(stream), planes_cl, H, W,
+                       reinterpret_cast<const float *>(mlp_packed), points, (long)N, radius, plan.span, grad, normal, density,
+                       plan.a0_lds);
     SC_LAUNCH_CHECK();
     return 0;
 }

@@ -4,9 +4,10 @@
 // (section 3.1h, tests/_dispref.py).
 //
 // project_kernel
-//   * density_grad_kernel's tile (csrc/field_normal.hip, csrc/field_fwd.h): a wave is 8 points x {value, d/dx, d/dy, d/dz}, the
-//     weights are staged in LDS once per workgroup, and one evaluation is that kernel's own sequence of operations, so the raw
-//     density d and the gradient g of an iterate are ops.field_normals' bits at that iterate.
+//   * density_grad_kernel's tile (csrc/field_normal.hip): a wave is 8 points x {value, d/dx, d/dy, d/dz}, the weights are staged
+//     in LDS once per workgroup (field_prologue, csrc/field_kernel.h), and one evaluation is field_eval_fwd (csrc/field_fwd.h),
+//     the call that kernel makes, so the raw density d and the gradient g of an iterate are ops.field_normals' bits at that
+//     iterate.
 //   * after an evaluation the eight lanes of a point all hold d and g (three quad broadcasts; the two halves agree after
 //     last_dot0_nobias's xor-shuffle) and run the rule redundantly in registers: current iterate, residual, masked gradient, best
 //     iterate, trust region, status, evaluation count.  No LDS, no memory traffic between two steps.
@@ -19,8 +20,6 @@
 //     kernel's.
 //
 // unfold kernels: fp32 without contraction (tests/_projref.py unfold restates them in NumPy bit for bit).
-#include <algorithm>
-
 #include "common.h"
 #include "field_fwd.h"
 #include "project_rule.h"
@@ -34,51 +33,27 @@ __global__ __launch_bounds__(512) void project_kernel(
     float radius, float span, float target, int K, float md2, float res_tol, float *__restrict__ out_pts,
     float *__restrict__ out_res, int *__restrict__ out_status, int *__restrict__ out_evals, int a0_lds) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
-    const int NH = hd.NH;
-    float *a0s = smem + lds_floats_for(NH);
-    if (a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
-    load_weights_to_lds(smem, blob, hd);
-    const LdsView L = lds_view(smem, NH);
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const int p = lane & 31, h = lane >> 5;
-    const int kind = p & 3;
+    const FieldCtx c = field_prologue<C>(smem, blob, a0_lds);
+    const int p = c.p, kind = p & 3;
     const bool is_value = kind == 0;
     const long ntiles = (N + 7) / 8;
-    const float *A0g = blob + hd.off_a0;
-    const long HW = (long)H * W;
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-    for (long tile = (long)blockIdx.x * nwave + wave; tile < ntiles; tile += (long)gridDim.x * nwave) {
+    for (long tile = (long)blockIdx.x * c.nwave + c.wave; tile < ntiles; tile += (long)gridDim.x * c.nwave) {
         long n = tile * 8 + (p >> 2);
         const bool valid = n < N;
         if (!valid) n = N - 1;   // a copy of the last point: it runs the same steps and stores nothing
         const float p0x = pts[3 * n], p0y = pts[3 * n + 1], p0z = pts[3 * n + 2];
         const bool fx = fabsf(p0x) >= radius, fy = fabsf(p0y) >= radius, fz = fabsf(p0z) >= radius;
-        ProjState s;
-        s.px = s.bx = p0x, s.py = s.by = p0y, s.pz = s.bz = p0z;
-        s.r = s.br = 0.f;
-        s.gx = s.gy = s.gz = 0.f;
-        s.status = 1, s.evals = 0, s.active = true;
+        ProjState s = proj_start(p0x, p0y, p0z, true);
         float qx = p0x, qy = p0y, qz = p0z;
         for (int k = 0; k <= K; ++k) {   // K <= 64 (checked at the entry): at most K + 1 evaluations
-            // one evaluation at (qx, qy, qz): density_grad_kernel's sequence
-            int off[3][4];
-            float wt[3][4];
-            point_taps<AC>(qx, qy, qz, radius, span, H, W, off, wt);
-            tangent_weights<AC>(kind, qx, qy, qz, radius, span, H, W, wt);
-            f32x16 x0 = is_value ? lds_bias16(L.bacc, 0, h, 0) : zero;
-            f32x16 x1 = is_value ? lds_bias16(L.bacc, 0, h, 1) : zero;
-            layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, x0, x1);
-            hidden_layers_fwd(L, NH, lane, h, is_value, x0, x1);
-            const float sv = last_dot0_nobias(L, h, x0, x1);
-            const float d = quad_bcast<0>(sv) + L.blast[0];
+            const float sv = field_eval_fwd<C, AC>(c, planes, H, W, radius, span, a0_lds, kind, qx, qy, qz);
+            const float d = quad_bcast<0>(sv) + c.L.blast[0];
             const float gx = quad_bcast<1>(sv), gy = quad_bcast<2>(sv), gz = quad_bcast<3>(sv);
             rule_update(s, k, K, d, gx, gy, gz, qx, qy, qz, p0x, p0y, p0z, fx, fy, fz, target, radius, md2, res_tol);
             if (__ballot(s.active) == 0ull) break;   // wave-uniform: all eight points have stopped
         }
-        if (valid && is_value && h == 0) {
+        if (valid && is_value && c.h == 0) {
             out_pts[3 * n] = s.bx, out_pts[3 * n + 1] = s.by, out_pts[3 * n + 2] = s.bz;
             if (out_res) out_res[n] = s.br;
             if (out_status) out_status[n] = s.status;
@@ -99,28 +74,18 @@ __global__ __launch_bounds__(512) void project_along_kernel(
     float max_dist, float res_tol, const int *__restrict__ scatter, long out_rows, float *__restrict__ out_height,
     float *__restrict__ out_res, int *__restrict__ out_status, int *__restrict__ out_evals, int a0_lds) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
-    const int NH = hd.NH;
-    float *a0s = smem + lds_floats_for(NH);
-    if (a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
-    load_weights_to_lds(smem, blob, hd);
-    const LdsView L = lds_view(smem, NH);
+    const FieldCtx c = field_prologue<C>(smem, blob, a0_lds);
 
     long N = cap;
     if (count) {
-        const long c = (long)*count;
-        N = c < 0 ? 0 : (c < cap ? c : cap);
+        const long cn = (long)*count;
+        N = cn < 0 ? 0 : (cn < cap ? cn : cap);
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const int p = lane & 31, h = lane >> 5;
-    const int kind = p & 3;
+    const int p = c.p, kind = p & 3;
     const bool is_value = kind == 0;
     const long ntiles = (N + 7) / 8;
-    const float *A0g = blob + hd.off_a0;
-    const long HW = (long)H * W;
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-    for (long tile = (long)blockIdx.x * nwave + wave; tile < ntiles; tile += (long)gridDim.x * nwave) {
+    for (long tile = (long)blockIdx.x * c.nwave + c.wave; tile < ntiles; tile += (long)gridDim.x * c.nwave) {
         long n = tile * 8 + (p >> 2);
         const bool valid = n < N;
         if (!valid) n = N - 1;   // a copy of the last point (N >= 1 here): it runs the same steps and stores nothing
@@ -135,22 +100,13 @@ __global__ __launch_bounds__(512) void project_along_kernel(
         for (int k = 0; k <= K; ++k) {   // K <= 64 (checked at the entry): at most K + 1 evaluations
             float qx, qy, qz;
             line_point(p0x, p0y, p0z, nx, ny, nz, s.s, qx, qy, qz);
-            // one evaluation at (qx, qy, qz): density_grad_kernel's sequence
-            int off[3][4];
-            float wt[3][4];
-            point_taps<AC>(qx, qy, qz, radius, span, H, W, off, wt);
-            tangent_weights<AC>(kind, qx, qy, qz, radius, span, H, W, wt);
-            f32x16 x0 = is_value ? lds_bias16(L.bacc, 0, h, 0) : zero;
-            f32x16 x1 = is_value ? lds_bias16(L.bacc, 0, h, 1) : zero;
-            layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, x0, x1);
-            hidden_layers_fwd(L, NH, lane, h, is_value, x0, x1);
-            const float sv = last_dot0_nobias(L, h, x0, x1);
-            const float d = quad_bcast<0>(sv) + L.blast[0];
+            const float sv = field_eval_fwd<C, AC>(c, planes, H, W, radius, span, a0_lds, kind, qx, qy, qz);
+            const float d = quad_bcast<0>(sv) + c.L.blast[0];
             const float gx = quad_bcast<1>(sv), gy = quad_bcast<2>(sv), gz = quad_bcast<3>(sv);
             line_update(s, k, K, d, gx, gy, gz, p0x, p0y, p0z, nx, ny, nz, target, radius, max_dist, res_tol);
             if (__ballot(s.active) == 0ull) break;   // wave-uniform: all eight points have stopped
         }
-        if (valid && is_value && h == 0) {
+        if (valid && is_value && c.h == 0) {
             const long o = scatter ? (long)scatter[n] : n;
             if (o >= 0 && o < out_rows) {
                 out_height[o] = s.bs;
@@ -241,13 +197,13 @@ extern "C" int sculpt_triplane_project(const float *planes_cl, int C, int H, int
                                        const float *points, long long N, float radius, int flags, float target, int max_steps,
                                        float max_dist, float res_tol, float *out_points, float *out_residual, int *out_status,
                                        int *out_evals, sculpt_stream_t stream) {
-    SC_REQUIRE(C == 40, "triplane_project: built for C=40 channels per plane (got %d)", C);
-    SC_REQUIRE(planes_cl && mlp_packed, "triplane_project: null input");
-    SC_REQUIRE(H >= 1 && W >= 1, "triplane_project: bad plane size %d x %d", H, W);
-    SC_REQUIRE(N >= 0, "triplane_project: negative point count %lld", N);
-    SC_REQUIRE((flags & ~(int)SCULPT_QUERY_ALIGN_CORNERS) == 0, "triplane_project: unknown flags %d", flags);
-    SC_REQUIRE(n_hidden_64 >= 0, "triplane_project: bad n_hidden_64");
-    SC_REQUIRE(radius > 0.f, "triplane_project: radius must be positive");
+    FieldPlan plan;
+    if (const int e = field_plan("triplane_project", C, planes_cl, mlp_packed, H, W, n_hidden_64, radius, plan, [&] {
+            SC_REQUIRE(N >= 0, "triplane_project: negative point count %lld", N);
+            SC_REQUIRE((flags & ~(int)SCULPT_QUERY_ALIGN_CORNERS) == 0, "triplane_project: unknown flags %d", flags);
+            return 0;
+        }))
+        return e;
     SC_REQUIRE(max_steps >= 0 && max_steps <= 64, "triplane_project: max_steps=%d (0 .. 64)", max_steps);
     SC_REQUIRE(max_dist > 0.f && max_dist < INFINITY, "triplane_project: max_dist=%g must be positive and finite", (double)max_dist);   // a NaN fails
     SC_REQUIRE(res_tol > 0.f && res_tol < INFINITY, "triplane_project: res_tol=%g must be positive and finite", (double)res_tol);
@@ -255,20 +211,13 @@ extern "C" int sculpt_triplane_project(const float *planes_cl, int C, int H, int
     if (N == 0) return 0;   // empty arrays have no address: nothing to refuse, nothing to launch
     SC_REQUIRE(out_points, "triplane_project: null out_points");
     SC_REQUIRE(points, "triplane_project: null points");
-    size_t lds = (size_t)lds_floats_for(n_hidden_64) * sizeof(float);
-    SC_REQUIRE(lds <= 160 * 1024, "triplane_project: %d hidden layers do not fit LDS", n_hidden_64);
-    const size_t a0_bytes = (size_t)3 * C * 64 * sizeof(float);
-    const int a0_lds = lds + a0_bytes <= 160 * 1024 ? 1 : 0;
-    if (a0_lds) lds += a0_bytes;
     auto kern = (flags & (int)SCULPT_QUERY_ALIGN_CORNERS) ? project_kernel<40, true> : project_kernel<40, false>;
-    SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long ntiles = ((long)N + 7) / 8;
-    const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
-    const float span = (float)((double)radius - (double)(-radius));
+    int grid;
+    if (const int e = field_grid(plan, kern, ((long)N + 7) / 8, grid)) return e;
     const float md2 = max_dist * max_dist;   // one fp32 product, as the rule states it
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W,
-                       reinterpret_cast<const float *>(mlp_packed), points, (long)N, radius, span, target, max_steps, md2, res_tol,
-                       out_points, out_residual, out_status, out_evals, a0_lds);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), plan.lds, as_stream(stream), planes_cl, H, W,
+                       reinterpret_cast<const float *>(mlp_packed), points, (long)N, radius, plan.span, target, max_steps, md2,
+                       res_tol, out_points, out_residual, out_status, out_evals, plan.a0_lds);
     SC_LAUNCH_CHECK();
     return 0;
 }
@@ -278,13 +227,13 @@ extern "C" int sculpt_triplane_project_along(const float *planes_cl, int C, int 
                                              float radius, int flags, float target, int max_steps, float max_dist, float res_tol,
                                              const int *scatter, long long out_rows, float *out_height, float *out_residual,
                                              int *out_status, int *out_evals, sculpt_stream_t stream) {
-    SC_REQUIRE(C == 40, "triplane_project_along: built for C=40 channels per plane (got %d)", C);
-    SC_REQUIRE(planes_cl && mlp_packed, "triplane_project_along: null input");
-    SC_REQUIRE(H >= 1 && W >= 1, "triplane_project_along: bad plane size %d x %d", H, W);
-    SC_REQUIRE(N >= 0, "triplane_project_along: negative point count %lld", N);
-    SC_REQUIRE((flags & ~(int)SCULPT_QUERY_ALIGN_CORNERS) == 0, "triplane_project_along: unknown flags %d", flags);
-    SC_REQUIRE(n_hidden_64 >= 0, "triplane_project_along: bad n_hidden_64");
-    SC_REQUIRE(radius > 0.f, "triplane_project_along: radius must be positive");
+    FieldPlan plan;
+    if (const int e = field_plan("triplane_project_along", C, planes_cl, mlp_packed, H, W, n_hidden_64, radius, plan, [&] {
+            SC_REQUIRE(N >= 0, "triplane_project_along: negative point count %lld", N);
+            SC_REQUIRE((flags & ~(int)SCULPT_QUERY_ALIGN_CORNERS) == 0, "triplane_project_along: unknown flags %d", flags);
+            return 0;
+        }))
+        return e;
     SC_REQUIRE(max_steps >= 0 && max_steps <= 64, "triplane_project_along: max_steps=%d (0 .. 64)", max_steps);
     SC_REQUIRE(max_dist > 0.f && max_dist < INFINITY, "triplane_project_along: max_dist=%g must be positive and finite", (double)max_dist);   // a NaN fails
     SC_REQUIRE(res_tol > 0.f && res_tol < INFINITY, "triplane_project_along: res_tol=%g must be positive and finite", (double)res_tol);
@@ -293,19 +242,13 @@ extern "C" int sculpt_triplane_project_along(const float *planes_cl, int C, int 
     if (N == 0 || (scatter && out_rows == 0)) return 0;   // empty arrays have no address: nothing to refuse, nothing to launch
     SC_REQUIRE(out_height, "triplane_project_along: null out_height");
     SC_REQUIRE(points && directions, "triplane_project_along: null points or directions");
-    size_t lds = (size_t)lds_floats_for(n_hidden_64) * sizeof(float);
-    SC_REQUIRE(lds <= 160 * 1024, "triplane_project_along: %d hidden layers do not fit LDS", n_hidden_64);
-    const size_t a0_bytes = (size_t)3 * C * 64 * sizeof(float);
-    const int a0_lds = lds + a0_bytes <= 160 * 1024 ? 1 : 0;
-    if (a0_lds) lds += a0_bytes;
     auto kern = (flags & (int)SCULPT_QUERY_ALIGN_CORNERS) ? project_along_kernel<40, true> : project_along_kernel<40, false>;
-    SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long ntiles = ((long)N + 7) / 8;
-    const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
-    const float span = (float)((double)radius - (double)(-radius));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W,
-                       reinterpret_cast<const float *>(mlp_packed), points, directions, (long)N, count, radius, span, target, max_steps,
-                       max_dist, res_tol, scatter, (long)out_rows, out_height, out_residual, out_status, out_evals, a0_lds);
+    int grid;
+    if (const int e = field_grid(plan, kern, ((long)N + 7) / 8, grid)) return e;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), plan.lds, as_stream(stream), planes_cl, H, W,
+                       reinterpret_cast<const float *>(mlp_packed), points, directions, (long)N, count, radius, plan.span, target,
+                       max_steps, max_dist, res_tol, scatter, (long)out_rows, out_height, out_residual, out_status, out_evals,
+                       plan.a0_lds);
     SC_LAUNCH_CHECK();
     return 0;
 }

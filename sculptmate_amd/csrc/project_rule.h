@@ -19,6 +19,16 @@ struct ProjState {
 
 __device__ __forceinline__ bool finite_f(float x) { return fabsf(x) < INFINITY; }
 
+// the state of a point before its first evaluation, which is at p0; `active` false: the point never takes a step
+__device__ __forceinline__ ProjState proj_start(float p0x, float p0y, float p0z, bool active) {
+    ProjState s;
+    s.px = s.bx = p0x, s.py = s.by = p0y, s.pz = s.bz = p0z;
+    s.r = s.br = 0.f;
+    s.gx = s.gy = s.gz = 0.f;
+    s.status = 1, s.evals = 0, s.active = active;
+    return s;
+}
+
 // One turn of the rule after the evaluation (d, g) at the candidate (qx, qy, qz): accept it (k == 0: it is p0), then the
 // checks and the step that lead to the next candidate, which is left in (qx, qy, qz).  DESIGN.md section 3.1e numbers the
 // operations.  -> whether the candidate that was just evaluated is now the best iterate (bx, by, bz): a caller that wants

@@ -15,6 +15,7 @@
 //     no cross-lane operation, no atomics, and a ray's result depends on nothing but the ray -- not on the grid, not on which
 //     rays share its tile.
 //   * a tile with no valid ray is skipped; an invalid ray in a mixed tile samples the box centre and stores white.
+//   * weights into LDS and the launch plan of all three kernels: field_prologue / field_plan / field_grid (field_kernel.h).
 //   * ray geometry and composite are compiled with contraction off (every fp32 operation rounded on its own, as torch on the
 //     CPU does): z_vals and xyz equal the reference's bit for bit.
 // Three quirks of the reference are kept: |d| < 1e-6 becomes +1e-6 whatever the sign of d; delta is the step of the unit
@@ -26,7 +27,8 @@
 //     render_rays_kernel<C> is the kernel it always was, instruction for instruction.
 //   * normal_sum = sum_s w_s n_s needs the field's gradient at every sample: render_passes_kernel, in the forward-mode layout
 //     of density_grad_kernel (csrc/field_normal.hip): a wave owns 8 rays x 4 columns {value, d/dx, d/dy, d/dz}, lane p serves
-//     ray p >> 2 and kind p & 3.  The value column is the point query's own evaluation, so density_act and colour, and with
+//     ray p >> 2 and kind p & 3, and a sample is one field_eval_fwd (field_fwd.h), which leaves what the last layer reads for
+//     the colour rows.  The value column is the point query's own evaluation, so density_act and colour, and with
 //     them w_s and every output of the colour kernel, have the colour kernel's bits (the same ray_box, t_mid block,
 //     density_act_f, color_f, expf and composite); a call that asks for normal_sum is this ONE launch, not two.  n_s is
 //     unit_normal_of (field_fwd.h), the rule and the bits of ops.field_normals at x_s = o + z_s d.  The value lane composites
@@ -35,8 +37,6 @@
 //     field) and adds nothing to any sum (n_s is finite by construction), so the tile stops evaluating; depths and zero weights
 //     of the tail are still written.  No threshold.  SCULPT_RENDER_FORM=noskip walks every sample (A/B); the two forms differ
 //     only for a field that is not finite (a NaN density where T == 0 gives w = NaN in the walk and +0 in the skip).
-#include <algorithm>
-
 #include "common.h"
 #include "field_fwd.h"
 #include "triplane_mlp.h"
@@ -79,20 +79,13 @@ __global__ __launch_bounds__(512) void render_rays_kernel(
     static_assert(sizeof...(Passes) == 0 || sizeof...(Passes) == 2, "no passes, or (float *depth_sum, float *premul)");
     constexpr bool PASSES = sizeof...(Passes) == 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
-    const int NH = hd.NH;
-    float *a0s = smem + lds_floats_for(NH);
-    if (a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
-    load_weights_to_lds(smem, blob, hd);
-    const LdsView L = lds_view(smem, NH);
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const int p = lane & 31, h = lane >> 5;
+    const FieldCtx c = field_prologue<C>(smem, blob, a0_lds);
+    const LdsView &L = c.L;
+    const int lane = c.lane, p = c.p, h = c.h;
     const long ntiles = (N + 31) / 32;
-    const float *A0g = blob + hd.off_a0;
     const long HW = (long)H * W;
 
-    for (long tile = (long)blockIdx.x * nwave + wave; tile < ntiles; tile += (long)gridDim.x * nwave) {
+    for (long tile = (long)blockIdx.x * c.nwave + c.wave; tile < ntiles; tile += (long)gridDim.x * c.nwave) {
         const long n = tile * 32 + p;
         const bool live = n < N, writer = live && h == 0;
         const long nc = live ? n : N - 1;
@@ -119,9 +112,9 @@ __global__ __launch_bounds__(512) void render_rays_kernel(
                 point_taps<false>(x[0], x[1], x[2], radius, span, H, W, off, wt);
                 f32x16 acc0 = lds_bias16(L.bacc, 0, h, 0);
                 f32x16 acc1 = lds_bias16(L.bacc, 0, h, 1);
-                layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, acc0, acc1);
+                layer0_channel_last<C>(planes, HW, off, wt, c.a0s, c.A0g, a0_lds, lane, h, acc0, acc1);
                 f32x16 x0 = silu16(acc0), x1 = silu16(acc1);
-                hidden_layers(L, NH, lane, h, x0, x1);
+                hidden_layers(L, c.NH, lane, h, x0, x1);
                 const float dens = density_act_f(last_dot(L, 0, h, x0, x1), density_bias);
                 const float r = color_f(last_dot(L, 1, h, x0, x1));
                 const float g = color_f(last_dot(L, 2, h, x0, x1));
@@ -182,23 +175,13 @@ __global__ __launch_bounds__(512) void render_passes_kernel(
     float *__restrict__ z_vals, float *__restrict__ weights, float *__restrict__ depth_sum, float *__restrict__ normal_sum,
     float *__restrict__ premul, int a0_lds, int noskip) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const MlpPackHeader hd = *reinterpret_cast<const MlpPackHeader *>(blob);
-    const int NH = hd.NH;
-    float *a0s = smem + lds_floats_for(NH);
-    if (a0_lds) stage_a0_in_lds<C>(a0s, blob, hd);
-    load_weights_to_lds(smem, blob, hd);
-    const LdsView L = lds_view(smem, NH);
-
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    const int p = lane & 31, h = lane >> 5;
-    const int kind = p & 3;
+    const FieldCtx c = field_prologue<C>(smem, blob, a0_lds);
+    const LdsView &L = c.L;
+    const int p = c.p, h = c.h, kind = p & 3;
     const bool is_value = kind == 0;
     const long ntiles = (N + 7) / 8;
-    const float *A0g = blob + hd.off_a0;
-    const long HW = (long)H * W;
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-    for (long tile = (long)blockIdx.x * nwave + wave; tile < ntiles; tile += (long)gridDim.x * nwave) {
+    for (long tile = (long)blockIdx.x * c.nwave + c.wave; tile < ntiles; tile += (long)gridDim.x * c.nwave) {
         const long n = tile * 8 + (p >> 2);
         const bool live = n < N, writer = live && is_value && h == 0;
         const long nc = live ? n : N - 1;
@@ -224,15 +207,8 @@ __global__ __launch_bounds__(512) void render_passes_kernel(
                     for (int k = 0; k < 3; ++k) x[k] = valid ? o[k] + z * d[k] : 0.f;
                     delta = tb - ta;
                 }
-                int off[3][4];
-                float wt[3][4];
-                point_taps<false>(x[0], x[1], x[2], radius, span, H, W, off, wt);
-                tangent_weights<false>(kind, x[0], x[1], x[2], radius, span, H, W, wt);
-                f32x16 x0 = is_value ? lds_bias16(L.bacc, 0, h, 0) : zero;
-                f32x16 x1 = is_value ? lds_bias16(L.bacc, 0, h, 1) : zero;
-                layer0_channel_last<C>(planes, HW, off, wt, a0s, A0g, a0_lds, lane, h, x0, x1);
-                hidden_layers_fwd(L, NH, lane, h, is_value, x0, x1);
-                const float q = last_dot0_nobias(L, h, x0, x1);
+                f32x16 x0, x1;
+                const float q = field_eval_fwd<C, false>(c, planes, H, W, radius, span, a0_lds, kind, x[0], x[1], x[2], x0, x1);
                 const float dens = density_act_f(quad_bcast<0>(q + L.blast[0]), density_bias);  // last_dot(L, 0, ...) of the value column
                 const float r = color_f(last_dot(L, 1, h, x0, x1));  // the colour of the value column; unused elsewhere
                 const float g = color_f(last_dot(L, 2, h, x0, x1));
@@ -296,29 +272,22 @@ extern "C" int sculpt_render_rays(const float *planes_cl, int C, int H, int W, c
                                   const float *rays_o, const float *rays_d, int64_t n_rays, float radius, float density_bias,
                                   const float *t_vals, int S, float *comp_rgb, float *opacity, float *z_vals, float *weights,
                                   sculpt_stream_t stream) {
-    SC_REQUIRE(C == 40, "render_rays: built for C=40 channels per plane (got %d)", C);
-    SC_REQUIRE(planes_cl && mlp_packed, "render_rays: null input");
-    SC_REQUIRE(H >= 1 && W >= 1, "render_rays: bad plane size %d x %d", H, W);
-    SC_REQUIRE(n_rays >= 0, "render_rays: negative ray count");
-    SC_REQUIRE(S >= 1, "render_rays: need at least one sample per ray (got %d)", S);
-    SC_REQUIRE(n_hidden_64 >= 0, "render_rays: bad n_hidden_64");
-    SC_REQUIRE(radius > 0.f, "render_rays: radius must be positive");
+    FieldPlan plan;
+    if (const int e = field_plan("render_rays", C, planes_cl, mlp_packed, H, W, n_hidden_64, radius, plan, [&] {
+            SC_REQUIRE(n_rays >= 0, "render_rays: negative ray count");
+            SC_REQUIRE(S >= 1, "render_rays: need at least one sample per ray (got %d)", S);
+            return 0;
+        }))
+        return e;
     if (n_rays == 0) return 0;
     SC_REQUIRE(rays_o && rays_d && t_vals && comp_rgb, "render_rays: null rays, t_vals or comp_rgb");
-    size_t lds = (size_t)lds_floats_for(n_hidden_64) * sizeof(float);
-    SC_REQUIRE(lds <= 160 * 1024, "render_rays: %d hidden layers do not fit LDS", n_hidden_64);
-    const size_t a0_bytes = (size_t)3 * C * 64 * sizeof(float);
-    const int a0_lds = lds + a0_bytes <= 160 * 1024 ? 1 : 0;
-    if (a0_lds) lds += a0_bytes;
     auto kern = render_rays_kernel<40>;
-    SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long ntiles = ((long)n_rays + 31) / 32;
-    const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
-    const float span = (float)((double)radius - (double)(-radius));
+    int grid;
+    if (const int e = field_grid(plan, kern, ((long)n_rays + 31) / 32, grid)) return e;
     const float box = (float)(1.0 - 1.0e-3) * radius;  // utils.py:131-133, the product rounded once in fp32
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W,
-                       reinterpret_cast<const float *>(mlp_packed), rays_o, rays_d, (long)n_rays, radius, span, box, density_bias,
-                       t_vals, S, comp_rgb, opacity, z_vals, weights, a0_lds);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), plan.lds, as_stream(stream), planes_cl, H, W,
+                       reinterpret_cast<const float *>(mlp_packed), rays_o, rays_d, (long)n_rays, radius, plan.span, box, density_bias,
+                       t_vals, S, comp_rgb, opacity, z_vals, weights, plan.a0_lds);
     SC_LAUNCH_CHECK();
     return 0;
 }
@@ -330,39 +299,30 @@ extern "C" int sculpt_render_passes(const float *planes_cl, int C, int H, int W,
     if (!depth_sum && !normal_sum && !premul)  // the colour picture alone: sculpt_render_rays' own launch
         return sculpt_render_rays(planes_cl, C, H, W, mlp_packed, n_hidden_64, rays_o, rays_d, n_rays, radius, density_bias, t_vals, S,
                                   comp_rgb, opacity, z_vals, weights, stream);
-    SC_REQUIRE(C == 40, "render_passes: built for C=40 channels per plane (got %d)", C);
-    SC_REQUIRE(planes_cl && mlp_packed, "render_passes: null input");
-    SC_REQUIRE(H >= 1 && W >= 1, "render_passes: bad plane size %d x %d", H, W);
-    SC_REQUIRE(n_rays >= 0, "render_passes: negative ray count");
-    SC_REQUIRE(S >= 1, "render_passes: need at least one sample per ray (got %d)", S);
-    SC_REQUIRE(n_hidden_64 >= 0, "render_passes: bad n_hidden_64");
-    SC_REQUIRE(radius > 0.f, "render_passes: radius must be positive");
+    FieldPlan plan;
+    if (const int e = field_plan("render_passes", C, planes_cl, mlp_packed, H, W, n_hidden_64, radius, plan, [&] {
+            SC_REQUIRE(n_rays >= 0, "render_passes: negative ray count");
+            SC_REQUIRE(S >= 1, "render_passes: need at least one sample per ray (got %d)", S);
+            return 0;
+        }))
+        return e;
     if (n_rays == 0) return 0;
     SC_REQUIRE(rays_o && rays_d && t_vals && comp_rgb, "render_passes: null rays, t_vals or comp_rgb");
-    size_t lds = (size_t)lds_floats_for(n_hidden_64) * sizeof(float);
-    SC_REQUIRE(lds <= 160 * 1024, "render_passes: %d hidden layers do not fit LDS", n_hidden_64);
-    const size_t a0_bytes = (size_t)3 * C * 64 * sizeof(float);
-    const int a0_lds = lds + a0_bytes <= 160 * 1024 ? 1 : 0;
-    if (a0_lds) lds += a0_bytes;
-    const float span = (float)((double)radius - (double)(-radius));
     const float box = (float)(1.0 - 1.0e-3) * radius;
+    int grid;
     const float *blob = reinterpret_cast<const float *>(mlp_packed);
     if (normal_sum) {  // everything in the forward-mode layout, one launch
         auto kern = render_passes_kernel<40>;
-        SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const long ntiles = ((long)n_rays + 7) / 8;
-        const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
+        if (const int e = field_grid(plan, kern, ((long)n_rays + 7) / 8, grid)) return e;
         const int noskip = form_has("SCULPT_RENDER_FORM", "noskip") ? 1 : 0;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W, blob, rays_o, rays_d, (long)n_rays,
-                           radius, span, box, density_bias, t_vals, S, comp_rgb, opacity, z_vals, weights, depth_sum, normal_sum, premul,
-                           a0_lds, noskip);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), plan.lds, as_stream(stream), planes_cl, H, W, blob, rays_o, rays_d, (long)n_rays,
+                           radius, plan.span, box, density_bias, t_vals, S, comp_rgb, opacity, z_vals, weights, depth_sum, normal_sum, premul,
+                           plan.a0_lds, noskip);
     } else {  // the colour kernel with its two more sums
         auto kern = render_rays_kernel<40, float *, float *>;
-        SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const long ntiles = ((long)n_rays + 31) / 32;
-        const int grid = (int)std::min<long>((ntiles + 7) / 8, num_cus());
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, as_stream(stream), planes_cl, H, W, blob, rays_o, rays_d, (long)n_rays,
-                           radius, span, box, density_bias, t_vals, S, comp_rgb, opacity, z_vals, weights, a0_lds, depth_sum, premul);
+        if (const int e = field_grid(plan, kern, ((long)n_rays + 31) / 32, grid)) return e;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), plan.lds, as_stream(stream), planes_cl, H, W, blob, rays_o, rays_d, (long)n_rays,
+                           radius, plan.span, box, density_bias, t_vals, S, comp_rgb, opacity, z_vals, weights, plan.a0_lds, depth_sum, premul);
     }
     SC_LAUNCH_CHECK();
     return 0;

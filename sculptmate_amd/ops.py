@@ -1264,6 +1264,36 @@ def _occlusion_composed(index, pts, nrm, dirs, offset, far):
 OCCLUSION_CAGE = 2.0 ** -6         # the default snap distance of a bake against a source, in longest sides of the source's bounds
 
 
+def _mesh_args(who, v_pos, faces):
+    """The mesh every atlas bake takes, checked: v_pos f32 [Nv, 3], faces i32 / i64 [Nf, 3], device tensors -> (v, f) contiguous."""
+    v = _req(v_pos.contiguous() if isinstance(v_pos, torch.Tensor) else v_pos, torch.float32, "v_pos")
+    if not (isinstance(faces, torch.Tensor) and faces.is_cuda):
+        raise SculptError("faces must be a CUDA/HIP tensor (no CPU fallback)")
+    if faces.dtype not in (torch.int32, torch.int64):
+        raise SculptError("%s: faces must be int32 or int64, got %s" % (who, faces.dtype))
+    f = faces.contiguous()
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise SculptError("%s: v_pos %s must be [Nv, 3] and faces %s [Nf, 3]" % (who, tuple(v.shape), tuple(f.shape)))
+    return v, f
+
+
+def _covered_texels(r, v, f):
+    """The coverage of texel_position (csrc/bake_texel.h) in torch: a texel is covered when its tri is in [0, Nf) (a NaN is
+    not) and the three vertex rows of that face are in [0, Nv) -> (covered bool [res, res], rast with (0, 0, 0, -1) wherever it
+    is not covered, so that bake_interpolate, which guards nothing, reads through checked rows only)."""
+    nv, nf = v.shape[0], f.shape[0]
+    tri = r[..., 3]
+    covered = (tri >= 0) & (tri < 2147483648.0)                     # a NaN fails both
+    if nf == 0 or nv == 0:
+        covered = torch.zeros_like(covered)
+    else:
+        t = torch.where(covered, tri, torch.zeros_like(tri)).to(torch.int64)
+        covered = covered & (t < nf)
+        rows = f[t.clamp(max=nf - 1)].to(torch.int64)               # [res, res, 3]
+        covered = covered & ((rows >= 0) & (rows < nv)).all(-1)
+    return covered, torch.where(covered[..., None], r, r.new_tensor([0.0, 0.0, 0.0, -1.0])).contiguous()
+
+
 def _bake_occlusion_args(who, v_pos, faces, normals, rast, occlusion, offset, seed, source, cage):
     """Rules first (ValueError, nothing launched), then the tensors (SculptError), then the index over S.
     -> (index or None when res == 0, v, f, nrm, rast, dirs, offset, far, cage)."""
@@ -1279,17 +1309,11 @@ def _bake_occlusion_args(who, v_pos, faces, normals, rast, occlusion, offset, se
             raise ValueError("%s: source must be None or (vertices, faces), got %r" % (who, type(source).__name__))
         if cage is not None and not (_is_real(cage) and 0.0 < float(np.float32(cage)) < math.inf):   # a NaN fails the comparison
             raise ValueError("cage must be None or a finite number > 0, got %r" % (cage,))
-    v = _req(v_pos.contiguous() if isinstance(v_pos, torch.Tensor) else v_pos, torch.float32, "v_pos")
-    if not (isinstance(faces, torch.Tensor) and faces.is_cuda):
-        raise SculptError("faces must be a CUDA/HIP tensor (no CPU fallback)")
-    if faces.dtype not in (torch.int32, torch.int64):
-        raise SculptError("%s: faces must be int32 or int64, got %s" % (who, faces.dtype))
-    f = faces.contiguous()
+    v, f = _mesh_args(who, v_pos, faces)
     nrm = _req(normals.contiguous() if isinstance(normals, torch.Tensor) else normals, torch.float32, "normals")
     r = _req(rast.contiguous() if isinstance(rast, torch.Tensor) else rast, torch.float32, "rast")
-    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or nrm.shape != v.shape:
-        raise SculptError("%s: v_pos %s must be [Nv, 3], normals %s the same and faces %s [Nf, 3]"
-                          % (who, tuple(v.shape), tuple(nrm.shape), tuple(f.shape)))
+    if nrm.shape != v.shape:
+        raise SculptError("%s: normals %s must be per vertex %s" % (who, tuple(nrm.shape), tuple(v.shape)))
     if r.ndim != 3 or r.shape[0] != r.shape[1] or r.shape[2] != 4:
         raise SculptError("%s: rast %s must be [res, res, 4]" % (who, tuple(r.shape)))
     P, F = _surface(v, f, who) if source is None else _surface(source[0], source[1], who)
@@ -1350,19 +1374,11 @@ def bake_occlusion_composed(v_pos, faces, normals, rast, occlusion=True, offset=
 
 
 def _bake_occlusion_composed(index, v, f, nrm, r, dirs, offset, far, cage):
-    res, nv, nf = r.shape[0], v.shape[0], f.shape[0]
+    res = r.shape[0]
     ao = torch.zeros(res * res, dtype=torch.float32, device=r.device)
-    cov = torch.zeros((res, res), dtype=torch.bool, device=r.device)
-    if index is None or nf == 0 or nv == 0:
+    cov, clean = _covered_texels(r, v, f)
+    if index is None:
         return ao.view(res, res), cov
-    # the coverage of texel_position, so that bake_interpolate (which guards nothing) reads through checked rows only
-    tri = r[..., 3]
-    cov = (tri >= 0) & (tri < 2147483648.0)                     # a NaN fails both
-    t = torch.where(cov, tri, torch.zeros_like(tri)).to(torch.int64)
-    cov = cov & (t < nf)
-    rows = f[t.clamp(max=nf - 1)].to(torch.int64)               # [res, res, 3]
-    cov = cov & ((rows >= 0) & (rows < nv)).all(-1)
-    clean = torch.where(cov[..., None], r, r.new_tensor([0.0, 0.0, 0.0, -1.0])).contiguous()
     at = torch.nonzero(cov.reshape(-1))[:, 0]
     if at.numel() == 0:
         return ao.view(res, res), cov
@@ -1771,6 +1787,17 @@ def _project_args(steps, max_dist, res_tol, target):
         raise ValueError("target must be finite, got %r" % (target,))
 
 
+_PROJECT_EXTRAS = (("residual", torch.float32), ("status", torch.int32), ("evals", torch.int32))   # what the searches can return
+
+
+def _want_extras(who, want):
+    want = tuple(want)
+    unknown = set(want) - {k for k, _ in _PROJECT_EXTRAS}
+    if unknown:
+        raise SculptError("%s: unknown output %s" % (who, sorted(unknown)))
+    return want
+
+
 def project_to_isosurface(planes, mlp, points, target, max_dist, steps=PROJECT_STEPS, res_tol=PROJECT_RES_TOL, radius=0.87,
                           align_corners=False, want=()):
     """`points` moved onto the iso-surface d(p) = target of the raw density (the `density` of field_normals / triplane_query,
@@ -1786,10 +1813,7 @@ def project_to_isosurface(planes, mlp, points, target, max_dist, steps=PROJECT_S
                               (not finite, or a zero gradient: a point outside all three planes)
        "evals"    i32 [...]   evaluations of (d, g) the point used, 1 .. steps + 1
     A point's result depends on that point alone.  steps == 0 evaluates once and returns the input points."""
-    want = tuple(want)
-    unknown = set(want) - {"residual", "status", "evals"}
-    if unknown:
-        raise SculptError("project_to_isosurface: unknown output %s" % sorted(unknown))
+    want = _want_extras("project_to_isosurface", want)
     _project_args(steps, max_dist, res_tol, target)
     if points.shape[-1] != 3:
         raise SculptError("project_to_isosurface: points %s must be [..., 3]" % (tuple(points.shape),))
@@ -1799,8 +1823,7 @@ def project_to_isosurface(planes, mlp, points, target, max_dist, steps=PROJECT_S
     pts = _req(points.reshape(-1, 3).contiguous(), torch.float32, "points")
     N = pts.shape[0]
     out = torch.empty((N, 3), dtype=torch.float32, device=pts.device)
-    ex = {k: torch.empty((N,), dtype=dt, device=pts.device) if k in want else None
-          for k, dt in (("residual", torch.float32), ("status", torch.int32), ("evals", torch.int32))}
+    ex = {k: torch.empty((N,), dtype=dt, device=pts.device) if k in want else None for k, dt in _PROJECT_EXTRAS}
     check(lib.sculpt_triplane_project(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(pts), N,
                                       float(radius), _lib.QUERY_ALIGN_CORNERS if align_corners else 0, float(target), int(steps),
                                       float(max_dist), float(res_tol), _ptr(out), _ptr(ex["residual"]), _ptr(ex["status"]),
@@ -2077,15 +2100,8 @@ def _bake_scene_args(who, planes, v_pos, faces, rast):
     """The arguments the atlas bakes of a scene code share, checked -> (channel-last planes, v, f, rast, res)."""
     if not isinstance(planes, ChannelLastPlanes):
         planes = ChannelLastPlanes(planes)
-    v = _req(v_pos.contiguous() if isinstance(v_pos, torch.Tensor) else v_pos, torch.float32, "v_pos")
-    if not (isinstance(faces, torch.Tensor) and faces.is_cuda):
-        raise SculptError("faces must be a CUDA/HIP tensor (no CPU fallback)")
-    if faces.dtype not in (torch.int32, torch.int64):
-        raise SculptError("%s: faces must be int32 or int64, got %s" % (who, faces.dtype))
-    f = faces.contiguous()
+    v, f = _mesh_args(who, v_pos, faces)
     r = _req(rast.contiguous() if isinstance(rast, torch.Tensor) else rast, torch.float32, "rast")
-    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
-        raise SculptError("%s: v_pos %s must be [Nv, 3] and faces %s [Nf, 3]" % (who, tuple(v.shape), tuple(f.shape)))
     if r.ndim != 3 or r.shape[0] != r.shape[1] or r.shape[2] != 4:
         raise SculptError("%s: rast %s must be [res, res, 4]" % (who, tuple(r.shape)))
     return planes, v, f, r, r.shape[0]
@@ -2114,17 +2130,10 @@ def corner_tangents(v_pos, faces, uvs, corner_normals):
     w = +1 / -1 the handedness (cross(N, T) * w points along dP/dv; a chart mirrored in the atlas gets -1).  A face without UV
     area, or a corner whose normal is parallel to dP/du, gets a unit vector perpendicular to the normal (its cross product with
     the axis of its smallest component) and w = +1."""
-    v = _req(v_pos.contiguous() if isinstance(v_pos, torch.Tensor) else v_pos, torch.float32, "v_pos")
-    if not (isinstance(faces, torch.Tensor) and faces.is_cuda):
-        raise SculptError("faces must be a CUDA/HIP tensor (no CPU fallback)")
-    if faces.dtype not in (torch.int32, torch.int64):
-        raise SculptError("corner_tangents: faces must be int32 or int64, got %s" % faces.dtype)
-    f = faces.contiguous()
+    v, f = _mesh_args("corner_tangents", v_pos, faces)
     uv = _req(uvs.contiguous() if isinstance(uvs, torch.Tensor) else uvs, torch.float32, "uvs")
     cn = _req(corner_normals.contiguous() if isinstance(corner_normals, torch.Tensor) else corner_normals, torch.float32,
               "corner_normals")
-    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
-        raise SculptError("corner_tangents: v_pos %s must be [Nv, 3] and faces %s [Nf, 3]" % (tuple(v.shape), tuple(f.shape)))
     nf = f.shape[0]
     if tuple(uv.shape) != (3 * nf, 2) or tuple(cn.shape) != (3 * nf, 3):
         raise SculptError("corner_tangents: uvs %s must be [%d, 2] and corner_normals %s [%d, 3] (three rows per face)"
@@ -2133,6 +2142,22 @@ def corner_tangents(v_pos, faces, uvs, corner_normals):
     check(lib.sculpt_corner_tangents(_ptr(v), v.shape[0], _ptr(f), int(f.dtype == torch.int64), nf, _ptr(uv), _ptr(cn), _ptr(out),
                                      _stream()))
     return out
+
+
+def _frame_args(who, frame, nf):
+    """`frame` of the normal bakes, checked -> (corner_normals, corner_tangents), or (None, None) without a frame."""
+    if frame is None:
+        return None, None
+    if not (isinstance(frame, (tuple, list)) and len(frame) == 2):
+        raise SculptError("%s: frame must be None or (corner_normals, corner_tangents)" % who)
+    cn = _req(frame[0], torch.float32, "corner_normals")
+    ct = _req(frame[1], torch.float32, "corner_tangents")
+    if tuple(cn.shape) != (3 * nf, 3) or tuple(ct.shape) != (3 * nf, 4):
+        raise SculptError("%s: corner_normals %s must be [%d, 3] and corner_tangents %s [%d, 4] (three rows per face)"
+                          % (who, tuple(cn.shape), 3 * nf, tuple(ct.shape), 3 * nf))
+    if nf == 0:   # no face, no frame rows: nothing is covered, and an empty tensor has no address
+        return None, None
+    return cn, ct
 
 
 def bake_scene_normal(planes, mlp, v_pos, faces, rast, radius=0.87, frame=None):
@@ -2147,22 +2172,11 @@ def bake_scene_normal(planes, mlp, v_pos, faces, rast, radius=0.87, frame=None):
     if isinstance(rast, torch.Tensor) and not rast.is_contiguous():   # a view of a larger image is a caller's mistake, not copied
         raise SculptError("bake_scene_normal: rast must be contiguous")
     planes, v, f, r, res = _bake_scene_args("bake_scene_normal", planes, v_pos, faces, rast)
-    cn = ct = None
-    if frame is not None:
-        if not (isinstance(frame, (tuple, list)) and len(frame) == 2):
-            raise SculptError("bake_scene_normal: frame must be None or (corner_normals, corner_tangents)")
-        cn = _req(frame[0], torch.float32, "corner_normals")
-        ct = _req(frame[1], torch.float32, "corner_tangents")
-        nf = f.shape[0]
-        if tuple(cn.shape) != (3 * nf, 3) or tuple(ct.shape) != (3 * nf, 4):
-            raise SculptError("bake_scene_normal: corner_normals %s must be [%d, 3] and corner_tangents %s [%d, 4] (three rows per "
-                              "face)" % (tuple(cn.shape), 3 * nf, tuple(ct.shape), 3 * nf))
+    cn, ct = _frame_args("bake_scene_normal", frame, f.shape[0])
     normal = torch.empty((res, res, 3), dtype=torch.float32, device=r.device)
     mask = torch.empty((res, res), dtype=torch.uint8, device=r.device)
     if res == 0:
         return normal, mask.view(torch.bool)
-    if frame is not None and f.shape[0] == 0:   # no face, no frame rows: nothing is covered, and an empty tensor has no address
-        cn = ct = None
     check(lib.sculpt_bake_scene_normal(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(v), v.shape[0],
                                        _ptr(f), int(f.dtype == torch.int64), f.shape[0], _ptr(r), res, float(radius), _ptr(cn),
                                        _ptr(ct), _ptr(normal), _ptr(mask), _stream()))
@@ -2172,30 +2186,13 @@ def bake_scene_normal(planes, mlp, v_pos, faces, rast, radius=0.87, frame=None):
 # ----------------------------------------------------------------------------------------------
 # bake at the surface: project each texel onto the iso-surface first (csrc/bake_surface.hip)
 # ----------------------------------------------------------------------------------------------
-_SURFACE_EXTRAS = (("residual", torch.float32), ("status", torch.int32), ("evals", torch.int32))
-
-
 def _bake_surface_args(who, planes, v_pos, faces, rast, target, max_dist, steps, res_tol, frame, want):
     """The checks the two routes of the surface bake share: _bake_scene_args, _project_args and the frame checks of
     bake_scene_normal -> (channel-last planes, v, f, rast, res, corner_normals or None, corner_tangents or None, want)."""
-    want = tuple(want)
-    unknown = set(want) - {k for k, _ in _SURFACE_EXTRAS}
-    if unknown:
-        raise SculptError("%s: unknown output %s" % (who, sorted(unknown)))
+    want = _want_extras(who, want)
     _project_args(steps, max_dist, res_tol, target)
     planes, v, f, r, res = _bake_scene_args(who, planes, v_pos, faces, rast)
-    cn = ct = None
-    if frame is not None:
-        if not (isinstance(frame, (tuple, list)) and len(frame) == 2):
-            raise SculptError("%s: frame must be None or (corner_normals, corner_tangents)" % who)
-        cn = _req(frame[0], torch.float32, "corner_normals")
-        ct = _req(frame[1], torch.float32, "corner_tangents")
-        nf = f.shape[0]
-        if tuple(cn.shape) != (3 * nf, 3) or tuple(ct.shape) != (3 * nf, 4):
-            raise SculptError("%s: corner_normals %s must be [%d, 3] and corner_tangents %s [%d, 4] (three rows per face)"
-                              % (who, tuple(cn.shape), 3 * nf, tuple(ct.shape), 3 * nf))
-        if nf == 0:   # no face, no frame rows: nothing is covered, and an empty tensor has no address
-            cn = ct = None
+    cn, ct = _frame_args(who, frame, f.shape[0])
     return planes, v, f, r, res, cn, ct, want
 
 
@@ -2220,7 +2217,7 @@ def bake_scene_surface(planes, mlp, v_pos, faces, rast, target, max_dist, steps=
     point = torch.empty((res, res, 3), dtype=torch.float32, device=dev)
     normal = torch.empty((res, res, 3), dtype=torch.float32, device=dev)
     mask = torch.empty((res, res), dtype=torch.uint8, device=dev)
-    ex = {k: torch.empty((res, res), dtype=dt, device=dev) if k in want else None for k, dt in _SURFACE_EXTRAS}
+    ex = {k: torch.empty((res, res), dtype=dt, device=dev) if k in want else None for k, dt in _PROJECT_EXTRAS}
     if res > 0:
         check(lib.sculpt_bake_scene_surface(_ptr(planes.data), planes.C, planes.H, planes.W, _ptr(mlp.blob), mlp.n_hidden, _ptr(v),
                                             v.shape[0], _ptr(f), int(f.dtype == torch.int64), f.shape[0], _ptr(r), res, float(radius),
@@ -2271,17 +2268,7 @@ def bake_scene_surface_composed(planes, mlp, v_pos, faces, rast, target, max_dis
     ex = {"residual": torch.zeros((res, res), dtype=torch.float32, device=dev),
           "status": torch.full((res, res), -1, dtype=torch.int32, device=dev),
           "evals": torch.zeros((res, res), dtype=torch.int32, device=dev)}
-    nv, nf = v.shape[0], f.shape[0]
-    tri = r[..., 3]
-    covered = (tri >= 0) & (tri < 2147483648.0)                     # a NaN fails both
-    if nf == 0 or nv == 0:
-        covered = torch.zeros_like(covered)
-    else:
-        t = torch.where(covered, tri, torch.zeros_like(tri)).to(torch.int64)
-        covered = covered & (t < nf)
-        rows = f[t.clamp(max=nf - 1)].to(torch.int64)               # [res, res, 3]
-        covered = covered & ((rows >= 0) & (rows < nv)).all(-1)
-        r = torch.where(covered[..., None], r, r.new_tensor([0.0, 0.0, 0.0, -1.0])).contiguous()
+    covered, r = _covered_texels(r, v, f)
     idx = covered.reshape(-1).nonzero()[:, 0]
     if idx.numel() > 0:
         pos = bake_interpolate(v, r, f).reshape(-1, 3)[idx].contiguous()
@@ -2352,10 +2339,7 @@ def project_along(planes, mlp, points, directions, target, max_dist, steps=DISPL
     count: a device int32 tensor of one element -- only the first min(count, N) points are read, and only their rows of the
     outputs are written; out: a dict of preallocated flat outputs ("height" and the extras) to write into, for the rows that
     must stay untouched.  A point's result depends on that point alone."""
-    want = tuple(want)
-    unknown = set(want) - {"residual", "status", "evals"}
-    if unknown:
-        raise SculptError("project_along: unknown output %s" % sorted(unknown))
+    want = _want_extras("project_along", want)
     _project_args(steps, max_dist, res_tol, target)
     if points.shape[-1] != 3 or tuple(points.shape) != tuple(directions.shape):
         raise SculptError("project_along: points %s and directions %s must both be [..., 3]" % (tuple(points.shape), tuple(directions.shape)))
@@ -2369,9 +2353,8 @@ def project_along(planes, mlp, points, directions, target, max_dist, steps=DISPL
         count = _req(count, torch.int32, "count")
         if count.numel() != 1:
             raise SculptError("project_along: count must hold one int32")
-    kinds = (("height", torch.float32), ("residual", torch.float32), ("status", torch.int32), ("evals", torch.int32))
     ex = {}
-    for k, dt in kinds:
+    for k, dt in (("height", torch.float32),) + _PROJECT_EXTRAS:
         if k != "height" and k not in want:
             ex[k] = None
         elif out is not None and k in out:
@@ -2395,13 +2378,10 @@ def bake_texel_list(v_pos, faces, rast, normals=None):
     mask bool [res,res])."""
     if not (isinstance(rast, torch.Tensor) and rast.is_contiguous()):
         raise SculptError("bake_texel_list: rast must be a contiguous tensor")
-    v = _req(v_pos.contiguous() if isinstance(v_pos, torch.Tensor) else v_pos, torch.float32, "v_pos")
-    if not (isinstance(faces, torch.Tensor) and faces.is_cuda) or faces.dtype not in (torch.int32, torch.int64):
-        raise SculptError("bake_texel_list: faces must be an int32 or int64 CUDA/HIP tensor")
-    f = faces.contiguous()
+    v, f = _mesh_args("bake_texel_list", v_pos, faces)
     r = _req(rast, torch.float32, "rast")
-    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or r.ndim != 3 or r.shape[0] != r.shape[1] or r.shape[2] != 4:
-        raise SculptError("bake_texel_list: v_pos [Nv,3], faces [Nf,3], rast [res,res,4]")
+    if r.ndim != 3 or r.shape[0] != r.shape[1] or r.shape[2] != 4:
+        raise SculptError("bake_texel_list: rast %s must be [res, res, 4]" % (tuple(r.shape),))
     nrm = None
     if normals is not None:
         nrm = _req(normals.contiguous(), torch.float32, "normals")
@@ -2427,14 +2407,8 @@ def _texel_list(v, f, r, nrm, images):
     return {k: t for k, t in got.items() if t is not None}
 
 
-_DISPLACEMENT_IMAGES = (("height", torch.float32), ("residual", torch.float32), ("status", torch.int32), ("evals", torch.int32))
-
-
 def _bake_displacement_args(who, planes, v_pos, faces, normals, rast, target, max_dist, steps, res_tol, want):
-    want = tuple(want)
-    unknown = set(want) - {"residual", "status", "evals"}
-    if unknown:
-        raise SculptError("%s: unknown output %s" % (who, sorted(unknown)))
+    want = _want_extras(who, want)
     _project_args(steps, max_dist, res_tol, target)
     if isinstance(rast, torch.Tensor) and not rast.is_contiguous():
         raise SculptError("%s: rast must be contiguous" % who)
@@ -2460,7 +2434,8 @@ def bake_displacement(planes, mlp, v_pos, faces, normals, rast, target, max_dist
     planes, v, f, nrm, r, res, want = _bake_displacement_args("bake_displacement", planes, v_pos, faces, normals, rast, target, max_dist,
                                                               steps, res_tol, want)
     dev = r.device
-    im = {k: torch.empty((res, res), dtype=dt, device=dev) if k == "height" or k in want else None for k, dt in _DISPLACEMENT_IMAGES}
+    im = {k: torch.empty((res, res), dtype=dt, device=dev) if k == "height" or k in want else None
+          for k, dt in (("height", torch.float32),) + _PROJECT_EXTRAS}
     if res == 0:
         return im["height"], torch.empty((0, 0), dtype=torch.bool, device=dev), {k: im[k] for k in want}
     got = _texel_list(v, f, r, nrm, im)
@@ -2482,17 +2457,7 @@ def bake_displacement_composed(planes, mlp, v_pos, faces, normals, rast, target,
           "residual": torch.zeros((res, res), dtype=torch.float32, device=dev),
           "status": torch.full((res, res), -1, dtype=torch.int32, device=dev),
           "evals": torch.zeros((res, res), dtype=torch.int32, device=dev)}
-    nv, nf = v.shape[0], f.shape[0]
-    tri = r[..., 3]
-    covered = (tri >= 0) & (tri < 2147483648.0)                     # a NaN fails both
-    if nf == 0 or nv == 0:
-        covered = torch.zeros_like(covered)
-    else:
-        t = torch.where(covered, tri, torch.zeros_like(tri)).to(torch.int64)
-        covered = covered & (t < nf)
-        rows = f[t.clamp(max=nf - 1)].to(torch.int64)               # [res, res, 3]
-        covered = covered & ((rows >= 0) & (rows < nv)).all(-1)
-        r = torch.where(covered[..., None], r, r.new_tensor([0.0, 0.0, 0.0, -1.0])).contiguous()
+    covered, r = _covered_texels(r, v, f)
     idx = covered.reshape(-1).nonzero()[:, 0]
     if idx.numel() > 0:
         pos = bake_interpolate(v, r, f).reshape(-1, 3)[idx].contiguous()

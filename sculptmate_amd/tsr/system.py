@@ -980,6 +980,34 @@ class TSR(KernelEngine):
     _chart_unwrapper = None   # the cached ChartUnwrapper
     _quads = None   # extract_meshes -> _reshaped: the extractor's quads as a Catmull-Clark cage; and back: the refined quads
 
+    def _iso_target(self, threshold, cells, resolution):
+        """The iso-surface density_act = threshold in the raw density, and a trust radius in cells of a `resolution`^3 lattice
+        -> (target = float32(ln(threshold) - density_bias), computed in double; max_dist = cells x the lattice spacing
+        2 radius / (resolution - 1))."""
+        cfg = self.renderer.cfg
+        return float(np.float32(math.log(float(threshold)) - float(cfg.density_bias))), cells * 2.0 * float(cfg.radius) / (int(resolution) - 1)
+
+    def _iso_search(self, caller, threshold, rule, resolution):
+        """What a public method that searches for the iso-surface checks and works out, from rule = (steps, cells) and
+        `resolution` (default: the marching-cubes resolution set last) -> (steps, target, max_dist) with _iso_target's two.
+        The threshold's ValueError comes before the weights are asked for, the resolution's after."""
+        steps, cells = rule
+        if not threshold > 0:
+            raise ValueError("TSR.%s: threshold must be positive, got %r" % (caller, threshold))
+        self._need_weights(caller)
+        if resolution is None:
+            if self.isosurface_helper is None:
+                raise ValueError("TSR.%s: no resolution given and no marching-cubes resolution set yet" % caller)
+            resolution = self.isosurface_helper.resolution
+        if int(resolution) < 2:
+            raise ValueError("TSR.%s: resolution must be at least 2, got %r" % (caller, resolution))
+        return (steps,) + self._iso_target(threshold, cells, resolution)
+
+    def _low_poly_frame(self, v, f, uv):
+        """The tangent frame of the low-poly mesh the normal maps are stored in -> (corner_normals [3*Nf, 3], corner_tangents [3*Nf, 4])."""
+        corner_n = (self.WINDING_OUTWARD * ops.vertex_normals(v, f))[f.reshape(-1).long()].contiguous()
+        return corner_n, ops.corner_tangents(v, f, uv, corner_n)
+
     def bake_normal_map(self, mesh: Mesh, scene_code, resolution=None, space="tangent", island_padding: float = 0.02,
                         unwrapper=None) -> Mesh:
         """The last step of a high-to-low workflow: the surface detail of the density field of `scene_code` ([3, C, H, W]),
@@ -1000,8 +1028,7 @@ class TSR(KernelEngine):
         res = _atlas_resolution(resolution, mesh, "bake_normal_map", ("texture",))
         with torch.no_grad():
             v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper, keep_uvs=True)
-            corner_n = (self.WINDING_OUTWARD * ops.vertex_normals(v, f))[f.reshape(-1).long()].contiguous()
-            corner_t = ops.corner_tangents(v, f, uv, corner_n)
+            corner_n, corner_t = self._low_poly_frame(v, f, uv)
             n, mask = ops.bake_scene_normal(self._field(scene_code), self.decoder, v, f, rast, radius=self.renderer.cfg.radius,
                                             frame=(corner_n, corner_t) if space == "tangent" else None)
             coded = self._coded_normals(n, mask, res, space)
@@ -1026,31 +1053,20 @@ class TSR(KernelEngine):
         values and encoding are exactly those of bake_texture / bake_normal_map.
         -> a Mesh with the input's vertices, faces and what bake_normal_map carries, plus uvs, texture and / or normal_map,
         normal_map_space, corner_normals, corner_tangents, on the device.  texture=False with normal_map=None is a ValueError."""
-        steps, cells = ops.project_rule(project)   # a ValueError before anything is launched
+        rule = ops.project_rule(project)   # a ValueError before anything is launched
         if normal_map is not None and normal_map not in self.NORMAL_MAP_FLAT:
             raise ValueError("TSR.bake_surface_maps: normal_map must be None, 'tangent' or 'object', got %r" % (normal_map,))
         if not texture and normal_map is None:
             raise ValueError("TSR.bake_surface_maps: nothing to bake (texture=False and normal_map=None)")
-        if not threshold > 0:
-            raise ValueError("TSR.bake_surface_maps: threshold must be positive, got %r" % (threshold,))
-        self._need_weights("bake_surface_maps")
-        if resolution is None:
-            if self.isosurface_helper is None:
-                raise ValueError("TSR.bake_surface_maps: no resolution given and no marching-cubes resolution set yet")
-            resolution = self.isosurface_helper.resolution
-        if int(resolution) < 2:
-            raise ValueError("TSR.bake_surface_maps: resolution must be at least 2, got %r" % (resolution,))
+        steps, target, max_dist = self._iso_search("bake_surface_maps", threshold, rule, resolution)
         res = _atlas_resolution(atlas_resolution, mesh, "bake_surface_maps", ("texture", "normal_map"))
         cfg = self.renderer.cfg
-        target = float(np.float32(math.log(float(threshold)) - float(cfg.density_bias)))   # as _projected
-        max_dist = cells * 2.0 * float(cfg.radius) / (int(resolution) - 1)
         with torch.no_grad():
             v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper, keep_uvs=True)
             planes = self._field(scene_code)
             corner_n = corner_t = None
             if normal_map is not None:
-                corner_n = (self.WINDING_OUTWARD * ops.vertex_normals(v, f))[f.reshape(-1).long()].contiguous()
-                corner_t = ops.corner_tangents(v, f, uv, corner_n)
+                corner_n, corner_t = self._low_poly_frame(v, f, uv)
             point, n, mask, _ = ops.bake_surface_route()(planes, self.decoder, v, f, rast, target, max_dist, steps=steps,
                                                          radius=cfg.radius, frame=(corner_n, corner_t) if normal_map == "tangent" else None)
             new = {}
@@ -1085,20 +1101,10 @@ class TSR(KernelEngine):
         displacement=map)."""
         from .displacement import DisplacementMap
 
-        steps, cells = ops.displacement_rule(displacement)   # a ValueError before anything is launched
-        if not threshold > 0:
-            raise ValueError("TSR.bake_displacement_map: threshold must be positive, got %r" % (threshold,))
-        self._need_weights("bake_displacement_map")
-        if resolution is None:
-            if self.isosurface_helper is None:
-                raise ValueError("TSR.bake_displacement_map: no resolution given and no marching-cubes resolution set yet")
-            resolution = self.isosurface_helper.resolution
-        if int(resolution) < 2:
-            raise ValueError("TSR.bake_displacement_map: resolution must be at least 2, got %r" % (resolution,))
+        rule = ops.displacement_rule(displacement)   # a ValueError before anything is launched
+        steps, target, max_dist = self._iso_search("bake_displacement_map", threshold, rule, resolution)
         res = _atlas_resolution(atlas_resolution, mesh, "bake_displacement_map", ("texture", "normal_map", "occlusion_map"))
         cfg = self.renderer.cfg
-        target = float(np.float32(math.log(float(threshold)) - float(cfg.density_bias)))   # as _projected
-        max_dist = cells * 2.0 * float(cfg.radius) / (int(resolution) - 1)
         with torch.no_grad():
             v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper, keep_uvs=True)
             planes = self._field(scene_code)
@@ -1113,7 +1119,7 @@ class TSR(KernelEngine):
         out = mesh if mesh.uvs is not None else mesh._derive(mesh.vertices, mesh.faces,
                                                              ("vertex_colors", "vertex_normals", "vertex_occlusion", "quads"), uvs=uv)
         return out, DisplacementMap(padded, mask, ex["status"], max_dist, evals=ex["evals"], residual0=before, residual=ex["residual"],
-                                    rule=(steps, cells))
+                                    rule=rule)
 
     def _coded_normals(self, n, mask, res, space):
         """A normal image as a map: encoded 0.5 + 0.5 n, padded, the flat value where the padding does not reach."""
@@ -1164,13 +1170,11 @@ class TSR(KernelEngine):
                             uvs=mesh.uvs if mesh.uvs is not None else uv, occlusion_map=ao_map, occlusion_map_rule=rule)
 
     def _projected(self, v_pos, t_pos_idx, planes, threshold, project, resolution):
-        """ops.mesh_project with this model's field: target = float32(ln(threshold) - density_bias) (computed in double),
-        max_dist = cells x the lattice spacing 2 radius / (resolution - 1)."""
+        """ops.mesh_project with this model's field, at _iso_target's target and max_dist (the geometry chain of extract_meshes
+        comes here with its checks made: no _iso_search)."""
         steps, cells = ops.project_rule(project)
-        cfg = self.renderer.cfg
-        target = float(np.float32(math.log(float(threshold)) - float(cfg.density_bias)))
-        max_dist = cells * 2.0 * float(cfg.radius) / (int(resolution) - 1)
-        return ops.mesh_project(planes, self.decoder, v_pos, t_pos_idx, target, max_dist, steps=steps, radius=cfg.radius)[0]
+        target, max_dist = self._iso_target(threshold, cells, resolution)
+        return ops.mesh_project(planes, self.decoder, v_pos, t_pos_idx, target, max_dist, steps=steps, radius=self.renderer.cfg.radius)[0]
 
     def project_mesh(self, mesh: Mesh, scene_code, threshold: float = 25.0, project=True, resolution=None) -> Mesh:
         """`mesh` with its vertices on the iso-surface density_act = threshold of the field of `scene_code` ([3, C, H, W] or an
@@ -1182,15 +1186,9 @@ class TSR(KernelEngine):
         gives the normals of the surface they now lie on).  What extract_meshes(project=...) does as its last geometry step;
         also the way to project the gathered mesh of extract_mesh_sharded.  Nothing waits for the device."""
         steps_cells = ops.project_rule(project)   # a ValueError before anything is launched
-        if not threshold > 0:
-            raise ValueError("TSR.project_mesh: threshold must be positive, got %r" % (threshold,))
-        self._need_weights("project_mesh")
+        self._iso_search("project_mesh", threshold, steps_cells, resolution)   # its ValueErrors too
         if resolution is None:
-            if self.isosurface_helper is None:
-                raise ValueError("TSR.project_mesh: no resolution given and no marching-cubes resolution set yet")
             resolution = self.isosurface_helper.resolution
-        if int(resolution) < 2:
-            raise ValueError("TSR.project_mesh: resolution must be at least 2, got %r" % (resolution,))
         if not isinstance(scene_code, ops.ChannelLastPlanes):
             scene_code = self._field(scene_code, channel_last=False).contiguous()
         with torch.no_grad():

@@ -92,6 +92,40 @@ def test_cpu_tensors_and_bad_parameters_are_refused():
                 fn(planes, None, torch.from_numpy(v), torch.from_numpy(f), rast, target, max_dist)
 
 
+def test_covered_texels_is_the_coverage_rule_of_the_kernels():
+    """ops._covered_texels, the one torch statement of texel_position's coverage (csrc/bake_texel.h), on CPU tensors: a 4 x 4
+    rast over 4 vertices and 2 faces whose tri holds -1, NaN, 2^31, nf, other values out of range, fractions (the kernel
+    truncates) and valid faces; a face that names vertex nv, one that names vertex -1; no face; no vertex.  The masks are
+    written out by hand."""
+    import torch
+
+    from sculptmate_amd import ops
+
+    nan, inf = float("nan"), float("inf")
+    tri = torch.tensor([[0.0, 1.0, -1.0, nan],
+                        [2.0 ** 31, 2.0, 0.0, 1.0],
+                        [1.9, -0.5, inf, 0.0],
+                        [-inf, 3.0, 1.0, 0.0]])
+    rast = torch.cat([torch.tensor([0.2, 0.3, 0.5]).expand(4, 4, 3), tri[..., None]], -1)
+    v = torch.arange(12, dtype=torch.float32).reshape(4, 3)
+    T, F = True, False
+    cases = [
+        ([[0, 1, 2], [0, 2, 3]], v, [[T, T, F, F], [F, F, T, T], [T, F, F, T], [F, F, T, T]]),
+        ([[0, 1, 2], [0, 2, 4]], v, [[T, F, F, F], [F, F, T, F], [F, F, F, T], [F, F, F, T]]),    # face 1 names vertex nv
+        ([[-1, 1, 2], [0, 2, 3]], v, [[F, T, F, F], [F, F, F, T], [T, F, F, F], [F, F, T, F]]),   # face 0 names vertex -1
+        ([], v, [[F] * 4] * 4),                                                                   # nf == 0
+        ([[0, 1, 2], [0, 2, 3]], v[:0], [[F] * 4] * 4),                                           # nv == 0
+    ]
+    for faces, verts, want in cases:
+        for dtype in (torch.int32, torch.int64):
+            f = torch.tensor(faces, dtype=dtype).reshape(-1, 3)
+            covered, clean = ops._covered_texels(rast, verts, f)
+            want_t = torch.tensor(want)
+            assert covered.dtype == torch.bool and torch.equal(covered, want_t)
+            assert clean.is_contiguous() and torch.equal(clean[want_t], rast[want_t])
+            assert torch.equal(clean[~want_t], torch.tensor([0.0, 0.0, 0.0, -1.0]).expand(int((~want_t).sum()), 4))
+
+
 @pytest.fixture(scope="module")
 def octahedron_bake():
     """The fp64 run of the restatement on the octahedron's cell atlas at 37^2 over the smoke field (decoder seed 1,
