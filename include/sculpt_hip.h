@@ -1227,6 +1227,42 @@ int sculpt_surface_weights(const float *P, const int32_t *F, int64_t nf, double 
 int sculpt_surface_sample(const float *P, const int32_t *F, int64_t nf, const int64_t *cdf, int64_t n, unsigned long long seed,
                           float *points, int32_t *face, float *uv, sculpt_stream_t stream);
 
+/* Inside / outside of a triangle surface (csrc/mesh_winding.hip; ops.mesh_winding, ops.mesh_contains, ops.mesh_signed_distance,
+ * ops.mesh_sdf_grid, ops.mesh_voxel_remesh).  Compiled without floating-point contraction and restated bit
+ * for bit in tests/_windref.py.  Added without a version change (new symbols only).  The mesh, the grid, the records and the order
+ * are those of sculpt_surface_closest.
+ *   sculpt_surface_winding          w [n][3] int32: per query Q[i] and axis a, the sum over ALL faces of the signed crossings of
+ *                                   the ray from Q[i] along +a under the watertight rule at the top of csrc/mesh_winding.hip
+ *                                   (box clause, edge signs with a symbolic tie-break, strictly ahead).  A non-finite query:
+ *                                   INT32_MIN three times.  No faces: zeros.  order == records == NULL: the plain form, one
+ *                                   thread per query in input order; otherwise the sorted form.  The same integers either way.
+ *   sculpt_surface_winding_lattice  the same at the points (i0, i1, i2) of a lattice, x_k = (float)(lo_host[k] + i_k h) with the
+ *                                   product and the sum in fp64: planes uint32 [n0 n1][ceil(n2 / 32)], bit i2 % 32 of word
+ *                                   i2 / 32 = at least two of the three counts are nonzero, bits past n2 zero (what
+ *                                   sculpt_mc_count_launch_for takes as sign planes); counts int32 [n0][n1][n2][3], always
+ *                                   written (one launch per axis shares each lattice line's walk; the vote reads them).
+ *                                   records are always needed with gnf > 0.  Each side 1 .. 1024.
+ *   sculpt_lattice_active_corners   the lattice points that are a corner of a cell whose 8 bits are not all equal, as ascending
+ *                                   linear indices (i0 n1 + i1) n2 + i2.  Two calls with the same offsets int32
+ *                                   [sculpt_lattice_active_blocks(n0, n1, n2) + 1]: list == NULL counts and scans (the last word
+ *                                   of offsets is the number of active points, for the caller to read back), list != NULL emits
+ *                                   at most `capacity` indices.
+ *   sculpt_sdf_fill                 vol f32 [n0][n1][n2]: +band / -band at every point by its bit; at listed point list[j] with
+ *                                   squared distance d2[j] (f64): d = (float)fmin(sqrt(d2[j]), band); bit set: d if d > 0 else
+ *                                   2^-126; bit clear: -d.  So (vol > 0) == bit at every lattice point.
+ * Null, misaligned or out-of-range arguments are refused with an error code and a message; n == 0 launches nothing. */
+int sculpt_surface_winding(const float *Q, int64_t n, const int64_t *order, const float *GP, const int32_t *GF, int64_t gnf,
+                           const float *records, const int32_t *items, const int32_t *start, const double *params_host, int32_t *w,
+                           sculpt_stream_t stream);
+int sculpt_surface_winding_lattice(const double *lo_host, double h, int n0, int n1, int n2, const float *GP, const int32_t *GF,
+                                   int64_t gnf, const float *records, const int32_t *items, const int32_t *start,
+                                   const double *params_host, uint32_t *planes, int32_t *counts, sculpt_stream_t stream);
+int64_t sculpt_lattice_active_blocks(int n0, int n1, int n2);
+int sculpt_lattice_active_corners(const uint32_t *planes, int n0, int n1, int n2, int32_t *offsets, int32_t *list, int64_t capacity,
+                                  sculpt_stream_t stream);
+int sculpt_sdf_fill(float *vol, const uint32_t *planes, int n0, int n1, int n2, const int32_t *list, const double *d2, int64_t n,
+                    double band, sculpt_stream_t stream);
+
 /* Rays against a triangle surface (csrc/mesh_ray.hip; ops.mesh_ray_cast, ops.mesh_occlusion).  Compiled
  * without floating-point contraction and restated bit for bit in tests/_rayref.py.  Added without a version change (new symbols
  * only).  The grid, the records, the order and amax are those of sculpt_surface_closest; the grid must cover the surface: lo is

@@ -241,6 +241,11 @@ SIGNATURES = {
     "sculpt_surface_pack": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "sculpt_surface_weights": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "sculpt_surface_sample": (_i, [_vp, _vp, _i64, _vp, _i64, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    "sculpt_surface_winding": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_surface_winding_lattice": (_i, [_vp, _d, _i, _i, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_lattice_active_blocks": (_i64, [_i, _i, _i]),
+    "sculpt_lattice_active_corners": (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "sculpt_sdf_fill": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i64, _d, _vp]),
     "sculpt_surface_ray_cast": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "sculpt_surface_occlusion": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp]),
     "sculpt_bake_occlusion": (_i, [_vp, _i, _vp, _sz, _vp, _i, _sz, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp,

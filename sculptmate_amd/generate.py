@@ -47,6 +47,9 @@ class TripoGenerator(GeneratorFacade):
     of a semi-regular, multires-friendly surface (TSR.extract_meshes; ops.mesh_subdivide).  (n, "catmull_clark") is the
     all-quad scheme of Blender's Subdivision Surface and Multires modifiers: it refines the quads of isosurface="surface_nets",
     or turns every triangle into three quads, and the plain sink receives the refined quads (ops.mesh_catmull_clark).
+    `voxel_remesh` (default None): an int R in 8 .. 1024 (cells along the longest side) or a tuple (R, band_cells) rebuilds every
+    mesh from its inside on a voxel lattice, on the device, after keep_components and before smooth -- Blender's Voxel Remesh:
+    overlapping parts fuse and the holes at the box close (TSR.extract_meshes; ops.mesh_voxel_remesh).
     `isosurface` (default "marching_cubes"): "surface_nets" extracts every mesh with surface nets on the device instead -- one
     vertex inside every cell the surface passes through, an all-quad mesh (Mesh.quads, which the plain Blender sink and
     Mesh.export's .obj receive) beside its triangles, no sliver triangles (TSR.extract_meshes; ops.surface_nets).
@@ -82,6 +85,7 @@ class TripoGenerator(GeneratorFacade):
         self.smooth = None
         self.project = None
         self.subdivide = None
+        self.voxel_remesh = None
         self.occlusion = None
         self.isosurface = "marching_cubes"
         self.normal_map = None
@@ -113,7 +117,7 @@ class TripoGenerator(GeneratorFacade):
                                                        normals=self.vertex_normals, isosurface=self.isosurface,
                                                        keep_components=self.keep_components, simplify=self.simplify,
                                                        smooth=self.smooth, project=self.project, subdivide=self.subdivide,
-                                                       occlusion=self.occlusion)
+                                                       occlusion=self.occlusion, voxel_remesh=self.voxel_remesh)
         except Exception as err:
             print(self.run_error_tag, err)
             return STATUS_FAILED

@@ -931,6 +931,29 @@ class _SurfaceIndex:
                                          _ptr(d2), _ptr(face), _ptr(closest), _stream()))
         return d2, face, closest
 
+    def winding(self, points):
+        """points f32 [N, 3] contiguous, N > 0 -> w int32 [N, 3], the axis winding counts (csrc/mesh_winding.hip)."""
+        n = points.shape[0]
+        w = torch.empty((n, 3), dtype=torch.int32, device=points.device)
+        order, records = self._sorted(points)
+        mesh, grid = self._grid_args()
+        check(lib.sculpt_surface_winding(_ptr(points), n, _ptr(order) if order is not None else None, *mesh,
+                                         _ptr(records) if records is not None else None, *grid[:3], _ptr(w), _stream()))
+        return w
+
+    def winding_lattice(self, lo, h, n, want_counts=False):
+        """The lattice of n = (n0, n1, n2) points lo + i h -> (sign planes int32 [n0 n1][ceil(n2 / 32)], counts int32
+        [n0, n1, n2, 3] or None); no coordinate tensor is made.  The counts are the kernels' meeting place, 12 bytes a point,
+        and are made either way."""
+        dev = self.P.device
+        planes = torch.empty((n[0] * n[1], (n[2] + 31) // 32), dtype=torch.int32, device=dev)
+        counts = torch.empty((n[0], n[1], n[2], 3), dtype=torch.int32, device=dev)
+        mesh, grid = self._grid_args()
+        check(lib.sculpt_surface_winding_lattice((ctypes.c_double * 3)(*lo), float(h), n[0], n[1], n[2], *mesh,
+                                                 _ptr(self.records()) if self.F.shape[0] else None, *grid[:3], _ptr(planes),
+                                                 _ptr(counts), _stream()))
+        return planes, counts if want_counts else None
+
     def _sorted(self, points, always=False):
         """(order, records) of the sorted query form for points f32 [N, 3], or (None, None) for the plain form (unless `always`)
         and for a surface without faces."""
@@ -1105,6 +1128,181 @@ def mesh_distance(vertices_a, faces_a, vertices_b, faces_b, samples=DISTANCE_SAM
         p, q = r[3] / ab.shape[0], r[7] / ba.shape[0]
         out.update(precision=p, recall=q, fscore=2.0 * p * q / (p + q) if p + q > 0 else 0.0)
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# inside / outside: axis winding counts, signed distance, voxel remesh (csrc/mesh_winding.hip)
+# ----------------------------------------------------------------------------------------------
+VOXEL_PAD = 2            # lattice cells around the bounds on every side
+VOXEL_BAND_CELLS = 2     # the default width of the distance band, in cells
+VOXEL_MAX_SIDE = 1024    # lattice points along a side
+
+
+def _inside(w):
+    """The majority vote over the three axis counts (a non-finite query's INT32_MIN marks count as outside)."""
+    return ((w != 0) & (w != -2 ** 31)).sum(1) >= 2
+
+
+def mesh_winding(points, vertices, faces):
+    """The integer winding counts of a triangle mesh around each of N query points along the three coordinate axes, on the
+    device.  points float [N, 3], vertices float [Nv, 3], faces int32 / int64 [Nf, 3] (device tensors; CPU tensors are refused).
+    -> w int32 [N, 3]: w[i, a] = the sum over ALL faces of the signed crossings of the ray from points[i] along +a.
+    Contract (csrc/mesh_winding.hip states the rule; tests/_windref.py restates it by brute force, bit for bit):
+      - positions are fp32 (other float dtypes are converted first), the arithmetic is fp64 without contraction;
+      - a face is crossed when the three edge signs seen along the axis agree (ties broken by a symbolic perturbation that is
+        antisymmetric in the edge's direction, so an edge or vertex under the ray is counted once, not twice or never) and the
+        face lies strictly ahead; the box clause (the query's two other coordinates within the face's bounds) is part of the rule;
+      - a closed surface wound counter-clockwise seen from outside gives +1 inside and 0 outside on every axis, an inward one -1,
+        a surface traversed twice +-2; on an open surface the axes may disagree;
+      - a non-finite query: INT32_MIN three times; no faces: zeros;
+      - a face index out of range and a non-finite vertex are a SculptError; N == 0 launches nothing;
+      - the uniform grid only accelerates; SCULPT_DISTANCE_FORM=plain selects the one-thread-per-query-in-input-order form, the
+        default sorts the queries by grid cell and reads packed face records: the same integers on every input."""
+    pts = _query_points(points, "mesh_winding")
+    P, F = _surface(vertices, faces, "mesh_winding")
+    if pts.shape[0] == 0:
+        return torch.empty((0, 3), dtype=torch.int32, device=pts.device)
+    return _SurfaceIndex(P, F).winding(pts)
+
+
+def mesh_contains(points, vertices, faces):
+    """inside bool [N]: at least two of the three counts of mesh_winding are nonzero -- the majority vote, which ignores the
+    orientation of the faces and outvotes one axis whose ray leaves through a hole.  A non-finite query is outside."""
+    return _inside(mesh_winding(points, vertices, faces))
+
+
+def mesh_signed_distance(points, vertices, faces):
+    """The signed distance of each of N query points to a triangle mesh, on the device: mesh_closest_points' result with the
+    distance negated inside, from ONE surface index.  -> (sd f64 [N], face i64 [N], closest f32 [N, 3]): sd = torch.sqrt(d2),
+    negated where mesh_contains holds; d2 = +inf (no face) and NaN (a non-finite query) pass through the square root."""
+    pts = _query_points(points, "mesh_signed_distance")
+    P, F = _surface(vertices, faces, "mesh_signed_distance")
+    if pts.shape[0] == 0:
+        d2, face, closest = _closest(None, pts)
+        return d2, face, closest
+    index = _SurfaceIndex(P, F)
+    d2, face, closest = _closest(index, pts)
+    sd = torch.sqrt(d2)
+    return torch.where(_inside(index.winding(pts)), -sd, sd), face, closest
+
+
+def mesh_winding_lattice(vertices, faces, lo, h, n, want_counts=False):
+    """mesh_contains at the points of a lattice, generated in the kernel (no [N, 3] tensor is made): lattice point (i0, i1, i2) of
+    n = (n0, n1, n2) lies at (float)(lo_k + i_k h), the product and the sum in fp64.  -> (sign planes int32 [n0 n1][ceil(n2 / 32)]
+    as marching_cubes(sign_planes=) takes them -- bit i2 % 32 of word i2 / 32, bits past n2 zero -- and, with want_counts,
+    mesh_winding's counts int32 [n0, n1, n2, 3], else None).  The same integers as mesh_winding at those coordinates."""
+    if not (len(lo) == 3 and len(n) == 3 and all(_is_real(x) for x in lo) and _is_real(h) and all(_is_count(k, 1, VOXEL_MAX_SIDE) for k in n)):
+        raise ValueError("lo must be three numbers, h a number and n three ints in 1 .. %d, got lo=%r, h=%r, n=%r" % (VOXEL_MAX_SIDE, lo, h, n))
+    P, F = _surface(vertices, faces, "mesh_winding_lattice")
+    return _SurfaceIndex(P, F).winding_lattice([float(x) for x in lo], float(h), [int(k) for k in n], want_counts)
+
+
+def voxel_rule(voxel_remesh):
+    """`voxel_remesh` of mesh_sdf_grid / mesh_voxel_remesh -> (R, band_cells): an int R in 8 .. 1024, the number of cells along
+    the longest side of the bounds, or a tuple (R, band_cells) with band_cells an int in 1 .. 16 (default 2), the width of the
+    distance band on either side of the surface.  Anything else, bool included, is a ValueError -- raised here, before anything is
+    launched."""
+    v = voxel_remesh
+    if _is_count(v, 8, 1024):
+        return int(v), VOXEL_BAND_CELLS
+    if isinstance(v, tuple) and len(v) == 2 and _is_count(v[0], 8, 1024) and _is_count(v[1], 1, 16):
+        return int(v[0]), int(v[1])
+    raise ValueError("voxel_remesh must be an int in 8 .. 1024 (cells along the longest side) or a tuple (that, band cells in "
+                     "1 .. 16), got %r" % (voxel_remesh,))
+
+
+def lattice_active_corners(sign_planes, n):
+    """The lattice points of sign planes int32 / uint32 [n0 n1][ceil(n2 / 32)] that are a corner of a cell whose 8 bits are not
+    all equal -- the points whose value marching cubes reads -- as ascending linear indices int32 [K].  One readback: K."""
+    n0, n1, n2 = n
+    dev = sign_planes.device
+    nb = int(lib.sculpt_lattice_active_blocks(n0, n1, n2))
+    if nb == 0:
+        raise SculptError(_lib.last_error() or "lattice_active_corners: lattice sides must be 1 .. %d" % VOXEL_MAX_SIDE, 2)
+    offsets = torch.empty(nb + 1, dtype=torch.int32, device=dev)
+    check(lib.sculpt_lattice_active_corners(_ptr(sign_planes), n0, n1, n2, _ptr(offsets), None, 0, _stream()))
+    k = int(offsets[-1].item())
+    listed = torch.empty(k, dtype=torch.int32, device=dev)
+    if k:
+        check(lib.sculpt_lattice_active_corners(_ptr(sign_planes), n0, n1, n2, _ptr(offsets), _ptr(listed), k, _stream()))
+    return listed
+
+
+def _lattice_points(listed, lo, h, n):
+    """f32 [K, 3]: the coordinates of the listed lattice points, (float)(lo_k + i_k h) with the product and the sum in fp64."""
+    idx = listed.long()
+    ijk = torch.stack([idx // (n[1] * n[2]), (idx // n[2]) % n[1], idx % n[2]], 1).to(torch.float64)
+    return (torch.tensor(lo, dtype=torch.float64, device=listed.device) + ijk * h).to(torch.float32).contiguous()
+
+
+def _voxel_lattice(index, R, who):
+    """(lo [3], h, n [3]) of the lattice of R cells along the longest side of the index's surface, VOXEL_PAD cells around it."""
+    if index.F.shape[0] == 0:
+        raise SculptError("%s: a mesh without faces has no inside" % who)
+    mn, ext = index.grid.bounds
+    longest = max(ext)
+    if not longest > 0.0:
+        raise SculptError("%s: the mesh's bounds have no extent" % who)
+    h = longest / R
+    lo = [mn[k] - VOXEL_PAD * h for k in range(3)]
+    n = [int(math.ceil(ext[k] / h)) + 1 + 2 * VOXEL_PAD for k in range(3)]
+    if max(n) > VOXEL_MAX_SIDE:
+        raise SculptError("%s: a lattice of %d x %d x %d points (at most %d a side)" % (who, n[0], n[1], n[2], VOXEL_MAX_SIDE))
+    return lo, h, n
+
+
+def _sdf_fill(planes, listed, d2, n, band):
+    """vol f32 [n0, n1, n2] of sculpt_sdf_fill: +-band by the planes' bits, the clamped signed distance at the listed points."""
+    vol = torch.empty(tuple(n), dtype=torch.float32, device=planes.device)
+    k = listed.shape[0]
+    check(lib.sculpt_sdf_fill(_ptr(vol), _ptr(planes), n[0], n[1], n[2], _ptr(listed) if k else None, _ptr(d2) if k else None, k,
+                              float(band), _stream()))
+    return vol
+
+
+def _sdf_grid(P, F, R, band_cells, who):
+    index = _SurfaceIndex(P, F)
+    lo, h, n = _voxel_lattice(index, R, who)
+    planes, _ = index.winding_lattice(lo, h, n)
+    listed = lattice_active_corners(planes, n)
+    d2 = index.closest(_lattice_points(listed, lo, h, n))[0] if listed.shape[0] else None
+    return _sdf_fill(planes, listed, d2, n, band_cells * h), planes, listed, lo, h
+
+
+def mesh_sdf_grid(vertices, faces, voxel_remesh):
+    """A banded signed-distance volume of a triangle mesh over a voxel lattice, positive INSIDE, on the device.  vertices float
+    [Nv, 3], faces int32 / int64 [Nf, 3] (device tensors); voxel_remesh: voxel_rule's R or (R, band_cells).
+    -> (vol f32 [n0, n1, n2], sign_planes int32 [n0 n1][ceil(n2 / 32)], lo [3] Python floats, h):
+      - h = longest side of the bounds / R in fp64; two cells of padding: lo_k = min_k - 2 h, n_k = ceil(extent_k / h) + 5;
+        lattice point (i0, i1, i2) lies at (float)(lo_k + i_k h);
+      - sign_planes: bit i2 % 32 of word i2 / 32 = mesh_contains at that point (generated in the kernel, no coordinate tensor),
+        what marching_cubes(sign_planes=) takes;
+      - vol: +band / -band by the bit, band = band_cells h; at the corners of the cells the surface passes through (the only
+        values marching cubes reads) the distance of mesh_closest_points, clamped to the band and signed by the bit, and never
+        zero inside: (vol > 0) == bit at EVERY lattice point;
+      - a mesh without faces, bounds without extent and a lattice side above 1024 points are a SculptError.
+    The closest-point query runs over the listed corners only.  Readbacks: the input check's status, the grid's two small results
+    and the length of the corner list."""
+    R, band_cells = voxel_rule(voxel_remesh)
+    P, F = _surface(vertices, faces, "mesh_sdf_grid")
+    vol, planes, _, lo, h = _sdf_grid(P, F, R, band_cells, "mesh_sdf_grid")
+    return vol, planes, lo, h
+
+
+def mesh_voxel_remesh(vertices, faces, voxel_remesh):
+    """Voxel remesh on the device: the mesh's inside, sampled on a lattice of R cells along the longest side (mesh_sdf_grid), and
+    marching cubes of that volume at level 0 -- overlapping parts fuse into one surface, holes narrower than the majority vote
+    can see through close, and the result is one clean surface at the lattice's resolution.
+    -> (vertices f32 [Nv', 3], faces i64 [Nf', 3]): marching_cubes(vol, 0.0, reference_order=True, sign_planes=planes) in lattice
+    units, then v h + lo in fp32 (the product, then the sum).  The volume is positive inside, as extract_meshes feeds marching
+    cubes, so the faces wind outward.  A mesh the lattice sees no inside of raises marching cubes' RuntimeError."""
+    R, band_cells = voxel_rule(voxel_remesh)
+    P, F = _surface(vertices, faces, "mesh_voxel_remesh")
+    vol, planes, _, lo, h = _sdf_grid(P, F, R, band_cells, "mesh_voxel_remesh")
+    v, f = marching_cubes(vol, 0.0, reference_order=True, sign_planes=planes)
+    h32 = torch.tensor(h, dtype=torch.float64, device=v.device).to(torch.float32)
+    lo32 = torch.tensor(lo, dtype=torch.float64, device=v.device).to(torch.float32)
+    return (v * h32) + lo32, f
 
 
 # ----------------------------------------------------------------------------------------------

@@ -291,11 +291,13 @@ class _Grid:
             self.params = (ctypes.c_double * 7)(0, 0, 0, 1, 1, 1, 1)
             self.items = self.start = None
             self.amax = self.longest = 0.0
+            self.bounds = None
             return
         pts = GP[GF.reshape(-1).long()].to(torch.float64)
         lo, hi = pts.min(0).values, pts.max(0).values
         b = ctx.read(lo[0:1], lo[1:2], lo[2:3], hi[0:1], hi[1:2], hi[2:3])
         lo3, ext = b[:3], [b[3 + k] - b[k] for k in range(3)]
+        self.bounds = (lo3, ext)  # least corner and extent over the vertices the faces name (ops.mesh_sdf_grid)
         self.amax = max(abs(x) for x in b)  # the largest |coordinate| of the surface (ops.mesh_closest_points)
         self.longest = longest = max(ext)  # the longest side of the bounds (ops.mesh_occlusion's default offset)
         per_side = max(1.0, min(math.sqrt(nf / 2.0), (4.0 * nf) ** (1.0 / 3.0)))

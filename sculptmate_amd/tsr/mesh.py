@@ -32,7 +32,7 @@ class Mesh:
     the extractor's faces (FACE_FIELDS): quads int [Nq, 4], the all-quad mesh over the same vertices that
       extract_meshes(isosurface="surface_nets") adds, while `faces` are still the extractor's -- faces[2q], faces[2q + 1] are
       quad q split along its shorter diagonal.  smooth and project keep it (faces and vertex numbering stay); keep_components,
-      simplify and the triangle schemes of subdivide (Loop, midpoint) make new faces and drop it; subdivide with
+      voxel_remesh, simplify and the triangle schemes of subdivide (Loop, midpoint) make new faces and drop it; subdivide with
       (n, "catmull_clark") sets it anew, to the refined quads, on any mesh.
     A step that makes one mesh from another names what it carries over (_derive); what it does not name is None on its result."""
 
@@ -142,6 +142,31 @@ class Mesh:
         and F-score.  samples=None measures from the meshes' own vertices: what an option such as smooth or simplify did to the
         surface, without sampling noise."""
         return ops.mesh_distance(self.vertices, self.faces, other.vertices, other.faces, samples=samples, seed=seed, threshold=threshold)
+
+    def winding_number(self, points):
+        """The integer winding counts of this mesh around each point along the three coordinate axes (ops.mesh_winding on its
+        device tensors; host arrays are refused like any CPU tensor) -> int32 [N, 3]: +1 inside a closed surface wound outward,
+        0 outside, on every axis."""
+        return ops.mesh_winding(points, self.vertices, self.faces)
+
+    def contains(self, points):
+        """Which points lie inside this mesh (ops.mesh_contains) -> bool [N]: at least two of the three axis counts nonzero."""
+        return ops.mesh_contains(points, self.vertices, self.faces)
+
+    def signed_distance(self, points):
+        """The distance of each point to this mesh, negative inside (ops.mesh_signed_distance)
+        -> (sd f64 [N], face i64 [N], closest f32 [N, 3])."""
+        return ops.mesh_signed_distance(points, self.vertices, self.faces)
+
+    def voxel_remesh(self, voxel_remesh) -> "Mesh":
+        """The mesh rebuilt from its inside on a voxel lattice (ops.mesh_voxel_remesh): voxel_remesh = an int R in 8 .. 1024
+        (cells along the longest side of the bounds) or a tuple (R, band_cells) (ops.voxel_rule).  Overlapping parts fuse, the
+        holes where the extractor met the box close, and smooth, simplify and subdivide get one clean closed surface to work on.
+        The step makes new vertices and new faces, so it carries nothing over: vertex_colors, vertex_normals and
+        vertex_occlusion, `quads`, uvs and every baked map are dropped (TSR.extract_meshes(voxel_remesh=...) evaluates colours
+        and normals at the final vertices instead)."""
+        v, f = ops.mesh_voxel_remesh(self.vertices, self.faces, voxel_remesh)
+        return self._derive(v, f)
 
     def ray_cast(self, origins, directions, t_min=0.0, t_max=math.inf):
         """The closest face of this mesh that each ray hits (ops.mesh_ray_cast on its device tensors; host arrays are refused
