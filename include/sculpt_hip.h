@@ -1263,6 +1263,43 @@ int sculpt_lattice_active_corners(const uint32_t *planes, int n0, int n1, int n2
 int sculpt_sdf_fill(float *vol, const uint32_t *planes, int n0, int n1, int n2, const int32_t *list, const double *d2, int64_t n,
                     double band, sculpt_stream_t stream);
 
+/* The mesh report (csrc/mesh_report.hip; ops.mesh_report, ops.mesh_self_intersections).  Compiled without
+ * floating-point contraction and restated in tests/_reportref.py.  Added without a version change (new symbols only).
+ *   sculpt_mesh_edge_census     counts int64 [8] on the device, over the undirected sorted half-edge keys of `topo`: [0] edges,
+ *                               [1] border edges (1 half-edge), [2] non-manifold edges (>= 3), [3] inconsistently wound edges
+ *                               (exactly 2 half-edges that start at the same vertex), [4] vertices named by at least one face,
+ *                               [5 .. 7] zero.  A face with a repeated index contributes its half-edges like any other,
+ *                               self-loops included.  Integer atomics, one per workgroup and figure: exact in any order.
+ *   sculpt_mesh_face_measures   per face with corners a, b, c (fp32 widened to fp64): area2 [nf] f64 = |cross(b - a, c - a)|
+ *                               (sculpt_surface_weights' value, bit for bit), vol6 [nf] f64 = (a0 (b1 c2 - b2 c1) - a1 (b0 c2 -
+ *                               b2 c0)) + a2 (b0 c1 - b1 c0); *n_degenerate (int64 on the device, zeroed by the call) = the faces
+ *                               that repeat an index or have area2 == 0.
+ *   sculpt_surface_self_count   the pairs of faces i < j that intersect under the rule at the top of csrc/mesh_report.hip:
+ *                               orient(a, b, c, d) of four vertex indices is 0 when two are equal and else the sign of the fp64
+ *                               determinant (u0 (v1 w2 - v2 w1) - u1 (v0 w2 - v2 w0)) + u2 (v0 w1 - v1 w0) of u, v, w = P[b], P[c],
+ *                               P[d] - P[a]; a segment (p, q) meets a triangle (a, b, c) when orient(a, b, c, p) orient(a, b, c,
+ *                               q) < 0 and orient(p, q, a, b), orient(p, q, b, c), orient(p, q, c, a) are all >= 0 or all <= 0 and
+ *                               not all zero; faces intersect when their fp32 boxes overlap (closed) and an edge of one meets
+ *                               the other.  n [gnf] int32 = the number of j > i that intersect i; flag [gnf] uint8, zeroed by
+ *                               the CALLER, gets 1 at both faces of every pair.  The mesh, the grid and the records are those
+ *                               of sculpt_surface_closest; the grid only skips pairs, and a pair is tested once, in the first
+ *                               cell its two boxes share.  order == records == NULL: the plain form, one thread per face in
+ *                               input order; otherwise order int64 [gnf] is a permutation of the faces (by first cell) and the
+ *                               boxes come from the records.  The same integers either way.
+ *   sculpt_surface_self_emit    the same walk; offsets int64 [gnf + 1] = the exclusive scan of n with the total last; writes
+ *                               keys[offsets[i] ..] = i << 32 | j, never at or past min(offsets[i + 1], capacity).  The order of
+ *                               one face's keys is unspecified: the caller sorts.
+ * Null, misaligned or out-of-range arguments are refused with an error code and a message; no faces launches nothing. */
+int sculpt_mesh_edge_census(const sculpt_rmd_topo_t *topo, int64_t *counts, sculpt_stream_t stream);
+int sculpt_mesh_face_measures(const float *P, const int32_t *F, int64_t nf, double *area2, double *vol6, int64_t *n_degenerate,
+                              sculpt_stream_t stream);
+int sculpt_surface_self_count(const float *GP, const int32_t *GF, int64_t gnf, const int64_t *order, const float *records,
+                              const int32_t *items, const int32_t *start, const double *params_host, int32_t *n, uint8_t *flag,
+                              sculpt_stream_t stream);
+int sculpt_surface_self_emit(const float *GP, const int32_t *GF, int64_t gnf, const int64_t *order, const float *records,
+                             const int32_t *items, const int32_t *start, const double *params_host, const int64_t *offsets,
+                             int64_t *keys, int64_t capacity, sculpt_stream_t stream);
+
 /* Rays against a triangle surface (csrc/mesh_ray.hip; ops.mesh_ray_cast, ops.mesh_occlusion).  Compiled
  * without floating-point contraction and restated bit for bit in tests/_rayref.py.  Added without a version change (new symbols
  * only).  The grid, the records, the order and amax are those of sculpt_surface_closest; the grid must cover the surface: lo is

@@ -246,6 +246,10 @@ SIGNATURES = {
     "sculpt_lattice_active_blocks": (_i64, [_i, _i, _i]),
     "sculpt_lattice_active_corners": (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "sculpt_sdf_fill": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i64, _d, _vp]),
+    "sculpt_mesh_edge_census": (_i, [_vp, _vp, _vp]),
+    "sculpt_mesh_face_measures": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "sculpt_surface_self_count": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_surface_self_emit": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sculpt_surface_ray_cast": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "sculpt_surface_occlusion": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp]),
     "sculpt_bake_occlusion": (_i, [_vp, _i, _vp, _sz, _vp, _i, _sz, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp,

@@ -50,6 +50,9 @@ class TripoGenerator(GeneratorFacade):
     `voxel_remesh` (default None): an int R in 8 .. 1024 (cells along the longest side) or a tuple (R, band_cells) rebuilds every
     mesh from its inside on a voxel lattice, on the device, after keep_components and before smooth -- Blender's Voxel Remesh:
     overlapping parts fuse and the holes at the box close (TSR.extract_meshes; ops.mesh_voxel_remesh).
+    `report` (default None): True leaves what every final mesh is -- edge census, watertight, Euler number, genus, area, volume
+    -- at `model.last_reports`, one dict per image, computed on the device before the hand-off; "full" adds the number of
+    self-intersecting face pairs (TSR.extract_meshes; ops.mesh_report).  The meshes themselves do not change.
     `isosurface` (default "marching_cubes"): "surface_nets" extracts every mesh with surface nets on the device instead -- one
     vertex inside every cell the surface passes through, an all-quad mesh (Mesh.quads, which the plain Blender sink and
     Mesh.export's .obj receive) beside its triangles, no sliver triangles (TSR.extract_meshes; ops.surface_nets).
@@ -87,6 +90,7 @@ class TripoGenerator(GeneratorFacade):
         self.subdivide = None
         self.voxel_remesh = None
         self.occlusion = None
+        self.report = None
         self.isosurface = "marching_cubes"
         self.normal_map = None
         self.occlusion_map = None
@@ -117,7 +121,8 @@ class TripoGenerator(GeneratorFacade):
                                                        normals=self.vertex_normals, isosurface=self.isosurface,
                                                        keep_components=self.keep_components, simplify=self.simplify,
                                                        smooth=self.smooth, project=self.project, subdivide=self.subdivide,
-                                                       occlusion=self.occlusion, voxel_remesh=self.voxel_remesh)
+                                                       occlusion=self.occlusion, voxel_remesh=self.voxel_remesh,
+                                                       report=self.report)
         except Exception as err:
             print(self.run_error_tag, err)
             return STATUS_FAILED

@@ -6,6 +6,7 @@ passes raw device pointers + sizes into libsculpt_hip.so.  No function has a CPU
 import ctypes
 import math
 import numbers
+import struct
 import threading
 import os
 
@@ -1303,6 +1304,144 @@ def mesh_voxel_remesh(vertices, faces, voxel_remesh):
     h32 = torch.tensor(h, dtype=torch.float64, device=v.device).to(torch.float32)
     lo32 = torch.tensor(lo, dtype=torch.float64, device=v.device).to(torch.float32)
     return (v * h32) + lo32, f
+
+
+# ----------------------------------------------------------------------------------------------
+# the mesh report: edge census, area and volume, self-intersections (csrc/mesh_report.hip)
+# ----------------------------------------------------------------------------------------------
+SELF_MAX_PAIRS = 1 << 26   # the default bound on an emitted pair list (8 bytes a pair)
+
+
+def _self_intersections(P, F, pairs, max_pairs):
+    """(count, flagged faces, flag uint8 [Nf], pairs int64 [count, 2] or None) of a checked surface with Nf > 0: count, scan, ONE
+    readback of the two totals, emit."""
+    dev, nf = P.device, F.shape[0]
+    index = _SurfaceIndex(P, F)
+    order = records = None
+    if not _lib.form_has("SCULPT_DISTANCE_FORM", "plain"):
+        records = index.records()
+        key = torch.empty(nf, dtype=torch.int32, device=dev)
+        check(lib.sculpt_surface_cells(_ptr(records[:, :3].contiguous()), nf, index.grid.params, _ptr(key), _stream()))   # the box's least corner
+        order = torch.sort(key, stable=True).indices
+    mesh, grid = index._grid_args()
+    form = (_ptr(order) if order is not None else None, _ptr(records) if records is not None else None)
+    n = torch.empty(nf, dtype=torch.int32, device=dev)
+    flag = torch.zeros(nf, dtype=torch.uint8, device=dev)
+    check(lib.sculpt_surface_self_count(*mesh, *form, *grid[:3], _ptr(n), _ptr(flag), _stream()))
+    offsets = torch.zeros(nf + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(n, 0, dtype=torch.int64)
+    total, flagged = torch.stack([offsets[-1], flag.sum()]).tolist()
+    if not pairs:
+        return total, flagged, flag, None
+    if total > max_pairs:
+        raise SculptError("mesh_self_intersections: %d intersecting pairs exceed max_pairs=%d" % (total, max_pairs))
+    keys = torch.empty(total, dtype=torch.int64, device=dev)
+    if total:
+        check(lib.sculpt_surface_self_emit(*mesh, *form, *grid[:3], _ptr(offsets), _ptr(keys), total, _stream()))
+        keys = torch.sort(keys).values
+    return total, flagged, flag, torch.stack([keys >> 32, keys & 0xFFFFFFFF], 1)
+
+
+def mesh_self_intersections(vertices, faces, pairs=False, max_pairs=SELF_MAX_PAIRS):
+    """Which faces of a triangle mesh pass through each other, on the device.  vertices float [Nv, 3], faces int32 / int64
+    [Nf, 3] (device tensors; CPU tensors are refused).
+    -> {"count": the number of intersecting pairs i < j, "faces": bool [Nf] -- the face is in at least one pair, "pairs": int64
+    [count, 2] in lexicographic order with pairs=True, else None}.
+    Contract (csrc/mesh_report.hip states the rule; tests/_reportref.py restates it by brute force over all pairs):
+      - positions are fp32 (other float dtypes are converted first), the arithmetic is fp64 without contraction;
+      - orient of four vertex INDICES is 0 when two are equal, else the sign of a 3 x 3 determinant; a segment meets a closed
+        triangle when its ends lie strictly on opposite sides of the plane and the three edge signs agree (zeros allowed, not
+        all zero); two faces intersect when their fp32 boxes overlap (closed) and an edge of one meets the other.  Faces that
+        share a vertex or an edge therefore do not count by that alone, and there is no adjacency special case;
+      - coplanar overlaps are not reported; a soup that repeats positions under different indices is judged by the arithmetic
+        alone; geometric truth holds where the arithmetic is exact (small-integer coordinates);
+      - pairs=True with more than max_pairs pairs is a SculptError, raised before the pair list is allocated;
+      - a face index out of range and a non-finite vertex are a SculptError; Nf == 0 launches nothing;
+      - the uniform grid only skips pairs, and each pair is tested once; SCULPT_DISTANCE_FORM=plain selects the
+        one-thread-per-face-in-input-order form, the default walks the faces in the order of their first cell and reads the
+        boxes from packed records: the same integers on every input, and the same tensors on every run;
+      - the host reads back the input check (the index range and the status), the grid's two small results (bounds, list
+        length) and the pair total with the number of flagged faces."""
+    if not (_is_count(max_pairs, 0) and isinstance(pairs, (bool, np.bool_))):
+        raise ValueError("pairs must be a bool and max_pairs an int >= 0, got pairs=%r, max_pairs=%r" % (pairs, max_pairs))
+    P, F = _surface(vertices, faces, "mesh_self_intersections")
+    if F.shape[0] == 0:
+        return {"count": 0, "faces": torch.zeros(0, dtype=torch.bool, device=P.device),
+                "pairs": torch.zeros((0, 2), dtype=torch.int64, device=P.device) if pairs else None}
+    total, _, flag, plist = _self_intersections(P, F, bool(pairs), int(max_pairs))
+    return {"count": total, "faces": flag.bool(), "pairs": plist}
+
+
+def mesh_face_measures(vertices, faces):
+    """(area2 f64 [Nf], vol6 f64 [Nf]) of a device mesh: twice the area and six times the signed volume under the origin of every
+    face, in fp64 on the fp32 positions (csrc/mesh_report.hip): area = sum(area2) / 2, volume = sum(vol6) / 6."""
+    P, F = _surface(vertices, faces, "mesh_face_measures")
+    return _face_measures(P, F, torch.zeros(1, dtype=torch.int64, device=P.device))[:2]
+
+
+def _face_measures(P, F, n_degenerate):
+    nf = F.shape[0]
+    area2 = torch.empty(nf, dtype=torch.float64, device=P.device)
+    vol6 = torch.empty(nf, dtype=torch.float64, device=P.device)
+    check(lib.sculpt_mesh_face_measures(_ptr(P) if nf else None, _ptr(F) if nf else None, nf, _ptr(area2) if nf else None,
+                                        _ptr(vol6) if nf else None, _ptr(n_degenerate), _stream()))
+    return area2, vol6
+
+
+def mesh_report(vertices, faces, self_intersections=True):
+    """What a triangle mesh is, asked on the device: the figures a caller wants before sculpting, printing or choosing
+    voxel_remesh=.  vertices float [Nv, 3], faces int32 / int64 [Nf, 3] (device tensors; CPU tensors are refused).
+    -> a plain dict of Python numbers and bools:
+        vertices, faces          Nv, Nf
+        referenced_vertices      vertices named by at least one face
+        edges, border_edges, nonmanifold_edges, inconsistent_edges
+                                 over the undirected edges: 1 face, >= 3 faces, exactly 2 faces that traverse it in the SAME
+                                 direction (a face with a repeated index contributes its half-edges like any other)
+        degenerate_faces         a repeated index, or area2 == 0
+        components               connected components that have a face (ops.mesh_components' labelling)
+        euler                    referenced_vertices - edges + faces
+        is_watertight            faces > 0 and border_edges == 0 and nonmanifold_edges == 0
+        is_winding_consistent    inconsistent_edges == 0 and nonmanifold_edges == 0
+        genus                    (2 components - euler) // 2 when watertight, consistent and that is a non-negative integer, else None
+        area, volume             sum |cross(b - a, c - a)| / 2 and sum det(a, b, c) / 6, per face in fp64 (csrc/mesh_report.hip),
+                                 summed by torch.sum in fp64 (the order of the sum is not pinned)
+        is_volume                watertight, consistent and volume > 0
+      and with self_intersections=True (mesh_self_intersections' rule):
+        self_intersections       the number of intersecting pairs of faces
+        self_intersecting_faces  the number of faces in at least one pair
+    Nf == 0 launches nothing after the input check.  Host readbacks: the input check's three (the index range's two ends and the
+    status), the topology's edge count, one for the census with the degenerate count and the two sums, one for the components'
+    counts, and with self_intersections the grid's two (bounds, list length) and the pair total."""
+    from .sf3d import remesh_device as rmd
+
+    P, F = _surface(vertices, faces, "mesh_report")
+    nv, nf, dev = P.shape[0], F.shape[0], P.device
+    r = {"vertices": nv, "faces": nf, "referenced_vertices": 0, "edges": 0, "border_edges": 0, "nonmanifold_edges": 0,
+         "inconsistent_edges": 0, "degenerate_faces": 0, "components": 0}
+    area2_sum = vol6_sum = 0.0
+    if nf:
+        topo = rmd._Topo(rmd._Ctx(), F, nv)
+        counts = torch.empty(8, dtype=torch.int64, device=dev)
+        check(lib.sculpt_mesh_edge_census(topo.ref(), _ptr(counts), _stream()))
+        area2, vol6 = _face_measures(P, F, counts[5:6])   # after the census, which zeroes all eight words
+        sums = torch.stack([area2.sum(), vol6.sum()])
+        words = torch.cat([counts, sums.view(torch.int64)]).tolist()   # ONE readback: six integers and the bits of two doubles
+        (r["edges"], r["border_edges"], r["nonmanifold_edges"], r["inconsistent_edges"], r["referenced_vertices"],
+         r["degenerate_faces"]) = words[:6]
+        area2_sum, vol6_sum = struct.unpack("<2d", struct.pack("<2q", *words[8:10]))
+        # a vertex no face names is a component of its own without a face: the others all have one
+        r["components"] = _cc_launch(F, nv, _lib.CC_KEEP_NONE, 0, 0.0)[1][0] - (nv - r["referenced_vertices"])
+    r["euler"] = r["referenced_vertices"] - r["edges"] + nf
+    r["is_watertight"] = nf > 0 and r["border_edges"] == 0 and r["nonmanifold_edges"] == 0
+    r["is_winding_consistent"] = r["inconsistent_edges"] == 0 and r["nonmanifold_edges"] == 0
+    g2 = 2 * r["components"] - r["euler"]
+    r["genus"] = g2 // 2 if r["is_watertight"] and r["is_winding_consistent"] and g2 >= 0 and g2 % 2 == 0 else None
+    r["area"] = area2_sum / 2.0
+    r["volume"] = vol6_sum / 6.0
+    r["is_volume"] = bool(r["is_watertight"] and r["is_winding_consistent"] and r["volume"] > 0)
+    if self_intersections:
+        r["self_intersections"], r["self_intersecting_faces"] = _self_intersections(P, F, False, 0)[:2] if nf else (0, 0)
+    return r
 
 
 # ----------------------------------------------------------------------------------------------

@@ -168,6 +168,38 @@ class Mesh:
         v, f = ops.mesh_voxel_remesh(self.vertices, self.faces, voxel_remesh)
         return self._derive(v, f)
 
+    def report(self, self_intersections=True) -> dict:
+        """What this mesh is (ops.mesh_report on its device tensors; host arrays are refused like any CPU tensor): the edge
+        census, Euler number, genus, area, volume and -- with self_intersections -- how many pairs of faces pass through each
+        other.  A plain dict, computed on every call: no field of the mesh, nothing is stored."""
+        return ops.mesh_report(self.vertices, self.faces, self_intersections=self_intersections)
+
+    def self_intersections(self, pairs=False) -> dict:
+        """Which faces of this mesh pass through each other (ops.mesh_self_intersections)
+        -> {"count", "faces": bool [Nf], "pairs": int64 [count, 2] or None}."""
+        return ops.mesh_self_intersections(self.vertices, self.faces, pairs=pairs)
+
+    # trimesh's names, computed on demand from report(self_intersections=False); never cached
+    @property
+    def is_watertight(self) -> bool:
+        return self.report(False)["is_watertight"]
+
+    @property
+    def is_winding_consistent(self) -> bool:
+        return self.report(False)["is_winding_consistent"]
+
+    @property
+    def euler_number(self) -> int:
+        return self.report(False)["euler"]
+
+    @property
+    def area(self) -> float:
+        return self.report(False)["area"]
+
+    @property
+    def volume(self) -> float:
+        return self.report(False)["volume"]
+
     def ray_cast(self, origins, directions, t_min=0.0, t_max=math.inf):
         """The closest face of this mesh that each ray hits (ops.mesh_ray_cast on its device tensors; host arrays are refused
         like any CPU tensor) -> (t f64 [N], face i64 [N], uv f32 [N, 2]); no hit: t = +inf, face = -1."""

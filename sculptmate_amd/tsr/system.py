@@ -965,6 +965,8 @@ class TSR(KernelEngine):
     # was made without __init__
     occlusion_map = None
     _occlusion_source = None
+    # None until a call of extract_meshes(report=True | "full"), then one ops.mesh_report dict per image of that call
+    last_reports = None
     # None | what ops.project_rule accepts (True, n, (n, cells)): when set, extract_meshes bakes the texture, and the normal map when
     # self.normal_map is set, AT THE SURFACE (bake_surface_maps) with its own threshold and resolution.  None: nothing new is launched
     bake_project = None
@@ -1199,8 +1201,8 @@ class TSR(KernelEngine):
 
     def extract_meshes(self, scene_codes, enable_texture=False, resolution: int = 256, threshold: float = 25.0,
                        x_range=None, density_events=None, bake_texture: int = 0, normals=None, isosurface="marching_cubes",
-                       keep_components=None, voxel_remesh=None, simplify=None, smooth=None, project=None, subdivide=None,
-                       occlusion=None) -> List[Mesh]:
+                       keep_components=None, voxel_remesh=None, report=None, simplify=None, smooth=None, project=None,
+                       subdivide=None, occlusion=None) -> List[Mesh]:
         """The arithmetic of system.py:171-200 without the Blender sink: returns device tensors.
         density_events: optional (start, stop) torch events recorded around the dense-grid launch (bench.py's live
         per-launch timing of the dominant kernel, on the stream it is launched on).
@@ -1268,7 +1270,14 @@ class TSR(KernelEngine):
         kernel (ops.mesh_occlusion) over the mesh's own grid.  Not a geometry step: it is computed with the colours and the
         normals, after the geometry chain, and changes no vertex and no face.  run, run_async, run_batched, run_pipelined,
         batch.run_sharded and extract_mesh_sharded do not take the option yet (their host hand-off copies four arrays): call
-        Mesh.ambient_occlusion on a device mesh instead."""
+        Mesh.ambient_occlusion on a device mesh instead.
+        report: None (default): nothing is launched, nothing changes.  True leaves self.last_reports, one dict per image: what
+        each FINAL device mesh is (ops.mesh_report without self-intersections: edge census, Euler number, genus, area, volume),
+        computed after everything else and before the hand-off; "full" adds the self-intersection count.  The returned meshes
+        are bit for bit those of the call without the keyword.  Pass it by keyword: it stands with the keywords the other
+        entry points do not take yet, so that the tail of the signature stays (..., subdivide, occlusion)."""
+        if not (report is None or report is True or (isinstance(report, str) and report == "full")):
+            raise ValueError("report must be None, True or 'full', got %r" % (report,))
         if normals not in (None, "field", "faces"):
             raise ValueError("normals must be None, 'field' or 'faces', got %r" % (normals,))
         ops.isosurface_rule(isosurface)   # a ValueError before anything is launched
@@ -1292,6 +1301,8 @@ class TSR(KernelEngine):
         r = self.renderer.cfg.radius
         R = resolution
         out = []
+        if report is not None:
+            self.last_reports = []
         quads_of = {}   # what the surface-nets extractor leaves beside the (vertices, faces) that _extract_filtered hands on
         if isosurface == "surface_nets":
             def mc(v, sign_planes=None):
@@ -1325,6 +1336,8 @@ class TSR(KernelEngine):
                 out[-1].quads = quads
             elif catmull_clark:   # the faces are the split of the refined quads
                 out[-1].quads = refined
+            if report is not None:
+                self.last_reports.append(ops.mesh_report(out[-1].vertices, out[-1].faces, self_intersections=report == "full"))
         return out
 
     @staticmethod
@@ -1523,8 +1536,8 @@ class TSR(KernelEngine):
 
     def extract_mesh(self, scene_codes, enable_texture=False, mesh_name="NewMesh", resolution: int = 256,
                      threshold: float = 25.0, bake_texture: int = 0, normals=None, isosurface="marching_cubes", keep_components=None,
-                     voxel_remesh=None, simplify=None, smooth=None, project=None, subdivide=None, occlusion=None):
-        """system.py:171-200: same signature (+ bake_texture, normals, occlusion and the geometry options keep_components, voxel_remesh,
+                     voxel_remesh=None, report=None, simplify=None, smooth=None, project=None, subdivide=None, occlusion=None):
+        """system.py:171-200: same signature (+ bake_texture, normals, occlusion, report and the geometry options keep_components, voxel_remesh,
         smooth, simplify, subdivide, project, all described at extract_meshes: the sink receives the final mesh); pushes each mesh into the sink (Blender when
         `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
         the textured sink (per-loop UVs + an image-texture material; with self.normal_map = "tangent" also normal_image=, the
@@ -1534,7 +1547,7 @@ class TSR(KernelEngine):
         textured sink stays on triangles, which its per-corner UVs belong to."""
         meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture, normals=normals,
                                      isosurface=isosurface, keep_components=keep_components, simplify=simplify, smooth=smooth, project=project,
-                                     subdivide=subdivide, occlusion=occlusion, voxel_remesh=voxel_remesh)
+                                     subdivide=subdivide, occlusion=occlusion, voxel_remesh=voxel_remesh, report=report)
         sink = self.mesh_sink or _default_sink()
         for m in meshes:
             if m.texture is not None:
