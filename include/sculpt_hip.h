@@ -1300,6 +1300,51 @@ int sculpt_surface_self_emit(const float *GP, const int32_t *GF, int64_t gnf, co
                              const int32_t *items, const int32_t *start, const double *params_host, const int64_t *offsets,
                              int64_t *keys, int64_t capacity, sculpt_stream_t stream);
 
+/* Fill holes (csrc/mesh_holes.hip; ops.mesh_border_loops, ops.mesh_fill_holes).  The rule stands at the top
+ * of csrc/mesh_holes.hip and is restated in tests/_holesref.py.  Compiled without floating-point contraction; everything up to the
+ * centroids is integers.  Added without a version change (new symbols only).  All arrays are on the device; nb is the number of
+ * border half-edges (the caller reads it from the scan of `flag`), and a "list index" is a position in their ascending list.
+ *   sculpt_mesh_border_mark      flag int32 [3 nf] = 1 at the one half-edge of every edge that has exactly one; vout, vin int32 [nv]
+ *                                = how many of them start / end at the vertex; start_of int32 [nv] = the smallest of them that
+ *                                starts there.  All four are initialised by the call.
+ *   sculpt_mesh_border_next      incl = the inclusive scan of flag.  list int32 [nb] = the border half-edges, ascending;
+ *                                next int32 [nb] = the list index of next(h), -1 for a blocked half-edge (an end with out != 1 or
+ *                                in != 1); counts int64 [8], zeroed by the call: [0] = the pinched vertices.
+ *   sculpt_mesh_border_label     pointer doubling over the two state buffers (int64 [nb] each), ceil(log2(nb)) + 1 rounds, each
+ *                                reading one buffer and writing the other: leader int32 [nb] = the list index of the smallest
+ *                                half-edge of the element's cycle, -1 when its chain reaches a blocked one; length int32 [nb],
+ *                                zeroed by the call, = the cycle's length at its leader.
+ *   sculpt_mesh_border_decide    max_edges == 0: every loop, else loops of at most max_edges >= 3 edges; in any case at most
+ *                                2^22 - 1.  emits, centre, heads int32 [nb] = 1 where the element emits a face / leads a filled
+ *                                loop of at least 4 edges / leads a loop; counts [1 .. 7] += loops, open half-edges, filled loops,
+ *                                filled edges, skipped loops, new vertices, new faces.
+ *   sculpt_mesh_border_loops     label int32 [nb] = the leader as a half-edge, -1 when open; leaders, lengths int32 [n_loops] in
+ *                                ascending leader order (heads_incl = the inclusive scan of heads).
+ *   sculpt_mesh_holes_centroids  rows Pn [n_new][3] (and An [n_new][channels], channels <= 8) = per filled loop of at least 4 edges,
+ *                                in ascending leader order, the mean over the starts of its half-edges: two order-independent
+ *                                passes (csrc/fixsum.h) over mag uint32 and acc int64 [n_new (3 + channels)], zeroed by the call,
+ *                                then (float)(ldexp((double)acc, e - 40) / (double)n).  centre_incl = the inclusive scan of centre.
+ *   sculpt_mesh_holes_emit       Fn int32 [n_faces][3], rows in ascending order of the emitting half-edge h = (a -> b): (b, a,
+ *                                nv + the loop's centroid row), or for a loop of 3 (b, a, end(next(h))) from the leader alone.
+ * Null or out-of-range arguments are refused with an error code and a message; no faces or nb == 0 launches nothing. */
+int sculpt_mesh_border_mark(const sculpt_rmd_topo_t *topo, int32_t *flag, int32_t *vout, int32_t *vin, int32_t *start_of,
+                            sculpt_stream_t stream);
+int sculpt_mesh_border_next(const sculpt_rmd_topo_t *topo, const int32_t *flag, const int32_t *incl, int64_t nb, const int32_t *vout,
+                            const int32_t *vin, const int32_t *start_of, int32_t *list, int32_t *next, int64_t *counts,
+                            sculpt_stream_t stream);
+int sculpt_mesh_border_label(const int32_t *next, int64_t nb, int64_t *state_a, int64_t *state_b, int32_t *leader, int32_t *length,
+                             sculpt_stream_t stream);
+int sculpt_mesh_border_decide(const int32_t *leader, const int32_t *length, int64_t nb, int64_t max_edges, int32_t *emits, int32_t *centre,
+                              int32_t *heads, int64_t *counts, sculpt_stream_t stream);
+int sculpt_mesh_border_loops(const int32_t *list, const int32_t *leader, const int32_t *length, const int32_t *heads_incl, int64_t nb,
+                             int64_t n_loops, int32_t *label, int32_t *leaders, int32_t *lengths, sculpt_stream_t stream);
+int sculpt_mesh_holes_centroids(const sculpt_rmd_topo_t *topo, const float *P, const float *A, int channels, const int32_t *list,
+                                const int32_t *leader, const int32_t *length, const int32_t *centre, const int32_t *centre_incl, int64_t nb,
+                                int64_t n_new, uint32_t *mag, int64_t *acc, float *Pn, float *An, sculpt_stream_t stream);
+int sculpt_mesh_holes_emit(const sculpt_rmd_topo_t *topo, const int32_t *list, const int32_t *next, const int32_t *leader,
+                           const int32_t *length, const int32_t *emits, const int32_t *emits_incl, const int32_t *centre,
+                           const int32_t *centre_incl, int64_t nb, int64_t n_new, int64_t n_faces, int32_t *Fn, sculpt_stream_t stream);
+
 /* Rays against a triangle surface (csrc/mesh_ray.hip; ops.mesh_ray_cast, ops.mesh_occlusion).  Compiled
  * without floating-point contraction and restated bit for bit in tests/_rayref.py.  Added without a version change (new symbols
  * only).  The grid, the records, the order and amax are those of sculpt_surface_closest; the grid must cover the surface: lo is

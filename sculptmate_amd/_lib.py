@@ -250,6 +250,13 @@ SIGNATURES = {
     "sculpt_mesh_face_measures": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "sculpt_surface_self_count": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sculpt_surface_self_emit": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sculpt_mesh_border_mark": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_mesh_border_next": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_mesh_border_label": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_mesh_border_decide": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_mesh_border_loops": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "sculpt_mesh_holes_centroids": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_mesh_holes_emit": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "sculpt_surface_ray_cast": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "sculpt_surface_occlusion": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp]),
     "sculpt_bake_occlusion": (_i, [_vp, _i, _vp, _sz, _vp, _i, _sz, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp,

@@ -41,4 +41,10 @@ __device__ __forceinline__ float fx_value(long long acc, unsigned mag) {
     return mag ? (float)ldexp((double)acc, fx_exp(mag) - FX_BITS) : 0.f;
 }
 
+// the mean of a sum of n terms: the integer sum scaled in double, divided by n in double, rounded once to float
+__device__ __forceinline__ float fx_mean(long long acc, unsigned mag, int n) {
+    if (mag >= FX_NONFINITE) return __uint_as_float(0x7fc00000u);
+    return mag ? (float)(ldexp((double)acc, fx_exp(mag) - FX_BITS) / (double)n) : 0.f;
+}
+
 }  // namespace sculpt

@@ -50,6 +50,11 @@ class TripoGenerator(GeneratorFacade):
     `voxel_remesh` (default None): an int R in 8 .. 1024 (cells along the longest side) or a tuple (R, band_cells) rebuilds every
     mesh from its inside on a voxel lattice, on the device, after keep_components and before smooth -- Blender's Voxel Remesh:
     overlapping parts fuse and the holes at the box close (TSR.extract_meshes; ops.mesh_voxel_remesh).
+    `fill_holes` (default None): True (every border loop) or an int max_edges >= 3 caps the holes of every mesh -- the loops
+    where the surface meets the box -- with fans, on the device, after keep_components and before voxel_remesh: Blender's
+    Clean Up > Fill Holes (sides=).  Every existing vertex and face stays as it is.  A fan suits a short or roughly planar loop
+    and nothing more: a long loop round a corner of the box gets a fan that cuts through the mesh, which `report` = "full"
+    shows and `voxel_remesh` repairs (TSR.extract_meshes; ops.mesh_fill_holes).
     `report` (default None): True leaves what every final mesh is -- edge census, watertight, Euler number, genus, area, volume
     -- at `model.last_reports`, one dict per image, computed on the device before the hand-off; "full" adds the number of
     self-intersecting face pairs (TSR.extract_meshes; ops.mesh_report).  The meshes themselves do not change.
@@ -89,6 +94,7 @@ class TripoGenerator(GeneratorFacade):
         self.project = None
         self.subdivide = None
         self.voxel_remesh = None
+        self.fill_holes = None
         self.occlusion = None
         self.report = None
         self.isosurface = "marching_cubes"
@@ -122,7 +128,7 @@ class TripoGenerator(GeneratorFacade):
                                                        keep_components=self.keep_components, simplify=self.simplify,
                                                        smooth=self.smooth, project=self.project, subdivide=self.subdivide,
                                                        occlusion=self.occlusion, voxel_remesh=self.voxel_remesh,
-                                                       report=self.report)
+                                                       report=self.report, fill_holes=self.fill_holes)
         except Exception as err:
             print(self.run_error_tag, err)
             return STATUS_FAILED

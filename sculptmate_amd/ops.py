@@ -1445,6 +1445,174 @@ def mesh_report(vertices, faces, self_intersections=True):
 
 
 # ----------------------------------------------------------------------------------------------
+# fill holes: border loops capped with fans (csrc/mesh_holes.hip)
+# ----------------------------------------------------------------------------------------------
+HOLES_MAX_EDGES = 2 ** 22 - 1   # the longest loop the fixed-point centroid sum cannot overflow at (csrc/fixsum.h)
+_HOLES_COUNTS = ("pinched_vertices", "loops", "open_half_edges", "filled_loops", "filled_edges", "skipped_loops", "new_vertices", "new_faces")
+
+
+def holes_rule(fill_holes):
+    """`fill_holes` of mesh_fill_holes -> max_edges of sculpt_mesh_border_decide: True -> 0 (every loop), an int n >= 3 -> n (loops
+    of at most n edges).  Anything else -- False, 0, 1, 2, a negative, a float, a bool in the int's place -- is a ValueError,
+    raised here, before anything is launched."""
+    if fill_holes is True:
+        return 0
+    if _is_count(fill_holes, 3):
+        return int(fill_holes)
+    raise ValueError("fill_holes must be True (every border loop) or an int >= 3 (loops of at most that many edges), got %r" % (fill_holes,))
+
+
+def _holes_input(vertices, faces, attributes, who):
+    from .sf3d import remesh_device as rmd
+
+    _device_mesh(vertices, faces, who)
+    P, F = rmd._inputs(vertices, faces, who)
+    return P, F, rmd._attributes(attributes, P.shape[0], who)
+
+
+def _holes_topology(P, F):
+    """The topology of a checked mesh with Nf > 0, the border flags and the border count -> a state dict; two readbacks (the edge
+    count, the border count)."""
+    from .sf3d import remesh_device as rmd
+
+    dev, nv, nf = P.device, P.shape[0], F.shape[0]
+    ctx = rmd._Ctx()
+    topo = rmd._Topo(ctx, F, nv)
+    flag = torch.empty(3 * nf, dtype=torch.int32, device=dev)
+    vout, vin, start_of = (torch.empty(nv, dtype=torch.int32, device=dev) for _ in range(3))
+    check(lib.sculpt_mesh_border_mark(topo.ref(), _ptr(flag), _ptr(vout), _ptr(vin), _ptr(start_of), _stream()))
+    incl = torch.cumsum(flag, 0, dtype=torch.int32)
+    return dict(ctx=ctx, topo=topo, flag=flag, vout=vout, vin=vin, start_of=start_of, incl=incl, nb=int(ctx.read(incl[-1:])))
+
+
+def _holes_loops(s, max_edges):
+    """next, the labels, the lengths, the per-loop decision and its scans on the state of _holes_topology (nb > 0); ONE readback,
+    of the eight totals -> the state, with `counts` a dict."""
+    dev, nb, topo = s["flag"].device, s["nb"], s["topo"]
+
+    def i32(*shape):
+        return torch.empty(shape, dtype=torch.int32, device=dev)
+
+    s.update(list=i32(nb), next=i32(nb), leader=i32(nb), length=i32(nb), flags=i32(3, nb))
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    state = torch.empty((2, nb), dtype=torch.int64, device=dev)
+    check(lib.sculpt_mesh_border_next(topo.ref(), _ptr(s["flag"]), _ptr(s["incl"]), nb, _ptr(s["vout"]), _ptr(s["vin"]), _ptr(s["start_of"]),
+                                      _ptr(s["list"]), _ptr(s["next"]), _ptr(counts), _stream()))
+    check(lib.sculpt_mesh_border_label(_ptr(s["next"]), nb, _ptr(state[0]), _ptr(state[1]), _ptr(s["leader"]), _ptr(s["length"]), _stream()))
+    emits, centre, heads = s["flags"]
+    check(lib.sculpt_mesh_border_decide(_ptr(s["leader"]), _ptr(s["length"]), nb, max_edges, _ptr(emits), _ptr(centre), _ptr(heads),
+                                        _ptr(counts), _stream()))
+    s["scans"] = torch.cumsum(s["flags"], 1, dtype=torch.int32)
+    s["ctx"].stats["readbacks"] += 1
+    s["counts"] = dict(zip(_HOLES_COUNTS, counts.tolist()), border_half_edges=nb)
+    return s
+
+
+def _holes_fill(s, P, F, A):
+    """The centroids and the new faces on the state of _holes_loops -> (vertices', faces' int32, attributes'); no readback."""
+    dev, nb, topo, c = P.device, s["nb"], s["topo"], s["counts"]
+    nv, nf, n_new, n_faces = P.shape[0], F.shape[0], c["new_vertices"], c["new_faces"]
+    if n_faces == 0:
+        return P, F, A
+    channels = 0 if A is None else A.shape[1]
+    emits, centre, _ = s["flags"]
+    emits_incl, centre_incl, _ = s["scans"]
+    Fo = torch.empty((nf + n_faces, 3), dtype=torch.int32, device=dev)
+    Fo[:nf] = F
+    Po, Ao = P, A
+    if n_new:
+        Po = torch.empty((nv + n_new, 3), dtype=torch.float32, device=dev)
+        Po[:nv] = P
+        if A is not None:
+            Ao = torch.empty((nv + n_new, channels), dtype=torch.float32, device=dev)
+            Ao[:nv] = A
+        mag = torch.empty(n_new * (3 + channels), dtype=torch.int32, device=dev)
+        acc = torch.empty(n_new * (3 + channels), dtype=torch.int64, device=dev)
+        check(lib.sculpt_mesh_holes_centroids(topo.ref(), _ptr(P), _ptr(A) if channels else None, channels, _ptr(s["list"]),
+                                              _ptr(s["leader"]), _ptr(s["length"]), _ptr(centre), _ptr(centre_incl), nb, n_new, _ptr(mag),
+                                              _ptr(acc), _ptr(Po[nv:]), _ptr(Ao[nv:]) if channels else None, _stream()))
+    check(lib.sculpt_mesh_holes_emit(topo.ref(), _ptr(s["list"]), _ptr(s["next"]), _ptr(s["leader"]), _ptr(s["length"]), _ptr(emits),
+                                     _ptr(emits_incl), _ptr(centre), _ptr(centre_incl), nb, n_new, n_faces, _ptr(Fo[nf:]), _stream()))
+    return Po, Fo, Ao
+
+
+def mesh_border_loops(vertices, faces):
+    """The border loops of a triangle mesh, on the device (the rule stands at the top of csrc/mesh_holes.hip; tests/_holesref.py
+    restates it).  vertices float [Nv, 3], faces int32 / int64 [Nf, 3] (device tensors; CPU tensors are refused).  Half-edge
+    h = 3 f + k runs from faces[f, k] to faces[f, (k + 1) % 3]; it is a border half-edge when its undirected edge has no other.
+    -> a dict:
+        half_edges         int32 [Nb]  the border half-edges, ascending
+        labels             int32 [Nb]  the loop of each: its leader (the loop's smallest half-edge), or -1 when it is open -- its
+                                       chain of `next` reaches a vertex where the border half-edges do not go one in, one out
+        leaders, lengths   int32 [L]   every loop's leader and number of edges, in ascending leader order
+        border_half_edges, loops, open_half_edges, pinched_vertices    Python ints
+    A face index out of range, a repeated index in a face and a non-finite position are a SculptError.  Nf == 0, or no border
+    half-edge, launches nothing after the topology.  Host readbacks: the input check's three (the index range's two ends and the
+    status), the topology's edge count, the border count (it sizes the lists and the doubling rounds), one tensor with the
+    totals."""
+    P, F, _ = _holes_input(vertices, faces, None, "mesh_border_loops")
+    dev = P.device
+    out = {"half_edges": torch.empty(0, dtype=torch.int32, device=dev), "border_half_edges": 0, "loops": 0, "open_half_edges": 0,
+           "pinched_vertices": 0}
+    out.update(labels=out["half_edges"].clone(), leaders=out["half_edges"].clone(), lengths=out["half_edges"].clone())
+    if F.shape[0] == 0:
+        return out
+    s = _holes_topology(P, F)
+    if s["nb"]:
+        s = _holes_loops(s, 0)
+        nb, n_loops = s["nb"], s["counts"]["loops"]
+        labels = torch.empty(nb, dtype=torch.int32, device=dev)
+        leaders, lengths = (torch.empty(n_loops, dtype=torch.int32, device=dev) for _ in range(2))
+        check(lib.sculpt_mesh_border_loops(_ptr(s["list"]), _ptr(s["leader"]), _ptr(s["length"]), _ptr(s["scans"][2]), nb, n_loops,
+                                           _ptr(labels), _ptr(leaders) if n_loops else None, _ptr(lengths) if n_loops else None, _stream()))
+        out.update(half_edges=s["list"], labels=labels, leaders=leaders, lengths=lengths,
+                   **{k: s["counts"][k] for k in ("border_half_edges", "loops", "open_half_edges", "pinched_vertices")})
+    s["ctx"].done()
+    return out
+
+
+def mesh_fill_holes(vertices, faces, fill_holes=True, attributes=None):
+    """The mesh with its border loops capped by fans, on the device: what trimesh's fill_holes and Blender's Clean Up > Fill Holes
+    (sides=) do between "report" and "remesh".  vertices float [Nv, 3], faces int32 / int64 [Nf, 3], attributes None or float
+    [Nv, C] with 1 <= C <= 8 (device tensors; CPU tensors are refused); fill_holes: True (every loop) or an int max_edges >= 3
+    (holes_rule).
+    -> (vertices' f32 [Nv + new_vertices, 3], faces' [Nf + new_faces, 3] in faces' dtype, attributes' f32 or None, info).
+    Contract (the rule stands at the top of csrc/mesh_holes.hip; tests/_holesref.py restates it bit for bit):
+      - every existing vertex and face stays exactly as it is: rows are only appended;
+      - a border half-edge is the one half-edge of an edge that has no other (the census of mesh_report); a vertex where they do
+        not go one in, one out is pinched (a bow-tie, inconsistent winding beside a hole), and a half-edge that touches one, or
+        whose chain of `next` reaches one, is open and stays open; the others form loops;
+      - a loop of n <= max_edges edges (and n <= 2^22 - 1 in any case) is filled: n >= 4 gets one new vertex, the centroid of its
+        n vertices, and n faces (b, a, centroid) over its half-edges (a -> b); n == 3 gets the one face (b, a, c) from its
+        smallest half-edge and no vertex.  New vertices follow in ascending order of the loops' smallest half-edges, new faces in
+        ascending order of the half-edge that emits them; they traverse the border edges in the opposite direction, so the
+        winding stays consistent, and every new edge ends at a new vertex, so no non-manifold edge arises;
+      - the centroid is an order-independent fixed-point sum (csrc/fixsum.h) divided by n in fp64 and rounded once to fp32; the
+        attributes of the new rows are the same mean over the loop's rows (a non-finite term gives NaN);
+      - info: border_half_edges, loops, open_half_edges, pinched_vertices, filled_loops, filled_edges, skipped_loops,
+        new_vertices, new_faces (Python ints);
+      - a face index out of range, a repeated index in a face and a non-finite position are a SculptError;
+      - Nf == 0, or no border half-edge: the input's values come back, and nothing is launched after the topology;
+      - deterministic: integer atomics and exact integer sums only; two calls give the same bits;
+      - host readbacks: the input check's three (the index range's two ends and the status), the topology's edge count, the border
+        count (it sizes the lists and the doubling rounds), one tensor with the totals.
+    NOT claimed: a fan is a good cap for a short or roughly planar, star-shaped loop, and nothing more.  A long loop that wraps round
+    an edge or a corner of the extraction box gets a fan that cuts through the mesh: max_edges is the control, mesh_report (its
+    self-intersections) the check, and mesh_voxel_remesh remains the answer for such loops."""
+    max_edges = holes_rule(fill_holes)
+    P, F, A = _holes_input(vertices, faces, attributes, "mesh_fill_holes")
+    info = dict.fromkeys(("border_half_edges",) + _HOLES_COUNTS, 0)
+    if F.shape[0]:
+        s = _holes_topology(P, F)
+        if s["nb"]:
+            s = _holes_loops(s, max_edges)
+            info.update(s["counts"])
+            P, F, A = _holes_fill(s, P, F, A)
+        s["ctx"].done()
+    return P, F.to(faces.dtype), A, info
+
+
+# ----------------------------------------------------------------------------------------------
 # rays against a surface: closest hit, ambient occlusion (csrc/mesh_ray.hip, DESIGN.md 3.3f)
 # ----------------------------------------------------------------------------------------------
 OCCLUSION_DIRECTIONS = 64          # what occlusion=True means

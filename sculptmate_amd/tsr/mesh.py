@@ -32,7 +32,7 @@ class Mesh:
     the extractor's faces (FACE_FIELDS): quads int [Nq, 4], the all-quad mesh over the same vertices that
       extract_meshes(isosurface="surface_nets") adds, while `faces` are still the extractor's -- faces[2q], faces[2q + 1] are
       quad q split along its shorter diagonal.  smooth and project keep it (faces and vertex numbering stay); keep_components,
-      voxel_remesh, simplify and the triangle schemes of subdivide (Loop, midpoint) make new faces and drop it; subdivide with
+      fill_holes, voxel_remesh, simplify and the triangle schemes of subdivide (Loop, midpoint) make new faces and drop it; subdivide with
       (n, "catmull_clark") sets it anew, to the refined quads, on any mesh.
     A step that makes one mesh from another names what it carries over (_derive); what it does not name is None on its result."""
 
@@ -167,6 +167,28 @@ class Mesh:
         and normals at the final vertices instead)."""
         v, f = ops.mesh_voxel_remesh(self.vertices, self.faces, voxel_remesh)
         return self._derive(v, f)
+
+    def fill_holes(self, fill_holes=True) -> "Mesh":
+        """The mesh with its border loops capped by fans on the device (ops.mesh_fill_holes): fill_holes = True (every loop) or an
+        int max_edges >= 3 (loops of at most that many edges; ops.holes_rule).  Every existing vertex and face stays exactly as
+        it is; a loop of four or more edges gets one new vertex at its centroid and a face per edge, a loop of three one face.
+        vertex_colors are extended by the mean of each loop's colours (attributes=).  Everything else is dropped: the vertex rows
+        of vertex_normals and vertex_occlusion would be short, uvs, corner_normals, corner_tangents and the baked maps have no
+        rows for the new faces, and `quads` no longer cover the faces.  NOT claimed: a fan is a good cap for a short or roughly
+        planar, star-shaped loop, and nothing more -- a long loop that wraps round an edge or a corner of the extraction box
+        gets a fan that cuts through the mesh; max_edges is the control, report() (its self-intersections) the check, and
+        voxel_remesh the answer for such loops."""
+        v, f, colors, _ = ops.mesh_fill_holes(self.vertices, self.faces, fill_holes, attributes=self.vertex_colors)
+        return self._derive(v, f, vertex_colors=colors)
+
+    def border_loops(self) -> dict:
+        """The border loops of this mesh as plain Python (ops.mesh_border_loops on its device tensors; host arrays are refused
+        like any CPU tensor): border_half_edges, loops, open_half_edges, pinched_vertices, and `lengths`, the sorted list of the
+        loops' edge counts -- what fill_holes(max_edges) would fill."""
+        r = ops.mesh_border_loops(self.vertices, self.faces)
+        out = {k: r[k] for k in ("border_half_edges", "loops", "open_half_edges", "pinched_vertices")}
+        out["lengths"] = sorted(r["lengths"].tolist())
+        return out
 
     def report(self, self_intersections=True) -> dict:
         """What this mesh is (ops.mesh_report on its device tensors; host arrays are refused like any CPU tensor): the edge

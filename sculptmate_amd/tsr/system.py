@@ -1201,8 +1201,8 @@ class TSR(KernelEngine):
 
     def extract_meshes(self, scene_codes, enable_texture=False, resolution: int = 256, threshold: float = 25.0,
                        x_range=None, density_events=None, bake_texture: int = 0, normals=None, isosurface="marching_cubes",
-                       keep_components=None, voxel_remesh=None, report=None, simplify=None, smooth=None, project=None,
-                       subdivide=None, occlusion=None) -> List[Mesh]:
+                       keep_components=None, fill_holes=None, voxel_remesh=None, report=None, simplify=None, smooth=None,
+                       project=None, subdivide=None, occlusion=None) -> List[Mesh]:
         """The arithmetic of system.py:171-200 without the Blender sink: returns device tensors.
         density_events: optional (start, stop) torch events recorded around the dense-grid launch (bench.py's live
         per-launch timing of the dominant kernel, on the stream it is launched on).
@@ -1264,6 +1264,17 @@ class TSR(KernelEngine):
         the holes where the extractor met the box close.  It makes new faces, so Mesh.quads is dropped and Catmull-Clark starts
         from the triangles.  run, run_async, run_batched, run_pipelined, batch.run_sharded and extract_mesh_sharded do not
         take the option yet: call Mesh.voxel_remesh on a device mesh instead.
+        fill_holes: None (default): nothing is launched, and the meshes are bit for bit what they were.  True (every border loop)
+        or an int max_edges >= 3 (loops of at most that many edges; ops.holes_rule): the border loops -- the holes where the
+        surface meets the box -- are capped with fans on the device (ops.mesh_fill_holes) AFTER keep_components and BEFORE
+        voxel_remesh, smooth and simplify, which then get a closed surface without resampling: every vertex and face of the
+        extractor stays exactly as it is, a loop of four or more edges gets one vertex at its centroid and a face per edge, a
+        loop of three one face.  It makes new faces, so Mesh.quads is dropped and Catmull-Clark starts from the triangles.  NOT
+        claimed: a fan is a good cap for a short or roughly planar, star-shaped loop, and nothing more; a long loop that wraps
+        round an edge or a corner of the box gets a fan that cuts through the mesh -- max_edges is the control, report="full"
+        the check, voxel_remesh the answer for such loops.  Pass it by keyword, like voxel_remesh and report.  run, run_async,
+        run_batched, run_pipelined, batch.run_sharded and extract_mesh_sharded do not take the option yet: call Mesh.fill_holes
+        on a device mesh instead.
         occlusion: None (default): nothing is launched, nothing changes.  True (64 directions), an int k in 1 .. 1024 or a tuple
         (k, max_distance) (ops.occlusion_rule): Mesh.vertex_occlusion = the ambient occlusion of the final mesh against itself,
         f32 [Nv], 1 = open, 0 = occluded -- Mesh.ambient_occlusion(occlusion, outward=TSR.WINDING_OUTWARD), one fused ray
@@ -1294,7 +1305,7 @@ class TSR(KernelEngine):
             if not threshold > 0:
                 raise ValueError("bake_project needs a positive threshold (the surface is ln(threshold) in the raw density), got %r" % (threshold,))
         geometry = dict(keep_components=keep_components, simplify=simplify, smooth=smooth, project=project, subdivide=subdivide,
-                        voxel_remesh=voxel_remesh)
+                        voxel_remesh=voxel_remesh, fill_holes=fill_holes)
         self._check_geometry(threshold, **geometry)   # a ValueError before anything is launched
         bake = int(bake_texture) if enable_texture else 0
         self.set_marching_cubes_resolution(resolution)
@@ -1315,7 +1326,7 @@ class TSR(KernelEngine):
                                           sign_planes=sign_planes)
 
         mc.takes_sign_planes = True
-        keeps_faces = keep_components is None and simplify is None and subdivide is None and voxel_remesh is None
+        keeps_faces = keep_components is None and simplify is None and subdivide is None and voxel_remesh is None and fill_holes is None
         catmull_clark = self._is_catmull_clark(subdivide)
         for scene_code in scene_codes:
             planes = scene_code.contiguous()
@@ -1328,7 +1339,8 @@ class TSR(KernelEngine):
                 v_pos, t_pos_idx = mc(vol)   # (both decoder modes have the fp32 range: a NaN here is a NaN of the model)
             quads = quads_of.pop("quads", None)
             # Catmull-Clark refines the extractor's quads while they still cover the faces (smooth keeps them), else the triangles
-            self._quads = quads if catmull_clark and keep_components is None and simplify is None and voxel_remesh is None else None
+            self._quads = (quads if catmull_clark and keep_components is None and simplify is None and voxel_remesh is None
+                           and fill_holes is None else None)
             v_pos, t_pos_idx = self._reshaped(v_pos, t_pos_idx, planes, threshold, R, **geometry)
             out.append(self._textured(v_pos, t_pos_idx, planes, enable_texture, bake, normals, occlusion, threshold=threshold, R=R))
             refined, self._quads = self._quads, None
@@ -1346,11 +1358,14 @@ class TSR(KernelEngine):
         return isinstance(subdivide, tuple) and len(subdivide) == 2 and subdivide[1] == "catmull_clark"
 
     @staticmethod
-    def _check_geometry(threshold, keep_components=None, simplify=None, smooth=None, project=None, subdivide=None, voxel_remesh=None):
+    def _check_geometry(threshold, keep_components=None, simplify=None, smooth=None, project=None, subdivide=None, voxel_remesh=None,
+                        fill_holes=None):
         """The rules of the geometry options that are set (ops.*_rule; an option left None is not looked at): a ValueError
         here comes before anything is launched."""
         if keep_components is not None:
             ops.keep_rule(keep_components)
+        if fill_holes is not None:
+            ops.holes_rule(fill_holes)
         if voxel_remesh is not None:
             ops.voxel_rule(voxel_remesh)
         if simplify is not None:
@@ -1365,11 +1380,13 @@ class TSR(KernelEngine):
                 raise ValueError("project needs a positive threshold (the surface is ln(threshold) in the raw density), got %r" % (threshold,))
 
     def _reshaped(self, v_pos, t_pos_idx, planes, threshold, R, keep_components=None, simplify=None, smooth=None, project=None,
-                  subdivide=None, voxel_remesh=None):
-        """The geometry half of extract_meshes, in its fixed order: keep_components -> voxel_remesh -> smooth -> simplify -> subdivide -> project,
+                  subdivide=None, voxel_remesh=None, fill_holes=None):
+        """The geometry half of extract_meshes, in its fixed order: keep_components -> fill_holes -> voxel_remesh -> smooth -> simplify -> subdivide -> project,
         each only when set -> (v_pos, t_pos_idx).  A new geometry step goes in here, and into _check_geometry, and nowhere else."""
         if keep_components is not None:
             v_pos, t_pos_idx = ops.mesh_keep_components(v_pos, t_pos_idx, keep_components)[:2]
+        if fill_holes is not None:
+            v_pos, t_pos_idx = ops.mesh_fill_holes(v_pos, t_pos_idx, fill_holes)[:2]
         if voxel_remesh is not None:
             v_pos, t_pos_idx = ops.mesh_voxel_remesh(v_pos, t_pos_idx, voxel_remesh)
         if smooth is not None:
@@ -1536,8 +1553,8 @@ class TSR(KernelEngine):
 
     def extract_mesh(self, scene_codes, enable_texture=False, mesh_name="NewMesh", resolution: int = 256,
                      threshold: float = 25.0, bake_texture: int = 0, normals=None, isosurface="marching_cubes", keep_components=None,
-                     voxel_remesh=None, report=None, simplify=None, smooth=None, project=None, subdivide=None, occlusion=None):
-        """system.py:171-200: same signature (+ bake_texture, normals, occlusion, report and the geometry options keep_components, voxel_remesh,
+                     fill_holes=None, voxel_remesh=None, report=None, simplify=None, smooth=None, project=None, subdivide=None, occlusion=None):
+        """system.py:171-200: same signature (+ bake_texture, normals, occlusion, report and the geometry options keep_components, fill_holes, voxel_remesh,
         smooth, simplify, subdivide, project, all described at extract_meshes: the sink receives the final mesh); pushes each mesh into the sink (Blender when
         `bpy` is importable, exactly like the reference's import_obj_blender) and also returns the meshes.  A baked mesh goes to
         the textured sink (per-loop UVs + an image-texture material; with self.normal_map = "tangent" also normal_image=, the
@@ -1547,7 +1564,7 @@ class TSR(KernelEngine):
         textured sink stays on triangles, which its per-corner UVs belong to."""
         meshes = self.extract_meshes(scene_codes, enable_texture, resolution, threshold, bake_texture=bake_texture, normals=normals,
                                      isosurface=isosurface, keep_components=keep_components, simplify=simplify, smooth=smooth, project=project,
-                                     subdivide=subdivide, occlusion=occlusion, voxel_remesh=voxel_remesh, report=report)
+                                     subdivide=subdivide, occlusion=occlusion, voxel_remesh=voxel_remesh, report=report, fill_holes=fill_holes)
         sink = self.mesh_sink or _default_sink()
         for m in meshes:
             if m.texture is not None:
