@@ -1373,6 +1373,31 @@ int sculpt_surface_occlusion(const float *P, const float *N, int64_t n, const in
                              const int32_t *items, const int32_t *start, const double *params_host, double amax, float *ao,
                              sculpt_stream_t stream);
 
+/* Wall thickness -- the shape diameter -- of points against the surface of the grid (csrc/mesh_ray.hip "thickness";
+ * ops.mesh_thickness, Mesh.thickness, TSR.bake_thickness_map), in one launch.  Added without a version
+ * change (a new symbol only).  The grid arguments, records, order and amax are those of sculpt_surface_occlusion.  Per point
+ * P[i] with normal N[i], under the cone set cone_dirs [k][3] of unit vectors about +z shared by all points, 1 <= k <= 1024; steps
+ * 1 - 3 and 5 - 6 in fp32 without contraction, every operation rounded on its own:
+ *   1  m = unit(n): s = (n.x n.x + n.y n.y) + n.z n.z, len = sqrt(s) correctly rounded, n / len per component; it applies only
+ *      when 0 < len < inf
+ *   2  the frame: sg = copysign(1, m.z), a = -1 / (sg + m.z), b = (m.x m.y) a, T = (1 + (sg (m.x m.x)) a, sg b, -(sg m.x)),
+ *      B = (b, sg + (m.y m.y) a, -m.y)
+ *   3  o = p - offset m per component (the product rounded, then the difference)
+ *   4  per direction j in order: d = (C_j.x T + C_j.y B) - C_j.z m per component; (t, f) = what sculpt_surface_ray_cast reports for
+ *      (o, d) over [0, max_distance]; the hit is valid iff a face was hit and, with g = cross(b - a, c - a) of its corners in fp64,
+ *      dot(g, d) outward > 0 strictly (the ray leaves through the back of the face); any other ray contributes nothing
+ *   5  valid rays only: dist = fp32(t), w = C_j.z, sw += w, swt += w dist (the product rounded, then the sum), thin = min(thin, dist)
+ *   6  thickness [n] f32 = swt / sw when a ray was valid, else +inf; thinnest [n] f32 = thin (+inf when none); valid [n] int32 the
+ *      number of valid rays
+ * A non-finite p or n: NaN, NaN, 0.  A normal to which unit does not apply (zero, overflowing): +inf, +inf, 0, nothing is cast; a
+ * surface without faces: the same.  outward is +1 (faces wind counter-clockwise seen from outside) or -1; offset finite,
+ * max_distance >= 0 (+inf allowed).  Null, misaligned or out-of-range arguments are refused with an error code and a message;
+ * n == 0 launches nothing. */
+int sculpt_surface_thickness(const float *P, const float *N, int64_t n, const int64_t *order, const float *cone_dirs, int k, float offset,
+                             float max_distance, double outward, const float *GP, const int32_t *GF, int64_t gnf, const float *records,
+                             const int32_t *items, const int32_t *start, const double *params_host, double amax, float *thickness,
+                             float *thinnest, int32_t *valid, sculpt_stream_t stream);
+
 /* Ambient-occlusion bake over a rasterised atlas (csrc/mesh_ray.hip; ops.bake_occlusion, TSR.bake_occlusion_map; DESIGN.md section
  * 3.3h): sculpt_surface_occlusion at every covered texel of the atlas of a LOW mesh (v_pos [nv][3], faces [nf][3] int32 or int64,
  * per-vertex normals v_nrm [nv][3]) against the surface S of the grid (GP, GF, gnf, records, items, start, params_host, amax: as

@@ -259,6 +259,7 @@ SIGNATURES = {
     "sculpt_mesh_holes_emit": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "sculpt_surface_ray_cast": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "sculpt_surface_occlusion": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp]),
+    "sculpt_surface_thickness": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _f, _f, _d, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
     "sculpt_bake_occlusion": (_i, [_vp, _i, _vp, _sz, _vp, _i, _sz, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp,
                                    _vp, _vp]),
     "sculpt_surface_render": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _f, _vp, _d, _vp, _vp]),

@@ -74,6 +74,31 @@
 // k in registers; ao = open / all, 1 when all == 0, NaN for a non-finite p or n.  A non-finite origin or direction hits nothing,
 // as in the closest-hit form.  No atomics, no ray is written to memory.
 //
+// ---- thickness (sculpt_surface_thickness; ops.mesh_thickness, Mesh.thickness, TSR.bake_thickness_map) --------
+// The shape diameter of a point: how far the rays of a cone about its INWARD normal travel before they leave the body again.
+// Per point p with normal n, the cone set C of K unit vectors about +z shared by all points (ops.thickness_directions), offset,
+// max_distance and outward (+1 when the faces wind counter-clockwise seen from outside, else -1).  Steps 1 - 3 and 5 - 6 are fp32
+// without contraction, every operation rounded on its own; tests/_thickref.py restates the rule in NumPy and
+// ops.mesh_thickness_composed in torch, bit for bit.
+//   1  m = unit(n) of the mesh render below.  A non-finite p or n: thickness = thinnest = NaN, valid = 0.  unit does not apply
+//      (a zero or overflowing normal): +inf, +inf, 0, nothing is cast.  A surface without faces: +inf, +inf, 0.
+//   2  the branch-free orthonormal frame of Duff et al.: sg = copysign(1, m.z), a = -1 / (sg + m.z), b = (m.x m.y) a,
+//      T = (1 + (sg (m.x m.x)) a, sg b, -(sg m.x)), B = (b, sg + (m.y m.y) a, -m.y)
+//   3  o = p - offset m per component (the product rounded, then the difference)
+//   4  per direction j = 0 .. K - 1, in that order: d = (C_j.x T + C_j.y B) - C_j.z m per component; (t, f) = the closest hit of
+//      (o, d) over [0, max_distance] by the rule above, exactly what sculpt_surface_ray_cast reports (a non-finite o or d and a
+//      zero d hit nothing).  The hit is VALID iff a face was hit and the ray leaves through its back: with g = cross(b - a, c - a)
+//      of f's corners in fp64 (as in the snap) and d widened, dot(g, d) outward > 0, strictly.  A ray that enters another body
+//      through a front face, or that hits nothing, contributes nothing.
+//   5  valid rays only, in registers: dist = fp32(t); w = C_j.z; sw += w; swt += w dist (the product rounded, then the sum);
+//      thin = min(thin, dist); valid += 1
+//   6  thickness = swt / sw when valid > 0, else +inf; thinnest = thin (+inf when none); valid as int32
+// Shape: one lane per point, the points in the order of their grid cell; m, T, B, o and the four accumulators stay in registers
+// over the loop; cast<true, false> serves the hit and the corners of the back-face test come from the packed record the walk
+// has just read.  Every one of the K rays of every point takes part -- the frame turns the cone onto the point's own normal, so
+// no lane idles on a direction its normal excludes, which a shared global set cannot avoid.  Neighbouring points have
+// neighbouring normals, so the 64 lanes of a wave cast nearly parallel rays from nearby origins at every j.  Nothing per ray is
+// written to memory, no atomics.
 // ---- the atlas bake (sculpt_bake_occlusion; ops.bake_occlusion, TSR.bake_occlusion_map) ---------------------
 // The occlusion above at every covered texel of a rasterised atlas of a LOW mesh, against the surface S the grid is built over
 // (the low mesh itself, or the high-poly surface it was simplified from), in one launch.  Per texel, fp32 unless said otherwise:
@@ -333,6 +358,70 @@ occlusion_kernel(Grid G, const float *__restrict__ P, const float *__restrict__ 
     ao[j] = occlusion_at(G, rec, px, py, pz, nx, ny, nz, dirs, K, offset, max_distance, amax);
 }
 
+// unit(x) of the header ("the mesh render") in place; false (x untouched) when it does not apply
+__device__ inline bool unit3(float (&x)[3]) {
+    const float s = (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2];
+    const float len = (float)sqrt((double)s);   // the correctly rounded fp32 root
+    if (!(len > 0.0f && len < INFINITY)) return false;
+    x[0] = x[0] / len;
+    x[1] = x[1] / len;
+    x[2] = x[2] / len;
+    return true;
+}
+
+// The thickness rule of the header: a lane keeps one point's frame, origin and sums in registers over the K rays of its cone.
+__global__ void __launch_bounds__(kThreads)
+thickness_kernel(Grid G, const float *__restrict__ P, const float *__restrict__ Nr, long n, const int64_t *__restrict__ order,
+                 const float *__restrict__ cone, int K, float offset, float max_distance, double outward,
+                 const float4 *__restrict__ rec, double amax, float *__restrict__ thickness, float *__restrict__ thinnest,
+                 int32_t *__restrict__ valid) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long at = order ? (long)order[i] : i;
+    const float px = P[3 * at], py = P[3 * at + 1], pz = P[3 * at + 2];
+    float m[3] = {Nr[3 * at], Nr[3 * at + 1], Nr[3 * at + 2]};
+    if (!(finite3(px, py, pz) && finite3(m[0], m[1], m[2]))) {
+        thickness[at] = thinnest[at] = NAN;
+        valid[at] = 0;
+        return;
+    }
+    float sw = 0.0f, swt = 0.0f, thin = INFINITY;
+    int count = 0;
+    if (unit3(m) && G.nf > 0) {
+        const float sg = copysignf(1.0f, m[2]);
+        const float a = -1.0f / (sg + m[2]);   // |sg + m.z| >= 1: the two have one sign
+        const float b = (m[0] * m[1]) * a;
+        const float T[3] = {1.0f + (sg * (m[0] * m[0])) * a, sg * b, -(sg * m[0])};
+        const float Bv[3] = {b, sg + (m[1] * m[1]) * a, -m[1]};
+        const float ox = px - offset * m[0], oy = py - offset * m[1], oz = pz - offset * m[2];
+        const bool castable = finite3(ox, oy, oz);
+        const D3 o = {(double)ox, (double)oy, (double)oz};
+        for (int j = 0; j < K; ++j) {
+            const float cx = cone[3 * j], cy = cone[3 * j + 1], cz = cone[3 * j + 2];
+            const float dx = (cx * T[0] + cy * Bv[0]) - cz * m[0];
+            const float dy = (cx * T[1] + cy * Bv[1]) - cz * m[1];
+            const float dz = (cx * T[2] + cy * Bv[2]) - cz * m[2];
+            if (!(castable && finite3(dx, dy, dz)) || (dx == 0.0f && dy == 0.0f && dz == 0.0f)) continue;
+            const D3 d = {(double)dx, (double)dy, (double)dz};
+            Hit H = {INFINITY, INT_MAX, 0.0, 0.0};
+            cast<true, false>(G, rec, o, d, 0.0, (double)max_distance, amax, H);
+            if (H.f == INT_MAX) continue;
+            const float4 r1 = rec[4 * (long)H.f + 1], r2 = rec[4 * (long)H.f + 2], r3 = rec[4 * (long)H.f + 3];
+            const D3 ca = {(double)r1.z, (double)r1.w, (double)r2.x}, cb = {(double)r2.y, (double)r2.z, (double)r2.w},
+                     cc = {(double)r3.x, (double)r3.y, (double)r3.z};
+            if (!(dot(cross(cb - ca, cc - ca), d) * outward > 0.0)) continue;   // through a front face: into another body
+            const float dist = (float)H.t;
+            sw += cz;
+            swt += cz * dist;
+            thin = fminf(thin, dist);
+            ++count;
+        }
+    }
+    thickness[at] = count > 0 ? swt / sw : INFINITY;
+    thinnest[at] = thin;
+    valid[at] = count;
+}
+
 // Step 4 of the atlas bake: (p, n) -> (q, m) in place.
 __device__ inline void snap_to_surface(const Grid &G, const float4 *__restrict__ rec, float cage, double amax, float (&p)[3], float (&n)[3]) {
     const float cx = cage * n[0], cy = cage * n[1], cz = cage * n[2];
@@ -459,17 +548,6 @@ __device__ inline void map_lookup(const float *__restrict__ map, int R, float U,
 #pragma unroll
     for (int c = 0; c < kC; ++c)
         out[c] = ((r0[x0 * kC + c] * gx + r0[x1 * kC + c] * fx) * gy) + ((r1[x0 * kC + c] * gx + r1[x1 * kC + c] * fx) * fy);
-}
-
-// unit(x) of the header in place; false (x untouched) when it does not apply
-__device__ inline bool unit3(float (&x)[3]) {
-    const float s = (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2];
-    const float len = (float)sqrt((double)s);   // the correctly rounded fp32 root
-    if (!(len > 0.0f && len < INFINITY)) return false;
-    x[0] = x[0] / len;
-    x[1] = x[1] / len;
-    x[2] = x[2] / len;
-    return true;
 }
 
 // the second phase: everything after the hit (B.f a face) is final
@@ -662,6 +740,27 @@ int sculpt_surface_occlusion(const float *P, const float *N, int64_t n, const in
     SC_REQUIRE(aligned16(records), "surface_occlusion: records not 16-byte aligned");
     const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
     RMD_LAUNCH(occlusion_kernel, n, G, P, N, (long)n, order, dirs, k, offset, max_distance, reinterpret_cast<const float4 *>(records), amax, ao);
+    return 0;
+}
+
+int sculpt_surface_thickness(const float *P, const float *N, int64_t n, const int64_t *order, const float *cone_dirs, int k, float offset,
+                             float max_distance, double outward, const float *GP, const int32_t *GF, int64_t gnf, const float *records,
+                             const int32_t *items, const int32_t *start, const double *params_host, double amax, float *thickness,
+                             float *thinnest, int32_t *valid, sculpt_stream_t stream) {
+    SC_REQUIRE(n >= 0 && 3 * n < ((int64_t)1 << 40), "surface_thickness: n=%lld out of range", (long long)n);
+    SC_REQUIRE(amax >= 0 && amax < INFINITY, "surface_thickness: amax=%g", amax);  // a NaN fails the comparison
+    SC_REQUIRE(k >= 1 && k <= kMaxDirections, "surface_thickness: %d directions (1 .. %d)", k, kMaxDirections);
+    SC_REQUIRE(max_distance >= 0, "surface_thickness: max_distance=%g", (double)max_distance);
+    SC_REQUIRE(isfinite(offset), "surface_thickness: offset=%g", (double)offset);
+    SC_REQUIRE(outward == 1.0 || outward == -1.0, "surface_thickness: outward=%g (+1 or -1)", outward);
+    if (n == 0) return 0;
+    if (int rc = check_grid("surface_thickness", GP, GF, gnf, params_host)) return rc;
+    SC_REQUIRE(P && N && cone_dirs && thickness && thinnest && valid, "surface_thickness: null array");
+    SC_REQUIRE(gnf == 0 || (items && start && records), "surface_thickness: null grid lists or records");
+    SC_REQUIRE(aligned16(records), "surface_thickness: records not 16-byte aligned");
+    const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
+    RMD_LAUNCH(thickness_kernel, n, G, P, N, (long)n, order, cone_dirs, k, offset, max_distance, outward,
+               reinterpret_cast<const float4 *>(records), amax, thickness, thinnest, valid);
     return 0;
 }
 

@@ -79,6 +79,10 @@ class TripoGenerator(GeneratorFacade):
     the height along the low-poly normal up to the field's iso-surface -- beside every baked texture, over its atlas
     (TSR.bake_displacement_map; copied to the model as TSR.displacement_map).  It comes back as the mesh's plain attribute
     `displacement`; Mesh.export(path, displacement=mesh.displacement) writes it.
+    `thickness_map` (default None): True, an int k or a tuple (k, max_distance) (ops.thickness_rule) bakes a thickness map -- the
+    wall thickness (shape diameter) of the mesh per texel -- beside every baked texture, over its atlas
+    (TSR.bake_thickness_map; copied to the model as TSR.thickness_map).  It comes back as the mesh's plain attribute
+    `thickness` (a tsr.thickness.ThicknessMap); its save(path) writes a 16-bit grey PNG.
     `atlas` (default "box"): "charts" unwraps every mesh a map is baked for with sf3d.unwrap.ChartUnwrapper -- charts that are
     connected pieces of surface -- instead of the box projection (copied to the model as TSR.atlas)."""
 
@@ -102,6 +106,7 @@ class TripoGenerator(GeneratorFacade):
         self.occlusion_map = None
         self.bake_project = None
         self.displacement_map = None
+        self.thickness_map = None
         self.atlas = "box"
 
     def _construct_model(self):
@@ -120,6 +125,7 @@ class TripoGenerator(GeneratorFacade):
             self.model.occlusion_map = self.occlusion_map
             self.model.bake_project = self.bake_project
             self.model.displacement_map = self.displacement_map
+            self.model.thickness_map = self.thickness_map
             self.model.atlas = self.atlas
             self.last_meshes = self.model.extract_mesh(codes, enable_texture=enable_texture, mesh_name=input_name,
                                                        resolution=self.mc_resolution,

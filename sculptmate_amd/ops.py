@@ -1000,6 +1000,21 @@ class _SurfaceIndex:
                                            _ptr(records) if records is not None else None, *grid, _ptr(ao), _stream()))
         return ao
 
+    def thickness(self, points, normals, cone_dirs, offset, max_distance, outward):
+        """points, normals f32 [N, 3], cone_dirs f32 [K, 3], all contiguous on the device, N > 0 -> (thickness f32 [N], thinnest
+        f32 [N], valid int32 [N]) in ONE launch (sculpt_surface_thickness); the points are always sorted by cell."""
+        n, dev = points.shape[0], points.device
+        thick = torch.empty(n, dtype=torch.float32, device=dev)
+        thin = torch.empty(n, dtype=torch.float32, device=dev)
+        valid = torch.empty(n, dtype=torch.int32, device=dev)
+        order, records = self._sorted(points, always=True)
+        mesh, grid = self._grid_args()
+        check(lib.sculpt_surface_thickness(_ptr(points), _ptr(normals), n, _ptr(order) if order is not None else None,
+                                           _ptr(cone_dirs), cone_dirs.shape[0], float(offset), float(max_distance), float(outward),
+                                           *mesh, _ptr(records) if records is not None else None, *grid, _ptr(thick), _ptr(thin),
+                                           _ptr(valid), _stream()))
+        return thick, thin, valid
+
 
 def _query_points(points, who):
     if not (isinstance(points, torch.Tensor) and points.is_cuda):
@@ -1806,6 +1821,16 @@ def _bake_occlusion_args(who, v_pos, faces, normals, rast, occlusion, offset, se
     if offset is not None and not (_is_real(offset) and math.isfinite(float(np.float32(offset)))):
         raise ValueError("offset must be None or a finite number, got %r" % (offset,))
     dirs = occlusion_directions(k, seed)      # checks the seed
+    _source_rule(who, source, cage)
+    index, v, f, nrm, r, offset, cage = _atlas_query_args(who, v_pos, faces, normals, rast, offset, source, cage)
+    if index is None:
+        return None, v, f, nrm, r, None, 0.0, math.inf, 0.0
+    far = math.inf if far is None else float(np.float32(far))
+    return index, v, f, nrm, r, torch.from_numpy(dirs).to(v.device), offset, far, cage
+
+
+def _source_rule(who, source, cage):
+    """The rule of `source` / `cage` of a bake against a surface: a ValueError before anything is launched."""
     if source is None:
         if cage is not None:
             raise ValueError("%s: cage snaps the texels onto a source surface; without a source it must be None, got %r" % (who, cage))
@@ -1814,6 +1839,11 @@ def _bake_occlusion_args(who, v_pos, faces, normals, rast, occlusion, offset, se
             raise ValueError("%s: source must be None or (vertices, faces), got %r" % (who, type(source).__name__))
         if cage is not None and not (_is_real(cage) and 0.0 < float(np.float32(cage)) < math.inf):   # a NaN fails the comparison
             raise ValueError("cage must be None or a finite number > 0, got %r" % (cage,))
+
+
+def _atlas_query_args(who, v_pos, faces, normals, rast, offset, source, cage):
+    """The tensors of a ray bake over an atlas, checked (SculptError), and the index over S with the defaults that depend on its
+    bounds -> (index or None when res == 0, v, f, nrm, rast, offset, cage), offset and cage rounded to fp32 (cage 0: no snap)."""
     v, f = _mesh_args(who, v_pos, faces)
     nrm = _req(normals.contiguous() if isinstance(normals, torch.Tensor) else normals, torch.float32, "normals")
     r = _req(rast.contiguous() if isinstance(rast, torch.Tensor) else rast, torch.float32, "rast")
@@ -1823,7 +1853,7 @@ def _bake_occlusion_args(who, v_pos, faces, normals, rast, occlusion, offset, se
         raise SculptError("%s: rast %s must be [res, res, 4]" % (who, tuple(r.shape)))
     P, F = _surface(v, f, who) if source is None else _surface(source[0], source[1], who)
     if r.shape[0] == 0:
-        return None, v, f, nrm, r, None, 0.0, math.inf, 0.0
+        return None, v, f, nrm, r, 0.0, 0.0
     index = _SurfaceIndex(P, F)
     if offset is None:
         offset = OCCLUSION_OFFSET * index.longest_side()
@@ -1831,8 +1861,7 @@ def _bake_occlusion_args(who, v_pos, faces, normals, rast, occlusion, offset, se
         cage = 0.0
     elif cage is None:
         cage = OCCLUSION_CAGE * index.longest_side()
-    far = math.inf if far is None else float(np.float32(far))
-    return index, v, f, nrm, r, torch.from_numpy(dirs).to(v.device), float(np.float32(offset)), far, float(np.float32(cage))
+    return index, v, f, nrm, r, float(np.float32(offset)), float(np.float32(cage))
 
 
 def bake_occlusion(v_pos, faces, normals, rast, occlusion=True, offset=None, seed=0, source=None, cage=None):
@@ -1924,6 +1953,206 @@ def _snap_composed(index, pts, nr, cage, want_stats=False):
     m = (g / ln[:, None]).float()
     out = torch.where(hit[:, None], q, pts).contiguous(), torch.where(good[:, None], m, nr).contiguous()
     return out + (hit,) if want_stats else out
+
+
+# ----------------------------------------------------------------------------------------------
+# wall thickness: the shape diameter per point, the thickness map (csrc/mesh_ray.hip sculpt_surface_thickness)
+# ----------------------------------------------------------------------------------------------
+THICKNESS_DIRECTIONS = 32          # what thickness=True means
+THICKNESS_CONE = 60.0              # the half-angle of the cone about the inward normal, in degrees
+
+
+def thickness_rule(thickness):
+    """`thickness` of the wall-thickness queries -> (k, max_distance): True (32 rays, of any length), an int k in 1 .. 1024 or a
+    tuple (k, max_distance) with max_distance > 0 (inf allowed) or None (any length) -- so a rule's own result is a rule.
+    Anything else -- False, None, a str, a bare float, NaN, another length -- is a ValueError, raised here, before anything is
+    launched."""
+    if thickness is True or (isinstance(thickness, np.bool_) and bool(thickness)):
+        return THICKNESS_DIRECTIONS, None
+    if _is_count(thickness, 1, OCCLUSION_MAX_DIRECTIONS):
+        return int(thickness), None
+    if isinstance(thickness, tuple) and len(thickness) == 2 and _is_count(thickness[0], 1, OCCLUSION_MAX_DIRECTIONS):
+        far = thickness[1]
+        if far is None:
+            return int(thickness[0]), None
+        if _is_real(far) and float(far) > 0.0:   # a NaN fails the comparison
+            return int(thickness[0]), float(far)
+    raise ValueError("thickness must be True, an int in 1 .. %d (rays) or (rays, max_distance) with max_distance > 0, got %r"
+                     % (OCCLUSION_MAX_DIRECTIONS, thickness))
+
+
+def thickness_directions(k, cone=THICKNESS_CONE, seed=0):
+    """The k directions of the thickness cone about +z: z_i = 1 - (1 - cos(cone)) (2 i + 1) / (2 k), an area-uniform spiral over
+    the spherical cap of half-angle `cone` degrees (0 < cone <= 90), phi_i = i x the golden angle + seed radians (`seed`, an int
+    in 0 .. 2^31 - 1, rotates the set about z), computed on the host in NumPy fp64, the rows normalised and rounded once ->
+    np.float32 [k, 3], every z in (cos(cone), 1).  k in 1 .. 1024.  Deterministic; needs no device.  The kernel turns the set
+    onto each point's own inward normal."""
+    if not (_is_count(k, 1, OCCLUSION_MAX_DIRECTIONS) and _is_count(seed, 0, 2 ** 31 - 1)):
+        raise ValueError("k must be an int in 1 .. %d and seed an int in 0 .. 2^31 - 1, got k=%r, seed=%r"
+                         % (OCCLUSION_MAX_DIRECTIONS, k, seed))
+    if not (_is_real(cone) and 0.0 < float(cone) <= 90.0):   # a NaN fails the comparison
+        raise ValueError("cone must be a half-angle in degrees with 0 < cone <= 90, got %r" % (cone,))
+    i = np.arange(int(k), dtype=np.float64)
+    z = 1.0 - (1.0 - math.cos(math.radians(float(cone)))) * (2.0 * i + 1.0) / (2.0 * float(int(k)))
+    r = np.sqrt(1.0 - z * z)
+    phi = i * GOLDEN_ANGLE + float(int(seed))
+    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], 1)
+    return (d / np.sqrt((d * d).sum(1, keepdims=True))).astype(np.float32)
+
+
+def _thickness_rules(thickness, cone, offset, seed, outward):
+    """The rules of a thickness call (ValueError, nothing launched) -> (cone set np.float32 [k, 3], far, outward)."""
+    k, far = thickness_rule(thickness)
+    dirs = thickness_directions(k, cone, seed)      # checks the cone and the seed
+    if offset is not None and not (_is_real(offset) and math.isfinite(float(np.float32(offset)))):
+        raise ValueError("offset must be None or a finite number, got %r" % (offset,))
+    if not (_is_real(outward) and float(outward) in (1.0, -1.0)):
+        raise ValueError("outward must be +1 or -1, got %r" % (outward,))
+    return dirs, (math.inf if far is None else float(np.float32(far))), float(outward)
+
+
+def _thickness_args(points, normals, vertices, faces, thickness, cone, offset, seed, outward, who):
+    dirs, far, outward = _thickness_rules(thickness, cone, offset, seed, outward)
+    pts, nrm = _query_points(points, who), _query_points(normals, who)
+    if pts.shape != nrm.shape:
+        raise SculptError("%s: points %s and normals %s differ in shape" % (who, tuple(pts.shape), tuple(nrm.shape)))
+    P, F = _surface(vertices, faces, who)
+    if pts.shape[0] == 0:
+        return None, pts, nrm, None, 0.0, far, outward
+    index = _SurfaceIndex(P, F)
+    if offset is None:
+        offset = OCCLUSION_OFFSET * index.longest_side()
+    return index, pts, nrm, torch.from_numpy(dirs).to(pts.device), float(np.float32(offset)), far, outward
+
+
+def _thickness_empty(dev):
+    return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.float32, device=dev),
+            torch.empty(0, dtype=torch.int32, device=dev))
+
+
+def mesh_thickness(points, normals, vertices, faces, thickness=True, cone=THICKNESS_CONE, offset=None, seed=0, outward=1.0):
+    """The wall thickness -- the shape diameter (Shapira et al.) -- of a triangle mesh at N points with OUTWARD normals, on the
+    device, in ONE launch (sculpt_surface_thickness): how far the rays of a cone about the inward normal travel before they
+    leave the body.  points, normals float [N, 3], vertices float [Nv, 3], faces int32 / int64 [Nf, 3] (device tensors; CPU
+    tensors are refused); thickness: True (32 rays), k or (k, max_distance) (thickness_rule); cone: the half-angle in degrees,
+    0 < cone <= 90, and seed: thickness_directions; offset: how far below the surface the rays start (None: 2^-13 of the longest
+    side of the surface's bounds), rounded to fp32; outward: +1 when the faces wind counter-clockwise seen from outside, -1
+    otherwise.  A bad rule is a ValueError before any launch.
+    -> (thickness f32 [N], thinnest f32 [N], valid int32 [N]).  Per point (the rule at the top of csrc/mesh_ray.hip,
+    "thickness"; fp32 without contraction): m = unit(n); the frame (T, B) of Duff et al. about m; o = p - offset m; for each
+    cone direction C_j in order d = (C_j.x T + C_j.y B) - C_j.z m and the closest hit (t, f) of (o, d) over [0, max_distance] as
+    mesh_ray_cast reports it; the hit is valid iff the ray leaves through the back of f: dot(cross(b - a, c - a), d) outward > 0
+    in fp64 -- a ray that enters another body through a front face, or hits nothing, contributes nothing.  thickness = the mean
+    of fp32(t) over the valid rays weighted by C_j.z, thinnest their minimum, valid their number; no valid ray: +inf, +inf, 0.
+    A non-finite p or n: NaN, NaN, 0.  A zero or overflowing normal, and a surface without faces: +inf, +inf, 0.  The outlier
+    rejection of the shape-diameter paper is left to the caller (thinnest and valid are there to judge by).  Bit for bit what
+    mesh_thickness_composed computes with one mesh_ray_cast per direction (tests/test_gpu_mesh_thickness.py; tests/_thickref.py
+    restates it in NumPy).  N == 0 launches nothing."""
+    index, pts, nrm, dirs, offset, far, outward = _thickness_args(points, normals, vertices, faces, thickness, cone, offset, seed,
+                                                                  outward, "mesh_thickness")
+    if index is None:
+        return _thickness_empty(pts.device)
+    return index.thickness(pts, nrm, dirs, offset, far, outward)
+
+
+def mesh_thickness_composed(points, normals, vertices, faces, thickness=True, cone=THICKNESS_CONE, offset=None, seed=0, outward=1.0):
+    """mesh_thickness by the composed route: the per-point directions in torch in the kernel's expression order, one closest-hit
+    query of every point per cone direction (mesh_ray_cast's kernels on one shared grid, each with its own sort), the back-face
+    test as a torch fp64 gather and the reductions in the kernel's order.  The yardstick the fused kernel is tested (same bits)
+    and timed against (tools/time_thickness.py)."""
+    index, pts, nrm, dirs, offset, far, outward = _thickness_args(points, normals, vertices, faces, thickness, cone, offset, seed,
+                                                                  outward, "mesh_thickness_composed")
+    if index is None:
+        return _thickness_empty(pts.device)
+    return _thickness_composed(index, pts, nrm, dirs, offset, far, outward)
+
+
+def _thickness_composed(index, pts, nrm, dirs, offset, far, outward):
+    """Every line is one elementwise kernel, so nothing is contracted."""
+    n, inf = pts.shape[0], math.inf
+    bad = ~(torch.isfinite(pts).all(1) & torch.isfinite(nrm).all(1))
+    m, ok = _unit3(nrm)
+    ok = ok & ~bad
+    mx, my, mz = m[:, 0], m[:, 1], m[:, 2]
+    sg = torch.copysign(torch.ones_like(mz), mz)
+    a = torch.full_like(mz, -1.0) / (sg + mz)   # a true division of two tensors (a scalar numerator would go through reciprocal)
+    b = (mx * my) * a
+    T = (1.0 + (sg * (mx * mx)) * a, sg * b, -(sg * mx))
+    B = (b, sg + (my * my) * a, -my)
+    o = pts - m * offset                        # fp32: the product rounded, then the difference
+    o = torch.where(ok[:, None], o, torch.full_like(o, math.nan)).contiguous()   # a point that casts nothing: NaN hits nothing
+    sw, swt = torch.zeros_like(mx), torch.zeros_like(mx)
+    thin = torch.full_like(mx, inf)
+    count = torch.zeros(n, dtype=torch.int32, device=pts.device)
+    P, F = index.P.double(), index.F.long()
+    for j in range(dirs.shape[0]):
+        c = dirs[j]
+        d = torch.stack([(T[k] * c[0] + B[k] * c[1]) - m[:, k] * c[2] for k in range(3)], 1).contiguous()
+        t, face, _ = index.ray_cast(o, d, 0.0, far)
+        hit = face >= 0
+        if F.shape[0]:
+            fi = face.clamp(min=0).long()
+            pa, pb, pc = P[F[fi, 0]], P[F[fi, 1]], P[F[fi, 2]]
+            e1, e2 = pb - pa, pc - pa
+            g = (e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                 e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0])
+            dd = d.double()
+            hit = hit & ((((g[0] * dd[:, 0] + g[1] * dd[:, 1]) + g[2] * dd[:, 2]) * outward) > 0)
+        dist = torch.where(hit, t, torch.zeros_like(t)).float()
+        sw = torch.where(hit, sw + c[2], sw)
+        swt = torch.where(hit, swt + c[2] * dist, swt)
+        thin = torch.where(hit, torch.minimum(thin, dist), thin)
+        count = count + hit.to(torch.int32)
+    thick = torch.where(count > 0, swt / sw, torch.full_like(sw, inf))
+    nan = torch.full_like(thick, math.nan)
+    return torch.where(bad, nan, thick), torch.where(bad, nan, thin), count
+
+
+def mesh_thickness_route():
+    """What Mesh.thickness and TSR.bake_thickness_map's point kernel go through: mesh_thickness (one launch), unless
+    SCULPT_DISTANCE_FORM holds the token `composedthickness` (then mesh_thickness_composed).  The two give the same bits; the
+    timings of tools/time_thickness.py are in DESIGN.md 3.3p."""
+    return mesh_thickness_composed if _lib.form_has("SCULPT_DISTANCE_FORM", "composedthickness") else mesh_thickness
+
+
+def _index_thickness(index, pts, nrm, dirs, offset, far, outward):
+    """The point query of the route in force on a shared index (the bake comes through here)."""
+    if _lib.form_has("SCULPT_DISTANCE_FORM", "composedthickness"):
+        return _thickness_composed(index, pts, nrm, dirs, offset, far, outward)
+    return index.thickness(pts, nrm, dirs, offset, far, outward)
+
+
+def bake_thickness(v_pos, faces, normals, rast, thickness=True, cone=THICKNESS_CONE, offset=None, seed=0, outward=1.0, source=None,
+                   cage=None):
+    """The wall thickness of a surface S at every covered texel of a rasterised atlas of a (low-poly) mesh: the thickness map a
+    baker ships beside normal and AO.  v_pos f32 [Nv, 3], faces i32 / i64 [Nf, 3], normals f32 [Nv, 3] per vertex (outward),
+    rast f32 [res, res, 4] from bake_rasterize (device tensors; CPU tensors are refused); thickness, cone, offset, seed, outward:
+    as for mesh_thickness (offset=None: 2^-13 of the longest side of S's bounds).  source / cage: as for bake_occlusion -- None:
+    S is the mesh itself; (vertices, faces): S is that surface and every texel is first snapped onto it (step 4 of the occlusion
+    bake), taking that face's unit normal on n's side.
+    -> (thickness f32, thinnest f32, valid int32, mask bool), each [res, res]: mesh_thickness's values at the covered texels
+    (NaN, NaN, 0 where the interpolated position or normal is not finite), exactly 0, 0, 0 and mask 0 where not covered.
+    The shape of the composed occlusion bake, which these atlases measured as the faster one: the coverage in
+    torch, nonzero, bake_interpolate of the positions and of the normals, the snap, the point kernel over the global cell-sorted
+    list of texels, and a scatter -- no fused tile kernel.  tests/_thickref.py restates the texel rule in NumPy, bit for bit.
+    res == 0 launches nothing."""
+    who = "bake_thickness"
+    dirs, far, outward = _thickness_rules(thickness, cone, offset, seed, outward)
+    _source_rule(who, source, cage)
+    index, v, f, nrm, r, offset, cage = _atlas_query_args(who, v_pos, faces, normals, rast, offset, source, cage)
+    res, dev = r.shape[0], r.device
+    thick = torch.zeros(res * res, dtype=torch.float32, device=dev)
+    thin = torch.zeros(res * res, dtype=torch.float32, device=dev)
+    valid = torch.zeros(res * res, dtype=torch.int32, device=dev)
+    cov, clean = _covered_texels(r, v, f)
+    at = torch.nonzero(cov.reshape(-1))[:, 0] if index is not None else None
+    if at is not None and at.numel():
+        pts = bake_interpolate(v, clean, f).reshape(-1, 3)[at].contiguous()
+        nr = bake_interpolate(nrm, clean, f).reshape(-1, 3)[at].contiguous()
+        if cage > 0.0 and index.F.shape[0]:
+            pts, nr = _snap_composed(index, pts, nr, cage)
+        thick[at], thin[at], valid[at] = _index_thickness(index, pts, nr, torch.from_numpy(dirs).to(dev), offset, far, outward)
+    return thick.view(res, res), thin.view(res, res), valid.view(res, res), cov
 
 
 # ----------------------------------------------------------------------------------------------

@@ -241,6 +241,21 @@ class Mesh:
         normals = float(outward) * ops.vertex_normals(self.vertices, self.faces)
         return ops.mesh_occlusion(self.vertices, normals, self.vertices, self.faces, occlusion, seed=seed)
 
+    def thickness(self, thickness=True, cone=60.0, seed=0, outward=1.0):
+        """Wall thickness per vertex -- the shape diameter -> (thickness f32 [Nv], thinnest f32 [Nv], valid int32 [Nv])
+        (ops.mesh_thickness on this mesh's device tensors; host arrays are refused): the points are the vertices, the normals
+        outward * ops.vertex_normals(vertices, faces) -- always the facet-average normals of THIS mesh.  thickness: True (32
+        rays), k or (k, max_distance) (ops.thickness_rule); cone: the half-angle of the cone about the inward normal, in
+        degrees; seed rotates the cone set; outward: +1 when the faces wind counter-clockwise seen from outside, -1 otherwise
+        (TSR.WINDING_OUTWARD for the meshes of TSR.extract_meshes).  thickness is the weighted mean length of the rays that
+        leave the body through the back of a face, thinnest the shortest of them, valid their number (+inf, +inf, 0 when none
+        did).  The result is returned, not stored."""
+        ops._thickness_rules(thickness, cone, None, seed, outward)   # a ValueError before anything is launched
+        ops._device_mesh(self.vertices, self.faces, "Mesh.thickness")
+        normals = float(outward) * ops.vertex_normals(self.vertices, self.faces)
+        return ops.mesh_thickness_route()(self.vertices, normals, self.vertices, self.faces, thickness, cone=cone, seed=seed,
+                                          outward=float(outward))
+
     def render(self, rays_o, rays_d, passes=("color",), ambient=0.3, light=None, outward=1.0):
         """Pictures of this mesh with everything it carries -- uvs and texture, normal map and its frame, occlusion map, vertex
         colours, normals and occlusion -- ray cast on the device (ops.mesh_render on its device tensors; host arrays are refused

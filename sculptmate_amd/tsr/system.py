@@ -974,6 +974,10 @@ class TSR(KernelEngine):
     # texture bake (bake_displacement_map on the baked mesh's atlas) and leaves it on the mesh as the plain attribute
     # `displacement` (a tsr.displacement.DisplacementMap, no Mesh field).  None: nothing new is launched
     displacement_map = None
+    # None | what ops.thickness_rule accepts (True, k, (k, max_distance)): when set, extract_meshes bakes a thickness map beside a
+    # texture bake (bake_thickness_map on the baked mesh's atlas, against the mesh itself) and leaves it on the mesh as the plain
+    # attribute `thickness` (a tsr.thickness.ThicknessMap, no Mesh field).  None: nothing new is launched
+    thickness_map = None
     # "box" | "charts": the unwrapper _atlas makes when no unwrapper= is passed.  "box": sf3d.unwrap.BoxProjectionUnwrapper, as
     # before.  "charts": sf3d.unwrap.ChartUnwrapper -- charts that are connected pieces of surface, however many layers the
     # object has, shelf-packed.  Anything else is a ValueError before a launch.
@@ -1171,6 +1175,45 @@ class TSR(KernelEngine):
                                                         "corner_normals", "corner_tangents"),
                             uvs=mesh.uvs if mesh.uvs is not None else uv, occlusion_map=ao_map, occlusion_map_rule=rule)
 
+    def bake_thickness_map(self, mesh: Mesh, source=None, resolution=None, thickness=True, cone=60.0, cage=None, seed=0,
+                           island_padding: float = 0.02, unwrapper=None):
+        """The thickness map a baker ships beside normal and AO: the wall thickness -- the shape diameter -- of the HIGH-poly
+        surface in the low-poly mesh's atlas.  Per covered texel the rays of a cone of half-angle `cone` degrees about the
+        inward normal (`thickness`: True = 32 rays, k, or (k, max_distance): ops.thickness_rule; `seed` rotates the set) are
+        followed to where they leave the body through the back of a face; the map holds their weighted mean length
+        (ops.bake_thickness; outward = WINDING_OUTWARD).  source, cage and the atlas: as bake_occlusion_map -- source=None: the
+        mesh against itself, cage must be None; source=a Mesh (the mesh before simplify): every texel is first snapped onto it.
+        Needs a device, no weights.
+        Stages: ops.vertex_normals * WINDING_OUTWARD -> ops.bake_rasterize -> ops.bake_thickness -> ops.dilate_fill with
+        res // 150 rounds on thickness + 1 over the texels with a finite value (what is still 0 afterwards was not reached).
+        -> (mesh, ThicknessMap): the mesh as it came, with uvs; the map (tsr/thickness.py) with thickness (padded), thinnest,
+        valid, mask and rule.  It is no Mesh field: the map has its own save()."""
+        from .thickness import ThicknessMap
+
+        rule = ops.thickness_rule(thickness)   # a ValueError before anything is launched
+        ops._thickness_rules(rule, cone, None, seed, self.WINDING_OUTWARD)
+        if self.device is None:
+            raise _lib.SculptError("TSR.bake_thickness_map: the model is on no device yet (to(device))")
+        if source is not None and not isinstance(source, Mesh):
+            raise ValueError("TSR.bake_thickness_map: source must be a Mesh or None, got %r" % (type(source).__name__,))
+        if source is None and cage is not None:
+            raise ValueError("TSR.bake_thickness_map: cage snaps the texels onto a source; without a source it must be None")
+        res = _atlas_resolution(resolution, mesh, "bake_thickness_map", ("texture", "normal_map", "occlusion_map"))
+        with torch.no_grad():
+            v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper, keep_uvs=True)
+            normals = (self.WINDING_OUTWARD * ops.vertex_normals(v, f)).contiguous()
+            src = None if source is None else (_f32(source.vertices, self.device), torch.as_tensor(source.faces).to(self.device).contiguous())
+            th, thin, valid, mask = ops.bake_thickness(v, f, normals, rast, thickness=rule, cone=cone, seed=seed,
+                                                       outward=self.WINDING_OUTWARD, source=src, cage=cage)
+            known = mask & torch.isfinite(th)
+            shifted = torch.where(known, th + 1.0, torch.zeros_like(th))
+            spread = self._padded(shifted[..., None].expand(res, res, 3), known, res)[..., 0]
+            padded = torch.where(spread != 0, (spread - 1.0).clamp(min=0.0), torch.zeros_like(th))
+            th_map = torch.where(mask, th, padded).contiguous()
+        out = mesh if mesh.uvs is not None else mesh._derive(mesh.vertices, mesh.faces,
+                                                             ("vertex_colors", "vertex_normals", "vertex_occlusion", "quads"), uvs=uv)
+        return out, ThicknessMap(th_map, thin, valid, mask, rule=rule)
+
     def _projected(self, v_pos, t_pos_idx, planes, threshold, project, resolution):
         """ops.mesh_project with this model's field, at _iso_target's target and max_dist (the geometry chain of extract_meshes
         comes here with its checks made: no _iso_search)."""
@@ -1300,6 +1343,8 @@ class TSR(KernelEngine):
             ops.displacement_rule(self.displacement_map)
             if not threshold > 0:
                 raise ValueError("displacement_map needs a positive threshold (the surface is ln(threshold) in the raw density), got %r" % (threshold,))
+        if self.thickness_map is not None:
+            ops.thickness_rule(self.thickness_map)
         if self.bake_project is not None:
             ops.project_rule(self.bake_project)
             if not threshold > 0:
@@ -1436,6 +1481,8 @@ class TSR(KernelEngine):
         if enable_texture and bake > 0 and self.displacement_map is not None:   # the texture's atlas and resolution
             mesh, mesh.displacement = self.bake_displacement_map(mesh, planes, threshold=threshold, displacement=self.displacement_map,
                                                                  resolution=R)
+        if enable_texture and bake > 0 and self.thickness_map is not None:   # the texture's atlas and resolution
+            mesh, mesh.thickness = self.bake_thickness_map(mesh, thickness=self.thickness_map)
         if normals == "field":
             mesh.vertex_normals = self.field_normals(v_pos, planes)
         elif normals == "faces":
