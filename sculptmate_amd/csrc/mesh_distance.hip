@@ -168,10 +168,10 @@ closest_kernel(Grid G, const float *__restrict__ Q, long n, const int64_t *__res
                                 const float dy = fmaxf(fmaxf(r0.y - py, py - r1.x), 0.0f);
                                 const float dz = fmaxf(fmaxf(r0.z - pz, pz - r1.y), 0.0f);
                                 if (dx * dx + dy * dy + dz * dz > thr) continue;
-                                const float4 r2 = rec[4 * (long)f + 2], r3 = rec[4 * (long)f + 3];
+                                D3 ca, cb, cc;
+                                face_corners(rec, f, ca, cb, cc);   // after the box test
                                 const double was = B.d;
-                                consider(B, p, {(double)r1.z, (double)r1.w, (double)r2.x}, {(double)r2.y, (double)r2.z, (double)r2.w},
-                                         {(double)r3.x, (double)r3.y, (double)r3.z}, f);
+                                consider(B, p, ca, cb, cc, f);
                                 if (B.d < was) {
                                     const double t = guard_radius(B.d, E);
                                     thr = (float)(t * t * kCullRel);
@@ -290,20 +290,16 @@ int sculpt_surface_cells(const float *Q, int64_t n, const double *params_host, i
 int sculpt_surface_closest(const float *Q, int64_t n, const int64_t *order, const float *GP, const int32_t *GF, int64_t gnf,
                            const float *records, const int32_t *items, const int32_t *start, const double *params_host, double amax,
                            double *d2, int32_t *face, float *closest, sculpt_stream_t stream) {
-    SC_REQUIRE(n >= 0 && 3 * n < ((int64_t)1 << 40), "surface_closest: n=%lld out of range", (long long)n);
+    if (int rc = check_surface_query("surface_closest", n, amax, gnf, items, start, records, false)) return rc;
     if (int rc = check_grid("surface_closest", GP, GF, gnf, params_host)) return rc;
     SC_REQUIRE((order == nullptr) == (records == nullptr), "surface_closest: the sorted form takes both the order and the records");
-    SC_REQUIRE(amax >= 0 && amax < INFINITY, "surface_closest: amax=%g", amax);  // a NaN fails the comparison
     if (n == 0) return 0;
     SC_REQUIRE(Q && d2 && face && closest, "surface_closest: null array");
-    SC_REQUIRE(gnf == 0 || (items && start), "surface_closest: null grid lists");
     const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
-    if (order) {
-        SC_REQUIRE(aligned16(records), "surface_closest: records not 16-byte aligned");
+    if (order)
         RMD_LAUNCH(closest_kernel<true>, n, G, Q, (long)n, order, reinterpret_cast<const float4 *>(records), amax, d2, face, closest);
-    } else {
+    else
         RMD_LAUNCH(closest_kernel<false>, n, G, Q, (long)n, nullptr, nullptr, amax, d2, face, closest);
-    }
     return 0;
 }
 

@@ -170,7 +170,6 @@ namespace {
 constexpr double kBoxSlack = 0x1p-40;   // E = kBoxSlack * S
 constexpr double kDetRel = 0x1p-60;
 constexpr double kWalkSlack = 4.0;      // W = kWalkSlack * E
-constexpr int kMaxDirections = 1024;
 
 struct Ray {
     D3 o, d;
@@ -285,6 +284,8 @@ __device__ void cast(const Grid &G, const float4 *__restrict__ rec, D3 o, D3 d, 
                         if (!slab(o.y, d.y, inv.y, (double)r0.y, (double)r1.x, W, lo_t, hi_t)) continue;
                         if (!slab(o.z, d.z, inv.z, (double)r0.z, (double)r1.y, W, lo_t, hi_t)) continue;
                         if (lo_t > hi_t) continue;
+                        // face_corners' decoding, spelt out: r1 is in registers already (through the helper every kernel that inlines
+                        // this walk came out 8 bytes longer), and r2 and r3 are read only for a face that passes the box test
                         const float4 r2 = rec[4 * (long)f + 2], r3 = rec[4 * (long)f + 3];
                         consider(B, R, {(double)r1.z, (double)r1.w, (double)r2.x}, {(double)r2.y, (double)r2.z, (double)r2.w},
                                  {(double)r3.x, (double)r3.y, (double)r3.z}, f);
@@ -406,9 +407,8 @@ thickness_kernel(Grid G, const float *__restrict__ P, const float *__restrict__ 
             Hit H = {INFINITY, INT_MAX, 0.0, 0.0};
             cast<true, false>(G, rec, o, d, 0.0, (double)max_distance, amax, H);
             if (H.f == INT_MAX) continue;
-            const float4 r1 = rec[4 * (long)H.f + 1], r2 = rec[4 * (long)H.f + 2], r3 = rec[4 * (long)H.f + 3];
-            const D3 ca = {(double)r1.z, (double)r1.w, (double)r2.x}, cb = {(double)r2.y, (double)r2.z, (double)r2.w},
-                     cc = {(double)r3.x, (double)r3.y, (double)r3.z};
+            D3 ca, cb, cc;
+            face_corners(rec, H.f, ca, cb, cc);
             if (!(dot(cross(cb - ca, cc - ca), d) * outward > 0.0)) continue;   // through a front face: into another body
             const float dist = (float)H.t;
             sw += cz;
@@ -433,9 +433,8 @@ __device__ inline void snap_to_surface(const Grid &G, const float4 *__restrict__
     cast<true, false>(G, rec, o, d, 0.0, 2.0, amax, B);
     if (B.f == INT_MAX) return;
     const D3 h = o + B.t * d;
-    const float4 r1 = rec[4 * (long)B.f + 1], r2 = rec[4 * (long)B.f + 2], r3 = rec[4 * (long)B.f + 3];
-    const D3 a = {(double)r1.z, (double)r1.w, (double)r2.x}, b = {(double)r2.y, (double)r2.z, (double)r2.w},
-             c = {(double)r3.x, (double)r3.y, (double)r3.z};
+    D3 a, b, c;
+    face_corners(rec, B.f, a, b, c);
     D3 g = cross(b - a, c - a);
     if (dot(g, {(double)n[0], (double)n[1], (double)n[2]}) < 0.0) g = {-g.x, -g.y, -g.z};
     const double len = sqrt(dot(g, g));
@@ -600,9 +599,8 @@ __device__ void shade_hit(const Grid &G, const float4 *__restrict__ rec, const M
             done = unit3(n);
         }
         if (!done) {
-            const float4 r1 = rec[4 * f + 1], r2 = rec[4 * f + 2], r3 = rec[4 * f + 3];
-            const D3 a = {(double)r1.z, (double)r1.w, (double)r2.x}, b = {(double)r2.y, (double)r2.z, (double)r2.w},
-                     c = {(double)r3.x, (double)r3.y, (double)r3.z};
+            D3 a, b, c;
+            face_corners(rec, f, a, b, c);
             D3 g = cross(b - a, c - a);
             g = {g.x * outward, g.y * outward, g.z * outward};
             const double len = sqrt(dot(g, g));
@@ -706,21 +704,17 @@ extern "C" {
 int sculpt_surface_ray_cast(const float *O, const float *D, int64_t n, const int64_t *order, const float *GP, const int32_t *GF,
                             int64_t gnf, const float *records, const int32_t *items, const int32_t *start, const double *params_host,
                             double amax, double tmin, double tmax, double *t, int32_t *face, float *uv, sculpt_stream_t stream) {
-    SC_REQUIRE(n >= 0 && 3 * n < ((int64_t)1 << 40), "surface_ray_cast: n=%lld out of range", (long long)n);
-    SC_REQUIRE(amax >= 0 && amax < INFINITY, "surface_ray_cast: amax=%g", amax);  // a NaN fails the comparison
+    if (int rc = check_surface_query("surface_ray_cast", n, amax, gnf, items, start, records, false)) return rc;
     SC_REQUIRE(tmin >= 0 && tmin <= tmax, "surface_ray_cast: the range must satisfy 0 <= tmin <= tmax, got [%g, %g]", tmin, tmax);
     SC_REQUIRE((order == nullptr) == (records == nullptr), "surface_ray_cast: the sorted form takes both the order and the records");
     if (n == 0) return 0;
     if (int rc = check_grid("surface_ray_cast", GP, GF, gnf, params_host)) return rc;
     SC_REQUIRE(O && D && t && face && uv, "surface_ray_cast: null array");
-    SC_REQUIRE(gnf == 0 || (items && start), "surface_ray_cast: null grid lists");
     const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
-    if (order) {
-        SC_REQUIRE(aligned16(records), "surface_ray_cast: records not 16-byte aligned");
+    if (order)
         RMD_LAUNCH(ray_kernel<true>, n, G, O, D, (long)n, order, reinterpret_cast<const float4 *>(records), amax, tmin, tmax, t, face, uv);
-    } else {
+    else
         RMD_LAUNCH(ray_kernel<false>, n, G, O, D, (long)n, nullptr, nullptr, amax, tmin, tmax, t, face, uv);
-    }
     return 0;
 }
 
@@ -728,16 +722,11 @@ int sculpt_surface_occlusion(const float *P, const float *N, int64_t n, const in
                              float max_distance, const float *GP, const int32_t *GF, int64_t gnf, const float *records,
                              const int32_t *items, const int32_t *start, const double *params_host, double amax, float *ao,
                              sculpt_stream_t stream) {
-    SC_REQUIRE(n >= 0 && 3 * n < ((int64_t)1 << 40), "surface_occlusion: n=%lld out of range", (long long)n);
-    SC_REQUIRE(amax >= 0 && amax < INFINITY, "surface_occlusion: amax=%g", amax);  // a NaN fails the comparison
-    SC_REQUIRE(k >= 1 && k <= kMaxDirections, "surface_occlusion: %d directions (1 .. %d)", k, kMaxDirections);
-    SC_REQUIRE(max_distance >= 0, "surface_occlusion: max_distance=%g", (double)max_distance);
-    SC_REQUIRE(isfinite(offset), "surface_occlusion: offset=%g", (double)offset);
+    if (int rc = check_surface_query("surface_occlusion", n, amax, gnf, items, start, records, true)) return rc;
+    if (int rc = check_ray_set("surface_occlusion", k, max_distance, offset)) return rc;
     if (n == 0) return 0;
     if (int rc = check_grid("surface_occlusion", GP, GF, gnf, params_host)) return rc;
     SC_REQUIRE(P && N && dirs && ao, "surface_occlusion: null array");
-    SC_REQUIRE(gnf == 0 || (items && start && records), "surface_occlusion: null grid lists or records");
-    SC_REQUIRE(aligned16(records), "surface_occlusion: records not 16-byte aligned");
     const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
     RMD_LAUNCH(occlusion_kernel, n, G, P, N, (long)n, order, dirs, k, offset, max_distance, reinterpret_cast<const float4 *>(records), amax, ao);
     return 0;
@@ -747,17 +736,12 @@ int sculpt_surface_thickness(const float *P, const float *N, int64_t n, const in
                              float max_distance, double outward, const float *GP, const int32_t *GF, int64_t gnf, const float *records,
                              const int32_t *items, const int32_t *start, const double *params_host, double amax, float *thickness,
                              float *thinnest, int32_t *valid, sculpt_stream_t stream) {
-    SC_REQUIRE(n >= 0 && 3 * n < ((int64_t)1 << 40), "surface_thickness: n=%lld out of range", (long long)n);
-    SC_REQUIRE(amax >= 0 && amax < INFINITY, "surface_thickness: amax=%g", amax);  // a NaN fails the comparison
-    SC_REQUIRE(k >= 1 && k <= kMaxDirections, "surface_thickness: %d directions (1 .. %d)", k, kMaxDirections);
-    SC_REQUIRE(max_distance >= 0, "surface_thickness: max_distance=%g", (double)max_distance);
-    SC_REQUIRE(isfinite(offset), "surface_thickness: offset=%g", (double)offset);
+    if (int rc = check_surface_query("surface_thickness", n, amax, gnf, items, start, records, true)) return rc;
+    if (int rc = check_ray_set("surface_thickness", k, max_distance, offset)) return rc;
     SC_REQUIRE(outward == 1.0 || outward == -1.0, "surface_thickness: outward=%g (+1 or -1)", outward);
     if (n == 0) return 0;
     if (int rc = check_grid("surface_thickness", GP, GF, gnf, params_host)) return rc;
     SC_REQUIRE(P && N && cone_dirs && thickness && thinnest && valid, "surface_thickness: null array");
-    SC_REQUIRE(gnf == 0 || (items && start && records), "surface_thickness: null grid lists or records");
-    SC_REQUIRE(aligned16(records), "surface_thickness: records not 16-byte aligned");
     const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
     RMD_LAUNCH(thickness_kernel, n, G, P, N, (long)n, order, cone_dirs, k, offset, max_distance, outward,
                reinterpret_cast<const float4 *>(records), amax, thickness, thinnest, valid);
@@ -770,18 +754,14 @@ int sculpt_bake_occlusion(const float *rast, int res, const float *v_pos, size_t
                           const double *params_host, double amax, float *ao, uint8_t *mask, sculpt_stream_t stream) {
     SC_REQUIRE(res >= 0 && res <= 32768, "bake_occlusion: resolution %d (0 .. 32768)", res);
     SC_REQUIRE(nv <= (size_t)1 << 40 && nf <= (size_t)1 << 40, "bake_occlusion: mesh too large");
-    SC_REQUIRE(amax >= 0 && amax < INFINITY, "bake_occlusion: amax=%g", amax);  // a NaN fails the comparison
-    SC_REQUIRE(k >= 1 && k <= kMaxDirections, "bake_occlusion: %d directions (1 .. %d)", k, kMaxDirections);
-    SC_REQUIRE(max_distance >= 0, "bake_occlusion: max_distance=%g", (double)max_distance);
-    SC_REQUIRE(isfinite(offset), "bake_occlusion: offset=%g", (double)offset);
+    if (int rc = check_surface_query("bake_occlusion", res, amax, gnf, items, start, records, true)) return rc;   // n: the side, in range
+    if (int rc = check_ray_set("bake_occlusion", k, max_distance, offset)) return rc;
     SC_REQUIRE(cage >= 0 && isfinite(cage), "bake_occlusion: cage=%g (0: no snap, or positive and finite)", (double)cage);
     if (res == 0) return 0;
     if (int rc = check_grid("bake_occlusion", GP, GF, gnf, params_host)) return rc;
     SC_REQUIRE(rast && dirs && ao && mask, "bake_occlusion: null array");
     SC_REQUIRE(aligned16(rast), "bake_occlusion: rast not 16-byte aligned");
     SC_REQUIRE(nf == 0 || (v_pos && faces && v_nrm && nv > 0), "bake_occlusion: null mesh");
-    SC_REQUIRE(gnf == 0 || (items && start && records), "bake_occlusion: null grid lists or records");
-    SC_REQUIRE(aligned16(records), "bake_occlusion: records not 16-byte aligned");
     const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
     const unsigned tiles = (unsigned)((res + kTile - 1) / kTile);
     hipLaunchKernelGGL(cage > 0.0f ? bake_occlusion_kernel<true> : bake_occlusion_kernel<false>, dim3(tiles, tiles, kPasses),
@@ -800,14 +780,12 @@ int sculpt_surface_render(const float *rays_o, const float *rays_d, int64_t n_im
     SC_REQUIRE(n_images <= 65535 && height <= ((int64_t)1 << 19) && width < ((int64_t)1 << 31),
                "surface_render: %lld images of %lld x %lld are too many or too large", (long long)n_images, (long long)height, (long long)width);
     SC_REQUIRE((double)n_images * (double)height * (double)width * 4.0 < 0x1p40, "surface_render: too many rays");
-    SC_REQUIRE(amax >= 0 && amax < INFINITY, "surface_render: amax=%g", amax);  // a NaN fails the comparison
+    if (int rc = check_surface_query("surface_render", n_images * height * width, amax, gnf, items, start, records, true)) return rc;   // n in range
     SC_REQUIRE(isfinite(ambient) && isfinite(outward), "surface_render: ambient=%g, outward=%g", (double)ambient, outward);
     SC_REQUIRE(material && out, "surface_render: null material or outputs");
     if (n_images == 0 || height == 0 || width == 0) return 0;
     if (int rc = check_grid("surface_render", GP, GF, gnf, params_host)) return rc;
     SC_REQUIRE(rays_o && rays_d, "surface_render: null rays");
-    SC_REQUIRE(gnf == 0 || (items && start && records), "surface_render: null grid lists or records");
-    SC_REQUIRE(aligned16(records), "surface_render: records not 16-byte aligned");
     SC_REQUIRE(out->color || out->shaded || out->opacity || out->rgba || out->depth || out->normal || out->occlusion || out->face,
                "surface_render: no pass asked for");
     const sculpt_render_material &m = *material;

@@ -388,19 +388,16 @@ extern "C" {
 int sculpt_surface_winding(const float *Q, int64_t n, const int64_t *order, const float *GP, const int32_t *GF, int64_t gnf,
                            const float *records, const int32_t *items, const int32_t *start, const double *params_host, int32_t *w,
                            sculpt_stream_t stream) {
-    SC_REQUIRE(n >= 0 && 3 * n < ((int64_t)1 << 40), "surface_winding: n=%lld out of range", (long long)n);
+    if (int rc = check_surface_query("surface_winding", n, 0.0 /* the counts take no amax */, gnf, items, start, records, false)) return rc;
     if (int rc = check_grid("surface_winding", GP, GF, gnf, params_host)) return rc;
     SC_REQUIRE((order == nullptr) == (records == nullptr), "surface_winding: the sorted form takes both the order and the records");
     if (n == 0) return 0;
     SC_REQUIRE(Q && w, "surface_winding: null array");
-    SC_REQUIRE(gnf == 0 || (items && start), "surface_winding: null grid lists");
     const Grid G = grid_of(GP, GF, (long)gnf, items, start, params_host);
-    if (order) {
-        SC_REQUIRE(aligned16(records), "surface_winding: records not 16-byte aligned");
+    if (order)
         RMD_LAUNCH(winding_kernel<true>, n, G, Q, (long)n, order, reinterpret_cast<const float4 *>(records), w);
-    } else {
+    else
         RMD_LAUNCH(winding_kernel<false>, n, G, Q, (long)n, nullptr, nullptr, w);
-    }
     return 0;
 }
 

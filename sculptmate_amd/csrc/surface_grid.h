@@ -71,15 +71,46 @@ Grid grid_of(const float *GP, const int32_t *GF, long gnf, const int32_t *items,
     return G;
 }
 
+// The packed record of face f (sculpt_surface_pack, csrc/mesh_distance.hip), 16 floats as four float4: words 0 .. 5 the box (min
+// x, y, z, max x, y, z), words 6 .. 14 the corners a, b, c, word 15 zero.  The corners lie in the last three float4.
+__device__ __forceinline__ void face_corners(const float4 *__restrict__ rec, long f, D3 &a, D3 &b, D3 &c) {
+    const float4 r1 = rec[4 * f + 1], r2 = rec[4 * f + 2], r3 = rec[4 * f + 3];
+    a = {(double)r1.z, (double)r1.w, (double)r2.x};
+    b = {(double)r2.y, (double)r2.z, (double)r2.w};
+    c = {(double)r3.x, (double)r3.y, (double)r3.z};
+}
+
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
-// what the surface queries (csrc/mesh_distance.hip, csrc/mesh_ray.hip) ask of a grid before they launch
+constexpr int kMaxDirections = 1024;
+
+// what the surface queries (csrc/mesh_distance.hip, csrc/mesh_winding.hip, csrc/mesh_ray.hip) ask of a grid before they launch
 inline int check_grid(const char *who, const float *GP, const int32_t *GF, int64_t gnf, const double *params) {
     SC_REQUIRE(gnf >= 0 && 3 * gnf < ((int64_t)1 << 31), "%s: %lld faces do not fit int32 indices", who, (long long)gnf);
     SC_REQUIRE(params, "%s: null grid params", who);
     SC_REQUIRE(gnf == 0 || (GP && GF), "%s: null mesh", who);
     for (int k = 0; k < 3; ++k) SC_REQUIRE(params[4 + k] >= 1 && params[4 + k] <= 1024, "%s: grid side %g (1 .. 1024)", who, params[4 + k]);
     SC_REQUIRE(params[3] > 0 && params[3] < INFINITY, "%s: grid cell %g", who, params[3]);
+    return 0;
+}
+
+// ... of the n queries themselves: a bad n or amax is refused whatever n is, the grid's lists and the records only when there is
+// something to launch (n > 0).  needs_records: the kernel has the packed form only (else null records select the plain form).
+inline int check_surface_query(const char *who, int64_t n, double amax, int64_t gnf, const int32_t *items, const int32_t *start,
+                               const float *records, bool needs_records) {
+    SC_REQUIRE(n >= 0 && 3 * n < ((int64_t)1 << 40), "%s: n=%lld out of range", who, (long long)n);
+    SC_REQUIRE(amax >= 0 && amax < INFINITY, "%s: amax=%g", who, amax);  // a NaN fails the comparison
+    if (n == 0) return 0;
+    SC_REQUIRE(gnf == 0 || (items && start && (records || !needs_records)), "%s: null grid lists%s", who, needs_records ? " or records" : "");
+    SC_REQUIRE(aligned16(records), "%s: records not 16-byte aligned", who);
+    return 0;
+}
+
+// ... and of a set of k rays per query that start `offset` off the point and reach max_distance
+inline int check_ray_set(const char *who, int k, float max_distance, float offset) {
+    SC_REQUIRE(k >= 1 && k <= kMaxDirections, "%s: %d directions (1 .. %d)", who, k, kMaxDirections);
+    SC_REQUIRE(max_distance >= 0, "%s: max_distance=%g", who, (double)max_distance);
+    SC_REQUIRE(isfinite(offset), "%s: offset=%g", who, (double)offset);
     return 0;
 }
 

@@ -25,6 +25,10 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def _opt(t):
+    return _ptr(t) if t is not None else None
+
+
 def _req(t, dtype, name):
     if not (isinstance(t, torch.Tensor) and t.is_cuda):
         raise SculptError("%s must be a CUDA/HIP tensor (no CPU fallback)" % name)
@@ -901,9 +905,20 @@ def _surface(vertices, faces, who):
     return rmd._inputs(vertices, faces, who, allow_repeated=True)
 
 
+def _out(n, dev, *spec):
+    """One uninitialised tensor [n, *shape] per (shape, dtype) of spec: a query's outputs, and with n == 0 its empty result."""
+    return tuple(torch.empty((n,) + shape, dtype=dtype, device=dev) for shape, dtype in spec)
+
+
+_CLOSEST_OUT = (((), torch.float64), ((), torch.int32), ((3,), torch.float32))      # d2, face, closest
+_RAY_OUT = (((), torch.float64), ((), torch.int32), ((2,), torch.float32))          # t, face, uv
+_THICKNESS_OUT = (((), torch.float32), ((), torch.float32), ((), torch.int32))      # thickness, thinnest, valid
+
+
 class _SurfaceIndex:
     """The remesher's uniform grid over a surface, and the packed face records of the sorted query form (built on first use):
-    one index serves the closest-point, ray and occlusion queries of a call."""
+    one index serves the closest-point, ray and occlusion queries of a call.  Every query method is an output allocation and one
+    C call whose surface arguments come from _args."""
 
     def __init__(self, P, F):
         from .sf3d import remesh_device as rmd
@@ -921,25 +936,18 @@ class _SurfaceIndex:
 
     def closest(self, points):
         """points f32 [N, 3] contiguous, N > 0 -> (d2 f64 [N], face int32 [N], closest f32 [N, 3])."""
-        g, dev, n, nf = self.grid, points.device, points.shape[0], self.F.shape[0]
-        d2 = torch.empty(n, dtype=torch.float64, device=dev)
-        face = torch.empty(n, dtype=torch.int32, device=dev)
-        closest = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        order, records = self._sorted(points)
-        check(lib.sculpt_surface_closest(_ptr(points), n, _ptr(order) if order is not None else None, _ptr(self.P) if nf else None,
-                                         _ptr(self.F) if nf else None, nf, _ptr(records) if records is not None else None,
-                                         _ptr(g.items) if nf else None, _ptr(g.start) if nf else None, g.params, float(g.amax),
-                                         _ptr(d2), _ptr(face), _ptr(closest), _stream()))
-        return d2, face, closest
+        n = points.shape[0]
+        out = _out(n, points.device, *_CLOSEST_OUT)
+        order, surface = self._args(self._sorted(points))
+        check(lib.sculpt_surface_closest(_ptr(points), n, _opt(order), *surface, *map(_ptr, out), _stream()))
+        return out
 
     def winding(self, points):
         """points f32 [N, 3] contiguous, N > 0 -> w int32 [N, 3], the axis winding counts (csrc/mesh_winding.hip)."""
         n = points.shape[0]
         w = torch.empty((n, 3), dtype=torch.int32, device=points.device)
-        order, records = self._sorted(points)
-        mesh, grid = self._grid_args()
-        check(lib.sculpt_surface_winding(_ptr(points), n, _ptr(order) if order is not None else None, *mesh,
-                                         _ptr(records) if records is not None else None, *grid[:3], _ptr(w), _stream()))
+        order, surface = self._args(self._sorted(points), amax=False)
+        check(lib.sculpt_surface_winding(_ptr(points), n, _opt(order), *surface, _ptr(w), _stream()))
         return w
 
     def winding_lattice(self, lo, h, n, want_counts=False):
@@ -949,17 +957,18 @@ class _SurfaceIndex:
         dev = self.P.device
         planes = torch.empty((n[0] * n[1], (n[2] + 31) // 32), dtype=torch.int32, device=dev)
         counts = torch.empty((n[0], n[1], n[2], 3), dtype=torch.int32, device=dev)
-        mesh, grid = self._grid_args()
-        check(lib.sculpt_surface_winding_lattice((ctypes.c_double * 3)(*lo), float(h), n[0], n[1], n[2], *mesh,
-                                                 _ptr(self.records()) if self.F.shape[0] else None, *grid[:3], _ptr(planes),
+        _, surface = self._args(amax=False)
+        check(lib.sculpt_surface_winding_lattice((ctypes.c_double * 3)(*lo), float(h), n[0], n[1], n[2], *surface, _ptr(planes),
                                                  _ptr(counts), _stream()))
         return planes, counts if want_counts else None
 
-    def _sorted(self, points, always=False):
-        """(order, records) of the sorted query form for points f32 [N, 3], or (None, None) for the plain form (unless `always`)
-        and for a surface without faces."""
+    def _sorted(self, points=None, always=False):
+        """(order, records) of the sorted query form for points f32 [N, 3] -- None: the faces themselves, by their boxes' least
+        corners -- or (None, None) for the plain form (unless `always`) and for a surface without faces."""
         if (_lib.form_has("SCULPT_DISTANCE_FORM", "plain") and not always) or not self.F.shape[0]:
             return None, None
+        if points is None:
+            points = self.records()[:, :3].contiguous()
         n = points.shape[0]
         key = torch.empty(n, dtype=torch.int32, device=points.device)
         check(lib.sculpt_surface_cells(_ptr(points), n, self.grid.params, _ptr(key), _stream()))
@@ -971,18 +980,23 @@ class _SurfaceIndex:
         return (_ptr(self.P) if nf else None, _ptr(self.F) if nf else None, nf), (_ptr(g.items) if nf else None,
                                                                                    _ptr(g.start) if nf else None, g.params, float(g.amax))
 
+    def _args(self, form=None, amax=True):
+        """What every C query takes of the surface -> (order, [P, F, Nf, records, items, start, params(, amax)]): the order as
+        the tensor (the caller holds it until its launch is issued, and passes _opt(order)), the rest as pointers, None for
+        whatever the form does not have and for every array of a surface without faces.  form: _sorted's (order, records);
+        None: no order and the packed records, for the kernels that have one form and an order of their own."""
+        order, records = form if form is not None else (None, self.records() if self.F.shape[0] else None)
+        mesh, grid = self._grid_args()
+        return order, [*mesh, _opt(records), *(grid if amax else grid[:3])]
+
     def ray_cast(self, origins, directions, t_min=0.0, t_max=math.inf):
         """origins, directions f32 [N, 3] contiguous, N > 0 -> (t f64 [N], face int32 [N], uv f32 [N, 2])."""
-        dev, n = origins.device, origins.shape[0]
-        t = torch.empty(n, dtype=torch.float64, device=dev)
-        face = torch.empty(n, dtype=torch.int32, device=dev)
-        uv = torch.empty((n, 2), dtype=torch.float32, device=dev)
-        order, records = self._sorted(origins)   # by the cell of the origin
-        mesh, grid = self._grid_args()
-        check(lib.sculpt_surface_ray_cast(_ptr(origins), _ptr(directions), n, _ptr(order) if order is not None else None, *mesh,
-                                          _ptr(records) if records is not None else None, *grid, float(t_min), float(t_max),
-                                          _ptr(t), _ptr(face), _ptr(uv), _stream()))
-        return t, face, uv
+        n = origins.shape[0]
+        out = _out(n, origins.device, *_RAY_OUT)
+        order, surface = self._args(self._sorted(origins))   # by the cell of the origin
+        check(lib.sculpt_surface_ray_cast(_ptr(origins), _ptr(directions), n, _opt(order), *surface, float(t_min), float(t_max),
+                                          *map(_ptr, out), _stream()))
+        return out
 
     def longest_side(self):
         """The longest side of the surface's bounds (0 without faces): the grid has read them back."""
@@ -993,27 +1007,20 @@ class _SurfaceIndex:
         points are sorted by cell whatever SCULPT_DISTANCE_FORM says (the fused kernel has one form)."""
         n = points.shape[0]
         ao = torch.empty(n, dtype=torch.float32, device=points.device)
-        order, records = self._sorted(points, always=True)
-        mesh, grid = self._grid_args()
-        check(lib.sculpt_surface_occlusion(_ptr(points), _ptr(normals), n, _ptr(order) if order is not None else None, _ptr(dirs),
-                                           dirs.shape[0], float(offset), float(max_distance), *mesh,
-                                           _ptr(records) if records is not None else None, *grid, _ptr(ao), _stream()))
+        order, surface = self._args(self._sorted(points, always=True))
+        check(lib.sculpt_surface_occlusion(_ptr(points), _ptr(normals), n, _opt(order), _ptr(dirs), dirs.shape[0], float(offset),
+                                           float(max_distance), *surface, _ptr(ao), _stream()))
         return ao
 
     def thickness(self, points, normals, cone_dirs, offset, max_distance, outward):
         """points, normals f32 [N, 3], cone_dirs f32 [K, 3], all contiguous on the device, N > 0 -> (thickness f32 [N], thinnest
         f32 [N], valid int32 [N]) in ONE launch (sculpt_surface_thickness); the points are always sorted by cell."""
-        n, dev = points.shape[0], points.device
-        thick = torch.empty(n, dtype=torch.float32, device=dev)
-        thin = torch.empty(n, dtype=torch.float32, device=dev)
-        valid = torch.empty(n, dtype=torch.int32, device=dev)
-        order, records = self._sorted(points, always=True)
-        mesh, grid = self._grid_args()
-        check(lib.sculpt_surface_thickness(_ptr(points), _ptr(normals), n, _ptr(order) if order is not None else None,
-                                           _ptr(cone_dirs), cone_dirs.shape[0], float(offset), float(max_distance), float(outward),
-                                           *mesh, _ptr(records) if records is not None else None, *grid, _ptr(thick), _ptr(thin),
-                                           _ptr(valid), _stream()))
-        return thick, thin, valid
+        n = points.shape[0]
+        out = _out(n, points.device, *_THICKNESS_OUT)
+        order, surface = self._args(self._sorted(points, always=True))
+        check(lib.sculpt_surface_thickness(_ptr(points), _ptr(normals), n, _opt(order), _ptr(cone_dirs), cone_dirs.shape[0], float(offset),
+                                           float(max_distance), float(outward), *surface, *map(_ptr, out), _stream()))
+        return out
 
 
 def _query_points(points, who):
@@ -1025,11 +1032,7 @@ def _query_points(points, who):
 
 
 def _closest(index, points):
-    if points.shape[0] == 0:
-        dev = points.device
-        return (torch.empty(0, dtype=torch.float64, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
-                torch.empty((0, 3), dtype=torch.float32, device=dev))
-    d2, face, closest = index.closest(points)
+    d2, face, closest = index.closest(points) if points.shape[0] else _out(0, points.device, *_CLOSEST_OUT)
     return d2, face.long(), closest
 
 
@@ -1049,9 +1052,7 @@ def mesh_closest_points(points, vertices, faces):
       - the host reads back the input check's status and the grid's two small results (bounds, list length)."""
     pts = _query_points(points, "mesh_closest_points")
     P, F = _surface(vertices, faces, "mesh_closest_points")
-    if pts.shape[0] == 0:
-        return _closest(None, pts)
-    return _closest(_SurfaceIndex(P, F), pts)
+    return _closest(_SurfaceIndex(P, F) if pts.shape[0] else None, pts)
 
 
 def _weights(P, F):
@@ -1194,8 +1195,7 @@ def mesh_signed_distance(points, vertices, faces):
     pts = _query_points(points, "mesh_signed_distance")
     P, F = _surface(vertices, faces, "mesh_signed_distance")
     if pts.shape[0] == 0:
-        d2, face, closest = _closest(None, pts)
-        return d2, face, closest
+        return _closest(None, pts)
     index = _SurfaceIndex(P, F)
     d2, face, closest = _closest(index, pts)
     sd = torch.sqrt(d2)
@@ -1332,17 +1332,11 @@ def _self_intersections(P, F, pairs, max_pairs):
     readback of the two totals, emit."""
     dev, nf = P.device, F.shape[0]
     index = _SurfaceIndex(P, F)
-    order = records = None
-    if not _lib.form_has("SCULPT_DISTANCE_FORM", "plain"):
-        records = index.records()
-        key = torch.empty(nf, dtype=torch.int32, device=dev)
-        check(lib.sculpt_surface_cells(_ptr(records[:, :3].contiguous()), nf, index.grid.params, _ptr(key), _stream()))   # the box's least corner
-        order = torch.sort(key, stable=True).indices
-    mesh, grid = index._grid_args()
-    form = (_ptr(order) if order is not None else None, _ptr(records) if records is not None else None)
+    order, surface = index._args(index._sorted(), amax=False)   # the faces in the order of their boxes' least corners
+    surface[3:3] = [_opt(order)]                                     # these two take the order between the mesh and the records
     n = torch.empty(nf, dtype=torch.int32, device=dev)
     flag = torch.zeros(nf, dtype=torch.uint8, device=dev)
-    check(lib.sculpt_surface_self_count(*mesh, *form, *grid[:3], _ptr(n), _ptr(flag), _stream()))
+    check(lib.sculpt_surface_self_count(*surface, _ptr(n), _ptr(flag), _stream()))
     offsets = torch.zeros(nf + 1, dtype=torch.int64, device=dev)
     offsets[1:] = torch.cumsum(n, 0, dtype=torch.int64)
     total, flagged = torch.stack([offsets[-1], flag.sum()]).tolist()
@@ -1352,7 +1346,7 @@ def _self_intersections(P, F, pairs, max_pairs):
         raise SculptError("mesh_self_intersections: %d intersecting pairs exceed max_pairs=%d" % (total, max_pairs))
     keys = torch.empty(total, dtype=torch.int64, device=dev)
     if total:
-        check(lib.sculpt_surface_self_emit(*mesh, *form, *grid[:3], _ptr(offsets), _ptr(keys), total, _stream()))
+        check(lib.sculpt_surface_self_emit(*surface, _ptr(offsets), _ptr(keys), total, _stream()))
         keys = torch.sort(keys).values
     return total, flagged, flag, torch.stack([keys >> 32, keys & 0xFFFFFFFF], 1)
 
@@ -1674,27 +1668,53 @@ def mesh_ray_cast(origins, directions, vertices, faces, t_min=0.0, t_max=math.in
 
 
 def _ray_cast(index, o, d, t_min, t_max):
-    if o.shape[0] == 0:
-        dev = o.device
-        return (torch.empty(0, dtype=torch.float64, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
-                torch.empty((0, 2), dtype=torch.float32, device=dev))
-    t, face, uv = index.ray_cast(o, d, t_min, t_max)
+    t, face, uv = index.ray_cast(o, d, t_min, t_max) if o.shape[0] else _out(0, o.device, *_RAY_OUT)
     return t, face.long(), uv
+
+
+def _spiral(k, seed, z):
+    """The golden-angle spiral with the heights z(i, k) of an fp64 index vector i: unit rows np.float32 [k, 3], rounded once."""
+    if not (_is_count(k, 1, OCCLUSION_MAX_DIRECTIONS) and _is_count(seed, 0, 2 ** 31 - 1)):
+        raise ValueError("k must be an int in 1 .. %d and seed an int in 0 .. 2^31 - 1, got k=%r, seed=%r"
+                         % (OCCLUSION_MAX_DIRECTIONS, k, seed))
+    i = np.arange(int(k), dtype=np.float64)
+    z = z(i, float(int(k)))
+    r = np.sqrt(1.0 - z * z)
+    phi = i * GOLDEN_ANGLE + float(int(seed))
+    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], 1)
+    return (d / np.sqrt((d * d).sum(1, keepdims=True))).astype(np.float32)
+
+
+def _ray_count_rule(x, default, name, rays):
+    """occlusion_rule and thickness_rule: True -> (default, None), k -> (k, None), (k, max_distance or None) -> itself."""
+    if x is True or (isinstance(x, np.bool_) and bool(x)):
+        return default, None
+    if _is_count(x, 1, OCCLUSION_MAX_DIRECTIONS):
+        return int(x), None
+    if isinstance(x, tuple) and len(x) == 2 and _is_count(x[0], 1, OCCLUSION_MAX_DIRECTIONS):
+        far = x[1]
+        if far is None:
+            return int(x[0]), None
+        if _is_real(far) and float(far) > 0.0:   # a NaN fails the comparison
+            return int(x[0]), float(far)
+    raise ValueError("%s must be True, an int in 1 .. %d (%s) or (%s, max_distance) with max_distance > 0, got %r"
+                     % (name, OCCLUSION_MAX_DIRECTIONS, rays, rays, x))
+
+
+def _offset_rule(offset):
+    if offset is not None and not (_is_real(offset) and math.isfinite(float(np.float32(offset)))):
+        raise ValueError("offset must be None or a finite number, got %r" % (offset,))
+
+
+def _far32(far):
+    return math.inf if far is None else float(np.float32(far))
 
 
 def occlusion_directions(k, seed=0):
     """The k directions of the ambient occlusion: the golden-angle spiral on the unit sphere, z_i = 1 - (2 i + 1) / k,
     phi_i = i x the golden angle + seed radians (`seed`, an int in 0 .. 2^31 - 1, rotates the set about z), computed on the host
     in NumPy fp64 and rounded once -> np.float32 [k, 3].  k in 1 .. 1024.  Deterministic; needs no device."""
-    if not (_is_count(k, 1, OCCLUSION_MAX_DIRECTIONS) and _is_count(seed, 0, 2 ** 31 - 1)):
-        raise ValueError("k must be an int in 1 .. %d and seed an int in 0 .. 2^31 - 1, got k=%r, seed=%r"
-                         % (OCCLUSION_MAX_DIRECTIONS, k, seed))
-    i = np.arange(int(k), dtype=np.float64)
-    z = 1.0 - (2.0 * i + 1.0) / float(int(k))
-    r = np.sqrt(1.0 - z * z)
-    phi = i * GOLDEN_ANGLE + float(int(seed))
-    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], 1)
-    return (d / np.sqrt((d * d).sum(1, keepdims=True))).astype(np.float32)
+    return _spiral(k, seed, lambda i, k: 1.0 - (2.0 * i + 1.0) / k)
 
 
 def occlusion_rule(occlusion):
@@ -1702,36 +1722,40 @@ def occlusion_rule(occlusion):
     1 .. 1024 or a tuple (k, max_distance) with max_distance > 0 (inf allowed) or None (any length) -- so a rule's own result is
     a rule.  Anything else -- False, None, a str, a bare float, NaN, another length -- is a ValueError, raised here, before
     anything is launched."""
-    if occlusion is True or (isinstance(occlusion, np.bool_) and bool(occlusion)):
-        return OCCLUSION_DIRECTIONS, None
-    if _is_count(occlusion, 1, OCCLUSION_MAX_DIRECTIONS):
-        return int(occlusion), None
-    if isinstance(occlusion, tuple) and len(occlusion) == 2 and _is_count(occlusion[0], 1, OCCLUSION_MAX_DIRECTIONS):
-        far = occlusion[1]
-        if far is None:
-            return int(occlusion[0]), None
-        if _is_real(far) and float(far) > 0.0:   # a NaN fails the comparison
-            return int(occlusion[0]), float(far)
-    raise ValueError("occlusion must be True, an int in 1 .. %d (directions) or (directions, max_distance) with max_distance > 0, "
-                     "got %r" % (OCCLUSION_MAX_DIRECTIONS, occlusion))
+    return _ray_count_rule(occlusion, OCCLUSION_DIRECTIONS, "occlusion", "directions")
 
 
-def _occlusion_args(points, normals, vertices, faces, occlusion, offset, seed, who):
+def _occlusion_rules(occlusion, offset, seed):
+    """The rules of an occlusion call (ValueError, nothing launched) -> (directions np.float32 [k, 3], far)."""
     k, far = occlusion_rule(occlusion)
-    if offset is not None and not (_is_real(offset) and math.isfinite(float(np.float32(offset)))):
-        raise ValueError("offset must be None or a finite number, got %r" % (offset,))
-    dirs = occlusion_directions(k, seed)      # checks the seed
+    _offset_rule(offset)
+    return occlusion_directions(k, seed), _far32(far)      # checks the seed
+
+
+def _offset32(index, offset):
+    """The origin offset of a ray query rounded to fp32; None: 2^-13 of the longest side of the index's surface."""
+    return float(np.float32(OCCLUSION_OFFSET * index.longest_side() if offset is None else offset))
+
+
+def _point_query_args(who, points, normals, vertices, faces, dirs, offset):
+    """The tensors of a query of points with normals, checked (SculptError) after the caller's rules, then the index with the
+    defaults that depend on its bounds -> (index or None when N == 0, pts, nrm, dirs on the device, offset rounded to fp32)."""
     pts, nrm = _query_points(points, who), _query_points(normals, who)
     if pts.shape != nrm.shape:
         raise SculptError("%s: points %s and normals %s differ in shape" % (who, tuple(pts.shape), tuple(nrm.shape)))
     P, F = _surface(vertices, faces, who)
     if pts.shape[0] == 0:
-        return None, pts, nrm, None, 0.0, math.inf
+        return None, pts, nrm, None, 0.0
     index = _SurfaceIndex(P, F)
-    if offset is None:
-        offset = OCCLUSION_OFFSET * index.longest_side()
-    far = math.inf if far is None else float(np.float32(far))
-    return index, pts, nrm, torch.from_numpy(dirs).to(pts.device), float(np.float32(offset)), far
+    return index, pts, nrm, torch.from_numpy(dirs).to(pts.device), _offset32(index, offset)
+
+
+def _mesh_occlusion(who, fused, points, normals, vertices, faces, occlusion, offset, seed):
+    dirs, far = _occlusion_rules(occlusion, offset, seed)
+    index, pts, nrm, dirs, offset = _point_query_args(who, points, normals, vertices, faces, dirs, offset)
+    if index is None:
+        return torch.empty(0, dtype=torch.float32, device=pts.device)
+    return index.occlusion(pts, nrm, dirs, offset, far) if fused else _occlusion_composed(index, pts, nrm, dirs, offset, far)
 
 
 def mesh_occlusion(points, normals, vertices, faces, occlusion=True, offset=None, seed=0):
@@ -1746,21 +1770,14 @@ def mesh_occlusion(points, normals, vertices, faces, occlusion=True, offset=None
     taking-part w_k), both in the order of k; 1 when no direction takes part (a zero normal); NaN for a non-finite p or n.  The
     normals are used as given (not normalised: ao is a ratio).  Bit for bit what mesh_occlusion_composed computes with one
     mesh_ray_cast per direction (tests/test_gpu_mesh_ray.py).  N == 0 launches nothing."""
-    index, pts, nrm, dirs, offset, far = _occlusion_args(points, normals, vertices, faces, occlusion, offset, seed, "mesh_occlusion")
-    if index is None:
-        return torch.empty(0, dtype=torch.float32, device=pts.device)
-    return index.occlusion(pts, nrm, dirs, offset, far)
+    return _mesh_occlusion("mesh_occlusion", True, points, normals, vertices, faces, occlusion, offset, seed)
 
 
 def mesh_occlusion_composed(points, normals, vertices, faces, occlusion=True, offset=None, seed=0):
     """mesh_occlusion by the composed route: one closest-hit query of every point per direction (mesh_ray_cast's kernels on one
     shared grid) and torch reductions in the kernel's order.  The yardstick the fused kernel is tested (same bits) and timed
     against (tools/time_occlusion.py); K launches and K sorts instead of one."""
-    index, pts, nrm, dirs, offset, far = _occlusion_args(points, normals, vertices, faces, occlusion, offset, seed,
-                                                         "mesh_occlusion_composed")
-    if index is None:
-        return torch.empty(0, dtype=torch.float32, device=pts.device)
-    return _occlusion_composed(index, pts, nrm, dirs, offset, far)
+    return _mesh_occlusion("mesh_occlusion_composed", False, points, normals, vertices, faces, occlusion, offset, seed)
 
 
 def _occlusion_composed(index, pts, nrm, dirs, offset, far):
@@ -1817,16 +1834,10 @@ def _covered_texels(r, v, f):
 def _bake_occlusion_args(who, v_pos, faces, normals, rast, occlusion, offset, seed, source, cage):
     """Rules first (ValueError, nothing launched), then the tensors (SculptError), then the index over S.
     -> (index or None when res == 0, v, f, nrm, rast, dirs, offset, far, cage)."""
-    k, far = occlusion_rule(occlusion)
-    if offset is not None and not (_is_real(offset) and math.isfinite(float(np.float32(offset)))):
-        raise ValueError("offset must be None or a finite number, got %r" % (offset,))
-    dirs = occlusion_directions(k, seed)      # checks the seed
+    dirs, far = _occlusion_rules(occlusion, offset, seed)
     _source_rule(who, source, cage)
     index, v, f, nrm, r, offset, cage = _atlas_query_args(who, v_pos, faces, normals, rast, offset, source, cage)
-    if index is None:
-        return None, v, f, nrm, r, None, 0.0, math.inf, 0.0
-    far = math.inf if far is None else float(np.float32(far))
-    return index, v, f, nrm, r, torch.from_numpy(dirs).to(v.device), offset, far, cage
+    return index, v, f, nrm, r, torch.from_numpy(dirs).to(v.device) if index is not None else None, offset, far, cage
 
 
 def _source_rule(who, source, cage):
@@ -1855,13 +1866,11 @@ def _atlas_query_args(who, v_pos, faces, normals, rast, offset, source, cage):
     if r.shape[0] == 0:
         return None, v, f, nrm, r, 0.0, 0.0
     index = _SurfaceIndex(P, F)
-    if offset is None:
-        offset = OCCLUSION_OFFSET * index.longest_side()
     if source is None:
         cage = 0.0
     elif cage is None:
         cage = OCCLUSION_CAGE * index.longest_side()
-    return index, v, f, nrm, r, float(np.float32(offset)), float(np.float32(cage))
+    return index, v, f, nrm, r, _offset32(index, offset), float(np.float32(cage))
 
 
 def bake_occlusion(v_pos, faces, normals, rast, occlusion=True, offset=None, seed=0, source=None, cage=None):
@@ -1889,11 +1898,9 @@ def _bake_occlusion_fused(index, v, f, nrm, r, dirs, offset, far, cage):
     mask = torch.empty((res, res), dtype=torch.uint8, device=r.device)
     if index is None:
         return ao, mask.view(torch.bool)
-    mesh, grid = index._grid_args()
-    records = index.records() if index.F.shape[0] else None
+    _, surface = index._args()
     check(lib.sculpt_bake_occlusion(_ptr(r), res, _ptr(v), v.shape[0], _ptr(f), int(f.dtype == torch.int64), f.shape[0], _ptr(nrm),
-                                    _ptr(dirs), dirs.shape[0], offset, far, cage, *mesh, _ptr(records), *grid, _ptr(ao), _ptr(mask),
-                                    _stream()))
+                                    _ptr(dirs), dirs.shape[0], offset, far, cage, *surface, _ptr(ao), _ptr(mask), _stream()))
     return ao, mask.view(torch.bool)
 
 
@@ -1907,20 +1914,27 @@ def bake_occlusion_composed(v_pos, faces, normals, rast, occlusion=True, offset=
     return _bake_occlusion_composed(index, v, f, nrm, r, dirs, offset, far, cage)
 
 
-def _bake_occlusion_composed(index, v, f, nrm, r, dirs, offset, far, cage):
-    res = r.shape[0]
-    ao = torch.zeros(res * res, dtype=torch.float32, device=r.device)
+def _atlas_points(index, v, f, nrm, r, cage):
+    """The composed atlas route up to its point query: the coverage in torch, nonzero, bake_interpolate of the positions and of
+    the normals, the snap -> (cov bool [res, res], at i64 [M] the covered texels' flat indices, pts f32 [M, 3], nr f32 [M, 3]);
+    at, pts and nr are None when nothing is covered or the index is None (res == 0)."""
     cov, clean = _covered_texels(r, v, f)
-    if index is None:
-        return ao.view(res, res), cov
-    at = torch.nonzero(cov.reshape(-1))[:, 0]
-    if at.numel() == 0:
-        return ao.view(res, res), cov
+    at = torch.nonzero(cov.reshape(-1))[:, 0] if index is not None else None
+    if at is None or at.numel() == 0:
+        return cov, None, None, None
     pts = bake_interpolate(v, clean, f).reshape(-1, 3)[at].contiguous()
     nr = bake_interpolate(nrm, clean, f).reshape(-1, 3)[at].contiguous()
     if cage > 0.0 and index.F.shape[0]:
         pts, nr = _snap_composed(index, pts, nr, cage)
-    ao[at] = index.occlusion(pts, nr, dirs, offset, far)
+    return cov, at, pts, nr
+
+
+def _bake_occlusion_composed(index, v, f, nrm, r, dirs, offset, far, cage):
+    res = r.shape[0]
+    ao = torch.zeros(res * res, dtype=torch.float32, device=r.device)
+    cov, at, pts, nr = _atlas_points(index, v, f, nrm, r, cage)
+    if at is not None:
+        ao[at] = index.occlusion(pts, nr, dirs, offset, far)
     return ao.view(res, res), cov
 
 
@@ -1932,6 +1946,16 @@ def bake_occlusion_route():
     return bake_occlusion if _lib.form_has("SCULPT_DISTANCE_FORM", "fusedbake") else bake_occlusion_composed
 
 
+def _face_cross64(P64, i0, i1, i2):
+    """cross(b - a, c - a) of the corners a, b, c = P64[i0], P64[i1], P64[i2] of n faces, in fp64 -> (gx, gy, gz), each [n]: P64 f64
+    [Nv, 3], i0, i1, i2 i64 [n] (the columns of F[fi]: the render has them already, so they are not gathered here a second time);
+    every component is a difference of two products, each its own elementwise kernel, so nothing is contracted."""
+    a, b, c = P64[i0], P64[i1], P64[i2]
+    e1, e2 = b - a, c - a
+    return (e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+            e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0])
+
+
 def _snap_composed(index, pts, nr, cage, want_stats=False):
     """Step 4 of the atlas bake in torch: every operation is one elementwise kernel, so nothing is contracted."""
     c = nr * cage                                # fp32
@@ -1940,11 +1964,8 @@ def _snap_composed(index, pts, nr, cage, want_stats=False):
     hit = face >= 0
     fi = face.clamp(min=0).long()
     q = (o.double() + t[:, None] * d.double()).float()          # a product, a sum, one rounding to fp32
-    P, F = index.P.double(), index.F.long()
-    a, b, cc = P[F[fi, 0]], P[F[fi, 1]], P[F[fi, 2]]
-    e1, e2 = b - a, cc - a
-    g = torch.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
-                     e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
+    F = index.F.long()
+    g = torch.stack(_face_cross64(index.P.double(), F[fi, 0], F[fi, 1], F[fi, 2]), 1)
     nd = nr.double()
     flip = ((g[:, 0] * nd[:, 0] + g[:, 1] * nd[:, 1]) + g[:, 2] * nd[:, 2]) < 0
     g = torch.where(flip[:, None], -g, g)
@@ -1967,18 +1988,7 @@ def thickness_rule(thickness):
     tuple (k, max_distance) with max_distance > 0 (inf allowed) or None (any length) -- so a rule's own result is a rule.
     Anything else -- False, None, a str, a bare float, NaN, another length -- is a ValueError, raised here, before anything is
     launched."""
-    if thickness is True or (isinstance(thickness, np.bool_) and bool(thickness)):
-        return THICKNESS_DIRECTIONS, None
-    if _is_count(thickness, 1, OCCLUSION_MAX_DIRECTIONS):
-        return int(thickness), None
-    if isinstance(thickness, tuple) and len(thickness) == 2 and _is_count(thickness[0], 1, OCCLUSION_MAX_DIRECTIONS):
-        far = thickness[1]
-        if far is None:
-            return int(thickness[0]), None
-        if _is_real(far) and float(far) > 0.0:   # a NaN fails the comparison
-            return int(thickness[0]), float(far)
-    raise ValueError("thickness must be True, an int in 1 .. %d (rays) or (rays, max_distance) with max_distance > 0, got %r"
-                     % (OCCLUSION_MAX_DIRECTIONS, thickness))
+    return _ray_count_rule(thickness, THICKNESS_DIRECTIONS, "thickness", "rays")
 
 
 def thickness_directions(k, cone=THICKNESS_CONE, seed=0):
@@ -1987,47 +1997,32 @@ def thickness_directions(k, cone=THICKNESS_CONE, seed=0):
     in 0 .. 2^31 - 1, rotates the set about z), computed on the host in NumPy fp64, the rows normalised and rounded once ->
     np.float32 [k, 3], every z in (cos(cone), 1).  k in 1 .. 1024.  Deterministic; needs no device.  The kernel turns the set
     onto each point's own inward normal."""
-    if not (_is_count(k, 1, OCCLUSION_MAX_DIRECTIONS) and _is_count(seed, 0, 2 ** 31 - 1)):
-        raise ValueError("k must be an int in 1 .. %d and seed an int in 0 .. 2^31 - 1, got k=%r, seed=%r"
-                         % (OCCLUSION_MAX_DIRECTIONS, k, seed))
-    if not (_is_real(cone) and 0.0 < float(cone) <= 90.0):   # a NaN fails the comparison
-        raise ValueError("cone must be a half-angle in degrees with 0 < cone <= 90, got %r" % (cone,))
-    i = np.arange(int(k), dtype=np.float64)
-    z = 1.0 - (1.0 - math.cos(math.radians(float(cone)))) * (2.0 * i + 1.0) / (2.0 * float(int(k)))
-    r = np.sqrt(1.0 - z * z)
-    phi = i * GOLDEN_ANGLE + float(int(seed))
-    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], 1)
-    return (d / np.sqrt((d * d).sum(1, keepdims=True))).astype(np.float32)
+    def z(i, k):   # after the spiral's own check of k and seed, as ever
+        if not (_is_real(cone) and 0.0 < float(cone) <= 90.0):   # a NaN fails the comparison
+            raise ValueError("cone must be a half-angle in degrees with 0 < cone <= 90, got %r" % (cone,))
+        return 1.0 - (1.0 - math.cos(math.radians(float(cone)))) * (2.0 * i + 1.0) / (2.0 * k)
+
+    return _spiral(k, seed, z)
 
 
 def _thickness_rules(thickness, cone, offset, seed, outward):
     """The rules of a thickness call (ValueError, nothing launched) -> (cone set np.float32 [k, 3], far, outward)."""
     k, far = thickness_rule(thickness)
     dirs = thickness_directions(k, cone, seed)      # checks the cone and the seed
-    if offset is not None and not (_is_real(offset) and math.isfinite(float(np.float32(offset)))):
-        raise ValueError("offset must be None or a finite number, got %r" % (offset,))
+    _offset_rule(offset)
     if not (_is_real(outward) and float(outward) in (1.0, -1.0)):
         raise ValueError("outward must be +1 or -1, got %r" % (outward,))
-    return dirs, (math.inf if far is None else float(np.float32(far))), float(outward)
+    return dirs, _far32(far), float(outward)
 
 
-def _thickness_args(points, normals, vertices, faces, thickness, cone, offset, seed, outward, who):
+def _mesh_thickness(who, fused, points, normals, vertices, faces, thickness, cone, offset, seed, outward):
     dirs, far, outward = _thickness_rules(thickness, cone, offset, seed, outward)
-    pts, nrm = _query_points(points, who), _query_points(normals, who)
-    if pts.shape != nrm.shape:
-        raise SculptError("%s: points %s and normals %s differ in shape" % (who, tuple(pts.shape), tuple(nrm.shape)))
-    P, F = _surface(vertices, faces, who)
-    if pts.shape[0] == 0:
-        return None, pts, nrm, None, 0.0, far, outward
-    index = _SurfaceIndex(P, F)
-    if offset is None:
-        offset = OCCLUSION_OFFSET * index.longest_side()
-    return index, pts, nrm, torch.from_numpy(dirs).to(pts.device), float(np.float32(offset)), far, outward
-
-
-def _thickness_empty(dev):
-    return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.float32, device=dev),
-            torch.empty(0, dtype=torch.int32, device=dev))
+    index, pts, nrm, dirs, offset = _point_query_args(who, points, normals, vertices, faces, dirs, offset)
+    if index is None:
+        return _out(0, pts.device, *_THICKNESS_OUT)
+    if fused:
+        return index.thickness(pts, nrm, dirs, offset, far, outward)
+    return _thickness_composed(index, pts, nrm, dirs, offset, far, outward)
 
 
 def mesh_thickness(points, normals, vertices, faces, thickness=True, cone=THICKNESS_CONE, offset=None, seed=0, outward=1.0):
@@ -2048,11 +2043,7 @@ def mesh_thickness(points, normals, vertices, faces, thickness=True, cone=THICKN
     rejection of the shape-diameter paper is left to the caller (thinnest and valid are there to judge by).  Bit for bit what
     mesh_thickness_composed computes with one mesh_ray_cast per direction (tests/test_gpu_mesh_thickness.py; tests/_thickref.py
     restates it in NumPy).  N == 0 launches nothing."""
-    index, pts, nrm, dirs, offset, far, outward = _thickness_args(points, normals, vertices, faces, thickness, cone, offset, seed,
-                                                                  outward, "mesh_thickness")
-    if index is None:
-        return _thickness_empty(pts.device)
-    return index.thickness(pts, nrm, dirs, offset, far, outward)
+    return _mesh_thickness("mesh_thickness", True, points, normals, vertices, faces, thickness, cone, offset, seed, outward)
 
 
 def mesh_thickness_composed(points, normals, vertices, faces, thickness=True, cone=THICKNESS_CONE, offset=None, seed=0, outward=1.0):
@@ -2060,11 +2051,7 @@ def mesh_thickness_composed(points, normals, vertices, faces, thickness=True, co
     query of every point per cone direction (mesh_ray_cast's kernels on one shared grid, each with its own sort), the back-face
     test as a torch fp64 gather and the reductions in the kernel's order.  The yardstick the fused kernel is tested (same bits)
     and timed against (tools/time_thickness.py)."""
-    index, pts, nrm, dirs, offset, far, outward = _thickness_args(points, normals, vertices, faces, thickness, cone, offset, seed,
-                                                                  outward, "mesh_thickness_composed")
-    if index is None:
-        return _thickness_empty(pts.device)
-    return _thickness_composed(index, pts, nrm, dirs, offset, far, outward)
+    return _mesh_thickness("mesh_thickness_composed", False, points, normals, vertices, faces, thickness, cone, offset, seed, outward)
 
 
 def _thickness_composed(index, pts, nrm, dirs, offset, far, outward):
@@ -2092,10 +2079,7 @@ def _thickness_composed(index, pts, nrm, dirs, offset, far, outward):
         hit = face >= 0
         if F.shape[0]:
             fi = face.clamp(min=0).long()
-            pa, pb, pc = P[F[fi, 0]], P[F[fi, 1]], P[F[fi, 2]]
-            e1, e2 = pb - pa, pc - pa
-            g = (e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
-                 e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0])
+            g = _face_cross64(P, F[fi, 0], F[fi, 1], F[fi, 2])
             dd = d.double()
             hit = hit & ((((g[0] * dd[:, 0] + g[1] * dd[:, 1]) + g[2] * dd[:, 2]) * outward) > 0)
         dist = torch.where(hit, t, torch.zeros_like(t)).float()
@@ -2113,13 +2097,6 @@ def mesh_thickness_route():
     SCULPT_DISTANCE_FORM holds the token `composedthickness` (then mesh_thickness_composed).  The two give the same bits; the
     timings of tools/time_thickness.py are in DESIGN.md 3.3p."""
     return mesh_thickness_composed if _lib.form_has("SCULPT_DISTANCE_FORM", "composedthickness") else mesh_thickness
-
-
-def _index_thickness(index, pts, nrm, dirs, offset, far, outward):
-    """The point query of the route in force on a shared index (the bake comes through here)."""
-    if _lib.form_has("SCULPT_DISTANCE_FORM", "composedthickness"):
-        return _thickness_composed(index, pts, nrm, dirs, offset, far, outward)
-    return index.thickness(pts, nrm, dirs, offset, far, outward)
 
 
 def bake_thickness(v_pos, faces, normals, rast, thickness=True, cone=THICKNESS_CONE, offset=None, seed=0, outward=1.0, source=None,
@@ -2144,14 +2121,10 @@ def bake_thickness(v_pos, faces, normals, rast, thickness=True, cone=THICKNESS_C
     thick = torch.zeros(res * res, dtype=torch.float32, device=dev)
     thin = torch.zeros(res * res, dtype=torch.float32, device=dev)
     valid = torch.zeros(res * res, dtype=torch.int32, device=dev)
-    cov, clean = _covered_texels(r, v, f)
-    at = torch.nonzero(cov.reshape(-1))[:, 0] if index is not None else None
-    if at is not None and at.numel():
-        pts = bake_interpolate(v, clean, f).reshape(-1, 3)[at].contiguous()
-        nr = bake_interpolate(nrm, clean, f).reshape(-1, 3)[at].contiguous()
-        if cage > 0.0 and index.F.shape[0]:
-            pts, nr = _snap_composed(index, pts, nr, cage)
-        thick[at], thin[at], valid[at] = _index_thickness(index, pts, nr, torch.from_numpy(dirs).to(dev), offset, far, outward)
+    cov, at, pts, nr = _atlas_points(index, v, f, nrm, r, cage)
+    if at is not None:
+        query = _thickness_composed if _lib.form_has("SCULPT_DISTANCE_FORM", "composedthickness") else _SurfaceIndex.thickness
+        thick[at], thin[at], valid[at] = query(index, pts, nr, torch.from_numpy(dirs).to(dev), offset, far, outward)
     return thick.view(res, res), thin.view(res, res), valid.view(res, res), cov
 
 
@@ -2314,11 +2287,9 @@ def _mesh_render_fused(job):
                                    m["vertex_colors"].shape[1] if m["vertex_colors"] is not None else 0)
     outputs = _lib.RenderOutputs(*[_ptr(out.get(p)) for p in ("color", "shaded", "opacity", "rgba", "depth", "normal", "occlusion", "face")])
     light = None if job.light is None else job.light.ctypes.data_as(ctypes.c_void_p)
-    mesh, grid = index._grid_args()
-    records = index.records() if index.F.shape[0] else None
     n_images, height, width = job.images
-    check(lib.sculpt_surface_render(_ptr(job.o), _ptr(job.d), n_images, height, width, *mesh, _ptr(records), *grid,
-                                    ctypes.byref(material), job.ambient, light, job.outward, ctypes.byref(outputs), _stream()))
+    check(lib.sculpt_surface_render(_ptr(job.o), _ptr(job.d), n_images, height, width, *index._args()[1], ctypes.byref(material),
+                                    job.ambient, light, job.outward, ctypes.byref(outputs), _stream()))
     return out
 
 
@@ -2420,11 +2391,7 @@ def _mesh_render_composed(job):
             albedo = torch.full((n, 3), MESH_RENDER_GREY, dtype=torch.float32, device=o.device)
     normal = None
     if "normal" in passes or "shaded" in passes:
-        P = index.P.double()
-        a, b, c = P[i0], P[i1], P[i2]
-        e1, e2 = b - a, c - a
-        g = torch.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
-                         e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1) * job.outward
+        g = torch.stack(_face_cross64(index.P.double(), i0, i1, i2), 1) * job.outward
         ln = torch.sqrt((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2])
         ok = (ln > 0) & (ln < math.inf)
         normal = torch.where(ok[:, None], (g / ln[:, None]).float(), torch.zeros((n, 3), dtype=torch.float32, device=o.device))

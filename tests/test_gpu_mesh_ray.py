@@ -220,6 +220,75 @@ def test_occlusion_of_odd_points(cuda):
     assert (none.cpu().numpy() == 1.0).all()                    # no face: nothing occludes
 
 
+# ------------------------------------------------------------------------------------------- one index, every query method
+_TETRA = (np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], np.float32),
+          np.array([[0, 2, 1], [0, 1, 3], [1, 2, 3], [2, 0, 3]], np.int32))       # wound outwards
+
+
+def _every_query(cuda, P, F, pts, nrm, O, D, occ_dirs, cone_dirs, offset):
+    """The five point and ray queries of ONE _SurfaceIndex over (P, F), as NumPy arrays."""
+    dev = [torch.from_numpy(np.ascontiguousarray(x)).to(cuda) for x in (P, F, pts, nrm, O, D, occ_dirs, cone_dirs)]
+    P_, F_, pts_, nrm_, O_, D_, occ_, cone_ = dev
+    index = ops._SurfaceIndex(P_, F_)
+    got = dict(closest=index.closest(pts_), winding=index.winding(pts_), ray_cast=index.ray_cast(O_, D_),
+               occlusion=index.occlusion(pts_, nrm_, occ_, offset, np.inf),
+               thickness=index.thickness(pts_, nrm_, cone_, offset, np.inf, 1.0))
+    return {k: [x.cpu().numpy() for x in (v if isinstance(v, tuple) else (v,))] for k, v in got.items()}
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_every_query_of_one_index_without_faces(cuda, monkeypatch, form):
+    """Every null pointer of the launch path at once: no mesh, no lists, no records, no order."""
+    _form(form, monkeypatch)
+    P = _TETRA[0]
+    pts = np.array([[0.2, 0.2, 0.2], [1, 1, 1], [-3, 0.5, 2]], np.float32)
+    nrm = np.array([[0, 0, 1], [1, 1, 1], [0, -1, 0]], np.float32)
+    D = np.array([[1, 0, 0], [-1, -1, -1], [0, 0, -2]], np.float32)
+    got = _every_query(cuda, P, np.zeros((0, 3), np.int32), pts, nrm, pts, D, ops.occlusion_directions(4), ops.thickness_directions(4),
+                       2.0 ** -10)
+    d2, face, closest = got["closest"]
+    assert d2.dtype == np.float64 and (d2 == np.inf).all() and face.dtype == np.int32 and (face == -1).all()
+    assert closest.dtype == np.float32 and np.array_equal(closest, pts)
+    assert got["winding"][0].dtype == np.int32 and got["winding"][0].shape == (3, 3) and (got["winding"][0] == 0).all()
+    t, face, uv = got["ray_cast"]
+    assert t.dtype == np.float64 and (t == np.inf).all() and face.dtype == np.int32 and (face == -1).all()
+    assert uv.dtype == np.float32 and uv.shape == (3, 2) and (uv == 0).all()
+    assert got["occlusion"][0].dtype == np.float32 and (got["occlusion"][0] == 1.0).all()
+    thick, thin, valid = got["thickness"]
+    assert thick.dtype == thin.dtype == np.float32 and (thick == np.inf).all() and (thin == np.inf).all()
+    assert valid.dtype == np.int32 and (valid == 0).all()
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_every_query_of_one_index_equals_the_brute_force(cuda, monkeypatch, form):
+    """A tetrahedron, one point inside and one outside, k = 4: every method of one index against its restatement, bit for bit."""
+    import _distref
+    import _thickref
+    import _windref
+
+    _form(form, monkeypatch)
+    P, F = _TETRA
+    pts = np.array([[0.2, 0.2, 0.2], [1, 1, 1]], np.float32)
+    nrm = np.array([[0, 0, 1], [0.5, 0.5, 0.70703125]], np.float32)
+    D = np.array([[1, 0.25, 0], [-1, -1, -1]], np.float32)
+    occ_dirs, cone_dirs, offset = ops.occlusion_directions(4), ops.thickness_directions(4), np.float32(2.0 ** -10)
+    got = _every_query(cuda, P, F, pts, nrm, pts, D, occ_dirs, cone_dirs, float(offset))
+    want = dict(closest=_distref.closest(pts, P, F), winding=(_windref.winding(pts, P, F),), ray_cast=RR.ray_cast(pts, D, P, F),
+                occlusion=(RR.occlusion(pts, nrm, occ_dirs, P, F, offset),), thickness=_thickref.thickness(pts, nrm, cone_dirs, P, F, offset))
+    for name in want:
+        assert len(got[name]) == len(want[name])
+        for g, w in zip(got[name], want[name]):
+            if g.dtype == np.int32 and w.dtype == np.int64:       # the index reports faces as int32, the restatements as int64
+                g = g.astype(np.int64)
+            assert g.dtype == w.dtype and g.shape == w.shape, (name, g.dtype, w.dtype, g.shape, w.shape)
+            assert np.array_equal(_bits(g), _bits(w)), (name, form, g, w)
+    # asserted on the REFERENCE: the case holds what it is meant to
+    assert want["closest"][0][0] > 0 and want["ray_cast"][1][0] >= 0 and want["ray_cast"][1][1] >= 0
+    assert (want["winding"][0][0] == 1).all() and (want["winding"][0][1] == 0).all()
+    assert want["thickness"][2][0] == 4 and want["thickness"][2][1] == 0            # inside: every ray leaves through a back face
+    assert want["occlusion"][0][0] == 0.0 and want["occlusion"][0][1] == 1.0        # inside a closed body; outside, facing away
+
+
 # ------------------------------------------------------------------------------------------------------------ end to end
 def test_extract_meshes_sets_the_vertex_occlusion(cuda):
     from _tsrmodel import small_model

@@ -63,6 +63,43 @@ def test_thickness_directions_defaults_and_refusals():
             ops.thickness_directions(k, cone, seed)
 
 
+def test_the_two_ray_count_rules_are_one_rule():
+    """occlusion_rule and thickness_rule differ in what True means (64 directions, 32 rays) and in nothing else."""
+    for x in (True, np.True_):
+        assert ops.occlusion_rule(x) == (64, None) and ops.thickness_rule(x) == (32, None)
+    for x in (False, None, 0, 1, 1024, 1025, 1.5, "8", (8, None), (8, 2.0), (8, math.inf), (8, 0.0), (8, math.nan), (8,), [8, 2.0]):
+        results = []
+        for rule in (ops.occlusion_rule, ops.thickness_rule):
+            try:
+                results.append(rule(x))
+            except ValueError:
+                results.append(ValueError)
+        assert results[0] == results[1], (x, results)
+    assert ops.occlusion_rule(1) == (1, None) and ops.occlusion_rule((8, 2.0)) == (8, 2.0)      # the table is not all refusals
+    with pytest.raises(ValueError):
+        ops.occlusion_rule((8, 0.0))
+
+
+@pytest.mark.parametrize("k", [1, 7, 64])
+@pytest.mark.parametrize("seed", [0, 3])
+def test_the_two_direction_sets_are_one_spiral(k, seed):
+    """Unit rows, and row i of both sets at the one azimuth phi_i = i x the golden angle + seed.  A unit vector rounded to fp32 has
+    a squared norm within 3 * 2^-24 of 1: each component is off by at most 2^-24 of itself, so the sum of squares by at most
+    2 * 2^-24 (1 + 2^-25) of the whole."""
+    occ, thick = ops.occlusion_directions(k, seed), ops.thickness_directions(k, 90.0, seed)
+    assert occ.dtype == thick.dtype == np.float32 and occ.shape == thick.shape == (k, 3)
+    for d in (occ, thick):
+        assert np.abs((d.astype(np.float64) ** 2).sum(1) - 1.0).max() <= 3.0 * 2.0 ** -24
+
+    def apart(a, b):   # the angle between two azimuths, whichever side of +-pi each was reported on
+        return np.abs((a - b + math.pi) % (2.0 * math.pi) - math.pi)
+
+    az_occ, az_thick = np.arctan2(occ[:, 1].astype(np.float64), occ[:, 0]), np.arctan2(thick[:, 1].astype(np.float64), thick[:, 0])
+    assert apart(az_occ, az_thick).max() <= 1e-6
+    phi = np.arange(k, dtype=np.float64) * ops.GOLDEN_ANGLE + float(seed)
+    assert apart(az_occ, phi).max() <= 1e-6 and apart(az_thick, phi).max() <= 1e-6
+
+
 # ------------------------------------------------------------------------------------------------- restatement vs closed forms
 def test_the_cubes_wind_outwards():
     from _rayref import cube
