@@ -1398,6 +1398,51 @@ int sculpt_surface_thickness(const float *P, const float *N, int64_t n, const in
                              const int32_t *items, const int32_t *start, const double *params_host, double amax, float *thickness,
                              float *thinnest, int32_t *valid, sculpt_stream_t stream);
 
+/* Discrete curvature ON THE DEVICE after Meyer, Desbrun, Schroeder, Barr 2003: the integrated mean and Gaussian curvature per
+ * vertex (csrc/mesh_curvature.hip; sf3d/remesh_device.py curvature_device, ops.mesh_curvature, Mesh.curvature,
+ * TSR.bake_curvature_map).  DEVICE pointers, asynchronous on `stream`, no host wait.  Added without a
+ * version change (new symbols only).  Compiled without floating-point contraction: all arithmetic is fp64 on the fp32 positions in
+ * a fixed order (restated in tests/_curvref.py; everything but atan2 to the bit).
+ *   sculpt_curvature_terms   per vertex u of the topology (its bnd: sculpt_rmd_boundary on zeroes), the corners of u in vfc order.
+ *                            Corner of face (i, j, k) in the face's cyclic order seen from i = u:
+ *                                e1 = pj - pi, e2 = pk - pi, g = e1 x e2, a2 = sqrt(g . g); unless 0 < a2 < inf it adds nothing
+ *                                di = e1 . e2, dj = (pi - pj) . (pk - pj), dk = (pi - pk) . (pj - pk), cot_j = dj / a2, cot_k = dk / a2
+ *                                theta = atan2(a2, di)
+ *                                a = ((e1 . e1) cot_k + (e2 . e2) cot_j) / 8 when none of di, dj, dk is < 0 (a right angle is
+ *                                    Voronoi), else a2 / 4 when di < 0, else a2 / 8                         (the mixed area)
+ *                                A = A + a, Th = Th + theta, Kv = Kv + (cot_k (pi - pj) + cot_j (pi - pk)), N = N + g
+ *                            valid [nv] u8 = bnd[u] == 0 and a face names u and A > 0.  area [nv] f64 = A, deficit [nv] f64 =
+ *                            6.283185307179586 - Th, hint [nv] f64 = ((outward sign(Kv . N)) sqrt(Kv . Kv)) / 4, the integrated
+ *                            mean curvature H A, positive on a convex surface whose faces wind outward (outward = +1; -1 for the
+ *                            other winding); an invalid vertex writes zeros.  A pinched vertex whose edges all have two faces
+ *                            is valid and gets the deficit of its whole angle sum.  P [nv][3]; work: 16-byte aligned, nv * 4
+ *                            floats (positions as x y z - rows).  The faces are trusted to be in range (sculpt_rmd_validate).
+ *   sculpt_curvature_ring    `rounds` (0 .. 8) times X'_u = X_u + the sum of X_v over the valid v of row u of the neighbour
+ *                            table (start, nb: sculpt_smooth_neighbours), in row order, for the channels hint, deficit and
+ *                            area; an invalid u stays zero.  In and out arrays [nv] f64 (out may be in); work_a, work_b: two
+ *                            distinct 32-byte aligned buffers of nv * 4 doubles.  nb holds n_nb entries, each in [0, nv):
+ *                            the caller's table is trusted, like F.
+ *   sculpt_curvature_finish  mean [nv] f32 = (float)(hint / area), gauss [nv] f32 = (float)(deficit / area), NaN where invalid.
+ * Null, misaligned or out-of-range arguments are refused with an error code and a message; nv == 0 launches nothing. */
+int sculpt_curvature_terms(const sculpt_rmd_topo_t *topo, const float *P, double outward, float *work, double *area, double *deficit,
+                           double *hint, uint8_t *valid, sculpt_stream_t stream);
+int sculpt_curvature_ring(const int32_t *start, const int32_t *nb, const uint8_t *valid, int64_t nv, int64_t n_nb, int rounds,
+                          const double *area, const double *deficit, const double *hint, double *work_a, double *work_b,
+                          double *area_out, double *deficit_out, double *hint_out, sculpt_stream_t stream);
+int sculpt_curvature_finish(const double *area, const double *deficit, const double *hint, const uint8_t *valid, int64_t nv, float *mean,
+                            float *gauss, sculpt_stream_t stream);
+
+/* A value per vertex read at points on a surface (csrc/mesh_curvature.hip; ops.surface_attribute_at): what lets an atlas bake
+ * read a high-poly mesh's per-vertex field at its snapped texels.  points [m][3], face [m] (the face each point lies on), P
+ * [nv][3], F [nf][3], values [nv][channels] f32, 1 <= channels <= 8 -> out [m][channels] f32.  Per point q on face (a, b, c), in
+ * fp64 without contraction: g = (pb - pa) x (pc - pa); w0 = clamp(((pb - q) x (pc - q)) . g / (g . g)),
+ * w1 = clamp(((pc - q) x (pa - q)) . g / (g . g)), w2 = clamp((1 - w0) - w1), clamp to [0, 1] by comparisons (a NaN stays).  Per
+ * channel s = 0 and s = s + w_k v_k over the corners in order whose value is no NaN, ws the sum of their weights likewise:
+ * (float)s when all three count, (float)(s / ws) when one or two do (one border vertex does not blank a texel), NaN when none
+ * does.  face < 0 or >= nf, or a corner outside [0, nv): NaN.  m == 0 launches nothing. */
+int sculpt_surface_attribute_at(const float *points, const int32_t *face, int64_t m, const float *P, const int32_t *F, int64_t nf,
+                                int64_t nv, const float *values, int channels, float *out, sculpt_stream_t stream);
+
 /* Ambient-occlusion bake over a rasterised atlas (csrc/mesh_ray.hip; ops.bake_occlusion, TSR.bake_occlusion_map; DESIGN.md section
  * 3.3h): sculpt_surface_occlusion at every covered texel of the atlas of a LOW mesh (v_pos [nv][3], faces [nf][3] int32 or int64,
  * per-vertex normals v_nrm [nv][3]) against the surface S of the grid (GP, GF, gnf, records, items, start, params_host, amax: as

@@ -260,6 +260,10 @@ SIGNATURES = {
     "sculpt_surface_ray_cast": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "sculpt_surface_occlusion": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp]),
     "sculpt_surface_thickness": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _f, _f, _d, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
+    "sculpt_curvature_terms": (_i, [_vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_curvature_ring": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sculpt_curvature_finish": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "sculpt_surface_attribute_at": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i, _vp, _vp]),
     "sculpt_bake_occlusion": (_i, [_vp, _i, _vp, _sz, _vp, _i, _sz, _vp, _vp, _i, _f, _f, _f, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp,
                                    _vp, _vp]),
     "sculpt_surface_render": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _d, _vp, _f, _vp, _d, _vp, _vp]),

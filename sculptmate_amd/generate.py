@@ -83,6 +83,10 @@ class TripoGenerator(GeneratorFacade):
     wall thickness (shape diameter) of the mesh per texel -- beside every baked texture, over its atlas
     (TSR.bake_thickness_map; copied to the model as TSR.thickness_map).  It comes back as the mesh's plain attribute
     `thickness` (a tsr.thickness.ThicknessMap); its save(path) writes a 16-bit grey PNG.
+    `curvature_map` (default None): True or an int r in 0 .. 8 (ops.curvature_rule: the rings the curvature is summed over) bakes a
+    curvature map -- mean and Gaussian curvature of the mesh per texel -- beside every baked texture, over its atlas
+    (TSR.bake_curvature_map; copied to the model as TSR.curvature_map).  It comes back as the mesh's plain attribute
+    `curvature` (a tsr.curvature.CurvatureMap); its save(path) writes a 16-bit grey PNG.
     `atlas` (default "box"): "charts" unwraps every mesh a map is baked for with sf3d.unwrap.ChartUnwrapper -- charts that are
     connected pieces of surface -- instead of the box projection (copied to the model as TSR.atlas)."""
 
@@ -107,6 +111,7 @@ class TripoGenerator(GeneratorFacade):
         self.bake_project = None
         self.displacement_map = None
         self.thickness_map = None
+        self.curvature_map = None
         self.atlas = "box"
 
     def _construct_model(self):
@@ -126,6 +131,7 @@ class TripoGenerator(GeneratorFacade):
             self.model.bake_project = self.bake_project
             self.model.displacement_map = self.displacement_map
             self.model.thickness_map = self.thickness_map
+            self.model.curvature_map = self.curvature_map
             self.model.atlas = self.atlas
             self.last_meshes = self.model.extract_mesh(codes, enable_texture=enable_texture, mesh_name=input_name,
                                                        resolution=self.mc_resolution,

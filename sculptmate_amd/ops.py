@@ -1852,9 +1852,8 @@ def _source_rule(who, source, cage):
             raise ValueError("cage must be None or a finite number > 0, got %r" % (cage,))
 
 
-def _atlas_query_args(who, v_pos, faces, normals, rast, offset, source, cage):
-    """The tensors of a ray bake over an atlas, checked (SculptError), and the index over S with the defaults that depend on its
-    bounds -> (index or None when res == 0, v, f, nrm, rast, offset, cage), offset and cage rounded to fp32 (cage 0: no snap)."""
+def _atlas_tensors(who, v_pos, faces, normals, rast):
+    """The tensors of a bake over an atlas, checked (SculptError) -> (v, f, nrm, rast), contiguous."""
     v, f = _mesh_args(who, v_pos, faces)
     nrm = _req(normals.contiguous() if isinstance(normals, torch.Tensor) else normals, torch.float32, "normals")
     r = _req(rast.contiguous() if isinstance(rast, torch.Tensor) else rast, torch.float32, "rast")
@@ -1862,6 +1861,13 @@ def _atlas_query_args(who, v_pos, faces, normals, rast, offset, source, cage):
         raise SculptError("%s: normals %s must be per vertex %s" % (who, tuple(nrm.shape), tuple(v.shape)))
     if r.ndim != 3 or r.shape[0] != r.shape[1] or r.shape[2] != 4:
         raise SculptError("%s: rast %s must be [res, res, 4]" % (who, tuple(r.shape)))
+    return v, f, nrm, r
+
+
+def _atlas_query_args(who, v_pos, faces, normals, rast, offset, source, cage):
+    """The tensors of a ray bake over an atlas, checked (SculptError), and the index over S with the defaults that depend on its
+    bounds -> (index or None when res == 0, v, f, nrm, rast, offset, cage), offset and cage rounded to fp32 (cage 0: no snap)."""
+    v, f, nrm, r = _atlas_tensors(who, v_pos, faces, normals, rast)
     P, F = _surface(v, f, who) if source is None else _surface(source[0], source[1], who)
     if r.shape[0] == 0:
         return None, v, f, nrm, r, 0.0, 0.0
@@ -1914,19 +1920,21 @@ def bake_occlusion_composed(v_pos, faces, normals, rast, occlusion=True, offset=
     return _bake_occlusion_composed(index, v, f, nrm, r, dirs, offset, far, cage)
 
 
-def _atlas_points(index, v, f, nrm, r, cage):
+def _atlas_points(index, v, f, nrm, r, cage, want_face=False):
     """The composed atlas route up to its point query: the coverage in torch, nonzero, bake_interpolate of the positions and of
     the normals, the snap -> (cov bool [res, res], at i64 [M] the covered texels' flat indices, pts f32 [M, 3], nr f32 [M, 3]);
-    at, pts and nr are None when nothing is covered or the index is None (res == 0)."""
+    at, pts and nr are None when nothing is covered or the index is None (res == 0).  want_face: one more value, the face of the
+    index's surface every texel was snapped onto (int32 [M], -1 where the snap ray hit nothing; None when nothing was snapped)."""
     cov, clean = _covered_texels(r, v, f)
     at = torch.nonzero(cov.reshape(-1))[:, 0] if index is not None else None
     if at is None or at.numel() == 0:
-        return cov, None, None, None
+        return (cov, None, None, None) + ((None,) if want_face else ())
     pts = bake_interpolate(v, clean, f).reshape(-1, 3)[at].contiguous()
     nr = bake_interpolate(nrm, clean, f).reshape(-1, 3)[at].contiguous()
+    face = None
     if cage > 0.0 and index.F.shape[0]:
-        pts, nr = _snap_composed(index, pts, nr, cage)
-    return cov, at, pts, nr
+        pts, nr, face = _snap_composed(index, pts, nr, cage, want_face=True)
+    return (cov, at, pts, nr) + ((face,) if want_face else ())
 
 
 def _bake_occlusion_composed(index, v, f, nrm, r, dirs, offset, far, cage):
@@ -1956,8 +1964,9 @@ def _face_cross64(P64, i0, i1, i2):
             e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0])
 
 
-def _snap_composed(index, pts, nr, cage, want_stats=False):
-    """Step 4 of the atlas bake in torch: every operation is one elementwise kernel, so nothing is contracted."""
+def _snap_composed(index, pts, nr, cage, want_stats=False, want_face=False):
+    """Step 4 of the atlas bake in torch: every operation is one elementwise kernel, so nothing is contracted.  want_face: the
+    face every ray hit (int32 [M], -1 where it hit nothing) comes back as one more value."""
     c = nr * cage                                # fp32
     o, d = pts + c, -c
     t, face, _ = index.ray_cast(o.contiguous(), d.contiguous(), 0.0, 2.0)
@@ -1973,7 +1982,8 @@ def _snap_composed(index, pts, nr, cage, want_stats=False):
     good = hit & (ln > 0) & (ln < math.inf)
     m = (g / ln[:, None]).float()
     out = torch.where(hit[:, None], q, pts).contiguous(), torch.where(good[:, None], m, nr).contiguous()
-    return out + (hit,) if want_stats else out
+    out = out + (hit,) if want_stats else out
+    return out + (face,) if want_face else out
 
 
 # ----------------------------------------------------------------------------------------------
@@ -2126,6 +2136,207 @@ def bake_thickness(v_pos, faces, normals, rast, thickness=True, cone=THICKNESS_C
         query = _thickness_composed if _lib.form_has("SCULPT_DISTANCE_FORM", "composedthickness") else _SurfaceIndex.thickness
         thick[at], thin[at], valid[at] = query(index, pts, nr, torch.from_numpy(dirs).to(dev), offset, far, outward)
     return thick.view(res, res), thin.view(res, res), valid.view(res, res), cov
+
+
+# ----------------------------------------------------------------------------------------------
+# discrete curvature: mean and Gaussian per vertex, the curvature map (csrc/mesh_curvature.hip)
+# ----------------------------------------------------------------------------------------------
+CURVATURE_MAX_RINGS = 8
+ATTRIBUTE_MAX_CHANNELS = 8
+
+
+def curvature_rule(curvature):
+    """`curvature` of the curvature queries -> rings: True (0 rings: the one-ring operator itself) or an int r in 0 .. 8 (r
+    rounds of sums over the neighbours).  Anything else -- False, None, a float, NaN, a str, 9 -- is a ValueError, raised here,
+    before anything is launched."""
+    if curvature is True:
+        return 0
+    if _is_count(curvature, 0, CURVATURE_MAX_RINGS):
+        return int(curvature)
+    raise ValueError("curvature must be True or an int in 0 .. %d (rings), got %r" % (CURVATURE_MAX_RINGS, curvature))
+
+
+def _outward_rule(outward):
+    if not (_is_real(outward) and float(outward) in (1.0, -1.0)):   # a NaN is in neither
+        raise ValueError("outward must be +1 or -1, got %r" % (outward,))
+    return float(outward)
+
+
+def mesh_curvature_terms(vertices, faces, outward=1.0):
+    """The raw terms of the discrete curvature operators of Meyer, Desbrun, Schroeder and Barr (2003) per vertex, on the device
+    (sculpt_curvature_terms, one gather).  vertices float [Nv, 3], faces int32 / int64 [Nf, 3] (device tensors; CPU tensors are
+    refused); outward: +1 when the faces wind counter-clockwise seen from outside, -1 otherwise.
+    -> (area f64 [Nv], the mixed (Voronoi, or barycentric at obtuse triangles) area; deficit f64 [Nv] = 2 pi - the angle sum, the
+    integrated Gaussian curvature; hint f64 [Nv], the integrated mean curvature H A, positive on a convex surface; valid bool
+    [Nv]).  The rule, corner by corner in fp64 without contraction, is at the top of csrc/mesh_curvature.hip; tests/_curvref.py
+    restates it in NumPy (bit for bit but for atan2).  valid is False -- and the three terms 0 -- where an edge at the vertex does
+    not have exactly two faces (a border, a fin), where no face names the vertex and where the area is not > 0.  A pinched
+    (bow-tie) vertex whose edges all have two faces is VALID and gets the deficit of its full angle sum: pinches are what
+    mesh_report finds.  A face index out of range, a repeated index in a face and a non-finite position are a SculptError;
+    Nf == 0 gives zeros and launches nothing."""
+    outward = _outward_rule(outward)
+    from .sf3d import remesh_device as rmd
+
+    _device_mesh(vertices, faces, "mesh_curvature")
+    area, deficit, hint, valid = rmd.curvature_device(vertices, faces, 0, outward, finish=False)
+    return area, deficit, hint, valid.view(torch.bool)
+
+
+def curvature_ring(terms, start, nb, rounds):
+    """`rounds` (0 .. 8) rounds of X'_u = X_u + the sum of X_v over the valid v of row u, in row order, on the three f64 channels
+    of terms = (area, deficit, hint, valid) as mesh_curvature_terms returns them; (start i32 [Nv + 1], nb i32) is the neighbour
+    CSR of the smoothing filter (distinct neighbours in ascending order).  An invalid u stays zero and invalid.  -> new (area,
+    deficit, hint, valid).  This is a walk-count-weighted average of the integrated curvature over the r-ring, not a geodesic
+    disc: a neighbour reached by more walks of length <= r counts more often, in numerator and denominator alike."""
+    if not _is_count(rounds, 0, CURVATURE_MAX_RINGS):
+        raise ValueError("rounds must be an int in 0 .. %d, got %r" % (CURVATURE_MAX_RINGS, rounds))
+    from .sf3d import remesh_device as rmd
+
+    area, deficit, hint = (_req(t, torch.float64, "terms") for t in terms[:3])
+    valid = terms[3]
+    if not (isinstance(valid, torch.Tensor) and valid.is_cuda and valid.dtype in (torch.bool, torch.uint8) and valid.is_contiguous()):
+        raise SculptError("terms: valid must be a contiguous bool / uint8 device tensor")
+    start, nb = _req(start, torch.int32, "start"), _req(nb, torch.int32, "nb")
+    nv = area.shape[0]
+    if not (deficit.shape == hint.shape == valid.shape == area.shape == (nv,) and start.shape == (nv + 1,) and nb.dim() == 1):
+        raise SculptError("curvature_ring: terms must be four [Nv] tensors and start [Nv + 1]")
+    ctx = rmd._Ctx()
+    out = rmd._curvature_ring(ctx, (area, deficit, hint, valid.view(torch.uint8)), start, nb, int(rounds))
+    ctx.done()
+    return out[:3] + (valid.view(torch.bool),)
+
+
+def mesh_curvature(vertices, faces, curvature=True, outward=1.0):
+    """Mean and Gaussian curvature per vertex of a triangle mesh, on the device: the discrete operators of Meyer, Desbrun,
+    Schroeder and Barr (2003).  vertices float [Nv, 3], faces int32 / int64 [Nf, 3] (device tensors; CPU tensors are refused);
+    curvature: True or the number of rings r in 0 .. 8 (curvature_rule); outward: +1 when the faces wind counter-clockwise seen
+    from outside, -1 otherwise (it only sets the sign of the mean curvature).  A bad rule is a ValueError before any launch.
+    -> (mean f32 [Nv], positive where the surface is convex; gauss f32 [Nv]; valid bool [Nv]).  Three steps, all fp64 in a fixed
+    order (csrc/mesh_curvature.hip): the raw terms (mesh_curvature_terms); r rounds of curvature_ring over the neighbour table of
+    the smoothing filter -- a walk-count-weighted average of the integrated curvature over the r-ring, not a geodesic disc, which
+    is what takes the lattice-scale noise of a marching-cubes mesh out; then mean = hint / area and gauss = deficit / area,
+    each rounded once to fp32.  Contract:
+      - an invalid vertex (on an edge without exactly two faces, named by no face, without area) has NaN in both and never
+        contributes to a neighbour; a pinched vertex whose edges all have two faces is valid (see mesh_curvature_terms);
+      - a face without area contributes nothing; a right angle takes the Voronoi area;
+      - a face index out of range, a repeated index in a face and a non-finite position are a SculptError;
+      - Nf == 0: NaN, NaN, False and nothing is launched;
+      - deterministic: gathers in a fixed order, no atomics; tests/_curvref.py restates every step in NumPy -- bit for bit but
+        for the angle sum, which goes through atan2;
+      - the host reads back the input check's status and the edge count of the one topology construction, nothing else."""
+    rings = curvature_rule(curvature)
+    outward = _outward_rule(outward)
+    from .sf3d import remesh_device as rmd
+
+    _device_mesh(vertices, faces, "mesh_curvature")
+    mean, gauss, valid = rmd.curvature_device(vertices, faces, rings, outward)
+    return mean, gauss, valid.view(torch.bool)
+
+
+def principal_curvatures(mean, gauss):
+    """(k1, k2) = H +- sqrt(max(H^2 - K, 0)) from mean = H and gauss = K (float32 tensors of one shape, on any device): computed
+    in fp64 and rounded once, k1 >= k2; plain elementwise torch.  A NaN in either gives NaN in both."""
+    if not (isinstance(mean, torch.Tensor) and isinstance(gauss, torch.Tensor) and mean.dtype == gauss.dtype == torch.float32
+            and mean.shape == gauss.shape):
+        raise SculptError("principal_curvatures: mean and gauss must be float32 tensors of one shape")
+    h, k = mean.double(), gauss.double()
+    d = h * h - k
+    root = torch.sqrt(torch.where(d < 0.0, torch.zeros_like(d), d))   # a NaN stays a NaN
+    return (h + root).float(), (h - root).float()
+
+
+def surface_attribute_at(points, face, vertices, faces, values):
+    """A per-vertex field read at points on a surface (sculpt_surface_attribute_at): points float [M, 3], face int32 / int64 [M]
+    (the face each point lies on, as a closest-point or ray query reports it; < 0: none), vertices float [Nv, 3], faces int32 /
+    int64 [Nf, 3], values f32 [Nv] or [Nv, C] with C <= 8 (device tensors) -> f32 [M] or [M, C].  Per point the barycentric
+    weights are ratios of sub-triangle cross products against the face's own cross product in fp64, each clamped to [0, 1], the
+    third 1 - w0 - w1, clamped; the value is the weighted sum in corner order, rounded once.  A corner whose value is NaN is
+    skipped and the remaining weights renormalised, so one border vertex does not blank a texel; all three NaN, a face < 0 and a
+    face without area give NaN.  M == 0 launches nothing."""
+    who = "surface_attribute_at"
+    pts = _query_points(points, who)
+    _device_mesh(vertices, faces, who)
+    if not (isinstance(face, torch.Tensor) and face.is_cuda and face.dtype in (torch.int32, torch.int64) and face.shape == (pts.shape[0],)):
+        raise SculptError("%s: face must be an int32 / int64 device tensor [M]" % who)
+    vals = _req(values.contiguous() if isinstance(values, torch.Tensor) else values, torch.float32, "values")
+    P = vertices.detach().reshape(-1, 3).to(torch.float32).contiguous()
+    F = faces.detach().reshape(-1, 3).to(torch.int32).contiguous()
+    flat = vals.dim() == 1
+    if vals.dim() not in (1, 2) or vals.shape[0] != P.shape[0] or not (flat or 1 <= vals.shape[1] <= ATTRIBUTE_MAX_CHANNELS):
+        raise SculptError("%s: values %s must be [Nv] or [Nv, C <= %d] with Nv = %d" % (who, tuple(vals.shape), ATTRIBUTE_MAX_CHANNELS,
+                                                                                       P.shape[0]))
+    return _attribute_at(pts, face.clamp(min=-1).to(torch.int32).contiguous(), P, F, vals)
+
+
+def _attribute_at(pts, face, P, F, vals):
+    """pts f32 [M, 3], face i32 [M], P f32 [Nv, 3], F i32 [Nf, 3], vals f32 [Nv] or [Nv, C], all contiguous -> f32 [M] or [M, C]."""
+    c = 1 if vals.dim() == 1 else vals.shape[1]
+    m = pts.shape[0]
+    out = torch.empty((m,) if vals.dim() == 1 else (m, c), dtype=torch.float32, device=pts.device)
+    if m:
+        nf, nv = F.shape[0], P.shape[0]
+        check(lib.sculpt_surface_attribute_at(_ptr(pts), _ptr(face), m, _ptr(P) if nv else None, _ptr(F) if nf else None, nf, nv,
+                                              _ptr(vals) if nv else None, c, _ptr(out), _stream()))
+    return out
+
+
+def _curvature_texels(v, f, clean, at, mean, gauss):
+    """The mesh's own per-vertex (mean, gauss) at the covered texels `at`: bake_interpolate of the rows (H, K, ok) with ok = 1
+    where neither is NaN and (0, 0, 0) elsewhere, then per texel by the number of its face's corners with ok: three -- the
+    interpolated value as it is; none -- NaN; one or two -- the value divided by the interpolated ok (the weights that count,
+    renormalised) -> (mean f32 [M], gauss f32 [M])."""
+    ok = ~(torch.isnan(mean) | torch.isnan(gauss))
+    zero = torch.zeros_like(mean)
+    attr = torch.stack([torch.where(ok, mean, zero), torch.where(ok, gauss, zero), ok.to(torch.float32)], 1).contiguous()
+    img = bake_interpolate(attr, clean, f).reshape(-1, 3)[at]
+    tri = clean.reshape(-1, 4)[at, 3].to(torch.int64)
+    n = ok[f[tri].to(torch.int64)].sum(1)
+    nan = torch.full_like(img[:, 0], math.nan)
+    pick = lambda x: torch.where(n == 3, x, torch.where(n == 0, nan, x / img[:, 2]))
+    return pick(img[:, 0]), pick(img[:, 1])
+
+
+def bake_curvature(v_pos, faces, normals, rast, curvature=True, outward=1.0, source=None, cage=None):
+    """Mean and Gaussian curvature at every covered texel of a rasterised atlas of a (low-poly) mesh: the curvature map a baker
+    ships beside normal, AO and thickness.  v_pos f32 [Nv, 3], faces i32 / i64 [Nf, 3], normals f32 [Nv, 3] per vertex, rast f32
+    [res, res, 4] from bake_rasterize (device tensors; CPU tensors are refused); curvature, outward: as for mesh_curvature.
+    source=None (cage must be None): the mesh's own mesh_curvature, interpolated over each face by bake_interpolate; a corner
+    whose value is NaN (a border vertex) is skipped and the other weights renormalised, all three NaN give NaN
+    (_curvature_texels).  source=(vertices, faces): the curvature of THAT surface -- the high-poly mesh the low one was
+    simplified from -- read where each texel lands on it: the texel is snapped as in bake_occlusion (the closest hit of the ray
+    from p + cage n towards p - cage n; cage=None: 2^-6 of the longest side of the source's bounds) and the source's per-vertex
+    values are read on the hit face by surface_attribute_at; a texel whose ray hits nothing falls back to the mesh's own value.
+    -> (mean f32, gauss f32, mask bool), each [res, res]: exactly 0 and mask 0 where not covered.  The composed atlas route (the
+    coverage in torch, nonzero, bake_interpolate, the snap, a scatter): no fused tile kernel.  A bad rule is a ValueError before
+    any launch; the meshes are checked as mesh_curvature checks them; res == 0 launches nothing."""
+    who = "bake_curvature"
+    rings = curvature_rule(curvature)
+    outward = _outward_rule(outward)
+    _source_rule(who, source, cage)
+    v, f, nrm, r = _atlas_tensors(who, v_pos, faces, normals, rast)
+    if source is not None:
+        _device_mesh(source[0], source[1], who)
+    res, dev = r.shape[0], r.device
+    mean = torch.zeros(res * res, dtype=torch.float32, device=dev)
+    gauss = torch.zeros(res * res, dtype=torch.float32, device=dev)
+    if res == 0:
+        return mean.view(0, 0), gauss.view(0, 0), torch.zeros((0, 0), dtype=torch.bool, device=dev)
+    own = mesh_curvature(v, f, rings, outward)
+    cov, clean = _covered_texels(r, v, f)
+    if source is None:
+        at, face = torch.nonzero(cov.reshape(-1))[:, 0], None
+    else:
+        high = mesh_curvature(source[0], source[1], rings, outward)
+        index, _, _, _, _, _, cage = _atlas_query_args(who, v, f, nrm, r, None, source, cage)
+        _, at, pts, _, face = _atlas_points(index, v, f, nrm, r, cage, want_face=True)
+    if at is not None and at.numel():
+        m, g = _curvature_texels(v, f, clean, at, own[0], own[1])
+        if face is not None:
+            hk = _attribute_at(pts, face, index.P, index.F, torch.stack([high[0], high[1]], 1).contiguous())
+            hit = face >= 0
+            m, g = torch.where(hit, hk[:, 0], m), torch.where(hit, hk[:, 1], g)
+        mean[at], gauss[at] = m, g
+    return mean.view(res, res), gauss.view(res, res), cov
 
 
 # ----------------------------------------------------------------------------------------------

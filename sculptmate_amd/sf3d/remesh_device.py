@@ -559,13 +559,19 @@ def simplify_device(v, f, target_faces):
     return P, F, index
 
 
-def _smooth_table(ctx, F, nv):
+def _plain_topo(ctx, F, nv):
+    """The topology of F with a zero `carry`: bnd[u] = 1 exactly where an edge at u does not have exactly two faces."""
+    return _Topo(ctx, F, nv, carry=torch.zeros(max(nv, 1), dtype=torch.uint8, device=F.device))
+
+
+def _smooth_table(ctx, F, nv, topo=None):
     """(start i32 [nv + 1], nb i32 [2 ne], fixed u8 [nv]) of the faces F: row u of the CSR holds the distinct neighbours of u in
     ascending order; fixed[u] = 1 where an edge at u does not have exactly two faces.  The topology gets a zero `carry`, so the
     remesher's more-than-64-neighbours feature rule is not applied: a high-valence vertex is smoothed like any other.  The
-    directed keys of the unique edges are distinct, so their sorted order -- and with it the table -- is unique."""
+    directed keys of the unique edges are distinct, so their sorted order -- and with it the table -- is unique.  topo: a
+    _plain_topo of F the caller has already (None: one is built)."""
     dev = F.device
-    T = _Topo(ctx, F, nv, carry=torch.zeros(max(nv, 1), dtype=torch.uint8, device=dev))
+    T = topo if topo is not None else _plain_topo(ctx, F, nv)
     keys = torch.empty(2 * T.ne, dtype=torch.int64, device=dev)
     check(lib.sculpt_smooth_edge_keys(T.ref(), _p(keys), ctx.stream))
     skeys = torch.sort(keys).values
@@ -598,6 +604,61 @@ def smooth_device(v, f, iterations, lam, mu):
         P = _smooth_steps(ctx, P, _smooth_table(ctx, F, P.shape[0]), iterations, lam, mu)
     ctx.done()
     return P
+
+
+def _curvature_terms(ctx, T, P, outward):
+    """(area, deficit, hint f64 [nv], valid u8 [nv]) of the topology T (a _plain_topo) over P f32 [nv, 3]: one pack and one gather."""
+    nv, dev = P.shape[0], P.device
+    area, deficit, hint = (torch.empty(nv, dtype=torch.float64, device=dev) for _ in range(3))
+    valid = torch.empty(nv, dtype=torch.uint8, device=dev)
+    work = torch.empty((max(nv, 1), 4), dtype=torch.float32, device=dev)
+    check(lib.sculpt_curvature_terms(T.ref(), _p(P), float(outward), _p(work), _p(area), _p(deficit), _p(hint), _p(valid), ctx.stream))
+    return area, deficit, hint, valid
+
+
+def _curvature_ring(ctx, terms, start, nb, rounds):
+    """`rounds` rounds of X'_u = X_u + the sum over the valid neighbours of u, on the three f64 channels of `terms` -> new terms."""
+    area, deficit, hint, valid = terms
+    nv, dev = area.shape[0], area.device
+    out = tuple(torch.empty(nv, dtype=torch.float64, device=dev) for _ in range(3))
+    work = torch.empty((2, max(nv, 1), 4), dtype=torch.float64, device=dev)
+    check(lib.sculpt_curvature_ring(_p(start), _p(nb), _p(valid), nv, nb.shape[0], int(rounds), _p(area), _p(deficit), _p(hint),
+                                    _p(work[0]), _p(work[1]), _p(out[0]), _p(out[1]), _p(out[2]), ctx.stream))
+    ctx.stats["curvature_rounds"] = int(rounds)
+    return out + (valid,)
+
+
+def _curvature_finish(ctx, terms):
+    area, deficit, hint, valid = terms
+    nv, dev = area.shape[0], area.device
+    mean, gauss = (torch.empty(nv, dtype=torch.float32, device=dev) for _ in range(2))
+    check(lib.sculpt_curvature_finish(_p(area), _p(deficit), _p(hint), _p(valid), nv, _p(mean), _p(gauss), ctx.stream))
+    return mean, gauss
+
+
+def curvature_device(v, f, rings, outward, finish=True):
+    """Discrete mean and Gaussian curvature per vertex (csrc/mesh_curvature.hip): the raw terms of every vertex from its corners,
+    `rings` rounds of sums over the neighbour table, the two quotients.  finish=True -> (mean f32, gauss f32, valid u8), each
+    [nv]; finish=False -> the terms after the rounds (area, deficit, hint f64 [nv], valid u8 [nv]).  Without faces: NaN / zeros
+    and nothing is launched.  The host reads back what one topology construction reads (the edge count) and, before it, the input
+    check's status; the neighbour table is built from that same topology, and only when rings > 0."""
+    P, F = _inputs(v, f, "mesh_curvature")
+    ctx = _Ctx()
+    nv, dev = P.shape[0], P.device
+    if F.shape[0] and nv:
+        T = _plain_topo(ctx, F, nv)
+        terms = _curvature_terms(ctx, T, P, outward)
+        if rings:
+            start, nb, _ = _smooth_table(ctx, F, nv, topo=T)
+            terms = _curvature_ring(ctx, terms, start, nb, rings)
+        out = _curvature_finish(ctx, terms) + (terms[3],) if finish else terms
+    elif finish:
+        out = (torch.full((nv,), math.nan, dtype=torch.float32, device=dev), torch.full((nv,), math.nan, dtype=torch.float32, device=dev),
+               torch.zeros(nv, dtype=torch.uint8, device=dev))
+    else:
+        out = tuple(torch.zeros(nv, dtype=torch.float64, device=dev) for _ in range(3)) + (torch.zeros(nv, dtype=torch.uint8, device=dev),)
+    ctx.done()
+    return out
 
 
 def decimate_device(v, f, face_ratio=0.1, num_faces=None):

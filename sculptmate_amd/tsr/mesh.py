@@ -256,6 +256,15 @@ class Mesh:
         return ops.mesh_thickness_route()(self.vertices, normals, self.vertices, self.faces, thickness, cone=cone, seed=seed,
                                           outward=float(outward))
 
+    def curvature(self, curvature=True, outward=1.0):
+        """Mean and Gaussian curvature per vertex -> (mean f32 [Nv], gauss f32 [Nv], valid bool [Nv]) (ops.mesh_curvature on this
+        mesh's device tensors; host arrays are refused): the discrete operators of Meyer et al., mean positive where the surface
+        is convex.  curvature: True or the number of rings in 0 .. 8 the integrated curvature is summed over (ops.curvature_rule;
+        a few rings take the lattice noise of an extracted mesh out); outward: +1 when the faces wind counter-clockwise seen from
+        outside, -1 otherwise (TSR.WINDING_OUTWARD for the meshes of TSR.extract_meshes).  Vertices on a border or a
+        non-manifold edge are invalid and NaN.  The result is returned, not stored."""
+        return ops.mesh_curvature(self.vertices, self.faces, curvature, outward)
+
     def render(self, rays_o, rays_d, passes=("color",), ambient=0.3, light=None, outward=1.0):
         """Pictures of this mesh with everything it carries -- uvs and texture, normal map and its frame, occlusion map, vertex
         colours, normals and occlusion -- ray cast on the device (ops.mesh_render on its device tensors; host arrays are refused

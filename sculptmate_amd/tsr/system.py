@@ -978,6 +978,10 @@ class TSR(KernelEngine):
     # texture bake (bake_thickness_map on the baked mesh's atlas, against the mesh itself) and leaves it on the mesh as the plain
     # attribute `thickness` (a tsr.thickness.ThicknessMap, no Mesh field).  None: nothing new is launched
     thickness_map = None
+    # None | what ops.curvature_rule accepts (True, rings): when set, extract_meshes bakes a curvature map beside a texture bake
+    # (bake_curvature_map on the baked mesh's atlas, the mesh's own curvature) and leaves it on the mesh as the plain attribute
+    # `curvature` (a tsr.curvature.CurvatureMap, no Mesh field).  None: nothing new is launched
+    curvature_map = None
     # "box" | "charts": the unwrapper _atlas makes when no unwrapper= is passed.  "box": sf3d.unwrap.BoxProjectionUnwrapper, as
     # before.  "charts": sf3d.unwrap.ChartUnwrapper -- charts that are connected pieces of surface, however many layers the
     # object has, shelf-packed.  Anything else is a ValueError before a launch.
@@ -1214,6 +1218,45 @@ class TSR(KernelEngine):
                                                              ("vertex_colors", "vertex_normals", "vertex_occlusion", "quads"), uvs=uv)
         return out, ThicknessMap(th_map, thin, valid, mask, rule=rule)
 
+    def bake_curvature_map(self, mesh: Mesh, source=None, resolution=None, curvature=True, cage=None, island_padding: float = 0.02,
+                           unwrapper=None):
+        """The curvature map a baker ships beside normal, AO and thickness: mean and Gaussian curvature in the low-poly mesh's
+        atlas -- grey is flat, white convex, black concave; what edge wear and dirt masks are made from.  `curvature`: True or
+        the number of rings in 0 .. 8 the integrated curvature is summed over (ops.curvature_rule).  source=None: the mesh's
+        own curvature, interpolated over its faces; cage must be None.  source=a Mesh (the mesh before simplify): the curvature
+        of THAT mesh, read where every texel lands on it (the snap of bake_occlusion_map; cage as there); a texel whose snap ray
+        hits nothing keeps the low mesh's value.  Needs a device, no weights.
+        Stages: ops.vertex_normals * WINDING_OUTWARD -> ops.bake_rasterize -> ops.bake_curvature (outward = WINDING_OUTWARD) ->
+        ops.dilate_fill with res // 150 rounds over the covered texels with finite values (what is still 0 afterwards was not
+        reached).
+        -> (mesh, CurvatureMap): the mesh as it came, with uvs; the map (tsr/curvature.py) with mean and gauss (padded), mask
+        and rule.  It is no Mesh field: the map has its own save()."""
+        from .curvature import CurvatureMap
+
+        rule = ops.curvature_rule(curvature)   # a ValueError before anything is launched
+        if self.device is None:
+            raise _lib.SculptError("TSR.bake_curvature_map: the model is on no device yet (to(device))")
+        if source is not None and not isinstance(source, Mesh):
+            raise ValueError("TSR.bake_curvature_map: source must be a Mesh or None, got %r" % (type(source).__name__,))
+        if source is None and cage is not None:
+            raise ValueError("TSR.bake_curvature_map: cage snaps the texels onto a source; without a source it must be None")
+        res = _atlas_resolution(resolution, mesh, "bake_curvature_map", ("texture", "normal_map", "occlusion_map"))
+        with torch.no_grad():
+            v, f, uv, rast = self._atlas(mesh, res, island_padding, unwrapper, keep_uvs=True)
+            normals = (self.WINDING_OUTWARD * ops.vertex_normals(v, f)).contiguous()
+            src = None if source is None else (_f32(source.vertices, self.device), torch.as_tensor(source.faces).to(self.device).contiguous())
+            mean, gauss, mask = ops.bake_curvature(v, f, normals, rast, curvature=rule, outward=self.WINDING_OUTWARD, source=src, cage=cage)
+            known = mask & torch.isfinite(mean) & torch.isfinite(gauss)
+            zero = torch.zeros_like(mean)
+            image = torch.stack([torch.where(known, mean, zero), torch.where(known, gauss, zero), known.to(mean.dtype)], -1)
+            spread = self._padded(image, known, res)     # the third channel is not 0 where a chart or the padding reaches
+            reached = spread[..., 2] != 0
+            mean_map = torch.where(mask, mean, torch.where(reached, spread[..., 0], zero)).contiguous()
+            gauss_map = torch.where(mask, gauss, torch.where(reached, spread[..., 1], zero)).contiguous()
+        out = mesh if mesh.uvs is not None else mesh._derive(mesh.vertices, mesh.faces,
+                                                             ("vertex_colors", "vertex_normals", "vertex_occlusion", "quads"), uvs=uv)
+        return out, CurvatureMap(mean_map, gauss_map, mask, rule=rule)
+
     def _projected(self, v_pos, t_pos_idx, planes, threshold, project, resolution):
         """ops.mesh_project with this model's field, at _iso_target's target and max_dist (the geometry chain of extract_meshes
         comes here with its checks made: no _iso_search)."""
@@ -1345,6 +1388,8 @@ class TSR(KernelEngine):
                 raise ValueError("displacement_map needs a positive threshold (the surface is ln(threshold) in the raw density), got %r" % (threshold,))
         if self.thickness_map is not None:
             ops.thickness_rule(self.thickness_map)
+        if self.curvature_map is not None:
+            ops.curvature_rule(self.curvature_map)
         if self.bake_project is not None:
             ops.project_rule(self.bake_project)
             if not threshold > 0:
@@ -1483,6 +1528,8 @@ class TSR(KernelEngine):
                                                                  resolution=R)
         if enable_texture and bake > 0 and self.thickness_map is not None:   # the texture's atlas and resolution
             mesh, mesh.thickness = self.bake_thickness_map(mesh, thickness=self.thickness_map)
+        if enable_texture and bake > 0 and self.curvature_map is not None:   # the texture's atlas and resolution
+            mesh, mesh.curvature = self.bake_curvature_map(mesh, curvature=self.curvature_map)
         if normals == "field":
             mesh.vertex_normals = self.field_normals(v_pos, planes)
         elif normals == "faces":
